@@ -541,6 +541,34 @@ def compact(res):
     return out
 
 
+DUMP_LIMIT = 64 << 20      # bytes: --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: every array a caller of the timed path received from its last step, as DIR/<name>.npy in float32.  An array
+    larger than what is left of the budget is cut to a fixed, seeded sample of its batch rows (the same rows whenever the arguments are
+    the same); their indices go next to it as DIR/<name>_rows.npy (float64).  Returns {name: shape written}."""
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_LIMIT - 4096           # (room for the .npy headers)
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > left:
+            k = min(a.shape[0], left // (a[0].nbytes + 8))
+            if k < 1:
+                raise SystemExit(f"--dump-outputs: one row of {name} ({a[0].nbytes} bytes) exceeds what is left of the {DUMP_LIMIT}-byte budget")
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=k, replace=False))
+            np.save(os.path.join(path, f"{name}_rows.npy"), rows.astype(np.float64))
+            left -= rows.size * 8
+            a = np.ascontiguousarray(a[rows])
+        elif os.path.exists(os.path.join(path, f"{name}_rows.npy")):
+            os.remove(os.path.join(path, f"{name}_rows.npy"))          # (left by an earlier, larger run into the same DIR)
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        left -= a.nbytes
+        written[name] = list(a.shape)
+    return written
+
+
 def emit(res):
     """Full record -> gpurun_out/bench_full.json (+ stderr); compact record -> the last (and only) stdout line."""
     full_dir = os.path.join(ROOT, "gpurun_out")
@@ -581,7 +609,12 @@ def main():
                     help="process-group backend for N>1 (nccl == RCCL over xGMI; gloo only for single-GPU smoke tests)")
     ap.add_argument("--all-on-device0", action="store_true",
                     help="testing aid: every rank uses cuda:0 (exercises the N>1 code path on a 1-GPU box; use with --backend gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the mels the timed path returned in its last step as DIR/mel.npy (float32, "
+                         f"<= {DUMP_LIMIT >> 20} MB: a seeded sample of the utterances if the batch is larger); inputs are fixed by the arguments")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -642,6 +675,10 @@ def main():
         assert out.shape[0] == len(lengths)
     valid_total = sum(lengths)
     assert torch.isfinite(out).all()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # out: the [global batch, 80, T] mels of the last timed call, in the order of `lengths` (what the caller of the path receives)
+        dumped = dump_outputs(args.dump_outputs, {"mel": out.float().cpu().numpy()})
 
     if rank == 0:
         dtype = DTYPE_KEY[precision]
@@ -664,6 +701,8 @@ def main():
             "hip_event_min_ms": round(min(ev_ms), 3),
             "_precision": precision, "_workload": args.workload,
         }
+        if dumped is not None:
+            res["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         prof = world == 1 and not args.no_profile
         call_eager = lambda: eng.sample(z, mask, mu, n_steps, use_graph=False, **kw)
         y_oracle = None

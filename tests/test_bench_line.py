@@ -52,6 +52,25 @@ def test_compact_line_survives_a_bloated_record():
     assert "roofline" in back and "cpu_baseline" in back and back["value"] == full["value"]
 
 
+def test_dump_outputs_stays_in_budget_and_samples_the_same_rows(tmp_path):
+    """--dump-outputs: float32 files; a batch over the budget is cut to the same seeded rows on every run, their indices stored beside it"""
+    import numpy as np
+    b = _bench()
+    b.DUMP_LIMIT = 1 << 20
+    small = np.arange(2 * 80 * 16, dtype=np.float64).reshape(2, 80, 16)
+    assert b.dump_outputs(str(tmp_path / "s"), {"mel": small}) == {"mel": [2, 80, 16]}
+    got = np.load(tmp_path / "s" / "mel.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.astype(np.float32))
+    big = np.random.default_rng(3).standard_normal((64, 80, 256)).astype(np.float32)       # 5.2 MB
+    shapes = [b.dump_outputs(str(tmp_path / d), {"mel": big}) for d in ("a", "b")]
+    assert shapes[0] == shapes[1] and shapes[0]["mel"][0] < 64
+    for d in ("a", "b"):
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= b.DUMP_LIMIT
+    rows = np.load(tmp_path / "a" / "mel_rows.npy")
+    assert rows.dtype == np.float64 and np.array_equal(rows, np.load(tmp_path / "b" / "mel_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "mel.npy"), big[rows.astype(np.int64)])
+
+
 def test_bench_has_no_unresolved_global_names():
     """bench.py's GPU-only branches never run in the CPU suite: a name that resolves nowhere (round 6: `np` in job_abs_err) would only
     surface in the driver's run.  Every implicitly-global name referenced inside any function of bench.py must be defined at module

@@ -43,6 +43,7 @@ def test_manifest_matches_param_shapes(golden_dir, name):
 
 @pytest.mark.parametrize("name", list(CASES))
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+@pytest.mark.usefixtures("golden_threads")
 def test_precond_and_taps(golden_dir, name, dtype):
     g = load(golden_dir, name)
     cfg = CASES[name]()

@@ -43,6 +43,7 @@ def module_path(tap, cfg):
 
 
 @pytest.mark.parametrize("name", list(CASES))
+@pytest.mark.usefixtures("golden_threads")
 def test_every_module_of_the_score_network_against_the_reference(name):
     mk, dex_dims = CASES[name]
     cfg = mk()

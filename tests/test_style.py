@@ -31,6 +31,7 @@ def _case(B=2, T=40, lengths=(40, 27)):
     return torch.from_numpy(mel), torch.from_numpy(lf0), torch.from_numpy(L)
 
 
+@pytest.mark.usefixtures("golden_threads")
 def test_oracle_matches_reference_golden():
     g = dict(np.load(os.path.join(GOLD, "style.npz")))
     W = {k: torch.from_numpy(v) for k, v in weights().items()}

@@ -58,6 +58,7 @@ def test_param_shapes_match_reference_state_dict(name):
 
 
 @pytest.mark.parametrize("name", CASES)
+@pytest.mark.usefixtures("golden_threads")
 def test_oracle_matches_reference_golden(name):
     g = dict(np.load(os.path.join(GOLD, f"text_{name}.npz")))
     W = {k: torch.from_numpy(v) for k, v in weights(name).items()}
