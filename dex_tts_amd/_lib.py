@@ -76,6 +76,11 @@ class DexAlignArgs(C.Structure):
                 ("attn_out_dev", C.c_void_p), ("workspace_dev", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+class DexF0Opts(C.Structure):
+    _fields_ = [("fs", C.c_double), ("frame_period_ms", C.c_double), ("f0_floor", C.c_double), ("f0_ceil", C.c_double),
+                ("channels_in_octave", C.c_double), ("allowed_range", C.c_double)]
+
+
 class DexDenoiseArgs(C.Structure):
     _fields_ = [("s", DexSampleArgs), ("x_dev", C.c_void_p)]
 
@@ -148,6 +153,13 @@ SYMBOLS = [
     ("dex_mel_workspace_bytes", C.c_size_t, [C.c_int, C.c_int]),
     ("dex_mel_spectrogram", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("dex_lf0_normalize", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("dex_f0_frames", C.c_int, [C.c_int, C.POINTER(DexF0Opts)]),
+    ("dex_f0_workspace_bytes", C.c_size_t, [C.c_int, C.POINTER(C.c_int32), C.POINTER(DexF0Opts)]),
+    ("dex_f0_peak_normalize", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("dex_f0_dio", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(DexF0Opts), C.c_void_p, C.c_void_p,
+                             C.c_size_t, C.c_void_p]),
+    ("dex_f0_stonemask", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(DexF0Opts), C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_size_t, C.c_void_p]),
 ]
 
 _lib = None

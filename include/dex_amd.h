@@ -194,11 +194,32 @@ size_t dex_mel_workspace_bytes(int B, int n_samples);
 int  dex_mel_spectrogram(DexMel* mel, const float* wav_dev, int B, int n_samples, float* mel_dev, float* energy_dev,
                          void* workspace_dev, size_t workspace_bytes, dex_stream_t stream);
 
-/* Deterministic tail of the DEX f0 front-end (DEX-TTS/synthesize.py:26-38,55-58): f0 [B,T] in Hz (0 = unvoiced; from the
- * host's DIO/StoneMask, a third-party CPU algorithm that stays on the host) -> lf0 [B,T] = normalize_lf0(log f0), what
+/* Deterministic tail of the DEX f0 front-end (DEX-TTS/synthesize.py:26-38,55-58): f0 [B,T] in Hz (0 = unvoiced; from
+ * dex_f0_dio + dex_f0_stonemask below, or from any other tracker) -> lf0 [B,T] = normalize_lf0(log f0), what
  * dex_style_encode takes as lf0_dev.  lengths_dev [B] int32 or NULL (= T); positions past an utterance's length are 0.
  * T <= 16382 frames (190 s of audio at hop 256): DEX_ERR_ARG beyond. */
 int  dex_lf0_normalize(const float* f0_dev, const int* lengths_dev, int B, int T, float* lf0_dev, dex_stream_t stream);
+
+/* ---- f0 tracker (DEX-TTS/synthesize.py:46-52): WORLD's DIO + StoneMask (M. Morise) on the device, for a ragged batch.  The
+ * contract is the docstring of tests/world_f0.py; parity with pyworld itself is NOT measured (pyworld is not available to this
+ * project): the kernels are held to that float64 restatement and to signals whose f0 is known analytically.  speed = 1 only (no
+ * decimation).  All arithmetic fp64 in a fixed order: a row's result is bitwise reproducible and independent of its batch.
+ * wav_dev [B, n_samples] fp32 (promoted to fp64 exactly); row b holds lengths_host[b] samples (a HOST array, each in
+ * [1, n_samples]).  Frame i lies at t = i * frame_period_ms / 1000; row b has F(lengths_host[b]) frames, F(L) =
+ * int(1000 L / fs / frame_period_ms) + 1.  Bad arguments return DEX_ERR_ARG before anything is enqueued. */
+typedef struct { double fs, frame_period_ms, f0_floor, f0_ceil, channels_in_octave, allowed_range; } DexF0Opts;  /* NULL = DEX's: 22050, 256/22050*1000, 71, 800, 2, 0.1 */
+int    dex_f0_frames(int n_samples, const DexF0Opts* opts);          /* host only: F of the contract; DEX_ERR_ARG for bad options */
+size_t dex_f0_workspace_bytes(int B, const int* lengths_host, const DexF0Opts* opts);   /* for dex_f0_dio; 0 for bad arguments */
+/* synthesize.py:46: out [B, n_samples] = float(x / max|x|) per row, computed in fp64 (0 past a row's length, and for a silent row). */
+int    dex_f0_peak_normalize(const float* wav_dev, const int* lengths_host, int B, int n_samples, float* out_dev, dex_stream_t s);
+/* pw.dio(x, fs, f0_floor, f0_ceil, channels_in_octave, frame_period, speed = 1, allowed_range) -> f0_dev [B, F(n_samples)] fp64,
+ * 0 past each row's F.  The workspace holds the per-row filter outputs and events (about (2 + 3 nb) max(L) doubles per row, nb = 7 bands by default). */
+int    dex_f0_dio(const float* wav_dev, const int* lengths_host, int B, int n_samples, const DexF0Opts* opts,
+                  double* f0_dev /* [B, F(n_samples)], 0 past each utterance's F */, void* ws, size_t ws_bytes, dex_stream_t s);
+/* pw.stonemask(x, f0, t, fs) with t the frame times above: f0_in_dev / f0_out_dev [B, F(n_samples)] fp64 (distinct buffers).
+ * Needs no workspace (ws may be NULL). */
+int    dex_f0_stonemask(const float* wav_dev, const int* lengths_host, int B, int n_samples, const DexF0Opts* opts,
+                        const double* f0_in_dev, double* f0_out_dev, void* ws, size_t ws_bytes, dex_stream_t s);
 
 /* ---- Vocoder: HiFi-GAN generator (GeDEX-TTS/hifigan/models.py:112-173, built by src/utils.py:251-281 from
  * hifigan/config.json) — the step right after the sampler: mel [B,80,T] -> waveform [B, T * prod(upsample_rates)].
