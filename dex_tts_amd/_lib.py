@@ -81,6 +81,17 @@ class DexF0Opts(C.Structure):
                 ("channels_in_octave", C.c_double), ("allowed_range", C.c_double)]
 
 
+class DexWavTrimOpts(C.Structure):
+    _fields_ = [("top_db", C.c_double), ("frame_length", C.c_int32), ("hop_length", C.c_int32), ("pad_mode", C.c_int32)]
+
+
+class DexWavResampleOpts(C.Structure):
+    _fields_ = [("num_zeros", C.c_int32), ("precision", C.c_int32), ("beta", C.c_double), ("rolloff", C.c_double)]
+
+
+WAV_PAD = {"constant": 0, "reflect": 1}
+
+
 class DexDenoiseArgs(C.Structure):
     _fields_ = [("s", DexSampleArgs), ("x_dev", C.c_void_p)]
 
@@ -160,6 +171,17 @@ SYMBOLS = [
                              C.c_size_t, C.c_void_p]),
     ("dex_f0_stonemask", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(DexF0Opts), C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("dex_wav_trim_workspace_bytes", C.c_size_t, [C.c_int, C.POINTER(C.c_int32), C.POINTER(DexWavTrimOpts)]),
+    ("dex_wav_trim", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(DexWavTrimOpts), C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("dex_wav_resampled_length", C.c_int, [C.c_int, C.c_int, C.c_int]),
+    ("dex_wav_resample_table_bytes", C.c_size_t, [C.POINTER(DexWavResampleOpts)]),
+    ("dex_wav_resample_table", C.c_int, [C.POINTER(DexWavResampleOpts), C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("dex_wav_resample", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                   C.POINTER(DexWavResampleOpts), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("dex_wav_peak_workspace_bytes", C.c_size_t, [C.c_int, C.c_int]),
+    ("dex_wav_peak_normalize_f64", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                             C.c_void_p]),
 ]
 
 _lib = None

@@ -129,16 +129,22 @@ def reference_features(wav, lengths=None, sr=SR, stft: TacotronSTFT = None):
     """synthesize.py:41-60 (preprocess_wav) after the trim and the resampler, which stay the caller's: wav [L] or [B, L] (a CUDA
     tensor, trimmed, at 22050 Hz; rows of ``lengths`` samples) -> the dict DeXTTS.forward / synthesize_tokens(style=...) take:
     ref / sty [B, 80, Tr] (the mel of the peak-normalised wav), ref_lengths / sty_lengths [B] (L // 256 + 1), lf0 [B, Tl]
-    (normalize_lf0(log f0[:tlen]) with tlen = min(F, mel frames)) and lf0_lengths [B]; lengths are int64 on the device."""
+    (normalize_lf0(log f0[:tlen]) with tlen = min(F, mel frames)) and lf0_lengths [B]; lengths are int64 on the device.
+    dex_tts_amd.wavprep.preprocess_wav does the trim and the resampler too."""
     if sr != SR:
         raise ValueError(f"reference_features needs {SR} Hz audio (there is no resampler), got {sr}")
     x, ln, _ = _rows(wav, lengths)
-    B, L = x.shape
-    dev = x.device
+    return _features(peak_normalize(x, ln), ln, stft)
+
+
+def _features(xn, ln, stft: TacotronSTFT = None):
+    """The mel / f0 / lf0 tail of preprocess_wav (synthesize.py:47-60) on peak-normalised fp32 rows xn [B, L] (a CUDA tensor) of host
+    int32 lengths ln -> the dict reference_features returns."""
+    B, L = xn.shape
+    dev = xn.device
     stft = stft if stft is not None else _stft(dev)
     lib = _lib.load()
     fp = HOP / SR * 1000.0
-    xn = peak_normalize(x, ln)
     f0, t = dio(xn, SR, frame_period=fp, lengths=ln)
     f0 = stonemask(xn, f0, t, SR, lengths=ln, frame_period=fp)
     mel_frames = [lib.dex_mel_frames(int(n)) for n in ln]

@@ -221,6 +221,43 @@ int    dex_f0_dio(const float* wav_dev, const int* lengths_host, int B, int n_sa
 int    dex_f0_stonemask(const float* wav_dev, const int* lengths_host, int B, int n_samples, const DexF0Opts* opts,
                         const double* f0_in_dev, double* f0_out_dev, void* ws, size_t ws_bytes, dex_stream_t s);
 
+/* ---- Reference wav preparation (DEX-TTS/synthesize.py:40-47, ahead of the f0 tracker): librosa.effects.trim(top_db = 30),
+ * resampy.resample(kaiser_best) to 22050 Hz and the fp64 peak normalisation, for a ragged, mixed-rate batch.  The contract is the
+ * docstring of tests/wav_prep.py; parity with librosa 0.9.2 and resampy themselves is NOT measured (neither is available to this
+ * project).  fp64 throughout, every reduction in a fixed order: a row's result is bitwise reproducible and independent of its batch.
+ * Row lengths, offsets and rates are HOST arrays; bad arguments return DEX_ERR_ARG before anything is enqueued. */
+enum { DEX_WAV_PAD_CONSTANT = 0, DEX_WAV_PAD_REFLECT = 1 };
+typedef struct {
+    double top_db;                    /* 30: a frame is non-silent iff 10 log10(mse / max mse) > -top_db (both floored at 1e-10) */
+    int32_t frame_length, hop_length; /* 2048, 512; frame_length must be a multiple of hop_length */
+    int32_t pad_mode;                 /* DEX_WAV_PAD_CONSTANT (zeros) or DEX_WAV_PAD_REFLECT (numpy "reflect"), frame_length / 2 each side */
+} DexWavTrimOpts;                     /* NULL = 30, 2048, 512, constant */
+typedef struct {
+    int32_t num_zeros, precision;     /* 64, 9: the table has 2^precision * num_zeros + 1 entries */
+    double beta, rolloff;             /* kaiser window beta 14.769656459379492, rolloff 0.9475937167399596 */
+} DexWavResampleOpts;                 /* NULL = resampy's kaiser_best */
+/* wav_dev [B, n_samples] fp32 (promoted exactly) -> bounds_dev [B, 2] int32 (start, end) of the non-silent part of each row; optional
+ * frame_mse_dev [B, 1 + n_samples / hop_length] fp64 (NULL: not written): each frame's mean square, 0 past a row's 1 + L / hop frames. */
+size_t dex_wav_trim_workspace_bytes(int B, const int* lengths_host, const DexWavTrimOpts* opts);   /* 0 for bad arguments */
+int    dex_wav_trim(const float* wav_dev, const int* lengths_host, int B, int n_samples, const DexWavTrimOpts* opts, int32_t* bounds_dev,
+                    double* frame_mse_dev, void* ws, size_t ws_bytes, dex_stream_t s);
+/* host only: (n_samples * sr_new) div sr_orig, DEX_ERR_ARG if a rate is <= 0, n_samples < 1, or the result is < 1 or above INT32_MAX */
+int    dex_wav_resampled_length(int n_samples, int sr_orig, int sr_new);
+/* The window table (2^precision * num_zeros + 1 pairs of doubles, 16-byte aligned): built once on the device by dex_wav_resample_table,
+ * then read by every dex_wav_resample call made with the same options. */
+size_t dex_wav_resample_table_bytes(const DexWavResampleOpts* opts);                             /* 0 for bad options */
+int    dex_wav_resample_table(const DexWavResampleOpts* opts, void* table_dev, size_t table_bytes, dex_stream_t s);
+/* Row b reads wav_dev[b * in_stride + offsets_host[b] ...] for lengths_host[b] samples at sr_orig_host[b] Hz and writes
+ * dex_wav_resampled_length(...) fp64 samples at sr_new to out_dev[b * out_stride ...], 0 up to out_stride.  A row already at sr_new
+ * is copied.  sr_new / sr_orig must be >= 1 / 2^precision. */
+int    dex_wav_resample(const float* wav_dev, int in_stride, const int* offsets_host, const int* lengths_host, const int* sr_orig_host,
+                        int B, int sr_new, const DexWavResampleOpts* opts, double* out_dev, int out_stride, const void* table_dev,
+                        size_t table_bytes, dex_stream_t s);
+/* synthesize.py:46 on fp64 rows: out [B, n_samples] fp32 = float(x / max|x|) per row (0 past a row's length and for a silent row). */
+size_t dex_wav_peak_workspace_bytes(int B, int n_samples);                                        /* 0 for bad arguments */
+int    dex_wav_peak_normalize_f64(const double* x_dev, const int* lengths_host, int B, int n_samples, float* out_dev, void* ws,
+                                  size_t ws_bytes, dex_stream_t s);
+
 /* ---- Vocoder: HiFi-GAN generator (GeDEX-TTS/hifigan/models.py:112-173, built by src/utils.py:251-281 from
  * hifigan/config.json) — the step right after the sampler: mel [B,80,T] -> waveform [B, T * prod(upsample_rates)].
  * A separate context: it shares nothing with the score network. */
