@@ -182,6 +182,13 @@ SYMBOLS = [
     ("dex_wav_peak_workspace_bytes", C.c_size_t, [C.c_int, C.c_int]),
     ("dex_wav_peak_normalize_f64", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                              C.c_void_p]),
+    ("dex_mas_log_prior", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("dex_mas_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    ("dex_mas_durations", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("dex_mas_loss_workspace_bytes", C.c_size_t, [C.c_int]),
+    ("dex_mas_losses", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                 C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 ]
 
 _lib = None

@@ -386,6 +386,30 @@ size_t dex_text_workspace_bytes(const DexText* txt, int B, int T);
 int  dex_text_encode(DexText* txt, const DexTextArgs* args, dex_stream_t stream);
 int  dex_text_align(DexText* txt, const DexAlignArgs* args, dex_stream_t stream);
 
+/* ---- Monotonic alignment search (Glow-TTS MAS) and the validation losses around it: the log-prior of compute_loss (GeDEX-TTS/model/
+ * tts.py:75-80, DEX :99-106), model.monotonic_align.maximum_path with the reference's exact fp32 semantics (value * mask, the -1e9
+ * sentinel, strict comparison in the backtrack) and the duration / prior loss reductions (tts.py:112-113, :148-149).  Lengths are HOST
+ * arrays; every bad argument, a row with t_y < t_x among them, is refused before anything is enqueued.  The result of a row does not
+ * depend on the other rows of its batch. */
+#define DEX_MAS_MAX_TX 2048
+#define DEX_MAS_MAX_TY 8192
+/* log_prior[b, y, x] ([B,Ty,Tx], frame-major: the layout the search reads) from mu_x [B,n_feats,Tx] and y [B,n_feats,Ty]; n_feats <= 128. */
+int    dex_mas_log_prior(const float* mu_x_dev, const float* y_dev, int B, int n_feats, int Tx, int Ty, float* log_prior_dev, dex_stream_t s);
+size_t dex_mas_workspace_bytes(int B, int Tx, int Ty);   /* 0 for bad arguments */
+/* value[b, x, y] at value_dev + b stride_b + x stride_x + y stride_y (element strides; mask_dev, optional, has the same strides and
+ * multiplies value first).  Row b searches the t_x = x_lengths_host[b] by t_y = y_lengths_host[b] corner, 1 <= t_x <= t_y.
+ * dur_dev [B,Tx] int32: frames per token (0 past t_x).  path_dev: optional dense [B,Tx,Ty] 0/1 path. */
+int    dex_mas_durations(const float* value_dev, const float* mask_dev, int B, int Tx, int Ty, int64_t stride_b, int64_t stride_x,
+                         int64_t stride_y, const int* x_lengths_host, const int* y_lengths_host, int32_t* dur_dev, float* path_dev,
+                         void* workspace_dev, size_t workspace_bytes, dex_stream_t s);
+size_t dex_mas_loss_workspace_bytes(int B);              /* 0 for bad arguments */
+/* out_dev[0] = dur_loss = sum (logw - log(1e-8 + dur) x_mask)^2 / sum x_lengths, logw / dur [B,Tx];
+ * out_dev[1] = prior_loss = sum 0.5 ((y - mu_y)^2 + log 2 pi) y_mask / (sum y_mask n_feats), y / mu_y [B,n_feats,Ty].
+ * Per-utterance partial sums in a fixed order, then one combine on the device: nothing is read back. */
+int    dex_mas_losses(const float* logw_dev, const int32_t* dur_dev, const int* x_lengths_host, int B, int Tx, const float* y_dev,
+                      const float* mu_y_dev, const int* y_lengths_host, int n_feats, int Ty, float* out_dev, void* workspace_dev,
+                      size_t workspace_bytes, dex_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
