@@ -141,6 +141,8 @@ SYMBOLS = [
     ("dex_style_finalize", C.c_int, [C.c_void_p, C.c_void_p]),
     ("dex_style_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("dex_style_encode", C.c_int, [C.c_void_p, C.POINTER(DexStyleArgs), C.c_void_p]),
+    ("dex_style_loss_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("dex_style_encode_loss", C.c_int, [C.c_void_p, C.POINTER(DexStyleArgs), C.c_float, C.c_void_p, C.c_void_p]),
     ("dex_text_create", C.c_int, [C.POINTER(DexTextConfig), C.POINTER(C.c_void_p)]),
     ("dex_text_destroy", None, [C.c_void_p]),
     ("dex_text_last_error", C.c_char_p, [C.c_void_p]),
@@ -189,6 +191,8 @@ SYMBOLS = [
     ("dex_mas_loss_workspace_bytes", C.c_size_t, [C.c_int]),
     ("dex_mas_losses", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                  C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("dex_loss_segment", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 ]
 
 _lib = None

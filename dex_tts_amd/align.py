@@ -7,10 +7,12 @@ path: CPU tensors and tensors that require grad are refused with RuntimeError.
     from dex_tts_amd.align import maximum_path        # drop-in for model.monotonic_align.maximum_path
     attn = maximum_path(log_prior, attn_mask.squeeze(1))
     dur = mas_durations(mu_x, x_lengths, y, y_lengths)  # [B, Tx] int32 frames per token (forced alignment)
+    y_cut, mu_y_cut, y_cut_mask, cut_lengths = segment(mu_x, dur, y, y_lengths, out_size=172)   # the random out_size cut
 """
 from __future__ import annotations
 
 import ctypes as C
+import random
 
 import numpy as np
 import torch
@@ -146,3 +148,49 @@ def dur_prior_losses(logw: torch.Tensor, dur: torch.Tensor, x_lengths, y: torch.
         _check(lib.dex_mas_losses(lw.data_ptr(), d.data_ptr(), _ptr(tx), B, Tx, yy.data_ptr(), mm.data_ptr(), _ptr(ty), F, Ty,
                                   out.data_ptr(), ws.data_ptr(), need, _stream(dev)), "dex_mas_losses")
     return out[0], out[1]
+
+
+def segment_offsets(y_lengths, out_size: int) -> np.ndarray:
+    """The per-row cut offsets of compute_loss (tts.py:119-124), drawn from Python's ``random`` exactly as the reference draws them:
+    ``random.choice(range(0, max_offset))`` for a row with max_offset = y_len - out_size > 0, else 0 without a draw.  After
+    ``random.seed(s)`` this returns the reference's offsets and leaves ``random`` in the reference's state.  -> int64 [B]."""
+    yl = np.asarray(torch.as_tensor(y_lengths).detach().cpu(), dtype=np.int64).reshape(-1)
+    return np.array([random.choice(range(0, m)) if m > 0 else 0 for m in (max(int(l) - int(out_size), 0) for l in yl)], dtype=np.int64)
+
+
+@torch.no_grad()
+def segment(mu_x: torch.Tensor, dur: torch.Tensor, y: torch.Tensor, y_lengths, out_size=None, offsets=None):
+    """The out_size cut of compute_loss and mu_y = attn^T mu_x on it (tts.py:115-144), without the [B, Tx, Ty] path:
+
+        mu_x [B, F, Tx], dur [B, Tx] int32 (mas_durations), y [B, F, Ty] + lengths
+        -> y_cut [B, F, S], mu_y_cut [B, F, S], y_cut_mask [B, 1, S] fp32 on the device, cut_lengths int64 [B] on the host
+
+    S = out_size when out_size < Ty (a cut), else Ty.  Row b keeps frames [off_b, off_b + cut_b), cut_b = min(S, y_len_b); past
+    cut_b every output is 0.  ``offsets`` (host, [B]) default to ``segment_offsets(y_lengths, out_size)`` for a cut and to 0
+    otherwise.  mu_y_cut is bitwise the reference's 0/1 matmul."""
+    dev = _dev(mu_x, dur, y)
+    lib = _lib.load()
+    if mu_x.dim() != 3 or y.dim() != 3 or mu_x.shape[:2] != y.shape[:2] or tuple(dur.shape) != (mu_x.shape[0], mu_x.shape[2]):
+        raise ValueError("mu_x must be [B, F, Tx], dur [B, Tx] and y [B, F, Ty]")
+    B, F, Tx = mu_x.shape
+    Ty = y.shape[2]
+    yl = _lens(y_lengths, B)
+    cut = out_size is not None and int(out_size) < Ty
+    S = int(out_size) if cut else Ty
+    if S < 1:
+        raise ValueError(f"out_size must be >= 1, got {out_size}")
+    if offsets is None:
+        offsets = segment_offsets(yl, S) if cut else np.zeros(B, np.int64)
+    off = np.asarray(torch.as_tensor(offsets).detach().cpu(), dtype=np.int64).reshape(-1)
+    cl = np.minimum(yl.astype(np.int64), S)
+    if off.shape != (B,) or (off < 0).any() or (off > yl - cl).any():
+        raise ValueError(f"offsets must hold B = {B} values with 0 <= offset <= y_length - min(S, y_length)")
+    off32 = np.ascontiguousarray(off.astype(np.int32))
+    with torch.cuda.device(dev):
+        m, yy, d = mu_x.to(torch.float32).contiguous(), y.to(torch.float32).contiguous(), dur.to(torch.int32).contiguous()
+        y_cut = torch.empty(B, F, S, dtype=torch.float32, device=dev)
+        mu_cut = torch.empty(B, F, S, dtype=torch.float32, device=dev)
+        mask = torch.empty(B, 1, S, dtype=torch.float32, device=dev)
+        _check(lib.dex_loss_segment(m.data_ptr(), d.data_ptr(), yy.data_ptr(), B, F, Tx, Ty, _ptr(yl), _ptr(off32), S, y_cut.data_ptr(),
+                                    mu_cut.data_ptr(), mask.data_ptr(), _stream(dev)), "dex_loss_segment")
+    return y_cut, mu_cut, mask, torch.from_numpy(cl)

@@ -7,6 +7,7 @@
 // the masked means, the VQ lookup and the GRU recurrence are the small kernels of style_elem.hip.  One call = ~70 launches
 // over a few hundred frames: once per reference utterance, ahead of 50-100 sampler steps.
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <map>
@@ -248,6 +249,7 @@ int dex_style_finalize(DexStyle* v, dex_stream_t stream) {
 
 namespace {
 struct SPlan { float *mr, *ms, *ml, *mel, *lf, *x, *a, *y, *z, *dots, *gi, *mean_a, *mean_b, *mean_c; size_t bytes; };
+size_t vq_part_bytes(int B, int Ts) { return ((size_t)B * Ts * sizeof(double) + 255) & ~size_t(255); }
 void style_plan(const DexStyle* v, int B, int Tr, int Ts, int Tl, void* ws, SPlan& P) {
     const DexStyleConfig& c = v->cfg;
     const int Tm = std::max(Tr, std::max(Ts, Tl));
@@ -301,7 +303,12 @@ size_t dex_style_workspace_bytes(const DexStyle* v, int B, int Tr, int Ts, int T
     return P.bytes;
 }
 
-int dex_style_encode(DexStyle* v, const DexStyleArgs* a, dex_stream_t stream) {
+}  // extern "C"
+
+namespace {
+// dex_style_encode, and with vq_loss_out: the VQ commitment loss into vq_loss_out (its per-row partials in the workspace past the
+// encoder's own plan), formed from the lookup's input and output before anything overwrites them.  Nothing else changes.
+int style_encode(DexStyle* v, const DexStyleArgs* a, dex_stream_t stream, float commit_w, float* vq_loss_out) {
     if (!v || !a) return DEX_ERR_ARG;
     if (!v->finalized) return v->fail(DEX_ERR_STATE, "dex_style_finalize has not been called");
     const DexStyleConfig& c = v->cfg;
@@ -312,7 +319,8 @@ int dex_style_encode(DexStyle* v, const DexStyleArgs* a, dex_stream_t stream) {
     for (int i = 0; i < c.tiv_layers; ++i) if (!a->ref_skips_out_dev[i]) return v->fail(DEX_ERR_ARG, "ref_skips_out_dev[%d] is null", i);
     if (((uintptr_t)a->workspace_dev & 255) != 0) return v->fail(DEX_ERR_ARG, "workspace must be 256-byte aligned");
     SPlan P; style_plan(v, a->B, a->Tr, a->Ts, a->Tl, nullptr, P);
-    if (P.bytes > a->workspace_bytes) return v->fail(DEX_ERR_WORKSPACE, "style workspace too small: need %zu bytes, got %zu", P.bytes, a->workspace_bytes);
+    const size_t need = P.bytes + (vq_loss_out ? vq_part_bytes(a->B, a->Ts) : 0);
+    if (need > a->workspace_bytes) return v->fail(DEX_ERR_WORKSPACE, "style workspace too small: need %zu bytes, got %zu", need, a->workspace_bytes);
     style_plan(v, a->B, a->Tr, a->Ts, a->Tl, a->workspace_dev, P);
     hipStream_t st = (hipStream_t)stream;
     const int B = a->B, Tr = a->Tr, Ts = a->Ts, Tl = a->Tl;
@@ -368,6 +376,8 @@ int dex_style_encode(DexStyle* v, const DexStyleArgs* a, dex_stream_t stream) {
         launch_igemm(g, PREC_FP32, st);
         VqP q{P.a, P.dots, v->R("tv_encoder.vq.embedding"), v->e2, P.ms, P.z, a->vq_idx_out_dev, (long)B * Ts, c.tv_n_emb, c.tv_cout};
         launch_vq_lookup(q, st);
+        if (vq_loss_out)
+            launch_vq_loss(P.a, P.z, P.ms, (long)B * Ts, c.tv_cout, (double*)((char*)a->workspace_dev + P.bytes), commit_w, vq_loss_out, st);
     }
     // sty_enc = mean(z_beforeVQ) + mean(lf0_enc)   (tts.py:62)
     launch_add_bcast_cl(P.mean_c, P.mean_a, B, 1, c.tv_cout, st);
@@ -391,6 +401,23 @@ int dex_style_encode(DexStyle* v, const DexStyleArgs* a, dex_stream_t stream) {
     }
     SCHK(v, hipGetLastError());
     return DEX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int dex_style_encode(DexStyle* v, const DexStyleArgs* a, dex_stream_t stream) { return style_encode(v, a, stream, 0.f, nullptr); }
+
+size_t dex_style_loss_workspace_bytes(const DexStyle* v, int B, int Tr, int Ts, int Tl) {
+    const size_t base = dex_style_workspace_bytes(v, B, Tr, Ts, Tl);
+    return base ? base + vq_part_bytes(B, Ts) : 0;
+}
+
+int dex_style_encode_loss(DexStyle* v, const DexStyleArgs* a, float commit_w, float* vq_loss_out_dev, dex_stream_t stream) {
+    if (!v || !a) return DEX_ERR_ARG;
+    if (!vq_loss_out_dev) return v->fail(DEX_ERR_ARG, "vq_loss_out_dev is null");
+    if (!std::isfinite(commit_w)) return v->fail(DEX_ERR_ARG, "commit_w must be finite");
+    return style_encode(v, a, stream, commit_w, vq_loss_out_dev);
 }
 
 }  // extern "C"

@@ -487,6 +487,10 @@ struct VqP { const float* X; const float* dots; const float* emb; const float* e
              long rows; int M, D; };
 void launch_vq_lookup(const VqP& p, hipStream_t st);
 void launch_row_sumsq(const float* X, float* out, long rows, int D, hipStream_t st);
+// VQ commitment loss (ref_encoder.py:226, eval mode) from the lookup's input X [R][D] and output Q = e[idx] * mask [R][D]:
+// part [R] fp64 per-row sums (workspace), out[0] = commit_w * sum (X mask - Q)^2 / (sum mask * D), one rounding (loss.hip)
+void launch_vq_loss(const float* X, const float* Q, const float* mask, long rows, int D, double* part, float commit_w, float* out,
+                    hipStream_t st);
 // one direction of one bidirectional GRU layer per (direction, batch element) workgroup (nn.GRU, hidden H = 96):
 // gi [B][T][2][3H] = W_ih x + b_ih (precomputed), Whh [2][3H][H], bhh [2][3H]; out [B][T][2H] (forward | reverse)
 struct GruP { const float* gi; const float* Whh; const float* bhh; float* out; int B, T, H; };

@@ -168,8 +168,11 @@ class StyleEncoders(nn.Module):
 
     @torch.no_grad()
     def forward(self, ref: torch.Tensor, ref_lengths: torch.Tensor, sty: torch.Tensor, sty_lengths: torch.Tensor,
-                lf0: torch.Tensor, lf0_lengths: torch.Tensor, return_indices: bool = False):
-        """tts.py:55-67: ref [B,80,Tr] (or [B,1,80,Tr]), sty [B,80,Ts], lf0 [B,Tl] + lengths -> (ref_skips, sty_dec, sty_enc)."""
+                lf0: torch.Tensor, lf0_lengths: torch.Tensor, return_indices: bool = False, return_vq_loss: bool = False):
+        """tts.py:55-67: ref [B,80,Tr] (or [B,1,80,Tr]), sty [B,80,Ts], lf0 [B,Tl] + lengths -> (ref_skips, sty_dec, sty_enc).
+        return_indices appends the VQ codes [B,Ts] int32; return_vq_loss appends, last, the eval-mode VQ commitment loss of
+        compute_loss (ref_encoder.py:226, commit_w of the tv_encoder config) as a 0-d device tensor (dex_style_encode_loss: the
+        other outputs are bitwise those of dex_style_encode)."""
         dev = ref.device
         self._engine(dev)
         with torch.cuda.device(dev):
@@ -186,7 +189,8 @@ class StyleEncoders(nn.Module):
             sty_dec = torch.empty(B, self.cfg["dim"] * 2, Ts, dtype=torch.float32, device=dev)
             sty_enc = torch.empty(B, tv["c_out"], dtype=torch.float32, device=dev)
             idx = torch.empty(B, Ts, dtype=torch.int32, device=dev)
-            need = int(self._lib.dex_style_workspace_bytes(self._ctx, B, Tr, Ts, Tl))
+            wsq = self._lib.dex_style_loss_workspace_bytes if return_vq_loss else self._lib.dex_style_workspace_bytes
+            need = int(wsq(self._ctx, B, Tr, Ts, Tl))
             if self._ws is None or self._ws.numel() < need + 256 or self._ws.device != dev:
                 self._ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
             base = (self._ws.data_ptr() + 255) // 256 * 256
@@ -194,6 +198,12 @@ class StyleEncoders(nn.Module):
             a = _lib.DexStyleArgs(B, Tr, Ts, Tl, ref.data_ptr(), rl.data_ptr(), sty.data_ptr(), sl.data_ptr(), lf0.data_ptr(), ll.data_ptr(),
                                   C.cast(arr, C.POINTER(C.c_void_p)), sty_dec.data_ptr(), sty_enc.data_ptr(), idx.data_ptr(), base,
                                   self._ws.numel() - (base - self._ws.data_ptr()))
-            self._check(self._lib.dex_style_encode(self._ctx, C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            if return_vq_loss:
+                vq_loss = torch.empty((), dtype=torch.float32, device=dev)
+                self._check(self._lib.dex_style_encode_loss(self._ctx, C.byref(a), float(tv.get("commit_w", 0.25)), vq_loss.data_ptr(), st))
+            else:
+                self._check(self._lib.dex_style_encode(self._ctx, C.byref(a), st))
             self._keep = (ref, sty, lf0, rl, sl, ll, arr)
-            return (skips, sty_dec, sty_enc, idx) if return_indices else (skips, sty_dec, sty_enc)
+            out = (skips, sty_dec, sty_enc) + ((idx,) if return_indices else ())
+            return out + (vq_loss,) if return_vq_loss else out

@@ -336,6 +336,12 @@ int  dex_style_load_weight_async(DexStyle* sty, const char* key, const float* w_
 int  dex_style_finalize(DexStyle* sty, dex_stream_t stream);
 size_t dex_style_workspace_bytes(const DexStyle* sty, int B, int Tr, int Ts, int Tl);
 int  dex_style_encode(DexStyle* sty, const DexStyleArgs* args, dex_stream_t stream);
+/* dex_style_encode plus the eval-mode VQ commitment loss of VQEmbeddingEMA.forward (ref_encoder.py:226) as a 0-d fp32 on the
+ * device: vq_loss_out_dev[0] = commit_w * sum (x m - e[idx] m)^2 / (sum m * tv_cout), x = z_beforeVQ [B,Ts,tv_cout], m the sty mask.
+ * Every output of dex_style_encode is bitwise the same.  Per-row fp64 partials in a fixed order, one combine, no atomics: the
+ * same bits on every run.  The workspace must hold dex_style_loss_workspace_bytes. */
+size_t dex_style_loss_workspace_bytes(const DexStyle* sty, int B, int Tr, int Ts, int Tl);
+int  dex_style_encode_loss(DexStyle* sty, const DexStyleArgs* args, float commit_w, float* vq_loss_out_dev, dex_stream_t stream);
 
 /* ---- Text encoder + durations + alignment: TextEncoder.forward (GeDEX-TTS/model/text_encoder.py:129-146, DEX
  * :126-142: embedding, ConvReluNorm prenet, RetNet in its parallel form with use_softmax = True / use_decay = False — the only
@@ -409,6 +415,17 @@ size_t dex_mas_loss_workspace_bytes(int B);              /* 0 for bad arguments 
 int    dex_mas_losses(const float* logw_dev, const int32_t* dur_dev, const int* x_lengths_host, int B, int Tx, const float* y_dev,
                       const float* mu_y_dev, const int* y_lengths_host, int n_feats, int Ty, float* out_dev, void* workspace_dev,
                       size_t workspace_bytes, dex_stream_t s);
+
+/* ---- Segment expand + cut of compute_loss (tts.py:115-144): from mu_x [B,n_feats,Tx], the search's durations dur [B,Tx] int32
+ * and y [B,n_feats,Ty], for t < cut_b = min(S, y_lengths_host[b]):
+ *     y_cut[b, :, t] = y[b, :, off_b + t],  mu_y_cut[b, :, t] = mu_x[b, :, k] with sum(dur[b, :k]) <= off_b + t < sum(dur[b, :k+1]),
+ *     y_cut_mask[b, 0, t] = 1;   every output is 0 for t >= cut_b (and mu_y_cut where no token owns the frame).
+ * y_cut / mu_y_cut [B,n_feats,S], y_cut_mask [B,1,S].  S = out_size for a cut, Ty for none; offsets_host NULL = all 0; each
+ * 0 <= off_b <= y_lengths_host[b] - cut_b.  mu_y_cut is bitwise the reference's attn_cut^T mu_x.  Tx <= DEX_MAS_MAX_TX,
+ * Ty <= DEX_MAS_MAX_TY.  Bad arguments are refused before anything is enqueued; a row's result does not depend on its batch. */
+int    dex_loss_segment(const float* mu_x_dev, const int32_t* dur_dev, const float* y_dev, int B, int n_feats, int Tx, int Ty,
+                        const int* y_lengths_host, const int* offsets_host, int S, float* y_cut_dev, float* mu_y_cut_dev,
+                        float* y_cut_mask_dev, dex_stream_t s);
 
 #ifdef __cplusplus
 }
