@@ -13,6 +13,11 @@
 // BigVGAN (DEX-TTS/bigvgan/models.py:138-211; DexVocoderConfig::activation != 0) is the same network with AMPBlock1: the leaky_relu
 // in front of every ResBlock conv and of conv_post becomes the anti-aliased Snake / SnakeBeta activation (alias_free_torch/act.py;
 // one aa_snake launch into a scratch tensor), the transposed convs take x as it is.
+//
+// Narrow stages (vocoder_narrow.hip): a stage whose width is a multiple of 8, at most 64 and not a multiple of 32 (BigVGAN 22 kHz / 80
+// bands: 48 and 24; HiFi-GAN V2: 16 and 8) runs its ResBlock convs and the transposed conv into it on direct exact-fp32 kernels, and
+// its anti-aliased activations on the lane-packed aa_snake; those kernels stay fp32 in the bf16 / fp16 modes.  Every other width
+// takes the implicit GEMM as before.
 #include <hip/hip_runtime.h>
 #include <cstdarg>
 #include <cstdio>
@@ -28,8 +33,8 @@ using namespace dex;
 namespace {
 struct VRaw { float* p = nullptr; std::vector<int64_t> shape; long numel = 0; bool loaded = false; };
 // (wlp: the same matrix as bf16 [0] / fp16 [1], [N][K] with K contiguous - the reduced-precision GEMM's weight operand)
-struct VConv { const float* w = nullptr; const float* b = nullptr; int cin, cout, k, dil; const void* wlp[2] = {nullptr, nullptr}; };     // packed [k*cin][cout]
-struct VUp { const float* w = nullptr; const float* b = nullptr; int cin, cout, k, u, pad; const void* wlp[2] = {nullptr, nullptr}; };    // packed [cin][k*cout]
+struct VConv { const float* w = nullptr; const float* b = nullptr; int cin, cout, k, dil; const void* wlp[2] = {nullptr, nullptr}; bool narrow = false; };  // packed [k*cin][cout]
+struct VUp { const float* w = nullptr; const float* b = nullptr; int cin, cout, k, u, pad; const void* wlp[2] = {nullptr, nullptr}; bool narrow = false; };   // packed [cin][k*cout]
 constexpr int MEL_LD = 96;          // num_mels padded to a multiple of 32 (K tiles of the implicit GEMM do not straddle taps)
 }  // namespace
 
@@ -87,7 +92,9 @@ int dex_voc_create(const DexVocoderConfig* cfg, DexVoc** out) {
     for (int i = 0; i < c.n_upsamples; ++i) {
         const int k = c.upsample_kernel_sizes[i], u = c.upsample_rates[i], co = stage_ch(c, i);
         if (u < 1 || k < u || (k - u) % 2) return v->fail(DEX_ERR_ARG, "upsample %d: kernel %d / rate %d unsupported (needs k >= u, k - u even)", i, k, u);
-        if (co % 32 || co < 32) return v->fail(DEX_ERR_ARG, "stage %d has %d channels: the implicit GEMM needs multiples of 32", i, co);
+        if (voc_narrow_width(co)) continue;          // the narrow kernels take any k, u that passed above
+        if (co % 32 || co < 32)
+            return v->fail(DEX_ERR_ARG, "stage %d has %d channels: the implicit GEMM needs multiples of 32, the narrow kernels multiples of 8 up to 64", i, co);
         if ((k * co) % 64) return v->fail(DEX_ERR_ARG, "stage %d: k * channels must be a multiple of 64", i);
     }
     if (stage_ch(c, c.n_upsamples - 1) > 64) return v->fail(DEX_ERR_ARG, "conv_post kernel handles <= 64 input channels");
@@ -183,7 +190,7 @@ int dex_voc_finalize(DexVoc* v, dex_stream_t stream) {
     };
     // Conv1d [Cout][Cin][k] -> [(tap*Cin_pad + ci)][Cout]
     auto conv = [&](const std::string& name, int cin, int cout, int k, int dil, int cin_pad) {
-        VConv o{}; o.cin = cin_pad; o.cout = cout; o.k = k; o.dil = dil;
+        VConv o{}; o.cin = cin_pad; o.cout = cout; o.k = k; o.dil = dil; o.narrow = voc_narrow_width(cout);
         const float* src = v->raw.at(name + ".weight").p;
         if (cin_pad == cin) {
             float* d = alloc((long)k * cin * cout);
@@ -200,19 +207,19 @@ int dex_voc_finalize(DexVoc* v, dex_stream_t stream) {
             o.w = d;
         }
         o.b = v->raw.at(name + ".bias").p;
-        if (o.w) lp_copies(o.w, k * cin_pad, cout, o.wlp);
+        if (o.w && !o.narrow) lp_copies(o.w, k * cin_pad, cout, o.wlp);      // (the narrow kernels read fp32 weights in every mode)
         return o;
     };
     v->pre = conv("conv_pre", c.num_mels, c.upsample_initial_channel, 7, 1, MEL_LD);
     v->ups.clear(); v->rb.clear();
     for (int i = 0; i < c.n_upsamples; ++i) {
         const int ci = c.upsample_initial_channel >> i, co = stage_ch(c, i), k = c.upsample_kernel_sizes[i], u = c.upsample_rates[i];
-        VUp up{}; up.cin = ci; up.cout = co; up.k = k; up.u = u; up.pad = (k - u) / 2;
+        VUp up{}; up.cin = ci; up.cout = co; up.k = k; up.u = u; up.pad = (k - u) / 2; up.narrow = voc_narrow_width(co);
         float* d = alloc((long)ci * k * co);
         const std::string upn = "ups." + std::to_string(i) + (v->big() ? ".0" : "");
         if (d) launch_permute4(v->raw.at(upn + ".weight").p, d, ci, co, k, 1, 0, 2, 1, 3, st);   // [ci][co][k] -> [ci][k][co]
         up.w = d; up.b = v->raw.at(upn + ".bias").p;
-        if (d) lp_copies(d, ci, k * co, up.wlp);
+        if (d && !up.narrow) lp_copies(d, ci, k * co, up.wlp);
         v->ups.push_back(up);
         for (int j = 0; j < 3; ++j) {
             const std::string p = "resblocks." + std::to_string(i * 3 + j);
@@ -269,7 +276,8 @@ void voc_plan(const DexVoc* v, int B, int T, void* ws, VPlan& P) {
     size_t act = (size_t)B * T * c.upsample_initial_channel, ymax = 0;
     long L = T;
     for (int i = 0; i < c.n_upsamples; ++i) {
-        ymax = std::max(ymax, (size_t)B * L * c.upsample_kernel_sizes[i] * stage_ch(c, i));
+        if (!voc_narrow_width(stage_ch(c, i)))            // (the narrow transposed conv writes its stage input directly)
+            ymax = std::max(ymax, (size_t)B * L * c.upsample_kernel_sizes[i] * stage_ch(c, i));
         L *= c.upsample_rates[i];
         act = std::max(act, (size_t)B * L * stage_ch(c, i));
     }
@@ -299,6 +307,18 @@ IGemmP conv1d(const float* X, int L, int B, const VConv& c, float slope, float* 
     g.B = B;
     return g;
 }
+// one ResBlock conv: the implicit GEMM, or the direct kernel at a narrow width
+void voc_conv(const float* X, int L, int B, const VConv& c, float slope, float* out, const float* res, int prec, hipStream_t st) {
+    if (c.narrow) {
+        NarrowConvP n{X, c.w, c.b, res, out, L, c.cout, c.k, c.dil, B, slope};
+        launch_narrow_conv1d(n, st);
+    } else {
+        launch_igemm(conv1d(X, L, B, c, slope, out, res), prec, st);
+    }
+}
+void voc_aa_snake(const AaSnakeP& s, hipStream_t st) {
+    if (voc_narrow_width(s.C)) launch_aa_snake_narrow(s, st); else launch_aa_snake(s, st);
+}
 }  // namespace
 
 extern "C" {
@@ -326,7 +346,10 @@ int dex_vocode(DexVoc* v, const float* mel_dev, int B, int T, float* wav_dev, vo
     long L = T;
     for (int i = 0; i < c.n_upsamples; ++i) {
         const VUp& up = v->ups[i];
-        {   // ConvTranspose1d(leaky_relu(x, 0.1)): GEMM + overlap-add
+        if (up.narrow) {     // ConvTranspose1d into a narrow stage: one direct kernel
+            NarrowConvTP n{P.x, up.w, up.b, P.a, (int)L, up.cin, up.cout, up.k, up.u, up.pad, B, v->big() ? 0.f : 0.1f};
+            launch_narrow_convt(n, st);
+        } else {   // ConvTranspose1d(leaky_relu(x, 0.1)): GEMM + overlap-add
             IGemmP g{};
             g.A = P.x; g.lda = up.cin; g.a_bstride = L * up.cin; g.Hi = 1; g.Wi = (int)L; g.Cin = up.cin;
             g.KH = 1; g.KW = 1; g.sh = 1; g.sw = 1; g.step_h = 1; g.step_w = 1; g.Ho = 1; g.Wo = (int)L;
@@ -347,14 +370,14 @@ int dex_vocode(DexVoc* v, const float* mel_dev, int B, int T, float* wav_dev, vo
                 if (v->big()) {      // AMPBlock1 (bigvgan/models.py:76-85): xt = c1(a_{2m}(x)); x = c2(a_{2m+1}(xt)) + x
                     const size_t ai = ((size_t)(i * 3 + j) * 6) + 2 * m;
                     AaSnakeP s1{cur, P.s, (int)L, up.cout, B, v->act_a[ai], v->act_ib[ai], v->filt};
-                    launch_aa_snake(s1, st);
-                    launch_igemm(conv1d(P.s, (int)L, B, cv[2 * m], 0.f, P.x, nullptr), prec, st);
+                    voc_aa_snake(s1, st);
+                    voc_conv(P.s, (int)L, B, cv[2 * m], 0.f, P.x, nullptr, prec, st);
                     AaSnakeP s2{P.x, P.s, (int)L, up.cout, B, v->act_a[ai + 1], v->act_ib[ai + 1], v->filt};
-                    launch_aa_snake(s2, st);
-                    launch_igemm(conv1d(P.s, (int)L, B, cv[2 * m + 1], 0.f, dst, cur), prec, st);
+                    voc_aa_snake(s2, st);
+                    voc_conv(P.s, (int)L, B, cv[2 * m + 1], 0.f, dst, cur, prec, st);
                 } else {
-                    launch_igemm(conv1d(cur, (int)L, B, cv[2 * m], 0.1f, P.x, nullptr), prec, st);          // xt = c1(lrelu(x))
-                    launch_igemm(conv1d(P.x, (int)L, B, cv[2 * m + 1], 0.1f, dst, cur), prec, st);          // x = c2(lrelu(xt)) + x
+                    voc_conv(cur, (int)L, B, cv[2 * m], 0.1f, P.x, nullptr, prec, st);           // xt = c1(lrelu(x))
+                    voc_conv(P.x, (int)L, B, cv[2 * m + 1], 0.1f, dst, cur, prec, st);           // x = c2(lrelu(xt)) + x
                 }
                 cur = dst;
             }
@@ -364,7 +387,7 @@ int dex_vocode(DexVoc* v, const float* mel_dev, int B, int T, float* wav_dev, vo
     const float* xin = P.x;
     if (v->big()) {          // activation_post (models.py:205) replaces the leaky_relu in front of conv_post
         AaSnakeP sp{P.x, P.s, (int)L, stage_ch(c, c.n_upsamples - 1), B, v->act_a.back(), v->act_ib.back(), v->filt};
-        launch_aa_snake(sp, st);
+        voc_aa_snake(sp, st);
         xin = P.s;
     }
     ConvPostP cp{xin, v->post_w, v->post_b, wav_dev, (int)L, stage_ch(c, c.n_upsamples - 1), B, v->big() ? 1.f : 0.01f};

@@ -463,6 +463,16 @@ struct AaSnakeP { const float* X; float* Y; int L, C, B; const float* a; const f
 void launch_aa_snake(const AaSnakeP& p, hipStream_t st);
 void launch_snake_coeffs(const float* alpha, const float* beta, float* a, float* inv_b, int C, int logscale, hipStream_t st);
 void launch_conv_post_tanh(const ConvPostP& p, hipStream_t st);
+// narrow stages (vocoder_narrow.hip): C % 8 == 0, C <= 64, C % 32 != 0 — direct exact-fp32 kernels in every precision mode.
+bool voc_narrow_width(int C);
+// Conv1d(C -> C, k, dil, same padding) on leaky_relu(X, slope) (0: X as stored) + bias (+ res); W packed [tap][ci][co]
+struct NarrowConvP { const float* X; const float* W; const float* bias; const float* res; float* Y; int L, C, k, dil, B; float slope; };
+void launch_narrow_conv1d(const NarrowConvP& p, hipStream_t st);
+// ConvTranspose1d(Cin -> C, k, stride u, pad) on leaky_relu(X, slope), GEMM and overlap-add fused; W packed [ci][j][co]; X [B][L][Cin] -> Y [B][L u][C]
+struct NarrowConvTP { const float* X; const float* W; const float* bias; float* Y; int L, Cin, C, k, u, pad, B; float slope; };
+void launch_narrow_convt(const NarrowConvTP& p, hipStream_t st);
+// aa_snake with the channel lanes packed (256 / C groups per block); the same per-element arithmetic as launch_aa_snake
+void launch_aa_snake_narrow(const AaSnakeP& p, hipStream_t st);
 
 // DEX style encoders (dex_style.hip; reference DEX-TTS/model/ref_encoder.py:8-140,199-237) ------------
 // LayerNorm over the channels of channels-last rows (nn.LayerNorm / base.LayerNorm: biased variance), affine, then * mask[b][t]

@@ -20,11 +20,16 @@ HIFIGAN_V1 = dict(num_mels=80, upsample_rates=[8, 8, 2, 2], upsample_kernel_size
 
 
 # BigVGAN-base, 22 kHz / 80 bands: the configuration src/utils.py:267 reads from bigvgan/bigvgan_base_22khz_80band/config.json (not in
-# the reference tree; these are the published values of that file).  The 112 M "bigvgan_22khz_80band" model (1536 initial channels,
-# six up-sampling stages down to 24 channels) is outside the implicit GEMM's 32-channel granule and is not built.
+# the reference tree; these are the published values of that file).
 BIGVGAN_BASE = dict(num_mels=80, upsample_rates=[8, 8, 2, 2], upsample_kernel_sizes=[16, 16, 4, 4], upsample_initial_channel=512,
                     resblock="1", resblock_kernel_sizes=[3, 7, 11], resblock_dilation_sizes=[[1, 3, 5], [1, 3, 5], [1, 3, 5]],
                     activation="snakebeta", snake_logscale=True)
+# BigVGAN, 22 kHz / 80 bands (112 M parameters): the reference's ``vocoder: 'bigvgan'`` choice, bigvgan/bigvgan_22khz_80band/config.json
+# (published values; not in the reference tree either).  Six up-sampling stages 768/384/192/96/48/24 wide: the first four run on the
+# implicit GEMM, the 48- and 24-channel stages on the narrow kernels (vocoder_narrow.hip).
+BIGVGAN_22KHZ = dict(num_mels=80, upsample_rates=[4, 4, 2, 2, 2, 2], upsample_kernel_sizes=[8, 8, 4, 4, 4, 4], upsample_initial_channel=1536,
+                     resblock="1", resblock_kernel_sizes=[3, 7, 11], resblock_dilation_sizes=[[1, 3, 5], [1, 3, 5], [1, 3, 5]],
+                     activation="snakebeta", snake_logscale=True)
 ACTIVATION = {None: 0, "snake": 1, "snakebeta": 2}
 
 
@@ -218,8 +223,8 @@ class Generator(nn.Module):
 
 
 def get_vocoder(config_path: Optional[str] = None, ckpt: Optional[dict] = None, device="cuda") -> Generator:
-    """src/utils.py:251-281 for the 'hifigan' choice: config.json -> Generator -> load ckpt['generator'] -> eval ->
-    remove_weight_norm -> device."""
+    """src/utils.py:251-281: config.json -> Generator -> load ckpt['generator'] -> eval -> remove_weight_norm -> device.  The
+    'hifigan' choice's config.json builds HiFi-GAN; a BigVGAN config.json ('bigvgan_base' or 'bigvgan': ``activation`` set) BigVGAN."""
     h = AttrDict(json.load(open(config_path))) if config_path else AttrDict(HIFIGAN_V1)      # a BigVGAN config.json selects BigVGAN
     g = Generator(h)
     if ckpt is not None:
@@ -227,4 +232,4 @@ def get_vocoder(config_path: Optional[str] = None, ckpt: Optional[dict] = None, 
     return g.eval().to(device)
 
 
-BigVGAN = Generator      # bigvgan/__init__.py: ``from .models import BigVGAN as Generator`` — Generator(AttrDict(BIGVGAN_BASE))
+BigVGAN = Generator      # bigvgan/__init__.py: ``from .models import BigVGAN as Generator`` — Generator(AttrDict(BIGVGAN_BASE / BIGVGAN_22KHZ))
