@@ -11,13 +11,13 @@ path: CPU tensors and tensors that require grad are refused with RuntimeError.
 """
 from __future__ import annotations
 
-import ctypes as C
 import random
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._native import check, i32_ptr, stream
 
 MAX_TX, MAX_TY = 2048, 8192          # include/dex_amd.h DEX_MAS_MAX_TX / DEX_MAS_MAX_TY
 
@@ -38,19 +38,6 @@ def _lens(v, B):
     return np.ascontiguousarray(ln.astype(np.int32))
 
 
-def _ptr(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int32))
-
-
-def _check(rc, what):
-    if rc != _lib.DEX_OK:
-        raise (ValueError if rc == -1 else RuntimeError)(f"{what} failed ({rc})")
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def log_prior(mu_x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     """tts.py:100-106: mu_x [B, F, Tx], y [B, F, Ty] -> log_prior [B, Tx, Ty] fp32 (a transposed view of the frame-major [B, Ty, Tx]
     tensor the search reads)."""
@@ -67,7 +54,7 @@ def _log_prior_yx(mu_x, y):
     with torch.cuda.device(dev):
         m, yy = mu_x.to(torch.float32).contiguous(), y.to(torch.float32).contiguous()
         out = torch.empty(B, Ty, Tx, dtype=torch.float32, device=dev)
-        _check(lib.dex_mas_log_prior(m.data_ptr(), yy.data_ptr(), B, F, Tx, Ty, out.data_ptr(), _stream(dev)), "dex_mas_log_prior")
+        check(lib.dex_mas_log_prior(m.data_ptr(), yy.data_ptr(), B, F, Tx, Ty, out.data_ptr(), stream(dev)), "dex_mas_log_prior")
     return out
 
 
@@ -87,9 +74,9 @@ def _search(value, mask, tx, ty, want_path):
         dur = torch.empty(B, Tx, dtype=torch.int32, device=dev)
         path = torch.empty(B, Tx, Ty, dtype=torch.float32, device=dev) if want_path else None
         sb, sx, sy = value.stride()
-        _check(lib.dex_mas_durations(value.data_ptr(), mask.data_ptr() if mask is not None else None, B, Tx, Ty, sb, sx, sy,
-                                     _ptr(tx), _ptr(ty), dur.data_ptr(), path.data_ptr() if path is not None else None,
-                                     ws.data_ptr(), need, _stream(dev)), "dex_mas_durations")
+        check(lib.dex_mas_durations(value.data_ptr(), mask.data_ptr() if mask is not None else None, B, Tx, Ty, sb, sx, sy,
+                                    i32_ptr(tx), i32_ptr(ty), dur.data_ptr(), path.data_ptr() if path is not None else None,
+                                    ws.data_ptr(), need, stream(dev)), "dex_mas_durations")
     return dur, path
 
 
@@ -145,8 +132,8 @@ def dur_prior_losses(logw: torch.Tensor, dur: torch.Tensor, x_lengths, y: torch.
         yy, mm = y.to(torch.float32).contiguous(), mu_y.to(torch.float32).contiguous()
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         out = torch.empty(2, dtype=torch.float32, device=dev)
-        _check(lib.dex_mas_losses(lw.data_ptr(), d.data_ptr(), _ptr(tx), B, Tx, yy.data_ptr(), mm.data_ptr(), _ptr(ty), F, Ty,
-                                  out.data_ptr(), ws.data_ptr(), need, _stream(dev)), "dex_mas_losses")
+        check(lib.dex_mas_losses(lw.data_ptr(), d.data_ptr(), i32_ptr(tx), B, Tx, yy.data_ptr(), mm.data_ptr(), i32_ptr(ty), F, Ty,
+                                 out.data_ptr(), ws.data_ptr(), need, stream(dev)), "dex_mas_losses")
     return out[0], out[1]
 
 
@@ -191,6 +178,6 @@ def segment(mu_x: torch.Tensor, dur: torch.Tensor, y: torch.Tensor, y_lengths, o
         y_cut = torch.empty(B, F, S, dtype=torch.float32, device=dev)
         mu_cut = torch.empty(B, F, S, dtype=torch.float32, device=dev)
         mask = torch.empty(B, 1, S, dtype=torch.float32, device=dev)
-        _check(lib.dex_loss_segment(m.data_ptr(), d.data_ptr(), yy.data_ptr(), B, F, Tx, Ty, _ptr(yl), _ptr(off32), S, y_cut.data_ptr(),
-                                    mu_cut.data_ptr(), mask.data_ptr(), _stream(dev)), "dex_loss_segment")
+        check(lib.dex_loss_segment(m.data_ptr(), d.data_ptr(), yy.data_ptr(), B, F, Tx, Ty, i32_ptr(yl), i32_ptr(off32), S, y_cut.data_ptr(),
+                                   mu_cut.data_ptr(), mask.data_ptr(), stream(dev)), "dex_loss_segment")
     return y_cut, mu_cut, mask, torch.from_numpy(cl)

@@ -14,12 +14,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._native import stream
 
 _FIXED = (1024, 256, 1024, 80, 22050, 0, 8000)
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 class TacotronSTFT:
@@ -61,7 +58,7 @@ class TacotronSTFT:
             mel = torch.empty(B, 80, frames, dtype=torch.float32, device=self.device)
             energy = torch.empty(B, frames, dtype=torch.float32, device=self.device)
             rc = self._lib.dex_mel_spectrogram(self._h, y.data_ptr(), B, L, mel.data_ptr(), energy.data_ptr(), self._ws.data_ptr(),
-                                               self._ws.numel(), _stream(self.device))
+                                               self._ws.numel(), stream(self.device))
             if rc != _lib.DEX_OK:
                 raise RuntimeError(f"dex_mel_spectrogram: {self._lib.dex_mel_last_error(self._h).decode()} ({rc})")
             return mel, energy
@@ -94,7 +91,7 @@ def lf0_from_f0(f0: torch.Tensor, lengths: torch.Tensor = None) -> torch.Tensor:
         B, T = x.shape
         ln = None if lengths is None else lengths.to(device=x.device, dtype=torch.int32).contiguous()
         out = torch.empty_like(x)
-        rc = lib.dex_lf0_normalize(x.data_ptr(), None if ln is None else ln.data_ptr(), B, T, out.data_ptr(), _stream(x.device))
+        rc = lib.dex_lf0_normalize(x.data_ptr(), None if ln is None else ln.data_ptr(), B, T, out.data_ptr(), stream(x.device))
         if rc != _lib.DEX_OK:
             raise RuntimeError(f"dex_lf0_normalize failed ({rc})")
         return out[0] if one else out

@@ -19,6 +19,7 @@
 
 #include "../../include/dex_amd.h"
 #include "kernels.h"
+#include "weight_store.h"
 
 using namespace dex;
 
@@ -88,7 +89,6 @@ static_assert(PREC_FP32 == DEX_PREC_FP32 && PREC_BF16 == DEX_PREC_BF16 && PREC_F
 namespace {
 void xcd_map_probe();       // (defined with the cluster launch plan below)
 
-struct RawW { float* p = nullptr; std::vector<int64_t> shape; long numel = 0; bool loaded = false; };
 struct TD { float* p; int ld; int coff; int C; int lp = 0; };   // channels-last activation view; lp: 16-bit elements (1 bf16, 2 fp16)
 
 struct ResW { const float *w1, *b1, *g1, *be1, *w2, *b2, *g2, *be2, *wr, *br, *mlp_w, *mlp_b; int cin, cout; };
@@ -124,12 +124,9 @@ struct Arena {                                             // bump allocator ove
 
 }  // namespace
 
-struct DexCtx {
+struct DexCtx : WeightStore {
+    DexCtx() : WeightStore("") {}
     DexConfig cfg{};
-    std::string err;
-    std::vector<std::string> keys;
-    std::map<std::string, RawW> raw;
-    std::vector<void*> owned;                              // hipMalloc'ed packed weights
     // low-precision twins of the fp32 [K][N] packs, one set per operand type: [0] bf16, [1] fp16 (both are packed at
     // finalize: the precision mode may change afterwards)
     // [2] = the split-weight mode (DEX_PREC_FP16X2): fp16 twins whose lo pack (fp16 of what the hi rounding lost, same layout) follows
@@ -143,7 +140,6 @@ struct DexCtx {
     bool lp() const { return precision != DEX_PREC_FP32; }
     const std::map<const float*, const void*>& lp_of() const { return lp_of_[lpi()]; }
     const std::map<const float*, const void*>& frag_of() const { return frag_of_[lpi()]; }
-    bool finalized = false;
     bool tuned = true;                                     // geometry the reduced-precision kernels are built for (dex_ctx_create)
     int precision = DEX_PREC_FP32;
     // packed weights
@@ -176,18 +172,7 @@ struct DexCtx {
     std::vector<GraphEntry> graphs;
     uint64_t graph_clock = 0;
     void drop_graphs() { for (auto& g : graphs) hipGraphExecDestroy(g.exec); graphs.clear(); }
-
-    int fail(int code, const char* fmt, ...) {
-        char buf[512];
-        va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-        err = buf;
-        return code;
-    }
 };
-
-#define HIPCHK(ctx, call)                                                                              \
-    do { hipError_t e_ = (call); if (e_ != hipSuccess)                                                 \
-        return (ctx)->fail(DEX_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
 // ================================================================================================
 // parameter inventory (mirrors dex_tts_amd/config.py:param_shapes; validated against the reference
@@ -207,73 +192,67 @@ int token_cols(const DexConfig& c, int wmid) {
 }
 int mlp_hidden(const DexConfig& c) { return (int)(c.dit_hidden * c.dit_mlp_ratio); }
 
-void add_key(DexCtx* x, const std::string& k, std::vector<int64_t> shape) {
-    x->keys.push_back(k);
-    RawW r; r.shape = std::move(shape); r.numel = 1;
-    for (auto d : r.shape) r.numel *= d;
-    x->raw[k] = r;
-}
 void add_resnet(DexCtx* x, const std::string& p, int cin, int cout, int tdim) {
-    add_key(x, p + ".mlp.1.weight", {cout, tdim}); add_key(x, p + ".mlp.1.bias", {cout});
+    x->add(p + ".mlp.1.weight", {cout, tdim}); x->add(p + ".mlp.1.bias", {cout});
     for (int blk = 1; blk <= 2; ++blk) {
         const std::string q = p + ".block" + std::to_string(blk) + ".block";
-        add_key(x, q + ".0.weight", {cout, blk == 1 ? cin : cout, 3, 3}); add_key(x, q + ".0.bias", {cout});
-        add_key(x, q + ".1.weight", {cout}); add_key(x, q + ".1.bias", {cout});
+        x->add(q + ".0.weight", {cout, blk == 1 ? cin : cout, 3, 3}); x->add(q + ".0.bias", {cout});
+        x->add(q + ".1.weight", {cout}); x->add(q + ".1.bias", {cout});
     }
-    if (cin != cout) { add_key(x, p + ".res_conv.weight", {cout, cin, 1, 1}); add_key(x, p + ".res_conv.bias", {cout}); }
+    if (cin != cout) { x->add(p + ".res_conv.weight", {cout, cin, 1, 1}); x->add(p + ".res_conv.bias", {cout}); }
 }
 void add_linattn(DexCtx* x, const std::string& p, int c) {
-    add_key(x, p + ".fn.g", {1});
-    add_key(x, p + ".fn.fn.to_qkv.weight", {384, c, 1, 1});
-    add_key(x, p + ".fn.fn.to_out.weight", {c, 128, 1, 1});
-    add_key(x, p + ".fn.fn.to_out.bias", {c});
+    x->add(p + ".fn.g", {1});
+    x->add(p + ".fn.fn.to_qkv.weight", {384, c, 1, 1});
+    x->add(p + ".fn.fn.to_out.weight", {c, 128, 1, 1});
+    x->add(p + ".fn.fn.to_out.bias", {c});
 }
 void build_inventory(DexCtx* x) {
     const DexConfig& c = x->cfg;
     const int d = c.dim;
-    add_key(x, "mlp.0.weight", {4 * d, d}); add_key(x, "mlp.0.bias", {4 * d});
-    add_key(x, "mlp.2.weight", {d, 4 * d}); add_key(x, "mlp.2.bias", {d});
+    x->add("mlp.0.weight", {4 * d, d}); x->add("mlp.0.bias", {4 * d});
+    x->add("mlp.2.weight", {d, 4 * d}); x->add("mlp.2.bias", {d});
     if (c.variant == DEX_VARIANT_DEX)
         for (const char* n : {"mlp_adap", "mlp_adap_sty"}) {
             const std::string s(n);
-            add_key(x, s + ".0.weight", {d, d}); add_key(x, s + ".0.bias", {d});
-            add_key(x, s + ".2.weight", {2 * d, d}); add_key(x, s + ".2.bias", {2 * d});
+            x->add(s + ".0.weight", {d, d}); x->add(s + ".0.bias", {d});
+            x->add(s + ".2.weight", {2 * d, d}); x->add(s + ".2.bias", {2 * d});
         }
     if (c.n_spks > 1) {
         const int e = c.spk_emb_dim;
-        add_key(x, "spk_mlp.0.weight", {4 * e, e}); add_key(x, "spk_mlp.0.bias", {4 * e});
-        add_key(x, "spk_mlp.2.weight", {c.n_feats, 4 * e}); add_key(x, "spk_mlp.2.bias", {c.n_feats});
+        x->add("spk_mlp.0.weight", {4 * e, e}); x->add("spk_mlp.0.bias", {4 * e});
+        x->add("spk_mlp.2.weight", {c.n_feats, 4 * e}); x->add("spk_mlp.2.bias", {c.n_feats});
     }
     for (int i = 0; i < c.n_stages; ++i) {
         const int ci = i == 0 ? in_planes(c) : stage_dim(c, i - 1), co = stage_dim(c, i);
         const std::string p = "downs." + std::to_string(i);
         add_resnet(x, p + ".0", ci, co, d); add_resnet(x, p + ".1", co, co, d); add_linattn(x, p + ".2", co);
-        if (i < c.n_stages - 1) { add_key(x, p + ".3.conv.weight", {co, co, 3, 3}); add_key(x, p + ".3.conv.bias", {co}); }
+        if (i < c.n_stages - 1) { x->add(p + ".3.conv.weight", {co, co, 3, 3}); x->add(p + ".3.conv.bias", {co}); }
     }
     const int hid = c.dit_hidden, mid = mid_dim(c), mh = mlp_hidden(c);
-    add_key(x, "vit.freq_new_pos_embed", {1, hid, grid_h(c), 1});
-    add_key(x, "vit.x_embedder.proj.0.weight", {mid, 1, c.dit_patch, c.dit_patch}); add_key(x, "vit.x_embedder.proj.0.bias", {mid});
-    add_key(x, "vit.x_embedder.proj.2.weight", {hid, mid, 1, 1}); add_key(x, "vit.x_embedder.proj.2.bias", {hid});
-    add_key(x, "vit.t_embedder.mlp.0.weight", {hid, 256}); add_key(x, "vit.t_embedder.mlp.0.bias", {hid});
-    add_key(x, "vit.t_embedder.mlp.2.weight", {hid, hid}); add_key(x, "vit.t_embedder.mlp.2.bias", {hid});
-    add_key(x, "vit.pos_conv.0.weight", {hid, hid / c.dit_conv_pos_groups, c.dit_conv_pos, c.dit_conv_pos});
-    add_key(x, "vit.pos_conv.0.bias", {hid});
+    x->add("vit.freq_new_pos_embed", {1, hid, grid_h(c), 1});
+    x->add("vit.x_embedder.proj.0.weight", {mid, 1, c.dit_patch, c.dit_patch}); x->add("vit.x_embedder.proj.0.bias", {mid});
+    x->add("vit.x_embedder.proj.2.weight", {hid, mid, 1, 1}); x->add("vit.x_embedder.proj.2.bias", {hid});
+    x->add("vit.t_embedder.mlp.0.weight", {hid, 256}); x->add("vit.t_embedder.mlp.0.bias", {hid});
+    x->add("vit.t_embedder.mlp.2.weight", {hid, hid}); x->add("vit.t_embedder.mlp.2.bias", {hid});
+    x->add("vit.pos_conv.0.weight", {hid, hid / c.dit_conv_pos_groups, c.dit_conv_pos, c.dit_conv_pos});
+    x->add("vit.pos_conv.0.bias", {hid});
     for (int k = 0; k < c.dit_depth; ++k) {
         const std::string p = "vit.blocks." + std::to_string(k);
-        add_key(x, p + ".attn.qkv.weight", {3 * hid, hid}); add_key(x, p + ".attn.qkv.bias", {3 * hid});
-        add_key(x, p + ".attn.proj.weight", {hid, hid}); add_key(x, p + ".attn.proj.bias", {hid});
-        add_key(x, p + ".mlp.fc1.weight", {mh, hid}); add_key(x, p + ".mlp.fc1.bias", {mh});
-        add_key(x, p + ".mlp.fc2.weight", {hid, mh}); add_key(x, p + ".mlp.fc2.bias", {hid});
-        add_key(x, p + ".adaLN_modulation.1.weight", {6 * hid, hid}); add_key(x, p + ".adaLN_modulation.1.bias", {6 * hid});
+        x->add(p + ".attn.qkv.weight", {3 * hid, hid}); x->add(p + ".attn.qkv.bias", {3 * hid});
+        x->add(p + ".attn.proj.weight", {hid, hid}); x->add(p + ".attn.proj.bias", {hid});
+        x->add(p + ".mlp.fc1.weight", {mh, hid}); x->add(p + ".mlp.fc1.bias", {mh});
+        x->add(p + ".mlp.fc2.weight", {hid, mh}); x->add(p + ".mlp.fc2.bias", {hid});
+        x->add(p + ".adaLN_modulation.1.weight", {6 * hid, hid}); x->add(p + ".adaLN_modulation.1.bias", {6 * hid});
     }
     const int so = c.dit_stride * c.dit_stride * mid;
-    add_key(x, "vit.final_layer.linear.weight", {so, hid}); add_key(x, "vit.final_layer.linear.bias", {so});
-    add_key(x, "vit.final_layer.adaLN_modulation.1.weight", {2 * hid, hid}); add_key(x, "vit.final_layer.adaLN_modulation.1.bias", {2 * hid});
+    x->add("vit.final_layer.linear.weight", {so, hid}); x->add("vit.final_layer.linear.bias", {so});
+    x->add("vit.final_layer.adaLN_modulation.1.weight", {2 * hid, hid}); x->add("vit.final_layer.adaLN_modulation.1.bias", {2 * hid});
     if (c.variant == DEX_VARIANT_DEX) {
-        for (const char* w : {"w_q", "w_k", "w_v", "linear"}) add_key(x, std::string("tv_adaptor.") + w + ".weight", {mid, mid});
+        for (const char* w : {"w_q", "w_k", "w_v", "linear"}) x->add(std::string("tv_adaptor.") + w + ".weight", {mid, mid});
         for (const char* s : {"mean_sap", "std_sap"}) {
-            add_key(x, std::string("tiv_adaptor.") + s + ".W.weight", {1, mid});
-            add_key(x, std::string("tiv_adaptor.") + s + ".W.bias", {1});
+            x->add(std::string("tiv_adaptor.") + s + ".W.weight", {1, mid});
+            x->add(std::string("tiv_adaptor.") + s + ".W.bias", {1});
         }
     }
     for (int j = 0; j < c.n_stages - 1; ++j) {
@@ -281,11 +260,11 @@ void build_inventory(DexCtx* x) {
         const int ci = stage_dim(c, i - 1), co = stage_dim(c, i);
         const std::string p = "ups." + std::to_string(j);
         add_resnet(x, p + ".0", co * 2, ci, d); add_resnet(x, p + ".1", ci, ci, d); add_linattn(x, p + ".2", ci);
-        add_key(x, p + ".3.conv.weight", {ci, ci, 4, 4}); add_key(x, p + ".3.conv.bias", {ci});
+        x->add(p + ".3.conv.weight", {ci, ci, 4, 4}); x->add(p + ".3.conv.bias", {ci});
     }
-    add_key(x, "final_block.block.0.weight", {d, d, 3, 3}); add_key(x, "final_block.block.0.bias", {d});
-    add_key(x, "final_block.block.1.weight", {d}); add_key(x, "final_block.block.1.bias", {d});
-    add_key(x, "final_conv.weight", {1, d, 1, 1}); add_key(x, "final_conv.bias", {1});
+    x->add("final_block.block.0.weight", {d, d, 3, 3}); x->add("final_block.block.0.bias", {d});
+    x->add("final_block.block.1.weight", {d}); x->add("final_block.block.1.bias", {d});
+    x->add("final_conv.weight", {1, d, 1, 1}); x->add("final_conv.bias", {1});
 }
 
 // ConvTranspose2d(4,2,1) -> four 2x2-tap parity sub-convolutions.
@@ -340,8 +319,7 @@ int dex_ctx_create(const DexConfig* cfg, DexCtx** out) {
 
 void dex_ctx_destroy(DexCtx* x) {
     if (!x) return;
-    for (auto& kv : x->raw) if (kv.second.p) hipFree(kv.second.p);
-    for (void* p : x->owned) hipFree(p);
+    x->release();
     if (x->mel_basis) hipFree(x->mel_basis);
     if (x->mel_filt) hipFree(x->mel_filt);
     if (x->mel_ws) hipFree(x->mel_ws);
@@ -355,39 +333,12 @@ void dex_ctx_destroy(DexCtx* x) {
 const char* dex_last_error(const DexCtx* x) { return x ? x->err.c_str() : "null context"; }
 int dex_ctx_num_weights(const DexCtx* x) { return x ? (int)x->keys.size() : 0; }
 
-int dex_ctx_weight_info(const DexCtx* x, int i, const char** key, int64_t shape[4], int* ndim) {
-    if (!x || i < 0 || i >= (int)x->keys.size()) return DEX_ERR_ARG;
-    const RawW& r = x->raw.at(x->keys[i]);
-    if (key) *key = x->keys[i].c_str();
-    if (ndim) *ndim = (int)r.shape.size();
-    if (shape) for (size_t k = 0; k < r.shape.size(); ++k) shape[k] = r.shape[k];
-    return DEX_OK;
-}
-
-static int load_weight_impl(DexCtx* x, const char* key, const float* w_dev, const int64_t* shape, int ndim, bool async, hipStream_t st) {
-    if (!x || !key || !w_dev) return DEX_ERR_ARG;
-    auto it = x->raw.find(key);
-    if (it == x->raw.end()) return x->fail(DEX_ERR_ARG, "unknown weight key '%s'", key);
-    RawW& r = it->second;
-    if ((int)r.shape.size() != ndim) return x->fail(DEX_ERR_ARG, "weight '%s': expected %d dims, got %d", key, (int)r.shape.size(), ndim);
-    for (int k = 0; k < ndim; ++k)
-        if (r.shape[k] != shape[k]) return x->fail(DEX_ERR_ARG, "weight '%s': dim %d is %lld, expected %lld", key, k, (long long)shape[k], (long long)r.shape[k]);
-    if (!r.p) HIPCHK(x, hipMalloc((void**)&r.p, r.numel * sizeof(float)));
-    if (async) {
-        HIPCHK(x, hipMemcpyAsync(r.p, w_dev, r.numel * sizeof(float), hipMemcpyDeviceToDevice, st));
-    } else {
-        HIPCHK(x, hipMemcpy(r.p, w_dev, r.numel * sizeof(float), hipMemcpyDeviceToDevice));
-        HIPCHK(x, hipStreamSynchronize(nullptr));       // a device-to-device hipMemcpy may return before it has run
-    }
-    r.loaded = true;
-    x->finalized = false;
-    return DEX_OK;
-}
+int dex_ctx_weight_info(const DexCtx* x, int i, const char** key, int64_t shape[4], int* ndim) { return x ? x->info(i, key, shape, ndim) : DEX_ERR_ARG; }
 int dex_ctx_load_weight(DexCtx* x, const char* key, const float* w_dev, const int64_t* shape, int ndim) {
-    return load_weight_impl(x, key, w_dev, shape, ndim, false, nullptr);
+    return x ? x->load(key, w_dev, shape, ndim, nullptr, true) : DEX_ERR_ARG;
 }
 int dex_ctx_load_weight_async(DexCtx* x, const char* key, const float* w_dev, const int64_t* shape, int ndim, dex_stream_t stream) {
-    return load_weight_impl(x, key, w_dev, shape, ndim, true, (hipStream_t)stream);
+    return x ? x->load(key, w_dev, shape, ndim, (hipStream_t)stream, false) : DEX_ERR_ARG;
 }
 
 int dex_ctx_set_precision(DexCtx* x, int precision) {
@@ -409,13 +360,8 @@ int dex_ctx_set_precision(DexCtx* x, int precision) {
 namespace {
 
 struct Packer {
-    DexCtx* x; hipStream_t st; int rc = DEX_OK;
-    float* alloc(long n) {
-        float* p = nullptr;
-        if (hipMalloc((void**)&p, n * sizeof(float)) != hipSuccess) { rc = x->fail(DEX_ERR_HIP, "hipMalloc of %ld floats failed", n); return nullptr; }
-        x->owned.push_back(p);
-        return p;
-    }
+    DexCtx* x; hipStream_t st;
+    float* alloc(long n) { return x->alloc(n); }
     // twin set t: 0 bf16, 1 fp16, 2 fp16 hi + lo.  pack3 runs `pack(src, dst, precision)` for the set: once, or (t == 2) on the weight
     // and on what its fp16 rounding lost (src - float(fp16(src)), through a scratch fp32 copy - packs are permutations, so the lo pack
     // has the hi pack's layout), the lo pack `n_dst` elements behind the hi pack.
@@ -556,10 +502,7 @@ void build_mel_constants(std::vector<float>& basis, std::vector<float>& filt) {
 
 extern "C" int dex_ctx_finalize(DexCtx* x, dex_stream_t stream) {
     if (!x) return DEX_ERR_ARG;
-    for (const auto& k : x->keys)
-        if (!x->raw.at(k).loaded) return x->fail(DEX_ERR_STATE, "weight '%s' was never loaded", k.c_str());
-    for (void* p : x->owned) hipFree(p);
-    x->owned.clear();
+    if (int rc = x->begin_finalize()) return rc;
     for (int t = 0; t < 3; ++t) { x->lp_of_[t].clear(); x->frag_of_[t].clear(); }
     x->lo_off_.clear();
     x->drop_graphs();
@@ -648,14 +591,14 @@ extern "C" int dex_ctx_finalize(DexCtx* x, dex_stream_t stream) {
     if (!x->mel_basis) {
         std::vector<float> basis, filt;
         build_mel_constants(basis, filt);
-        HIPCHK(x, hipMalloc((void**)&x->mel_basis, basis.size() * sizeof(float)));
-        HIPCHK(x, hipMalloc((void**)&x->mel_filt, filt.size() * sizeof(float)));
-        HIPCHK(x, hipMemcpy(x->mel_basis, basis.data(), basis.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(x, hipMemcpy(x->mel_filt, filt.data(), filt.size() * sizeof(float), hipMemcpyHostToDevice));
+        DEX_HIPCHK(x, hipMalloc((void**)&x->mel_basis, basis.size() * sizeof(float)));
+        DEX_HIPCHK(x, hipMalloc((void**)&x->mel_filt, filt.size() * sizeof(float)));
+        DEX_HIPCHK(x, hipMemcpy(x->mel_basis, basis.data(), basis.size() * sizeof(float), hipMemcpyHostToDevice));
+        DEX_HIPCHK(x, hipMemcpy(x->mel_filt, filt.data(), filt.size() * sizeof(float), hipMemcpyHostToDevice));
     }
-    if (P.rc != DEX_OK) return P.rc;
-    HIPCHK(x, hipStreamSynchronize(st));
-    HIPCHK(x, hipGetLastError());
+    if (x->alloc_rc != DEX_OK) return x->alloc_rc;
+    DEX_HIPCHK(x, hipStreamSynchronize(st));
+    DEX_HIPCHK(x, hipGetLastError());
     x->finalized = true;
     return DEX_OK;
 }
@@ -1827,7 +1770,7 @@ int dex_denoise_once(DexCtx* x, const DexDenoiseArgs* da, dex_stream_t stream) {
     hipLaunchKernelGGL(set_sigma_pair, dim3(1), dim3(1), 0, st, a->sigmas_dev, P.sig2);
     R.prepare(P.sig2, 1);
     R.step(a->out_dev, nullptr);
-    HIPCHK(x, hipGetLastError());
+    DEX_HIPCHK(x, hipGetLastError());
     return DEX_OK;
 }
 
@@ -1855,7 +1798,7 @@ int dex_sample(DexCtx* x, const DexSampleArgs* a, dex_stream_t stream) {
     if (!use_graph) {
         rc = enqueue();
         if (rc) return rc;
-        HIPCHK(x, hipGetLastError());
+        DEX_HIPCHK(x, hipGetLastError());
         return DEX_OK;
     }
     // One graph = the whole call.  Every device pointer the captured kernels dereference is part of the key, so a replay
@@ -1883,7 +1826,7 @@ int dex_sample(DexCtx* x, const DexSampleArgs* a, dex_stream_t stream) {
             x->graphs.erase(x->graphs.begin() + lru);
         }
         hipGraph_t graph = nullptr;
-        HIPCHK(x, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+        DEX_HIPCHK(x, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
         rc = enqueue();
         hipError_t ec = hipStreamEndCapture(st, &graph);          // always leave capture mode
         if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
@@ -1897,8 +1840,8 @@ int dex_sample(DexCtx* x, const DexSampleArgs* a, dex_stream_t stream) {
     }
     x->last_xerr = hit->xerr;           // a replay enqueues nothing on the host: dex_call_status reads the word the CAPTURED launches write
     hit->stamp = ++x->graph_clock;
-    HIPCHK(x, hipGraphLaunch(hit->exec, st));
-    HIPCHK(x, hipGetLastError());
+    DEX_HIPCHK(x, hipGraphLaunch(hit->exec, st));
+    DEX_HIPCHK(x, hipGetLastError());
     return DEX_OK;
 }
 
@@ -1917,7 +1860,7 @@ int dex_tap_copy(DexCtx* x, const char* name, float* dst, size_t dst_bytes, dex_
         if (t.name == name) {
             const size_t rows = (size_t)t.shape[0], C = (size_t)t.shape[1], ld = (size_t)t.shape[2];
             if (dst_bytes < rows * C * 4) return x->fail(DEX_ERR_ARG, "tap '%s' needs %zu bytes", name, rows * C * 4);
-            HIPCHK(x, hipMemcpy2DAsync(dst, C * 4, t.p, ld * 4, C * 4, rows, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+            DEX_HIPCHK(x, hipMemcpy2DAsync(dst, C * 4, t.p, ld * 4, C * 4, rows, hipMemcpyDeviceToDevice, (hipStream_t)stream));
             return DEX_OK;
         }
     return x->fail(DEX_ERR_ARG, "unknown tap '%s'", name);
@@ -1981,8 +1924,8 @@ int dex_call_status_begin(DexCtx* x, dex_stream_t stream) {
         if (hipHostMalloc(reinterpret_cast<void**>(&x->st_host), sizeof(int), hipHostMallocDefault) != hipSuccess) return x->fail(DEX_ERR_HIP, "dex_call_status_begin: hipHostMalloc failed");
         if (hipEventCreateWithFlags(&x->st_ev, hipEventDisableTiming) != hipSuccess) return x->fail(DEX_ERR_HIP, "dex_call_status_begin: hipEventCreate failed");
     }
-    HIPCHK(x, hipMemcpyAsync(x->st_host, x->last_xerr, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(x, hipEventRecord(x->st_ev, (hipStream_t)stream));
+    DEX_HIPCHK(x, hipMemcpyAsync(x->st_host, x->last_xerr, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    DEX_HIPCHK(x, hipEventRecord(x->st_ev, (hipStream_t)stream));
     x->st_pending = true;
     return DEX_OK;
 }
@@ -2081,16 +2024,16 @@ int dex_mel_from_wav(DexCtx* x, const float* wav_dev, int n, float* mel_dev, flo
     if (!x->mel_basis) {
         std::vector<float> basis, filt;
         build_mel_constants(basis, filt);
-        HIPCHK(x, hipMalloc((void**)&x->mel_basis, basis.size() * sizeof(float)));
-        HIPCHK(x, hipMalloc((void**)&x->mel_filt, filt.size() * sizeof(float)));
-        HIPCHK(x, hipMemcpy(x->mel_basis, basis.data(), basis.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(x, hipMemcpy(x->mel_filt, filt.data(), filt.size() * sizeof(float), hipMemcpyHostToDevice));
+        DEX_HIPCHK(x, hipMalloc((void**)&x->mel_basis, basis.size() * sizeof(float)));
+        DEX_HIPCHK(x, hipMalloc((void**)&x->mel_filt, filt.size() * sizeof(float)));
+        DEX_HIPCHK(x, hipMemcpy(x->mel_basis, basis.data(), basis.size() * sizeof(float), hipMemcpyHostToDevice));
+        DEX_HIPCHK(x, hipMemcpy(x->mel_filt, filt.data(), filt.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     const size_t need = dex_mel_workspace_bytes(1, n);
     if (need > x->mel_ws_bytes) {       // grow-only scratch, single-stream use (documented in include/dex_amd.h)
-        if (x->mel_ws) { HIPCHK(x, hipStreamSynchronize(st)); hipFree(x->mel_ws); }
+        if (x->mel_ws) { DEX_HIPCHK(x, hipStreamSynchronize(st)); hipFree(x->mel_ws); }
         x->mel_ws = nullptr; x->mel_ws_bytes = 0;
-        HIPCHK(x, hipMalloc(&x->mel_ws, need));
+        DEX_HIPCHK(x, hipMalloc(&x->mel_ws, need));
         x->mel_ws_bytes = need;
     }
     if (mel_enqueue(x->mel_basis, x->mel_filt, wav_dev, 1, n, mel_dev, energy_dev, x->mel_ws, st)) return x->fail(DEX_ERR_HIP, "mel front-end launch failed");

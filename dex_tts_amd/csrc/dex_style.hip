@@ -8,63 +8,38 @@
 // over a few hundred frames: once per reference utterance, ahead of 50-100 sampler steps.
 #include <hip/hip_runtime.h>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/dex_amd.h"
 #include "kernels.h"
+#include "weight_store.h"
 
 using namespace dex;
 
 namespace {
-struct SRaw { float* p = nullptr; std::vector<int64_t> shape; long numel = 0; bool loaded = false; };
-struct SConv { const float* w = nullptr; const float* b = nullptr; int cin, cout, k; };      // packed [k*cin][cout], bias or null
-struct SProj { SConv c1, c2, pr; const float *g1, *b1, *g2, *b2; };
+struct SProj { PackedConv c1, c2, pr; const float *g1, *b1, *g2, *b2; };
 constexpr int MEL_LD = 96, LF0_LD = 32;
 }  // namespace
 
-struct DexStyle {
+struct DexStyle : WeightStore {
+    DexStyle() : WeightStore("style ") {}
     DexStyleConfig cfg{};
-    std::string err;
-    std::vector<std::string> keys;
-    std::map<std::string, SRaw> raw;
-    std::vector<void*> owned;
-    bool finalized = false;
-    SConv tiv_in; std::vector<SConv> tiv_b0, tiv_b1;
-    SConv tv_in, tv_out, tv_p1; std::vector<SConv> tv_b0, tv_b1; SProj tv_p0;
+    PackedConv tiv_in; std::vector<PackedConv> tiv_b0, tiv_b1;
+    PackedConv tv_in, tv_out, tv_p1; std::vector<PackedConv> tv_b0, tv_b1; SProj tv_p0;
     const float* embT = nullptr; const float* e2 = nullptr;       // codebook as a GEMM operand [D][M], |e|^2 [M]
-    SConv lf_in, lf_out; SProj lf_proj;
+    PackedConv lf_in, lf_out; SProj lf_proj;
     std::vector<const float*> gru_wih, gru_bih, gru_whh, gru_bhh;   // per layer: [in][2*3H], [2*3H], [2][3H][H], [2][3H]
-    SConv sty;
-    int fail(int code, const char* fmt, ...) {
-        char buf[512];
-        va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-        err = buf;
-        return code;
-    }
-    const float* R(const std::string& k) const { return raw.at(k).p; }
+    PackedConv sty;
 };
 
-#define SCHK(v, call)                                                                                  \
-    do { hipError_t e_ = (call); if (e_ != hipSuccess)                                                 \
-        return (v)->fail(DEX_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
-
 namespace {
-void skey(DexStyle* v, const std::string& k, std::vector<int64_t> shape) {
-    v->keys.push_back(k);
-    SRaw r; r.shape = std::move(shape); r.numel = 1;
-    for (auto d : r.shape) r.numel *= d;
-    v->raw[k] = r;
-}
 void proj_keys(DexStyle* v, const std::string& p, int cin, int ch) {
-    skey(v, p + ".conv_1.weight", {ch, cin, 3}); skey(v, p + ".conv_1.bias", {ch});
-    skey(v, p + ".norm_1.gamma", {ch}); skey(v, p + ".norm_1.beta", {ch});
-    skey(v, p + ".conv_2.weight", {ch, ch, 3}); skey(v, p + ".conv_2.bias", {ch});
-    skey(v, p + ".norm_2.gamma", {ch}); skey(v, p + ".norm_2.beta", {ch});
-    skey(v, p + ".proj.weight", {ch, ch, 1}); skey(v, p + ".proj.bias", {ch});
+    v->add(p + ".conv_1.weight", {ch, cin, 3}); v->add(p + ".conv_1.bias", {ch});
+    v->add(p + ".norm_1.gamma", {ch}); v->add(p + ".norm_1.beta", {ch});
+    v->add(p + ".conv_2.weight", {ch, ch, 3}); v->add(p + ".conv_2.bias", {ch});
+    v->add(p + ".norm_2.gamma", {ch}); v->add(p + ".norm_2.beta", {ch});
+    v->add(p + ".proj.weight", {ch, ch, 1}); v->add(p + ".proj.bias", {ch});
 }
 }  // namespace
 
@@ -83,103 +58,55 @@ int dex_style_create(const DexStyleConfig* cfg, DexStyle** out) {
     if (c.tv_n_emb % 64 || c.tv_n_emb < 64) return v->fail(DEX_ERR_ARG, "n_emb must be a multiple of 64");
     if (c.lf0_cout != c.tv_cout || c.lf0_cout_g != c.tv_cout_g) return v->fail(DEX_ERR_ARG, "lf0 and tv encoder output widths must match (they are added, tts.py:62-65)");
     if (c.tiv_layers < 1 || c.tiv_layers > 8 || c.tv_layers < 1 || c.lf0_layers < 1 || c.lf0_layers > 4) return v->fail(DEX_ERR_ARG, "layer counts out of range");
-    skey(v, "tiv_encoder.in_conv.conv.weight", {c.tiv_ch, c.n_mels, 3}); skey(v, "tiv_encoder.in_conv.conv.bias", {c.tiv_ch});
+    v->add("tiv_encoder.in_conv.conv.weight", {c.tiv_ch, c.n_mels, 3}); v->add("tiv_encoder.in_conv.conv.bias", {c.tiv_ch});
     for (int i = 0; i < c.tiv_layers; ++i) {
         const std::string p = "tiv_encoder.conv_blocks." + std::to_string(i) + ".conv_block";
-        skey(v, p + ".0.conv.weight", {c.tiv_ch, c.tiv_ch, 3}); skey(v, p + ".0.conv.bias", {c.tiv_ch});
-        skey(v, p + ".1.conv.weight", {c.tiv_ch, c.tiv_ch, 3});
+        v->add(p + ".0.conv.weight", {c.tiv_ch, c.tiv_ch, 3}); v->add(p + ".0.conv.bias", {c.tiv_ch});
+        v->add(p + ".1.conv.weight", {c.tiv_ch, c.tiv_ch, 3});
     }
-    skey(v, "tv_encoder.in_conv.conv.weight", {c.tv_ch, c.n_mels, 3});
-    skey(v, "tv_encoder.in_conv.ln.weight", {c.tv_ch}); skey(v, "tv_encoder.in_conv.ln.bias", {c.tv_ch});
+    v->add("tv_encoder.in_conv.conv.weight", {c.tv_ch, c.n_mels, 3});
+    v->add("tv_encoder.in_conv.ln.weight", {c.tv_ch}); v->add("tv_encoder.in_conv.ln.bias", {c.tv_ch});
     for (int i = 0; i < c.tv_layers; ++i) {
         const std::string p = "tv_encoder.conv_blocks." + std::to_string(i) + ".conv_block";
-        skey(v, p + ".0.conv.weight", {c.tv_ch, c.tv_ch, 3});
-        skey(v, p + ".0.ln.weight", {c.tv_ch}); skey(v, p + ".0.ln.bias", {c.tv_ch});
-        skey(v, p + ".1.conv.weight", {c.tv_ch, c.tv_ch, 3});
+        v->add(p + ".0.conv.weight", {c.tv_ch, c.tv_ch, 3});
+        v->add(p + ".0.ln.weight", {c.tv_ch}); v->add(p + ".0.ln.bias", {c.tv_ch});
+        v->add(p + ".1.conv.weight", {c.tv_ch, c.tv_ch, 3});
     }
-    skey(v, "tv_encoder.out_conv.conv.weight", {c.tv_cout, c.tv_ch, 3});
-    skey(v, "tv_encoder.vq.embedding", {c.tv_n_emb, c.tv_cout});
+    v->add("tv_encoder.out_conv.conv.weight", {c.tv_cout, c.tv_ch, 3});
+    v->add("tv_encoder.vq.embedding", {c.tv_n_emb, c.tv_cout});
     proj_keys(v, "tv_encoder.proj_0", c.tv_cout, c.tv_cout_g);
-    skey(v, "tv_encoder.proj_1.conv.weight", {c.tv_cout_g, c.tv_cout_g, 3}); skey(v, "tv_encoder.proj_1.conv.bias", {c.tv_cout_g});
-    skey(v, "lf0_encoder.in_conv.conv.weight", {c.lf0_ch, 1, 3});
-    skey(v, "lf0_encoder.in_conv.ln.weight", {c.lf0_ch}); skey(v, "lf0_encoder.in_conv.ln.bias", {c.lf0_ch});
+    v->add("tv_encoder.proj_1.conv.weight", {c.tv_cout_g, c.tv_cout_g, 3}); v->add("tv_encoder.proj_1.conv.bias", {c.tv_cout_g});
+    v->add("lf0_encoder.in_conv.conv.weight", {c.lf0_ch, 1, 3});
+    v->add("lf0_encoder.in_conv.ln.weight", {c.lf0_ch}); v->add("lf0_encoder.in_conv.ln.bias", {c.lf0_ch});
     const int H = c.lf0_ch / 2;
     for (int l = 0; l < c.lf0_layers; ++l)
         for (const char* sfx : {"", "_reverse"}) {
             const std::string t = "_l" + std::to_string(l) + sfx;
-            skey(v, "lf0_encoder.rnn_layer.weight_ih" + t, {3 * H, c.lf0_ch}); skey(v, "lf0_encoder.rnn_layer.weight_hh" + t, {3 * H, H});
-            skey(v, "lf0_encoder.rnn_layer.bias_ih" + t, {3 * H}); skey(v, "lf0_encoder.rnn_layer.bias_hh" + t, {3 * H});
+            v->add("lf0_encoder.rnn_layer.weight_ih" + t, {3 * H, c.lf0_ch}); v->add("lf0_encoder.rnn_layer.weight_hh" + t, {3 * H, H});
+            v->add("lf0_encoder.rnn_layer.bias_ih" + t, {3 * H}); v->add("lf0_encoder.rnn_layer.bias_hh" + t, {3 * H});
         }
-    skey(v, "lf0_encoder.out_conv.conv.weight", {c.lf0_cout, c.lf0_ch, 3});
-    skey(v, "lf0_encoder.out_conv.ln.weight", {c.lf0_cout}); skey(v, "lf0_encoder.out_conv.ln.bias", {c.lf0_cout});
+    v->add("lf0_encoder.out_conv.conv.weight", {c.lf0_cout, c.lf0_ch, 3});
+    v->add("lf0_encoder.out_conv.ln.weight", {c.lf0_cout}); v->add("lf0_encoder.out_conv.ln.bias", {c.lf0_cout});
     proj_keys(v, "lf0_encoder.proj", c.lf0_cout, c.lf0_cout_g);
-    skey(v, "conv_sty.weight", {c.sty_out, c.tv_cout_g, 1}); skey(v, "conv_sty.bias", {c.sty_out});
+    v->add("conv_sty.weight", {c.sty_out, c.tv_cout_g, 1}); v->add("conv_sty.bias", {c.sty_out});
     return DEX_OK;
 }
 
-void dex_style_destroy(DexStyle* v) {
-    if (!v) return;
-    for (auto& kv : v->raw) if (kv.second.p) hipFree(kv.second.p);
-    for (void* p : v->owned) hipFree(p);
-    delete v;
-}
+void dex_style_destroy(DexStyle* v) { if (v) { v->release(); delete v; } }
 const char* dex_style_last_error(const DexStyle* v) { return v ? v->err.c_str() : "null style context"; }
 int dex_style_num_weights(const DexStyle* v) { return v ? (int)v->keys.size() : 0; }
-int dex_style_weight_info(const DexStyle* v, int i, const char** key, int64_t shape[4], int* ndim) {
-    if (!v || i < 0 || i >= (int)v->keys.size()) return DEX_ERR_ARG;
-    const SRaw& r = v->raw.at(v->keys[i]);
-    if (key) *key = v->keys[i].c_str();
-    if (ndim) *ndim = (int)r.shape.size();
-    if (shape) for (size_t k = 0; k < r.shape.size(); ++k) shape[k] = r.shape[k];
-    return DEX_OK;
-}
+int dex_style_weight_info(const DexStyle* v, int i, const char** key, int64_t shape[4], int* ndim) { return v ? v->info(i, key, shape, ndim) : DEX_ERR_ARG; }
 int dex_style_load_weight_async(DexStyle* v, const char* key, const float* w_dev, const int64_t* shape, int ndim, dex_stream_t stream) {
-    if (!v || !key || !w_dev) return DEX_ERR_ARG;
-    auto it = v->raw.find(key);
-    if (it == v->raw.end()) return v->fail(DEX_ERR_ARG, "unknown style weight key '%s'", key);
-    SRaw& r = it->second;
-    if ((int)r.shape.size() != ndim) return v->fail(DEX_ERR_ARG, "weight '%s': expected %d dims, got %d", key, (int)r.shape.size(), ndim);
-    for (int k = 0; k < ndim; ++k)
-        if (r.shape[k] != shape[k]) return v->fail(DEX_ERR_ARG, "weight '%s': dim %d is %lld, expected %lld", key, k, (long long)shape[k], (long long)r.shape[k]);
-    if (!r.p) SCHK(v, hipMalloc((void**)&r.p, r.numel * sizeof(float)));
-    SCHK(v, hipMemcpyAsync(r.p, w_dev, r.numel * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    r.loaded = true;
-    v->finalized = false;
-    return DEX_OK;
+    return v ? v->load(key, w_dev, shape, ndim, (hipStream_t)stream, false) : DEX_ERR_ARG;
 }
 
 int dex_style_finalize(DexStyle* v, dex_stream_t stream) {
     if (!v) return DEX_ERR_ARG;
-    for (const auto& k : v->keys)
-        if (!v->raw.at(k).loaded) return v->fail(DEX_ERR_STATE, "style weight '%s' was never loaded", k.c_str());
-    for (void* p : v->owned) hipFree(p);
-    v->owned.clear();
+    if (int rc = v->begin_finalize()) return rc;
     hipStream_t st = (hipStream_t)stream;
     const DexStyleConfig& c = v->cfg;
-    int rc = DEX_OK;
-    auto alloc = [&](long n) -> float* {
-        float* p = nullptr;
-        if (hipMalloc((void**)&p, n * sizeof(float)) != hipSuccess) { rc = v->fail(DEX_ERR_HIP, "hipMalloc of %ld floats failed", n); return nullptr; }
-        v->owned.push_back(p);
-        return p;
-    };
-    // Conv1d [cout][cin][k] -> [(tap*cin_pad + ci)][cout], zero rows for padded input channels
     auto conv = [&](const std::string& wkey, const char* bkey_or_null, int cin, int cout, int k, int cin_pad) {
-        SConv o{}; o.cin = cin_pad; o.cout = cout; o.k = k;
-        const float* src = v->R(wkey);
-        float* t = alloc((long)k * cin * cout);
-        if (t) launch_permute4(src, t, cout, cin, k, 1, 2, 1, 0, 3, st);
-        if (cin_pad == cin) o.w = t;
-        else {
-            float* d = alloc((long)k * cin_pad * cout);
-            if (t && d) {
-                hipMemsetAsync(d, 0, (size_t)k * cin_pad * cout * sizeof(float), st);
-                hipMemcpy2DAsync(d, (size_t)cin_pad * cout * 4, t, (size_t)cin * cout * 4, (size_t)cin * cout * 4, k, hipMemcpyDeviceToDevice, st);
-            }
-            o.w = d;
-        }
-        o.b = bkey_or_null ? v->R(bkey_or_null) : nullptr;
-        return o;
+        return pack_conv1d(*v, wkey, bkey_or_null, cin, cout, k, cin_pad, st);
     };
     auto proj = [&](const std::string& p, int cin, int ch) {
         SProj o{};
@@ -208,8 +135,8 @@ int dex_style_finalize(DexStyle* v, dex_stream_t stream) {
     v->tv_p0 = proj("tv_encoder.proj_0", c.tv_cout, c.tv_cout_g);
     v->tv_p1 = conv("tv_encoder.proj_1.conv.weight", "tv_encoder.proj_1.conv.bias", c.tv_cout_g, c.tv_cout_g, 3, c.tv_cout_g);
     {   // codebook [M][D] -> GEMM operand [D][M]; |e|^2
-        float* et = alloc((long)c.tv_n_emb * c.tv_cout);
-        float* e2 = alloc(c.tv_n_emb);
+        float* et = v->alloc((long)c.tv_n_emb * c.tv_cout);
+        float* e2 = v->alloc(c.tv_n_emb);
         if (et) launch_permute4(v->R("tv_encoder.vq.embedding"), et, c.tv_n_emb, c.tv_cout, 1, 1, 1, 0, 2, 3, st);
         if (e2) launch_row_sumsq(v->R("tv_encoder.vq.embedding"), e2, c.tv_n_emb, c.tv_cout, st);
         v->embT = et; v->e2 = e2;
@@ -221,11 +148,11 @@ int dex_style_finalize(DexStyle* v, dex_stream_t stream) {
     v->gru_wih.clear(); v->gru_bih.clear(); v->gru_whh.clear(); v->gru_bhh.clear();
     for (int l = 0; l < c.lf0_layers; ++l) {
         // input projection of both directions as ONE GEMM: [in][fwd 3H | rev 3H]; recurrent weights [2][3H][H]
-        float* wih = alloc((long)c.lf0_ch * 6 * H); float* bih = alloc(6 * H); float* whh = alloc(2L * 3 * H * H); float* bhh = alloc(6 * H);
+        float* wih = v->alloc((long)c.lf0_ch * 6 * H); float* bih = v->alloc(6 * H); float* whh = v->alloc(2L * 3 * H * H); float* bhh = v->alloc(6 * H);
         for (int d = 0; d < 2; ++d) {
             const std::string t = "_l" + std::to_string(l) + (d ? "_reverse" : "");
             if (wih) {      // [3H][in] -> columns d*3H.. of [in][6H]
-                float* tmp = alloc((long)c.lf0_ch * 3 * H);
+                float* tmp = v->alloc((long)c.lf0_ch * 3 * H);
                 if (tmp) {
                     launch_permute4(v->R("lf0_encoder.rnn_layer.weight_ih" + t), tmp, 3 * H, c.lf0_ch, 1, 1, 1, 0, 2, 3, st);
                     hipMemcpy2DAsync(wih + d * 3 * H, (size_t)6 * H * 4, tmp, (size_t)3 * H * 4, (size_t)3 * H * 4, c.lf0_ch, hipMemcpyDeviceToDevice, st);
@@ -238,9 +165,9 @@ int dex_style_finalize(DexStyle* v, dex_stream_t stream) {
         v->gru_wih.push_back(wih); v->gru_bih.push_back(bih); v->gru_whh.push_back(whh); v->gru_bhh.push_back(bhh);
     }
     v->sty = conv("conv_sty.weight", "conv_sty.bias", c.tv_cout_g, c.sty_out, 1, c.tv_cout_g);
-    if (rc != DEX_OK) return rc;
-    SCHK(v, hipStreamSynchronize(st));
-    SCHK(v, hipGetLastError());
+    if (v->alloc_rc != DEX_OK) return v->alloc_rc;
+    DEX_HIPCHK(v, hipStreamSynchronize(st));
+    DEX_HIPCHK(v, hipGetLastError());
     v->finalized = true;
     return DEX_OK;
 }
@@ -265,7 +192,7 @@ void style_plan(const DexStyle* v, int B, int Tr, int Ts, int Tl, void* ws, SPla
     P.bytes = (off + 255) & ~size_t(255);
 }
 // Conv1d(k, padding k/2) on [B][T][cin] -> [B][T][cout]; act 0 / 2 (ReLU); res added before the mask
-void conv1d(const float* X, int T, int B, const SConv& c, const float* inmask, int act, const float* res, const float* outmask, float* out, hipStream_t st) {
+void conv1d(const float* X, int T, int B, const PackedConv& c, const float* inmask, int act, const float* res, const float* outmask, float* out, hipStream_t st) {
     IGemmP g{};
     g.A = X; g.lda = c.cin; g.a_bstride = (long)T * c.cin;
     g.Hi = 1; g.Wi = T; g.Cin = c.cin;
@@ -381,7 +308,7 @@ int style_encode(DexStyle* v, const DexStyleArgs* a, dex_stream_t stream, float 
     }
     // sty_enc = mean(z_beforeVQ) + mean(lf0_enc)   (tts.py:62)
     launch_add_bcast_cl(P.mean_c, P.mean_a, B, 1, c.tv_cout, st);
-    SCHK(v, hipMemcpyAsync(a->sty_enc_out_dev, P.mean_c, (size_t)B * c.tv_cout * sizeof(float), hipMemcpyDeviceToDevice, st));
+    DEX_HIPCHK(v, hipMemcpyAsync(a->sty_enc_out_dev, P.mean_c, (size_t)B * c.tv_cout * sizeof(float), hipMemcpyDeviceToDevice, st));
     projection(v->tv_p0, P.z, Ts, B, P.ms, P.a, P.y, P.x, st);                                  // proj_0 -> P.x
     conv1d(P.x, Ts, B, v->tv_p1, P.ms, 2, nullptr, P.ms, P.z, st);                              // proj_1 (BN folded) -> relu -> * mask
     launch_add_bcast_cl(P.z, P.mean_b, B, Ts, c.tv_cout_g, st);                                 // + mean lf0_dec (tts.py:65)
@@ -399,7 +326,7 @@ int style_encode(DexStyle* v, const DexStyleArgs* a, dex_stream_t stream, float 
         launch_inorm_cl(P.y, nxt, P.mr, B, Tr, c.tiv_ch, 1e-5f, st);                            // InstanceNorm1D, then the next block's * mask
         std::swap(cur, nxt);
     }
-    SCHK(v, hipGetLastError());
+    DEX_HIPCHK(v, hipGetLastError());
     return DEX_OK;
 }
 }  // namespace

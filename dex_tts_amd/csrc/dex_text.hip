@@ -11,55 +11,27 @@
 // ~150 launches over a few hundred token rows, once per utterance.
 #include <hip/hip_runtime.h>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/dex_amd.h"
 #include "kernels.h"
+#include "weight_store.h"
 
 using namespace dex;
 
 namespace {
-struct TRaw { float* p = nullptr; std::vector<int64_t> shape; long numel = 0; bool loaded = false; };
-struct TConv { const float* w = nullptr; const float* b = nullptr; int cin, cout, k; };      // packed [k*cin][cout], bias or null
 struct TLayer { const float *rln, *fln, *wqkvg, *wout, *wgf, *wfc2; const float *a1sw, *a1sb, *a1bw, *a1bb, *a2sw, *a2sb, *a2bw, *a2bb; };
 constexpr int HP = 128;               // padded head width of the attention operands
 }  // namespace
 
-struct DexText {
+struct DexText : WeightStore {
+    DexText() : WeightStore("text-encoder ") {}
     DexTextConfig cfg{};
-    std::string err;
-    std::vector<std::string> keys;
-    std::map<std::string, TRaw> raw;
-    std::vector<void*> owned;
-    bool finalized = false;
     int E = 0, kd = 0;
-    TConv pre[3], pre_proj, dp1, dp2;
+    PackedConv pre[3], pre_proj, dp1, dp2;
     std::vector<TLayer> layers;
-    int fail(int code, const char* fmt, ...) {
-        char buf[512];
-        va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-        err = buf;
-        return code;
-    }
-    const float* R(const std::string& k) const { return raw.at(k).p; }
 };
-
-#define TCHK(v, call)                                                                                  \
-    do { hipError_t e_ = (call); if (e_ != hipSuccess)                                                 \
-        return (v)->fail(DEX_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
-
-namespace {
-void tkey(DexText* v, const std::string& k, std::vector<int64_t> shape) {
-    v->keys.push_back(k);
-    TRaw r; r.shape = std::move(shape); r.numel = 1;
-    for (auto d : r.shape) r.numel *= d;
-    v->raw[k] = r;
-}
-}  // namespace
 
 extern "C" {
 
@@ -81,95 +53,56 @@ int dex_text_create(const DexTextConfig* cfg, DexText** out) {
     if (c.variant == DEX_VARIANT_DEX && c.n_spks > 1) return v->fail(DEX_ERR_ARG, "the DEX text encoder takes the style vector, not a speaker embedding");
     v->kd = E / c.n_heads;
     const int nc = c.n_channels, F = c.filter_channels, D = c.filter_channels_dp;
-    tkey(v, "emb.weight", {c.n_vocab, nc});
+    v->add("emb.weight", {c.n_vocab, nc});
     for (int i = 0; i < 3; ++i) {
         const std::string s = std::to_string(i);
-        tkey(v, "prenet.conv_layers." + s + ".weight", {nc, nc, 5}); tkey(v, "prenet.conv_layers." + s + ".bias", {nc});
-        tkey(v, "prenet.norm_layers." + s + ".gamma", {nc}); tkey(v, "prenet.norm_layers." + s + ".beta", {nc});
+        v->add("prenet.conv_layers." + s + ".weight", {nc, nc, 5}); v->add("prenet.conv_layers." + s + ".bias", {nc});
+        v->add("prenet.norm_layers." + s + ".gamma", {nc}); v->add("prenet.norm_layers." + s + ".beta", {nc});
     }
-    tkey(v, "prenet.proj.weight", {nc, nc, 1}); tkey(v, "prenet.proj.bias", {nc});
+    v->add("prenet.proj.weight", {nc, nc, 1}); v->add("prenet.proj.bias", {nc});
     for (int i = 0; i < c.n_layers; ++i) {
         const std::string p = "encoder.layers." + std::to_string(i);
-        for (const char* n : {"q_proj", "k_proj", "v_proj", "g_proj", "out_proj"}) tkey(v, p + ".retention." + n + ".weight", {E, E});
-        tkey(v, p + ".retention_layer_norm.weight", {E});
-        tkey(v, p + ".ffn.fc1.weight", {F, E}); tkey(v, p + ".ffn.fc2.weight", {E, F}); tkey(v, p + ".ffn.gate.weight", {F, E});
-        tkey(v, p + ".final_layer_norm.weight", {E});
+        for (const char* n : {"q_proj", "k_proj", "v_proj", "g_proj", "out_proj"}) v->add(p + ".retention." + n + ".weight", {E, E});
+        v->add(p + ".retention_layer_norm.weight", {E});
+        v->add(p + ".ffn.fc1.weight", {F, E}); v->add(p + ".ffn.fc2.weight", {E, F}); v->add(p + ".ffn.gate.weight", {F, E});
+        v->add(p + ".final_layer_norm.weight", {E});
         if (c.variant == DEX_VARIANT_DEX)
             for (const char* a : {"adaln_1", "adaln_2"})
-                for (const char* w : {"W_scale", "W_bias"}) { tkey(v, p + "." + a + "." + w + ".weight", {E, E}); tkey(v, p + "." + a + "." + w + ".bias", {E}); }
+                for (const char* w : {"W_scale", "W_bias"}) { v->add(p + "." + a + "." + w + ".weight", {E, E}); v->add(p + "." + a + "." + w + ".bias", {E}); }
     }
-    tkey(v, "encoder.layer_norm.weight", {E});
-    tkey(v, "encoder.retnet_rel_pos.angle", {v->kd});
-    tkey(v, "proj_m.weight", {c.n_feats, E, 1}); tkey(v, "proj_m.bias", {c.n_feats});
-    tkey(v, "proj_w.conv_1.weight", {D, E, c.kernel_size}); tkey(v, "proj_w.conv_1.bias", {D});
-    tkey(v, "proj_w.norm_1.gamma", {D}); tkey(v, "proj_w.norm_1.beta", {D});
-    tkey(v, "proj_w.conv_2.weight", {D, D, c.kernel_size}); tkey(v, "proj_w.conv_2.bias", {D});
-    tkey(v, "proj_w.norm_2.gamma", {D}); tkey(v, "proj_w.norm_2.beta", {D});
-    tkey(v, "proj_w.proj.weight", {1, D, 1}); tkey(v, "proj_w.proj.bias", {1});
+    v->add("encoder.layer_norm.weight", {E});
+    v->add("encoder.retnet_rel_pos.angle", {v->kd});
+    v->add("proj_m.weight", {c.n_feats, E, 1}); v->add("proj_m.bias", {c.n_feats});
+    v->add("proj_w.conv_1.weight", {D, E, c.kernel_size}); v->add("proj_w.conv_1.bias", {D});
+    v->add("proj_w.norm_1.gamma", {D}); v->add("proj_w.norm_1.beta", {D});
+    v->add("proj_w.conv_2.weight", {D, D, c.kernel_size}); v->add("proj_w.conv_2.bias", {D});
+    v->add("proj_w.norm_2.gamma", {D}); v->add("proj_w.norm_2.beta", {D});
+    v->add("proj_w.proj.weight", {1, D, 1}); v->add("proj_w.proj.bias", {1});
     return DEX_OK;
 }
 
-void dex_text_destroy(DexText* v) {
-    if (!v) return;
-    for (auto& kv : v->raw) if (kv.second.p) hipFree(kv.second.p);
-    for (void* p : v->owned) hipFree(p);
-    delete v;
-}
+void dex_text_destroy(DexText* v) { if (v) { v->release(); delete v; } }
 const char* dex_text_last_error(const DexText* v) { return v ? v->err.c_str() : "null text context"; }
 int dex_text_num_weights(const DexText* v) { return v ? (int)v->keys.size() : 0; }
-int dex_text_weight_info(const DexText* v, int i, const char** key, int64_t shape[4], int* ndim) {
-    if (!v || i < 0 || i >= (int)v->keys.size()) return DEX_ERR_ARG;
-    const TRaw& r = v->raw.at(v->keys[i]);
-    if (key) *key = v->keys[i].c_str();
-    if (ndim) *ndim = (int)r.shape.size();
-    if (shape) for (size_t k = 0; k < r.shape.size(); ++k) shape[k] = r.shape[k];
-    return DEX_OK;
-}
+int dex_text_weight_info(const DexText* v, int i, const char** key, int64_t shape[4], int* ndim) { return v ? v->info(i, key, shape, ndim) : DEX_ERR_ARG; }
 int dex_text_load_weight_async(DexText* v, const char* key, const float* w_dev, const int64_t* shape, int ndim, dex_stream_t stream) {
-    if (!v || !key || !w_dev) return DEX_ERR_ARG;
-    auto it = v->raw.find(key);
-    if (it == v->raw.end()) return v->fail(DEX_ERR_ARG, "unknown text-encoder weight key '%s'", key);
-    TRaw& r = it->second;
-    if ((int)r.shape.size() != ndim) return v->fail(DEX_ERR_ARG, "weight '%s': expected %d dims, got %d", key, (int)r.shape.size(), ndim);
-    for (int k = 0; k < ndim; ++k)
-        if (r.shape[k] != shape[k]) return v->fail(DEX_ERR_ARG, "weight '%s': dim %d is %lld, expected %lld", key, k, (long long)shape[k], (long long)r.shape[k]);
-    if (!r.p) TCHK(v, hipMalloc((void**)&r.p, r.numel * sizeof(float)));
-    TCHK(v, hipMemcpyAsync(r.p, w_dev, r.numel * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    r.loaded = true;
-    v->finalized = false;
-    return DEX_OK;
+    return v ? v->load(key, w_dev, shape, ndim, (hipStream_t)stream, false) : DEX_ERR_ARG;
 }
 
 int dex_text_finalize(DexText* v, dex_stream_t stream) {
     if (!v) return DEX_ERR_ARG;
-    for (const auto& k : v->keys)
-        if (!v->raw.at(k).loaded) return v->fail(DEX_ERR_STATE, "text-encoder weight '%s' was never loaded", k.c_str());
-    for (void* p : v->owned) hipFree(p);
-    v->owned.clear();
+    if (int rc = v->begin_finalize()) return rc;
     hipStream_t st = (hipStream_t)stream;
     const DexTextConfig& c = v->cfg;
     const int E = v->E, F = c.filter_channels;
-    int rc = DEX_OK;
-    auto alloc = [&](long n) -> float* {
-        float* p = nullptr;
-        if (hipMalloc((void**)&p, n * sizeof(float)) != hipSuccess) { rc = v->fail(DEX_ERR_HIP, "hipMalloc of %ld floats failed", n); return nullptr; }
-        v->owned.push_back(p);
-        return p;
-    };
     // Conv1d / Linear weight [cout][cin][k] -> GEMM operand [(tap*cin + ci)][cout]
-    auto conv = [&](const std::string& wkey, const char* bkey, int cin, int cout, int k) {
-        TConv o{}; o.cin = cin; o.cout = cout; o.k = k;
-        float* t = alloc((long)k * cin * cout);
-        if (t) launch_permute4(v->R(wkey), t, cout, cin, k, 1, 2, 1, 0, 3, st);
-        o.w = t; o.b = bkey ? v->R(bkey) : nullptr;
-        return o;
-    };
+    auto conv = [&](const std::string& wkey, const char* bkey, int cin, int cout, int k) { return pack_conv1d(*v, wkey, bkey, cin, cout, k, cin, st); };
     // several Linear weights [n_i][K] side by side as one operand [K][sum n_i]
     auto concat_t = [&](std::vector<std::string> ks, int K, int n_each) -> const float* {
         const int N = n_each * (int)ks.size();
-        float* d = alloc((long)K * N);
+        float* d = v->alloc((long)K * N);
         for (size_t j = 0; j < ks.size(); ++j) {
-            float* tmp = alloc((long)K * n_each);
+            float* tmp = v->alloc((long)K * n_each);
             if (d && tmp) {
                 launch_permute4(v->R(ks[j]), tmp, n_each, K, 1, 1, 1, 0, 2, 3, st);
                 hipMemcpy2DAsync(d + j * n_each, (size_t)N * 4, tmp, (size_t)n_each * 4, (size_t)n_each * 4, K, hipMemcpyDeviceToDevice, st);
@@ -201,9 +134,9 @@ int dex_text_finalize(DexText* v, dex_stream_t stream) {
     }
     v->dp1 = conv("proj_w.conv_1.weight", "proj_w.conv_1.bias", E, c.filter_channels_dp, c.kernel_size);
     v->dp2 = conv("proj_w.conv_2.weight", "proj_w.conv_2.bias", c.filter_channels_dp, c.filter_channels_dp, c.kernel_size);
-    if (rc != DEX_OK) return rc;
-    TCHK(v, hipStreamSynchronize(st));
-    TCHK(v, hipGetLastError());
+    if (v->alloc_rc != DEX_OK) return v->alloc_rc;
+    DEX_HIPCHK(v, hipStreamSynchronize(st));
+    DEX_HIPCHK(v, hipGetLastError());
     v->finalized = true;
     return DEX_OK;
 }
@@ -229,7 +162,7 @@ void text_plan(const DexText* v, int B, int T, void* ws, TPlan& P) {
     P.bytes = (off + 255) & ~size_t(255);
 }
 // Conv1d(k, padding k/2) / Linear (k = 1) on [B][T][lda] -> [B][T][ldc]; act 0 / 2 (ReLU); res added before the mask
-void conv1d(const float* X, int lda, int T, int B, const TConv& c, const float* inmask, int act, const float* res, int ldres, const float* outmask,
+void conv1d(const float* X, int lda, int T, int B, const PackedConv& c, const float* inmask, int act, const float* res, int ldres, const float* outmask,
             float* out, int ldc, hipStream_t st) {
     IGemmP g{};
     g.A = X; g.lda = lda; g.a_bstride = (long)T * lda;
@@ -246,7 +179,7 @@ void conv1d(const float* X, int lda, int T, int B, const TConv& c, const float* 
     launch_igemm(g, PREC_FP32, st);
 }
 void linear(const float* X, int lda, int T, int B, const float* W, int K, int N, const float* res, int ldres, float* out, int ldc, hipStream_t st) {
-    TConv c{W, nullptr, K, N, 1};
+    PackedConv c{W, nullptr, K, N, 1};
     conv1d(X, lda, T, B, c, nullptr, 0, res, ldres, nullptr, out, ldc, st);
 }
 void row_norm(const float* X, int ldx, float* Y, int ldy, long rows, int C, int mode, const float* g, const float* b, float eps, int relu,
@@ -348,7 +281,7 @@ int dex_text_encode(DexText* v, const DexTextArgs* a, dex_stream_t stream) {
     launch_small_linear(pw, st);
     launch_cl_to_cf_mask(P.logw, 1, P.mask, a->logw_out_dev, B, T, 1, st);                         // [B][1][T] == [B][T], * mask
     launch_durations(a->logw_out_dev, P.mask, a->length_scale, a->w_ceil_out_dev, P.cum, a->y_lengths_out_dev, B, T, st);
-    TCHK(v, hipGetLastError());
+    DEX_HIPCHK(v, hipGetLastError());
     return DEX_OK;
 }
 
@@ -363,7 +296,7 @@ int dex_text_align(DexText* v, const DexAlignArgs* a, dex_stream_t stream) {
     launch_cumsum_rows(a->w_ceil_dev, cum, a->B, a->T, st);
     AlignP p{a->mu_x_dev, cum, a->x_lengths_dev, a->y_lengths_dev, a->B, a->T, a->Ty, v->cfg.n_feats, a->mu_y_out_dev, a->y_mask_out_dev, a->attn_out_dev};
     launch_align(p, st);
-    TCHK(v, hipGetLastError());
+    DEX_HIPCHK(v, hipGetLastError());
     return DEX_OK;
 }
 

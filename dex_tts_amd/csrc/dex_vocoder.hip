@@ -19,32 +19,25 @@
 // its anti-aliased activations on the lane-packed aa_snake; those kernels stay fp32 in the bf16 / fp16 modes.  Every other width
 // takes the implicit GEMM as before.
 #include <hip/hip_runtime.h>
-#include <cstdarg>
-#include <cstdio>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/dex_amd.h"
 #include "kernels.h"
+#include "weight_store.h"
 
 using namespace dex;
 
 namespace {
-struct VRaw { float* p = nullptr; std::vector<int64_t> shape; long numel = 0; bool loaded = false; };
 // (wlp: the same matrix as bf16 [0] / fp16 [1], [N][K] with K contiguous - the reduced-precision GEMM's weight operand)
 struct VConv { const float* w = nullptr; const float* b = nullptr; int cin, cout, k, dil; const void* wlp[2] = {nullptr, nullptr}; bool narrow = false; };  // packed [k*cin][cout]
 struct VUp { const float* w = nullptr; const float* b = nullptr; int cin, cout, k, u, pad; const void* wlp[2] = {nullptr, nullptr}; bool narrow = false; };   // packed [cin][k*cout]
 constexpr int MEL_LD = 96;          // num_mels padded to a multiple of 32 (K tiles of the implicit GEMM do not straddle taps)
 }  // namespace
 
-struct DexVoc {
+struct DexVoc : WeightStore {
+    DexVoc() : WeightStore("vocoder ") {}
     DexVocoderConfig cfg{};
-    std::string err;
-    std::vector<std::string> keys;
-    std::map<std::string, VRaw> raw;
-    std::vector<void*> owned;
-    bool finalized = false;
     int precision = DEX_PREC_FP32;      // DEX_PREC_BF16 / DEX_PREC_FP16: the convolutions' operands (fp32 accumulation, fp32 activations in HBM)
     VConv pre;
     std::vector<VUp> ups;
@@ -54,25 +47,9 @@ struct DexVoc {
     std::vector<const float*> act_a, act_ib;
     const float* filt = nullptr;
     bool big() const { return cfg.activation != 0; }
-    int fail(int code, const char* fmt, ...) {
-        char buf[512];
-        va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-        err = buf;
-        return code;
-    }
 };
 
-#define VCHK(v, call)                                                                                  \
-    do { hipError_t e_ = (call); if (e_ != hipSuccess)                                                 \
-        return (v)->fail(DEX_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
-
 namespace {
-void vkey(DexVoc* v, const std::string& k, std::vector<int64_t> shape) {
-    v->keys.push_back(k);
-    VRaw r; r.shape = std::move(shape); r.numel = 1;
-    for (auto d : r.shape) r.numel *= d;
-    v->raw[k] = r;
-}
 int stage_ch(const DexVocoderConfig& c, int i) { return c.upsample_initial_channel >> (i + 1); }
 long total_up(const DexVocoderConfig& c) { long u = 1; for (int i = 0; i < c.n_upsamples; ++i) u *= c.upsample_rates[i]; return u; }
 }  // namespace
@@ -103,11 +80,11 @@ int dex_voc_create(const DexVocoderConfig* cfg, DexVoc** out) {
     const bool big = c.activation != 0, beta = c.activation == 2;
     const std::string upsfx = big ? ".0" : "";                      // BigVGAN nests each transposed conv in a ModuleList
     const int c0 = c.upsample_initial_channel;
-    vkey(v, "conv_pre.weight", {c0, c.num_mels, 7}); vkey(v, "conv_pre.bias", {c0});
+    v->add("conv_pre.weight", {c0, c.num_mels, 7}); v->add("conv_pre.bias", {c0});
     for (int i = 0; i < c.n_upsamples; ++i) {
         const int ci = c0 >> i, co = c0 >> (i + 1);
-        vkey(v, "ups." + std::to_string(i) + upsfx + ".weight", {ci, co, c.upsample_kernel_sizes[i]});      // ConvTranspose1d: [in, out, k]
-        vkey(v, "ups." + std::to_string(i) + upsfx + ".bias", {co});
+        v->add("ups." + std::to_string(i) + upsfx + ".weight", {ci, co, c.upsample_kernel_sizes[i]});      // ConvTranspose1d: [in, out, k]
+        v->add("ups." + std::to_string(i) + upsfx + ".bias", {co});
     }
     for (int i = 0; i < c.n_upsamples; ++i)
         for (int j = 0; j < 3; ++j) {
@@ -115,75 +92,42 @@ int dex_voc_create(const DexVocoderConfig* cfg, DexVoc** out) {
             const std::string p = "resblocks." + std::to_string(i * 3 + j);
             for (const char* cs : {".convs1.", ".convs2."})
                 for (int m = 0; m < 3; ++m) {
-                    vkey(v, p + cs + std::to_string(m) + ".weight", {ch, ch, k});
-                    vkey(v, p + cs + std::to_string(m) + ".bias", {ch});
+                    v->add(p + cs + std::to_string(m) + ".weight", {ch, ch, k});
+                    v->add(p + cs + std::to_string(m) + ".bias", {ch});
                 }
             if (big)
                 for (int l = 0; l < 6; ++l) {
-                    vkey(v, p + ".activations." + std::to_string(l) + ".act.alpha", {ch});
-                    if (beta) vkey(v, p + ".activations." + std::to_string(l) + ".act.beta", {ch});
+                    v->add(p + ".activations." + std::to_string(l) + ".act.alpha", {ch});
+                    if (beta) v->add(p + ".activations." + std::to_string(l) + ".act.beta", {ch});
                 }
         }
     if (big) {
         const int cl = stage_ch(c, c.n_upsamples - 1);
-        vkey(v, "activation_post.act.alpha", {cl});
-        if (beta) vkey(v, "activation_post.act.beta", {cl});
-        vkey(v, "activation_post.upsample.filter", {1, 1, 12}); vkey(v, "activation_post.downsample.lowpass.filter", {1, 1, 12});
+        v->add("activation_post.act.alpha", {cl});
+        if (beta) v->add("activation_post.act.beta", {cl});
+        v->add("activation_post.upsample.filter", {1, 1, 12}); v->add("activation_post.downsample.lowpass.filter", {1, 1, 12});
     }
-    vkey(v, "conv_post.weight", {1, stage_ch(c, c.n_upsamples - 1), 7}); vkey(v, "conv_post.bias", {1});
+    v->add("conv_post.weight", {1, stage_ch(c, c.n_upsamples - 1), 7}); v->add("conv_post.bias", {1});
     return DEX_OK;
 }
 
-void dex_voc_destroy(DexVoc* v) {
-    if (!v) return;
-    for (auto& kv : v->raw) if (kv.second.p) hipFree(kv.second.p);
-    for (void* p : v->owned) hipFree(p);
-    delete v;
-}
+void dex_voc_destroy(DexVoc* v) { if (v) { v->release(); delete v; } }
 const char* dex_voc_last_error(const DexVoc* v) { return v ? v->err.c_str() : "null vocoder context"; }
 int dex_voc_num_weights(const DexVoc* v) { return v ? (int)v->keys.size() : 0; }
-int dex_voc_weight_info(const DexVoc* v, int i, const char** key, int64_t shape[4], int* ndim) {
-    if (!v || i < 0 || i >= (int)v->keys.size()) return DEX_ERR_ARG;
-    const VRaw& r = v->raw.at(v->keys[i]);
-    if (key) *key = v->keys[i].c_str();
-    if (ndim) *ndim = (int)r.shape.size();
-    if (shape) for (size_t k = 0; k < r.shape.size(); ++k) shape[k] = r.shape[k];
-    return DEX_OK;
-}
+int dex_voc_weight_info(const DexVoc* v, int i, const char** key, int64_t shape[4], int* ndim) { return v ? v->info(i, key, shape, ndim) : DEX_ERR_ARG; }
 int dex_voc_load_weight_async(DexVoc* v, const char* key, const float* w_dev, const int64_t* shape, int ndim, dex_stream_t stream) {
-    if (!v || !key || !w_dev) return DEX_ERR_ARG;
-    auto it = v->raw.find(key);
-    if (it == v->raw.end()) return v->fail(DEX_ERR_ARG, "unknown vocoder weight key '%s'", key);
-    VRaw& r = it->second;
-    if ((int)r.shape.size() != ndim) return v->fail(DEX_ERR_ARG, "weight '%s': expected %d dims, got %d", key, (int)r.shape.size(), ndim);
-    for (int k = 0; k < ndim; ++k)
-        if (r.shape[k] != shape[k]) return v->fail(DEX_ERR_ARG, "weight '%s': dim %d is %lld, expected %lld", key, k, (long long)shape[k], (long long)r.shape[k]);
-    if (!r.p) VCHK(v, hipMalloc((void**)&r.p, r.numel * sizeof(float)));
-    VCHK(v, hipMemcpyAsync(r.p, w_dev, r.numel * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    r.loaded = true;
-    v->finalized = false;
-    return DEX_OK;
+    return v ? v->load(key, w_dev, shape, ndim, (hipStream_t)stream, false) : DEX_ERR_ARG;
 }
 
 int dex_voc_finalize(DexVoc* v, dex_stream_t stream) {
     if (!v) return DEX_ERR_ARG;
-    for (const auto& k : v->keys)
-        if (!v->raw.at(k).loaded) return v->fail(DEX_ERR_STATE, "vocoder weight '%s' was never loaded", k.c_str());
-    for (void* p : v->owned) hipFree(p);
-    v->owned.clear();
+    if (int rc = v->begin_finalize()) return rc;
     hipStream_t st = (hipStream_t)stream;
     const DexVocoderConfig& c = v->cfg;
-    int rc = DEX_OK;
-    auto alloc = [&](long n) -> float* {
-        float* p = nullptr;
-        if (hipMalloc((void**)&p, n * sizeof(float)) != hipSuccess) { rc = v->fail(DEX_ERR_HIP, "hipMalloc of %ld floats failed", n); return nullptr; }
-        v->owned.push_back(p);
-        return p;
-    };
     // reduced-precision copies of a packed fp32 [K][N] matrix: bf16 and fp16, [N][K]
     auto lp_copies = [&](const float* w, int K, int N, const void* (&out)[2]) {
         for (int t = 0; t < 2; ++t) {
-            void* d = alloc(((long)K * N + 1) / 2);
+            void* d = v->alloc(((long)K * N + 1) / 2);
             if (d) launch_pack_lp_nk(w, d, K, N, t ? DEX_PREC_FP16 : DEX_PREC_BF16, st);
             out[t] = d;
         }
@@ -191,22 +135,8 @@ int dex_voc_finalize(DexVoc* v, dex_stream_t stream) {
     // Conv1d [Cout][Cin][k] -> [(tap*Cin_pad + ci)][Cout]
     auto conv = [&](const std::string& name, int cin, int cout, int k, int dil, int cin_pad) {
         VConv o{}; o.cin = cin_pad; o.cout = cout; o.k = k; o.dil = dil; o.narrow = voc_narrow_width(cout);
-        const float* src = v->raw.at(name + ".weight").p;
-        if (cin_pad == cin) {
-            float* d = alloc((long)k * cin * cout);
-            if (d) launch_permute4(src, d, cout, cin, k, 1, 2, 1, 0, 3, st);      // [o][i][k][1] -> [k][i][o][1]
-            o.w = d;
-        } else {        // zero rows for the padded input channels
-            float* t = alloc((long)k * cin * cout);
-            float* d = alloc((long)k * cin_pad * cout);
-            if (t && d) {
-                launch_permute4(src, t, cout, cin, k, 1, 2, 1, 0, 3, st);
-                hipMemsetAsync(d, 0, (size_t)k * cin_pad * cout * sizeof(float), st);
-                hipMemcpy2DAsync(d, (size_t)cin_pad * cout * 4, t, (size_t)cin * cout * 4, (size_t)cin * cout * 4, k, hipMemcpyDeviceToDevice, st);
-            }
-            o.w = d;
-        }
-        o.b = v->raw.at(name + ".bias").p;
+        o.w = conv1d_operand(*v, v->R(name + ".weight"), cin, cout, k, cin_pad, st);
+        o.b = v->R(name + ".bias");
         if (o.w && !o.narrow) lp_copies(o.w, k * cin_pad, cout, o.wlp);      // (the narrow kernels read fp32 weights in every mode)
         return o;
     };
@@ -215,10 +145,10 @@ int dex_voc_finalize(DexVoc* v, dex_stream_t stream) {
     for (int i = 0; i < c.n_upsamples; ++i) {
         const int ci = c.upsample_initial_channel >> i, co = stage_ch(c, i), k = c.upsample_kernel_sizes[i], u = c.upsample_rates[i];
         VUp up{}; up.cin = ci; up.cout = co; up.k = k; up.u = u; up.pad = (k - u) / 2; up.narrow = voc_narrow_width(co);
-        float* d = alloc((long)ci * k * co);
+        float* d = v->alloc((long)ci * k * co);
         const std::string upn = "ups." + std::to_string(i) + (v->big() ? ".0" : "");
-        if (d) launch_permute4(v->raw.at(upn + ".weight").p, d, ci, co, k, 1, 0, 2, 1, 3, st);   // [ci][co][k] -> [ci][k][co]
-        up.w = d; up.b = v->raw.at(upn + ".bias").p;
+        if (d) launch_permute4(v->R(upn + ".weight"), d, ci, co, k, 1, 0, 2, 1, 3, st);   // [ci][co][k] -> [ci][k][co]
+        up.w = d; up.b = v->R(upn + ".bias");
         if (d && !up.narrow) lp_copies(d, ci, k * co, up.wlp);
         v->ups.push_back(up);
         for (int j = 0; j < 3; ++j) {
@@ -233,8 +163,8 @@ int dex_voc_finalize(DexVoc* v, dex_stream_t stream) {
     if (v->big()) {
         const bool beta = c.activation == 2;
         auto coeffs = [&](const std::string& p, int ch) {
-            float* a = alloc(ch); float* ib = alloc(ch);
-            if (a && ib) launch_snake_coeffs(v->raw.at(p + ".alpha").p, v->raw.at(p + (beta ? ".beta" : ".alpha")).p, a, ib, ch, c.snake_logscale, st);
+            float* a = v->alloc(ch); float* ib = v->alloc(ch);
+            if (a && ib) launch_snake_coeffs(v->R(p + ".alpha"), v->R(p + (beta ? ".beta" : ".alpha")), a, ib, ch, c.snake_logscale, st);
             v->act_a.push_back(a); v->act_ib.push_back(ib);
         };
         for (int i = 0; i < c.n_upsamples; ++i)
@@ -242,17 +172,17 @@ int dex_voc_finalize(DexVoc* v, dex_stream_t stream) {
                 for (int l = 0; l < 6; ++l)
                     coeffs("resblocks." + std::to_string(i * 3 + j) + ".activations." + std::to_string(l) + ".act", stage_ch(c, i));
         coeffs("activation_post.act", stage_ch(c, c.n_upsamples - 1));
-        v->filt = v->raw.at("activation_post.upsample.filter").p;      // (the host checks that every resampling filter of the checkpoint equals it)
+        v->filt = v->R("activation_post.upsample.filter");      // (the host checks that every resampling filter of the checkpoint equals it)
     }
     {   // conv_post [1][C][7] -> [tap][c]
         const int cl = stage_ch(c, c.n_upsamples - 1);
-        float* d = alloc(7L * cl);
-        if (d) launch_permute4(v->raw.at("conv_post.weight").p, d, 1, cl, 7, 1, 0, 2, 1, 3, st);
-        v->post_w = d; v->post_b = v->raw.at("conv_post.bias").p;
+        float* d = v->alloc(7L * cl);
+        if (d) launch_permute4(v->R("conv_post.weight"), d, 1, cl, 7, 1, 0, 2, 1, 3, st);
+        v->post_w = d; v->post_b = v->R("conv_post.bias");
     }
-    if (rc != DEX_OK) return rc;
-    VCHK(v, hipStreamSynchronize(st));
-    VCHK(v, hipGetLastError());
+    if (v->alloc_rc != DEX_OK) return v->alloc_rc;
+    DEX_HIPCHK(v, hipStreamSynchronize(st));
+    DEX_HIPCHK(v, hipGetLastError());
     v->finalized = true;
     return DEX_OK;
 }
@@ -392,7 +322,7 @@ int dex_vocode(DexVoc* v, const float* mel_dev, int B, int T, float* wav_dev, vo
     }
     ConvPostP cp{xin, v->post_w, v->post_b, wav_dev, (int)L, stage_ch(c, c.n_upsamples - 1), B, v->big() ? 1.f : 0.01f};
     launch_conv_post_tanh(cp, st);
-    VCHK(v, hipGetLastError());
+    DEX_HIPCHK(v, hipGetLastError());
     return DEX_OK;
 }
 

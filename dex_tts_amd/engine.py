@@ -8,6 +8,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import _lib
+from ._native import stream
 from .config import ScoreNetConfig, param_shapes
 
 
@@ -86,9 +87,6 @@ class ScoreNetEngine:
         except Exception:
             pass
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def set_precision(self, name: str):
         self._check(self.lib.dex_ctx_set_precision(self.h, _lib.PRECISION[name]))
 
@@ -98,7 +96,7 @@ class ScoreNetEngine:
             # every copy is enqueued on torch's CURRENT stream, i.e. behind the .to()/.contiguous() kernels that may have
             # produced the staging tensor on it; dex_ctx_finalize packs on the same stream and waits for it on the host,
             # so the packed weights are complete for sampler calls on any stream afterwards
-            st = self._stream()
+            st = stream(self.device)
             staged = []
             for key, shape in self.shapes.items():
                 if key not in weights:
@@ -265,14 +263,14 @@ class ScoreNetEngine:
                 if deferred:
                     self.status(wait=True)         # the previous call's verdict (its event has long passed; raises if that call lost a hand-off)
                 for attempt in (0, 1):
-                    self._check(self.lib.dex_sample(self.h, C.byref(a), self._stream()))
+                    self._check(self.lib.dex_sample(self.h, C.byref(a), stream(self.device)))
                     # calls that used in-launch hand-offs (small grids: the cluster form of the DiT block) are checked: a lost hand-off
                     # poisons the outputs with NaN, and a NaN mel must not leave silently.  Deferred: the check rides the
                     # stream behind the call; sync: dex_call_status waits (it returns at once for calls that used no hand-offs).
                     if deferred:
-                        self._check(self.lib.dex_call_status_begin(self.h, self._stream()))
+                        self._check(self.lib.dex_call_status_begin(self.h, stream(self.device)))
                         break
-                    rc = self.lib.dex_call_status(self.h, self._stream()) if self.check_handoffs else 0
+                    rc = self.lib.dex_call_status(self.h, stream(self.device)) if self.check_handoffs else 0
                     if rc == 0:
                         break
                     if attempt == 0 and rc == _lib.DEX_ERR_HANDOFF_XCD:
@@ -298,7 +296,7 @@ class ScoreNetEngine:
             d = _lib.DexDenoiseArgs()
             keep = self._fill_args(d.s, mu, mask, sig, out, 1, spk, ref, sty, sty_lengths, False)
             d.x_dev = x.data_ptr()
-            self._check(self.lib.dex_denoise_once(self.h, C.byref(d), self._stream()))
+            self._check(self.lib.dex_denoise_once(self.h, C.byref(d), stream(self.device)))
             self._keep = keep + [x]
             return out
 
@@ -312,7 +310,7 @@ class ScoreNetEngine:
                 nd = C.c_int()
                 self._check(self.lib.dex_tap_info(self.h, name, shp, C.byref(nd)))
                 t = torch.empty(int(shp[0]), int(shp[1]), dtype=torch.float32, device=self.device)
-                self._check(self.lib.dex_tap_copy(self.h, name, C.c_void_p(t.data_ptr()), t.numel() * 4, self._stream()))
+                self._check(self.lib.dex_tap_copy(self.h, name, C.c_void_p(t.data_ptr()), t.numel() * 4, stream(self.device)))
                 out[name.decode()] = t
             torch.cuda.synchronize(self.device)
         return out
@@ -333,7 +331,7 @@ class ScoreNetEngine:
     def handoff_timeouts(self) -> int:
         """Debug: did a workgroup hand-off of the last sample / denoise_once call time out (cluster form of the DiT row chain)?"""
         with torch.cuda.device(self.device):
-            return int(self.lib.dex_debug_handoff_timeouts(self.h, self._stream()))
+            return int(self.lib.dex_debug_handoff_timeouts(self.h, stream(self.device)))
 
     def xcd_local(self) -> int:
         """Debug: 1 if this device deals workgroup b to XCD b % 8 (the cluster row chain then keeps its hand-offs inside one L2)."""
@@ -347,6 +345,6 @@ class ScoreNetEngine:
             frames = self.lib.dex_mel_frames(n)
             mel = torch.empty(80, frames, dtype=torch.float32, device=self.device)
             energy = torch.empty(frames, dtype=torch.float32, device=self.device)
-            self._check(self.lib.dex_mel_from_wav(self.h, wav.data_ptr(), n, mel.data_ptr(), energy.data_ptr(), self._stream()))
+            self._check(self.lib.dex_mel_from_wav(self.h, wav.data_ptr(), n, mel.data_ptr(), energy.data_ptr(), stream(self.device)))
             self._keep = [wav]
             return mel, energy

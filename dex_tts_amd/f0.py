@@ -11,42 +11,15 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._native import check, device_rows, i32_ptr, stream
 from .audio import TacotronSTFT, lf0_from_f0
 
 SR = 22050
 HOP = 256
 
 
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _opts(fs, frame_period, f0_floor=71.0, f0_ceil=800.0, channels_in_octave=2.0, allowed_range=0.1):
     return _lib.DexF0Opts(float(fs), float(frame_period), float(f0_floor), float(f0_ceil), float(channels_in_octave), float(allowed_range))
-
-
-def _rows(x, lengths):
-    """x [L] or [B, L] (device) -> (fp32 [B, L] on the device, host int32 lengths, one-row flag)."""
-    if not torch.is_tensor(x) or not x.is_cuda:
-        raise RuntimeError("the f0 tracker runs on an MI355X only (no CPU path): pass a CUDA tensor")
-    one = x.dim() == 1
-    x = x.reshape(1, -1) if one else x
-    if x.dim() != 2 or x.shape[1] < 1:
-        raise ValueError("x must be [L] or [B, L]")
-    B, L = x.shape
-    ln = np.full(B, L, dtype=np.int32) if lengths is None else np.asarray(torch.as_tensor(lengths).cpu(), dtype=np.int32).reshape(-1)
-    if ln.shape != (B,) or (ln < 1).any() or (ln > L).any():
-        raise ValueError(f"lengths must hold B = {B} values in [1, {L}]")
-    return x.to(torch.float32).contiguous(), np.ascontiguousarray(ln), one
-
-
-def _lens_ptr(ln):
-    return ln.ctypes.data_as(C.POINTER(C.c_int32))
-
-
-def _check(rc, what):
-    if rc != _lib.DEX_OK:
-        raise (ValueError if rc == -1 else RuntimeError)(f"{what} failed ({rc})")
 
 
 def frames(n_samples, fs=SR, frame_period=HOP / SR * 1000.0):
@@ -60,19 +33,19 @@ def dio(x, fs, f0_floor=71.0, f0_ceil=800.0, channels_in_octave=2.0, frame_perio
     if speed != 1:
         raise ValueError("only speed = 1 is built (DIO's decimation is not)")
     lib = _lib.load()
-    x, ln, one = _rows(x, lengths)
+    x, ln, one = device_rows(x, lengths)
     B, L = x.shape
     o = _opts(fs, frame_period, f0_floor, f0_ceil, channels_in_octave, allowed_range)
     F = lib.dex_f0_frames(L, C.byref(o))
-    _check(F if F < 0 else 0, "dex_f0_frames")
-    need = int(lib.dex_f0_workspace_bytes(B, _lens_ptr(ln), C.byref(o)))
+    check(F if F < 0 else 0, "dex_f0_frames")
+    need = int(lib.dex_f0_workspace_bytes(B, i32_ptr(ln), C.byref(o)))
     if need == 0:
         raise ValueError("dex_f0_workspace_bytes rejected the arguments")
     with torch.cuda.device(x.device):
         ws = torch.empty(need, dtype=torch.uint8, device=x.device)
         f0 = torch.empty(B, F, dtype=torch.float64, device=x.device)
-        _check(lib.dex_f0_dio(x.data_ptr(), _lens_ptr(ln), B, L, C.byref(o), f0.data_ptr(), ws.data_ptr(), need, _stream(x.device)),
-               "dex_f0_dio")
+        check(lib.dex_f0_dio(x.data_ptr(), i32_ptr(ln), B, L, C.byref(o), f0.data_ptr(), ws.data_ptr(), need, stream(x.device)),
+              "dex_f0_dio")
     t = torch.from_numpy(np.arange(F) * float(frame_period) / 1000.0).to(x.device)    # the contract's t_i, rounded as on the host
     return (f0[0] if one else f0), t
 
@@ -81,7 +54,7 @@ def stonemask(x, f0, t, fs, lengths=None, frame_period=None):
     """pw.stonemask on the device: x as for ``dio``, f0 [F] / [B, F] from ``dio``, t its frame times (i * frame_period / 1000;
     frame_period is taken from t unless given) -> refined f0 of f0's shape, float64."""
     lib = _lib.load()
-    x, ln, one = _rows(x, lengths)
+    x, ln, one = device_rows(x, lengths)
     B, L = x.shape
     t = torch.as_tensor(t, dtype=torch.float64).cpu().reshape(-1)
     if frame_period is None:
@@ -92,26 +65,26 @@ def stonemask(x, f0, t, fs, lengths=None, frame_period=None):
         raise ValueError("t must be the uniform frame times i * frame_period / 1000 that dio returns")
     o = _opts(fs, frame_period)
     F = lib.dex_f0_frames(L, C.byref(o))
-    _check(F if F < 0 else 0, "dex_f0_frames")
+    check(F if F < 0 else 0, "dex_f0_frames")
     f0 = torch.as_tensor(f0)
     f0 = (f0.reshape(1, -1) if f0.dim() == 1 else f0).to(device=x.device, dtype=torch.float64).contiguous()
     if f0.shape != (B, F):
         raise ValueError(f"f0 must be [{B}, {F}] for {L} samples, got {tuple(f0.shape)}")
     with torch.cuda.device(x.device):
         out = torch.empty_like(f0)
-        _check(lib.dex_f0_stonemask(x.data_ptr(), _lens_ptr(ln), B, L, C.byref(o), f0.data_ptr(), out.data_ptr(), None, 0,
-                                    _stream(x.device)), "dex_f0_stonemask")
+        check(lib.dex_f0_stonemask(x.data_ptr(), i32_ptr(ln), B, L, C.byref(o), f0.data_ptr(), out.data_ptr(), None, 0,
+                                   stream(x.device)), "dex_f0_stonemask")
     return out[0] if one else out
 
 
 def peak_normalize(x, lengths=None):
     """synthesize.py:46 ``wav / max(abs(wav))`` per row, in fp64 on the device, rounded to fp32 (0 past a row's length)."""
     lib = _lib.load()
-    x, ln, one = _rows(x, lengths)
+    x, ln, one = device_rows(x, lengths)
     B, L = x.shape
     with torch.cuda.device(x.device):
         out = torch.empty_like(x)
-        _check(lib.dex_f0_peak_normalize(x.data_ptr(), _lens_ptr(ln), B, L, out.data_ptr(), _stream(x.device)), "dex_f0_peak_normalize")
+        check(lib.dex_f0_peak_normalize(x.data_ptr(), i32_ptr(ln), B, L, out.data_ptr(), stream(x.device)), "dex_f0_peak_normalize")
     return out[0] if one else out
 
 
@@ -133,11 +106,11 @@ def reference_features(wav, lengths=None, sr=SR, stft: TacotronSTFT = None):
     dex_tts_amd.wavprep.preprocess_wav does the trim and the resampler too."""
     if sr != SR:
         raise ValueError(f"reference_features needs {SR} Hz audio (there is no resampler), got {sr}")
-    x, ln, _ = _rows(wav, lengths)
-    return _features(peak_normalize(x, ln), ln, stft)
+    x, ln, _ = device_rows(wav, lengths)
+    return features(peak_normalize(x, ln), ln, stft)
 
 
-def _features(xn, ln, stft: TacotronSTFT = None):
+def features(xn, ln, stft: TacotronSTFT = None):
     """The mel / f0 / lf0 tail of preprocess_wav (synthesize.py:47-60) on peak-normalised fp32 rows xn [B, L] (a CUDA tensor) of host
     int32 lengths ln -> the dict reference_features returns."""
     B, L = xn.shape

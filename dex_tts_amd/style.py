@@ -12,12 +12,12 @@ codebook).  The arithmetic runs in libdexamd.so (``dex_style_encode``); no CPU p
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Tuple
+from typing import Dict
 
 import torch
-import torch.nn as nn
 
 from . import _lib
+from ._native import NativeModule, stream
 
 VCTK = dict(tv_encoder=dict(c_in=80, num_layer=6, c_h=128, c_out=192, c_out_g=192, commit_w=0.25, n_emb=512),
             lf0_encoder=dict(c_in=1, c_h=192, c_out=192, c_out_g=192, num_layer=2),
@@ -92,79 +92,23 @@ def fold_batchnorm(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return out
 
 
-class StyleEncoders(nn.Module):
+class StyleEncoders(NativeModule):
+    """``load_state_dict`` accepts the four sub-dicts of a DeXTTS checkpoint (keys tv_encoder.* / lf0_encoder.* / tiv_encoder.* /
+    conv_sty.*; other keys are ignored unless ``strict``)."""
+    prefix, noun = "dex_style", "style"
+
     def __init__(self, cfg=None):
         super().__init__()
         self.cfg = dict(VCTK) if cfg is None else cfg
-        self.shapes = param_shapes(self.cfg)
-        for key, shape in self.shapes.items():
-            dt = torch.int64 if key.endswith("num_batches_tracked") else torch.float32
-            self.register_buffer(key.replace(".", "__"), torch.zeros(shape, dtype=dt), persistent=False)
-        self._ctx = None
-        self._lib = None
-        self._loaded_key = None
-        self._ws = None
+        self._register(param_shapes(self.cfg), dtype=lambda key: torch.int64 if key.endswith("num_batches_tracked") else torch.float32)
 
-    def state_dict(self, *a, **k):
-        return {key: getattr(self, key.replace(".", "__")) for key in self.shapes}
+    def _config(self):
+        tv, lf, ti = self.cfg["tv_encoder"], self.cfg["lf0_encoder"], self.cfg["tiv_encoder"]
+        return _lib.DexStyleConfig(tv["c_in"], ti["num_layer"], ti["c_h"], tv["num_layer"], tv["c_h"], tv["c_out"], tv["c_out_g"], tv["n_emb"],
+                                   lf["c_h"], lf["c_out"], lf["c_out_g"], lf["num_layer"], self.cfg["dim"] * 2)
 
-    def load_state_dict(self, sd, strict: bool = True):
-        """Accepts the four sub-dicts of a DeXTTS checkpoint (keys tv_encoder.* / lf0_encoder.* / tiv_encoder.* / conv_sty.*;
-        other keys are ignored unless ``strict``)."""
-        mine = {k: v for k, v in sd.items() if k in self.shapes}
-        missing = [k for k in self.shapes if k not in mine]
-        if strict and (missing or len(mine) != len(sd)):
-            extra = [k for k in sd if k not in self.shapes]
-            raise RuntimeError(f"StyleEncoders.load_state_dict: missing {missing[:4]}, unexpected {extra[:4]}")
-        for k, v in mine.items():
-            buf = getattr(self, k.replace(".", "__"))
-            if tuple(v.shape) != tuple(buf.shape):
-                raise RuntimeError(f"{k}: shape {tuple(v.shape)} != {tuple(buf.shape)}")
-            buf.copy_(v.detach().to(buf.dtype))
-        self._loaded_key = None
-        return self
-
-    def _check(self, rc):
-        if rc != 0:
-            msg = self._lib.dex_style_last_error(self._ctx)
-            raise RuntimeError(f"libdexamd style error {rc}: {msg.decode() if msg else '?'}")
-
-    def _engine(self, device):
-        if device.type != "cuda":
-            raise RuntimeError("dex_tts_amd runs on an AMD GPU (torch device 'cuda' on ROCm); no CPU path exists")
-        if self._ctx is None:
-            self._lib = _lib.load()
-            tv, lf, ti = self.cfg["tv_encoder"], self.cfg["lf0_encoder"], self.cfg["tiv_encoder"]
-            c = _lib.DexStyleConfig(tv["c_in"], ti["num_layer"], ti["c_h"], tv["num_layer"], tv["c_h"], tv["c_out"], tv["c_out_g"], tv["n_emb"],
-                                    lf["c_h"], lf["c_out"], lf["c_out_g"], lf["num_layer"], self.cfg["dim"] * 2)
-            ctx = C.c_void_p()
-            rc = self._lib.dex_style_create(C.byref(c), C.byref(ctx))
-            self._ctx = ctx
-            self._check(rc)
-        bufs = [getattr(self, k.replace(".", "__")) for k in self.shapes]
-        key = (str(device),) + tuple((b._version, b.data_ptr()) for b in bufs)
-        if key != self._loaded_key:
-            folded = fold_batchnorm({k: v.float() if v.is_floating_point() else v for k, v in self.state_dict().items()})
-            with torch.cuda.device(device):
-                st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-                keep = []
-                for i in range(self._lib.dex_style_num_weights(self._ctx)):
-                    name = C.c_char_p(); shp = (C.c_int64 * 4)(); nd = C.c_int()
-                    self._check(self._lib.dex_style_weight_info(self._ctx, i, C.byref(name), shp, C.byref(nd)))
-                    k = name.value.decode()
-                    w = folded[k].to(device=device, dtype=torch.float32).contiguous()
-                    shape = (C.c_int64 * 4)(*([int(s) for s in w.shape] + [0] * (4 - w.dim())))
-                    self._check(self._lib.dex_style_load_weight_async(self._ctx, k.encode(), C.c_void_p(w.data_ptr()), shape, w.dim(), st))
-                    keep.append(w)
-                self._check(self._lib.dex_style_finalize(self._ctx, st))
-            self._loaded_key = key
-
-    def __del__(self):
-        try:
-            if self._ctx is not None and self._ctx.value:
-                self._lib.dex_style_destroy(self._ctx)
-        except Exception:
-            pass
+    def _library_weights(self):
+        return fold_batchnorm({k: v.float() if v.is_floating_point() else v for k, v in self.state_dict().items()})
 
     @torch.no_grad()
     def forward(self, ref: torch.Tensor, ref_lengths: torch.Tensor, sty: torch.Tensor, sty_lengths: torch.Tensor,
@@ -191,14 +135,11 @@ class StyleEncoders(nn.Module):
             idx = torch.empty(B, Ts, dtype=torch.int32, device=dev)
             wsq = self._lib.dex_style_loss_workspace_bytes if return_vq_loss else self._lib.dex_style_workspace_bytes
             need = int(wsq(self._ctx, B, Tr, Ts, Tl))
-            if self._ws is None or self._ws.numel() < need + 256 or self._ws.device != dev:
-                self._ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
-            base = (self._ws.data_ptr() + 255) // 256 * 256
+            base, nbytes = self._workspace(need, dev)
             arr = (C.c_void_p * len(skips))(*[s.data_ptr() for s in skips])
             a = _lib.DexStyleArgs(B, Tr, Ts, Tl, ref.data_ptr(), rl.data_ptr(), sty.data_ptr(), sl.data_ptr(), lf0.data_ptr(), ll.data_ptr(),
-                                  C.cast(arr, C.POINTER(C.c_void_p)), sty_dec.data_ptr(), sty_enc.data_ptr(), idx.data_ptr(), base,
-                                  self._ws.numel() - (base - self._ws.data_ptr()))
-            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                                  C.cast(arr, C.POINTER(C.c_void_p)), sty_dec.data_ptr(), sty_enc.data_ptr(), idx.data_ptr(), base, nbytes)
+            st = stream(dev)
             if return_vq_loss:
                 vq_loss = torch.empty((), dtype=torch.float32, device=dev)
                 self._check(self._lib.dex_style_encode_loss(self._ctx, C.byref(a), float(tv.get("commit_w", 0.25)), vq_loss.data_ptr(), st))

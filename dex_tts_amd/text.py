@@ -15,9 +15,9 @@ import ctypes as C
 from typing import Dict, Optional
 
 import torch
-import torch.nn as nn
 
 from . import _lib
+from ._native import NativeModule, stream
 
 
 def fix_len_compatibility(length: int, num_downsamplings_in_unet: int = 2) -> int:     # model/utils.py:13-17
@@ -58,7 +58,9 @@ def param_shapes(n_vocab, n_feats, n_channels, filter_channels, filter_channels_
     return o
 
 
-class TextEncoder(nn.Module):
+class TextEncoder(NativeModule):
+    prefix, noun = "dex_text", "text"
+
     def __init__(self, n_vocab, n_feats, n_channels, filter_channels, filter_channels_dp, n_heads, n_layers, kernel_size, p_dropout=0.1,
                  use_softmax=True, use_decay=False, window_size=None, spk_emb_dim=64, n_spks=1, variant="gedex"):
         super().__init__()
@@ -67,80 +69,16 @@ class TextEncoder(nn.Module):
         self.n_vocab, self.n_feats, self.n_channels, self.n_heads, self.n_layers = n_vocab, n_feats, n_channels, n_heads, n_layers
         self.filter_channels, self.filter_channels_dp, self.kernel_size = filter_channels, filter_channels_dp, kernel_size
         self.spk_emb_dim, self.n_spks, self.variant = spk_emb_dim, n_spks, variant
-        self.shapes = param_shapes(n_vocab, n_feats, n_channels, filter_channels, filter_channels_dp, n_heads, n_layers, kernel_size,
-                                   spk_emb_dim, n_spks, variant)
-        for key, shape in self.shapes.items():
-            self.register_buffer(key.replace(".", "__"), torch.zeros(shape, dtype=torch.float32), persistent=False)
-        self._ctx = None
-        self._lib = None
-        self._loaded_key = None
-        self._ws = None
+        self._register(param_shapes(n_vocab, n_feats, n_channels, filter_channels, filter_channels_dp, n_heads, n_layers, kernel_size,
+                                    spk_emb_dim, n_spks, variant))
         self._last = None
 
-    # ---- checkpoint surface
-    def state_dict(self, *a, **k):
-        return {key: getattr(self, key.replace(".", "__")) for key in self.shapes}
+    def _config(self):
+        return _lib.DexTextConfig(_lib.VARIANT[self.variant], self.n_vocab, self.n_feats, self.n_channels, self.filter_channels,
+                                  self.filter_channels_dp, self.n_heads, self.n_layers, self.kernel_size, self.n_spks, self.spk_emb_dim, 1, 0)
 
-    def load_state_dict(self, sd, strict: bool = True):
-        mine = {k: v for k, v in sd.items() if k in self.shapes}
-        missing = [k for k in self.shapes if k not in mine]
-        extra = [k for k in sd if k not in self.shapes]
-        if strict and (missing or extra):
-            raise RuntimeError(f"TextEncoder.load_state_dict: missing {missing[:4]}, unexpected {extra[:4]}")
-        for k, v in mine.items():
-            buf = getattr(self, k.replace(".", "__"))
-            if tuple(v.shape) != tuple(buf.shape):
-                raise RuntimeError(f"{k}: shape {tuple(v.shape)} != {tuple(buf.shape)}")
-            buf.copy_(v.detach().to(buf.dtype))
-        self._loaded_key = None
-        return self
-
-    def _check(self, rc):
-        if rc != 0:
-            msg = self._lib.dex_text_last_error(self._ctx)
-            raise RuntimeError(f"libdexamd text error {rc}: {msg.decode() if msg else '?'}")
-
-    def _engine(self, device):
-        if device.type != "cuda":
-            raise RuntimeError("dex_tts_amd runs on an AMD GPU (torch device 'cuda' on ROCm); no CPU path exists")
-        if self._ctx is None:
-            self._lib = _lib.load()
-            c = _lib.DexTextConfig(_lib.VARIANT[self.variant], self.n_vocab, self.n_feats, self.n_channels, self.filter_channels,
-                                   self.filter_channels_dp, self.n_heads, self.n_layers, self.kernel_size, self.n_spks, self.spk_emb_dim, 1, 0)
-            ctx = C.c_void_p()
-            rc = self._lib.dex_text_create(C.byref(c), C.byref(ctx))
-            self._ctx = ctx
-            self._check(rc)
-        bufs = [getattr(self, k.replace(".", "__")) for k in self.shapes]
-        key = (str(device),) + tuple((b._version, b.data_ptr()) for b in bufs)
-        if key != self._loaded_key:
-            sd = self.state_dict()
-            with torch.cuda.device(device):
-                st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-                keep = []
-                for i in range(self._lib.dex_text_num_weights(self._ctx)):
-                    name = C.c_char_p(); shp = (C.c_int64 * 4)(); nd = C.c_int()
-                    self._check(self._lib.dex_text_weight_info(self._ctx, i, C.byref(name), shp, C.byref(nd)))
-                    k = name.value.decode()
-                    w = sd[k].to(device=device, dtype=torch.float32).contiguous()
-                    shape = (C.c_int64 * 4)(*([int(s) for s in w.shape] + [0] * (4 - w.dim())))
-                    self._check(self._lib.dex_text_load_weight_async(self._ctx, k.encode(), C.c_void_p(w.data_ptr()), shape, w.dim(), st))
-                    keep.append(w)
-                self._check(self._lib.dex_text_finalize(self._ctx, st))
-            self._loaded_key = key
-
-    def __del__(self):
-        try:
-            if self._ctx is not None and self._ctx.value:
-                self._lib.dex_text_destroy(self._ctx)
-        except Exception:
-            pass
-
-    def _workspace(self, need, dev):
-        if self._ws is None or self._ws.numel() < need + 256 or self._ws.device != dev:
-            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
-        base = (self._ws.data_ptr() + 255) // 256 * 256
-        return base, self._ws.numel() - (base - self._ws.data_ptr())
+    def _library_weights(self):
+        return self.state_dict()
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor, x_lengths: torch.Tensor, *args, spk: Optional[torch.Tensor] = None, length_scale: float = 1.0):
@@ -180,7 +118,7 @@ class TextEncoder(nn.Module):
             a = _lib.DexTextArgs(B, T, tok.data_ptr(), xl.data_ptr(), spk.data_ptr() if spk is not None else None,
                                  sty.data_ptr() if sty is not None else None, float(length_scale), mu.data_ptr(), logw.data_ptr(), w_ceil.data_ptr(),
                                  y_len.data_ptr(), base, nbytes)
-            self._check(self._lib.dex_text_encode(self._ctx, C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            self._check(self._lib.dex_text_encode(self._ctx, C.byref(a), stream(dev)))
             x_mask = (torch.arange(T, device=dev)[None, :] < xl[:, None]).to(torch.float32).unsqueeze(1)       # sequence_mask: the returned tensor only
             self._last = dict(mu=mu, w_ceil=w_ceil, y_len=y_len, xl=xl, keep=(tok, spk, sty))
             return mu, logw, x_mask
@@ -204,6 +142,6 @@ class TextEncoder(nn.Module):
             cum = torch.empty(B * T, dtype=torch.float32, device=dev)
             a = _lib.DexAlignArgs(B, T, Ty, mu.data_ptr(), w_ceil.data_ptr(), xl.data_ptr(), y_len.data_ptr(), mu_y.data_ptr(), y_mask.data_ptr(),
                                   attn.data_ptr() if attn is not None else None, cum.data_ptr(), cum.numel() * 4)
-            self._check(self._lib.dex_text_align(self._ctx, C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            self._check(self._lib.dex_text_align(self._ctx, C.byref(a), stream(dev)))
             self._keep = cum
             return mu_y, y_mask, attn, y_len.to(torch.int64), y_max

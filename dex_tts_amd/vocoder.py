@@ -11,9 +11,9 @@ import json
 from typing import Dict, Optional
 
 import torch
-import torch.nn as nn
 
 from . import _lib
+from ._native import NativeModule, stream
 
 HIFIGAN_V1 = dict(num_mels=80, upsample_rates=[8, 8, 2, 2], upsample_kernel_sizes=[16, 16, 4, 4], upsample_initial_channel=512,
                   resblock="1", resblock_kernel_sizes=[3, 7, 11], resblock_dilation_sizes=[[1, 3, 5], [1, 3, 5], [1, 3, 5]])
@@ -85,6 +85,22 @@ def param_shapes(h) -> Dict[str, tuple]:
     return out
 
 
+def make_config(h) -> _lib.DexVocoderConfig:
+    """The library's DexVocoderConfig of a HiFi-GAN / BigVGAN config (config.json keys, attribute or dict access)."""
+    c = _lib.DexVocoderConfig()
+    rates, ksz, rk, rd = (list(_get(h, n)) for n in ("upsample_rates", "upsample_kernel_sizes", "resblock_kernel_sizes", "resblock_dilation_sizes"))
+    c.num_mels, c.upsample_initial_channel, c.n_upsamples = int(_get(h, "num_mels", 80)), int(_get(h, "upsample_initial_channel")), len(rates)
+    for i, (u, k) in enumerate(zip(rates, ksz)):
+        c.upsample_rates[i], c.upsample_kernel_sizes[i] = int(u), int(k)
+    c.activation, c.snake_logscale = ACTIVATION[_get(h, "activation")], int(bool(_get(h, "snake_logscale", False)))
+    c.n_resblock_kernels = len(rk)
+    for j, k in enumerate(rk[:3]):
+        c.resblock_kernel_sizes[j] = int(k)
+        for m in range(3):
+            c.resblock_dilation_sizes[j][m] = int(rd[j][m])
+    return c
+
+
 def fold_weight_norm(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """``weight = g * v / ||v||`` with the norm over every dim but 0 (torch.nn.utils.weight_norm, dim=0 — also for the
     ConvTranspose1d layers, whose dim 0 is the INPUT channel): what remove_weight_norm() leaves (models.py:169-173)."""
@@ -102,100 +118,38 @@ def fold_weight_norm(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return out
 
 
-class Generator(nn.Module):
+class Generator(NativeModule):
+    prefix, noun = "dex_voc", "vocoder"
+
     def __init__(self, h=None):
         super().__init__()
         h = AttrDict(HIFIGAN_V1) if h is None else h
         if str(_get(h, "resblock", "1")) != "1":
             raise ValueError("only ResBlock / AMPBlock type '1' (hifigan/config.json V1, bigvgan base) is built")
         self.h = h
-        self.shapes = param_shapes(h)
-        for key, shape in self.shapes.items():           # flat parameter registry under the reference's dotted names
-            self.register_buffer(key.replace(".", "__"), torch.zeros(shape), persistent=False)
-        self._ctx: Optional[C.c_void_p] = None
-        self._lib = None
-        self._loaded_key = None
-        self._ws = None
+        self._register(param_shapes(h))
 
     # ---- checkpoint surface ---------------------------------------------------------------------------------------
-    def state_dict(self, *a, **k):
-        return {key: getattr(self, key.replace(".", "__")) for key in self.shapes}
-
-    def load_state_dict(self, sd, strict: bool = True):
-        sd = fold_weight_norm(dict(sd))
-        missing = [k for k in self.shapes if k not in sd]
-        extra = [k for k in sd if k not in self.shapes]
-        if strict and (missing or extra):
-            raise RuntimeError(f"Generator.load_state_dict: missing {missing[:4]}, unexpected {extra[:4]}")
-        for key, shape in self.shapes.items():
-            if key in sd:
-                t = sd[key].detach().to(torch.float32)
-                if tuple(t.shape) != tuple(shape):
-                    raise RuntimeError(f"{key}: shape {tuple(t.shape)} != {tuple(shape)}")
-                getattr(self, key.replace(".", "__")).copy_(t)
-        self._loaded_key = None
-        return self
+    def _fold_checkpoint(self, sd):
+        return fold_weight_norm(sd)
 
     def remove_weight_norm(self):
         """No-op: weight norm is folded at load time (the reference calls this right after loading, utils.py:278)."""
         return self
 
     # ---- engine -----------------------------------------------------------------------------------------------------
-    def _check(self, rc):
-        if rc != 0:
-            msg = self._lib.dex_voc_last_error(self._ctx)
-            raise RuntimeError(f"libdexamd vocoder error {rc}: {msg.decode() if msg else '?'}")
+    def _config(self):
+        return make_config(self.h)
 
-    def _engine(self, device):
-        if device.type != "cuda":
-            raise RuntimeError("dex_tts_amd runs on an AMD GPU (torch device 'cuda' on ROCm); no CPU path exists")
-        if self._ctx is None:
-            self._lib = _lib.load()
-            c = _lib.DexVocoderConfig()
-            h = self.h
-            rates, ksz, rk, rd = (list(_get(h, n)) for n in ("upsample_rates", "upsample_kernel_sizes", "resblock_kernel_sizes", "resblock_dilation_sizes"))
-            c.num_mels, c.upsample_initial_channel, c.n_upsamples = int(_get(h, "num_mels", 80)), int(_get(h, "upsample_initial_channel")), len(rates)
-            for i, (u, k) in enumerate(zip(rates, ksz)):
-                c.upsample_rates[i], c.upsample_kernel_sizes[i] = int(u), int(k)
-            c.activation, c.snake_logscale = ACTIVATION[_get(h, "activation")], int(bool(_get(h, "snake_logscale", False)))
-            c.n_resblock_kernels = len(rk)
-            for j, k in enumerate(rk[:3]):
-                c.resblock_kernel_sizes[j] = int(k)
-                for m in range(3):
-                    c.resblock_dilation_sizes[j][m] = int(rd[j][m])
-            ctx = C.c_void_p()
-            rc = self._lib.dex_voc_create(C.byref(c), C.byref(ctx))
-            self._ctx = ctx
-            self._check(rc)
-        bufs = [getattr(self, k.replace(".", "__")) for k in self.shapes]
-        key = (str(device),) + tuple((b._version, b.data_ptr()) for b in bufs)
-        if key != self._loaded_key:
-            # BigVGAN: the library takes ONE copy of the resampling filter (all 73 buffers are the same Kaiser-sinc constant)
-            filt = [k for k in self.shapes if k.endswith(".filter")]
-            if filt:
-                f0 = getattr(self, "activation_post.upsample.filter".replace(".", "__"))
-                for k in filt:
-                    if not torch.equal(getattr(self, k.replace(".", "__")), f0):
-                        raise RuntimeError(f"{k} differs from activation_post.upsample.filter: per-layer resampling filters are not supported")
-            with torch.cuda.device(device):
-                st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-                keep = []
-                for name, shape in self.shapes.items():
-                    if name.endswith(".filter") and not name.startswith("activation_post."):
-                        continue
-                    w = getattr(self, name.replace(".", "__")).to(device=device, dtype=torch.float32).contiguous()
-                    shp = (C.c_int64 * 4)(*([int(s) for s in shape] + [0] * (4 - len(shape))))
-                    self._check(self._lib.dex_voc_load_weight_async(self._ctx, name.encode(), C.c_void_p(w.data_ptr()), shp, len(shape), st))
-                    keep.append(w)
-                self._check(self._lib.dex_voc_finalize(self._ctx, st))
-            self._loaded_key = key
-
-    def __del__(self):
-        try:
-            if self._ctx is not None and self._ctx.value:
-                self._lib.dex_voc_destroy(self._ctx)
-        except Exception:
-            pass
+    def _library_weights(self):
+        # BigVGAN: the library takes ONE copy of the resampling filter (all 73 buffers are the same Kaiser-sinc constant) and lists only
+        # activation_post's pair
+        sd = self.state_dict()
+        f0 = sd.get("activation_post.upsample.filter")
+        for k in self.shapes:
+            if k.endswith(".filter") and not torch.equal(sd[k], f0):
+                raise RuntimeError(f"{k} differs from activation_post.upsample.filter: per-layer resampling filters are not supported")
+        return sd
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -211,13 +165,11 @@ class Generator(nn.Module):
                 raise ValueError(f"mel has {M} channels, the generator expects {_get(self.h, 'num_mels', 80)}")
             n = int(self._lib.dex_voc_samples(self._ctx, T))
             need = int(self._lib.dex_voc_workspace_bytes(self._ctx, B, T))
-            if self._ws is None or self._ws.numel() < need + 256 or self._ws.device != dev:
-                self._ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
-            base = (self._ws.data_ptr() + 255) // 256 * 256
+            base, nbytes = self._workspace(need, dev)
             wav = torch.empty(B, 1, n, dtype=torch.float32, device=dev)
-            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            st = stream(dev)
             self._check(self._lib.dex_vocode(self._ctx, C.c_void_p(mel.data_ptr()), B, T, C.c_void_p(wav.data_ptr()), C.c_void_p(base),
-                                             self._ws.numel() - (base - self._ws.data_ptr()), st))
+                                             nbytes, st))
             self._keep = mel
             return wav
 

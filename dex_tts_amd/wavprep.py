@@ -17,6 +17,7 @@ import torch
 
 from . import _lib
 from . import f0 as F0
+from ._native import check, device_rows, i32_ptr, stream
 
 SR = F0.SR
 
@@ -51,10 +52,6 @@ def _i32(v):
     return np.ascontiguousarray(np.asarray(v, dtype=np.int32))
 
 
-def _ptr(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int32))
-
-
 def _rates(sr, B):
     srs = np.full(B, sr, dtype=np.int64) if np.ndim(sr) == 0 else np.asarray(sr, dtype=np.int64).reshape(-1)
     if srs.shape != (B,) or (srs <= 0).any() or (srs > np.iinfo(np.int32).max).any():
@@ -67,18 +64,18 @@ def trim(wav, lengths=None, top_db=30.0, frame_length=2048, hop_length=512, pad_
     [2] or [B, 2] int32 on the device, (start, end) of the non-silent part.  return_mse: also each frame's mean square, float64
     [F] or [B, F] with F = 1 + L // hop_length (0 past a row's own frames)."""
     lib = _lib.load()
-    x, ln, one = F0._rows(wav, lengths)
+    x, ln, one = device_rows(wav, lengths)
     B, L = x.shape
     o = _trim_opts(top_db, frame_length, hop_length, pad_mode)
-    need = int(lib.dex_wav_trim_workspace_bytes(B, F0._lens_ptr(ln), C.byref(o)))
+    need = int(lib.dex_wav_trim_workspace_bytes(B, i32_ptr(ln), C.byref(o)))
     if need == 0:
         raise ValueError("dex_wav_trim_workspace_bytes rejected the arguments")
     with torch.cuda.device(x.device):
         ws = torch.empty(need, dtype=torch.uint8, device=x.device)
         bounds = torch.empty(B, 2, dtype=torch.int32, device=x.device)
         mse = torch.empty(B, 1 + L // int(hop_length), dtype=torch.float64, device=x.device) if return_mse else None
-        F0._check(lib.dex_wav_trim(x.data_ptr(), F0._lens_ptr(ln), B, L, C.byref(o), bounds.data_ptr(),
-                                   mse.data_ptr() if return_mse else None, ws.data_ptr(), need, F0._stream(x.device)), "dex_wav_trim")
+        check(lib.dex_wav_trim(x.data_ptr(), i32_ptr(ln), B, L, C.byref(o), bounds.data_ptr(),
+                               mse.data_ptr() if return_mse else None, ws.data_ptr(), need, stream(x.device)), "dex_wav_trim")
     if return_mse:
         return (bounds[0], mse[0]) if one else (bounds, mse)
     return bounds[0] if one else bounds
@@ -102,7 +99,7 @@ def _table(dev):
         need = int(lib.dex_wav_resample_table_bytes(None))
         with torch.cuda.device(dev):
             tab = torch.empty(need, dtype=torch.uint8, device=dev)
-            F0._check(lib.dex_wav_resample_table(None, tab.data_ptr(), need, F0._stream(dev)), "dex_wav_resample_table")
+            check(lib.dex_wav_resample_table(None, tab.data_ptr(), need, stream(dev)), "dex_wav_resample_table")
             torch.cuda.current_stream(dev).synchronize()          # ready for calls on any stream
         _TABLE[dev] = tab
     return _TABLE[dev]
@@ -117,8 +114,8 @@ def _resample(x, offsets, lengths, srs, sr_new):
     tab = _table(x.device)
     with torch.cuda.device(x.device):
         y = torch.empty(B, Lm, dtype=torch.float64, device=x.device)
-        F0._check(lib.dex_wav_resample(x.data_ptr(), Ls, _ptr(offsets), _ptr(lengths), _ptr(srs), B, int(sr_new), None, y.data_ptr(), Lm,
-                                       tab.data_ptr(), tab.numel(), F0._stream(x.device)), "dex_wav_resample")
+        check(lib.dex_wav_resample(x.data_ptr(), Ls, i32_ptr(offsets), i32_ptr(lengths), i32_ptr(srs), B, int(sr_new), None, y.data_ptr(), Lm,
+                                   tab.data_ptr(), tab.numel(), stream(x.device)), "dex_wav_resample")
     return y, lo
 
 
@@ -127,7 +124,7 @@ def resample(wav, sr_orig, sr_new, lengths=None, offsets=None):
     ``lengths[b]`` samples from ``offsets[b]`` (default 0) at ``sr_orig`` Hz (an int or one per row) -> (y, lengths_out): y [L_out]
     or [B, max L_out] float64 on the device (0 past a row's length), lengths_out a host int32 array.  A row already at sr_new is
     copied."""
-    x, _, one = F0._rows(wav, None)
+    x, _, one = device_rows(wav, None)
     B, L = x.shape
     ln = np.full(B, L, np.int32) if lengths is None else _i32(torch.as_tensor(lengths).cpu()).reshape(-1)
     off = np.zeros(B, np.int32) if offsets is None else _i32(torch.as_tensor(offsets).cpu()).reshape(-1)
@@ -158,8 +155,8 @@ def peak_normalize_f64(y, lengths=None):
     with torch.cuda.device(y.device):
         ws = torch.empty(max(need, 1), dtype=torch.uint8, device=y.device)
         out = torch.empty(B, L, dtype=torch.float32, device=y.device)
-        F0._check(lib.dex_wav_peak_normalize_f64(y.data_ptr(), _ptr(ln), B, L, out.data_ptr(), ws.data_ptr(), need, F0._stream(y.device)),
-                  "dex_wav_peak_normalize_f64")
+        check(lib.dex_wav_peak_normalize_f64(y.data_ptr(), i32_ptr(ln), B, L, out.data_ptr(), ws.data_ptr(), need, stream(y.device)),
+              "dex_wav_peak_normalize_f64")
     return out[0] if one else out
 
 
@@ -183,7 +180,7 @@ def prepare(wav, sr=None, lengths=None, top_db=30.0, pad_mode="constant"):
         wav, lengths, sr = _load([wav] if isinstance(wav, (str, os.PathLike)) else list(wav))
     elif sr is None:
         raise ValueError("pass the sample rate of the tensor's rows")
-    x, ln, _ = F0._rows(wav, lengths)
+    x, ln, _ = device_rows(wav, lengths)
     B = x.shape[0]
     srs = _rates(sr, B)
     bounds = trim(x, ln, top_db=top_db, pad_mode=pad_mode).cpu().numpy().reshape(B, 2)
@@ -197,4 +194,4 @@ def preprocess_wav(wav, sr=None, lengths=None, stft=None, top_db=30.0, pad_mode=
     Hz (an int or one per row).  Trim at the source rate, resample to 22050 Hz in fp64 where the rate differs, peak-normalise in fp64,
     round to fp32 once (``prepare``), then the mel and the f0 tracker -> the dict of ``dex_tts_amd.f0.reference_features`` (which
     DeXTTS.forward / synthesize_tokens(style=...) take)."""
-    return F0._features(*prepare(wav, sr, lengths, top_db, pad_mode), stft)
+    return F0.features(*prepare(wav, sr, lengths, top_db, pad_mode), stft)

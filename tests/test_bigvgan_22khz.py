@@ -78,17 +78,7 @@ def test_oracle_matches_reference_golden(golden_threads):
 
 def _create(h):
     lib = _lib.load()
-    c = _lib.DexVocoderConfig()
-    rates, ksz = h["upsample_rates"], h["upsample_kernel_sizes"]
-    c.num_mels, c.upsample_initial_channel, c.n_upsamples = 80, h["upsample_initial_channel"], len(rates)
-    for i, (u, k) in enumerate(zip(rates, ksz)):
-        c.upsample_rates[i], c.upsample_kernel_sizes[i] = u, k
-    c.activation, c.snake_logscale = V.ACTIVATION[h.get("activation")], int(bool(h.get("snake_logscale", False)))
-    c.n_resblock_kernels = 3
-    for j in range(3):
-        c.resblock_kernel_sizes[j] = h["resblock_kernel_sizes"][j]
-        for m in range(3):
-            c.resblock_dilation_sizes[j][m] = h["resblock_dilation_sizes"][j][m]
+    c = V.make_config(h)
     ctx = C.c_void_p()
     rc = lib.dex_voc_create(C.byref(c), C.byref(ctx))
     msg = lib.dex_voc_last_error(ctx).decode()
