@@ -193,6 +193,16 @@ SYMBOLS = [
                                  C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("dex_loss_segment", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("dex_gl_create", C.c_int, [C.POINTER(C.c_void_p)]),
+    ("dex_gl_destroy", None, [C.c_void_p]),
+    ("dex_gl_last_error", C.c_char_p, [C.c_void_p]),
+    ("dex_gl_workspace_bytes", C.c_size_t, [C.c_int, C.c_int]),
+    ("dex_stft_transform", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("dex_stft_inverse", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_size_t, C.c_void_p]),
+    ("dex_griffin_lim", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                  C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("dex_mel_to_linear", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 ]
 
 _lib = None

@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from ._native import stream
+from .griffin_lim import STFT
 
 _FIXED = (1024, 256, 1024, 80, 22050, 0, 8000)
 
@@ -37,6 +38,10 @@ class TacotronSTFT:
             raise RuntimeError(f"dex_mel_create failed ({rc})")
         self._h = h
         self._ws = None
+        # audio/stft.py:137; the reference's inv_mel_spec reads `_stft_fn` (tools.py:28), which its own class never defines: the alias
+        # lets dex_tts_amd.griffin_lim.inv_mel_spec take this object
+        self.stft_fn = STFT(filter_length, hop_length, win_length)
+        self._stft_fn = self.stft_fn
 
     def __del__(self):
         try:

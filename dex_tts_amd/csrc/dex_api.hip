@@ -355,6 +355,26 @@ int dex_ctx_set_precision(DexCtx* x, int precision) {
 
 }  // extern "C"
 
+// librosa.filters.mel(22050, 1024, 80, 0, 8000) [80][513]: Slaney scale + slaney area normalisation, in double, rounded once
+void dex::slaney_mel_filterbank(float* filt) {
+    const int nb = 513;
+    const int n_mels = 80; const double sr = 22050, fmin = 0, fmax = 8000;
+    auto hz2mel = [](double f) { const double fsp = 200.0 / 3; return f >= 1000.0 ? 1000.0 / fsp + log(f / 1000.0) / (log(6.4) / 27.0) : f / fsp; };
+    auto mel2hz = [](double m) { const double fsp = 200.0 / 3, mlm = 1000.0 / fsp; return m >= mlm ? 1000.0 * exp(log(6.4) / 27.0 * (m - mlm)) : fsp * m; };
+    std::vector<double> mf(n_mels + 2);
+    const double m0 = hz2mel(fmin), m1 = hz2mel(fmax);
+    for (int i = 0; i < n_mels + 2; ++i) mf[i] = mel2hz(m0 + (m1 - m0) * i / (n_mels + 1));
+    for (int i = 0; i < n_mels; ++i) {
+        const double enorm = 2.0 / (mf[i + 2] - mf[i]);
+        for (int k = 0; k < nb; ++k) {
+            const double fr = (sr / 2.0) * k / (nb - 1);
+            const double lower = (fr - mf[i]) / (mf[i + 1] - mf[i]), upper = (mf[i + 2] - fr) / (mf[i + 2] - mf[i + 1]);
+            const double w = fmax > 0 ? std::max(0.0, std::min(lower, upper)) : 0.0;
+            filt[(size_t)i * nb + k] = (float)(w * enorm);
+        }
+    }
+}
+
 // ================================================================================================
 // weight packing
 namespace {
@@ -479,23 +499,8 @@ void build_mel_constants(std::vector<float>& basis, std::vector<float>& filt) {
             basis[(size_t)n * NP + IM + k] = (float)(-sin(ang)) * win;
         }
     }
-    // librosa.filters.mel(22050, 1024, 80, 0, 8000), Slaney scale + slaney area normalisation
-    const int n_mels = 80; const double sr = 22050, fmin = 0, fmax = 8000;
-    auto hz2mel = [](double f) { const double fsp = 200.0 / 3; return f >= 1000.0 ? 1000.0 / fsp + log(f / 1000.0) / (log(6.4) / 27.0) : f / fsp; };
-    auto mel2hz = [](double m) { const double fsp = 200.0 / 3, mlm = 1000.0 / fsp; return m >= mlm ? 1000.0 * exp(log(6.4) / 27.0 * (m - mlm)) : fsp * m; };
-    std::vector<double> mf(n_mels + 2);
-    const double m0 = hz2mel(fmin), m1 = hz2mel(fmax);
-    for (int i = 0; i < n_mels + 2; ++i) mf[i] = mel2hz(m0 + (m1 - m0) * i / (n_mels + 1));
-    filt.assign((size_t)n_mels * nb, 0.f);
-    for (int i = 0; i < n_mels; ++i) {
-        const double enorm = 2.0 / (mf[i + 2] - mf[i]);
-        for (int k = 0; k < nb; ++k) {
-            const double fr = (sr / 2.0) * k / (nb - 1);
-            const double lower = (fr - mf[i]) / (mf[i + 1] - mf[i]), upper = (mf[i + 2] - fr) / (mf[i + 2] - mf[i + 1]);
-            const double w = fmax > 0 ? std::max(0.0, std::min(lower, upper)) : 0.0;
-            filt[(size_t)i * nb + k] = (float)(w * enorm);
-        }
-    }
+    filt.assign((size_t)80 * nb, 0.f);
+    dex::slaney_mel_filterbank(filt.data());
 }
 
 }  // namespace

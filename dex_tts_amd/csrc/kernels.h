@@ -537,5 +537,7 @@ struct MagMelP { const float* spec; int ld; int im_off; int frames; int nbins; c
 void launch_magmel(const MagMelP& p, hipStream_t st, int B = 1);
 // DEX style front-end: log-f0 + per-utterance normalisation (DEX-TTS/synthesize.py:26-38,55-58); lengths may be null
 void launch_lf0_normalize(const float* f0, const int* lengths, int B, int T, float* out, hipStream_t st);
+// librosa.filters.mel(22050, 1024, 80, 0, 8000) into filt [80][513] (host; the table of the mel front-end and of dex_mel_to_linear)
+void slaney_mel_filterbank(float* filt);
 
 }  // namespace dex

@@ -15,6 +15,7 @@ array (e.g. dumped from the reference, or synthetic).  CLI:
 
     python -m dex_tts_amd.synthesize --config <reference base.yaml> --mu mu_y.npy [--lengths 210,180] [--ckpt model.pth]
            [--n_timesteps 50] [--temperature 1.5] [--seed 100] [--precision fp32|bf16|fp16] --out mel.npy
+           [--wav out.wav [--griffin_iters 60]]        (Griffin-Lim waveforms of the mels, dex_tts_amd.griffin_lim)
 """
 from __future__ import annotations
 
@@ -131,6 +132,9 @@ def main(argv=None):
     ap.add_argument("--precision", default="fp32")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--out", required=True)
+    ap.add_argument("--wav", default=None, help="also write each mel as a Griffin-Lim waveform (no vocoder weights needed): OUT.wav for "
+                                                "one utterance, OUT_<b>.wav for utterance b of a batch")
+    ap.add_argument("--griffin_iters", type=int, default=60, help="Griffin-Lim iterations of --wav (audio/tools.py inv_mel_spec)")
     a = ap.parse_args(argv)
 
     seed_init(a.seed)
@@ -166,6 +170,24 @@ def main(argv=None):
     mel = decode(model, mu.to(a.device), lengths.to(a.device), a.n_timesteps, a.temperature, **kw)
     np.save(a.out, mel.cpu().numpy())
     print(f"{a.out}: mel {tuple(mel.shape)}")
+    if a.wav:
+        write_wavs(mel, lengths, a.wav, a.griffin_iters)
+
+
+def write_wavs(mel: torch.Tensor, lengths: torch.Tensor, path: str, n_iters: int = 60):
+    """--wav: each decoded mel [80, lengths[b]] through Griffin-Lim (dex_tts_amd.griffin_lim.mel_to_wav, the reference's
+    inv_mel_spec) -> a float32 wav of 256 (lengths[b] - 2) samples at 22050 Hz; path for one utterance, <stem>_<b><ext> for a batch."""
+    import os
+    from scipy.io.wavfile import write
+    from .griffin_lim import SAMPLING_RATE, mel_to_wav
+
+    n = [int(v) for v in lengths.tolist()]
+    wav = mel_to_wav(mel, n, n_iters=n_iters).cpu().numpy()
+    stem, ext = os.path.splitext(path)
+    for b in range(wav.shape[0]):
+        out = path if wav.shape[0] == 1 else f"{stem}_{b}{ext or '.wav'}"
+        write(out, SAMPLING_RATE, wav[b, : 256 * (n[b] - 2)])
+        print(f"{out}: {256 * (n[b] - 2)} samples (Griffin-Lim, {n_iters} iterations)")
 
 
 if __name__ == "__main__":

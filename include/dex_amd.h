@@ -427,6 +427,35 @@ int    dex_loss_segment(const float* mu_x_dev, const int32_t* dur_dev, const flo
                         const int* y_lengths_host, const int* offsets_host, int S, float* y_cut_dev, float* mu_y_cut_dev,
                         float* y_cut_mask_dev, dex_stream_t s);
 
+/* ---- Griffin-Lim mel inversion (audio/tools.py:18-34 inv_mel_spec -> audio/audio_processing.py:66-82 griffin_lim -> audio/stft.py:52-121
+ * STFT.transform / STFT.inverse with window_sumsquare), the reference's only mel -> waveform path without a vocoder checkpoint.  Only
+ * the reference configuration: filter_length 1024, hop 256, win_length 1024, periodic Hann, 80 Slaney mels at 22050 Hz.  Every frame
+ * is a 1024-point real FFT in LDS (fp32).  Frame counts and lengths are HOST arrays; bad arguments return an error code, with a
+ * message in dex_gl_last_error, before anything is enqueued.  No call synchronises or allocates; a row's result does not depend on
+ * its batch, and samples past a row's length are 0.  Spectrograms are [B,513,F] (bins x frames, frames contiguous); the waveform of
+ * a row of F frames has 256 (F - 1) samples, in rows of 256 (max_frames - 1). */
+typedef struct DexGl DexGl;
+int  dex_gl_create(DexGl** out);                   /* the handle's tables: FFT twiddles, the window, its square in fp64, the mel basis */
+void dex_gl_destroy(DexGl* gl);
+const char* dex_gl_last_error(const DexGl* gl);
+size_t dex_gl_workspace_bytes(int B, int max_frames);   /* for the inverse and Griffin-Lim; 0 for bad arguments */
+/* STFT.transform: wav_dev [B, n_samples], row b lengths_host[b] samples (513 .. n_samples) -> magnitude and atan2 phase
+ * [B, 513, n_samples / 256 + 1]; row b fills its first lengths_host[b] / 256 + 1 frames, the rest is not written. */
+int  dex_stft_transform(DexGl* gl, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, float* mag_dev,
+                        float* phase_dev, dex_stream_t stream);
+/* STFT.inverse: mag, phase [B, 513, max_frames], row b frames_host[b] frames (2 .. max_frames) -> wav_dev [B, 256 (max_frames - 1)]. */
+int  dex_stft_inverse(DexGl* gl, const float* mag_dev, const float* phase_dev, const int32_t* frames_host, int B, int max_frames,
+                      float* wav_dev, void* workspace_dev, size_t workspace_bytes, dex_stream_t stream);
+/* griffin_lim with the initial angles given: signal = inverse(S, angles), then n_iters >= 0 times signal = inverse(S, phase(transform
+ * (signal))).  mag, angles [B, 513, max_frames], row b frames_host[b] frames (4 .. max_frames) -> wav_dev [B, 256 (max_frames - 1)].
+ * 2 (n_iters + 1) launches per 64 rows. */
+int  dex_griffin_lim(DexGl* gl, const float* mag_dev, const float* angles_dev, const int32_t* frames_host, int B, int max_frames,
+                     int n_iters, float* wav_dev, void* workspace_dev, size_t workspace_bytes, dex_stream_t stream);
+/* inv_mel_spec's spec_from_mel[:, :, :-1]: mel [B, 80, T] (row b mel_frames_host[b] frames, 2 .. T) -> 1000 exp(mel)^T mel_basis,
+ * [B, 513, T - 1]: row b fills mel_frames_host[b] - 1 frames (its last mel frame is dropped) and 0 past them. */
+int  dex_mel_to_linear(DexGl* gl, const float* mel_dev, const int32_t* mel_frames_host, int B, int T, float* spec_dev,
+                       dex_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
