@@ -12,7 +12,8 @@ For N>1 the batch is B utterances PER GPU (weak scaling): every rank holds only 
 sharder (dex_tts_amd.dist.sample_sharded) and the finished mels are all-gathered over RCCL inside the timed region
 (the path's one exchange step).  Prints ONE JSON line on rank 0.
 
-The default N=1 run also carries, in the same line: `roofline` for the dominant kernel SYMBOL of the workload (HIP
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: nothing else.  With --full
+an N=1 run also carries, in the same line: `roofline` for the dominant kernel SYMBOL of the workload (HIP
 events on the launch stream; HBM traffic from the committed PMC summary), `roofline_attention` (the DiT attention
 kernel on its own), `fp32_mode`, `roofline_batch32`, driver-timed blocks for BASELINE.json configs[2], [3] (per-GPU
 share) and [4] under `configs`, and `cpu_baseline` (the CPU oracle on the host cores, bounded sample).
@@ -479,6 +480,11 @@ def _err2(e):
     return None if not e else {"max": float(f"{e['max']:.3g}"), "mean": float(f"{e['mean']:.3g}")}
 
 
+def has_profiled_blocks(res):
+    """whether the record carries roofline entries (those splice fields from the committed profiles: --full runs only)"""
+    return any(k in res for k in ("roofline", "roofline_attention", "batch32", "configs"))
+
+
 def compact(res):
     """The ONE stdout line: the contract's keys + roofline / roofline_attention / cpu_baseline / parity_mode / batch32 / per-config
     values, <= COMPACT_LIMIT bytes whatever the full record holds (tests/test_bench_line.py).  The full record goes to
@@ -530,9 +536,11 @@ def compact(res):
     if "frontend" in res:
         out["frontend_ms"] = {k: v.get("ms_per_call") for k, v in res["frontend"].items()}
     out["full_record"] = res.get("_full_path")
-    ph = profiles_head()
-    out["profiles_head"] = {"commit": ph["commit"], "stale": ph["stale"]}       # the tree the spliced rocprof_avg_launch_us / traffic fields were measured on
-    out["abs_err_measured"] = "in this run"                                     # configs[*].abs_err: pinned jobs vs the oracle's stored outputs (job_abs_err)
+    if has_profiled_blocks(res):
+        ph = profiles_head()
+        out["profiles_head"] = {"commit": ph["commit"], "stale": ph["stale"]}   # the tree the spliced rocprof_avg_launch_us / traffic fields were measured on
+    if "configs" in res:
+        out["abs_err_measured"] = "in this run"                                 # configs[*].abs_err: pinned jobs vs the oracle's stored outputs (job_abs_err)
     # belt and braces: drop the optional blocks, least important first, until the line fits
     for k in ("frontend_ms", "vocoder_bigvgan", "vocoder_bf16", "vocoder", "batch32_bucketed", "fp16_mode", "exact_fp32_mode", "configs"):
         if len(json.dumps(out)) < COMPACT_LIMIT - 256:
@@ -580,7 +588,8 @@ def emit(res):
             json.dump({k: v for k, v in res.items() if not k.startswith("_")}, f)
     except OSError:
         res["_full_path"] = None
-    res["profiles_head"] = profiles_head()
+    if has_profiled_blocks(res):
+        res["profiles_head"] = profiles_head()
     print("[bench full record] " + json.dumps({k: v for k, v in res.items() if not k.startswith("_")}), file=sys.stderr, flush=True)
     line = json.dumps(compact(res))
     assert len(line) < COMPACT_LIMIT, len(line)
@@ -602,9 +611,12 @@ def main():
     ap.add_argument("--bucket-width", type=int, default=0,
                     help="opt-in length bucketing of the timed job (dex_tts_amd.dist.sample_bucketed): utterances whose length rounds up to the "
                          "same multiple of this many frames are padded to their own maximum and sampled as a batch of their own")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the configs[2]/[3]/[4] blocks of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: after the headline, also measure the CPU baseline, per-kernel rooflines, the other precisions, the B=32 set, "
+                         "configs[2]-[4], the vocoders and the front-end (off: the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="--full without the profiled blocks (rooflines, other modes, configs)")
+    ap.add_argument("--no-configs", action="store_true", help="--full without the configs[2]/[3]/[4] blocks")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend for N>1 (nccl == RCCL over xGMI; gloo only for single-GPU smoke tests)")
     ap.add_argument("--all-on-device0", action="store_true",
@@ -703,12 +715,12 @@ def main():
         }
         if dumped is not None:
             res["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
-        prof = world == 1 and not args.no_profile
+        prof = world == 1 and args.full and not args.no_profile
         call_eager = lambda: eng.sample(z, mask, mu, n_steps, use_graph=False, **kw)
         y_oracle = None
         err = lambda y: None if y_oracle is None else {"max": float((y.float().cpu() - y_oracle).abs().max()), "mean": float((y.float().cpu() - y_oracle).abs().mean()),
                                                        "against": "CPU oracle (fp32 restatement of the reference, pinned to it bit for bit), the whole job"}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # (timed on the host cores while the GPU idles; for the B=1 headline job the oracle runs the WHOLE job and its result is the
             # checker every mode's abs_err below is measured against)
             res["cpu_baseline"], y_oracle = cpu_baseline(cfg, weights, B, T, n_steps, TrTs, full=(args.workload == "gedex_b1" and not args.bucket_width))

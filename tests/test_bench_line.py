@@ -52,6 +52,18 @@ def test_compact_line_survives_a_bloated_record():
     assert "roofline" in back and "cpu_baseline" in back and back["value"] == full["value"]
 
 
+def test_plain_line_keeps_the_contract_without_profile_fields():
+    """a run without --full measures no profiled block: its line keeps the contract's keys and names no committed profiles"""
+    b = _bench()
+    full = json.load(open(FULL[-1]))
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                                  "vs_baseline", "dtype", "data", "config", "rtf", "ms_per_euler_step", "hip_event_median_ms")}
+    assert not b.has_profiled_blocks(plain) and b.has_profiled_blocks(full)
+    back = json.loads(json.dumps(b.compact(plain)))
+    assert {k: back[k] for k in plain} == plain
+    assert "profiles_head" not in back and "abs_err_measured" not in back
+
+
 def test_dump_outputs_stays_in_budget_and_samples_the_same_rows(tmp_path):
     """--dump-outputs: float32 files; a batch over the budget is cut to the same seeded rows on every run, their indices stored beside it"""
     import numpy as np

@@ -4,7 +4,7 @@ set -x
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}; TAG=${1:-round2}; O=$R/gpurun_out/$TAG; mkdir -p $O
 B="--no-cpu-baseline --no-profile"
-python $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
+python $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 for w in gedex_b1 gedex_b32 dex_b32 gedex_long; do
   rm -rf /tmp/p_$w
   rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$w -o t -- python $R/bench.py --workload $w --steps 2 --warmup 1 --graph off $B > $O/${w}_bench_under_rocprof.json 2>/dev/null

@@ -53,5 +53,5 @@ for k, c in agg.items():
     print(k, {a: round(b / 1e6, 2) for a, b in sorted(c.items())})
 PY
 done
-python $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
+python $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 ls -la $O
