@@ -237,6 +237,8 @@ struct LinKvCtxP { const float* X; int ldx; int x_coff; long xb; int npix; int C
                    int h2_bf16;                             // H2 is bf16 [npix][C]
                    int res_lp;                              // res is stored in the mode's 16-bit type [npix][C] (written by Conv3P::xout_lp)
                    int xout_lp;     long wkv_lo_off = 0;        // split-weight mode: elements from a weight of Wkv to its lo half
+                   int headwaves = 0;                       // the head-parallel form (small grids, linattn_fused.hip), where the build has it
+                   long long* dbg = nullptr;                // optional phase stamps, DEX_TIMING builds only (tools/kvctx_stamps)
 };                          // Xout is written in the mode's 16-bit type (its one reader, the tail kernel, takes LinOut2P::x_lp)
 void launch_linattn_kvctx(const LinKvCtxP& p, int precision, hipStream_t st);
 struct LinMergeP { const float* part_m; const float* part_s; const float* part_c; int nblk;

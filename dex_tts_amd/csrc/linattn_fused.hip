@@ -24,6 +24,132 @@ union LFrag { uint4 u; lp8 v; };
 constexpr float LOG2E_F = 1.4426950408889634f;
 
 
+// Phase stamps of the context pass (-DDEX_TIMING builds only, tools/kvctx_stamps): cycles spent by thread 0 of a workgroup between
+// consecutive stamps, accumulated per phase, written to p.dbg[workgroup * 8 + k] (k = 7: the whole workgroup).
+#ifdef DEX_TIMING
+#define KSTAMP_DECL long long tk[8] = {0, 0, 0, 0, 0, 0, 0, 0}; const long long tk0 = __builtin_readcyclecounter(); long long tlast = tk0;
+#define KSTAMP(k) do { const long long now_ = __builtin_readcyclecounter(); tk[k] += now_ - tlast; tlast = now_; } while (0)
+#define KSTAMP_STORE(n)                                                                                               \
+    if (p.dbg && threadIdx.x == 0) {                                                                                  \
+        long long* d_ = p.dbg + ((long)blockIdx.y * gridDim.x + blockIdx.x) * 8;                                      \
+        for (int k_ = 0; k_ < (n); ++k_) d_[k_] = tk[k_];                                                             \
+        d_[7] = __builtin_readcyclecounter() - tk0;                                                                   \
+    }
+#else
+#define KSTAMP_DECL
+#define KSTAMP(k) do {} while (0)
+#define KSTAMP_STORE(n)
+#endif
+
+// The prologue of one K-step of a lane's x fragment (PRO forms): the 8 raw values in xa / xc (16-bit H2: xa holds all 8) become
+// x = mask * (Mish(GN(h2)) + r)  (identity shortcut)  or  mask * Mish(GN(h2)) + r  (res_conv shortcut), are written to Xout when
+// `live`, and replace xa / xc.  The head-parallel form's copy of the 4-wave form's inline prologue (that form keeps its own code, so the
+// batch sizes run the same instructions as before): the same operations, and the same bits (tests/test_gpu_linattn_headwaves.py).
+__device__ __forceinline__ void kv_prologue8(const LinKvCtxP& p, float4& xa, float4& xc, const float4& ra, const float4& rc, const float* gsc_s,
+                                             const float* gsh_s, int ch, bool hb, bool rlp, bool has_r, bool under, bool xlp, float mkv,
+                                             bool live, long orow) {
+    // Products and sums fuse only where written (fmaf).  Left to the backend, the choice depended on the surrounding code: here it fused
+    // (y + r) less often than in the 4-wave form, and 2.8 % of the fp32 x at 40x256 C = 128 differed in the last bit.  Written out below
+    // are exactly the fusions the backend gives the 4-wave form in every instantiation: (y + r) = fma(t, q, r) under the mask, nothing else.
+#pragma clang fp contract(on)
+    float v[8] = {xa.x, xa.y, xa.z, xa.w, xc.x, xc.y, xc.z, xc.w};
+    if (hb) {
+        const unsigned u0 = __float_as_uint(xa.x), u1 = __float_as_uint(xa.y), u2 = __float_as_uint(xa.z), u3 = __float_as_uint(xa.w);
+        v[0] = lp_lo(u0); v[1] = lp_hi(u0); v[2] = lp_lo(u1); v[3] = lp_hi(u1);
+        v[4] = lp_lo(u2); v[5] = lp_hi(u2); v[6] = lp_lo(u3); v[7] = lp_hi(u3);
+    }
+    float r_[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const float4 sc0 = *reinterpret_cast<const float4*>(gsc_s + ch), sc1 = *reinterpret_cast<const float4*>(gsc_s + ch + 4);
+    const float4 sh0 = *reinterpret_cast<const float4*>(gsh_s + ch), sh1 = *reinterpret_cast<const float4*>(gsh_s + ch + 4);
+    const float gsc[8] = {sc0.x, sc0.y, sc0.z, sc0.w, sc1.x, sc1.y, sc1.z, sc1.w};
+    const float gsh[8] = {sh0.x, sh0.y, sh0.z, sh0.w, sh1.x, sh1.y, sh1.z, sh1.w};
+    if (has_r) {
+        if (rlp) {
+            const unsigned u0 = __float_as_uint(ra.x), u1 = __float_as_uint(ra.y), u2 = __float_as_uint(ra.z), u3 = __float_as_uint(ra.w);
+            r_[0] = lp_lo(u0); r_[1] = lp_hi(u0); r_[2] = lp_lo(u1); r_[3] = lp_hi(u1); r_[4] = lp_lo(u2); r_[5] = lp_hi(u2); r_[6] = lp_lo(u3); r_[7] = lp_hi(u3);
+        } else { r_[0] = ra.x; r_[1] = ra.y; r_[2] = ra.z; r_[3] = ra.w; r_[4] = rc.x; r_[5] = rc.y; r_[6] = rc.z; r_[7] = rc.w; }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float t = fmaf(v[j], gsc[j], gsh[j]);
+        const float e = __expf(fminf(t, 20.f));
+        const float n = e * (e + 2.f);
+        const float q = n * __builtin_amdgcn_rcpf(n + 2.f);         // Mish = t * q (rcp: 1 ulp, bf16 consumers)
+        v[j] = under ? fmaf(t, q, r_[j]) * mkv : fmaf(t * q, mkv, r_[j]);
+    }
+    xa = make_float4(v[0], v[1], v[2], v[3]); xc = make_float4(v[4], v[5], v[6], v[7]);
+    if (live) {
+        if (xlp) {       // 16-bit x for the tail kernel: its q operand rounds x the same way, its residual term reads the rounded value
+            u16* xh = reinterpret_cast<u16*>(p.Xout) + orow * p.C + ch;
+            *reinterpret_cast<uint4*>(xh) = make_uint4(pack2_lp(v[0], v[1]), pack2_lp(v[2], v[3]), pack2_lp(v[4], v[5]), pack2_lp(v[6], v[7]));
+        } else {
+            float* xo = p.Xout + orow * p.C + ch;
+            *reinterpret_cast<float4*>(xo) = xa;
+            *reinterpret_cast<float4*>(xo + 4) = xc;
+        }
+    }
+}
+
+// One head of one 32-pixel sub-tile: k_h and v_h tiles from the x fragments `af` and the k | v rows in LDS (2 x 16 accumulator registers),
+// the running softmax statistics of the head's 32 channels, then ctx_h^T += v_h^T p_h from those registers.  The body of the 4-wave
+// form's head loop, the same operations in the same order, so a (sub-tile, head) state is the same bits in either form.
+// KG > 0: a scheduling fence after every KG K-steps, so the k | v fragments of at most KG steps are in flight (128-register budgets).
+template <int C, bool SEED, int KG = 0>
+__device__ __forceinline__ void kv_head_step(const u16* Ws, int h, int i, int hh, const LFrag* af, const f32x16& kseed, int px0, int npix,
+                                             f32x16& ctx, float& m_run, float& s_run) {
+    constexpr int LDW = C + 8, KS = C / 16;
+    f32x16 kh, vh;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { kh[r] = SEED ? kseed[r] : 0.f; vh[r] = 0.f; }
+    const u16* bk = Ws + (h * 32 + i) * LDW + hh * 8;
+    const u16* bv = Ws + ((4 + h) * 32 + i) * LDW + hh * 8;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        LFrag fk, fv; fk.u = *reinterpret_cast<const uint4*>(bk + ks * 16); fv.u = *reinterpret_cast<const uint4*>(bv + ks * 16);
+        kh = DEX_MFMA_LP(af[ks].v, fk.v, kh, 0, 0, 0);
+        vh = DEX_MFMA_LP(af[ks].v, fv.v, vh, 0, 0, 0);
+#ifdef DEX_LP_WSPLIT
+        LFrag lk, lv; lk.u = *reinterpret_cast<const uint4*>(bk + 256 * LDW + ks * 16); lv.u = *reinterpret_cast<const uint4*>(bv + 256 * LDW + ks * 16);
+        kh = DEX_MFMA_LP(af[ks].v, lk.v, kh, 0, 0, 0);
+        vh = DEX_MFMA_LP(af[ks].v, lv.v, vh, 0, 0, 0);
+#endif
+        if constexpr (KG > 0) { if ((ks + 1) % KG == 0) __builtin_amdgcn_sched_barrier(0); }
+    }
+    // column (channel d = lane&31) max over the 32 pixels of the sub-tile
+    float mx = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        if constexpr (!SEED) { if (px0 + (r & 3) + 8 * (r >> 2) + 4 * hh >= npix) kh[r] = -INFINITY; }
+        mx = fmaxf(mx, kh[r]);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    // fp16 operands: the softmax reference sits 14 octaves BELOW the running maximum, so p = exp(k - ref) spans
+    // [.., 2^14] and a position 2^-38 below the maximum still survives the fp16 rounding of the MFMA operand (over
+    // n = 80*T positions nearly all of them sit far below the maximum); the partial's (m, s, ctx) are consistent
+    // with that reference, so nothing downstream changes.  bf16 has fp32's exponent range: no shift.
+    constexpr float KSHIFT = LP_IS_F16 ? 14.f * 0.69314718056f : 0.f;
+    const float mn = fmaxf(m_run, mx - KSHIFT);
+    const float alpha = __expf(m_run - mn);
+    m_run = mn;
+    const float nmn2 = -mn * LOG2E_F;
+    float ps = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { kh[r] = __builtin_amdgcn_exp2f(fmaf(kh[r], LOG2E_F, nmn2)); ps += kh[r]; }
+    s_run = s_run * alpha + ps;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) ctx[r] *= alpha;
+    // ctx^T[e][d] += sum_px v[px][e] * p[px][d]   (A = v tile regs, B = p tile regs, same pixel order)
+#pragma unroll
+    for (int k2 = 0; k2 < 2; ++k2) {
+        LFrag va, pb;
+        va.u.x = pack2_lp(vh[8 * k2 + 0], vh[8 * k2 + 1]); va.u.y = pack2_lp(vh[8 * k2 + 2], vh[8 * k2 + 3]);
+        va.u.z = pack2_lp(vh[8 * k2 + 4], vh[8 * k2 + 5]); va.u.w = pack2_lp(vh[8 * k2 + 6], vh[8 * k2 + 7]);
+        pb.u.x = pack2_lp(kh[8 * k2 + 0], kh[8 * k2 + 1]); pb.u.y = pack2_lp(kh[8 * k2 + 2], kh[8 * k2 + 3]);
+        pb.u.z = pack2_lp(kh[8 * k2 + 4], kh[8 * k2 + 5]); pb.u.w = pack2_lp(kh[8 * k2 + 6], kh[8 * k2 + 7]);
+        ctx = DEX_MFMA_LP(va.v, pb.v, ctx, 0, 0, 0);
+    }
+}
+
 // grid (nblk, B); 256 threads; each wave owns `nsub` consecutive 32-pixel sub-tiles.
 // part_m/part_s: [B][4][nblk][32], part_c: [B][4][nblk][32 d][32 e]   (same layout linattn_combine reads)
 // FL >= 0 (round 5): the flags of the PRO form as COMPILE-TIME constants - bit 0 h2_bf16, bit 1 res_lp, bit 2 xout_lp, bit 3 res_under_mask.  As
@@ -35,6 +161,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C == 64 ? 2
     constexpr int LDW = C + 8, KS = C / 16;
     extern __shared__ __attribute__((aligned(16))) u16 smem_la[];
     u16* Ws = smem_la;                                       // [256][LDW]  rows: k(4x32) then v(4x32)
+    KSTAMP_DECL
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 31, hh = lane >> 5;
     const int blk = blockIdx.x, b = blockIdx.y;
@@ -120,6 +247,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C == 64 ? 2
             mkv = mrow[(pxr % p.W) * p.mask_ws];
         }
     }
+    KSTAMP(0);
     __shared__ float smean[8], srstd[8];
     __shared__ __attribute__((aligned(16))) float gsc_s[PRO ? C : 4], gsh_s[PRO ? C : 4];   // GroupNorm folded to x*gsc + gsh per channel
     if constexpr (PRO) {
@@ -140,6 +268,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C == 64 ? 2
         }
         __syncthreads();
     }
+    KSTAMP(1);
     for (int sub = 0; sub < p.nsub; ++sub) {
         const int px0 = px_base + sub * 32;
         if (px0 >= p.npix) break;
@@ -224,6 +353,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C == 64 ? 2
                 mkv = mrow[(pxr % p.W) * p.mask_ws];
             }
         }
+        KSTAMP(2);
         // head by head: k_h and v_h tiles (2 x 16 accumulator registers live instead of the 128 of all eight tiles at once -
         // the kernel sat at one wave per SIMD), softmax statistics, then ctx_h += v_h^T p_h from those registers
         // (round 6) SEED forms: the ragged last sub-tile's pixels >= npix enter as -inf seeds of the k accumulators, once per sub-tile,
@@ -286,6 +416,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C == 64 ? 2
             }
             __builtin_amdgcn_sched_barrier(0);            // keep the heads sequential: interleaving them brings all tiles back to life
         }
+        KSTAMP(4);
     }
     // ---- merge the 4 waves of the workgroup through LDS, write one partial per head
     __syncthreads();                                          // weights no longer needed
@@ -301,6 +432,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C == 64 ? 2
         if (hh == 0) { mm[(wave * 4 + h) * 32 + i] = m_run[h]; ms[(wave * 4 + h) * 32 + i] = st; }
     }
     __syncthreads();
+    KSTAMP(5);
     for (int idx = tid; idx < 4 * 1024; idx += 256) {
         const int h = idx >> 10, d = (idx >> 5) & 31, e = idx & 31;
         float M = -INFINITY;
@@ -318,6 +450,233 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C == 64 ? 2
         p.part_c[pidx * 1024 + d * 32 + e] = acc;
         if (e == 0) { p.part_m[pidx * 32 + d] = M; p.part_s[pidx * 32 + d] = s; }
     }
+    KSTAMP(6);
+    KSTAMP_STORE(7)
+}
+
+// Head-parallel form of the same pass for grids below one round of the chip's workgroup slots (B = 1..3: the form above is one long
+// dependent chain per wave - prologue, then four head chains back to back - on 80-160 of the 256 CUs).  The workgroup owns the same
+// 4 x nsub sub-tiles and writes the same partials; it runs 16 waves, wave = (slot, head): slot = the pixel range the form above gives
+// wave `slot`, head = the one head this wave carries through every sub-tile.  Per sub-tile the prologue (GN + Mish + shortcut + mask,
+// the Xout store) is split by channel quarter over the slot's four head-waves, and the bf16 x fragments go through an LDS image
+// [4 slots][2 sub-tile buffers][32 px][C + 8] (double-buffered: one barrier per sub-tile).  Each head-wave then runs kv_head_step for
+// its head - the same instructions on the same fragments as the form above, so every (slot, head) state and every partial is the same
+// bits - and the LDS merge walks the same (h, d, e) space in the same wave order with four times the threads.
+// Not in the split-weight build at C = 128: two weight images (139 KB) and the x image do not fit in the 160 KB of LDS.
+// grid (nblk, B); 1024 threads.
+template <int C, bool PRO, int FL = -1>
+__global__ __launch_bounds__(1024) void linattn_kvctx_hw_kernel(const LinKvCtxP p) {
+    constexpr int LDW = C + 8, KS = C / 16, KQ = KS / 4;      // KQ: K-steps of the prologue per head-wave
+#ifdef DEX_LP_WSPLIT
+    constexpr int NWI = 2;                                     // hi + lo weight images
+#else
+    constexpr int NWI = 1;
+#endif
+    extern __shared__ __attribute__((aligned(16))) u16 smem_la[];
+    u16* Ws = smem_la;                                         // [NWI][256][LDW]  rows: k(4x32) then v(4x32)
+    u16* Xs = smem_la + NWI * 256 * LDW;                       // [4 slots][2][32][LDW]  bf16 x fragments of the current sub-tile
+    KSTAMP_DECL
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int hd = wave & 3, slot = wave >> 2;
+    const int i = lane & 31, hh = lane >> 5;
+    const int blk = blockIdx.x, b = blockIdx.y;
+    const u16* Wg = reinterpret_cast<const u16*>(p.Wkv);       // bf16 [256][C]
+    {
+        uint4 wr[C / 32];
+#pragma unroll
+        for (int j = 0; j < C / 32; ++j) {
+            const int it = tid + 1024 * j;
+            wr[j] = *reinterpret_cast<const uint4*>(Wg + (long)(it / (C / 8)) * C + (it % (C / 8)) * 8);
+        }
+#pragma unroll
+        for (int j = 0; j < C / 32; ++j) {
+            const int it = tid + 1024 * j;
+            *reinterpret_cast<uint4*>(Ws + (it / (C / 8)) * LDW + (it % (C / 8)) * 8) = wr[j];
+        }
+#ifdef DEX_LP_WSPLIT
+#pragma unroll
+        for (int j = 0; j < C / 32; ++j) {
+            const int it = tid + 1024 * j;
+            wr[j] = *reinterpret_cast<const uint4*>(Wg + p.wkv_lo_off + (long)(it / (C / 8)) * C + (it % (C / 8)) * 8);
+        }
+#pragma unroll
+        for (int j = 0; j < C / 32; ++j) {
+            const int it = tid + 1024 * j;
+            *reinterpret_cast<uint4*>(Ws + 256 * LDW + (it / (C / 8)) * LDW + (it % (C / 8)) * 8) = wr[j];
+        }
+#endif
+    }
+    const float* X = PRO ? p.H2 + (long)b * p.npix * C : p.X + (long)b * p.xb + p.x_coff;
+    const int ldx = PRO ? C : p.ldx;
+    const float* R = (PRO && p.res) ? p.res + (long)b * p.resb : nullptr;
+    const float* mrow = PRO ? p.mask + (long)b * p.mask_bstride : nullptr;
+    const int px_base = (blk * 4 + slot) * p.nsub * 32;
+    const int ch0 = hd * KQ * 16 + hh * 8;                     // this lane's first prologue channel
+
+    f32x16 ctxT;
+    float m_run = -INFINITY, s_run = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) ctxT[r] = 0.f;
+    float4 xa[KQ], xc[KQ], ra[PRO ? KQ : 1], rc[PRO ? KQ : 1];
+    float mkv = 1.f;
+    float ga_pre = 0.f, be_pre = 0.f;
+    if constexpr (PRO) { if (tid < C) { ga_pre = p.gamma[tid]; be_pre = p.beta[tid]; } }
+    const bool hb = FL >= 0 ? (FL & 1) != 0 : (PRO && p.h2_bf16 != 0);
+    const bool rlp = FL >= 0 ? (FL & 2) != 0 : (PRO && p.res_lp != 0);
+    const bool xlp = FL >= 0 ? (FL & 4) != 0 : (p.xout_lp != 0);
+    const unsigned short* Rh = (PRO && p.res) ? reinterpret_cast<const unsigned short*>(p.res) + (long)b * p.resb : nullptr;
+    const unsigned short* Xh = PRO ? reinterpret_cast<const unsigned short*>(p.H2) + (long)b * p.npix * C : nullptr;
+    // this lane's quarter of the raw rows of one sub-tile (pixel px0 + i, channels ch0 + 16 ks .. +8)
+    auto load_rows = [&](int px0) {
+        const int pxr = min(px0 + i, p.npix - 1);
+        if (hb) {
+#pragma unroll
+            for (int ks = 0; ks < KQ; ++ks) { xa[ks] = *reinterpret_cast<const float4*>(Xh + (long)pxr * C + ch0 + ks * 16); xc[ks] = xa[ks]; }
+        } else {
+            const float* xr = X + (long)pxr * ldx + ch0;
+#pragma unroll
+            for (int ks = 0; ks < KQ; ++ks) {
+                xa[ks] = *reinterpret_cast<const float4*>(xr + ks * 16);
+                xc[ks] = *reinterpret_cast<const float4*>(xr + ks * 16 + 4);
+            }
+        }
+        if constexpr (PRO) {
+            if (R) {
+                if (rlp) {
+#pragma unroll
+                    for (int ks = 0; ks < KQ; ++ks) { ra[ks] = *reinterpret_cast<const float4*>(Rh + (long)pxr * p.ldres + ch0 + ks * 16); rc[ks] = ra[ks]; }
+                } else {
+                    const float* rr = R + (long)pxr * p.ldres + ch0;
+#pragma unroll
+                    for (int ks = 0; ks < KQ; ++ks) {
+                        ra[ks] = *reinterpret_cast<const float4*>(rr + ks * 16);
+                        rc[ks] = *reinterpret_cast<const float4*>(rr + ks * 16 + 4);
+                    }
+                }
+            }
+            mkv = mrow[(pxr % p.W) * p.mask_ws];
+        }
+    };
+    load_rows(px_base);
+    KSTAMP(0);
+    __shared__ float smean[8], srstd[8];
+    __shared__ __attribute__((aligned(16))) float gsc_s[PRO ? C : 4], gsh_s[PRO ? C : 4];
+    if constexpr (PRO) {
+        if (tid < 256) {   // 8 groups x GN_SLOTS partials == the first 4 waves
+            const int g = tid / GN_SLOTS;
+            const longlong2 sv = *reinterpret_cast<const longlong2*>(p.gn_stats + (((long)b * 8 + g) * GN_SLOTS + (tid % GN_SLOTS)) * 2);
+            long long s1 = sv.x, s2 = sv.y;
+            gn_slots_reduce<GN_SLOTS>(s1, s2);
+            if ((tid % GN_SLOTS) == 0) gn_moments(s1, s2, 1e-5, smean[g], srstd[g]);
+        }
+    }
+    __syncthreads();
+    if constexpr (PRO) {
+        if (tid < C) {
+            const float ga = ga_pre * srstd[tid / (C / 8)];
+            gsc_s[tid] = ga;
+            gsh_s[tid] = be_pre - smean[tid / (C / 8)] * ga;
+        }
+        __syncthreads();
+    }
+    KSTAMP(1);
+    constexpr bool SEED = C == 128 || (FL >= 0 && (FL & 2) != 0);
+    // every wave runs all nsub iterations (the barrier is workgroup-wide); a slot past the end skips the work
+    for (int sub = 0; sub < p.nsub; ++sub) {
+        const int px0 = px_base + sub * 32;
+        const bool act = px0 < p.npix;
+        u16* xs = Xs + ((slot * 2 + (sub & 1)) * 32 + i) * LDW;
+        if (act) {
+            if constexpr (PRO) {
+                const bool under = FL >= 0 ? (FL & 8) != 0 : (p.res_under_mask != 0);
+                const bool live = px0 + i < p.npix;
+                const long orow = (long)b * p.npix + min(px0 + i, p.npix - 1);
+#pragma unroll
+                for (int ks = 0; ks < KQ; ++ks)
+                    kv_prologue8(p, xa[ks], xc[ks], ra[ks], rc[ks], gsc_s, gsh_s, ch0 + ks * 16, hb, rlp, R != nullptr, under, xlp, mkv, live, orow);
+            }
+#pragma unroll
+            for (int ks = 0; ks < KQ; ++ks)
+                *reinterpret_cast<uint4*>(xs + ch0 + ks * 16) =
+                    make_uint4(pack2_lp(xa[ks].x, xa[ks].y), pack2_lp(xa[ks].z, xa[ks].w), pack2_lp(xc[ks].x, xc[ks].y), pack2_lp(xc[ks].z, xc[ks].w));
+            if (sub + 1 < p.nsub) load_rows(px0 + 32);
+        }
+        KSTAMP(2);
+        __syncthreads();                                       // the slot's x image is complete (and the image of sub - 1 is free)
+        KSTAMP(3);
+        if (!act) continue;
+        LFrag af[KS];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) af[ks].u = *reinterpret_cast<const uint4*>(xs + ks * 16 + hh * 8);
+        f32x16 kseed;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) kseed[r] = (SEED && px0 + (r & 3) + 8 * (r >> 2) + 4 * hh >= p.npix) ? -INFINITY : 0.f;
+        kv_head_step<C, SEED, (C == 128 ? 4 : 0)>(Ws, hd, i, hh, af, kseed, px0, p.npix, ctxT, m_run, s_run);   // (C = 128: 128 registers, no spill)
+        KSTAMP(4);
+    }
+    // ---- merge: the same LDS layout and walk as the form above, wave `slot` of that form = slot here
+    __syncthreads();
+    float* mS = reinterpret_cast<float*>(smem_la);             // [4 slots][4 heads][32 d][33]  ctx as [d][e]
+    float* mm = mS + 4 * 4 * 32 * 33;
+    float* ms = mm + 4 * 4 * 32;
+    {
+        const float st = s_run + __shfl_xor(s_run, 32);
+        float* dst = mS + ((slot * 4 + hd) * 32 + i) * 33;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dst[(r & 3) + 8 * (r >> 2) + 4 * hh] = ctxT[r];
+        if (hh == 0) { mm[(slot * 4 + hd) * 32 + i] = m_run; ms[(slot * 4 + hd) * 32 + i] = st; }
+    }
+    __syncthreads();
+    KSTAMP(5);
+    for (int idx = tid; idx < 4 * 1024; idx += 1024) {
+        const int h = idx >> 10, d = (idx >> 5) & 31, e = idx & 31;
+        float M = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) M = fmaxf(M, mm[(w * 4 + h) * 32 + d]);
+        float acc = 0.f, s = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const float mw = mm[(w * 4 + h) * 32 + d];
+            const float f = (mw == -INFINITY) ? 0.f : __expf(mw - M);
+            acc = fmaf(f, mS[((w * 4 + h) * 32 + d) * 33 + e], acc);
+            s = fmaf(f, ms[(w * 4 + h) * 32 + d], s);
+        }
+        const long pidx = ((long)b * 4 + h) * p.nblk + blk;
+        p.part_c[pidx * 1024 + d * 32 + e] = acc;
+        if (e == 0) { p.part_m[pidx * 32 + d] = M; p.part_s[pidx * 32 + d] = s; }
+    }
+    KSTAMP(6);
+    KSTAMP_STORE(7)
+}
+
+// the head-parallel form exists for every C of every build but the split-weight one at C = 128 (LDS)
+static bool kvctx_hw_supported(int C) {
+#ifdef DEX_LP_WSPLIT
+    return C == 64;
+#else
+    return C == 64 || C == 128;
+#endif
+}
+template <int CC>
+static void launch_kvctx_hw(const LinKvCtxP& p, int fl, bool pro, dim3 grid, size_t lds, hipStream_t st) {
+    constexpr int LDS_HW = 144 * 1024;
+    static bool attr = false;
+    if (!attr) {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&linattn_kvctx_hw_kernel<CC, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HW);
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&linattn_kvctx_hw_kernel<CC, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HW);
+#define KVHW_ATTR(F) hipFuncSetAttribute(reinterpret_cast<const void*>(&linattn_kvctx_hw_kernel<CC, true, F>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HW);
+        KVHW_ATTR(1) KVHW_ATTR(3) KVHW_ATTR(5) KVHW_ATTR(7) KVHW_ATTR(9) KVHW_ATTR(11) KVHW_ATTR(13) KVHW_ATTR(15)
+#undef KVHW_ATTR
+        attr = true;
+    }
+#define KVHW_CASE(F) case F: hipLaunchKernelGGL((linattn_kvctx_hw_kernel<CC, true, F>), grid, dim3(1024), lds, st, p); break;
+    switch (fl) {
+        KVHW_CASE(1) KVHW_CASE(3) KVHW_CASE(5) KVHW_CASE(7) KVHW_CASE(9) KVHW_CASE(11) KVHW_CASE(13) KVHW_CASE(15)
+        default:
+            if (pro) hipLaunchKernelGGL((linattn_kvctx_hw_kernel<CC, true>), grid, dim3(1024), lds, st, p);
+            else hipLaunchKernelGGL((linattn_kvctx_hw_kernel<CC, false>), grid, dim3(1024), lds, st, p);
+    }
+#undef KVHW_CASE
 }
 
 void launch_linattn_kvctx(const LinKvCtxP& p, hipStream_t st) {
@@ -345,6 +704,19 @@ void launch_linattn_kvctx(const LinKvCtxP& p, hipStream_t st) {
     dim3 grid(p.nblk, p.B);
     const bool pro = p.H2 != nullptr;
     const int fl = pro ? (p.h2_bf16 != 0 ? 1 : 0) | (p.res_lp != 0 ? 2 : 0) | (p.xout_lp != 0 ? 4 : 0) | (p.res_under_mask != 0 ? 8 : 0) : -1;
+    if (p.headwaves && kvctx_hw_supported(p.C)) {
+        g_last_symbol = "linattn_kvctx_hw_kernel";
+        // weight image(s) + the x image [4][2][32][C + 8]; the merge reuses the same bytes
+        const size_t lds_hw = lds_w + (size_t)4 * 2 * 32 * (p.C + 8) * sizeof(u16);
+        const size_t lds2 = lds_hw > lds_m ? lds_hw : lds_m;
+#ifdef DEX_LP_WSPLIT
+        launch_kvctx_hw<64>(p, fl, pro, grid, lds2, st);
+#else
+        if (p.C == 64) launch_kvctx_hw<64>(p, fl, pro, grid, lds2, st);
+        else launch_kvctx_hw<128>(p, fl, pro, grid, lds2, st);
+#endif
+        return;
+    }
 #define KVCTX_CASE(CC, F) case F: hipLaunchKernelGGL((linattn_kvctx_kernel<CC, true, F>), grid, dim3(256), lds, st, p); break;
 #define KVCTX_LAUNCH(CC)                                                                                                              \
     switch (fl) {                                                                                                                      \
@@ -353,6 +725,7 @@ void launch_linattn_kvctx(const LinKvCtxP& p, hipStream_t st) {
             if (pro) hipLaunchKernelGGL((linattn_kvctx_kernel<CC, true>), grid, dim3(256), lds, st, p);                                \
             else hipLaunchKernelGGL((linattn_kvctx_kernel<CC, false>), grid, dim3(256), lds, st, p);                                   \
     }
+    g_last_symbol = "linattn_kvctx_kernel";
     if (p.C == 64) { KVCTX_LAUNCH(64) } else { KVCTX_LAUNCH(128) }
 #undef KVCTX_LAUNCH
 #undef KVCTX_CASE
