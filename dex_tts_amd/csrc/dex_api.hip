@@ -35,7 +35,7 @@ const char* const KNOB_NAMES[] = {
     "DEX_ATTN_SHARED_W8", "DEX_CONVT_MT", "DEX_CONVT_WGS", "DEX_CONV_DOWN_WGS", "DEX_CONV_REGW", "DEX_CONV_REGW_RES", "DEX_CONV_SMALL_MAX", "DEX_CONV_TH8",
     "DEX_CONV_W8", "DEX_DWCONV_CAP", "DEX_FINAL_CAP", "DEX_FIRST_CAP", "DEX_FIRST_MFMA", "DEX_GEMM_NWALK", "DEX_NWALK_SPLIT", "DEX_NWALK_BM", "DEX_POS_COL", "DEX_POS_COL_MIN",
     "DEX_POS_CT", "DEX_REGW_MIN_TILES", "DEX_REGW_WGS", "DEX_ROWCHAIN64", "DEX_ROWCHAIN64A", "DEX_TIV_CAP", "DEX_TV_CHAIN", "DEX_TIV_FOLD", "DEX_LINATTN_NSUB", "DEX_TV_FOLD", "DEX_OUT2_MIN", "DEX_NWALK_DMA",
-    "DEX_LINATTN_HEADWAVES"};
+    "DEX_LINATTN_HEADWAVES", "DEX_LINATTN_OUT2_HW"};
 constexpr int N_KNOBS = (int)(sizeof(KNOB_NAMES) / sizeof(KNOB_NAMES[0]));
 // value of one variable: a decimal integer; unset, empty or without digits ("true", "on") = KNOB_UNSET, so a typo leaves the default
 // form on instead of silently switching it off
@@ -1105,6 +1105,9 @@ struct Runner {
             LinOut2P o{X.p, X.ld, X.coff, npix * X.ld, (int)npix, X.C, w.wq_frag[x->lpi()], s.mbf, w.bias_eff, out, ldo, ocoff, npix * ldo, B, out_lp ? 1 : 0,
                        out2_lp, ldo2, ocoff2, npix * ldo2, xlp ? 1 : 0};
             o.wq_lo_off = x->lpi() == 2 ? 128L * X.C : 0;
+            // the wave-split tail (4 waves per 32-pixel slot) wherever the direct form would run - the latency regime, B = 1..3 at 40x256;
+            // the throughput form keeps the larger grids (and every 16-bit x / y).  DEX_LINATTN_OUT2_HW: 0 = never, 1 = wherever x and y are fp32.
+            o.hw = knob_or("DEX_LINATTN_OUT2_HW", linattn_out2_lp_out_supported((int)npix, B) ? 0 : 1) != 0 ? 1 : 0;
             run("linattn_out", 4.0 * npix * B * 128.0 * X.C, ((out_lp ? 6.0 : 8.0) - (xlp ? 2.0 : 0.0) + (out2_lp ? 2.0 : 0.0)) * npix * X.C * B, [&] { launch_linattn_out2(o, x->precision, st); });
             return;
         }

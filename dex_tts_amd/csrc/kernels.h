@@ -249,6 +249,8 @@ struct LinOut2P { const float* X; int ldx; int x_coff; long xb; int npix; int C;
                   int y_lp;         // 1: Y is stored in the mode's 16-bit type (throughput form only: linattn_out2_lp_out_supported)
                   void* Y2; int ldy2; int y2_coff; long y2b;   // optional second copy of Y in the mode's 16-bit type (throughput form only): the skip half of the up path's concatenation buffer
                   int x_lp;     long wq_lo_off = 0;         // split-weight mode: elements from a weight of Wq to its lo half
+                  int hw = 0;                               // the wave-split latency form (fp32 X and Y only, linattn_fused.hip) instead of the direct one
+                  long long* dbg = nullptr;                 // optional phase stamps, DEX_TIMING builds only (tools/out2_stamps)
                   };      // 1: X is stored in the mode's 16-bit type [npix][C] (throughput form only; written by LinKvCtxP::xout_lp)
 void launch_linattn_out2(const LinOut2P& p, int precision, hipStream_t st);
 bool linattn_out2_lp_out_supported(int npix, int B);

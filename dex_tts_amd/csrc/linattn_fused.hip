@@ -481,6 +481,14 @@ __global__ __launch_bounds__(1024) void linattn_kvctx_hw_kernel(const LinKvCtxP 
     const int i = lane & 31, hh = lane >> 5;
     const int blk = blockIdx.x, b = blockIdx.y;
     const u16* Wg = reinterpret_cast<const u16*>(p.Wkv);       // bf16 [256][C]
+    // the GroupNorm statistics and affine are requested first: they return ahead of the weights and rows, and the reduce below runs
+    // while the rows are in flight (it waited behind every row before: loads return in order)
+    uint4 sv = make_uint4(0u, 0u, 0u, 0u);
+    float ga_pre = 0.f, be_pre = 0.f;
+    if constexpr (PRO) {
+        if (tid < 8 * GN_SLOTS) sv = *reinterpret_cast<const uint4*>(p.gn_stats + (((long)b * 8 + tid / GN_SLOTS) * GN_SLOTS + (tid % GN_SLOTS)) * 2);
+        if (tid < C) { ga_pre = p.gamma[tid]; be_pre = p.beta[tid]; }
+    }
     {
         uint4 wr[C / 32];
 #pragma unroll
@@ -519,8 +527,6 @@ __global__ __launch_bounds__(1024) void linattn_kvctx_hw_kernel(const LinKvCtxP 
     for (int r = 0; r < 16; ++r) ctxT[r] = 0.f;
     float4 xa[KQ], xc[KQ], ra[PRO ? KQ : 1], rc[PRO ? KQ : 1];
     float mkv = 1.f;
-    float ga_pre = 0.f, be_pre = 0.f;
-    if constexpr (PRO) { if (tid < C) { ga_pre = p.gamma[tid]; be_pre = p.beta[tid]; } }
     const bool hb = FL >= 0 ? (FL & 1) != 0 : (PRO && p.h2_bf16 != 0);
     const bool rlp = FL >= 0 ? (FL & 2) != 0 : (PRO && p.res_lp != 0);
     const bool xlp = FL >= 0 ? (FL & 4) != 0 : (p.xout_lp != 0);
@@ -562,22 +568,24 @@ __global__ __launch_bounds__(1024) void linattn_kvctx_hw_kernel(const LinKvCtxP 
     __shared__ float smean[8], srstd[8];
     __shared__ __attribute__((aligned(16))) float gsc_s[PRO ? C : 4], gsh_s[PRO ? C : 4];
     if constexpr (PRO) {
-        if (tid < 256) {   // 8 groups x GN_SLOTS partials == the first 4 waves
+        if (tid < 8 * GN_SLOTS) {   // 8 groups x GN_SLOTS partials == the first 4 waves
             const int g = tid / GN_SLOTS;
-            const longlong2 sv = *reinterpret_cast<const longlong2*>(p.gn_stats + (((long)b * 8 + g) * GN_SLOTS + (tid % GN_SLOTS)) * 2);
-            long long s1 = sv.x, s2 = sv.y;
+            // first touch through a pinned instruction (conv_gn.h, cv_gn_finish): as a plain move it is hoisted behind the load, and
+            // its s_waitcnt would stall the wave before the weight and row loads are issued
+            long long s1 = (long long)(((unsigned long long)mov_pinned(sv.y) << 32) | mov_pinned(sv.x));
+            long long s2 = (long long)(((unsigned long long)mov_pinned(sv.w) << 32) | mov_pinned(sv.z));
             gn_slots_reduce<GN_SLOTS>(s1, s2);
             if ((tid % GN_SLOTS) == 0) gn_moments(s1, s2, 1e-5, smean[g], srstd[g]);
         }
     }
-    __syncthreads();
+    lds_barrier();                                             // LDS only (weight image, moments): the rows stay in flight
     if constexpr (PRO) {
         if (tid < C) {
             const float ga = ga_pre * srstd[tid / (C / 8)];
             gsc_s[tid] = ga;
             gsh_s[tid] = be_pre - smean[tid / (C / 8)] * ga;
         }
-        __syncthreads();
+        lds_barrier();
     }
     KSTAMP(1);
     constexpr bool SEED = C == 128 || (FL >= 0 && (FL & 2) != 0);
@@ -826,6 +834,7 @@ void launch_linattn_merge(const LinMergeP& p, hipStream_t st) {
 template <int C>
 __global__ __launch_bounds__(256) void linattn_out2_direct_kernel(const LinOut2P p) {
     constexpr int KS1 = C / 16, CT = C / 32;
+    KSTAMP_DECL
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 31, hh = lane >> 5;
     const int b = blockIdx.y;
@@ -848,6 +857,7 @@ __global__ __launch_bounds__(256) void linattn_out2_direct_kernel(const LinOut2P
     for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) w2f[ct][ks] = w2[(ct * 8 + ks) * 64];
+    KSTAMP(0);
     LFrag xf[KS1];
 #pragma unroll
     for (int ks = 0; ks < KS1; ++ks) {
@@ -877,6 +887,7 @@ __global__ __launch_bounds__(256) void linattn_out2_direct_kernel(const LinOut2P
             qf[t * 2 + k2].u.z = pack2_lp(q[8 * k2 + 4], q[8 * k2 + 5]); qf[t * 2 + k2].u.w = pack2_lp(q[8 * k2 + 6], q[8 * k2 + 7]);
         }
     }
+    KSTAMP(2);
     // ---- GEMM2 + epilogue: rows co = ct*32 + (r&3) + 8*(r>>2) + 4*hh  ->  4 consecutive channels per register quad
     float* Y = p.Y + (long)b * p.yb + p.y_coff;
     const bool ok = px0 + i < p.npix;
@@ -897,6 +908,7 @@ __global__ __launch_bounds__(256) void linattn_out2_direct_kernel(const LinOut2P
             LFrag af; af.u = w2f[ct][ks];
             y = DEX_MFMA_LP(af.v, qf[ks].v, y, 0, 0, 0);
         }
+        KSTAMP(4);
         if (ok) {
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
@@ -907,7 +919,153 @@ __global__ __launch_bounds__(256) void linattn_out2_direct_kernel(const LinOut2P
                 *reinterpret_cast<float4*>(Y + (long)(px0 + i) * p.ldy + co) = o;
             }
         }
+        KSTAMP(5);
     }
+    KSTAMP_STORE(7)
+}
+
+// Tail, wave-split latency form (small grids): the direct form's work for one 32-pixel slot spread over the four waves of a workgroup.
+//   x:     wave t loads and rounds K-quarter t of the slot's x fragments (the direct form's pack2_lp), shared through LDS;
+//   GEMM1: wave t computes q^T he tile t - the direct form's chain, same K order and operands (split-weight build: hi then lo per
+//          fragment) - and packs it to the same B fragments, shared through LDS;
+//   GEMM2: wave t < C/32 runs the whole 8-K-step chain of co tile t, then that tile's epilogue (y + residual + bias in the same order).
+// Every output is the direct form's bits.  Each wave fetches only its own Wq tile and W2 co tile (C = 128: 8 + 8 KB instead of 64 KB), all
+// issued at entry; the bias comes through the scalar cache, and at C = 128 the residual of co tile t is wave t's own x quarter (the two
+// pixel halves trade the other half of their 8-channel runs), so that form issues 20 vector loads per wave where the direct one issues 112.
+// At 40x256 the grid covers the CUs instead of 80 of them.  (Four slots per 16-wave workgroup, the same 80 workgroups as the direct form,
+// measured slower: 10.4 against 6.4 us at 40x256 C = 128 - DESIGN.md section 8.)
+// fp32 X and Y only (no x_lp / y_lp / Y2: the direct form's regime).  grid (ceil(npix / 32), B), 256 threads.
+template <int C>
+__global__ __launch_bounds__(256) void linattn_out2_hw_kernel(const LinOut2P p) {
+    constexpr int KS1 = C / 16, CT = C / 32, KQ = KS1 / 4;     // KQ: x K-steps loaded per wave
+    __shared__ uint4 xs[KS1][64], qs[8][64];                   // lane-indexed fragment images: conflict-free b128
+    KSTAMP_DECL
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int t = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i = lane & 31, hh = lane >> 5;
+    const int b = blockIdx.y;
+    const int px0 = blockIdx.x * 32;
+    if (px0 >= p.npix) return;
+    const float* X = p.X + (long)b * p.xb + p.x_coff;
+    const int px = min(px0 + i, p.npix - 1);
+    // every global load of the wave at entry: its x quarter, its Wq tile, its W2 co tile (+ C = 64: its residual rows), the bias
+    float4 xa[KQ], xc[KQ];
+    const float* xr = X + (long)px * p.ldx + hh * 8;
+#pragma unroll
+    for (int k = 0; k < KQ; ++k) {
+        const int ks = t * KQ + k;
+        xa[k] = *reinterpret_cast<const float4*>(xr + ks * 16);
+        xc[k] = *reinterpret_cast<const float4*>(xr + ks * 16 + 4);
+    }
+    const uint4* wq = reinterpret_cast<const uint4*>(p.Wq) + lane;                  // bf16, fragment order [he tile][K-step][lane][8]
+    uint4 wqf[KS1];
+#ifdef DEX_LP_WSPLIT
+    uint4 wql[KS1];
+#endif
+#pragma unroll
+    for (int ks = 0; ks < KS1; ++ks) {
+        wqf[ks] = wq[(t * KS1 + ks) * 64];
+#ifdef DEX_LP_WSPLIT
+        wql[ks] = wq[(t * KS1 + ks) * 64 + p.wq_lo_off / 8];                         // the lo half of the same fragment
+#endif
+    }
+    const bool g2 = t < CT;                                     // (uniform) this wave owns co tile t
+    const int ct = g2 ? t : 0;
+    const uint4* w2 = reinterpret_cast<const uint4*>(p.W2) + (long)b * CT * 8 * 64 + lane;
+    uint4 w2f[8];
+    float4 res[4], bia[4];
+    if (g2) {
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) w2f[ks] = w2[(ct * 8 + ks) * 64];
+        if constexpr (C != 128) {
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) res[g4] = *reinterpret_cast<const float4*>(X + (long)px * p.ldx + ct * 32 + 8 * g4 + 4 * hh);
+        }
+        // the bias through the scalar cache: a uniform load of the tile's 32 channels, then each half keeps its 4 of every 8 (a bit blend:
+        // written as a select, the pair of loads was folded into ONE load from a selected address - a private array in scratch)
+        const float4* bt = reinterpret_cast<const float4*>(p.bias + ct * 32);
+        const unsigned hm = 0u - (unsigned)hh;
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+            const float4 b0 = bt[2 * g4], b1 = bt[2 * g4 + 1];
+            bia[g4] = make_float4(__uint_as_float((__float_as_uint(b1.x) & hm) | (__float_as_uint(b0.x) & ~hm)),
+                                  __uint_as_float((__float_as_uint(b1.y) & hm) | (__float_as_uint(b0.y) & ~hm)),
+                                  __uint_as_float((__float_as_uint(b1.z) & hm) | (__float_as_uint(b0.z) & ~hm)),
+                                  __uint_as_float((__float_as_uint(b1.w) & hm) | (__float_as_uint(b0.w) & ~hm)));
+        }
+    }
+    KSTAMP(0);
+    // ---- x quarter -> the slot's fragment image
+#pragma unroll
+    for (int k = 0; k < KQ; ++k) {
+        LFrag f;
+        f.u.x = pack2_lp(xa[k].x, xa[k].y); f.u.y = pack2_lp(xa[k].z, xa[k].w);
+        f.u.z = pack2_lp(xc[k].x, xc[k].y); f.u.w = pack2_lp(xc[k].z, xc[k].w);
+        xs[t * KQ + k][lane] = f.u;
+    }
+    if constexpr (C == 128) {
+        // wave t's x quarter is channels 32t .. 32t + 31 of its pixel = the residual of co tile t: lane half hh holds channels
+        // 16k + 8hh + 0..7 (k = 0, 1) and needs 8 g4 + 4hh + 0..3; the halves swap the 4 channels the other one needs (exact copies)
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const float4 snd = hh ? xa[k] : xc[k];
+            float4 rcv;
+            rcv.x = __shfl_xor(snd.x, 32); rcv.y = __shfl_xor(snd.y, 32); rcv.z = __shfl_xor(snd.z, 32); rcv.w = __shfl_xor(snd.w, 32);
+            res[2 * k] = hh ? rcv : xa[k];
+            res[2 * k + 1] = hh ? xc[k] : rcv;
+        }
+    }
+    lds_barrier();                                             // LDS only: the Wq, W2, residual and bias loads stay in flight
+    KSTAMP(1);
+    // ---- GEMM1: q^T he tile t
+    {
+        f32x16 q;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) q[r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS1; ++ks) {
+            LFrag af, xf; af.u = wqf[ks]; xf.u = xs[ks][lane];
+            q = DEX_MFMA_LP(af.v, xf.v, q, 0, 0, 0);
+#ifdef DEX_LP_WSPLIT
+            LFrag al; al.u = wql[ks];
+            q = DEX_MFMA_LP(al.v, xf.v, q, 0, 0, 0);
+#endif
+        }
+#pragma unroll
+        for (int k2 = 0; k2 < 2; ++k2) {
+            LFrag f;
+            f.u.x = pack2_lp(q[8 * k2 + 0], q[8 * k2 + 1]); f.u.y = pack2_lp(q[8 * k2 + 2], q[8 * k2 + 3]);
+            f.u.z = pack2_lp(q[8 * k2 + 4], q[8 * k2 + 5]); f.u.w = pack2_lp(q[8 * k2 + 6], q[8 * k2 + 7]);
+            qs[t * 2 + k2][lane] = f.u;
+        }
+    }
+    KSTAMP(2);
+    lds_barrier();
+    KSTAMP(3);
+    if (!g2) return;
+    // ---- GEMM2 + epilogue of co tile t: rows co = ct*32 + (r&3) + 8*(r>>2) + 4*hh  ->  4 consecutive channels per register quad
+    f32x16 y;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) y[r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+        LFrag af, qf; af.u = w2f[ks]; qf.u = qs[ks][lane];
+        y = DEX_MFMA_LP(af.v, qf.v, y, 0, 0, 0);
+    }
+    KSTAMP(4);
+    float* Y = p.Y + (long)b * p.yb + p.y_coff;
+    if (px0 + i < p.npix) {
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+            const int co = ct * 32 + 8 * g4 + 4 * hh;
+            float4 o;
+            o.x = y[g4 * 4 + 0] + res[g4].x + bia[g4].x; o.y = y[g4 * 4 + 1] + res[g4].y + bia[g4].y;
+            o.z = y[g4 * 4 + 2] + res[g4].z + bia[g4].z; o.w = y[g4 * 4 + 3] + res[g4].w + bia[g4].w;
+            *reinterpret_cast<float4*>(Y + (long)(px0 + i) * p.ldy + co) = o;
+        }
+    }
+    KSTAMP(5);
+    KSTAMP_STORE(7)
 }
 // Tail, throughput form (large grids: +1.2 % end to end at B=32): y = x + W2 (Wq x) + g*b per pixel, two chained MFMA GEMMs computed TRANSPOSED so that no operand ever
 // needs a layout change:  q^T[he][px] = Wq[he][:] . x[px][:]  (A = Wq rows, B = x rows),  then
@@ -1063,6 +1221,14 @@ void launch_linattn_out2(const LinOut2P& p, hipStream_t st) {
     if (!attr) {
         hipFuncSetAttribute(reinterpret_cast<const void*>(&linattn_out2_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)4 * 32 * 132 * sizeof(float)));
         attr = true;
+    }
+    const bool lp_io = p.x_lp || p.y_lp || p.Y2;
+    if (p.hw && !lp_io) {                              // the wave-split latency form (launcher: DEX_LINATTN_OUT2_HW)
+        g_last_symbol = "linattn_out2_hw_kernel";
+        const dim3 g1((p.npix + 31) / 32, p.B);
+        if (p.C == 64) hipLaunchKernelGGL(linattn_out2_hw_kernel<64>, g1, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL(linattn_out2_hw_kernel<128>, g1, dim3(256), 0, st, p);
+        return;
     }
     if ((long)grid.x * p.B < out2_min_wgs()) {        // latency regime: the direct form
         if (p.C == 64) hipLaunchKernelGGL(linattn_out2_direct_kernel<64>, grid, dim3(256), 0, st, p);
