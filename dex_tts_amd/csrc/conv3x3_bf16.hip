@@ -146,8 +146,8 @@ __device__ __forceinline__ void cv_res_store(const Conv3P& p, const f32x16 (&acc
     }
 }
 
-// CC channels per chunk, output-channel slice [slice*NSL, +NSL) of COUT, TH rows (waves: TH x (4/TH)).
-// grid.z = b * (COUT/NSL) + slice.
+// CC channels per chunk, output-channel slice [slice*NSL, +NSL) of COUT, TH rows (waves: TH x (NW/TH); wave = one row x NSL/(NW/TH)
+// channels).  grid.z = b * (COUT/NSL) + slice.
 template <int CC, int COUT, int NSL, int TH, bool PRO2 = false, bool RES = false, bool XB = false, int NW = 4>
 __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
     constexpr int PW = 34, PH = TH + 2;
@@ -158,10 +158,17 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
     constexpr int NSLICE = COUT / NSL;
     constexpr int ITEMS = PH * PW * (CC / 8);            // 8-channel patch items
     constexpr int NI = (ITEMS + NTHR - 1) / NTHR;        // per thread
-    constexpr int WPT = NSL * CC / 8 / NTHR;             // weight items (16 B) per thread per tap
+    constexpr int WITEMS = NSL * CC / 8;                 // weight items (16 B) per tap
+    constexpr int WPT = (WITEMS + NTHR - 1) / NTHR;      // ... per thread
+    constexpr bool WFULL = WITEMS % NTHR == 0;           // (the one-round forms: whole waves past WITEMS stage no weights)
     constexpr int RING = CC == 128 ? (PRO2 ? 1 : 2) : 3;  // taps of weights in flight ahead of the MFMAs
-    constexpr int NPASS = CC == 128 ? (TH == 8 ? (PRO2 ? 8 : 4) : (PRO2 ? 5 : 2)) : (PRO2 ? 3 : 1);   // patch staging passes: 128-channel chunks (or two source tensors) would need >256 registers in one
-    constexpr int NIP = (NI + NPASS - 1) / NPASS;        // (1 workgroup per CU instead of 2: measured 16 -> 22 us at 40x256)
+    // patch staging passes: 128-channel chunks (or two source tensors) would need >256 registers in one (1 workgroup per CU instead
+    // of 2: measured 16 -> 22 us at 40x256).  The 5-row one-round forms: at Cin 128 (five waves, 256 registers) the items per pass of
+    // the 2-row forms; at Cin 64 (ten waves: three per SIMD, 168 registers) 1 / 2 / 3 items per pass for PRO2 / fp32 / bf16 input -
+    // one pass more and the fused-tail form spills (16 - 124 B per lane), the fp32-input form of the split-weight build 16 B.
+    constexpr int NPASS = TH == 5 ? (CC == 128 ? (PRO2 ? 6 : 3) : (PRO2 ? 3 : XB ? 1 : 2))
+                                  : CC == 128 ? (TH == 8 ? (PRO2 ? 8 : 4) : (PRO2 ? 5 : 2)) : (PRO2 ? 3 : 1);
+    constexpr int NIP = (NI + NPASS - 1) / NPASS;
 #ifdef DEX_LP_WSPLIT
     // split weights: the nine taps run twice over the same patch - taps 9..17 are the lo halves of the weights, p.w_lo_off elements
     // behind their hi halves (same [COUT][9*Cin] layout); the 1x1 shortcut's lo half replaces its hi half in rbuf after the centre tap.
@@ -175,7 +182,7 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
 #else
     constexpr int NTAP = 9;
 #endif
-    static_assert(NT >= 1 && WPT >= 1, "tile");
+    static_assert(NT >= 1 && WPT >= 1 && NW % TH == 0 && NTHR % (CC / 8) == 0, "tile");
     extern __shared__ __attribute__((aligned(16))) u16 smem[];
     u16* patch = smem;                                // [PH*PW][LDP]
     u16* wbuf = smem + PH * PW * LDP;                 // [2][NSL][LDP]
@@ -247,14 +254,16 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
     }
     // weight item j of this thread: output channel wn[j], 8 input channels at wc8[j] (same for every tap)
     int wofs[WPT], wlds[WPT];
+    bool wok[WPT];
 #pragma unroll
     for (int j = 0; j < WPT; ++j) {
         const int it = tid + NTHR * j;
         const int n = it / (CC / 8), c8 = (it % (CC / 8)) * 8;
         wofs[j] = n * K + c8;
         wlds[j] = n * LDP + c8;
+        wok[j] = WFULL || it < WITEMS;
     }
-    const int pc8 = (tid % (CC / 8)) * 8;             // 256 % (CC/8) == 0: a thread's patch items share one channel chunk
+    const int pc8 = (tid % (CC / 8)) * 8;             // NTHR % (CC/8) == 0: a thread's patch items share one channel chunk
 
     CvGnLoads gnl{};
     if (pro) gnl = cv_gn_issue(p, b, tid, step);
@@ -306,6 +315,7 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
 #pragma unroll
                     for (int j = 0; j < WPT; ++j) {
                         const int it = tid + NTHR * j;
+                        if (!wok[j]) continue;
                         rwr[j] = *reinterpret_cast<const u32x4*>(Rg + (long)(it / (CC / 8)) * p.Cin + cbase + (it % (CC / 8)) * 8);
 #ifdef DEX_LP_WSPLIT
                         rwl[j] = *reinterpret_cast<const u32x4*>(Rg + p.res_lo_off + (long)(it / (CC / 8)) * p.Cin + cbase + (it % (CC / 8)) * 8);
@@ -313,11 +323,11 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
                     }
                 }
 #pragma unroll
-                for (int j = 0; j < WPT; ++j) w0r[j] = *reinterpret_cast<const u32x4*>(Wg + wofs[j] + cbase);
+                for (int j = 0; j < WPT; ++j) if (wok[j]) w0r[j] = *reinterpret_cast<const u32x4*>(Wg + wofs[j] + cbase);
 #pragma unroll
                 for (int s = 0; s < RING; ++s)
 #pragma unroll
-                    for (int j = 0; j < WPT; ++j) wr[s][j] = *reinterpret_cast<const u32x4*>(Wg + wofs[j] + WS_TAPOFS(s + 1) + cbase);
+                    for (int j = 0; j < WPT; ++j) if (wok[j]) wr[s][j] = *reinterpret_cast<const u32x4*>(Wg + wofs[j] + WS_TAPOFS(s + 1) + cbase);
                 CSTAMP(0);
                 if (pro && ch == 0) cv_gn_finish<COEF_N>(p, gnl, tid, coef);
                 __builtin_amdgcn_sched_barrier(0);
@@ -375,10 +385,10 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
             }
         }
 #pragma unroll
-        for (int j = 0; j < WPT; ++j) *reinterpret_cast<u32x4*>(wbuf + wlds[j]) = w0r[j];
+        for (int j = 0; j < WPT; ++j) if (wok[j]) *reinterpret_cast<u32x4*>(wbuf + wlds[j]) = w0r[j];
         if constexpr (RES) {
 #pragma unroll
-            for (int j = 0; j < WPT; ++j) *reinterpret_cast<u32x4*>(rbuf + wlds[j]) = rwr[j];
+            for (int j = 0; j < WPT; ++j) if (wok[j]) *reinterpret_cast<u32x4*>(rbuf + wlds[j]) = rwr[j];
         }
         CSTAMP(2);
         // ---- nine taps; tap t's weights sit in wbuf[t & 1], taps t+1 .. t+RING are in registers / in flight
@@ -389,11 +399,11 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
             if (tt + 1 < NTAP) {
                 u16* wn = wbuf + ((tt + 1) & 1) * NSL * LDP;
 #pragma unroll
-                for (int j = 0; j < WPT; ++j) *reinterpret_cast<u32x4*>(wn + wlds[j]) = wr[tt % RING][j];
+                for (int j = 0; j < WPT; ++j) if (wok[j]) *reinterpret_cast<u32x4*>(wn + wlds[j]) = wr[tt % RING][j];
                 if (tt + 1 + RING < NTAP) {
 #pragma unroll
                     for (int j = 0; j < WPT; ++j)
-                        wr[tt % RING][j] = *reinterpret_cast<const u32x4*>(Wg + wofs[j] + WS_TAPOFS(tt + 1 + RING) + cbase);
+                        if (wok[j]) wr[tt % RING][j] = *reinterpret_cast<const u32x4*>(Wg + wofs[j] + WS_TAPOFS(tt + 1 + RING) + cbase);
                 }
                 __builtin_amdgcn_sched_barrier(0);    // the refill loads issue before the MFMAs, not dripped between them
             }
@@ -401,7 +411,7 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
             if constexpr (RES) {
                 if (tt == 5) {                        // every wave is past the centre tap (barrier above): the shortcut's lo half for tap 13
 #pragma unroll
-                    for (int j = 0; j < WPT; ++j) *reinterpret_cast<u32x4*>(rbuf + wlds[j]) = rwl[j];
+                    for (int j = 0; j < WPT; ++j) if (wok[j]) *reinterpret_cast<u32x4*>(rbuf + wlds[j]) = rwl[j];
                 }
             }
 #endif
@@ -437,6 +447,10 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
     if (p.dbg && tid == 0) {
         long long* d = p.dbg + ((long)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 8;
         for (int k = 0; k < 5; ++k) d[k] = tk[k];
+        unsigned hw, xcc;                             // where the workgroup ran: CU / SIMD / wave slot, and the XCD
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        d[5] = hw; d[6] = xcc & 15u;
         d[7] = __builtin_readcyclecounter() - tk0;
     }
 #endif
@@ -511,6 +525,44 @@ bool conv3x3_cat_lp_in_supported(int H, int W, int B, int Cin, int Cout) {
     return w8 && tiles4 >= small_max;
 }
 
+// One-round forms of the small grids (B = 1 at T <= 512).  The 2- and 4-row forms deal 320 workgroups to 256 CUs at 80x512 (64 -> 64)
+// and at 40x256 (Cout 128): two workgroups fit per CU, so some CUs run two at once and issue twice the patch and weight bytes (the
+// load issue is what these launches are bound by), and the launch waits for them.  5-row tiles - ten waves of one row x
+// 32 channels at Cout 64, and 32-channel output slices of five row-waves for 64 -> 128 - give 256 workgroups there, one per CU.  Taken
+// where that grid fits one round of the device's CUs and the current form's grid does not; DEX_CONV_ROUND1=0 keeps the current form.
+// Same chunks, taps and K steps per output element on the same MFMA as the 2- / 4-row forms: the same bits.  Measured (tools/convbench
+// b1): 12.7 -> 10.2 / 15.5 -> 12.1 / 11.5 -> 9.6 us at 80x512 (PRO / fused tail / plain), 9.8 -> 8.7 (64 -> 128 + shortcut) at 40x256;
+// five waves of one row x 64 channels at 80x512 gained a third of that.  Kept on the current forms: 128 -> 128 (the same 5 x 32 slices
+// on five waves: 13.6 -> 13.2 us back to back but 13.6 -> 14.2 in the sampler's step, and 15.6 -> 16.9 for the fused tail - one SIMD
+// holds two 72-MFMA waves, as on a doubled CU before) and, in the split-weight build, the 64 -> 64 fused tail (ten waves leave 168
+// registers, and its 18-tap form spills at that).
+static bool launch_c3_round1(const Conv3P& p, bool small, hipStream_t st) {
+    if (!knob_or("DEX_CONV_ROUND1", 1)) return false;
+    const bool tail_ = p.pro_res != nullptr;
+#ifdef DEX_LP_WSPLIT
+    const bool c64 = p.Cin == 64 && p.Cout == 64 && !p.res_w && !tail_;          // the 64 -> 64 forms (NSL 64, one slice)
+#else
+    const bool c64 = p.Cin == 64 && p.Cout == 64 && !p.res_w;
+#endif
+    const bool r128 = p.Cin == 64 && p.Cout == 128 && p.res_w && !tail_ && !p.x_bf16;   // 64 -> 128 with the fused shortcut
+    if (!c64 && !r128) return false;
+    const long strips = (long)((p.W + 31) / 32) * p.B;
+    const long cur = c64 ? strips * (small ? (p.H + 1) / 2 : (p.H + 3) / 4) : strips * (small ? (p.H + 1) / 2 * 2 : (p.H + 3) / 4);   // (64 -> 128: NSL 64 / 128)
+    const long one = strips * ((p.H + 4) / 5) * (c64 ? 1 : 4);
+    const long ncu = device_cus();
+    if (cur <= ncu || one > ncu || one * 4 < ncu * 3) return false;      // (and it keeps three quarters of the CUs busy: 40x400 at T = 800
+                                                                         // would put its 64 -> 64 convs on 104 CUs)
+    if (c64) {
+#ifndef DEX_LP_WSPLIT
+        if (tail_) { p.x_bf16 ? launch_c3<64, 64, 64, 5, true, false, true, 10>(p, st) : launch_c3<64, 64, 64, 5, true, false, false, 10>(p, st); return true; }
+#endif
+        p.x_bf16 ? launch_c3<64, 64, 64, 5, false, false, true, 10>(p, st) : launch_c3<64, 64, 64, 5, false, false, false, 10>(p, st);
+    } else {
+        launch_c3<64, 128, 32, 5, false, true, false, 5>(p, st);
+    }
+    return true;
+}
+
 void launch_conv3x3_lp(const Conv3P& p, hipStream_t st) {
     if (const int tpw = conv3x3_stream_tiles(p)) { launch_conv3x3_stream(p, tpw, st); return; }   // batched synthesis
     if (conv3x3_regw_form(p)) { launch_conv3x3_regw(p, st); return; }                              // 128-channel layers, batched synthesis
@@ -551,6 +603,7 @@ void launch_conv3x3_lp(const Conv3P& p, hipStream_t st) {
         p.x_bf16 ? launch_c3<128, 64, 64, 4, false, true, true, 8>(p, st) : launch_c3<128, 64, 64, 4, false, true, false, 8>(p, st);
         return;
     }
+    if (launch_c3_round1(p, small, st)) return;
     if (p.x_bf16) {       // raw conv output stored as bf16: the GroupNorm-prologue forms with Cin == Cout (conv3x3_bf16_xb_supported)
         if (tail_) {
             if (p.Cin == 64) { small ? launch_c3<64, 64, 64, 2, true, false, true>(p, st) : launch_c3<64, 64, 64, 4, true, false, true>(p, st); }
