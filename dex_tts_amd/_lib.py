@@ -26,6 +26,15 @@ class DexConfig(C.Structure):
                 ("dit_conv_pos", C.c_int32), ("dit_conv_pos_groups", C.c_int32)]
 
 
+TABLES_SCALED, TABLES_CHURN = 1, 2                # DexSamplerTables.flags
+TABLE_EVAL_COLS, TABLE_STEP_COLS = 8, 4
+
+
+class DexSamplerTables(C.Structure):
+    _fields_ = [("sigma_dev", C.c_void_p), ("coef_dev", C.c_void_p), ("step_dev", C.c_void_p), ("n_rows", C.c_int32),
+                ("flags", C.c_uint32)]
+
+
 class DexSampleArgs(C.Structure):
     _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("n_steps", C.c_int32),
                 ("z_dev", C.c_void_p), ("mu_dev", C.c_void_p), ("mask_dev", C.c_void_p), ("sigmas_dev", C.c_void_p),
@@ -34,7 +43,8 @@ class DexSampleArgs(C.Structure):
                 ("sty_dev", C.c_void_p), ("sty_lengths_dev", C.c_void_p), ("Ts", C.c_int32),
                 ("out_dev", C.c_void_p), ("workspace_dev", C.c_void_p), ("workspace_bytes", C.c_size_t),
                 ("use_graph", C.c_int32), ("solver", C.c_int32),
-                ("noise_dev", C.c_void_p), ("S_churn", C.c_float), ("S_min", C.c_float), ("S_max", C.c_float), ("S_noise", C.c_float)]
+                ("noise_dev", C.c_void_p), ("S_churn", C.c_float), ("S_min", C.c_float), ("S_max", C.c_float), ("S_noise", C.c_float),
+                ("tables", C.POINTER(DexSamplerTables))]
 
 
 class DexVocoderConfig(C.Structure):

@@ -651,6 +651,7 @@ struct Plan {
     float* tiv_aff;                            // TIV adaptor folded into the patch embedding's load: [B][2][mid] coefficients (launch_tiv_coef)
     void *tv_kp, *tv_vtp; int tv_nkpad;        // the one-launch TV adaptor's 16-bit key / value operands (TvKvPrepP)
     float *tv_G, *tv_Vp, *tv_g0, *tv_v0p, *tv_xmean;   // its folded form (TvFold2P): G = K W_q, V' = V W_l^T ([B][Ts + 1][mid], row 0 unused), the time token's rows per step, the IN2d means
+    float* xin;                                // ablation tables with DEX_TABLES_SCALED: the network's input x / s (the last buffer of the plan)
     size_t bytes;
 };
 
@@ -827,6 +828,7 @@ void make_plan(const DexCtx* x, const Dims& d, void* ws, Plan& P) {
         P.tv_G = A.f((size_t)B * (d.Ts + 1) * mid); P.tv_Vp = A.f((size_t)B * (d.Ts + 1) * mid);
         P.tv_g0 = A.f((size_t)n * mid); P.tv_v0p = A.f((size_t)n * mid); P.tv_xmean = A.f((size_t)B * mid);
     }
+    P.xin = A.f((size_t)B * 80 * d.T);          // (last, so that every other buffer keeps its offset)
     P.bytes = (A.off + 255) & ~size_t(255);
 }
 
@@ -841,6 +843,9 @@ struct Runner {
     gnfix_t* stats_other = nullptr;   // arena to clear for the next step (eager mode), or null
     int fin_mode = 0;               // FinalP::mode of this network evaluation (Heun predictor / corrector)
     const float* fin_htab = nullptr;
+    const float* fin_gtab = nullptr;        // ablation tables: the general update (final_kernel<true>) with these rows, ...
+    const float* fin_xstate = nullptr;      // ... the state x of this evaluation (xcur is its network input x / s) ...
+    float* fin_xin_next = nullptr;          // ... and where the next evaluation's input goes (scaled tables), or null
 
     template <typename F> void run(const char* name, double flops, double bytes, F&& f) {
         if (x->prof_on) {
@@ -1565,7 +1570,7 @@ struct Runner {
         gnfix_t* stf = next_stats();
         const bool hfb = h_bf16() && fast_conv(c.dim, c.dim) && x->lp_of().count(x->fin_w);
         conv3x3("conv3x3", U, 80, P.d.T, 1, true, x->fin_w, x->fin_b, c.dim, P.hF, stf, nullptr, nullptr, nullptr, false, hfb);
-        FinalP f{};
+        FinalGP f{};
         f.x_bf16 = hfb ? x->lp_kind() : 0;
         f.X = P.hF; f.xb = 80L * P.d.T * c.dim; f.npix = 80 * P.d.T; f.W = P.d.T; f.C = c.dim; f.groups = 8; f.stats = stf;
         f.gamma = x->fin_g; f.beta = x->fin_be; f.mask = mask; f.mask_bstride = P.d.T; f.wfc = x->fconv_w; f.bfc = x->fconv_b;
@@ -1573,7 +1578,9 @@ struct Runner {
         f.zero_ptr = reinterpret_cast<float*>(stats_other); f.zero_n = P.stats_bytes / (long)sizeof(float);
         f.poison = P.xflag ? reinterpret_cast<const int*>(P.xflag + (P.xflag_bytes - sizeof(int)) / sizeof(unsigned)) : nullptr;
         f.mode = fin_mode; f.htab = fin_htab; f.dbuf = P.dbuf; f.xhat = P.xbuf;
-        run("final_conv_euler", 14.0 * 80 * P.d.T * c.dim * B, 80.0 * P.d.T * ((hfb ? 2.0 : 4.0) * c.dim + 12.0) * B, [&] { launch_final(f, st); });
+        f.gtab = fin_gtab; f.xstate = fin_xstate; f.xin_next = fin_xin_next;
+        run("final_conv_euler", 14.0 * 80 * P.d.T * c.dim * B, 80.0 * P.d.T * ((hfb ? 2.0 : 4.0) * c.dim + 12.0) * B,
+            [&] { if (fin_gtab) launch_final_general(f, st); else launch_final(f, st); });
     }
 
     // conditioning tables for every Euler step (depend only on sigma_i)
@@ -1659,10 +1666,18 @@ int validate(DexCtx* x, const DexSampleArgs* a, bool need_z) {
     if (a->B < 1 || a->T < 4 || (a->T % 4) != 0) return x->fail(DEX_ERR_ARG, "T (%d) must be a positive multiple of 4 (fix_len_compatibility), B >= 1", a->T);
     if ((a->T >> (x->cfg.n_stages - 1)) * (1 << (x->cfg.n_stages - 1)) != a->T) return x->fail(DEX_ERR_ARG, "T must be divisible by 2^(n_stages-1)");
     if (need_z && a->n_steps < 2) return x->fail(DEX_ERR_ARG, "n_steps must be >= 2 (edm.py:157 divides by num_steps - 1)");
-    if (!a->mu_dev || !a->mask_dev || !a->sigmas_dev || !a->out_dev || !a->workspace_dev) return x->fail(DEX_ERR_ARG, "null device pointer");
+    const bool tables = need_z && a->tables;          // (dex_denoise_once ignores the tables)
+    if (!a->mu_dev || !a->mask_dev || (!a->sigmas_dev && !tables) || !a->out_dev || !a->workspace_dev) return x->fail(DEX_ERR_ARG, "null device pointer");
     if (need_z && !a->z_dev) return x->fail(DEX_ERR_ARG, "z_dev is null");
-    if (need_z && a->S_churn < 0.f) return x->fail(DEX_ERR_ARG, "S_churn must be >= 0");
-    if (need_z && a->S_churn > 0.f && !a->noise_dev) return x->fail(DEX_ERR_ARG, "S_churn > 0 needs noise_dev ([n_steps][B,80,T] draws of randn_like, edm.py:196)");
+    if (need_z && !tables && a->S_churn < 0.f) return x->fail(DEX_ERR_ARG, "S_churn must be >= 0");
+    if (need_z && !tables && a->S_churn > 0.f && !a->noise_dev) return x->fail(DEX_ERR_ARG, "S_churn > 0 needs noise_dev ([n_steps][B,80,T] draws of randn_like, edm.py:196)");
+    if (tables) {
+        const DexSamplerTables* tb = a->tables;
+        if (!tb->sigma_dev || !tb->coef_dev || !tb->step_dev) return x->fail(DEX_ERR_ARG, "DexSamplerTables: null table pointer");
+        if (tb->n_rows != dex_num_evals(a->n_steps, a->solver))
+            return x->fail(DEX_ERR_ARG, "DexSamplerTables: n_rows (%d) must be dex_num_evals(n_steps, solver) = %d", tb->n_rows, dex_num_evals(a->n_steps, a->solver));
+        if (tb->flags & ~(uint32_t)(DEX_TABLES_SCALED | DEX_TABLES_CHURN)) return x->fail(DEX_ERR_ARG, "DexSamplerTables: unknown flags 0x%x", tb->flags);
+    }
     if (x->cfg.n_spks > 1 && !a->spk_dev) return x->fail(DEX_ERR_ARG, "spk_dev required when n_spks > 1");
     if (x->cfg.variant == DEX_VARIANT_DEX) {
         if (!a->ref_skips_dev || !a->sty_dev || !a->sty_lengths_dev || a->Tr < 2 || a->Ts < 1 || a->n_ref < 1 || a->n_ref > 7)
@@ -1733,6 +1748,55 @@ int enqueue_euler(DexCtx* x, const DexSampleArgs* a, hipStream_t st) {
         R.step(nullptr, P.xbuf);
     }
     R.run("copy_out", 0, 8.0 * nx, [&] { launch_scale_copy(P.xbuf, a->out_dev, nx, nullptr, st); });      // (a kernel node like every other link of a captured call: see zero_fill)
+    return DEX_OK;
+}
+
+// The general ablation_sampler (edm.py:109-216) from the host's tables (DexSamplerTables): any discretization / schedule / scaling /
+// alpha, Euler or Heun.  Evaluation e reads row e everywhere: cond_prep its sigma, the update (final_kernel<true>) its coefficients.
+// The launches per evaluation are those of enqueue_euler / enqueue_heun; the x_hat update of a step runs only under DEX_TABLES_CHURN,
+// and with DEX_TABLES_SCALED the network reads x / s from P.xin, which the kernel before it writes (init, x_hat update or the last update).
+int enqueue_tables(DexCtx* x, const DexSampleArgs* a, hipStream_t st) {
+    const DexSamplerTables* tb = a->tables;
+    const int n = a->n_steps, E = tb->n_rows;
+    const bool heun = a->solver == DEX_SOLVER_HEUN;
+    const bool scaled = (tb->flags & DEX_TABLES_SCALED) != 0, churn = (tb->flags & DEX_TABLES_CHURN) != 0;
+    Plan P; Dims d{a->B, a->T, a->Tr, a->Ts, E};
+    make_plan(x, d, a->workspace_dev, P);
+    Runner R{x, P, st, a->mask_dev, a->mu_dev, P.xbuf, a, false};
+    R.prepare(tb->sigma_dev, E);          // c_in / c_skip / c_out and c_noise = ln(sigma) / 4 at sigma(t) of every evaluation
+    const long nx = (long)a->B * 80 * a->T;
+    float* xin = scaled ? P.xin : nullptr;
+    auto coef = [&](int e) { return tb->coef_dev + (long)e * DEX_TABLE_EVAL_COLS; };
+    // x_0 = z c0 (edm.py:188-189); without x_hat updates x_hat_0 = x_0, whose input x_0 / s(t_hat_0) is written here
+    R.run("init_scale", 0, 8.0 * nx, [&] { launch_ablation_init(a->z_dev, P.xbuf, tb->step_dev + 2, churn ? nullptr : xin, coef(0) + 1, nx, st); });
+    gnfix_t* arena[2] = {P.stats, P.stats + P.stats_bytes / (long)sizeof(gnfix_t)};
+    zero_fill(P.stats, 2 * P.stats_bytes, st);
+    R.fin_gtab = tb->coef_dev;
+    int e = 0;
+    for (int i = 0; i < n; ++i) {
+        const bool corrector = heun && i < n - 1;          // Heun: every step but the last evaluates the corrector too (edm.py:207)
+        R.sp = e; R.stats_base = arena[e & 1]; R.stats_other = arena[(e + 1) & 1];
+        if (churn)          // x_hat = r x_cur + k randn_like(x_cur), in place (edm.py:196), and its input x_hat / s(t_hat)
+            R.run("churn_noise", 3.0 * nx, 16.0 * nx, [&] {
+                launch_ablation_churn(P.xbuf, a->noise_dev ? a->noise_dev + (long)i * nx : nullptr, tb->step_dev + (long)i * DEX_TABLE_STEP_COLS,
+                                      xin, coef(e) + 1, nx, st);
+            });
+        R.xcur = scaled ? xin : P.xbuf; R.fin_xstate = P.xbuf;
+        R.fin_mode = corrector ? 1 : 0;
+        // the next input: the corrector's x' / s(t'), or the next step's x_next / s(t_hat) when no x_hat update comes first
+        R.fin_xin_next = (scaled && (corrector || (!churn && i < n - 1))) ? xin : nullptr;
+        R.step(nullptr, corrector ? P.xprime : P.xbuf);
+        ++e;
+        if (corrector) {
+            R.sp = e; R.stats_base = arena[e & 1]; R.stats_other = arena[(e + 1) & 1];
+            R.xcur = scaled ? xin : P.xprime; R.fin_xstate = P.xprime;
+            R.fin_mode = 2;
+            R.fin_xin_next = (scaled && !churn) ? xin : nullptr;      // (a next step exists: i < n - 1)
+            R.step(nullptr, P.xbuf);
+            ++e;
+        }
+    }
+    R.run("copy_out", 0, 8.0 * nx, [&] { launch_scale_copy(P.xbuf, a->out_dev, nx, nullptr, st); });
     return DEX_OK;
 }
 
@@ -1808,7 +1872,7 @@ int dex_sample(DexCtx* x, const DexSampleArgs* a, dex_stream_t stream) {
     }
     x->taps.clear();
     if (x->prof_on) { for (auto& pr : x->prof) { hipEventDestroy(pr.a); hipEventDestroy(pr.b); } x->prof.clear(); x->prof_agg.clear(); }
-    auto enqueue = [&]() { return heun ? enqueue_heun(x, a, st) : enqueue_euler(x, a, st); };
+    auto enqueue = [&]() { return a->tables ? enqueue_tables(x, a, st) : heun ? enqueue_heun(x, a, st) : enqueue_euler(x, a, st); };
     const bool use_graph = a->use_graph && !x->prof_on;
     if (!use_graph) {
         rc = enqueue();
@@ -1828,6 +1892,12 @@ int dex_sample(DexCtx* x, const DexSampleArgs* a, dex_stream_t stream) {
                                  (uint64_t)(uintptr_t)(a->S_churn > 0.f ? a->noise_dev : nullptr)};
     key.push_back((uint64_t)g_xcd_gen.load(std::memory_order_acquire));          // placement rule of the cluster hand-offs (see g_xcd_map)
     for (float v : {a->S_churn, a->S_min, a->S_max, a->S_noise}) { uint32_t u; memcpy(&u, &v, 4); key.push_back(u); }
+    key.push_back(a->tables ? 1u : 0u);             // the general sampler: its flags pick the launches, its tables are read at replay
+    if (const DexSamplerTables* tb = a->tables) {
+        for (uint64_t v : {(uint64_t)tb->flags, (uint64_t)tb->n_rows, (uint64_t)(uintptr_t)tb->sigma_dev, (uint64_t)(uintptr_t)tb->coef_dev,
+                           (uint64_t)(uintptr_t)tb->step_dev, (uint64_t)(uintptr_t)((tb->flags & DEX_TABLES_CHURN) ? a->noise_dev : nullptr)})
+            key.push_back(v);
+    }
     for (int j = 0; j < a->n_ref; ++j) key.push_back((uint64_t)(uintptr_t)a->ref_skips_dev[j]);
     for (int v : knobs.v) key.push_back((uint64_t)(uint32_t)v);          // EVERY registered knob, as this call sees it
     DexCtx::GraphEntry* hit = nullptr;

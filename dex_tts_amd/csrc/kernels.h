@@ -203,6 +203,19 @@ struct FinalP {
     const int* poison;                                    // optional device word: non-zero (a workgroup hand-off of this call timed out) -> the outputs are NaN
 };
 void launch_final(const FinalP& p, hipStream_t st);
+// The general update of ablation_sampler's tables (final_kernel<FinalGP>; DexSamplerTables in dex_amd.h; FinalP's own kernel is
+// untouched): row `step` of gtab is [sigma, s, A, Bc, h, alpha h, w0, w1].  xcur is the network input x / s, xstate the state x it
+// came from (may alias xcur): d = A xstate - Bc D; mode 0 xnext = xstate + h d; mode 1 (predictor) dbuf = d, xnext = xstate +
+// (alpha h) d; mode 2 (corrector) xnext = xhat + h (w0 dbuf + w1 d).  xin_next (optional): the next input, xnext / s of row step + 1.
+struct FinalGP : FinalP {
+    const float* gtab; const float* xstate; float* xin_next;
+};
+void launch_final_general(const FinalGP& p, hipStream_t st);
+// ablation_sampler with tables: x_hat = r x + k noise (edm.py:196; rk = the step's [r, k]; noise NULL = zero), in place, rounded
+// like the reference's mul / mul / add; xin (optional) = x_hat / *s, the network's input
+void launch_ablation_churn(float* x, const float* noise, const float* rk, float* xin, const float* s, long n, hipStream_t st);
+// x = z * *c0 (edm.py:189); xin (optional) = x / *s
+void launch_ablation_init(const float* z, float* x, const float* c0, float* xin, const float* s, long n, hipStream_t st);
 // "Increase noise temporarily" tables (edm.py:194-196, schedule 'linear', scaling 'none'): for the schedule t_0..t_N
 //   t_hat[i] = t_i + gamma_i t_i,  gamma_i = min(S_churn / n, sqrt(2) - 1) if S_min <= t_i <= S_max else 0  (t_hat[n] = 0),
 //   h[i] = t_{i+1} - t_hat[i],  ncoef[i] = sqrt(max(t_hat^2 - t_i^2, 0)) * S_noise      — fp32, in the reference's op order.

@@ -471,8 +471,11 @@ void launch_gn_apply(const GnApplyP& p, hipStream_t st) {
 // A block owns FIN_U groups of 32 pixels per pass and issues every load of the pass - activations, mask, sampler state -
 // before the first use (the first version walked its pixels one dependent load at a time: 125 us for 168 MB at B=32);
 // the per-channel GroupNorm coefficient and final_conv weight live in registers for the block's life; Mish on packed pairs.
+// final_kernel<FinalP>: the EDM sampler's update; final_kernel<FinalGP>: the general update of ablation_sampler's tables (GEN).
 constexpr int FIN_U = 4;
-__global__ __launch_bounds__(256) void final_kernel(const FinalP p) {
+template <typename PT>
+__global__ __launch_bounds__(256) void final_kernel(const PT p) {
+    constexpr bool GEN = std::is_same<PT, FinalGP>::value;
     __shared__ float smean[32], srstd[32];
     const int tid = threadIdx.x, b = blockIdx.y;
     const int cpg = p.C / p.groups;
@@ -507,10 +510,16 @@ __global__ __launch_bounds__(256) void final_kernel(const FinalP p) {
     const bool poisoned = p.poison && *p.poison;
     const float inv = 1.f / sigma;
     const float h = p.htab ? p.htab[step] : sigma_next - sigma;
+    float gA = 0.f, gB = 0.f, gh = 0.f, gah = 0.f, gw0 = 0.f, gw1 = 0.f, gsn = 1.f;
+    if constexpr (GEN) {                             // this evaluation's row [sigma, s, A, Bc, h, alpha h, w0, w1]
+        const float* g = p.gtab + (long)step * 8;
+        gA = g[2]; gB = g[3]; gh = g[4]; gah = g[5]; gw0 = g[6]; gw1 = g[7];
+        if (p.xin_next) gsn = g[8 + 1];              // s of the next evaluation (there is one whenever xin_next is set)
+    }
     const long stride = (long)gridDim.x * 32 * FIN_U;
     for (long base = (long)blockIdx.x * 32 * FIN_U; base < p.npix; base += stride) {
         uint4 raw[FIN_U][2][2];                      // [pass][64-channel block][fp32: two halves; bf16: [0] only]
-        float mk[FIN_U], xc[FIN_U], xa[FIN_U], xd[FIN_U];
+        float mk[FIN_U], xc[FIN_U], xa[FIN_U], xd[FIN_U], xs[FIN_U];
 #pragma unroll
         for (int u = 0; u < FIN_U; ++u) {
             const long pr = base + u * 32 + (tid >> 3);
@@ -520,6 +529,7 @@ __global__ __launch_bounds__(256) void final_kernel(const FinalP p) {
             xc[u] = p.xcur[o];
             xa[u] = p.mode == 2 ? p.xhat[o] : 0.f;
             xd[u] = p.mode == 2 ? p.dbuf[o] : 0.f;
+            if constexpr (GEN) xs[u] = p.xstate[o];
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 if (k < nblk) {
@@ -563,7 +573,21 @@ __global__ __launch_bounds__(256) void final_kernel(const FinalP p) {
                 // x_next multiplied by h / (2 sigma') ~ 1e2 (measured before: 3e-4 against the oracle at n = 4, now ~1e-5).
                 const float D = poisoned ? __builtin_nanf("") : __fadd_rn(__fmul_rn(c_skip, xc[u]), __fmul_rn(c_out, f));
                 if (p.denoised) p.denoised[o] = D;
-                if (p.xnext) {
+                if constexpr (GEN) {
+                    // edm.py:202-214 for any schedule / scaling / alpha: d = A x - Bc D on the state, then the solver's update
+                    const float d = __fsub_rn(__fmul_rn(gA, xs[u]), __fmul_rn(gB, D));
+                    float xn;
+                    if (p.mode == 2) {
+                        xn = __fadd_rn(xa[u], __fmul_rn(gh, __fadd_rn(__fmul_rn(gw0, xd[u]), __fmul_rn(gw1, d))));
+                    } else if (p.mode == 1) {
+                        p.dbuf[o] = d;
+                        xn = __fadd_rn(xs[u], __fmul_rn(gah, d));
+                    } else {
+                        xn = __fadd_rn(xs[u], __fmul_rn(gh, d));
+                    }
+                    p.xnext[o] = xn;
+                    if (p.xin_next) p.xin_next[o] = __fdiv_rn(xn, gsn);
+                } else if (p.xnext) {
                     const float d = __fsub_rn(__fmul_rn(inv, xc[u]), __fmul_rn(inv, D));
                     if (p.mode == 2) {
                         p.xnext[o] = __fadd_rn(xa[u], __fmul_rn(h, __fadd_rn(__fmul_rn(0.5f, xd[u]), __fmul_rn(0.5f, d))));
@@ -620,7 +644,7 @@ __global__ void heun_expand_kernel(const float* t_hat, const float* hin, int n, 
 void launch_heun_expand(const float* t_hat, const float* hin, int n, float* sig, float* h, hipStream_t st) {
     hipLaunchKernelGGL(heun_expand_kernel, dim3((n + 63) / 64), dim3(64), 0, st, t_hat, hin, n, sig, h);
 }
-void launch_final(const FinalP& p, hipStream_t st) {
+static long final_blocks(const FinalP& p) {
     // every block pays the GroupNorm-coefficient prologue (fp64 divide + sqrt behind a barrier, ~2 us): at large batch
     // keep the total near 16K blocks so each one streams several 16-pixel groups instead of one
     long blocks = (p.npix + 32 * FIN_U - 1) / (32 * FIN_U);      // one pass of FIN_U 32-pixel groups per block ...
@@ -631,7 +655,40 @@ void launch_final(const FinalP& p, hipStream_t st) {
     const long capt = knob_or("DEX_FINAL_CAP", 1536);
     const long cap = capt / p.B > 32 ? capt / p.B : 32;
     if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(final_kernel, dim3((unsigned)blocks, p.B), dim3(256), 0, st, p);
+    return blocks;
+}
+void launch_final(const FinalP& p, hipStream_t st) {
+    hipLaunchKernelGGL(final_kernel<FinalP>, dim3((unsigned)final_blocks(p), p.B), dim3(256), 0, st, p);
+}
+void launch_final_general(const FinalGP& p, hipStream_t st) {
+    hipLaunchKernelGGL(final_kernel<FinalGP>, dim3((unsigned)final_blocks(p), p.B), dim3(256), 0, st, p);
+}
+__global__ void ablation_churn_kernel(float* x, const float* noise, const float* rk, float* xin, const float* s, long n) {
+    const float r = rk[0], k = rk[1];
+    const float sv = xin ? *s : 1.f;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        float v = __fmul_rn(r, x[i]);
+        if (noise) v = __fadd_rn(v, __fmul_rn(k, noise[i]));
+        x[i] = v;
+        if (xin) xin[i] = __fdiv_rn(v, sv);
+    }
+}
+void launch_ablation_churn(float* x, const float* noise, const float* rk, float* xin, const float* s, long n, hipStream_t st) {
+    long blocks = (n + 255) / 256; if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(ablation_churn_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, noise, rk, xin, s, n);
+}
+__global__ void ablation_init_kernel(const float* z, float* x, const float* c0, float* xin, const float* s, long n) {
+    const float c = *c0;
+    const float sv = xin ? *s : 1.f;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const float v = __fmul_rn(z[i], c);
+        x[i] = v;
+        if (xin) xin[i] = __fdiv_rn(v, sv);
+    }
+}
+void launch_ablation_init(const float* z, float* x, const float* c0, float* xin, const float* s, long n, hipStream_t st) {
+    long blocks = (n + 255) / 256; if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(ablation_init_kernel, dim3((unsigned)blocks), dim3(256), 0, st, z, x, c0, xin, s, n);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -103,6 +103,11 @@ class Diffusion(nn.Module):
         self.rng_parity = True                   # replay the reference's per-step randn_like draws (edm.py:196)
         # ablation_sampler's stochastic settings (edm.py:109,194-196); the reference wires the defaults (S_churn = 0)
         self.S_churn, self.S_min, self.S_max, self.S_noise = 0.0, 0.0, float("inf"), 1.0
+        # the rest of ablation_sampler's arguments (edm.py:109-110) at what the reference wires (diffusion.py:216); any other value
+        # runs the general sampler from host tables (dex_tts_amd.edm.ablation_tables)
+        self.discretization, self.schedule, self.scaling, self.alpha = "edm", "linear", "none", 1
+        self.sigma_min, self.sigma_max, self.rho = None, None, 7
+        self.epsilon_s, self.C_1, self.C_2, self.M = 1e-3, 0.001, 0.008, 1000
         self._engine = None
         self._engine_key = None
         self._make_sampler()
@@ -159,7 +164,32 @@ class Diffusion(nn.Module):
             self._engine_key = key
         return self._engine
 
+    def _tables(self, steps):
+        """The general sampler's tables for this module's settings, or None when they are the EDM sampler the reference wires
+        (edm / linear / none, alpha = 1, the default range): that one keeps its own path."""
+        g = lambda k, d: getattr(self, k, d)           # (modules pickled before these attributes existed)
+        disc, sched, scal, alpha = g("discretization", "edm"), g("schedule", "linear"), g("scaling", "none"), g("alpha", 1)
+        smin, smax, rho = g("sigma_min", None), g("sigma_max", None), g("rho", 7)
+        if (disc, sched, scal) == ("edm", "linear", "none") and alpha == 1 and smin is None and smax is None and rho == 7:
+            return None
+        from .edm import ablation_tables
+        return ablation_tables(int(steps), self.solver, disc, sched, scal, sigma_min=smin, sigma_max=smax, rho=rho,
+                               epsilon_s=g("epsilon_s", 1e-3), C_1=g("C_1", 0.001), C_2=g("C_2", 0.008), M=g("M", 1000), alpha=alpha,
+                               S_churn=self.S_churn, S_min=self.S_min, S_max=self.S_max, S_noise=self.S_noise)
+
+    def _sample_tables(self, z, mask, mu, tab, randn_like, spk=None, ref=None, sty=None, sty_lengths=None):
+        """ablation_sampler from host tables (dex_tts_amd.edm.ablation_sampler and forward with non-default settings)."""
+        eng = self.engine(z.device)
+        noise = None
+        if tab.noise:          # the reference's randn_like(x_cur), one per step in its order (edm.py:196), where it changes the result
+            noise = torch.stack([randn_like(z) for _ in range(tab.n_steps)])
+        return eng.sample(z, mask, mu, tab.n_steps, spk=spk, ref=ref, sty=sty, sty_lengths=sty_lengths, use_graph=self.use_graph,
+                          solver=tab.solver, noise=noise, tables=tab)
+
     def _sample(self, z, mask, mu, steps, spk=None, ref=None, sty=None, sty_lengths=None):
+        tab = self._tables(steps)
+        if tab is not None:
+            return self._sample_tables(z, mask, mu, tab, torch.randn_like, spk, ref, sty, sty_lengths)
         eng = self.engine(z.device)
         noise = None
         if self.S_churn > 0:
@@ -172,7 +202,9 @@ class Diffusion(nn.Module):
     def _advance_rng(self, like: torch.Tensor, n: int):
         """The reference draws ``randn_like(x_cur)`` once per Euler step and multiplies it by 0
         (edm.py:196); only the generator state matters.  Advance the Philox offset by the same amount."""
-        if not self.rng_parity or n <= 0 or self.S_churn > 0:      # (with S_churn > 0 the draws were really made, in _sample)
+        tab = self._tables(n) if n >= 2 else None
+        drew = tab.noise if tab is not None else self.S_churn > 0
+        if not self.rng_parity or n <= 0 or drew:      # (draws that change the result were really made, in _sample)
             return
         gen = torch.cuda.default_generators[like.device.index if like.device.index is not None else torch.cuda.current_device()]
         if n > 1 and hasattr(gen, "get_offset") and hasattr(gen, "set_offset"):

@@ -14,8 +14,10 @@ than silently detached.
 """
 from __future__ import annotations
 
+import functools
 import math
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -82,3 +84,242 @@ class EDMLoss(nn.Module):
             rows.append(denoise(xn[b:b + 1], sig_host[b], mask[b:b + 1], mu[b:b + 1], **kw))
         D_yn = torch.cat(rows, 0)
         return torch.sum(weight * ((D_yn - x0) ** 2)) / torch.sum(mask * self.n_feats)          # edm.py:66
+
+
+# ---- the general ablation_sampler (GeDEX-TTS/model/edm.py:109-216, DEX :104-211) ----------------------------------------------------
+# Every time-step discretisation, noise schedule, scaling schedule, solver, alpha and range its signature selects.  The host turns the
+# arguments into fp32 tables once (ablation_tables: cached per argument tuple); the device runs the sampler from them (dex_sample with
+# DexSampleArgs.tables, include/dex_amd.h).  The scalar arithmetic below repeats the reference's: torch CPU fp32 operations on 0-dim
+# tensors, one rounding per operation, with Python / numpy float64 scalars exactly where the reference has them.
+
+TABLES_SCALED, TABLES_CHURN = 1, 2        # DEX_TABLES_* of include/dex_amd.h
+
+
+def _vp_sigma(beta_d, beta_min):
+    """The VP schedule's noise level: sigma(t) = (e^(beta_d t^2 / 2 + beta_min t) - 1)^(1/2)."""
+    def sigma(t):
+        expo = 0.5 * beta_d * (t ** 2) + beta_min * t
+        return (math.e ** expo - 1) ** 0.5
+    return sigma
+
+
+def _vp_sigma_inv(beta_d, beta_min):
+    """Its inverse: t(sigma) = ((beta_min^2 + 2 beta_d ln(sigma^2 + 1))^(1/2) - beta_min) / beta_d."""
+    def inv(sig):
+        root = (beta_min ** 2 + 2 * beta_d * (sig ** 2 + 1).log()).sqrt()
+        return (root - beta_min) / beta_d
+    return inv
+
+
+@functools.lru_cache(maxsize=8, typed=True)
+def _iddpm_levels(M, C_1, C_2):
+    """iDDPM's M + 1 noise levels (cosine alpha-bar): u_M = 0 and, for j = M .. 1 in that order, in fp32,
+    u_{j-1} = ((u_j^2 + 1) / max(abar(j - 1) / abar(j), C_1) - 1)^(1/2)."""
+    def abar(j):                                   # j: a 0-dim int64 tensor; the arithmetic is fp32
+        return (0.5 * np.pi * j / M / (C_2 + 1)).sin() ** 2
+    u = torch.zeros(M + 1)
+    for j in torch.arange(M, 0, -1):
+        ratio = (abar(j - 1) / abar(j)).clip(min=C_1)
+        u[j - 1] = ((u[j] ** 2 + 1) / ratio - 1).sqrt()
+    return u
+
+
+class AblationTables:
+    """The fp32 tables of one ablation_sampler configuration, laid out as DexSamplerTables: ``sigma`` [E + 1] (the noise level of
+    every network evaluation, then 0; E = n_steps for Euler, 2 n_steps - 1 for Heun), ``coef`` [E, 8] (sigma, s, A, Bc, h, alpha h,
+    w0, w1), ``step`` [n_steps, 4] (r, k, c0 on row 0, 0).  ``flags``: DEX_TABLES_*; ``noise``: some step's k is not 0, so the
+    per-step randn_like draws change the result."""
+
+    def __init__(self, solver, n_steps, sigma, coef, step, flags, noise):
+        self.solver, self.n_steps = solver, n_steps
+        self.sigma, self.coef, self.step = sigma, coef, step
+        self.flags, self.noise = flags, noise
+        self._dev = {}
+
+    @classmethod
+    def from_arrays(cls, solver, n_steps, coef, step, scaled):
+        """Tables from their coef [E, 8] and step [n_steps, 4] arrays; the flags and the noise flag follow from the values."""
+        coef, step = torch.as_tensor(coef, dtype=torch.float32), torch.as_tensor(step, dtype=torch.float32)
+        sig = torch.cat([coef[:, 0], torch.zeros(1)])
+        noise = bool((step[:, 1] != 0).any())
+        churn = noise or bool((step[:, 0] != 1).any())
+        flags = (TABLES_SCALED if scaled else 0) | (TABLES_CHURN if churn else 0)
+        return cls(solver, n_steps, sig, coef, step, flags, noise)
+
+    @property
+    def n_rows(self) -> int:
+        return int(self.coef.shape[0])
+
+    def to(self, device):
+        """(sigma, coef, step) on ``device``, copied once per device."""
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = tuple(t.to(device) for t in (self.sigma, self.coef, self.step))
+        return self._dev[key]
+
+
+@functools.lru_cache(maxsize=64, typed=True)
+def ablation_tables(num_steps, solver, discretization, schedule, scaling, sigma_min=None, sigma_max=None, rho=7, epsilon_s=1e-3,
+                    C_1=0.001, C_2=0.008, M=1000, alpha=1, S_churn=0, S_min=0, S_max=float("inf"), S_noise=1) -> AblationTables:
+    """Everything the device needs for ``ablation_sampler(..., num_steps, solver, discretization, schedule, scaling, ...)``
+    (edm.py:109-216), computed on the CPU in fp32 in the reference's operation order; cached per argument tuple.
+
+    Row e of ``coef`` belongs to network evaluation e at time t (t_hat_i for step i's Euler / predictor evaluation, t'_i = t_hat_i +
+    alpha h_i for its corrector): sigma(t), s(t), A = sigma'(t)/sigma(t) + s'(t)/s(t), Bc = sigma'(t) s(t)/sigma(t), h_i = t_{i+1} -
+    t_hat_i, alpha h_i, w0 = 1 - 1/(2 alpha), w1 = 1/(2 alpha).  Row i of ``step``: r = s(t_hat)/s(t_cur) and k = (max(sigma(t_hat)^2
+    - sigma(t_cur)^2, 0))^(1/2) s(t_hat) S_noise of x_hat = r x_cur + k randn_like(x_cur) (edm.py:196), and on row 0 c0 = sigma(t_0)
+    s(t_0) of x_0 = latents c0.  The network's range is the library EDMPrecond's, sigma_min = 0 and sigma_max = inf (edm.py:77-78)."""
+    if solver not in ("euler", "heun"):
+        raise ValueError(f"solver must be 'euler' or 'heun', got {solver!r}")
+    if discretization not in ("vp", "ve", "iddpm", "edm"):
+        raise ValueError(f"discretization must be 'vp', 've', 'iddpm' or 'edm', got {discretization!r}")
+    if schedule not in ("vp", "ve", "linear"):
+        raise ValueError(f"schedule must be 'vp', 've' or 'linear', got {schedule!r}")
+    if scaling not in ("vp", "none"):
+        raise ValueError(f"scaling must be 'vp' or 'none', got {scaling!r}")
+    n = int(num_steps)
+    if n < 2:
+        raise ValueError("num_steps must be >= 2 (the reference divides by num_steps - 1)")
+
+    # the range: the discretisation's defaults, clamped to what the network supports (edm.py:124-134)
+    if sigma_min is None:
+        sigma_min = {"vp": _vp_sigma(19.9, 0.1)(epsilon_s), "ve": 0.02, "iddpm": 0.002, "edm": 0.002}[discretization]
+    if sigma_max is None:
+        sigma_max = {"vp": _vp_sigma(19.9, 0.1)(1), "ve": 100, "iddpm": 81, "edm": 80}[discretization]
+    sigma_min, sigma_max = max(sigma_min, 0), min(sigma_max, float("inf"))
+    # the VP betas that put sigma(epsilon_s) = sigma_min and sigma(1) = sigma_max: numpy float64 (edm.py:137-138)
+    log_min, log_max = np.log(sigma_min ** 2 + 1), np.log(sigma_max ** 2 + 1)
+    beta_d = 2 * (log_min / epsilon_s - log_max) / (epsilon_s - 1)
+    beta_min = log_max - 0.5 * beta_d
+
+    # noise levels of the steps (edm.py:141-157)
+    idx = torch.arange(n)
+    if discretization == "vp":
+        sigma_steps = _vp_sigma(beta_d, beta_min)(1 + idx / (n - 1) * (epsilon_s - 1))
+    elif discretization == "ve":
+        t_ve = (sigma_max ** 2) * ((sigma_min ** 2 / sigma_max ** 2) ** (idx / (n - 1)))
+        sigma_steps = t_ve.sqrt()
+    elif discretization == "iddpm":
+        u = _iddpm_levels(M, C_1, C_2)
+        u = u[torch.logical_and(u >= sigma_min, u <= sigma_max)]
+        pick = ((len(u) - 1) / (n - 1) * idx).round().to(torch.int64)          # round half to even
+        sigma_steps = u[pick]
+    else:
+        top, bottom = sigma_max ** (1 / rho), sigma_min ** (1 / rho)
+        sigma_steps = (top + idx / (n - 1) * (bottom - top)) ** rho
+
+    # sigma(t), sigma'(t), t(sigma) of the schedule and s(t), s'(t) of the scaling (edm.py:159-181).  Where the reference has the
+    # Python ints 1 / 0 (linear sigma', the 'none' scaling) they stay ints: they leave the fp32 operations they meet unrounded.
+    if schedule == "vp":
+        sigma, sigma_inv = _vp_sigma(beta_d, beta_min), _vp_sigma_inv(beta_d, beta_min)
+
+        def sigma_d(t):
+            return 0.5 * (beta_min + beta_d * t) * (sigma(t) + 1 / sigma(t))
+    elif schedule == "ve":
+        def sigma(t):
+            return t.sqrt()
+
+        def sigma_d(t):
+            return 0.5 / t.sqrt()
+
+        def sigma_inv(sig):
+            return sig ** 2
+    else:
+        def sigma(t):
+            return t
+
+        def sigma_d(t):
+            return 1
+
+        def sigma_inv(sig):
+            return sig
+    if scaling == "vp":
+        def s(t):
+            return 1 / (1 + sigma(t) ** 2).sqrt()
+
+        def s_d(t):
+            return -sigma(t) * sigma_d(t) * (s(t) ** 3)
+    else:
+        def s(t):
+            return 1
+
+        def s_d(t):
+            return 0
+
+    # time steps t_i = t(sigma_i) (the library's EDMPrecond.round_sigma is the identity), t_N = 0 (edm.py:184-185)
+    t_steps = torch.cat([sigma_inv(sigma_steps), torch.zeros(1)])
+    heun = solver == "heun"
+    w0, w1 = (1 - 1 / (2 * alpha), 1 / (2 * alpha)) if heun else (0.5, 0.5)
+
+    def row(t, h):
+        sg, st, dsg = sigma(t), s(t), sigma_d(t)
+        return [sg, st, dsg / sg + s_d(t) / st, dsg * st / sg, h, alpha * h, w0, w1]
+
+    rows, steps = [], []
+    for i in range(n):                                                        # edm.py:190-214
+        t_cur, t_next = t_steps[i], t_steps[i + 1]
+        sg_cur = sigma(t_cur)
+        gamma = min(S_churn / n, np.sqrt(2) - 1) if S_min <= sg_cur <= S_max else 0
+        t_hat = sigma_inv(sg_cur + gamma * sg_cur)
+        k = (sigma(t_hat) ** 2 - sg_cur ** 2).clip(min=0).sqrt() * s(t_hat) * S_noise
+        c0 = sigma(t_steps[0]) * s(t_steps[0]) if i == 0 else 0
+        steps.append([s(t_hat) / s(t_cur), k, c0, 0])
+        h = t_next - t_hat
+        rows.append(row(t_hat, h))
+        if heun and i < n - 1:
+            rows.append(row(t_hat + alpha * h, h))
+
+    def f32(table):
+        return torch.stack([torch.stack([torch.as_tensor(v, dtype=torch.float32).reshape(()) for v in r]) for r in table])
+
+    return AblationTables.from_arrays(solver, n, f32(rows), f32(steps), scaling == "vp")
+
+
+_SAMPLER_ARGS = ("spk", "class_labels", "randn_like", "num_steps", "sigma_min", "sigma_max", "rho", "solver", "discretization", "schedule",
+                 "scaling", "epsilon_s", "C_1", "C_2", "M", "alpha", "S_churn", "S_min", "S_max", "S_noise")
+_DEX_ARGS = ("ref", "ref_lengths", "sty", "sty_lengths")
+_SAMPLER_DEFAULTS = dict(spk=None, class_labels=None, randn_like=torch.randn_like, num_steps=18, sigma_min=None, sigma_max=None, rho=7,
+                         solver="heun", discretization="edm", schedule="linear", scaling="none", epsilon_s=1e-3, C_1=0.001, C_2=0.008,
+                         M=1000, alpha=1, S_churn=0, S_min=0, S_max=float("inf"), S_noise=1, ref=None, ref_lengths=None, sty=None,
+                         sty_lengths=None)
+_TABLE_ARGS = ("sigma_min", "sigma_max", "rho", "epsilon_s", "C_1", "C_2", "M", "alpha", "S_churn", "S_min", "S_max", "S_noise")
+
+
+def _owner_of(net):
+    from .diffusion import _Precond
+    if not isinstance(net, _Precond):
+        raise TypeError("net must be the precond_model of a dex_tts_amd.diffusion.Diffusion (the score network runs in libdexamd.so)")
+    owner = net._owner() if net._owner is not None else None
+    if owner is None:
+        raise RuntimeError("precond_model has no live owner (it belongs to a dex_tts_amd.diffusion.Diffusion)")
+    return owner
+
+
+@torch.no_grad()
+def ablation_sampler(net, latents, mask=None, mu=None, *args, **kwargs):
+    """The reference's ``ablation_sampler`` (GeDEX-TTS/model/edm.py:109-216, DEX-TTS :104-211) on the device, with its full signature
+    in the argument order of the net's tree:
+        GeDEX: ablation_sampler(net, latents, mask, mu, spk, class_labels, randn_like, num_steps, sigma_min, sigma_max, rho, solver,
+                                discretization, schedule, scaling, epsilon_s, C_1, C_2, M, alpha, S_churn, S_min, S_max, S_noise)
+        DEX:   ablation_sampler(net, latents, mask, mu, ref, ref_lengths, sty, sty_lengths, spk, class_labels, ...)
+    and the reference's defaults (solver 'heun', 18 steps, edm / linear / none).  ``net`` must be a library ``Diffusion``'s
+    ``precond_model``; ``class_labels`` is accepted and unused, as in the reference.  ``randn_like(latents)`` is called once per step,
+    in the reference's order, when the noise term of some step is not zero (S_churn > 0, or a schedule whose t(sigma(t)) round trip
+    moves t); the draws are handed to the device."""
+    owner = _owner_of(net)
+    names = (_DEX_ARGS if owner.cfg.variant == "dex" else ()) + _SAMPLER_ARGS
+    if len(args) > len(names):
+        raise TypeError(f"ablation_sampler() takes at most {4 + len(names)} positional arguments")
+    a = dict(_SAMPLER_DEFAULTS)
+    a.update(zip(names, args))
+    for k, v in kwargs.items():
+        if k not in names:
+            raise TypeError(f"ablation_sampler() got an unexpected keyword argument {k!r}")
+        if k in names[:len(args)]:
+            raise TypeError(f"ablation_sampler() got multiple values for argument {k!r}")
+        a[k] = v
+    if mask is None or mu is None:
+        raise ValueError("mask and mu are required: the score network is conditioned on them")
+    tab = ablation_tables(a["num_steps"], a["solver"], a["discretization"], a["schedule"], a["scaling"], **{k: a[k] for k in _TABLE_ARGS})
+    return owner._sample_tables(latents, mask, mu, tab, a["randn_like"], spk=a["spk"], ref=a["ref"], sty=a["sty"],
+                                sty_lengths=a["sty_lengths"])

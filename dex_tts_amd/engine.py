@@ -200,7 +200,7 @@ class ScoreNetEngine:
         return bufs
 
     def sample(self, z, mask, mu, n_steps, spk=None, ref=None, sty=None, sty_lengths=None, use_graph=False,
-               solver="euler", noise=None, S_churn=0.0, S_min=0.0, S_max=float("inf"), S_noise=1.0):
+               solver="euler", noise=None, S_churn=0.0, S_min=0.0, S_max=float("inf"), S_noise=1.0, tables=None):
         """ablation_sampler(solver, edm, linear, none) for latent z — edm.py:109-216.  ``solver`` is 'euler' (what
         Diffusion wires, diffusion.py:216) or 'heun' (edm.py:207-214; 2n-1 network evaluations).  Asynchronous.
         ``use_graph``: the whole call (conditioning tables + every network evaluation) is one cached hipGraph.
@@ -208,7 +208,10 @@ class ScoreNetEngine:
         default (``check_handoffs = "deferred"``: the verdict surfaces at the next call or at ``status()``), or before the mel is handed out
         (``check_handoffs = True``: blocks the host until the call has finished).
         ``S_churn > 0`` turns on the stochastic sampler (edm.py:194-196); ``noise`` [n_steps,B,80,T] then holds step i's
-        ``randn_like(x_cur)`` draw (the caller owns the RNG, as with ablation_sampler's ``randn_like`` argument)."""
+        ``randn_like(x_cur)`` draw (the caller owns the RNG, as with ablation_sampler's ``randn_like`` argument).
+        ``tables`` (``dex_tts_amd.edm.ablation_tables`` for this n_steps / solver): the general ablation_sampler of those tables
+        (any discretization / schedule / scaling / alpha / range); S_churn .. S_noise are then ignored, and ``noise`` is needed
+        exactly when ``tables.noise``."""
         with torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
             run_on = cur
@@ -224,7 +227,13 @@ class ScoreNetEngine:
                 z = z.to(device=self.device, dtype=torch.float32).contiguous()
                 B, _, T = mu.shape
                 mask = self._prep_mask(mask, B, T, self.device)
-                sig = edm_sigmas(n_steps).to(self.device)
+                tabs = []
+                if tables is not None:
+                    if tables.n_steps != n_steps or tables.solver != solver:
+                        raise ValueError(f"tables were made for {tables.n_steps} {tables.solver} steps, not {n_steps} {solver}")
+                    sig, *tabs = tables.to(self.device)          # evaluation sigmas [E + 1], coefficients [E, 8], step rows [n, 4]
+                else:
+                    sig = edm_sigmas(n_steps).to(self.device)
                 if self.cfg.variant == "dex" and ref is not None and sty is not None and sty_lengths is not None:
                     ref = [r.to(device=self.device, dtype=torch.float32).contiguous() for r in ref]
                     sty = sty.to(device=self.device, dtype=torch.float32).contiguous()
@@ -233,20 +242,28 @@ class ScoreNetEngine:
                     spk = spk.to(device=self.device, dtype=torch.float32).contiguous()
                 else:
                     spk = None
-                churn = (S_churn, S_min, S_max, S_noise) if S_churn and S_churn > 0 else None
+                churn = (S_churn, S_min, S_max, S_noise) if tables is None and S_churn and S_churn > 0 else None
                 if churn is not None:
                     if noise is None:
                         raise ValueError("S_churn > 0 needs the per-step noise draws (noise=[n_steps,B,80,T])")
+                    noise = noise.to(device=self.device, dtype=torch.float32).contiguous()
+                elif tables is not None and tables.noise:
+                    if noise is None or tuple(noise.shape) != (n_steps, B, 80, T):
+                        raise ValueError(f"these tables add noise (edm.py:196): noise of shape {(n_steps, B, 80, T)} is needed")
                     noise = noise.to(device=self.device, dtype=torch.float32).contiguous()
                 else:
                     noise = None
                 if use_graph:
                     dexin = ([sty, sty_lengths] + list(ref)) if (self.cfg.variant == "dex" and ref is not None) else []
-                    flat = [z, mu, mask, sig] + ([spk] if spk is not None else []) + ([noise] if noise is not None else []) + dexin
+                    flat = [z, mu, mask, sig] + tabs + ([spk] if spk is not None else []) + ([noise] if noise is not None else []) + dexin
                     key = (n_steps, solver, spk is not None, noise is not None) + tuple((tuple(t.shape), t.dtype) for t in flat)
+                    if tables is not None:
+                        key += ("tables", tables.flags)
                     st = self._staged(key, flat)
                     z, mu, mask, sig = st[:4]
                     k = 4
+                    if tabs:
+                        tabs = st[4:6]; k = 6
                     if spk is not None:
                         spk = st[k]; k += 1
                     if noise is not None:
@@ -259,6 +276,13 @@ class ScoreNetEngine:
                 a = _lib.DexSampleArgs()
                 keep = self._fill_args(a, mu, mask, sig, out, n_steps, spk, ref, sty, sty_lengths, use_graph, solver, noise, churn)
                 a.z_dev = z.data_ptr()
+                if tables is not None:
+                    tb = _lib.DexSamplerTables(sig.data_ptr(), tabs[0].data_ptr(), tabs[1].data_ptr(), tables.n_rows, tables.flags)
+                    a.tables = C.pointer(tb)
+                    keep += list(tabs) + [tb]
+                    if noise is not None:
+                        a.noise_dev = noise.data_ptr()
+                        keep.append(noise)
                 deferred = self.check_handoffs == "deferred"
                 if deferred:
                     self.status(wait=True)         # the previous call's verdict (its event has long passed; raises if that call lost a hand-off)

@@ -3,7 +3,8 @@
  *
  * Drop-in boundary for the reference's Diffusion.forward(..., infer=True) hot path
  *   GeDEX-TTS/model/diffusion.py:220-229, DEX-TTS/model/diffusion.py:250-259
- *   -> ablation_sampler (euler/edm/linear/none)   GeDEX-TTS/model/edm.py:109-216 (DEX :104-211)
+ *   -> ablation_sampler (euler|heun, any alpha; discretization vp/ve/iddpm/edm, schedule vp/ve/linear, scaling vp/none,
+ *      range overrides, churn)                    GeDEX-TTS/model/edm.py:109-216 (DEX :104-211)
  *   -> EDMPrecond.forward                          model/edm.py:88-98
  *   -> DiffusionDenoiser.forward (+DiTMask, TV/TIV adaptors)
  *                                                  GeDEX diffusion.py:168-207, DEX :190-236, model/dit.py:485-525,
@@ -52,6 +53,34 @@ typedef enum { DEX_PREC_FP32 = 0, DEX_PREC_BF16 = 1, DEX_PREC_FP16 = 2,
 /* ablation_sampler's solver argument (edm.py:107). */
 typedef enum { DEX_SOLVER_EULER = 0, DEX_SOLVER_HEUN = 1 } DexSolver;
 
+/* The general ablation_sampler (edm.py:109-216): every branch of discretization / schedule / scaling / alpha / range, as fp32 tables
+ * the HOST computes in the reference's operation order (dex_tts_amd/edm.py: ablation_tables) and hands over in DEVICE memory (a
+ * captured graph reads them at replay).  Row e describes network evaluation e (n_steps rows for Euler, 2 n_steps - 1 for Heun: step
+ * i's predictor at t_hat_i, then its corrector at t'_i = t_hat_i + alpha h_i, none on the last step).  Per evaluation the library does
+ *     D = c_skip(sigma) x_in + c_out(sigma) F(c_in(sigma) x_in, ln(sigma) / 4)      with x_in = x / s   (edm.py:88-98, 201, 212)
+ *     d = A x - Bc D                                                                 (edm.py:202, 213)
+ *     Euler / last step:  x_next = x_hat + h d;    Heun predictor:  x' = x_hat + (alpha h) d;
+ *     Heun corrector:     x_next = x_hat + h (w0 d_cur + w1 d')                      (edm.py:203-214)
+ * every product and sum rounded on its own, like the reference's torch operations.  Each step starts from
+ *     x_hat = r x_cur + k noise_i  (edm.py:196; only when DEX_TABLES_CHURN is set),   and the call from x_0 = z c0 (edm.py:189).
+ * alpha needs no flag: the predictor's step alpha h and the corrector's weights are table columns. */
+enum {
+    DEX_TABLES_SCALED = 1,  /* scaling 'vp': the network input x / s is kept in a buffer of its own (s = 1 otherwise: x_in IS x) */
+    DEX_TABLES_CHURN = 2    /* some step has r != 1 or k != 0: every step begins with the x_hat update; noise_dev = [n_steps][B,80,T]
+                             * draws, or NULL when every k is 0 */
+};
+#define DEX_TABLE_EVAL_COLS 8   /* coef_dev row: sigma, s, A, Bc, h, alpha h, w0, w1 */
+#define DEX_TABLE_STEP_COLS 4   /* step_dev row: r, k, c0 (row 0 only, else 0), 0 */
+typedef struct {
+    const float* sigma_dev;     /* [n_rows + 1]: sigma(t) of every evaluation (the network's noise level), then 0 */
+    const float* coef_dev;      /* [n_rows][DEX_TABLE_EVAL_COLS]: sigma(t); s(t); A = sigma'(t)/sigma(t) + s'(t)/s(t);
+                                 * Bc = sigma'(t) s(t)/sigma(t); the step's h = t_next - t_hat; alpha h; w0 = 1 - 1/(2 alpha); w1 = 1/(2 alpha) */
+    const float* step_dev;      /* [n_steps][DEX_TABLE_STEP_COLS]: r = s(t_hat)/s(t_cur); k = sqrt(max(sigma(t_hat)^2 - sigma(t_cur)^2, 0))
+                                 * s(t_hat) S_noise; c0 = sigma(t_0) s(t_0) */
+    int32_t n_rows;             /* must be dex_num_evals(n_steps, solver) */
+    uint32_t flags;             /* DEX_TABLES_* */
+} DexSamplerTables;
+
 /* Mirrors Diffusion(**cfg.decoder, dit_cfg=cfg.dit): GeDEX diffusion.py:210, dit.py:339-356. */
 typedef struct {
     int32_t variant;        /* DexVariant */
@@ -94,11 +123,15 @@ typedef struct {
     const float* noise_dev;     /* [n_steps][B,80,T]: step i's randn_like(x_cur) draw (the caller owns the RNG); required
                                  * when S_churn > 0, ignored otherwise */
     float S_churn, S_min, S_max, S_noise;   /* S_max <= 0 means +inf; S_noise is used as given when S_churn > 0 */
+    /* NULL: the EDM sampler above (edm / linear / none, alpha = 1), bit for bit what it always was.  Otherwise the general
+     * ablation_sampler of the tables (the struct is host memory, the tables device memory): sigmas_dev and S_churn .. S_noise are
+     * then ignored, and noise_dev is read only under DEX_TABLES_CHURN. */
+    const DexSamplerTables* tables;
 } DexSampleArgs;
 
 /* One EDMPrecond.forward call (edm.py:88-98): out = c_skip*x + c_out*F(c_in*x, mask, mu, ln(sigma)/4). */
 typedef struct {
-    DexSampleArgs s;            /* z_dev is ignored; n_steps ignored; sigmas_dev[0] = sigma */
+    DexSampleArgs s;            /* z_dev is ignored; n_steps ignored; tables ignored; sigmas_dev[0] = sigma */
     const float* x_dev;         /* [B,80,T] */
 } DexDenoiseArgs;
 
