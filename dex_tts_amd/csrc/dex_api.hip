@@ -173,7 +173,45 @@ struct DexCtx : WeightStore {
     std::vector<GraphEntry> graphs;
     uint64_t graph_clock = 0;
     void drop_graphs() { for (auto& g : graphs) hipGraphExecDestroy(g.exec); graphs.clear(); }
+    template <typename F> int replay(const std::vector<uint64_t>& key, hipStream_t st, F&& enqueue);
+    // taps and profile rows describe the last call: every dex_sample / dex_denoise_once starts from none
+    void reset_records() {
+        taps.clear();
+        if (prof_on) { for (auto& pr : prof) { hipEventDestroy(pr.a); hipEventDestroy(pr.b); } prof.clear(); prof_agg.clear(); }
+    }
 };
+
+// Replay the graph cached under `key` on `st`; a miss captures enqueue() first (evicting the least recently used of 8 graphs).
+template <typename F> int DexCtx::replay(const std::vector<uint64_t>& key, hipStream_t st, F&& enqueue) {
+    GraphEntry* hit = nullptr;
+    for (auto& g : graphs) if (g.key == key) { hit = &g; break; }
+    if (!hit) {
+        constexpr size_t MAX_GRAPHS = 8;
+        if (graphs.size() >= MAX_GRAPHS) {                 // evict the least recently used graph
+            size_t lru = 0;
+            for (size_t i = 1; i < graphs.size(); ++i) if (graphs[i].stamp < graphs[lru].stamp) lru = i;
+            hipGraphExecDestroy(graphs[lru].exec);
+            graphs.erase(graphs.begin() + lru);
+        }
+        hipGraph_t graph = nullptr;
+        DEX_HIPCHK(this, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+        const int rc = enqueue();
+        hipError_t ec = hipStreamEndCapture(st, &graph);          // always leave capture mode
+        if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
+        if (ec != hipSuccess || !graph) return fail(DEX_ERR_HIP, "stream capture failed: %s", hipGetErrorString(ec));
+        hipGraphExec_t exec = nullptr;
+        ec = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        hipGraphDestroy(graph);
+        if (ec != hipSuccess) return fail(DEX_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ec));
+        graphs.push_back({key, exec, 0, last_xerr});        // (the Runner set last_xerr while its launches were captured)
+        hit = &graphs.back();
+    }
+    last_xerr = hit->xerr;           // a replay enqueues nothing on the host: dex_call_status reads the word the CAPTURED launches write
+    hit->stamp = ++graph_clock;
+    DEX_HIPCHK(this, hipGraphLaunch(hit->exec, st));
+    DEX_HIPCHK(this, hipGetLastError());
+    return DEX_OK;
+}
 
 // ================================================================================================
 // parameter inventory (mirrors dex_tts_amd/config.py:param_shapes; validated against the reference
@@ -832,6 +870,15 @@ void make_plan(const DexCtx* x, const Dims& d, void* ws, Plan& P) {
     P.bytes = (A.off + 255) & ~size_t(255);
 }
 
+// What the last kernel of a network evaluation does with the denoised output (FinalP / FinalGP in kernels.h).
+struct Update {
+    int mode = 0;                       // FinalP::mode: 0 Euler step, 1 Heun predictor, 2 Heun corrector
+    const float* htab = nullptr;        // step size per evaluation, or null: sigma_next - sigma
+    const float* gtab = nullptr;        // ablation tables: the general update (final_kernel<true>) with these rows, ...
+    const float* xstate = nullptr;      // ... the state x of this evaluation (Runner::xcur is its network input x / s) ...
+    float* xin_next = nullptr;          // ... and where the next evaluation's input goes (scaled tables), or null
+};
+
 struct Runner {
     DexCtx* x; const Plan& P; hipStream_t st;
     const float* mask; const float* mu; const float* xcur;
@@ -841,11 +888,7 @@ struct Runner {
     int sp = 0;                     // index of the current network evaluation (a by-value launch argument of every kernel)
     gnfix_t* stats_base = nullptr;  // statistics arena of this step
     gnfix_t* stats_other = nullptr;   // arena to clear for the next step (eager mode), or null
-    int fin_mode = 0;               // FinalP::mode of this network evaluation (Heun predictor / corrector)
-    const float* fin_htab = nullptr;
-    const float* fin_gtab = nullptr;        // ablation tables: the general update (final_kernel<true>) with these rows, ...
-    const float* fin_xstate = nullptr;      // ... the state x of this evaluation (xcur is its network input x / s) ...
-    float* fin_xin_next = nullptr;          // ... and where the next evaluation's input goes (scaled tables), or null
+    Update up;                      // the update of this network evaluation (assigned whole, once per evaluation)
 
     template <typename F> void run(const char* name, double flops, double bytes, F&& f) {
         if (x->prof_on) {
@@ -1577,10 +1620,10 @@ struct Runner {
         f.xcur = xcur; f.denoised = denoised; f.xnext = xnext; f.scal = P.scal; f.scal_stride = SCAL_STRIDE; f.step = sp; f.B = B;
         f.zero_ptr = reinterpret_cast<float*>(stats_other); f.zero_n = P.stats_bytes / (long)sizeof(float);
         f.poison = P.xflag ? reinterpret_cast<const int*>(P.xflag + (P.xflag_bytes - sizeof(int)) / sizeof(unsigned)) : nullptr;
-        f.mode = fin_mode; f.htab = fin_htab; f.dbuf = P.dbuf; f.xhat = P.xbuf;
-        f.gtab = fin_gtab; f.xstate = fin_xstate; f.xin_next = fin_xin_next;
+        f.mode = up.mode; f.htab = up.htab; f.dbuf = P.dbuf; f.xhat = P.xbuf;
+        f.gtab = up.gtab; f.xstate = up.xstate; f.xin_next = up.xin_next;
         run("final_conv_euler", 14.0 * 80 * P.d.T * c.dim * B, 80.0 * P.d.T * ((hfb ? 2.0 : 4.0) * c.dim + 12.0) * B,
-            [&] { if (fin_gtab) launch_final_general(f, st); else launch_final(f, st); });
+            [&] { if (up.gtab) launch_final_general(f, st); else launch_final(f, st); });
     }
 
     // conditioning tables for every Euler step (depend only on sigma_i)
@@ -1690,114 +1733,120 @@ int validate(DexCtx* x, const DexSampleArgs* a, bool need_z) {
 
 __global__ void set_sigma_pair(const float* src, float* dst) { dst[0] = src[0]; dst[1] = 0.f; }
 
-// ablation_sampler(solver='heun', alpha=1) — edm.py:199-214.  2n-1 network evaluations: evaluation 2i is step i's
-// predictor at t_i, evaluation 2i+1 its corrector at t' = t_i + h (none on the last step).  The conditioning tables are
-// built per EVALUATION; the last kernel of each evaluation does the predictor / corrector update.  Eager launches only.
-int enqueue_heun(DexCtx* x, const DexSampleArgs* a, hipStream_t st) {
-    const int n = a->n_steps, E = 2 * n - 1;
+struct Eval {                   // one network evaluation of a sampler call
+    const float* xin;           // network input (Runner::xcur)
+    float* xout;                // where the update writes
+    Update up;
+    int noise_step = -1;        // >= 0: the x_hat update of that step runs first (before predictor evaluations only)
+};
+
+// The sampler kinds of dex_sample run the same launches per evaluation; they differ in the table row an evaluation reads, the
+// buffers it connects and the small kernels in front of it.
+//   Euler (edm.py:186-208): n evaluations.  Under churn the network sees t_hat_i, the update uses h_i = t_{i+1} - t_hat_i.
+//   Heun, alpha = 1 (edm.py:199-214): 2n-1 evaluations, 2i is step i's predictor at t_i, 2i+1 its corrector at t' = t_i + h (none
+//     on the last step: edm.py:207); the conditioning tables are built per EVALUATION.
+//   Tables (the general ablation_sampler, edm.py:109-216, from the host's DexSamplerTables: any discretization / schedule / scaling
+//     / alpha, Euler or Heun): evaluation e reads row e everywhere, cond_prep its sigma, the update (final_kernel<true>) its
+//     coefficients.  The x_hat update of a step runs only under DEX_TABLES_CHURN, and with DEX_TABLES_SCALED the network reads
+//     x / s from P.xin, which the kernel before it writes (init, x_hat update or the last update).
+struct SamplerKind {
+    const DexSamplerTables* tb;
+    bool heun, churn, scaled;
+    int n, E;
+    explicit SamplerKind(const DexSampleArgs* a)
+        : tb(a->tables), heun(a->solver == DEX_SOLVER_HEUN), churn(tb ? (tb->flags & DEX_TABLES_CHURN) != 0 : a->S_churn > 0.f),
+          scaled(tb && (tb->flags & DEX_TABLES_SCALED) != 0), n(a->n_steps), E(tb ? tb->n_rows : dex_num_evals(a->n_steps, a->solver)) {}
+
+    Eval eval(const Plan& P, int e) const {
+        const int i = heun ? e / 2 : e;                             // the step of evaluation e
+        const bool corrector = heun && (e & 1);                     // (then a next step exists: i < n - 1)
+        const bool predictor = heun && !corrector && i < n - 1;     // a corrector follows
+        const int mode = corrector ? 2 : predictor ? 1 : 0, noise_step = (churn && !corrector) ? i : -1;
+        float* x = corrector ? P.xprime : P.xbuf;                   // the state this evaluation starts from ...
+        float* xout = predictor ? P.xprime : P.xbuf;                // ... and the one it leaves
+        if (!tb) return {x, xout, {mode, heun ? P.htab : churn ? P.hstep : nullptr}, noise_step};
+        // the next input: the corrector's x' / s(t'), or the next step's x_next / s(t_hat) when no x_hat update comes first
+        float* xin_next = (scaled && (predictor || (!churn && i < n - 1))) ? P.xin : nullptr;
+        return {scaled ? P.xin : x, xout, {mode, nullptr, tb->coef_dev, x, xin_next}, noise_step};
+    }
+};
+
+// One sampler call: conditioning tables of every evaluation, x_0, the evaluations, the copy to the caller.  The GroupNorm
+// statistics alternate between two arenas; each evaluation's last kernel clears the arena of the next one.  Eager launches only.
+int enqueue_sampler(DexCtx* x, const DexSampleArgs* a, hipStream_t st) {
+    const SamplerKind k(a);
+    const DexSamplerTables* tb = k.tb;
+    const int n = k.n, E = k.E;
     Plan P; Dims d{a->B, a->T, a->Tr, a->Ts, E};
     make_plan(x, d, a->workspace_dev, P);
     Runner R{x, P, st, a->mask_dev, a->mu_dev, P.xbuf, a, false};
-    launch_churn_tables(a->sigmas_dev, n, a->S_churn, a->S_min, a->S_max, a->S_noise, P.that, P.hstep, P.ncoef, st);
-    launch_heun_expand(P.that, P.hstep, n, P.hsig, P.htab, st);
-    R.prepare(P.hsig, E);
-    const bool churn = a->S_churn > 0.f;
     const long nx = (long)a->B * 80 * a->T;
-    // x_0 = z * t_0 (edm.py:188-189; t_0, not t_hat_0)
-    R.run("init_scale", 0, 8.0 * nx, [&] { launch_scale_copy(a->z_dev, P.xbuf, nx, a->sigmas_dev, st); });
-    gnfix_t* arena[2] = {P.stats, P.stats + P.stats_bytes / (long)sizeof(gnfix_t)};
-    zero_fill(P.stats, 2 * P.stats_bytes, st);
-    R.fin_htab = P.htab;
-    for (int e = 0; e < E; ++e) {
-        const bool corrector = (e & 1) != 0, last = (e == E - 1);
-        R.sp = e; R.stats_base = arena[e & 1]; R.stats_other = arena[(e + 1) & 1];
-        if (churn && !corrector)        // x_hat = x_cur + sqrt(t_hat^2 - t_cur^2) S_noise randn_like(x_cur), in place (edm.py:196)
-            R.run("churn_noise", 2.0 * nx, 12.0 * nx, [&] { launch_add_noise(P.xbuf, a->noise_dev + (long)(e / 2) * nx, P.ncoef + e / 2, nx, st); });
-        R.xcur = corrector ? P.xprime : P.xbuf;
-        R.fin_mode = corrector ? 2 : (last ? 0 : 1);
-        R.step(nullptr, (corrector || last) ? P.xbuf : P.xprime);
-    }
-    R.run("copy_out", 0, 8.0 * nx, [&] { launch_scale_copy(P.xbuf, a->out_dev, nx, nullptr, st); });      // (a kernel node like every other link of a captured call: see zero_fill)
-    return DEX_OK;
-}
-
-// ablation_sampler(solver='euler') — edm.py:186-208.  The step index is a launch argument and the GroupNorm statistics
-// alternate between two arenas; each step's last kernel clears the arena of the next step.
-int enqueue_euler(DexCtx* x, const DexSampleArgs* a, hipStream_t st) {
-    Plan P; Dims d{a->B, a->T, a->Tr, a->Ts, a->n_steps};
-    make_plan(x, d, a->workspace_dev, P);
-    Runner R{x, P, st, a->mask_dev, a->mu_dev, P.xbuf, a, false};
-    R.sp = 0;
-    const bool churn = a->S_churn > 0.f;
-    const long nx = (long)a->B * 80 * a->T;
-    if (churn) {        // the network sees t_hat_i, the update uses h_i = t_{i+1} - t_hat_i (edm.py:194-199)
-        launch_churn_tables(a->sigmas_dev, a->n_steps, a->S_churn, a->S_min, a->S_max, a->S_noise, P.that, P.hstep, P.ncoef, st);
-        R.prepare(P.that, a->n_steps);
-        R.fin_htab = P.hstep;
-    } else {
-        R.prepare(a->sigmas_dev, a->n_steps);
-    }
-    // x_0 = z * t_0 (edm.py:188-189)
-    R.run("init_scale", 0, 8.0 * nx, [&] { launch_scale_copy(a->z_dev, P.xbuf, nx, a->sigmas_dev, st); });
-    gnfix_t* arena[2] = {P.stats, P.stats + P.stats_bytes / (long)sizeof(gnfix_t)};
-    zero_fill(P.stats, 2 * P.stats_bytes, st);
-    for (int i = 0; i < a->n_steps; ++i) {
-        R.sp = i; R.stats_base = arena[i & 1]; R.stats_other = arena[(i + 1) & 1];
-        if (churn)          // x_hat = x_cur + sqrt(t_hat^2 - t_cur^2) S_noise randn_like(x_cur), in place (edm.py:196)
-            R.run("churn_noise", 2.0 * nx, 12.0 * nx, [&] { launch_add_noise(P.xbuf, a->noise_dev + (long)i * nx, P.ncoef + i, nx, st); });
-        R.step(nullptr, P.xbuf);
-    }
-    R.run("copy_out", 0, 8.0 * nx, [&] { launch_scale_copy(P.xbuf, a->out_dev, nx, nullptr, st); });      // (a kernel node like every other link of a captured call: see zero_fill)
-    return DEX_OK;
-}
-
-// The general ablation_sampler (edm.py:109-216) from the host's tables (DexSamplerTables): any discretization / schedule / scaling /
-// alpha, Euler or Heun.  Evaluation e reads row e everywhere: cond_prep its sigma, the update (final_kernel<true>) its coefficients.
-// The launches per evaluation are those of enqueue_euler / enqueue_heun; the x_hat update of a step runs only under DEX_TABLES_CHURN,
-// and with DEX_TABLES_SCALED the network reads x / s from P.xin, which the kernel before it writes (init, x_hat update or the last update).
-int enqueue_tables(DexCtx* x, const DexSampleArgs* a, hipStream_t st) {
-    const DexSamplerTables* tb = a->tables;
-    const int n = a->n_steps, E = tb->n_rows;
-    const bool heun = a->solver == DEX_SOLVER_HEUN;
-    const bool scaled = (tb->flags & DEX_TABLES_SCALED) != 0, churn = (tb->flags & DEX_TABLES_CHURN) != 0;
-    Plan P; Dims d{a->B, a->T, a->Tr, a->Ts, E};
-    make_plan(x, d, a->workspace_dev, P);
-    Runner R{x, P, st, a->mask_dev, a->mu_dev, P.xbuf, a, false};
-    R.prepare(tb->sigma_dev, E);          // c_in / c_skip / c_out and c_noise = ln(sigma) / 4 at sigma(t) of every evaluation
-    const long nx = (long)a->B * 80 * a->T;
-    float* xin = scaled ? P.xin : nullptr;
+    float* xin = k.scaled ? P.xin : nullptr;
     auto coef = [&](int e) { return tb->coef_dev + (long)e * DEX_TABLE_EVAL_COLS; };
-    // x_0 = z c0 (edm.py:188-189); without x_hat updates x_hat_0 = x_0, whose input x_0 / s(t_hat_0) is written here
-    R.run("init_scale", 0, 8.0 * nx, [&] { launch_ablation_init(a->z_dev, P.xbuf, tb->step_dev + 2, churn ? nullptr : xin, coef(0) + 1, nx, st); });
+    if (tb) {
+        R.prepare(tb->sigma_dev, E);          // c_in / c_skip / c_out and c_noise = ln(sigma) / 4 at sigma(t) of every evaluation
+    } else {
+        if (k.heun || k.churn) launch_churn_tables(a->sigmas_dev, n, a->S_churn, a->S_min, a->S_max, a->S_noise, P.that, P.hstep, P.ncoef, st);
+        if (k.heun) launch_heun_expand(P.that, P.hstep, n, P.hsig, P.htab, st);
+        R.prepare(k.heun ? P.hsig : k.churn ? P.that : a->sigmas_dev, E);
+    }
+    // x_0 = z * t_0 (edm.py:188-189; t_0, not t_hat_0).  Tables: x_0 = z c0; without x_hat updates x_hat_0 = x_0, whose input
+    // x_0 / s(t_hat_0) is written here
+    R.run("init_scale", 0, 8.0 * nx, [&] {
+        if (tb) launch_ablation_init(a->z_dev, P.xbuf, tb->step_dev + 2, k.churn ? nullptr : xin, coef(0) + 1, nx, st);
+        else launch_scale_copy(a->z_dev, P.xbuf, nx, a->sigmas_dev, st);
+    });
     gnfix_t* arena[2] = {P.stats, P.stats + P.stats_bytes / (long)sizeof(gnfix_t)};
     zero_fill(P.stats, 2 * P.stats_bytes, st);
-    R.fin_gtab = tb->coef_dev;
-    int e = 0;
-    for (int i = 0; i < n; ++i) {
-        const bool corrector = heun && i < n - 1;          // Heun: every step but the last evaluates the corrector too (edm.py:207)
+    for (int e = 0; e < E; ++e) {
+        const Eval ev = k.eval(P, e);
+        const int i = ev.noise_step;
         R.sp = e; R.stats_base = arena[e & 1]; R.stats_other = arena[(e + 1) & 1];
-        if (churn)          // x_hat = r x_cur + k randn_like(x_cur), in place (edm.py:196), and its input x_hat / s(t_hat)
+        if (i >= 0 && tb)       // x_hat = r x_cur + k randn_like(x_cur), in place (edm.py:196), and its input x_hat / s(t_hat)
             R.run("churn_noise", 3.0 * nx, 16.0 * nx, [&] {
                 launch_ablation_churn(P.xbuf, a->noise_dev ? a->noise_dev + (long)i * nx : nullptr, tb->step_dev + (long)i * DEX_TABLE_STEP_COLS,
                                       xin, coef(e) + 1, nx, st);
             });
-        R.xcur = scaled ? xin : P.xbuf; R.fin_xstate = P.xbuf;
-        R.fin_mode = corrector ? 1 : 0;
-        // the next input: the corrector's x' / s(t'), or the next step's x_next / s(t_hat) when no x_hat update comes first
-        R.fin_xin_next = (scaled && (corrector || (!churn && i < n - 1))) ? xin : nullptr;
-        R.step(nullptr, corrector ? P.xprime : P.xbuf);
-        ++e;
-        if (corrector) {
-            R.sp = e; R.stats_base = arena[e & 1]; R.stats_other = arena[(e + 1) & 1];
-            R.xcur = scaled ? xin : P.xprime; R.fin_xstate = P.xprime;
-            R.fin_mode = 2;
-            R.fin_xin_next = (scaled && !churn) ? xin : nullptr;      // (a next step exists: i < n - 1)
-            R.step(nullptr, P.xbuf);
-            ++e;
-        }
+        else if (i >= 0)        // x_hat = x_cur + sqrt(t_hat^2 - t_cur^2) S_noise randn_like(x_cur), in place (edm.py:196)
+            R.run("churn_noise", 2.0 * nx, 12.0 * nx, [&] { launch_add_noise(P.xbuf, a->noise_dev + (long)i * nx, P.ncoef + i, nx, st); });
+        R.xcur = ev.xin; R.up = ev.up;
+        R.step(nullptr, ev.xout);
     }
-    R.run("copy_out", 0, 8.0 * nx, [&] { launch_scale_copy(P.xbuf, a->out_dev, nx, nullptr, st); });
+    R.run("copy_out", 0, 8.0 * nx, [&] { launch_scale_copy(P.xbuf, a->out_dev, nx, nullptr, st); });      // (a kernel node like every other link of a captured call: see zero_fill)
     return DEX_OK;
+}
+
+// What dex_sample and dex_denoise_once hold while they enqueue: one reading of every knob (also part of the graph-cache key), the
+// split-weight mode, the XCD placement probe (once per device, before any capture; normally already done by dex_ctx_create), and
+// no hand-off word yet (the call sets last_xerr again if it uses in-launch hand-offs: dex_call_status).
+struct CallScope {
+    const KnobSnapshot knobs;
+    const KnobScope knob_scope{&knobs};
+    const WsplitScope wsplit_scope;
+    explicit CallScope(DexCtx* x) : wsplit_scope(x->precision == DEX_PREC_FP16X2) { xcd_map_probe(); x->last_xerr = nullptr; }
+};
+
+// One graph = the whole call.  Every device pointer the captured kernels dereference is part of the key, so a replay
+// is only ever issued against the buffers it was captured with (the host mirror keeps persistent staging buffers, which
+// makes every call of one shape a cache hit).
+std::vector<uint64_t> graph_key(const DexSampleArgs* a, int precision, hipStream_t st, const KnobSnapshot& knobs) {
+    std::vector<uint64_t> key = {(uint64_t)a->B, (uint64_t)a->T, (uint64_t)a->Tr, (uint64_t)a->Ts, (uint64_t)a->n_steps, (uint64_t)a->solver,
+                                 (uint64_t)precision, (uint64_t)a->n_ref, (uint64_t)(uintptr_t)st,
+                                 (uint64_t)(uintptr_t)a->z_dev, (uint64_t)(uintptr_t)a->mu_dev, (uint64_t)(uintptr_t)a->mask_dev,
+                                 (uint64_t)(uintptr_t)a->sigmas_dev, (uint64_t)(uintptr_t)a->spk_dev, (uint64_t)(uintptr_t)a->sty_dev,
+                                 (uint64_t)(uintptr_t)a->sty_lengths_dev, (uint64_t)(uintptr_t)a->out_dev, (uint64_t)(uintptr_t)a->workspace_dev,
+                                 (uint64_t)(uintptr_t)(a->S_churn > 0.f ? a->noise_dev : nullptr)};
+    key.push_back((uint64_t)g_xcd_gen.load(std::memory_order_acquire));          // placement rule of the cluster hand-offs (see g_xcd_map)
+    for (float v : {a->S_churn, a->S_min, a->S_max, a->S_noise}) { uint32_t u; memcpy(&u, &v, 4); key.push_back(u); }
+    key.push_back(a->tables ? 1u : 0u);             // the general sampler: its flags pick the launches, its tables are read at replay
+    if (const DexSamplerTables* tb = a->tables) {
+        for (uint64_t v : {(uint64_t)tb->flags, (uint64_t)tb->n_rows, (uint64_t)(uintptr_t)tb->sigma_dev, (uint64_t)(uintptr_t)tb->coef_dev,
+                           (uint64_t)(uintptr_t)tb->step_dev, (uint64_t)(uintptr_t)((tb->flags & DEX_TABLES_CHURN) ? a->noise_dev : nullptr)})
+            key.push_back(v);
+    }
+    for (int j = 0; j < a->n_ref; ++j) key.push_back((uint64_t)(uintptr_t)a->ref_skips_dev[j]);
+    for (int v : knobs.v) key.push_back((uint64_t)(uint32_t)v);          // EVERY registered knob, as this call sees it
+    return key;
 }
 
 }  // namespace
@@ -1832,18 +1881,13 @@ int dex_denoise_once(DexCtx* x, const DexDenoiseArgs* da, dex_stream_t stream) {
     int rc = validate(x, a, false);
     if (rc) return rc;
     if (!da->x_dev) return x->fail(DEX_ERR_ARG, "x_dev is null");
-    const KnobSnapshot knobs;
-    const KnobScope knob_scope(&knobs);
-    const WsplitScope wsplit_scope(x->precision == DEX_PREC_FP16X2);
-    xcd_map_probe();
-    x->last_xerr = nullptr;
+    const CallScope scope(x);
     hipStream_t st = (hipStream_t)stream;
     Plan P; Dims d{a->B, a->T, a->Tr, a->Ts, 1};
     make_plan(x, d, nullptr, P);
     if (P.bytes > a->workspace_bytes) return x->fail(DEX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", P.bytes, a->workspace_bytes);
     make_plan(x, d, a->workspace_dev, P);
-    x->taps.clear();
-    if (x->prof_on) { for (auto& pr : x->prof) { hipEventDestroy(pr.a); hipEventDestroy(pr.b); } x->prof.clear(); x->prof_agg.clear(); }     // (rows describe the last call, as in dex_sample)
+    x->reset_records();
     Runner R{x, P, st, a->mask_dev, a->mu_dev, da->x_dev, a, true};
     R.sp = 0; R.stats_base = P.stats; R.stats_other = nullptr;
     hipLaunchKernelGGL(set_sigma_pair, dim3(1), dim3(1), 0, st, a->sigmas_dev, P.sig2);
@@ -1857,77 +1901,24 @@ int dex_sample(DexCtx* x, const DexSampleArgs* a, dex_stream_t stream) {
     int rc = validate(x, a, true);
     if (rc) return rc;
     if (a->solver != DEX_SOLVER_EULER && a->solver != DEX_SOLVER_HEUN) return x->fail(DEX_ERR_ARG, "solver must be DEX_SOLVER_EULER or DEX_SOLVER_HEUN (edm.py:107)");
-    const KnobSnapshot knobs;            // one reading of every knob for this call (graph-cache key below)
-    const KnobScope knob_scope(&knobs);
-    const WsplitScope wsplit_scope(x->precision == DEX_PREC_FP16X2);
-    xcd_map_probe();                    // (once per device, before any capture; normally already done by dex_ctx_create)
-    x->last_xerr = nullptr;             // set again by this call if it uses in-launch hand-offs (dex_call_status)
+    const CallScope scope(x);
     hipStream_t st = (hipStream_t)stream;
-    const bool heun = a->solver == DEX_SOLVER_HEUN;
     {
         Plan P; Dims d{a->B, a->T, a->Tr, a->Ts, dex_num_evals(a->n_steps, a->solver)};
         make_plan(x, d, nullptr, P);
         if (P.bytes > a->workspace_bytes)
             return x->fail(DEX_ERR_WORKSPACE, "workspace too small: need %zu bytes (dex_workspace_bytes with dex_num_evals(n_steps, solver)), got %zu", P.bytes, a->workspace_bytes);
     }
-    x->taps.clear();
-    if (x->prof_on) { for (auto& pr : x->prof) { hipEventDestroy(pr.a); hipEventDestroy(pr.b); } x->prof.clear(); x->prof_agg.clear(); }
-    auto enqueue = [&]() { return a->tables ? enqueue_tables(x, a, st) : heun ? enqueue_heun(x, a, st) : enqueue_euler(x, a, st); };
-    const bool use_graph = a->use_graph && !x->prof_on;
-    if (!use_graph) {
+    x->reset_records();
+    auto enqueue = [&]() { return enqueue_sampler(x, a, st); };
+    if (!a->use_graph || x->prof_on) {
         rc = enqueue();
         if (rc) return rc;
         DEX_HIPCHK(x, hipGetLastError());
         return DEX_OK;
     }
-    // One graph = the whole call.  Every device pointer the captured kernels dereference is part of the key, so a replay
-    // is only ever issued against the buffers it was captured with (the host mirror keeps persistent staging buffers, which
-    // makes every call of one shape a cache hit).
     if (st == nullptr) return x->fail(DEX_ERR_ARG, "use_graph needs a non-default stream (the legacy null stream cannot be captured)");
-    std::vector<uint64_t> key = {(uint64_t)a->B, (uint64_t)a->T, (uint64_t)a->Tr, (uint64_t)a->Ts, (uint64_t)a->n_steps, (uint64_t)a->solver,
-                                 (uint64_t)x->precision, (uint64_t)a->n_ref, (uint64_t)(uintptr_t)st,
-                                 (uint64_t)(uintptr_t)a->z_dev, (uint64_t)(uintptr_t)a->mu_dev, (uint64_t)(uintptr_t)a->mask_dev,
-                                 (uint64_t)(uintptr_t)a->sigmas_dev, (uint64_t)(uintptr_t)a->spk_dev, (uint64_t)(uintptr_t)a->sty_dev,
-                                 (uint64_t)(uintptr_t)a->sty_lengths_dev, (uint64_t)(uintptr_t)a->out_dev, (uint64_t)(uintptr_t)a->workspace_dev,
-                                 (uint64_t)(uintptr_t)(a->S_churn > 0.f ? a->noise_dev : nullptr)};
-    key.push_back((uint64_t)g_xcd_gen.load(std::memory_order_acquire));          // placement rule of the cluster hand-offs (see g_xcd_map)
-    for (float v : {a->S_churn, a->S_min, a->S_max, a->S_noise}) { uint32_t u; memcpy(&u, &v, 4); key.push_back(u); }
-    key.push_back(a->tables ? 1u : 0u);             // the general sampler: its flags pick the launches, its tables are read at replay
-    if (const DexSamplerTables* tb = a->tables) {
-        for (uint64_t v : {(uint64_t)tb->flags, (uint64_t)tb->n_rows, (uint64_t)(uintptr_t)tb->sigma_dev, (uint64_t)(uintptr_t)tb->coef_dev,
-                           (uint64_t)(uintptr_t)tb->step_dev, (uint64_t)(uintptr_t)((tb->flags & DEX_TABLES_CHURN) ? a->noise_dev : nullptr)})
-            key.push_back(v);
-    }
-    for (int j = 0; j < a->n_ref; ++j) key.push_back((uint64_t)(uintptr_t)a->ref_skips_dev[j]);
-    for (int v : knobs.v) key.push_back((uint64_t)(uint32_t)v);          // EVERY registered knob, as this call sees it
-    DexCtx::GraphEntry* hit = nullptr;
-    for (auto& g : x->graphs) if (g.key == key) { hit = &g; break; }
-    if (!hit) {
-        constexpr size_t MAX_GRAPHS = 8;
-        if (x->graphs.size() >= MAX_GRAPHS) {                 // evict the least recently used graph
-            size_t lru = 0;
-            for (size_t i = 1; i < x->graphs.size(); ++i) if (x->graphs[i].stamp < x->graphs[lru].stamp) lru = i;
-            hipGraphExecDestroy(x->graphs[lru].exec);
-            x->graphs.erase(x->graphs.begin() + lru);
-        }
-        hipGraph_t graph = nullptr;
-        DEX_HIPCHK(x, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        rc = enqueue();
-        hipError_t ec = hipStreamEndCapture(st, &graph);          // always leave capture mode
-        if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
-        if (ec != hipSuccess || !graph) return x->fail(DEX_ERR_HIP, "stream capture failed: %s", hipGetErrorString(ec));
-        hipGraphExec_t exec = nullptr;
-        ec = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        if (ec != hipSuccess) return x->fail(DEX_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ec));
-        x->graphs.push_back({key, exec, 0, x->last_xerr});        // (the Runner set last_xerr while its launches were captured)
-        hit = &x->graphs.back();
-    }
-    x->last_xerr = hit->xerr;           // a replay enqueues nothing on the host: dex_call_status reads the word the CAPTURED launches write
-    hit->stamp = ++x->graph_clock;
-    DEX_HIPCHK(x, hipGraphLaunch(hit->exec, st));
-    DEX_HIPCHK(x, hipGetLastError());
-    return DEX_OK;
+    return x->replay(graph_key(a, x->precision, st, scope.knobs), st, enqueue);
 }
 
 // ---- taps ---------------------------------------------------------------------------------------

@@ -120,6 +120,7 @@ class ScoreNetEngine:
     # ---------------------------------------------------------------------------------------
     def _fill_args(self, a: _lib.DexSampleArgs, mu, mask, sigmas, out, n_steps, spk, ref, sty, sty_lengths, use_graph,
                    solver="euler", noise=None, churn=None):
+        """Fill the C argument block from inputs in the form ``_inputs`` returns; the list it returns keeps them alive."""
         if solver not in _lib.SOLVER:
             raise ValueError(f"solver must be 'euler' or 'heun' (edm.py:107), got {solver!r}")
         B, F, T = mu.shape
@@ -132,14 +133,11 @@ class ScoreNetEngine:
         a.B, a.T, a.n_steps = B, T, n_steps
         a.mu_dev, a.mask_dev, a.sigmas_dev, a.out_dev = mu.data_ptr(), mask.data_ptr(), sigmas.data_ptr(), out.data_ptr()
         a.spk_dev = None
-        if spk is not None and self.cfg.n_spks > 1:
-            spk = spk.to(device=self.device, dtype=torch.float32).contiguous()
+        if spk is not None:
             keep.append(spk); a.spk_dev = spk.data_ptr()
         a.ref_skips_dev, a.n_ref, a.Tr, a.sty_dev, a.sty_lengths_dev, a.Ts = None, 0, 0, None, None, 0
         if self.cfg.variant == "dex":
-            ref = [r.to(device=self.device, dtype=torch.float32).contiguous() for r in ref]
-            sty = sty.to(device=self.device, dtype=torch.float32).contiguous()
-            sl = sty_lengths.to(device=self.device, dtype=torch.int32).contiguous()
+            sl = sty_lengths
             if not 1 <= len(ref) <= 7:
                 raise ValueError(f"DEX needs 1..7 reference skips, got {len(ref)}")
             mid = self.cfg.mid_dim
@@ -173,28 +171,37 @@ class ScoreNetEngine:
             a.S_max = 0.0 if S_max == float("inf") else float(S_max)          # <= 0 is the library's +inf
         return keep
 
-    @staticmethod
-    def _prep_mask(mask, B, T, device):
-        m = mask.to(device=device, dtype=torch.float32).reshape(B, T).contiguous()
-        return m
+    def _inputs(self, mu, mask, spk, ref, sty, sty_lengths):
+        """The conditioning inputs of sample() / denoise_once() on the device, in the library's types, contiguous (spk only for
+        multi-speaker models, the style inputs only for DEX)."""
+        f32 = dict(device=self.device, dtype=torch.float32)
+        mu = mu.to(**f32).contiguous()
+        B, _, T = mu.shape
+        mask = mask.to(**f32).reshape(B, T).contiguous()
+        spk = spk.to(**f32).contiguous() if spk is not None and self.cfg.n_spks > 1 else None
+        if self.cfg.variant == "dex" and ref is not None and sty is not None and sty_lengths is not None:
+            ref = [r.to(**f32).contiguous() for r in ref]
+            sty = sty.to(**f32).contiguous()
+            sty_lengths = sty_lengths.to(device=self.device, dtype=torch.int32).contiguous()
+        return mu, mask, spk, ref, sty, sty_lengths
 
-    def _staged(self, key, tensors):
+    def _staged(self, key, tensors: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """Persistent device buffers for graph replays: a captured graph dereferences fixed addresses, so the inputs of a
-        call are copied into buffers that live as long as the engine (one set per shape), which makes every call of a
-        shape a hit in the library's graph cache."""
+        call are copied, name by name, into buffers that live as long as the engine (one set per shape), which makes every
+        call of a shape a hit in the library's graph cache."""
         bufs = self._stage.get(key)
         if bufs is None:
             if len(self._stage) >= 8:                       # least recently used shape goes, together with its output buffer
                 old = next(iter(self._stage))
                 self._stage.pop(old)
                 self._stage_out.pop(old, None)
-            bufs = [torch.empty_like(t) for t in tensors]
+            bufs = {name: torch.empty_like(t) for name, t in tensors.items()}
             self._stage[key] = bufs
         else:
             self._stage[key] = self._stage.pop(key)          # dicts keep insertion order: re-insert = most recently used
         cur = torch.cuda.current_stream(self.device)
-        for b, t in zip(bufs, tensors):
-            b.copy_(t, non_blocking=True)
+        for name, t in tensors.items():
+            bufs[name].copy_(t, non_blocking=True)
             if t.is_cuda:
                 t.record_stream(cur)       # the caller's tensor may be freed (and its block reused on ITS stream) before this copy has run
         return bufs
@@ -223,53 +230,41 @@ class ScoreNetEngine:
                 self._side.wait_stream(cur)
                 run_on = self._side
             with torch.cuda.stream(run_on):
-                mu = mu.to(device=self.device, dtype=torch.float32).contiguous()
+                mu, mask, spk, ref, sty, sty_lengths = self._inputs(mu, mask, spk, ref, sty, sty_lengths)
                 z = z.to(device=self.device, dtype=torch.float32).contiguous()
                 B, _, T = mu.shape
-                mask = self._prep_mask(mask, B, T, self.device)
-                tabs = []
+                coef = step = None
                 if tables is not None:
                     if tables.n_steps != n_steps or tables.solver != solver:
                         raise ValueError(f"tables were made for {tables.n_steps} {tables.solver} steps, not {n_steps} {solver}")
-                    sig, *tabs = tables.to(self.device)          # evaluation sigmas [E + 1], coefficients [E, 8], step rows [n, 4]
+                    sig, coef, step = tables.to(self.device)     # evaluation sigmas [E + 1], coefficients [E, 8], step rows [n, 4]
                 else:
                     sig = edm_sigmas(n_steps).to(self.device)
-                if self.cfg.variant == "dex" and ref is not None and sty is not None and sty_lengths is not None:
-                    ref = [r.to(device=self.device, dtype=torch.float32).contiguous() for r in ref]
-                    sty = sty.to(device=self.device, dtype=torch.float32).contiguous()
-                    sty_lengths = sty_lengths.to(device=self.device, dtype=torch.int32).contiguous()
-                if spk is not None and self.cfg.n_spks > 1:
-                    spk = spk.to(device=self.device, dtype=torch.float32).contiguous()
-                else:
-                    spk = None
                 churn = (S_churn, S_min, S_max, S_noise) if tables is None and S_churn and S_churn > 0 else None
                 if churn is not None:
                     if noise is None:
                         raise ValueError("S_churn > 0 needs the per-step noise draws (noise=[n_steps,B,80,T])")
-                    noise = noise.to(device=self.device, dtype=torch.float32).contiguous()
                 elif tables is not None and tables.noise:
                     if noise is None or tuple(noise.shape) != (n_steps, B, 80, T):
                         raise ValueError(f"these tables add noise (edm.py:196): noise of shape {(n_steps, B, 80, T)} is needed")
-                    noise = noise.to(device=self.device, dtype=torch.float32).contiguous()
                 else:
                     noise = None
+                if noise is not None:
+                    noise = noise.to(device=self.device, dtype=torch.float32).contiguous()
                 if use_graph:
-                    dexin = ([sty, sty_lengths] + list(ref)) if (self.cfg.variant == "dex" and ref is not None) else []
-                    flat = [z, mu, mask, sig] + tabs + ([spk] if spk is not None else []) + ([noise] if noise is not None else []) + dexin
-                    key = (n_steps, solver, spk is not None, noise is not None) + tuple((tuple(t.shape), t.dtype) for t in flat)
+                    # every device input of the call by name, in a fixed order; absent ones are left out
+                    inp = {"z": z, "mu": mu, "mask": mask, "sig": sig, "coef": coef, "step": step, "spk": spk, "noise": noise}
+                    if self.cfg.variant == "dex" and ref is not None:
+                        inp.update(sty=sty, sty_lengths=sty_lengths, **{f"ref{j}": r for j, r in enumerate(ref)})
+                    inp = {name: t for name, t in inp.items() if t is not None}
+                    key = (n_steps, solver, spk is not None, noise is not None) + tuple((tuple(t.shape), t.dtype) for t in inp.values())
                     if tables is not None:
                         key += ("tables", tables.flags)
-                    st = self._staged(key, flat)
-                    z, mu, mask, sig = st[:4]
-                    k = 4
-                    if tabs:
-                        tabs = st[4:6]; k = 6
-                    if spk is not None:
-                        spk = st[k]; k += 1
-                    if noise is not None:
-                        noise = st[k]; k += 1
-                    if dexin:
-                        sty, sty_lengths, ref = st[k], st[k + 1], st[k + 2:]
+                    inp = self._staged(key, inp)
+                    z, mu, mask, sig = inp["z"], inp["mu"], inp["mask"], inp["sig"]
+                    coef, step, spk, noise = inp.get("coef"), inp.get("step"), inp.get("spk"), inp.get("noise")
+                    if "sty" in inp:
+                        sty, sty_lengths, ref = inp["sty"], inp["sty_lengths"], [inp[f"ref{j}"] for j in range(len(ref))]
                     out = self._stage_out.setdefault(key, torch.empty_like(mu))
                 else:
                     out = torch.empty_like(mu)
@@ -277,9 +272,9 @@ class ScoreNetEngine:
                 keep = self._fill_args(a, mu, mask, sig, out, n_steps, spk, ref, sty, sty_lengths, use_graph, solver, noise, churn)
                 a.z_dev = z.data_ptr()
                 if tables is not None:
-                    tb = _lib.DexSamplerTables(sig.data_ptr(), tabs[0].data_ptr(), tabs[1].data_ptr(), tables.n_rows, tables.flags)
+                    tb = _lib.DexSamplerTables(sig.data_ptr(), coef.data_ptr(), step.data_ptr(), tables.n_rows, tables.flags)
                     a.tables = C.pointer(tb)
-                    keep += list(tabs) + [tb]
+                    keep += [coef, step, tb]
                     if noise is not None:
                         a.noise_dev = noise.data_ptr()
                         keep.append(noise)
@@ -311,10 +306,8 @@ class ScoreNetEngine:
     def denoise_once(self, x, sigma: float, mask, mu, spk=None, ref=None, sty=None, sty_lengths=None):
         """One EDMPrecond.forward (edm.py:88-98); also records debug taps."""
         with torch.cuda.device(self.device):
-            mu = mu.to(device=self.device, dtype=torch.float32).contiguous()
+            mu, mask, spk, ref, sty, sty_lengths = self._inputs(mu, mask, spk, ref, sty, sty_lengths)
             x = x.to(device=self.device, dtype=torch.float32).contiguous()
-            B, _, T = mu.shape
-            mask = self._prep_mask(mask, B, T, self.device)
             sig = torch.tensor([float(sigma), 0.0], dtype=torch.float32).to(self.device)
             out = torch.empty_like(mu)
             d = _lib.DexDenoiseArgs()
