@@ -92,7 +92,7 @@ void xcd_map_probe();       // (defined with the cluster launch plan below)
 
 struct TD { float* p; int ld; int coff; int C; int lp = 0; };   // channels-last activation view; lp: 16-bit elements (1 bf16, 2 fp16)
 
-struct ResW { const float *w1, *b1, *g1, *be1, *w2, *b2, *g2, *be2, *wr, *br, *mlp_w, *mlp_b; int cin, cout; };
+struct ResW { PackedW w1, w2, wr; const float *b1, *g1, *be1, *b2, *g2, *be2, *br, *mlp_w, *mlp_b; int cin, cout; };     // wr: empty without a res_conv
 constexpr int ATT_KSPLIT_MAX = 4;     // key-split attention partials kept per token by the 32-query forms (dit_rowchain.hip merges them)
 // The 64-query form (attention_q64.hip) may split further where there are few tokens (long-form: one utterance, thousands of tokens, 40
 // workgroup-sized query groups for 256 CUs): up to 8 partials there, 4 at batch size (the partial buffer is tokens x hidden x cap fp32).
@@ -104,8 +104,8 @@ static bool attention_q64_regime(int N, int B) {
     const int nt32 = (N + 31) / 32, ng = (nt32 + 7) / 8;
     return 2L * B * ng * ks >= 128;
 }
-struct LinW { const float *wqkv, *wqkv_raw, *wout_raw, *bias_eff, *g; const void *wq_lp[3], *wkv_lp[3], *wq_frag[3]; int C; };   // [0] bf16, [1] fp16, [2] fp16 hi + lo
-struct DitBlockW { const float *wqkv, *bqkv, *wproj, *bproj, *wfc1, *bfc1, *wfc2, *bfc2, *ada_w, *ada_b; };
+struct LinW { PackedW wqkv; const float *wqkv_raw, *wout_raw, *bias_eff, *g; LpView wkv[3], wq_frag[3]; int C; };   // wkv, wq_frag: 16-bit k | v rows / q rows in fragment order of wqkv_raw, per twin set
+struct DitBlockW { PackedW wqkv, wproj, wfc1, wfc2; const float *bqkv, *bproj, *bfc1, *bfc2, *ada_w, *ada_b; };
 
 struct Prof { std::string name; hipEvent_t a, b; double flops, bytes; };
 struct ProfAgg { std::string name; int calls; double ms, flops, bytes; };
@@ -128,33 +128,28 @@ struct Arena {                                             // bump allocator ove
 struct DexCtx : WeightStore {
     DexCtx() : WeightStore("") {}
     DexConfig cfg{};
-    // low-precision twins of the fp32 [K][N] packs, one set per operand type: [0] bf16, [1] fp16 (both are packed at
-    // finalize: the precision mode may change afterwards)
-    // [2] = the split-weight mode (DEX_PREC_FP16X2): fp16 twins whose lo pack (fp16 of what the hi rounding lost, same layout) follows
-    // the hi pack; lo_off_ maps a twin pointer to the distance in elements from a hi element to its lo element
-    std::map<const float*, const void*> lp_of_[3];         // -> [N][K] twin
-    std::map<const float*, const void*> frag_of_[3];       // -> MFMA-fragment-order twin (DiT row chain)
-    std::map<const void*, long> lo_off_;
-    long lo_off(const void* twin) const { auto it = lo_off_.find(twin); return it == lo_off_.end() ? 0 : it->second; }
+    // Every weight a matrix kernel reads is a PackedW (weight_store.h): the fp32 [K][N] pack and its 16-bit twins, one set per operand
+    // type - [0] bf16, [1] fp16, [2] the split-weight mode (DEX_PREC_FP16X2): fp16 twins whose lo pack follows the hi pack, lo_off elements
+    // behind.  lpi() is the set of the current mode; the launch code reads w.nk[lpi()] / w.frag[lpi()] and nothing else picks a set.
     int lpi() const { return precision == DEX_PREC_FP16X2 ? 2 : precision == DEX_PREC_FP16 ? 1 : 0; }
     int lp_kind() const { return precision == DEX_PREC_BF16 ? 1 : 2; }      // the element-wise kernels' runtime code (fp16 for both fp16 modes)
     bool lp() const { return precision != DEX_PREC_FP32; }
-    const std::map<const float*, const void*>& lp_of() const { return lp_of_[lpi()]; }
-    const std::map<const float*, const void*>& frag_of() const { return frag_of_[lpi()]; }
     bool tuned = true;                                     // geometry the reduced-precision kernels are built for (dex_ctx_create)
     int precision = DEX_PREC_FP32;
     // packed weights
     std::vector<std::vector<ResW>> down_res, up_res;       // [stage][2]
     std::vector<LinW> down_lin, up_lin;
-    std::vector<const float*> down_ds_w, down_ds_b;        // Downsample
-    std::vector<const float*> up_us_w, up_us_b;            // Upsample: 4 parity matrices back to back
+    std::vector<PackedW> down_ds_w;                        // Downsample
+    std::vector<std::vector<PackedW>> up_us_w;             // Upsample: [stage][parity], 4 matrices back to back (one group)
+    std::vector<const float*> down_ds_b, up_us_b;
     const float *fc_w3 = nullptr, *fc_w1 = nullptr;        // first conv packs
-    const float *fin_w = nullptr, *fin_b = nullptr, *fin_g = nullptr, *fin_be = nullptr, *fconv_w = nullptr, *fconv_b = nullptr;
-    const float *pe_dw = nullptr, *pe_db = nullptr, *pe_pw = nullptr, *pe_pb = nullptr, *pos_w = nullptr, *pos_b = nullptr, *freq_pos = nullptr;
-    const void* pos_wfrag[3] = {nullptr, nullptr, nullptr}; // pos-conv weights in MFMA fragment order (pos_conv.hip), bf16 / fp16 / fp16 hi + lo
+    PackedW fin_w, pe_pw, fl_w, tv_wk, tv_wv, tv_wl;
+    PackedW pos_w;                                         // group 0 of the G pos-conv matrices; frag: all groups in MFMA fragment order (pos_conv.hip)
+    const float *fin_b = nullptr, *fin_g = nullptr, *fin_be = nullptr, *fconv_w = nullptr, *fconv_b = nullptr;
+    const float *pe_dw = nullptr, *pe_db = nullptr, *pe_pb = nullptr, *pos_b = nullptr, *freq_pos = nullptr;
     std::vector<DitBlockW> blocks;
-    const float *fl_w = nullptr, *fl_b = nullptr, *fl_ada_w = nullptr, *fl_ada_b = nullptr;
-    const float *tv_wq_raw = nullptr, *tv_wk = nullptr, *tv_wv = nullptr, *tv_wl = nullptr;
+    const float *fl_b = nullptr, *fl_ada_w = nullptr, *fl_ada_b = nullptr;
+    const float *tv_wq_raw = nullptr;
     // mel front-end constants
     float *mel_basis = nullptr, *mel_filt = nullptr; void* mel_ws = nullptr; size_t mel_ws_bytes = 0;
     const int* last_xerr = nullptr;     // time-out word of the last call's cluster row chain (inside that call's workspace)
@@ -423,7 +418,7 @@ struct Packer {
     float* alloc(long n) { return x->alloc(n); }
     // twin set t: 0 bf16, 1 fp16, 2 fp16 hi + lo.  pack3 runs `pack(src, dst, precision)` for the set: once, or (t == 2) on the weight
     // and on what its fp16 rounding lost (src - float(fp16(src)), through a scratch fp32 copy - packs are permutations, so the lo pack
-    // has the hi pack's layout), the lo pack `n_dst` elements behind the hi pack.
+    // has the hi pack's layout), the lo pack `n_dst` elements behind the hi pack.  Returns the view of what it packed.
     float* tmp = nullptr; long tmp_n = 0;
     float* scratch(long n) {
         if (n > tmp_n) { tmp = alloc(n); tmp_n = tmp ? n : 0; }     // (stream-ordered reuse: every pack of this Packer runs on `st`)
@@ -431,38 +426,37 @@ struct Packer {
     }
     static constexpr int NSETS = 3;
     static long set_elems(int t, long n) { return t == 2 ? 2 * n : n; }
-    template <class F> void pack3(int t, const float* src, long n_src, unsigned short* dst, long n_dst, F pack) {
-        if (t < 2) { pack(src, dst, t ? PREC_FP16 : PREC_BF16); return; }
+    template <class F> LpView pack3(int t, const float* src, long n_src, unsigned short* dst, long n_dst, F pack) {
+        if (t < 2) { pack(src, dst, t ? PREC_FP16 : PREC_BF16); return {dst, 0}; }
         pack(src, dst, PREC_FP16);
         float* lo = scratch(n_src);
-        if (!lo) return;
+        if (!lo) return {};
         launch_f32_residual_lp(src, lo, n_src, PREC_FP16, st);
         pack(lo, dst + n_dst, PREC_FP16);
+        return {dst, n_dst};
     }
-    // 16-bit [N][K] twins of `count` consecutive fp32 [K][N] matrices starting at p
-    void twin(const float* p, int count, int K, int N) {
-        if (!p) return;
+    // the handles of `count` consecutive fp32 [K][N] matrices starting at p, with their 16-bit [N][K] twins (one group per set)
+    std::vector<PackedW> twin(const float* p, int count, int K, int N) {
+        std::vector<PackedW> w(count);
+        if (!p) return w;
+        for (int c = 0; c < count; ++c) w[c].f32 = p + (long)c * K * N;
         for (int t = 0; t < NSETS; ++t) {
             const long n = (long)count * K * N;
             unsigned short* d = (unsigned short*)alloc((set_elems(t, n) + 1) / 2);
-            if (!d) return;
-            for (int c = 0; c < count; ++c) {
-                unsigned short* dc = d + (long)c * K * N;
-                pack3(t, p + (long)c * K * N, (long)K * N, dc, n, [&](const float* s, unsigned short* o, int prec) { launch_pack_lp_nk(s, o, K, N, prec, st); });
-                x->lp_of_[t][p + (long)c * K * N] = dc;
-                if (t == 2) x->lo_off_[dc] = n;
-            }
+            if (!d) return w;
+            for (int c = 0; c < count; ++c)
+                w[c].nk[t] = pack3(t, w[c].f32, (long)K * N, d + (long)c * K * N, n, [&](const float* s, unsigned short* o, int prec) { launch_pack_lp_nk(s, o, K, N, prec, st); });
         }
+        return w;
     }
-    void frag(const float* p, int K, int N) {
-        if (!p) return;
+    // ... and the MFMA-fragment-order twins of one of them
+    void frag(PackedW& w, int K, int N) {
+        if (!w) return;
         for (int t = 0; t < NSETS; ++t) {
             const long n = (long)K * N;
             unsigned short* d = (unsigned short*)alloc((set_elems(t, n) + 1) / 2);
             if (!d) return;
-            pack3(t, p, n, d, n, [&](const float* s, unsigned short* o, int prec) { launch_pack_lp_frag(s, o, K, N, prec, st); });
-            x->frag_of_[t][p] = d;
-            if (t == 2) x->lo_off_[d] = n;
+            w.frag[t] = pack3(t, w.f32, n, d, n, [&](const float* s, unsigned short* o, int prec) { launch_pack_lp_frag(s, o, K, N, prec, st); });
         }
     }
     const RawW& R(const std::string& k) { return x->raw.at(k); }
@@ -474,11 +468,10 @@ struct Packer {
         return dst;
     }
     // conv / linear weight [out, in, kh, kw] -> [(kh*KW+kw)*in + ci][out]
-    const float* kn(const std::string& k) {
+    PackedW kn(const std::string& k) {
         const auto& s = R(k).shape;
         const int o = (int)s[0], i = (int)s[1], kh = s.size() > 2 ? (int)s[2] : 1, kw = s.size() > 3 ? (int)s[3] : 1;
-        const float* f = perm(k, o, i, kh, kw, 2, 3, 1, 0);
-        twin(f, 1, i * kh * kw, o);
+        PackedW f = twin(perm(k, o, i, kh, kw, 2, 3, 1, 0), 1, i * kh * kw, o)[0];
         if (kh == 3 && kw == 3 && ((i == 128 && o == 128) || (i == 64 && o == 128))) frag(f, 9 * i, o);      // weights-in-registers strip convolutions (conv3x3_regw.hip)
         if (kh == 1 && kw == 1 && i == 64 && o == 128) frag(f, i, o);                                          // ... and the 1x1 shortcut fused into the 64 -> 128 one
         return f;
@@ -492,7 +485,7 @@ struct Packer {
             r.wr = perm(p + ".res_conv.weight", cout, cin, 1, 1, 1, 2, 3, 0);
         } else {
             r.w1 = kn(b1 + ".0.weight");
-            r.wr = (cin != cout) ? kn(p + ".res_conv.weight") : nullptr;
+            if (cin != cout) r.wr = kn(p + ".res_conv.weight");
         }
         r.br = (cin != cout) ? raw(p + ".res_conv.bias") : nullptr;
         r.b1 = raw(b1 + ".0.bias"); r.g1 = raw(b1 + ".1.weight"); r.be1 = raw(b1 + ".1.bias");
@@ -510,12 +503,10 @@ struct Packer {
         {   // bf16 copy of the q | k | v rows in their native [N][K] layout (MFMA operands of the fused kernels)
             for (int t = 0; t < NSETS; ++t) {
                 unsigned short* qb = (unsigned short*)alloc((set_elems(t, 384L * c) + 1) / 2);
-                if (qb) pack3(t, l.wqkv_raw, 384L * c, qb, 384L * c, [&](const float* s, unsigned short* o, int prec) { launch_f32_to_lp(s, o, 384L * c, prec, st); });
-                l.wq_lp[t] = qb; l.wkv_lp[t] = qb ? qb + 128L * c : nullptr;        // (t == 2: the lo rows 384 c elements behind)
+                if (qb) l.wkv[t] = {qb + 128L * c, pack3(t, l.wqkv_raw, 384L * c, qb, 384L * c, [&](const float* s, unsigned short* o, int prec) { launch_f32_to_lp(s, o, 384L * c, prec, st); }).lo_off};
                 // the q rows again in MFMA fragment order (A operand of the tail's first GEMM: 1 KB contiguous per wave load)
                 unsigned short* qf = (unsigned short*)alloc((set_elems(t, 128L * c) + 1) / 2);
-                if (qf) pack3(t, l.wqkv_raw, 128L * c, qf, 128L * c, [&](const float* s, unsigned short* o, int prec) { launch_pack_lp_frag_nk(s, o, c, 128, prec, st); });
-                l.wq_frag[t] = qf;
+                if (qf) l.wq_frag[t] = pack3(t, l.wqkv_raw, 128L * c, qf, 128L * c, [&](const float* s, unsigned short* o, int prec) { launch_pack_lp_frag_nk(s, o, c, 128, prec, st); });
             }
         }
         l.g = raw(p + ".fn.g");
@@ -547,8 +538,6 @@ void build_mel_constants(std::vector<float>& basis, std::vector<float>& filt) {
 extern "C" int dex_ctx_finalize(DexCtx* x, dex_stream_t stream) {
     if (!x) return DEX_ERR_ARG;
     if (int rc = x->begin_finalize()) return rc;
-    for (int t = 0; t < 3; ++t) { x->lp_of_[t].clear(); x->frag_of_[t].clear(); }
-    x->lo_off_.clear();
     x->drop_graphs();
     const DexConfig& c = x->cfg;
     hipStream_t st = (hipStream_t)stream;
@@ -573,12 +562,9 @@ extern "C" int dex_ctx_finalize(DexCtx* x, dex_stream_t stream) {
         x->up_res[j].push_back(P.resnet(p + ".1", ci, ci, false));
         x->up_lin.push_back(P.linattn(p + ".2", ci));
         float* wt = P.alloc(16L * ci * ci);
-        if (wt) {
-            hipLaunchKernelGGL(pack_convt_kernel, dim3(256), dim3(256), 0, st, P.raw(p + ".3.conv.weight"), wt, ci, ci);
-            P.twin(wt, 4, 4 * ci, ci);
-            if (convt_up_supported(ci, 1, 1, ci, ci)) for (int par = 0; par < 4; ++par) P.frag(wt + (long)par * 4 * ci * ci, 4 * ci, ci);   // convt_up.hip
-        }
-        x->up_us_w.push_back(wt); x->up_us_b.push_back(P.raw(p + ".3.conv.bias"));
+        if (wt) hipLaunchKernelGGL(pack_convt_kernel, dim3(256), dim3(256), 0, st, P.raw(p + ".3.conv.weight"), wt, ci, ci);
+        x->up_us_w.push_back(P.twin(wt, 4, 4 * ci, ci)); x->up_us_b.push_back(P.raw(p + ".3.conv.bias"));
+        if (convt_up_supported(ci, 1, 1, ci, ci)) for (PackedW& w : x->up_us_w.back()) P.frag(w, 4 * ci, ci);   // convt_up.hip
     }
     x->fin_w = P.kn("final_block.block.0.weight"); x->fin_b = P.raw("final_block.block.0.bias");
     x->fin_g = P.raw("final_block.block.1.weight"); x->fin_be = P.raw("final_block.block.1.bias");
@@ -587,26 +573,26 @@ extern "C" int dex_ctx_finalize(DexCtx* x, dex_stream_t stream) {
     x->pe_dw = P.perm("vit.x_embedder.proj.0.weight", mid, 1, c.dit_patch, c.dit_patch, 2, 3, 1, 0);
     x->pe_db = P.raw("vit.x_embedder.proj.0.bias");
     x->pe_pw = P.kn("vit.x_embedder.proj.2.weight"); x->pe_pb = P.raw("vit.x_embedder.proj.2.bias");
-    x->pos_w = P.perm("vit.pos_conv.0.weight", G, hid / G, hid / G, kp * kp, 0, 3, 2, 1);   // [G][tap][ci][n]
+    const float* posw = P.perm("vit.pos_conv.0.weight", G, hid / G, hid / G, kp * kp, 0, 3, 2, 1);   // [G][tap][ci][n]
     if ((hid / G) % 32) {       // e.g. 48-channel groups (hidden 384): [G][tap][ci][n] -> zero-padded [G][tap][cgp][cgp], cgp = 64
         const int cg = hid / G, cgp = 64;
         float* wp = P.alloc((long)G * kp * kp * cgp * cgp);
         if (wp) {
             hipMemsetAsync(wp, 0, (size_t)G * kp * kp * cgp * cgp * sizeof(float), st);
             for (long gt = 0; gt < (long)G * kp * kp; ++gt)     // one 2-D copy per (group, tap): cg rows of cg floats into a cgp x cgp tile
-                hipMemcpy2DAsync(wp + gt * cgp * cgp, (size_t)cgp * 4, x->pos_w + gt * cg * cg, (size_t)cg * 4, (size_t)cg * 4, cg, hipMemcpyDeviceToDevice, st);
+                hipMemcpy2DAsync(wp + gt * cgp * cgp, (size_t)cgp * 4, posw + gt * cg * cg, (size_t)cg * 4, (size_t)cg * 4, cg, hipMemcpyDeviceToDevice, st);
         }
-        x->pos_w = wp;
+        x->pos_w = wp;           // (no [N][K] twins: this form runs on the fp32 operand in every mode)
     } else
-    P.twin(x->pos_w, G, kp * kp * (hid / G), hid / G);
-    x->pos_wfrag[0] = x->pos_wfrag[1] = x->pos_wfrag[2] = nullptr;
+    x->pos_w = P.twin(posw, G, kp * kp * (hid / G), hid / G)[0];
     if (pos_conv_direct_supported(hid, G, kp, token_rows(c))) {
         const long kn_ = (long)kp * kp * (hid / G) * (hid / G);
         for (int t = 0; t < Packer::NSETS; ++t) {
             unsigned short* wf = (unsigned short*)P.alloc((Packer::set_elems(t, G * kn_) + 1) / 2);
-            if (wf) for (int g = 0; g < G; ++g)
-                P.pack3(t, x->pos_w + g * kn_, kn_, wf + g * kn_, G * kn_, [&](const float* s, unsigned short* o, int prec) { launch_pack_lp_frag(s, o, kp * kp * (hid / G), hid / G, prec, st); });
-            x->pos_wfrag[t] = wf;
+            if (wf) for (int g = 0; g < G; ++g) {
+                const LpView v = P.pack3(t, x->pos_w.f32 + g * kn_, kn_, wf + g * kn_, G * kn_, [&](const float* s, unsigned short* o, int prec) { launch_pack_lp_frag(s, o, kp * kp * (hid / G), hid / G, prec, st); });
+                if (g == 0) x->pos_w.frag[t] = v;
+            }
         }
     }
     x->pos_b = P.raw("vit.pos_conv.0.bias");
@@ -908,15 +894,15 @@ struct Runner {
         x->taps.push_back(t);
     }
 
-    IGemmP base_gemm(const float* A, int lda, int acoff, int H, int W, int Cin, const float* Wt, int N, const float* bias,
+    IGemmP base_gemm(const float* A, int lda, int acoff, int H, int W, int Cin, const PackedW& Wt, int N, const float* bias,
                      float* C, int ldc, int ccoff) {
         IGemmP g{};
         g.A = A; g.lda = lda; g.a_bstride = (long)H * W * lda; g.a_coff = acoff;
         g.Hi = H; g.Wi = W; g.Cin = Cin;
         g.KH = 1; g.KW = 1; g.sh = 1; g.sw = 1; g.off_h = 0; g.off_w = 0; g.step_h = 1; g.step_w = 1;
         g.Ho = H; g.Wo = W;
-        g.W = Wt; g.w_bstride = 0; g.w_gstride = 0;
-        { auto it = x->lp_of().find(Wt); g.Wbf = (it != x->lp_of().end()) ? it->second : nullptr; }
+        g.W = Wt.f32; g.w_bstride = 0; g.w_gstride = 0;
+        g.Wbf = Wt.nk[x->lpi()].p; g.w_lo_off = Wt.nk[x->lpi()].lo_off;      // (split-weight mode: where the lo pack of this twin sits; operands built at run time set both themselves)
         g.N = N; g.K = Cin; g.ksplit = 1; g.groups = 1;
         g.bias = bias; g.bias_bstride = 0;
         g.C = C; g.ldc = ldc; g.c_bstride = (long)H * W * ldc; g.c_sstride = 0; g.c_coff = ccoff;
@@ -927,9 +913,7 @@ struct Runner {
         g.step = sp; g.unpatch_s = 0; g.unpatch_C = 0; g.B = P.d.B;
         return g;
     }
-    void gemm(const char* name, const IGemmP& g_in) {
-        IGemmP g = g_in;
-        if (!g.w_lo_off) g.w_lo_off = g.Wbf ? x->lo_off(g.Wbf) : 0;      // split-weight mode: where the lo pack of this twin sits (0: a plain 16-bit operand; set by the caller for operands built at run time)
+    void gemm(const char* name, const IGemmP& g) {
         const double M = (double)g.Ho * g.Wo * g.B;
         const double fl = 2.0 * M * g.N * g.groups * g.K;
         const double by = 4.0 * (M * g.Cin * g.groups + M * g.N * g.groups * g.ksplit + (double)g.K * g.N * g.groups);
@@ -946,15 +930,15 @@ struct Runner {
     static bool ln_fusable(int K) { return K == 64 || K == 128 || K == 256 || K == 512; }
     bool h_bf16() const { return x->lp() && !knob_off("DEX_H_BF16"); }
     bool fast_conv(int cin, int cout) const { return x->lp() && conv3x3_bf16_supported(cin, cout); }
-    void conv3x3(const char* name, const TD& X, int H, int W, int mask_ws, bool inmask, const float* Wt, const float* bias, int Cout, float* out,
+    void conv3x3(const char* name, const TD& X, int H, int W, int mask_ws, bool inmask, const PackedW& Wt, const float* bias, int Cout, float* out,
                  gnfix_t* gn = nullptr, const Pro* pro = nullptr, const ResW* shortcut = nullptr, float* shortcut_out = nullptr,
                  bool xb = false, bool yb = false) {
-        auto it = x->lp_of().find(Wt);
-        if (fast_conv(X.C, Cout) && it != x->lp_of().end()) {
+        const int t = x->lpi();
+        if (fast_conv(X.C, Cout) && Wt.nk[t].p) {
             Conv3P c{};
             c.x_bf16 = (xb || X.lp) ? 1 : 0; c.y_bf16 = yb ? 1 : 0;
             c.X = X.p; c.ldx = X.ld; c.x_coff = X.coff; c.H = H; c.W = W; c.Cin = X.C; c.Cout = Cout;
-            c.Wbf = it->second; c.w_lo_off = x->lo_off(c.Wbf); c.bias = bias; c.Y = out; c.mask = mask; c.mask_ws = mask_ws; c.mask_bstride = P.d.T;
+            c.Wbf = Wt.nk[t].p; c.w_lo_off = Wt.nk[t].lo_off; c.bias = bias; c.Y = out; c.mask = mask; c.mask_ws = mask_ws; c.mask_bstride = P.d.T;
             if (pro) { c.pro_stats = pro->stats; c.pro_gamma = pro->gamma; c.pro_beta = pro->beta; c.pro_tadd = pro->tadd; c.pro_res = pro->res; c.pro_xout = pro->xout;
                 if (pro->res2) {
                     const FirstConvP& f = pro->res2f;
@@ -962,11 +946,11 @@ struct Runner {
                     c.res2_scal = f.scal; c.res2_scal_stride = f.scal_stride; c.res2_planes = f.planes;
                 } }
             c.step = sp; c.gn_stats = gn; c.B = P.d.B;
-            { auto itf = x->frag_of().find(Wt); c.Wfrag = itf != x->frag_of().end() ? itf->second : nullptr; }   // conv3x3_regw.hip
+            c.Wfrag = Wt.frag[t].p;   // conv3x3_regw.hip
             const bool want_xout_lp = pro && pro->xout && pro->xout_lp_ok;
             if (shortcut) {       // the block's 1x1 res_conv rides on the centre tap of this conv
-                c.res_w = x->lp_of().at(shortcut->wr); c.res_lo_off = x->lo_off(c.res_w); c.res_b = shortcut->br; c.res_y = shortcut_out;
-                { auto itf = x->frag_of().find(shortcut->wr); c.res_wfrag = itf != x->frag_of().end() ? itf->second : nullptr; }
+                c.res_w = shortcut->wr.nk[t].p; c.res_lo_off = shortcut->wr.nk[t].lo_off; c.res_b = shortcut->br; c.res_y = shortcut_out;
+                c.res_wfrag = shortcut->wr.frag[t].p;
             }
             if (want_xout_lp && (c.pro_res || c.res2_w) && conv3x3_strip_form(c)) { c.xout_lp = 1; pro->xout_lp = true; }
             const double M = (double)H * W * P.d.B;
@@ -1011,15 +995,15 @@ struct Runner {
         gnfix_t* st1 = nullptr;
         // h1 / h2 of this block as bf16: conv2 must be the GroupNorm-prologue conv that can read bf16, conv1 a kernel that can
         // write it; h2 additionally needs a fused consumer (the next block's first conv or the attention's context pass)
-        const bool conv2_fast = fast_conv(w.cout, w.cout) && conv3x3_bf16_xb_supported(w.cout, w.cout) && x->lp_of().count(w.w2);
-        const bool conv1_fast = first_layer || (head ? true : (fast_conv(X.C, w.cout) && x->lp_of().count(w.w1)));
+        const bool conv2_fast = fast_conv(w.cout, w.cout) && conv3x3_bf16_xb_supported(w.cout, w.cout);
+        const bool conv1_fast = first_layer || (head ? true : fast_conv(X.C, w.cout));
         const bool h1b = h_bf16() && conv2_fast && conv1_fast;
         const bool h2b = h_bf16() && conv2_fast && (ctail || tail);
         if (first_layer) {
             FirstConvP f{};
             f.h1_bf16 = h1b ? x->lp_kind() : 0;
             f.mu = mu; f.x = xcur; f.spk = P.spk_plane; f.mask = mask; f.B = P.d.B; f.H = s.H; f.T = s.W; f.planes = w.cin; f.C = w.cout;
-            f.W3 = w.w1; f.b3 = w.b1; f.W1 = w.wr; f.b1 = w.br; f.scal = P.scal; f.scal_stride = SCAL_STRIDE; f.step = sp;
+            f.W3 = w.w1.f32; f.b3 = w.b1; f.W1 = w.wr.f32; f.b1 = w.br; f.scal = P.scal; f.scal_stride = SCAL_STRIDE; f.step = sp;
             f.h1 = s.h1; f.res = s.rbuf;
             // the 1x1 shortcut of this block is two or three FMAs per value from the input planes: when the consumer is the next
             // block's fused-tail convolution it recomputes it, and the fp32 [B,H,T,64] tensor is neither written nor read
@@ -1039,7 +1023,7 @@ struct Runner {
                 head->xout_lp_ok = tail != nullptr && !w.wr && lp_inter_cur && head->xout == X.p && X.coff == 0 && X.ld == X.C && !knob_off("DEX_RES_X_LP");
                 conv3x3("conv3x3", H2, s.H, s.W, s.mask_ws, true, w.w1, w.b1, w.cout, s.h1, st1, head, nullptr, nullptr, head->x_bf16, h1b);
             } else {
-                fused_res = w.wr && fast_conv(X.C, w.cout) && conv3x3_bf16_res_supported(X.C, w.cout) && x->lp_of().count(w.wr);
+                fused_res = w.wr && fast_conv(X.C, w.cout) && conv3x3_bf16_res_supported(X.C, w.cout);
                 conv3x3("conv3x3", X, s.H, s.W, s.mask_ws, true, w.w1, w.b1, w.cout, s.h1, st1, nullptr, fused_res ? &w : nullptr, s.rbuf, false, h1b);
             }
             if (fused_res) {
@@ -1096,7 +1080,7 @@ struct Runner {
         const int s2c = c.dit_stride * c.dit_stride * mid;
         IGemmP fl = base_gemm(fuse_lnf ? P.tok : P.xn, hid, 0, P.Hf, P.Wt, hid, x->fl_w, s2c, x->fl_b, out, ldo, ocoff);
         if (fuse_lnf) { fl.ln_shift = P.fin_mod; fl.ln_scale = P.fin_mod + hid; fl.ln_step_stride = 2L * hid; }
-        { auto it = x->frag_of().find(x->fl_w); fl.Wfrag = (it != x->frag_of().end()) ? it->second : nullptr; }
+        fl.Wfrag = x->fl_w.frag[x->lpi()].p;
         fl.unpatch_s = c.dit_stride; fl.unpatch_C = mid; fl.OHf = P.Hm; fl.OWf = P.Wm;
         fl.c_bstride = (long)P.Hm * P.Wm * ldo;
         fl.outmask = mask; fl.outmask_ws = mask_ws;
@@ -1135,8 +1119,8 @@ struct Runner {
             const int nblk = (int)((npix + 128L * nsub - 1) / (128L * nsub));
             LinKvCtxP k{};
             if (tail) k = *tail;
-            k.X = X.p; k.ldx = X.ld; k.x_coff = X.coff; k.xb = npix * X.ld; k.npix = (int)npix; k.C = X.C; k.Wkv = w.wkv_lp[x->lpi()];
-            k.wkv_lo_off = x->lpi() == 2 ? 384L * X.C : 0;          // (the q | k | v rows were converted as one array: Packer::linattn)
+            k.X = X.p; k.ldx = X.ld; k.x_coff = X.coff; k.xb = npix * X.ld; k.npix = (int)npix; k.C = X.C; k.Wkv = w.wkv[x->lpi()].p;
+            k.wkv_lo_off = w.wkv[x->lpi()].lo_off;
             k.nsub = nsub; k.nblk = nblk; k.part_m = s.pm; k.part_s = s.ps; k.part_c = s.pc; k.B = B;
             // the head-parallel form of the context pass (16 waves, one head each) while the grid fits in one round of the chip's CUs - the
             // latency regime (B = 1..3); the batch forms keep the 4-wave one.  DEX_LINATTN_HEADWAVES: 0 = never, 1 = always.
@@ -1150,9 +1134,9 @@ struct Runner {
             run("linattn_kvctx", 2.0 * npix * B * (256.0 * X.C + 128 * 32), (tail ? (tail->h2_bf16 ? 10.0 : 12.0) - (xlp ? 2.0 : 0.0) : 4.0) * npix * X.C * B, [&] { launch_linattn_kvctx(k, x->precision, st); });
             LinMergeP mg{s.pm, s.ps, s.pc, nblk, w.wout_raw, w.g, X.C, s.mbf, B};
             run("linattn_merge", 2.0 * 128 * 32 * X.C * B, 4.0 * nblk * 4 * 1088 * B, [&] { launch_linattn_merge(mg, x->precision, st); });
-            LinOut2P o{X.p, X.ld, X.coff, npix * X.ld, (int)npix, X.C, w.wq_frag[x->lpi()], s.mbf, w.bias_eff, out, ldo, ocoff, npix * ldo, B, out_lp ? 1 : 0,
+            LinOut2P o{X.p, X.ld, X.coff, npix * X.ld, (int)npix, X.C, w.wq_frag[x->lpi()].p, s.mbf, w.bias_eff, out, ldo, ocoff, npix * ldo, B, out_lp ? 1 : 0,
                        out2_lp, ldo2, ocoff2, npix * ldo2, xlp ? 1 : 0};
-            o.wq_lo_off = x->lpi() == 2 ? 128L * X.C : 0;
+            o.wq_lo_off = w.wq_frag[x->lpi()].lo_off;
             // the wave-split tail (4 waves per 32-pixel slot) wherever the direct form would run - the latency regime, B = 1..3 at 40x256;
             // the throughput form keeps the larger grids (and every 16-bit x / y).  DEX_LINATTN_OUT2_HW: 0 = never, 1 = wherever x and y are fp32.
             o.hw = knob_or("DEX_LINATTN_OUT2_HW", linattn_out2_lp_out_supported((int)npix, B) ? 0 : 1) != 0 ? 1 : 0;
@@ -1180,11 +1164,10 @@ struct Runner {
         dw.k = c.dit_patch; dw.s = c.dit_stride; dw.pad = c.dit_patch / 2; dw.Wd = x->pe_dw; dw.bd = x->pe_db;
         dw.mask = mask_input ? mask : nullptr; dw.mask_ws = mask_ws; dw.mask_bstride = P.d.T;
         dw.Y = P.pe0; dw.Hf = P.Hf; dw.Wt = P.Wt; dw.B = B; dw.aff = in_aff;
-        auto pw_lp = x->lp_of().find(x->pe_pw);
         if (patch_fused()) {
             // small grids: depthwise conv + SiLU + pointwise GEMM in ONE launch (bit-identical to the two-kernel form below)
             run("patch_embed", 2.0 * B * N * mid * (c.dit_patch * c.dit_patch + hid), 4.0 * B * (P.Hm * P.Wm * mid + N * hid),
-                [&] { launch_patch_embed_fused(dw, pw_lp->second, x->pe_pb, P.emb, hid, x->precision, st); });
+                [&] { launch_patch_embed_fused(dw, x->pe_pw.nk[x->lpi()].p, x->pe_pb, P.emb, hid, x->precision, st); });
         } else {
             run("patch_dwconv_silu", 2.0 * B * N * mid * c.dit_patch * c.dit_patch, 4.0 * B * (P.Hm * P.Wm + N) * mid, [&] { launch_dwconv_silu(dw, st); });
             IGemmP pe = base_gemm(P.pe0, mid, 0, P.Hf, P.Wt, mid, x->pe_pw, hid, x->pe_pb, P.emb, hid, 0);
@@ -1193,8 +1176,8 @@ struct Runner {
         // grouped 16x16 pos-conv, split-K partials (bias added in the tail)
         const int G = c.dit_conv_pos_groups, kp = c.dit_conv_pos, cg = hid / G;
         int nsplit = POS_SPLIT, pcg = 0, pcgp = 0;
-        if (x->lp() && x->pos_wfrag[x->lpi()]) {
-            PosConvP pcd{P.emb, x->pos_wfrag[x->lpi()], P.pos_part, P.Hf, P.Wt, hid, G, B};
+        if (x->lp() && x->pos_w.frag[x->lpi()].p) {
+            PosConvP pcd{P.emb, x->pos_w.frag[x->lpi()].p, P.pos_part, P.Hf, P.Wt, hid, G, B};
             run("pos_conv", 2.0 * B * N * (double)kp * kp * cg * hid, 8.0 * B * N * hid + 2.0 * kp * kp * cg * hid, [&] { launch_pos_conv_direct(pcd, x->precision, st); });
             nsplit = 1;
         } else {
@@ -1207,7 +1190,6 @@ struct Runner {
             IGemmP pc = base_gemm(src, G * cgp, 0, P.Hf, P.Wt, cgp, x->pos_w, cgp, nullptr, P.pos_part, G * cgp, 0);
             pc.KH = kp; pc.KW = kp; pc.off_h = -(kp / 2); pc.off_w = -(kp / 2); pc.K = kp * kp * cgp;
             pc.groups = G; pc.w_gstride = (long)kp * kp * cgp * cgp; pc.ksplit = POS_SPLIT; pc.c_sstride = (long)B * N * G * cgp;
-            if (cgp != cg) pc.Wbf = nullptr;
             gemm("pos_conv", pc);
             pcg = cgp != cg ? cg : 0; pcgp = cgp;
         }
@@ -1216,7 +1198,7 @@ struct Runner {
         if (debug) hipMemcpyAsync(P.dbg_tok, P.tok, (size_t)B * N * hid * 4, hipMemcpyDeviceToDevice, st);
         tap("tok_in", P.dbg_tok, (long)B * N, hid, hid);
         const float scale = 1.0f / sqrtf((float)(hid / c.dit_heads));
-        const bool chain = x->lp() && dit_rowchain_supported(hid, mh) && c.dit_heads == 2 && x->frag_of().count(x->blocks[0].wproj) &&
+        const bool chain = x->lp() && dit_rowchain_supported(hid, mh) && c.dit_heads == 2 &&
                            !knob_off("DEX_DIT_CHAIN");          // 0: one GEMM / attention launch per operation (A/B runs)
         for (int k = 0; k < c.dit_depth; ++k) {
             const DitBlockW& w = x->blocks[k];
@@ -1240,7 +1222,7 @@ struct Runner {
                 }
             }
             if (chain && k == 0) {                                   // first block: LN + modulate + qkv only
-                ch.qkv_only = 1; ch.Wq = x->frag_of().at(w.wqkv); ch.bq = w.bqkv;
+                ch.qkv_only = 1; ch.Wq = w.wqkv.frag[x->lpi()].p; ch.bq = w.bqkv;
                 ch.Qh = P.qh; ch.Kh = P.kh; ch.Vt = P.vt;        // block 0 reads set 0
                 ch.next_shift = ada; ch.next_scale = ada + hid; ch.next_step_stride = 6L * hid;
                 run("dit_qkv", 2.0 * B * N * 3.0 * hid * hid, 4.0 * B * N * hid + 2.0 * B * N * 3 * hid, [&] { launch_dit_rowchain(ch, x->precision, st); });
@@ -1310,11 +1292,11 @@ struct Runner {
                 ch.attn_inline = separate ? 0 : 1; ch.o_lp = o_lp ? 1 : 0; ch.tail_row0 = tail_row0; ch.tail_ks = tail_ks;
                 const bool last = k + 1 == c.dit_depth;
                 ch.O = P.ao; ch.ksplit = ks; ch.o_sstride = (long)B * N * hid; ch.ml = P.att_ml;
-                ch.Wp = x->frag_of().at(w.wproj); ch.W1 = x->frag_of().at(w.wfc1); ch.W2 = x->frag_of().at(w.wfc2);
+                ch.Wp = w.wproj.frag[x->lpi()].p; ch.W1 = w.wfc1.frag[x->lpi()].p; ch.W2 = w.wfc2.frag[x->lpi()].p;
                 ch.bp = w.bproj; ch.b1 = w.bfc1; ch.b2 = w.bfc2;
                 if (!last) {
                     const DitBlockW& wn = x->blocks[k + 1];
-                    ch.Wq = x->frag_of().at(wn.wqkv); ch.bq = wn.bqkv;
+                    ch.Wq = wn.wqkv.frag[x->lpi()].p; ch.bq = wn.bqkv;
                     ch.next_shift = P.ada[k + 1]; ch.next_scale = P.ada[k + 1] + hid; ch.next_step_stride = 6L * hid;
                 }
                 const double M = (double)B * N;
@@ -1372,7 +1354,7 @@ struct Runner {
     // PatchEmbed2D runs as one launch (patch_embed.hip; small grids)
     bool patch_fused() const {
         const DexConfig& c = x->cfg;
-        return x->lp() && !debug && !knob_off("DEX_PATCH_FUSED") && x->lp_of().count(x->pe_pw) &&
+        return x->lp() && !debug && !knob_off("DEX_PATCH_FUSED") &&
                patch_embed_fused_supported(c.dit_patch, mid_dim(c), c.dit_hidden, (long)P.d.B * P.N);
     }
     // The TIV adaptor's y = IN2d(x) * s + m (ref_encoder.py:271) has ONE consumer, the patch embedding's depthwise convolution: outside
@@ -1381,7 +1363,7 @@ struct Runner {
     bool tiv_fold() const { return !debug && P.tiv_aff && knob_or("DEX_TIV_FOLD", 1) != 0; }
     // the TV adaptor runs as one launch (attention_bf16.hip tv_chain_kernel)
     bool tv_chain_on() const {
-        return x->lp() && x->lp_of().count(x->tv_wl) && P.tv_kp && tv_chain_form(P.Hm * P.Wm, mid_dim(x->cfg), P.d.B);
+        return x->lp() && x->tv_wl.nk[x->lpi()].p && P.tv_kp && tv_chain_form(P.Hm * P.Wm, mid_dim(x->cfg), P.d.B);
     }
     // ... in its folded form (w_q and `linear` inside the style operands: kernels.h TvFold2P).  bf16 / fp16 modes: the split-weight mode would need K' and
     // V' as hi + lo pairs, i.e. twice the MFMAs of the key tiles that bound the kernel - it keeps the projections (DEX_TV_FOLD=0: every mode does)
@@ -1427,9 +1409,9 @@ struct Runner {
         // ONE launch per 128 pixels (attention_bf16.hip tv_chain_kernel; DEX_TV_CHAIN=0: the three launches below).  q and the
         // attention output never reach HBM; the style keys / values become 16-bit operands once per call (prepare()), the time token's row per step.
         if (chain) {
-            const void* wl = x->lp_of().at(x->tv_wl);
+            const LpView& wl = x->tv_wl.nk[x->lpi()];
             TvChainP tc{X.p, X.ld, X.coff, npix * X.ld, (int)npix, P.Wm, mask, mask_ws, (long)P.d.T,
-                        P.tv_wbf, fo.split ? (long)B * mid * mid : 0L, P.tv_beff, wl, x->lo_off(wl),
+                        P.tv_wbf, fo.split ? (long)B * mid * mid : 0L, P.tv_beff, wl.p, wl.lo_off,
                         P.tv_kp, P.tv_vtp, P.tv_nkpad, P.d.Ts + 1, args->sty_lengths_dev, 1, 1.0f / sqrtf((float)mid),
                         P.tv_out, P.tiv_stats, B};
             run("tv_chain", 4.0 * B * (double)npix * mid * mid + 4.0 * B * (double)npix * (P.d.Ts + 1) * mid, 8.0 * B * npix * mid,
@@ -1445,7 +1427,7 @@ struct Runner {
         a.scale = 1.0f / sqrtf((float)mid); a.B = B; a.head_dim = mid;
         // the attention output has one reader, the output projection below, which rounds it to the operand type: at batch size it is
         // stored in that type (same bits, half the bytes of one 84 MB tensor written and read per Euler step at B = 32)
-        const bool ao_lp = lp_inter_cur && mid == 128 && x->lp_of().count(x->tv_wl) && attention_lp_shared_form((int)npix, 1, B, 1);
+        const bool ao_lp = lp_inter_cur && mid == 128 && x->tv_wl.nk[x->lpi()].p && attention_lp_shared_form((int)npix, 1, B, 1);
         a.o_lp = ao_lp ? 1 : 0;
         run("tv_attention", 4.0 * B * (double)npix * (P.d.Ts + 1) * mid, (ao_lp ? 2.0 : 4.0) * B * npix * mid + 4.0 * B * (npix + 2 * (P.d.Ts + 1)) * mid, [&] { launch_attention(a, x->precision, st); });
         IGemmP o = base_gemm(P.tv_ao, mid, 0, P.Hm, P.Wm, mid, x->tv_wl, mid, nullptr, P.tv_out, mid, 0);
@@ -1489,8 +1471,8 @@ struct Runner {
             const StageBuf& sm_ = P.down[ns - 1];
             const ResW& uw = x->up_res[0][0];
             const bool tail_ok = linattn_fused(sm_.C) && linattn_out2_lp_out_supported((int)sm_.npix, B);
-            const bool conv_ok = uw.wr && fast_conv(2 * sm_.C, uw.cout) && conv3x3_bf16_res_supported(2 * sm_.C, uw.cout) && x->lp_of().count(uw.wr) &&
-                                 x->lp_of().count(uw.w1) && conv3x3_cat_lp_in_supported(P.up[0].H, P.up[0].W, B, 2 * sm_.C, uw.cout);
+            const bool conv_ok = uw.wr && fast_conv(2 * sm_.C, uw.cout) && conv3x3_bf16_res_supported(2 * sm_.C, uw.cout) &&
+                                 conv3x3_cat_lp_in_supported(P.up[0].H, P.up[0].W, B, 2 * sm_.C, uw.cout);
             IGemmP fl = final_gemm(sm_.mask_ws, P.cat[0], 2 * sm_.C, 0);
             fl.c_lp = x->lp_kind();
             cat_lp = !knob_off("DEX_CAT_LP") && tail_ok && conv_ok && fl.Wbf && igemm_nwalk_form(fl);
@@ -1502,7 +1484,7 @@ struct Runner {
             // fused form (bf16 mode, 64/128 channels, block 0 has a res_conv)
             Pro t0{};
             const bool defer0 = x->lp() && conv3x3_bf16_tail_supported(s.C) && fast_conv(s.C, s.C) &&
-                                (i == 0 || x->down_res[i][0].wr != nullptr);
+                                (i == 0 || x->down_res[i][0].wr);
             resblock(x->down_res[i][0], s, cur, P.tadd_down[2 * i], s.r0out, i == 0, nullptr, nullptr, defer0 ? &t0 : nullptr);
             TD r0{s.r0out, s.C, 0, s.C};
             LinKvCtxP tail{};
@@ -1515,7 +1497,7 @@ struct Runner {
             }
             // the Downsample conv is this output's only reader at level 0 (the reference's hiddens.append of this level is never
             // popped; deeper levels live in the up path's concatenation buffer, which is read as fp32)
-            const bool t1_lp = lp_inter && i == 0 && i < ns - 1 && linattn_fused(s.C) && linattn_out2_lp_out_supported((int)s.npix, B) && x->lp_of().count(x->down_ds_w[i]);
+            const bool t1_lp = lp_inter && i == 0 && i < ns - 1 && linattn_fused(s.C) && linattn_out2_lp_out_supported((int)s.npix, B);
             const bool skip16 = cat_lp && i == ns - 1;          // the mid stage's output is also the skip half of the up path's concatenation buffer
             linattn(x->down_lin[i], s, r1, s.attn_out, s.attn_ld, s.attn_coff, defer ? &tail : nullptr, t1_lp,
                     skip16 ? P.cat16 : nullptr, s.attn_ld, s.attn_coff);
@@ -1529,14 +1511,14 @@ struct Runner {
                 g.inmask = mask; g.inmask_ws = s.mask_ws;
                 // its output feeds the next stage's first ResnetBlock (3x3 conv + fused 1x1 shortcut) and nothing else
                 const ResW& nw = x->down_res[i + 1][0];
-                const bool t2_lp = lp_inter && x->lp_of().count(x->down_ds_w[i]) && nw.wr && fast_conv(s.C, nw.cout) && conv3x3_bf16_res_supported(s.C, nw.cout) &&
-                                   x->lp_of().count(nw.wr) && x->lp_of().count(nw.w1) && conv3x3_plain_lp_in_supported(g.Ho, g.Wo, B, s.C, nw.cout);
+                const bool t2_lp = lp_inter && nw.wr && fast_conv(s.C, nw.cout) && conv3x3_bf16_res_supported(s.C, nw.cout) &&
+                                   conv3x3_plain_lp_in_supported(g.Ho, g.Wo, B, s.C, nw.cout);
                 g.a_lp = t1_lp ? lpk : 0; g.c_lp = t2_lp ? lpk : 0;
                 const bool strip_off = knob_off("DEX_CONV_DOWN");
-                if (x->lp() && !strip_off && x->frag_of().count(x->down_ds_w[i]) && conv_down_supported(s.C, s.H, s.W, a.ld, s.C, a.coff)) {
+                if (x->lp() && !strip_off && x->down_ds_w[i].frag[x->lpi()].p && conv_down_supported(s.C, s.H, s.W, a.ld, s.C, a.coff)) {
                     ConvDownP d{};
                     d.X = a.p; d.a_lp = g.a_lp; d.ldx = a.ld; d.xb = (long)s.H * s.W * a.ld; d.x_coff = a.coff; d.H = s.H; d.W = s.W;
-                    d.Wfrag = x->frag_of().at(x->down_ds_w[i]); d.bias = x->down_ds_b[i];
+                    d.Wfrag = x->down_ds_w[i].frag[x->lpi()].p; d.bias = x->down_ds_b[i];
                     d.Y = s.ds_out; d.c_lp = g.c_lp; d.ldy = s.C; d.y_coff = 0;
                     d.inmask = mask; d.inmask_ws = s.mask_ws; d.mask_bstride = P.d.T; d.B = B;
                     const double M = 0.25 * s.H * s.W * B;
@@ -1567,7 +1549,7 @@ struct Runner {
             if (cat_lp && j == 0) X = TD{reinterpret_cast<float*>(P.cat16), 2 * stage_dim(c, i), 0, 2 * stage_dim(c, i), lpk};
             Pro t0{};
             const bool defer0 = x->lp() && conv3x3_bf16_tail_supported(s.C) && fast_conv(s.C, s.C) &&
-                                x->up_res[j][0].wr != nullptr;
+                                x->up_res[j][0].wr;
             resblock(x->up_res[j][0], s, X, P.tadd_up[2 * j], s.r0out, false, nullptr, nullptr, defer0 ? &t0 : nullptr);
             TD r0{s.r0out, s.C, 0, s.C};
             LinKvCtxP tail{};
@@ -1578,7 +1560,7 @@ struct Runner {
                 char n0[24], n1[24]; snprintf(n0, sizeof n0, "ups.%d.0", j); snprintf(n1, sizeof n1, "ups.%d.1", j);
                 tap(n0, s.r0out, B * s.npix, s.C, s.C); tap(n1, s.r1out, B * s.npix, s.C, s.C);
             }
-            const bool t5_lp = lp_inter && linattn_fused(s.C) && linattn_out2_lp_out_supported((int)s.npix, B) && x->lp_of().count(x->up_us_w[j]);
+            const bool t5_lp = lp_inter && linattn_fused(s.C) && linattn_out2_lp_out_supported((int)s.npix, B);
             linattn(x->up_lin[j], s, r1, s.attn_out, s.C, 0, defer ? &tail : nullptr, t5_lp);
             char nm[16]; snprintf(nm, sizeof nm, "up%d", j);
             tap(nm, s.attn_out, B * s.npix, s.C, s.C);
@@ -1586,19 +1568,19 @@ struct Runner {
             float* dst; int ldd;
             if (j < ns - 2) { dst = P.cat[j + 1]; ldd = 2 * stage_dim(c, i - 1); } else { dst = P.up_out; ldd = s.C; }
             {
-                IGemmP g = base_gemm(s.attn_out, s.C, 0, s.H, s.W, s.C, x->up_us_w[j], s.C, x->up_us_b[j], dst, ldd, 0);
+                IGemmP g = base_gemm(s.attn_out, s.C, 0, s.H, s.W, s.C, x->up_us_w[j][0], s.C, x->up_us_b[j], dst, ldd, 0);      // (parity 0's handle: the GEMM walks the group of four)
                 g.KH = 2; g.KW = 2; g.step_h = -1; g.step_w = -1; g.K = 4 * s.C; g.parity = 1;
                 g.OHf = 2 * s.H; g.OWf = 2 * s.W; g.osh = 2; g.osw = 2;
                 g.c_bstride = 4L * s.H * s.W * ldd;
                 g.inmask = mask; g.inmask_ws = s.mask_ws;
                 g.a_lp = t5_lp ? lpk : 0;
-                up_out_lp = lp_inter && j == ns - 2 && x->lp_of().count(x->up_us_w[j]) && x->lp_of().count(x->fin_w) && conv3x3_res2_form(80, P.d.T, B);
+                up_out_lp = lp_inter && j == ns - 2 && conv3x3_res2_form(80, P.d.T, B);
                 g.c_lp = up_out_lp ? lpk : 0;
                 const bool strip_off = knob_off("DEX_CONVT_UP");
-                if (x->lp() && x->frag_of().count(x->up_us_w[j]) && !strip_off && convt_up_supported(s.C, s.H, s.W, s.C, ldd)) {
+                if (x->lp() && x->up_us_w[j][0].frag[x->lpi()].p && !strip_off && convt_up_supported(s.C, s.H, s.W, s.C, ldd)) {
                     ConvTUpP u{};
                     u.X = s.attn_out; u.a_lp = g.a_lp; u.ldx = s.C; u.xb = (long)s.H * s.W * s.C; u.x_coff = 0; u.H = s.H; u.W = s.W;
-                    for (int par = 0; par < 4; ++par) u.Wfrag[par] = x->frag_of().at(x->up_us_w[j] + (long)par * 4 * s.C * s.C);
+                    for (int par = 0; par < 4; ++par) u.Wfrag[par] = x->up_us_w[j][par].frag[x->lpi()].p;
                     u.bias = x->up_us_b[j];
                     u.Y = dst; u.c_lp = g.c_lp; u.ldy = ldd; u.y_coff = 0;
                     u.inmask = mask; u.inmask_ws = s.mask_ws; u.mask_bstride = P.d.T; u.B = B;
@@ -1611,7 +1593,7 @@ struct Runner {
         tap("up_out", P.up_out, (long)B * 80 * P.d.T, c.dim, c.dim);
         TD U{P.up_out, c.dim, 0, c.dim, up_out_lp ? lpk : 0};
         gnfix_t* stf = next_stats();
-        const bool hfb = h_bf16() && fast_conv(c.dim, c.dim) && x->lp_of().count(x->fin_w);
+        const bool hfb = h_bf16() && fast_conv(c.dim, c.dim);
         conv3x3("conv3x3", U, 80, P.d.T, 1, true, x->fin_w, x->fin_b, c.dim, P.hF, stf, nullptr, nullptr, nullptr, false, hfb);
         FinalGP f{};
         f.x_bf16 = hfb ? x->lp_kind() : 0;
@@ -1688,12 +1670,12 @@ struct Runner {
             if (tv_fold_on()) {        // folded form: G = K W_q and V' = V W_l^T in fp32 (style rows once per call, the time token's rows of every step), V'^T as the 16-bit operand
                 const long kvb = (long)(args->Ts + 1) * mid;
                 for (int which = 0; which < 2; ++which) {
-                    IGemmP g = base_gemm((which ? P.tv_V : P.tv_K) + mid, mid, 0, 1, args->Ts, mid, which ? x->tv_wl : x->tv_wq_raw, mid, nullptr,
-                                         (which ? P.tv_Vp : P.tv_G) + mid, mid, 0);       // w_q raw [n][k] IS the packed [K = n][N = k] matrix of K W_q
-                    g.a_bstride = kvb; g.c_bstride = kvb; g.Wbf = nullptr;
+                    IGemmP g = base_gemm((which ? P.tv_V : P.tv_K) + mid, mid, 0, 1, args->Ts, mid, which ? x->tv_wl.f32 : x->tv_wq_raw, mid, nullptr,
+                                         (which ? P.tv_Vp : P.tv_G) + mid, mid, 0);       // w_q raw [n][k] IS the packed [K = n][N = k] matrix of K W_q; the fp32 packs alone: no 16-bit operand
+                    g.a_bstride = kvb; g.c_bstride = kvb;
                     gemm("tv_fold_kv", g);
-                    IGemmP t = base_gemm(which ? P.tv_v0 : P.tv_k0, mid, 0, 1, n, mid, which ? x->tv_wl : x->tv_wq_raw, mid, nullptr, which ? P.tv_v0p : P.tv_g0, mid, 0);
-                    t.B = 1; t.Wbf = nullptr;
+                    IGemmP t = base_gemm(which ? P.tv_v0 : P.tv_k0, mid, 0, 1, n, mid, which ? x->tv_wl.f32 : x->tv_wq_raw, mid, nullptr, which ? P.tv_v0p : P.tv_g0, mid, 0);
+                    t.B = 1;
                     gemm("tv_fold_time_rows", t);
                 }
                 TvKvPrepP kp{P.tv_G, P.tv_Vp, kvb, args->Ts + 1, P.tv_nkpad, P.tv_kp, P.tv_vtp, B};      // (K' is written by every step's launch_tv_fold2)

@@ -29,9 +29,9 @@
 using namespace dex;
 
 namespace {
-// (wlp: the same matrix as bf16 [0] / fp16 [1], [N][K] with K contiguous - the reduced-precision GEMM's weight operand)
-struct VConv { const float* w = nullptr; const float* b = nullptr; int cin, cout, k, dil; const void* wlp[2] = {nullptr, nullptr}; bool narrow = false; };  // packed [k*cin][cout]
-struct VUp { const float* w = nullptr; const float* b = nullptr; int cin, cout, k, u, pad; const void* wlp[2] = {nullptr, nullptr}; bool narrow = false; };   // packed [cin][k*cout]
+// (w.nk: the same matrix as bf16 [0] / fp16 [1], [N][K] with K contiguous - the reduced-precision GEMM's weight operand; the vocoder has no split-weight mode)
+struct VConv { PackedW w; const float* b = nullptr; int cin, cout, k, dil; bool narrow = false; };  // packed [k*cin][cout]
+struct VUp { PackedW w; const float* b = nullptr; int cin, cout, k, u, pad; bool narrow = false; };   // packed [cin][k*cout]
 constexpr int MEL_LD = 96;          // num_mels padded to a multiple of 32 (K tiles of the implicit GEMM do not straddle taps)
 }  // namespace
 
@@ -125,11 +125,11 @@ int dex_voc_finalize(DexVoc* v, dex_stream_t stream) {
     hipStream_t st = (hipStream_t)stream;
     const DexVocoderConfig& c = v->cfg;
     // reduced-precision copies of a packed fp32 [K][N] matrix: bf16 and fp16, [N][K]
-    auto lp_copies = [&](const float* w, int K, int N, const void* (&out)[2]) {
+    auto lp_copies = [&](PackedW& w, int K, int N) {
         for (int t = 0; t < 2; ++t) {
             void* d = v->alloc(((long)K * N + 1) / 2);
-            if (d) launch_pack_lp_nk(w, d, K, N, t ? DEX_PREC_FP16 : DEX_PREC_BF16, st);
-            out[t] = d;
+            if (d) launch_pack_lp_nk(w.f32, d, K, N, t ? DEX_PREC_FP16 : DEX_PREC_BF16, st);
+            w.nk[t].p = d;
         }
     };
     // Conv1d [Cout][Cin][k] -> [(tap*Cin_pad + ci)][Cout]
@@ -137,7 +137,7 @@ int dex_voc_finalize(DexVoc* v, dex_stream_t stream) {
         VConv o{}; o.cin = cin_pad; o.cout = cout; o.k = k; o.dil = dil; o.narrow = voc_narrow_width(cout);
         o.w = conv1d_operand(*v, v->R(name + ".weight"), cin, cout, k, cin_pad, st);
         o.b = v->R(name + ".bias");
-        if (o.w && !o.narrow) lp_copies(o.w, k * cin_pad, cout, o.wlp);      // (the narrow kernels read fp32 weights in every mode)
+        if (o.w && !o.narrow) lp_copies(o.w, k * cin_pad, cout);      // (the narrow kernels read fp32 weights in every mode)
         return o;
     };
     v->pre = conv("conv_pre", c.num_mels, c.upsample_initial_channel, 7, 1, MEL_LD);
@@ -149,7 +149,7 @@ int dex_voc_finalize(DexVoc* v, dex_stream_t stream) {
         const std::string upn = "ups." + std::to_string(i) + (v->big() ? ".0" : "");
         if (d) launch_permute4(v->R(upn + ".weight"), d, ci, co, k, 1, 0, 2, 1, 3, st);   // [ci][co][k] -> [ci][k][co]
         up.w = d; up.b = v->R(upn + ".bias");
-        if (d && !up.narrow) lp_copies(d, ci, k * co, up.wlp);
+        if (d && !up.narrow) lp_copies(up.w, ci, k * co);
         v->ups.push_back(up);
         for (int j = 0; j < 3; ++j) {
             const std::string p = "resblocks." + std::to_string(i * 3 + j);
@@ -220,14 +220,17 @@ void voc_plan(const DexVoc* v, int B, int T, void* ws, VPlan& P) {
     P.y = take(ymax);
     P.bytes = (off + 255) & ~size_t(255);
 }
-thread_local int g_voc_lp = -1;        // -1: fp32 operands; 0 / 1: bf16 / fp16 weight copies (set by dex_vocode for the duration of its enqueue)
-IGemmP conv1d(const float* X, int L, int B, const VConv& c, float slope, float* out, const float* res) {
+// the weight operands of a GEMM in mode `prec`: the fp32 pack, and in the bf16 / fp16 modes its 16-bit copy
+void voc_weight(IGemmP& g, const PackedW& w, int prec) {
+    g.W = w.f32; g.Wbf = prec == DEX_PREC_BF16 ? w.nk[0].p : prec == DEX_PREC_FP16 ? w.nk[1].p : nullptr;
+}
+IGemmP conv1d(const float* X, int L, int B, const VConv& c, float slope, float* out, const float* res, int prec) {
     IGemmP g{};
     g.A = X; g.lda = c.cin; g.a_bstride = (long)L * c.cin; g.a_coff = 0;
     g.Hi = 1; g.Wi = L; g.Cin = c.cin;
     g.KH = 1; g.KW = c.k; g.sh = 1; g.sw = 1; g.off_h = 0; g.off_w = -c.dil * (c.k - 1) / 2; g.step_h = 1; g.step_w = c.dil;
     g.Ho = 1; g.Wo = L;
-    g.W = c.w; g.Wbf = g_voc_lp >= 0 ? c.wlp[g_voc_lp] : nullptr; g.N = c.cout; g.K = c.k * c.cin; g.ksplit = 1; g.groups = 1;
+    voc_weight(g, c.w, prec); g.N = c.cout; g.K = c.k * c.cin; g.ksplit = 1; g.groups = 1;
     g.bias = c.b;
     g.C = out; g.ldc = c.cout; g.c_bstride = (long)L * c.cout; g.c_coff = 0;
     g.OHf = 1; g.OWf = L; g.osh = 1; g.osw = 1;
@@ -240,10 +243,10 @@ IGemmP conv1d(const float* X, int L, int B, const VConv& c, float slope, float* 
 // one ResBlock conv: the implicit GEMM, or the direct kernel at a narrow width
 void voc_conv(const float* X, int L, int B, const VConv& c, float slope, float* out, const float* res, int prec, hipStream_t st) {
     if (c.narrow) {
-        NarrowConvP n{X, c.w, c.b, res, out, L, c.cout, c.k, c.dil, B, slope};
+        NarrowConvP n{X, c.w.f32, c.b, res, out, L, c.cout, c.k, c.dil, B, slope};
         launch_narrow_conv1d(n, st);
     } else {
-        launch_igemm(conv1d(X, L, B, c, slope, out, res), prec, st);
+        launch_igemm(conv1d(X, L, B, c, slope, out, res, prec), prec, st);
     }
 }
 void voc_aa_snake(const AaSnakeP& s, hipStream_t st) {
@@ -270,20 +273,19 @@ int dex_vocode(DexVoc* v, const float* mel_dev, int B, int T, float* wav_dev, vo
     hipStream_t st = (hipStream_t)stream;
     const DexVocoderConfig& c = v->cfg;
     const int prec = v->precision;
-    g_voc_lp = prec == DEX_PREC_BF16 ? 0 : prec == DEX_PREC_FP16 ? 1 : -1;
     launch_mel_to_cl(mel_dev, P.mel, B, c.num_mels, T, MEL_LD, st);
-    launch_igemm(conv1d(P.mel, T, B, v->pre, 0.f, P.x, nullptr), prec, st);                  // conv_pre
+    launch_igemm(conv1d(P.mel, T, B, v->pre, 0.f, P.x, nullptr, prec), prec, st);                  // conv_pre
     long L = T;
     for (int i = 0; i < c.n_upsamples; ++i) {
         const VUp& up = v->ups[i];
         if (up.narrow) {     // ConvTranspose1d into a narrow stage: one direct kernel
-            NarrowConvTP n{P.x, up.w, up.b, P.a, (int)L, up.cin, up.cout, up.k, up.u, up.pad, B, v->big() ? 0.f : 0.1f};
+            NarrowConvTP n{P.x, up.w.f32, up.b, P.a, (int)L, up.cin, up.cout, up.k, up.u, up.pad, B, v->big() ? 0.f : 0.1f};
             launch_narrow_convt(n, st);
         } else {   // ConvTranspose1d(leaky_relu(x, 0.1)): GEMM + overlap-add
             IGemmP g{};
             g.A = P.x; g.lda = up.cin; g.a_bstride = L * up.cin; g.Hi = 1; g.Wi = (int)L; g.Cin = up.cin;
             g.KH = 1; g.KW = 1; g.sh = 1; g.sw = 1; g.step_h = 1; g.step_w = 1; g.Ho = 1; g.Wo = (int)L;
-            g.W = up.w; g.Wbf = g_voc_lp >= 0 ? up.wlp[g_voc_lp] : nullptr; g.N = up.k * up.cout; g.K = up.cin; g.ksplit = 1; g.groups = 1;
+            voc_weight(g, up.w, prec); g.N = up.k * up.cout; g.K = up.cin; g.ksplit = 1; g.groups = 1;
             g.C = P.y; g.ldc = g.N; g.c_bstride = L * g.N; g.OHf = 1; g.OWf = (int)L; g.osh = 1; g.osw = 1;
             g.inmask_ws = 1; g.outmask_ws = 1; g.gate_nstride = 1; g.act_in_slope = v->big() ? 0.f : 0.1f; g.B = B;     // BigVGAN: no activation here
             launch_igemm(g, prec, st);

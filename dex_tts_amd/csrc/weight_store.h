@@ -1,6 +1,6 @@
 // weight_store.h — the weight plumbing every context of the C ABI shares (DexCtx, DexText, DexStyle, DexVoc derive from WeightStore):
 // the inventory of reference state-dict keys and shapes, the raw fp32 copies the caller uploads under those keys, the device buffers
-// finalize packs from them, and the context's last error.  Host code only.
+// finalize packs from them, the handle that carries a packed weight's 16-bit twins (PackedW), and the context's last error.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
@@ -18,6 +18,19 @@
         return (obj)->fail(DEX_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
 namespace dex {
+
+// A packed weight as the launch code holds it.  The reduced-precision modes read 16-bit twins of the fp32 pack, one set per mode: [0] bf16,
+// [1] fp16, [2] fp16 hi + lo (the split-weight mode: fp16 of the weight, and in the same layout fp16 of what that rounding lost).  All sets
+// are packed at finalize - the precision mode may change afterwards - and the context picks the index in ONE place (lpi()).  A twin that
+// was not packed is a null view: the forms that need it test the handle.  Matrices packed together as a group (the Upsample's parity
+// matrices, the grouped pos-conv) are one handle each, in order; handle 0 also serves a kernel that walks the whole group by stride.
+struct LpView { const void* p = nullptr; long lo_off = 0; };      // 16-bit operand; lo_off: elements from a hi element to its lo element (0: no lo pack)
+struct PackedW {
+    PackedW(const float* f = nullptr) : f32(f) {}      // (an fp32-only operand, e.g. one built at run time, is a handle without twins)
+    const float* f32;                 // the fp32 pack ([K][N]) every mode can read
+    LpView nk[3], frag[3];            // [N][K] twin / MFMA-fragment-order twin per set
+    explicit operator bool() const { return f32 != nullptr; }
+};
 
 struct RawW { float* p = nullptr; std::vector<int64_t> shape; long numel = 0; bool loaded = false; };
 
