@@ -106,6 +106,10 @@ class DexDenoiseArgs(C.Structure):
     _fields_ = [("s", DexSampleArgs), ("x_dev", C.c_void_p)]
 
 
+class DexDenoiseBatchArgs(C.Structure):
+    _fields_ = [("s", DexSampleArgs), ("x_dev", C.c_void_p), ("sigma_dev", C.c_void_p)]
+
+
 # every symbol include/dex_amd.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("dex_ctx_create", C.c_int, [C.POINTER(DexConfig), C.POINTER(C.c_void_p)]),
@@ -122,6 +126,7 @@ SYMBOLS = [
     ("dex_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("dex_sample", C.c_int, [C.c_void_p, C.POINTER(DexSampleArgs), C.c_void_p]),
     ("dex_denoise_once", C.c_int, [C.c_void_p, C.POINTER(DexDenoiseArgs), C.c_void_p]),
+    ("dex_denoise_batch", C.c_int, [C.c_void_p, C.POINTER(DexDenoiseBatchArgs), C.c_void_p]),
     ("dex_edm_sigmas", C.c_int, [C.c_int, C.POINTER(C.c_float)]),
     ("dex_num_taps", C.c_int, [C.c_void_p]),
     ("dex_tap_name", C.c_char_p, [C.c_void_p, C.c_int]),

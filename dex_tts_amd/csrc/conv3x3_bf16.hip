@@ -208,7 +208,7 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
     const int xs = p.skip_dead ? (int)((blockIdx.x + blockIdx.y + blockIdx.z) % gridDim.x) : (int)blockIdx.x;
     const int w0 = xs * 32, h0 = blockIdx.y * TH;
     const int b = blockIdx.z / NSLICE, slice = blockIdx.z % NSLICE;
-    const int step = p.step;
+    const int step = p.step + b * p.row_bstride;      // this utterance's row of the conditioning tables (kernels.h)
     const float* X = p.X + (long)b * p.H * p.W * p.ldx + p.x_coff;
     const u16* Xh = reinterpret_cast<const u16*>(p.X) + (long)b * p.H * p.W * p.ldx + p.x_coff;   // XB: the input is bf16
     const float* mrow = p.mask + (long)b * p.mask_bstride;

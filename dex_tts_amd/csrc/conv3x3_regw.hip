@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void conv3x3_rw_kernel(const Conv3P p, const i
     const int iw0 = seg * G::MPX;
     const int r0 = chunk * rows_per_wg, r1 = min(p.H, r0 + rows_per_wg);
     const bool full_strip = iw0 + G::MPX <= p.W;                                // workgroup-uniform
-    const int step = p.step;
+    const int step = p.step + b * p.row_bstride;      // this utterance's row of the conditioning tables (kernels.h)
     const float* X = p.X + (long)b * p.H * p.W * p.ldx + p.x_coff;
     const u16* Xh = reinterpret_cast<const u16*>(p.X) + (long)b * p.H * p.W * p.ldx + p.x_coff;
     const float* mrow = p.mask + (long)b * p.mask_bstride;

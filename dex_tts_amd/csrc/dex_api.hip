@@ -872,6 +872,7 @@ struct Runner {
     bool debug;
     int gn_idx = 0;
     int sp = 0;                     // index of the current network evaluation (a by-value launch argument of every kernel)
+    int rbs = 0;                    // per-utterance stride of that index (kernels.h row_bstride): 1 in dex_denoise_batch (row b for utterance b), else 0
     gnfix_t* stats_base = nullptr;  // statistics arena of this step
     gnfix_t* stats_other = nullptr;   // arena to clear for the next step (eager mode), or null
     Update up;                      // the update of this network evaluation (assigned whole, once per evaluation)
@@ -910,7 +911,7 @@ struct Runner {
         g.inmask = nullptr; g.inmask_ws = 1; g.outmask = nullptr; g.outmask_ws = 1; g.mask_bstride = P.d.T;
         g.act = 0; g.gate = nullptr; g.gate_nstride = 1; g.gate_step_stride = 0;
         g.res = nullptr; g.ldres = 0; g.res_bstride = 0; g.res_coff = 0;
-        g.step = sp; g.unpatch_s = 0; g.unpatch_C = 0; g.B = P.d.B;
+        g.step = sp; g.row_bstride = rbs; g.unpatch_s = 0; g.unpatch_C = 0; g.B = P.d.B;
         return g;
     }
     void gemm(const char* name, const IGemmP& g) {
@@ -945,7 +946,7 @@ struct Runner {
                     c.pro_res = nullptr; c.res2_w = f.W1; c.res2_b = f.b1; c.res2_mu = f.mu; c.res2_x = f.x; c.res2_spk = f.spk;
                     c.res2_scal = f.scal; c.res2_scal_stride = f.scal_stride; c.res2_planes = f.planes;
                 } }
-            c.step = sp; c.gn_stats = gn; c.B = P.d.B;
+            c.step = sp; c.row_bstride = rbs; c.gn_stats = gn; c.B = P.d.B;
             c.Wfrag = Wt.frag[t].p;   // conv3x3_regw.hip
             const bool want_xout_lp = pro && pro->xout && pro->xout_lp_ok;
             if (shortcut) {       // the block's 1x1 res_conv rides on the centre tap of this conv
@@ -977,7 +978,7 @@ struct Runner {
         a.X = h; a.ldx = C; a.xb = npix * C; a.Y = out; a.ldy = C; a.yb = npix * C; a.y_coff = 0;
         a.npix = (int)npix; a.W = W; a.C = C; a.groups = 8; a.stats = stats; a.gamma = gamma; a.beta = beta;
         a.mask = mask; a.mask_ws = mask_ws; a.mask_bstride = P.d.T;
-        a.tadd = tadd; a.tadd_step_stride = C; a.step = sp;
+        a.tadd = tadd; a.tadd_step_stride = C; a.step = sp; a.row_bstride = rbs;
         a.res = res; a.ldres = ldres; a.resb = resb; a.res_under_mask = res_under_mask ? 1 : 0; a.B = P.d.B;
         run("gn_apply_mish", 12.0 * npix * C * P.d.B, (res ? 12.0 : 8.0) * npix * C * P.d.B, [&] { launch_gn_apply(a, st); });
     }
@@ -1003,7 +1004,7 @@ struct Runner {
             FirstConvP f{};
             f.h1_bf16 = h1b ? x->lp_kind() : 0;
             f.mu = mu; f.x = xcur; f.spk = P.spk_plane; f.mask = mask; f.B = P.d.B; f.H = s.H; f.T = s.W; f.planes = w.cin; f.C = w.cout;
-            f.W3 = w.w1.f32; f.b3 = w.b1; f.W1 = w.wr.f32; f.b1 = w.br; f.scal = P.scal; f.scal_stride = SCAL_STRIDE; f.step = sp;
+            f.W3 = w.w1.f32; f.b3 = w.b1; f.W1 = w.wr.f32; f.b1 = w.br; f.scal = P.scal; f.scal_stride = SCAL_STRIDE; f.step = sp; f.row_bstride = rbs;
             f.h1 = s.h1; f.res = s.rbuf;
             // the 1x1 shortcut of this block is two or three FMAs per value from the input planes: when the consumer is the next
             // block's fused-tail convolution it recomputes it, and the fp32 [B,H,T,64] tensor is neither written nor read
@@ -1206,7 +1207,7 @@ struct Runner {
             const bool fuse_ln = x->lp() && ln_fusable(hid);      // LayerNorm+modulate inside the GEMM's A staging (single-shot K: 64 / 128 / 256 / 512)
             DitChainP ch{};
             if (chain) {
-                ch.ksplit = 0; ch.heads = c.dit_heads; ch.rows_per_batch = N; ch.X = P.tok; ch.ada = ada; ch.step = sp; ch.M = B * N; ch.B = B;
+                ch.ksplit = 0; ch.heads = c.dit_heads; ch.rows_per_batch = N; ch.X = P.tok; ch.ada = ada; ch.step = sp; ch.row_bstride = rbs; ch.M = B * N; ch.B = B;
                 // operand set k & 1 is read by block k (separate attention kernel or in-kernel attention), the other is written
                 ch.Qh = (k & 1) ? P.qh : P.qh2; ch.Kh = (k & 1) ? P.kh : P.kh2; ch.Vt = (k & 1) ? P.vt : P.vt2;
                 ch.Qin = (k & 1) ? P.qh2 : P.qh; ch.Kin = (k & 1) ? P.kh2 : P.kh; ch.Vin = (k & 1) ? P.vt2 : P.vt;
@@ -1233,7 +1234,7 @@ struct Runner {
                 IGemmP q = base_gemm(fuse_ln ? P.tok : P.xn, hid, 0, 1, N, hid, w.wqkv, 3 * hid, w.bqkv, P.qkv, 3 * hid, 0);
                 if (fuse_ln) { q.ln_shift = ada + 0 * hid; q.ln_scale = ada + 1 * hid; q.ln_step_stride = 6L * hid; }
                 else {
-                    LnModP l1{P.tok, P.xn, N, hid, ada + 0 * hid, ada + 1 * hid, 6L * hid, sp, B};
+                    LnModP l1{P.tok, P.xn, N, hid, ada + 0 * hid, ada + 1 * hid, 6L * hid, sp, B, rbs};
                     run("ln_modulate", 8.0 * B * N * hid, 8.0 * B * N * hid, [&] { launch_ln_mod(l1, st); });
                 }
                 gemm("dit_qkv", q);
@@ -1325,7 +1326,7 @@ struct Runner {
             IGemmP f1 = base_gemm(fuse_ln ? P.tok : P.xn, hid, 0, 1, N, hid, w.wfc1, mh, w.bfc1, P.hmlp, mh, 0);
             if (fuse_ln) { f1.ln_shift = ada + 3 * hid; f1.ln_scale = ada + 4 * hid; f1.ln_step_stride = 6L * hid; }
             else {
-                LnModP l2{P.tok, P.xn, N, hid, ada + 3 * hid, ada + 4 * hid, 6L * hid, sp, B};
+                LnModP l2{P.tok, P.xn, N, hid, ada + 3 * hid, ada + 4 * hid, 6L * hid, sp, B, rbs};
                 run("ln_modulate", 8.0 * B * N * hid, 8.0 * B * N * hid, [&] { launch_ln_mod(l2, st); });
             }
             f1.act = 1;
@@ -1343,7 +1344,7 @@ struct Runner {
         }
         const bool fuse_lnf = x->lp() && ln_fusable(hid);
         if (!fuse_lnf) {
-            LnModP lf{P.tok, P.xn, N, hid, P.fin_mod, P.fin_mod + hid, 2L * hid, sp, B};
+            LnModP lf{P.tok, P.xn, N, hid, P.fin_mod, P.fin_mod + hid, 2L * hid, sp, B, rbs};
             run("ln_modulate", 8.0 * B * N * hid, 8.0 * B * N * hid, [&] { launch_ln_mod(lf, st); });
         }
         IGemmP fl = final_gemm(mask_ws, out, ldo, ocoff);
@@ -1381,7 +1382,7 @@ struct Runner {
         if (tv_fold_on()) {
             // folded form: one element-wise launch turns the statistics into this step's K' (and the time token's rows), then the chain
             TvFold2P f2{P.tv_stats, (int)npix, 1e-5f, P.tv_G, (long)(P.d.Ts + 1) * mid, P.tv_g0, P.tv_v0p, sp, P.d.Ts + 1, P.tv_nkpad, mid,
-                        1.0f / sqrtf((float)mid), P.tv_kp, P.tv_vtp, P.tv_xmean, reinterpret_cast<float*>(P.tiv_stats), stats_floats, x->lp_kind(), B};
+                        1.0f / sqrtf((float)mid), P.tv_kp, P.tv_vtp, P.tv_xmean, reinterpret_cast<float*>(P.tiv_stats), stats_floats, x->lp_kind(), B, rbs};
             run("tv_fold_keys", 2.0 * B * (P.d.Ts + 1) * mid, 6.0 * B * (P.d.Ts + 1) * mid, [&] { launch_tv_fold2(f2, st); });
             TvChainP tc{X.p, X.ld, X.coff, npix * X.ld, (int)npix, P.Wm, mask, mask_ws, (long)P.d.T,
                         nullptr, 0L, nullptr, nullptr, 0L,
@@ -1403,6 +1404,7 @@ struct Runner {
         if (!chain) gemm("tv_q", q);
         TvRow0P r0{P.tv_k0, P.tv_v0, sp, P.tv_K, P.tv_V, (long)(P.d.Ts + 1) * mid, mid, B, reinterpret_cast<float*>(P.tv_stats),
                    (long)B * mid * IN_SLOTS * 2 * 2 * (long)(sizeof(gnfix_t) / sizeof(float))};
+        r0.row_bstride = rbs;
         if (chain) { r0.Kp = P.tv_kp; r0.VTp = P.tv_vtp; r0.NkPad = P.tv_nkpad; r0.lp_kind = x->lp_kind(); }
         run("tv_time_token", 0, 8.0 * mid * B, [&] { launch_tv_row0(r0, st); });
         // Batch regime, reduced-precision modes: q projection, attention, output projection, residual, mask and the TIV statistics as
@@ -1442,7 +1444,7 @@ struct Runner {
     }
     void tiv(long npix) {
         const int B = P.d.B, mid = mid_dim(x->cfg);
-        TivApplyP ta{P.tv_out, mid, npix * mid, P.tiv_out, mid, npix * mid, (int)npix, mid, P.tiv_stats, 1e-5f, P.sap_s, P.sap_m, sp, B};
+        TivApplyP ta{P.tv_out, mid, npix * mid, P.tiv_out, mid, npix * mid, (int)npix, mid, P.tiv_stats, 1e-5f, P.sap_s, P.sap_m, sp, B, rbs};
         if (tiv_fold()) { run("tiv_coefficients", 0, 16.0 * mid * B, [&] { launch_tiv_coef(ta, P.tiv_aff, st); }); return; }
         run("tiv_adain", 2.0 * npix * mid * B, 8.0 * npix * mid * B, [&] { launch_tiv_apply(ta, st); });
         tap("tiv", P.tiv_out, B * npix, mid, mid);
@@ -1454,8 +1456,8 @@ struct Runner {
         const int B = P.d.B, ns = c.n_stages;
         gn_idx = 0;
         if (debug) {                          // (G1 checkpoints: this step's rows of the conditioning tables - the time MLP and the DiT's TimestepEmbedder)
-            tap("mlp", P.temb + (long)sp * c.dim, 1, c.dim, c.dim);
-            tap("vit.t_embedder", P.c_emb + (long)sp * c.dit_hidden, 1, c.dit_hidden, c.dit_hidden);
+            tap("mlp", P.temb + (long)sp * c.dim, rbs ? B : 1, c.dim, c.dim);          // (a row per utterance in dex_denoise_batch)
+            tap("vit.t_embedder", P.c_emb + (long)sp * c.dit_hidden, rbs ? B : 1, c.dit_hidden, c.dit_hidden);
         }
         if (!stats_other) zero_fill(stats_base, P.stats_bytes, st);   // single call (dex_denoise_once): clear in place
         TD cur{nullptr, 0, 0, 0};
@@ -1599,7 +1601,7 @@ struct Runner {
         f.x_bf16 = hfb ? x->lp_kind() : 0;
         f.X = P.hF; f.xb = 80L * P.d.T * c.dim; f.npix = 80 * P.d.T; f.W = P.d.T; f.C = c.dim; f.groups = 8; f.stats = stf;
         f.gamma = x->fin_g; f.beta = x->fin_be; f.mask = mask; f.mask_bstride = P.d.T; f.wfc = x->fconv_w; f.bfc = x->fconv_b;
-        f.xcur = xcur; f.denoised = denoised; f.xnext = xnext; f.scal = P.scal; f.scal_stride = SCAL_STRIDE; f.step = sp; f.B = B;
+        f.xcur = xcur; f.denoised = denoised; f.xnext = xnext; f.scal = P.scal; f.scal_stride = SCAL_STRIDE; f.step = sp; f.row_bstride = rbs; f.B = B;
         f.zero_ptr = reinterpret_cast<float*>(stats_other); f.zero_n = P.stats_bytes / (long)sizeof(float);
         f.poison = P.xflag ? reinterpret_cast<const int*>(P.xflag + (P.xflag_bytes - sizeof(int)) / sizeof(unsigned)) : nullptr;
         f.mode = up.mode; f.htab = up.htab; f.dbuf = P.dbuf; f.xhat = P.xbuf;
@@ -1609,7 +1611,7 @@ struct Runner {
     }
 
     // conditioning tables for every Euler step (depend only on sigma_i)
-    void prepare(const float* sigmas_dev, int n) {
+    void prepare(const float* sigmas_dev, int n, bool levels = false) {      // levels: n independent noise levels (no sigmas_dev[n])
         const DexConfig& c = x->cfg;
         const int dim = c.dim, hid = c.dit_hidden, B = P.d.B, mid = mid_dim(c);
         auto R = [&](const std::string& k) { return x->raw.at(k).p; };
@@ -1621,7 +1623,7 @@ struct Runner {
         if (P.xflag) zero_fill(P.xflag, P.xflag_bytes, st);     // hand-off flags of the cluster row chain: zero before every call (epochs count within it)
         zero_fill(P.vt, P.vt_bytes, st);      // key padding of the transposed V operand (attention_direct.hip)
         zero_fill(P.vt2, P.vt_bytes, st);
-        CondPrepP cp{sigmas_dev, n, c.pe_scale, dim, P.scal, SCAL_STRIDE, P.t_unet, P.t_dit};
+        CondPrepP cp{sigmas_dev, n, c.pe_scale, dim, P.scal, SCAL_STRIDE, P.t_unet, P.t_dit, levels ? 1 : 0};
         run("cond_prep", 0, 0, [&] { launch_cond_prep(cp, st); });
         lin(P.t_unet, dim, n, dim, "mlp.0", true, 4 * dim, P.tmp_u, 0, 1);
         lin(P.tmp_u, 4 * dim, n, 4 * dim, "mlp.2", true, dim, P.temb, 0, 0);
@@ -1874,6 +1876,35 @@ int dex_denoise_once(DexCtx* x, const DexDenoiseArgs* da, dex_stream_t stream) {
     R.sp = 0; R.stats_base = P.stats; R.stats_other = nullptr;
     hipLaunchKernelGGL(set_sigma_pair, dim3(1), dim3(1), 0, st, a->sigmas_dev, P.sig2);
     R.prepare(P.sig2, 1);
+    R.step(a->out_dev, nullptr);
+    DEX_HIPCHK(x, hipGetLastError());
+    return DEX_OK;
+}
+
+// EDMPrecond.forward with a noise level per utterance (edm.py:88-98: sigma.reshape(-1, 1, 1)): the conditioning pipeline builds B rows
+// from sigma_dev - row b is what a one-evaluation call at sigma_dev[b] builds - and every kernel of the evaluation reads row
+// step + b * row_bstride = b of its tables (kernels.h).  Eager launches, nothing read back, nothing allocated.
+int dex_denoise_batch(DexCtx* x, const DexDenoiseBatchArgs* da, dex_stream_t stream) {
+    if (!da) return DEX_ERR_ARG;
+    if (!x) return DEX_ERR_ARG;
+    if (!da->sigma_dev) return x->fail(DEX_ERR_ARG, "sigma_dev is null (dex_denoise_batch takes [B] noise levels in device memory)");
+    DexSampleArgs sa = da->s; sa.sigmas_dev = da->sigma_dev;          // (s.sigmas_dev is ignored by this call: the levels are sigma_dev)
+    const DexSampleArgs* a = &sa;
+    int rc = validate(x, a, false);
+    if (rc) return rc;
+    if (!da->x_dev) return x->fail(DEX_ERR_ARG, "x_dev is null");
+    if (a->use_graph) return x->fail(DEX_ERR_ARG, "dex_denoise_batch does not capture graphs: call it with use_graph = 0");
+    const CallScope scope(x);
+    hipStream_t st = (hipStream_t)stream;
+    Plan P; Dims d{a->B, a->T, a->Tr, a->Ts, a->B};          // a conditioning row per utterance
+    make_plan(x, d, nullptr, P);
+    if (P.bytes > a->workspace_bytes)
+        return x->fail(DEX_ERR_WORKSPACE, "workspace too small: need %zu bytes (dex_workspace_bytes with n_evals = B), got %zu", P.bytes, a->workspace_bytes);
+    make_plan(x, d, a->workspace_dev, P);
+    x->reset_records();
+    Runner R{x, P, st, a->mask_dev, a->mu_dev, da->x_dev, a, true};
+    R.sp = 0; R.rbs = 1; R.stats_base = P.stats; R.stats_other = nullptr;
+    R.prepare(da->sigma_dev, a->B, true);
     R.step(a->out_dev, nullptr);
     DEX_HIPCHK(x, hipGetLastError());
     return DEX_OK;

@@ -216,7 +216,7 @@ void launch_in_fold(const InFoldP& p, hipStream_t st) {
 __global__ __launch_bounds__(256) void tiv_apply_kernel(const TivApplyP p) {
     __shared__ float sa[256], sb[256];
     const int tid = threadIdx.x, b = blockIdx.y;
-    const int step = p.step;
+    const int step = p.step + b * p.row_bstride;      // this utterance's row of the conditioning tables (kernels.h)
     if (tid < p.C) {
         float mean, rstd;
         in_mean_rstd(p.stats, (long)b * p.C + tid, p.npix, p.eps, mean, rstd);
@@ -263,8 +263,9 @@ __global__ void tiv_coef_kernel(const TivApplyP p, float* aff) {
     if (tid < p.C) {          // (the arithmetic of tiv_apply_kernel's prologue: the consumer's fmaf(x, a, c) gives tiv_apply's bits)
         float mean, rstd;
         in_mean_rstd(p.stats, (long)b * p.C + tid, p.npix, p.eps, mean, rstd);
-        const float s = p.s_tab[((long)p.step * p.B + b) * p.C + tid];
-        const float m = p.m_tab[((long)p.step * p.B + b) * p.C + tid];
+        const long row = p.step + b * p.row_bstride;
+        const float s = p.s_tab[(row * p.B + b) * p.C + tid];
+        const float m = p.m_tab[(row * p.B + b) * p.C + tid];
         aff[((long)b * 2 + 0) * p.C + tid] = rstd * s;
         aff[((long)b * 2 + 1) * p.C + tid] = m - mean * rstd * s;
     }
@@ -282,7 +283,7 @@ void launch_tiv_apply(const TivApplyP& p, hipStream_t st) {
 
 __global__ void tv_row0_kernel(const TvRow0P p) {
     const int b = blockIdx.x, c = threadIdx.x;
-    const int step = p.step;
+    const int step = p.step + b * p.row_bstride;      // this utterance's row of the conditioning tables (kernels.h)
     if (p.zero_ptr) for (long i = (long)b * blockDim.x + c; i < p.zero_n; i += (long)gridDim.x * blockDim.x) p.zero_ptr[i] = 0.f;
     if (b < p.B && c < p.C) {
         const float kv = p.k0[(long)step * p.C + c], vv = p.v0[(long)step * p.C + c];
@@ -321,7 +322,7 @@ __global__ __launch_bounds__(256) void tv_fold2_kernel(const TvFold2P p) {
             p.xmean[(long)b * C + tid] = mean;
             // key 0 of V'^T in fragment order: tile 0, piece (t = ch / 32, q = 0), lane ch % 32 (hh = 0), element 0
             reinterpret_cast<unsigned short*>(p.VTp)[(long)b * C * p.NkPad + (((tid >> 5) * 4) * 64 + (tid & 31)) * 8] =
-                (unsigned short)(pack2_kind(p.v0p[(long)p.step * C + tid], 0.f, p.lp_kind) & 0xffffu);
+                (unsigned short)(pack2_kind(p.v0p[(long)(p.step + b * p.row_bstride) * C + tid], 0.f, p.lp_kind) & 0xffffu);
         }
     }
     __syncthreads();
@@ -332,7 +333,7 @@ __global__ __launch_bounds__(256) void tv_fold2_kernel(const TvFold2P p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int key = blockIdx.x * 64 + (tid >> 4) + 16 * j;
-        const float* src = key == 0 ? p.g0 + (long)p.step * C + c8 : p.G + (long)b * p.gb + (long)min(key, p.Nk - 1) * C + c8;
+        const float* src = key == 0 ? p.g0 + (long)(p.step + b * p.row_bstride) * C + c8 : p.G + (long)b * p.gb + (long)min(key, p.Nk - 1) * C + c8;
         ga[j] = *reinterpret_cast<const float4*>(src); gc[j] = *reinterpret_cast<const float4*>(src + 4);
     }
 #pragma unroll

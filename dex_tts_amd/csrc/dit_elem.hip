@@ -194,7 +194,7 @@ __global__ __launch_bounds__(256) void ln_mod_kernel(const LnModP p) {
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const long rows = (long)p.B * p.rows_per_batch;
     if (row >= rows) return;
-    const int step = p.step;
+    const int step = p.step + (p.row_bstride ? (int)(row / p.rows_per_batch) * p.row_bstride : 0);      // this utterance's row of the tables (kernels.h)
     const float* x = p.X + row * p.D;
     const int per = p.D >> 6;
     float v[8];

@@ -359,7 +359,7 @@ __global__ __launch_bounds__(RC_NW * 64) void dit_rowchain_kernel(const DitChain
     if (p.xcd_map) { const int slot = (int)blockIdx.x >> 3; b = ((int)blockIdx.x & 7) + 8 * (slot / tpb); n0 = (slot % tpb) * RC_ROWS; }
     else { b = blockIdx.x / tpb; n0 = (blockIdx.x - b * tpb) * RC_ROWS; }
     const long mb = (long)b * N;                               // first global row of this batch element
-    const int step = p.step;
+    const int step = p.step + b * p.row_bstride;      // this utterance's row of the conditioning tables (kernels.h)
     const float* ada = p.ada + (long)step * 6 * RC_H;
     const bool has_q = p.next_shift != nullptr;
 
@@ -682,7 +682,7 @@ __global__ __launch_bounds__(RC_NW * 64) void dit_rowchain64_kernel(const DitCha
     const int N = p.rows_per_batch, tpb = (N + 63) / 64;
     const int b = blockIdx.x / tpb, n0 = (blockIdx.x - b * tpb) * 64;
     const long mb = (long)b * N;
-    const int step = p.step;
+    const int step = p.step + b * p.row_bstride;      // this utterance's row of the conditioning tables (kernels.h)
     const float* ada = p.ada + (long)step * 6 * RC_H;
     const bool has_q = p.next_shift != nullptr;
 #ifdef DEX_TIMING
@@ -898,7 +898,7 @@ __global__ __launch_bounds__(256) void dit_rowchain64a_kernel(const DitChainP p)
 #endif
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int N = p.rows_per_batch, tpb = (N + 63) / 64, ntiles = p.B * tpb;
-    const int step = p.step;
+    const int step = p.step;                  // (one parameter set per workgroup, whose tiles span utterances: the launcher keeps row_bstride != 0 away)
     const float* ada = p.ada + (long)step * 6 * RC_H;
     const bool has_q = p.next_shift != nullptr;
     const unsigned long long wp = reinterpret_cast<unsigned long long>(p.Wp), w1 = reinterpret_cast<unsigned long long>(p.W1);
@@ -1149,7 +1149,7 @@ __global__ __launch_bounds__(RC_NW * 64) void dit_rowchain_cluster_kernel(const 
     const unsigned flagv = p.epoch | (my_xcc << 24);
     const int b = cluster / tpb, n0 = (cluster - b * tpb) * RC_ROWS;
     const long mb = (long)b * N;
-    const int step = p.step;
+    const int step = p.step + b * p.row_bstride;      // this utterance's row of the conditioning tables (kernels.h)
     const float* ada = p.ada + (long)step * 6 * RC_H;
     const bool has_q = p.next_shift != nullptr;
     float* slab = p.xslab + (long)cluster * DIT_CLUSTER_SLAB_FLOATS;     // [e][member][32*256 + 256]
@@ -1610,7 +1610,7 @@ void launch_dit_rowchain(const DitChainP& p, hipStream_t st) {
                 hipFuncSetAttribute(reinterpret_cast<const void*>(&dit_rowchain64_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)RC64_LDS);
                 attr64 = true;
             }
-            if (knob_or("DEX_ROWCHAIN64A", 1) && (p.qkv_only || (p.o_lp && p.ksplit <= 1 && p.tail_ks <= 1))) {   // the generated streams (0: the round-3 kernel)
+            if (knob_or("DEX_ROWCHAIN64A", 1) && p.row_bstride == 0 && (p.qkv_only || (p.o_lp && p.ksplit <= 1 && p.tail_ks <= 1))) {   // the generated streams (0: the round-3 kernel)
                 static bool attr64a = false;
                 if (!attr64a) {
                     hipFuncSetAttribute(reinterpret_cast<const void*>(&dit_rowchain64a_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)RCA_LDS_BYTES);

@@ -3,6 +3,9 @@
 // "step" is the index of the network evaluation inside one sampler call: per-step conditioning tables are indexed as
 // table[step*stride + ...].  It is a by-value launch argument (the whole call is one hipGraph with a node per launch; round 1
 // replayed a one-step graph and read the index from device memory - a dependent load at the head of every kernel).
+// "row_bstride" (a member of every struct that carries `step`) is the per-utterance stride of that index: batch element b reads row
+// step + b * row_bstride.  0 = one row for the whole batch (every sampler call); 1 with step = 0 = row b for utterance b, the call with
+// a noise level per utterance (dex_denoise_batch).  By value as well: one integer multiply-add on a workgroup-uniform value.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -75,6 +78,7 @@ struct IGemmP {
     const float* gate; int gate_nstride; long gate_step_stride;
     const float* res; int ldres; long res_bstride; int res_coff;
     int step;
+    int row_bstride = 0;                               // gate / ln_shift / ln_scale row of batch element b: step + b * row_bstride
     int unpatch_s, unpatch_C;                          // >0: scatter rows (f,w) x cols (p1,p2,c) -> NHWC image
     int parity;                                        // 1: blockIdx.z = b*4 + (ph*2+pw): ConvTranspose2d(4,2,1) as four 2x2-tap
                                                        // sub-convolutions in ONE launch (off/oh0/ow0 = parity, weights += par*K*N)
@@ -140,6 +144,7 @@ struct Conv3P {
     // x_bf16: X is bf16 [.. ldx] (PRO / PRO2 forms only); y_bf16: Y is written as bf16.  Statistics stay fp32.
     int x_bf16, y_bf16;
     long w_lo_off = 0, res_lo_off = 0;                       // split-weight mode (PREC_FP16X2): elements from a weight of Wbf / res_w to its lo half
+    int row_bstride = 0;                                     // pro_tadd / res2_scal row of batch element b: step + b * row_bstride
     int skip_dead = 0;                                       // set by the launchers (DEX_CONV_SKIP_DEAD): tiles whose whole input patch lies in an utterance's padding
                                                              // (mask 0 in every column) skip loads, prologue and MFMAs - conv(0) + bias is what they would compute
 };
@@ -165,6 +170,7 @@ struct FirstConvP {
     float* h1; float* res;                                // [B,H,T,C] each
     int h1_bf16;                                          // h1 stored as bf16 (1) / fp16 (2): its only reader is the next conv's GN prologue
     gnfix_t* gn_stats;                                    // fused GroupNorm partials of h1 (8 groups, slot-spread) or null
+    int row_bstride = 0;                                  // scal row of batch element b: step + b * row_bstride
 };
 void launch_first_conv(const FirstConvP& p, hipStream_t st);
 
@@ -181,6 +187,7 @@ struct GnApplyP {
     const float* tadd; long tadd_step_stride; int step;
     const float* res; int ldres; long resb; int res_under_mask;   // 1: y = mask*(mish + tadd + res)
     int B;
+    int row_bstride = 0;                                  // tadd row of batch element b: step + b * row_bstride
 };
 void launch_gn_apply(const GnApplyP& p, hipStream_t st);
 
@@ -201,6 +208,7 @@ struct FinalP {
     int mode; const float* htab; float* dbuf; const float* xhat;
     int x_bf16;                                           // X (the final conv's raw output) is bf16 (1) / fp16 (2)
     const int* poison;                                    // optional device word: non-zero (a workgroup hand-off of this call timed out) -> the outputs are NaN
+    int row_bstride = 0;                                  // scal row of batch element b: step + b * row_bstride (the combine only: `denoised`, no update)
 };
 void launch_final(const FinalP& p, hipStream_t st);
 // The general update of ablation_sampler's tables (final_kernel<FinalGP>; DexSamplerTables in dex_amd.h; FinalP's own kernel is
@@ -298,7 +306,7 @@ void launch_group_pad(const float* src, float* dst, long rows, int G, int cg, in
 
 // LayerNorm(eps 1e-6, no affine) + modulate (dit.py:78-79,288-289,330)
 struct LnModP { const float* X; float* Y; int rows_per_batch; int D; const float* shift; const float* scale;
-                long step_stride; int step; int B; };
+                long step_stride; int step; int B; int row_bstride = 0; };
 void launch_ln_mod(const LnModP& p, hipStream_t st);
 
 // Row-local remainder of a DiT block + the next block's qkv projection in one launch (dit_rowchain.hip; bf16 mode,
@@ -321,6 +329,7 @@ struct DitChainP { const float* O; int ksplit; long o_sstride; const float* ml; 
                    int xlocal;                              // 1: the members of a cluster share an XCD (hand-offs through its L2; grid padded to rounds of 8 clusters)
                    int xdrop;
                    int tail_row0 = 0, tail_ks = 0;
+                   int row_bstride = 0;                     // ada / next_shift / next_scale row of batch element b: step + b * row_bstride
                    int xcds = 8; };            // xlocal: the clusters are dealt to the first `xcds` XCDs only (workgroups of the others leave at once): fewer L2s fetch the weights and K / V^T      // 64-row form: rows from tail_row0 on are merged from tail_ks fp32 partials in O slots 1.. (AttnDirectP::tail_g); 0 / 1 = off                            // tests only (DEX_DEBUG_DROP_HANDOFF): 1 member 3 never raises its flags -> the peers' waits time out; 2 L2-scope hand-offs across XCDs
 // cluster form of the row chain: workgroups per 32-row tile, bytes of exchange slab / flag words per tile, and whether a launch
 // of B x N rows takes it (all workgroups co-resident: <= one per CU)
@@ -381,7 +390,8 @@ void launch_small_linear(const SmallLinP& p, hipStream_t st);
 
 // Per-step EDM scalars + sinusoidal features from the sigma table (edm.py:90-94, diffusion.py:110-117, dit.py:250-254)
 struct CondPrepP { const float* sigmas; int n; float pe_scale; int dim; float* scal; int scal_stride;
-                   float* t_unet; float* t_dit; };
+                   float* t_unet; float* t_dit;
+                   int no_next = 0; };       // 1: sigmas holds n independent levels, not a schedule - sigma_next = 0, sigmas[n] is not read
 void launch_cond_prep(const CondPrepP& p, hipStream_t st);
 
 // misc elementwise
@@ -417,14 +427,16 @@ struct InFoldP { const gnfix_t* stats; int npix; float eps; const float* Wq; int
 void launch_in_fold(const InFoldP& p, hipStream_t st);
 // TIV: y = IN2d(x)*s + m  (ref_encoder.py:271); s,m indexed [step][b][C]
 struct TivApplyP { const float* X; int ld; long xb; float* Y; int ldy; long yb; int npix; int C; const gnfix_t* stats;
-                   float eps; const float* s_tab; const float* m_tab; int step; int B; };
+                   float eps; const float* s_tab; const float* m_tab; int step; int B;
+                   int row_bstride = 0; };      // table row of batch element b: step + b * row_bstride
 void launch_tiv_apply(const TivApplyP& p, hipStream_t st);
 // the same transform as per-channel coefficients for a consumer that applies it on load: aff [B][2][C] (y = x * aff[b][0][c] + aff[b][1][c]; p.X / p.Y unused)
 void launch_tiv_coef(const TivApplyP& p, float* aff, hipStream_t st);
 // write per-step time-token rows into K/V row 0 (ref_encoder.py:157)
 struct TvRow0P { const float* k0; const float* v0; int step; float* K; float* V; long kvb; int C; int B;
                  float* zero_ptr; long zero_n;             // optional: clear the IN2d statistics for their next use
-                 void* Kp = nullptr; void* VTp = nullptr; int NkPad = 0; int lp_kind = 0; };   // optional: row 0 of the one-launch adaptor's 16-bit operands too (TvKvPrepP layouts, C = 128)
+                 void* Kp = nullptr; void* VTp = nullptr; int NkPad = 0; int lp_kind = 0;
+                 int row_bstride = 0; };   // optional: row 0 of the one-launch adaptor's 16-bit operands too (TvKvPrepP layouts, C = 128)
 void launch_tv_row0(const TvRow0P& p, hipStream_t st);
 // The TV adaptor as ONE launch in the batch regime (attention_bf16.hip, reduced-precision modes; ref_encoder.py:154-179):
 //   out = mask * (x + linear(softmax((IN2d(x) W_q^T / sqrt(C)) K^T) V))   with the InstanceNorm folded into a per-utterance W_eff, b_eff
@@ -453,7 +465,8 @@ struct TvChainP { const float* X; int ldx; int x_coff; long x_bstride; int npix;
 //   xmean[b][k]    = mean[b,k]
 // and clears zero_n floats at zero_ptr (the TIV statistics: their last reader was the previous step's launch_tiv_coef).  C = 128.
 struct TvFold2P { const gnfix_t* stats; int npix; float eps; const float* G; long gb; const float* g0; const float* v0p; int step;
-                  int Nk; int NkPad; int C; float scale; void* Kp; void* VTp; float* xmean; float* zero_ptr; long zero_n; int lp_kind; int B; };
+                  int Nk; int NkPad; int C; float scale; void* Kp; void* VTp; float* xmean; float* zero_ptr; long zero_n; int lp_kind; int B;
+                  int row_bstride = 0; };      // g0 / v0p row of batch element b: step + b * row_bstride
 void launch_tv_fold2(const TvFold2P& p, hipStream_t st);
 bool tv_chain_form(int npix, int C, int B);
 void launch_tv_kv_prep(const TvKvPrepP& p, int precision, hipStream_t st);

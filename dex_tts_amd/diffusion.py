@@ -74,6 +74,38 @@ class _Precond(nn.Module):
             raise RuntimeError("precond_model has no live owner (it belongs to a dex_tts_amd.diffusion.Diffusion)")
         return owner.engine(x.device).denoise_once(x, sigma, mask, mu, **kw)
 
+    def _denoise_batch(self, x, sigma, mask, mu, **kw):
+        """One EDMPrecond.forward with a noise level per utterance (``sigma``: a device tensor of B elements) on the owner's engine."""
+        owner = self._owner() if self._owner is not None else None
+        if owner is None:
+            raise RuntimeError("precond_model has no live owner (it belongs to a dex_tts_amd.diffusion.Diffusion)")
+        return owner.engine(x.device).denoise_batch(x, sigma, mask, mu, **kw)
+
+    @torch.no_grad()
+    def forward(self, x, sigma, mask, mu, *dex_args, spk=None, mask_ratio=0):
+        """The reference's ``EDMPrecond.forward`` (edm.py:88-98).  GeDEX: ``forward(x, sigma, mask, mu, spk=None, mask_ratio=0)``; DEX:
+        ``forward(x, sigma, mask, mu, ref, ref_lengths, sty, sty_lengths, spk=None, mask_ratio=0)``.  ``sigma``: a tensor with one
+        element per utterance ([B], [B,1] or [B,1,1]: one batched evaluation, the levels never leave the device), or a Python
+        float / one-element tensor (one level for the whole batch).  Forward-only."""
+        if mask_ratio:
+            raise NotImplementedError("mask_ratio > 0 (DiT token masking, dit.py:145-163) is unreachable with the shipped configs and not built")
+        if any(t is not None and torch.is_tensor(t) and t.requires_grad for t in (x, mu, sigma)):
+            raise RuntimeError("precond_model here is forward-only (the HIP score network has no backward); train with the reference module")
+        kw = {}
+        if dex_args:
+            if len(dex_args) != 4:
+                raise TypeError("DEX: forward(x, sigma, mask, mu, ref, ref_lengths, sty, sty_lengths, ...)")
+            ref, _ref_lengths, sty, sty_lengths = dex_args
+            kw = dict(ref=ref, sty=sty, sty_lengths=sty_lengths)
+        if spk is not None:
+            kw["spk"] = spk
+        B = x.shape[0]
+        if torch.is_tensor(sigma) and sigma.numel() == B and (B > 1 or sigma.dim() >= 1):
+            return self._denoise_batch(x, sigma, mask, mu, **kw)
+        if torch.is_tensor(sigma) and sigma.numel() != 1:
+            raise ValueError(f"sigma has {sigma.numel()} elements: expected one, or one per utterance ({B})")
+        return self._denoise_once(x, float(sigma), mask, mu, **kw)
+
 
 def _cfg_get(obj, name, default):
     if isinstance(obj, dict):
@@ -217,7 +249,7 @@ class Diffusion(nn.Module):
 
     # ---- reference call surface ----------------------------------------------------------------
     @torch.no_grad()
-    def forward(self, x, mask, mu, *args, n_timesteps=1, spk=None, infer=False, temperature=1.0, mask_ratio=0, **kw):
+    def forward(self, x, mask, mu, *args, n_timesteps=1, spk=None, infer=False, temperature=1.0, mask_ratio=0, batched=False, rnd_normal=None, eps=None, **kw):
         names = ["ref", "ref_lengths", "sty", "sty_lengths"] if self.cfg.variant == "dex" else []
         names += ["n_timesteps", "spk", "infer", "temperature", "mask_ratio"]
         vals = {"n_timesteps": n_timesteps, "spk": spk, "infer": infer, "temperature": temperature, "mask_ratio": mask_ratio}
@@ -229,7 +261,9 @@ class Diffusion(nn.Module):
         if not vals["infer"]:                     # diffusion.py:222-224 / :252-254: the EDM training-loss VALUE (no backward on this path)
             dex = (vals["ref"], vals["ref_lengths"], vals["sty"], vals["sty_lengths"]) if self.cfg.variant == "dex" else ()
             self._bind_owner()                    # (an unpickled module restores its sub-modules' state after its own)
-            return self.loss_fn(self.precond_model, x, mask, mu, *dex, spk=vals["spk"], mask_ratio=vals["mask_ratio"])
+            # batched (infer=False only): the B noise levels in ONE network call (dex_tts_amd/edm.py); False keeps every earlier result's bits
+            return self.loss_fn(self.precond_model, x, mask, mu, *dex, spk=vals["spk"], mask_ratio=vals["mask_ratio"], batched=batched,
+                                rnd_normal=rnd_normal, eps=eps)          # (the two draws, injected: tests; None = drawn as in the reference)
         shape = (mu.shape[0], 80, mu.shape[2])
         z = torch.randn(shape, device=x.device) / vals["temperature"] + mu            # diffusion.py:227
         if self.cfg.variant == "dex":

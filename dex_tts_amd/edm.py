@@ -4,9 +4,12 @@
 Same constructor, same ``forward`` argument order, same two generator draws in the same order (``randn([B,1,1])`` for the
 noise level, then ``randn_like(x0)``), same weighting branches (``loss_type`` 'base', 'base_min_k', 'base_log_k', 'min_snr_k',
 'max_snr_k', 'snr', 'inv_snr').  The denoiser evaluation ``D(x0 + n; sigma)`` — all of the arithmetic that matters — runs in
-libdexamd.so (``dex_denoise_once``), one utterance per call because every utterance has its own sigma and the library's
-conditioning tables are per call; the per-utterance scalars (sigma, weight) and the final masked mean are a handful of stock
-torch ops on [B,1,1] / [B,80,T] tensors, as VERDICT round 2 item 7 allows.
+libdexamd.so.  Every utterance has its own sigma.  ``batched=False`` (the default, whose results keep their bits) reads the B
+levels back to the host and calls ``dex_denoise_once`` once per utterance at B = 1; ``batched=True`` evaluates the whole batch in
+ONE ``dex_denoise_batch`` call - the library builds a conditioning row per utterance from the device vector of levels, as the
+reference's ``EDMPrecond.forward`` does with ``sigma.reshape(-1, 1, 1)`` - with sigma, the weight and the masked mean staying on
+the device.  The per-utterance scalars (sigma, weight) and the final masked mean are a handful of stock torch ops on [B,1,1] /
+[B,80,T] tensors, as VERDICT round 2 item 7 allows.
 
 This is the loss VALUE (validation / monitoring, parity with the reference on fixed draws — tests/golden/edm_loss.npz).  The HIP
 path has no backward pass: training stays with the reference module, and a tensor that requires grad is refused loudly rather
@@ -47,11 +50,13 @@ class EDMLoss(nn.Module):
         self.P_mean, self.P_std, self.sigma_data, self.n_feats, self.loss_type = P_mean, P_std, sigma_data, n_feats, loss_type
 
     @torch.no_grad()
-    def forward(self, precond_model, x0, mask, mu, *dex_args, spk=None, mask_ratio=0, rnd_normal=None, eps=None):
+    def forward(self, precond_model, x0, mask, mu, *dex_args, spk=None, mask_ratio=0, rnd_normal=None, eps=None, batched=False):
         """GeDEX: ``forward(precond_model, x0, mask, mu, spk=None, mask_ratio=0)``; DEX: ``forward(precond_model, x0, mask, mu,
         ref, ref_lengths, sty, sty_lengths, spk=None, mask_ratio=0)``.  ``precond_model`` is the owning ``Diffusion``'s
         ``precond_model`` (it carries the engine hook); ``rnd_normal`` / ``eps`` inject the two draws (tests), otherwise they
-        come from the device generator exactly as in the reference."""
+        come from the device generator exactly as in the reference.  ``batched``: one ``denoise_batch`` call with the B noise levels
+        on the device instead of a host read and B calls at B = 1 (same draws, same weighting; the network's arithmetic is that of
+        a batch-B evaluation, so the value agrees with the looped one to the kernels' single-call bound, not bit for bit)."""
         if mask_ratio:
             raise NotImplementedError("mask_ratio > 0 (DiT token masking, dit.py:145-163) is unreachable with the shipped configs and not built")
         if any(t is not None and torch.is_tensor(t) and t.requires_grad for t in (x0, mu)):
@@ -73,6 +78,17 @@ class EDMLoss(nn.Module):
             eps = torch.randn_like(x0)                                            # edm.py:65
         n = (eps.to(x0.device) + mu) * sigma
         xn = x0 + n
+        if batched:
+            denoise_b = getattr(precond_model, "_denoise_batch", None)
+            if denoise_b is None:
+                raise TypeError("precond_model must be dex_tts_amd.diffusion.Diffusion.precond_model")
+            kw = {}
+            if ref is not None:
+                kw = dict(ref=ref, sty=sty, sty_lengths=sty_lengths)
+            if spk is not None:
+                kw["spk"] = spk
+            D_yn = denoise_b(xn, sigma, mask, mu, **kw)
+            return torch.sum(weight * ((D_yn - x0) ** 2)) / torch.sum(mask * self.n_feats)      # edm.py:66
         sig_host = sigma.reshape(B).tolist()                                       # one host read: each utterance has its own sigma
         rows = []
         for b in range(B):

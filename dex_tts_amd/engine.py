@@ -317,6 +317,26 @@ class ScoreNetEngine:
             self._keep = keep + [x]
             return out
 
+    def denoise_batch(self, x, sigma, mask, mu, spk=None, ref=None, sty=None, sty_lengths=None):
+        """EDMPrecond.forward with a noise level per utterance (edm.py:88-98, ``sigma.reshape(-1, 1, 1)``) as ONE network evaluation:
+        ``sigma`` is a tensor of B elements ([B], [B,1] or [B,1,1]) that stays on the device - nothing is read back, nothing waits.
+        Records debug taps like denoise_once."""
+        with torch.cuda.device(self.device):
+            mu, mask, spk, ref, sty, sty_lengths = self._inputs(mu, mask, spk, ref, sty, sty_lengths)
+            B = mu.shape[0]
+            if not torch.is_tensor(sigma) or sigma.numel() != B or tuple(sigma.shape) not in ((B,), (B, 1), (B, 1, 1)):
+                raise ValueError(f"sigma must be a tensor of shape ({B},), ({B}, 1) or ({B}, 1, 1), one noise level per utterance")
+            x = x.to(device=self.device, dtype=torch.float32).contiguous()
+            sig = sigma.to(device=self.device, dtype=torch.float32).reshape(B).contiguous()
+            out = torch.empty_like(mu)
+            d = _lib.DexDenoiseBatchArgs()
+            keep = self._fill_args(d.s, mu, mask, sig, out, B, spk, ref, sty, sty_lengths, False)      # (n_steps = B sizes the workspace: a row per utterance)
+            d.x_dev = x.data_ptr()
+            d.sigma_dev = sig.data_ptr()
+            self._check(self.lib.dex_denoise_batch(self.h, C.byref(d), stream(self.device)))
+            self._keep = keep + [x, sig]
+            return out
+
     def taps(self) -> Dict[str, torch.Tensor]:
         """Named intermediates of the last denoise_once call, each [rows, C] (channels-last)."""
         out = {}

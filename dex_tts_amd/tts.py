@@ -69,7 +69,7 @@ class _TTSBase(nn.Module):
             raise ValueError(f"every y_length < out_size = {out_size} < y.shape[-1] = {Ty}: the reference's y_cut_mask "
                              "(sequence_mask(y_cut_lengths)) is narrower than y_cut and does not broadcast (tts.py:138,149)")
 
-    def _loss_tail(self, mu_x, logw, x_lengths, y, y_lengths, out_size, offsets, dex, spk, rnd_normal, eps):
+    def _loss_tail(self, mu_x, logw, x_lengths, y, y_lengths, out_size, offsets, dex, spk, rnd_normal, eps, batched=False):
         """DEX tts.py:94-153 (GeDEX :65-122) after the text encoder: MAS -> durations -> cut -> mu_y -> dur / prior / EDM losses."""
         dur = align.mas_durations(mu_x, x_lengths, y, y_lengths)                             # :95-108
         if out_size is not None and out_size < y.shape[-1]:                                  # :116-138
@@ -81,7 +81,8 @@ class _TTSBase(nn.Module):
             y_c = y.to(torch.float32)
         dur_loss, prior_loss = align.dur_prior_losses(logw, dur, x_lengths, y_c, mu_y, cut_lengths)   # :111-113, :150-151
         self.decoder._bind_owner()                                                            # Diffusion.forward(infer=False) with the draws
-        diff_loss = self.decoder.loss_fn(self.decoder.precond_model, y_c, y_mask, mu_y, *dex, spk=spk, rnd_normal=rnd_normal, eps=eps)
+        diff_loss = self.decoder.loss_fn(self.decoder.precond_model, y_c, y_mask, mu_y, *dex, spk=spk, rnd_normal=rnd_normal, eps=eps,
+                                         batched=batched)
         return dur_loss, prior_loss, diff_loss
 
     def compute_loss(self, *a, **k):
@@ -115,15 +116,18 @@ class GeDEXTTS(_TTSBase):
         return mu_y[:, :, :y_max_length], dec_out[:, :, :y_max_length], attn[:, :, :y_max_length]                             # :50,53,55
 
     @torch.no_grad()
-    def loss_value(self, x, x_lengths, y, y_lengths, spk=None, out_size=None, mask_ratio=0, *, offsets=None, rnd_normal=None, eps=None):
+    def loss_value(self, x, x_lengths, y, y_lengths, spk=None, out_size=None, mask_ratio=0, *, offsets=None, rnd_normal=None, eps=None,
+                   batched=False):
         """GeDEX-TTS/model/tts.py:57-121 (compute_loss) in eval mode -> (dur_loss, prior_loss, diff_loss), 0-d device tensors.
         ``offsets`` (host [B]) replace the cut's ``random`` draws, ``rnd_normal`` [B,1,1] / ``eps`` [B,F,S] the EDM loss's device
-        draws; without them the draws happen where the reference makes them."""
+        draws; without them the draws happen where the reference makes them.  ``batched=True``: the EDM loss evaluates the score
+        network ONCE for the whole batch at its B noise levels (dex_tts_amd/edm.py) instead of B times at B = 1; ``dur`` and ``prior``
+        keep their bits, ``diff`` agrees to the kernels' single-call bound."""
         self._loss_checks((x, y, spk), x_lengths, y, y_lengths, out_size, mask_ratio)
         if self.n_spks > 1:
             spk = self.spk_emb(spk)                                                          # tts.py:60-61
         mu_x, logw, _ = self.encoder(x, x_lengths, spk=spk)                                   # :64
-        return self._loss_tail(mu_x, logw, x_lengths, y, y_lengths, out_size, offsets, (), spk, rnd_normal, eps)
+        return self._loss_tail(mu_x, logw, x_lengths, y, y_lengths, out_size, offsets, (), spk, rnd_normal, eps, batched)
 
 
 class DeXTTS(_TTSBase):
@@ -155,11 +159,12 @@ class DeXTTS(_TTSBase):
 
     @torch.no_grad()
     def loss_value(self, x, x_lengths, y, y_lengths, ref, ref_lengths, sty, sty_lengths, lf0, lf0_lengths, spk=None, out_size=None,
-                   mask_ratio=0, *, offsets=None, rnd_normal=None, eps=None):
+                   mask_ratio=0, *, offsets=None, rnd_normal=None, eps=None, batched=False):
         """DEX-TTS/model/tts.py:86-153 (compute_loss) in eval mode -> (dur_loss, prior_loss, diff_loss, vq_loss), 0-d device
-        tensors.  ``offsets`` / ``rnd_normal`` / ``eps`` inject the draws as in GeDEXTTS.loss_value."""
+        tensors.  ``offsets`` / ``rnd_normal`` / ``eps`` inject the draws and ``batched`` picks the one-call EDM loss as in
+        GeDEXTTS.loss_value."""
         self._loss_checks((x, y, ref, sty, lf0, spk), x_lengths, y, y_lengths, out_size, mask_ratio)
         ref_skips, sty_dec, sty_enc, vq_loss = self.style(ref, ref_lengths, sty, sty_lengths, lf0, lf0_lengths, return_vq_loss=True)  # :78-91
         mu_x, logw, _ = self.encoder(x, x_lengths, sty_enc, spk=None)                                                                # :93
         dex = (ref_skips, ref_lengths, sty_dec, sty_lengths)
-        return self._loss_tail(mu_x, logw, x_lengths, y, y_lengths, out_size, offsets, dex, spk, rnd_normal, eps) + (vq_loss,)
+        return self._loss_tail(mu_x, logw, x_lengths, y, y_lengths, out_size, offsets, dex, spk, rnd_normal, eps, batched) + (vq_loss,)

@@ -5,7 +5,8 @@
  *   GeDEX-TTS/model/diffusion.py:220-229, DEX-TTS/model/diffusion.py:250-259
  *   -> ablation_sampler (euler|heun, any alpha; discretization vp/ve/iddpm/edm, schedule vp/ve/linear, scaling vp/none,
  *      range overrides, churn)                    GeDEX-TTS/model/edm.py:109-216 (DEX :104-211)
- *   -> EDMPrecond.forward                          model/edm.py:88-98
+ *   -> EDMPrecond.forward                          model/edm.py:88-98   (one noise level for the batch inside the sampler and in
+ *                                                  dex_denoise_once; one per utterance, as EDMLoss draws them, in dex_denoise_batch)
  *   -> DiffusionDenoiser.forward (+DiTMask, TV/TIV adaptors)
  *                                                  GeDEX diffusion.py:168-207, DEX :190-236, model/dit.py:485-525,
  *                                                  DEX-TTS/model/ref_encoder.py:142-179,255-273
@@ -13,7 +14,7 @@
  *
  * Conventions: every pointer named *_dev is a DEVICE pointer (HBM) to contiguous fp32 unless stated;
  * all work is enqueued asynchronously on the caller's HIP stream; the library never synchronises the
- * stream inside dex_sample/dex_denoise_once.  Functions return 0 on success and a negative DexStatus
+ * stream inside dex_sample/dex_denoise_once/dex_denoise_batch.  Functions return 0 on success and a negative DexStatus
  * otherwise; nothing throws across the ABI; dex_last_error() gives the message.
  * Ownership: the caller owns inputs, outputs and the workspace; the library owns the context, its
  * packed weight copies (hipMalloc at dex_ctx_finalize) and captured hipGraphs.
@@ -135,6 +136,20 @@ typedef struct {
     const float* x_dev;         /* [B,80,T] */
 } DexDenoiseArgs;
 
+/* EDMPrecond.forward with a noise level PER UTTERANCE (edm.py:89 sigma.reshape(-1, 1, 1); what EDMLoss.forward calls, edm.py:31-68):
+ *     out_dev[b] = c_skip(sigma_b) x_b + c_out(sigma_b) F(c_in(sigma_b) x_b, mask_b, mu_b, ln(sigma_b) / 4, ...)
+ * in ONE network evaluation: asynchronous, sigma_dev is never read by the host, nothing synchronises, nothing is allocated.  The
+ * conditioning tables hold one row per utterance, so the workspace is dex_workspace_bytes(ctx, B, T, Tr, Ts, n_evals = B).
+ * Refused with DEX_ERR_ARG before anything is enqueued: a null x_dev / sigma_dev, B < 1, the shapes dex_denoise_once refuses, and
+ * use_graph = 1 (this call is not captured).  The VALUES of sigma_dev are the caller's business, as in the reference: a level that
+ * is not positive and finite gives NaN / inf rows, no error.  Taps, profile rows and dex_call_status* treat it as "the LAST call"
+ * like dex_denoise_once (the "mlp" and "vit.t_embedder" taps have B rows). */
+typedef struct {
+    DexSampleArgs s;            /* as in DexDenoiseArgs: z_dev, n_steps, tables, sigmas_dev, solver, churn fields ignored */
+    const float* x_dev;         /* [B,80,T] */
+    const float* sigma_dev;     /* [B] fp32, DEVICE memory: utterance b's noise level (edm.py:89 sigma.reshape(-1,1,1)) */
+} DexDenoiseBatchArgs;
+
 int  dex_ctx_create(const DexConfig* cfg, DexCtx** out);
 void dex_ctx_destroy(DexCtx* ctx);
 const char* dex_last_error(const DexCtx* ctx);
@@ -159,17 +174,18 @@ int  dex_ctx_load_weight_async(DexCtx* ctx, const char* key, const float* w_dev,
 int  dex_ctx_finalize(DexCtx* ctx, dex_stream_t stream);
 int  dex_ctx_set_precision(DexCtx* ctx, int precision /* DexPrecision */);
 
-/* n_evals = number of network evaluations of the run: dex_num_evals(n_steps, solver). */
+/* n_evals = number of network evaluations of the run: dex_num_evals(n_steps, solver); for dex_denoise_batch: B. */
 size_t dex_workspace_bytes(const DexCtx* ctx, int B, int T, int Tr, int Ts, int n_evals);
 /* Euler: n_steps.  Heun (edm.py:202-214): 2*n_steps - 1 (no corrector on the last step). */
 int  dex_num_evals(int n_steps, int solver /* DexSolver */);
 int  dex_sample(DexCtx* ctx, const DexSampleArgs* args, dex_stream_t stream);
 int  dex_denoise_once(DexCtx* ctx, const DexDenoiseArgs* args, dex_stream_t stream);
+int  dex_denoise_batch(DexCtx* ctx, const DexDenoiseBatchArgs* args, dex_stream_t stream);
 
 /* EDM rho=7 schedule in fp32 on the host (edm.py:157): writes n_steps+1 values, last one 0. */
 int  dex_edm_sigmas(int n_steps, float* sigmas_host);
 
-/* Debug taps: copy a named intermediate of the LAST dex_denoise_once/dex_sample call out of the
+/* Debug taps: copy a named intermediate of the LAST dex_denoise_once/dex_denoise_batch/dex_sample call out of the
  * workspace (device->device, async on stream).  Names: see dex_tap_name(i).  Layout NHWC fp32. */
 int  dex_num_taps(const DexCtx* ctx);
 const char* dex_tap_name(const DexCtx* ctx, int i);
