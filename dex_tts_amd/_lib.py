@@ -14,7 +14,7 @@ DEX_ERR_HANDOFF, DEX_ERR_HANDOFF_XCD = -5, -6        # include/dex_amd.h: dex_ca
 DEX_PENDING = 1                                   # dex_call_status_poll(wait = 0)
 VARIANT = {"gedex": 0, "dex": 1}
 PRECISION = {"fp32": 0, "bf16": 1, "fp16": 2, "fp16x2": 3}
-SOLVER = {"euler": 0, "heun": 1}
+SOLVER = {"euler": 0, "heun": 1, "dpmpp_2m": 2}
 
 
 class DexConfig(C.Structure):

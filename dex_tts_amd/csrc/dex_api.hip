@@ -863,6 +863,9 @@ struct Update {
     const float* gtab = nullptr;        // ablation tables: the general update (final_kernel<true>) with these rows, ...
     const float* xstate = nullptr;      // ... the state x of this evaluation (Runner::xcur is its network input x / s) ...
     float* xin_next = nullptr;          // ... and where the next evaluation's input goes (scaled tables), or null
+    const float* mtab = nullptr;        // multistep tables: x_next = a x + b D + c D_prev (final_kernel<FinalMP>) with these rows, ...
+    const float* dprev_in = nullptr;    // ... the D of the evaluation before (null on the first: nothing is read) ...
+    float* dprev_out = nullptr;         // ... and where this evaluation's D goes
 };
 
 struct Runner {
@@ -1606,8 +1609,11 @@ struct Runner {
         f.poison = P.xflag ? reinterpret_cast<const int*>(P.xflag + (P.xflag_bytes - sizeof(int)) / sizeof(unsigned)) : nullptr;
         f.mode = up.mode; f.htab = up.htab; f.dbuf = P.dbuf; f.xhat = P.xbuf;
         f.gtab = up.gtab; f.xstate = up.xstate; f.xin_next = up.xin_next;
+        FinalMP fm{};
+        static_cast<FinalP&>(fm) = f;
+        fm.mtab = up.mtab; fm.dprev_in = up.dprev_in; fm.dprev_out = up.dprev_out;
         run("final_conv_euler", 14.0 * 80 * P.d.T * c.dim * B, 80.0 * P.d.T * ((hfb ? 2.0 : 4.0) * c.dim + 12.0) * B,
-            [&] { if (up.gtab) launch_final_general(f, st); else launch_final(f, st); });
+            [&] { if (up.mtab) launch_final_multistep(fm, st); else if (up.gtab) launch_final_general(f, st); else launch_final(f, st); });
     }
 
     // conditioning tables for every Euler step (depend only on sigma_i)
@@ -1733,15 +1739,19 @@ struct Eval {                   // one network evaluation of a sampler call
 //     / alpha, Euler or Heun): evaluation e reads row e everywhere, cond_prep its sigma, the update (final_kernel<true>) its
 //     coefficients.  The x_hat update of a step runs only under DEX_TABLES_CHURN, and with DEX_TABLES_SCALED the network reads
 //     x / s from P.xin, which the kernel before it writes (init, x_hat update or the last update).
+//   Multistep (DPM-Solver++(2M), tables only, neither scaled nor churned): n evaluations, each x_next = a x + b D + c D_prev in
+//     place on P.xbuf from row e's (a, b, c); D_prev lives in P.dbuf (Heun's slope buffer, which make_plan always allocates),
+//     written by every evaluation and read by every one but the first.
 struct SamplerKind {
     const DexSamplerTables* tb;
-    bool heun, churn, scaled;
+    bool heun, multistep, churn, scaled;
     int n, E;
     explicit SamplerKind(const DexSampleArgs* a)
-        : tb(a->tables), heun(a->solver == DEX_SOLVER_HEUN), churn(tb ? (tb->flags & DEX_TABLES_CHURN) != 0 : a->S_churn > 0.f),
+        : tb(a->tables), heun(a->solver == DEX_SOLVER_HEUN), multistep(a->solver == DEX_SOLVER_DPMPP_2M), churn(tb ? (tb->flags & DEX_TABLES_CHURN) != 0 : a->S_churn > 0.f),
           scaled(tb && (tb->flags & DEX_TABLES_SCALED) != 0), n(a->n_steps), E(tb ? tb->n_rows : dex_num_evals(a->n_steps, a->solver)) {}
 
     Eval eval(const Plan& P, int e) const {
+        if (multistep) return {P.xbuf, P.xbuf, {0, nullptr, nullptr, nullptr, nullptr, tb->coef_dev, e == 0 ? nullptr : P.dbuf, P.dbuf}, -1};
         const int i = heun ? e / 2 : e;                             // the step of evaluation e
         const bool corrector = heun && (e & 1);                     // (then a next step exists: i < n - 1)
         const bool predictor = heun && !corrector && i < n - 1;     // a corrector follows
@@ -1913,7 +1923,13 @@ int dex_denoise_batch(DexCtx* x, const DexDenoiseBatchArgs* da, dex_stream_t str
 int dex_sample(DexCtx* x, const DexSampleArgs* a, dex_stream_t stream) {
     int rc = validate(x, a, true);
     if (rc) return rc;
-    if (a->solver != DEX_SOLVER_EULER && a->solver != DEX_SOLVER_HEUN) return x->fail(DEX_ERR_ARG, "solver must be DEX_SOLVER_EULER or DEX_SOLVER_HEUN (edm.py:107)");
+    if (a->solver != DEX_SOLVER_EULER && a->solver != DEX_SOLVER_HEUN && a->solver != DEX_SOLVER_DPMPP_2M)
+        return x->fail(DEX_ERR_ARG, "solver must be DEX_SOLVER_EULER, DEX_SOLVER_HEUN (edm.py:107) or DEX_SOLVER_DPMPP_2M");
+    if (a->solver == DEX_SOLVER_DPMPP_2M) {
+        if (!a->tables) return x->fail(DEX_ERR_ARG, "DEX_SOLVER_DPMPP_2M runs from DexSampleArgs.tables only (rows [sigma, 1, a, b, c, 0, 0, 0])");
+        if (a->tables->flags & (DEX_TABLES_SCALED | DEX_TABLES_CHURN))
+            return x->fail(DEX_ERR_ARG, "DEX_SOLVER_DPMPP_2M takes neither DEX_TABLES_SCALED nor DEX_TABLES_CHURN (flags 0x%x): it runs in the (x, sigma) frame without fresh noise", a->tables->flags);
+    }
     const CallScope scope(x);
     hipStream_t st = (hipStream_t)stream;
     {

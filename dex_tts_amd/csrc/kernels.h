@@ -219,6 +219,14 @@ struct FinalGP : FinalP {
     const float* gtab; const float* xstate; float* xin_next;
 };
 void launch_final_general(const FinalGP& p, hipStream_t st);
+// The two-step multistep update (DPM-Solver++(2M), final_kernel<FinalMP>; the other two kernels are untouched): row `step` of mtab is
+// [sigma, 1, a, b, c, 0, 0, 0] and xnext = a xcur + b D + c D_prev, every product and sum rounded on its own.  dprev_in: the denoised
+// output of the evaluation before (NULL on the first one: the buffer is uninitialised memory and is not read); dprev_out (optional):
+// where D goes for the next one.  The two may be the same buffer: an element is read and written by the same thread.
+struct FinalMP : FinalP {
+    const float* mtab; const float* dprev_in; float* dprev_out;
+};
+void launch_final_multistep(const FinalMP& p, hipStream_t st);
 // ablation_sampler with tables: x_hat = r x + k noise (edm.py:196; rk = the step's [r, k]; noise NULL = zero), in place, rounded
 // like the reference's mul / mul / add; xin (optional) = x_hat / *s, the network's input
 void launch_ablation_churn(float* x, const float* noise, const float* rk, float* xin, const float* s, long n, hipStream_t st);

@@ -471,11 +471,14 @@ void launch_gn_apply(const GnApplyP& p, hipStream_t st) {
 // A block owns FIN_U groups of 32 pixels per pass and issues every load of the pass - activations, mask, sampler state -
 // before the first use (the first version walked its pixels one dependent load at a time: 125 us for 168 MB at B=32);
 // the per-channel GroupNorm coefficient and final_conv weight live in registers for the block's life; Mish on packed pairs.
-// final_kernel<FinalP>: the EDM sampler's update; final_kernel<FinalGP>: the general update of ablation_sampler's tables (GEN).
+// final_kernel<FinalP>: the EDM sampler's update; final_kernel<FinalGP>: the general update of ablation_sampler's tables (GEN);
+// final_kernel<FinalMP>: the two-step multistep update x_next = a x + b D + c D_prev (MS), whose D_prev load rides in the same
+// early load group as the sampler state.
 constexpr int FIN_U = 4;
 template <typename PT>
 __global__ __launch_bounds__(256) void final_kernel(const PT p) {
     constexpr bool GEN = std::is_same<PT, FinalGP>::value;
+    constexpr bool MS = std::is_same<PT, FinalMP>::value;
     __shared__ float smean[32], srstd[32];
     const int tid = threadIdx.x, b = blockIdx.y;
     const int cpg = p.C / p.groups;
@@ -516,10 +519,15 @@ __global__ __launch_bounds__(256) void final_kernel(const PT p) {
         gA = g[2]; gB = g[3]; gh = g[4]; gah = g[5]; gw0 = g[6]; gw1 = g[7];
         if (p.xin_next) gsn = g[8 + 1];              // s of the next evaluation (there is one whenever xin_next is set)
     }
+    float ma = 0.f, mb = 0.f, mc = 0.f;
+    if constexpr (MS) {                              // this evaluation's row [sigma, 1, a, b, c, 0, 0, 0]
+        const float* g = p.mtab + (long)step * 8;
+        ma = g[2]; mb = g[3]; mc = g[4];
+    }
     const long stride = (long)gridDim.x * 32 * FIN_U;
     for (long base = (long)blockIdx.x * 32 * FIN_U; base < p.npix; base += stride) {
         uint4 raw[FIN_U][2][2];                      // [pass][64-channel block][fp32: two halves; bf16: [0] only]
-        float mk[FIN_U], xc[FIN_U], xa[FIN_U], xd[FIN_U], xs[FIN_U];
+        float mk[FIN_U], xc[FIN_U], xa[FIN_U], xd[FIN_U], xs[FIN_U], xp[FIN_U];
 #pragma unroll
         for (int u = 0; u < FIN_U; ++u) {
             const long pr = base + u * 32 + (tid >> 3);
@@ -527,8 +535,12 @@ __global__ __launch_bounds__(256) void final_kernel(const PT p) {
             const long o = (long)b * p.npix + px;
             mk[u] = mrow[(int)(px % p.W)];
             xc[u] = p.xcur[o];
-            xa[u] = p.mode == 2 ? p.xhat[o] : 0.f;
-            xd[u] = p.mode == 2 ? p.dbuf[o] : 0.f;
+            if constexpr (MS) {
+                xp[u] = p.dprev_in ? p.dprev_in[o] : 0.f;        // (no history on the first evaluation: the buffer is not read)
+            } else {
+                xa[u] = p.mode == 2 ? p.xhat[o] : 0.f;
+                xd[u] = p.mode == 2 ? p.dbuf[o] : 0.f;
+            }
             if constexpr (GEN) xs[u] = p.xstate[o];
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
@@ -573,7 +585,11 @@ __global__ __launch_bounds__(256) void final_kernel(const PT p) {
                 // x_next multiplied by h / (2 sigma') ~ 1e2 (measured before: 3e-4 against the oracle at n = 4, now ~1e-5).
                 const float D = poisoned ? __builtin_nanf("") : __fadd_rn(__fmul_rn(c_skip, xc[u]), __fmul_rn(c_out, f));
                 if (p.denoised) p.denoised[o] = D;
-                if constexpr (GEN) {
+                if constexpr (MS) {
+                    // DPM-Solver++(2M) in the (x, sigma) frame: the exponential integrator's step with the previous evaluation's D
+                    if (p.dprev_out) p.dprev_out[o] = D;
+                    p.xnext[o] = __fadd_rn(__fadd_rn(__fmul_rn(ma, xc[u]), __fmul_rn(mb, D)), __fmul_rn(mc, xp[u]));
+                } else if constexpr (GEN) {
                     // edm.py:202-214 for any schedule / scaling / alpha: d = A x - Bc D on the state, then the solver's update
                     const float d = __fsub_rn(__fmul_rn(gA, xs[u]), __fmul_rn(gB, D));
                     float xn;
@@ -672,6 +688,9 @@ __global__ void ablation_churn_kernel(float* x, const float* noise, const float*
         x[i] = v;
         if (xin) xin[i] = __fdiv_rn(v, sv);
     }
+}
+void launch_final_multistep(const FinalMP& p, hipStream_t st) {
+    hipLaunchKernelGGL(final_kernel<FinalMP>, dim3((unsigned)final_blocks(p), p.B), dim3(256), 0, st, p);
 }
 void launch_ablation_churn(float* x, const float* noise, const float* rk, float* xin, const float* s, long n, hipStream_t st) {
     long blocks = (n + 255) / 256; if (blocks > 2048) blocks = 2048;

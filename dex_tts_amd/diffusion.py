@@ -131,7 +131,7 @@ class Diffusion(nn.Module):
         self._bind_owner()
         self.precision = "fp32"
         self.use_graph = False
-        self.solver = "euler"                    # the reference wires 'euler' (diffusion.py:216); 'heun' = edm.py:207-214
+        self.solver = "euler"                    # the reference wires 'euler' (diffusion.py:216); 'heun' = edm.py:207-214; 'dpmpp_2m' = DPM-Solver++(2M)
         self.rng_parity = True                   # replay the reference's per-step randn_like draws (edm.py:196)
         # ablation_sampler's stochastic settings (edm.py:109,194-196); the reference wires the defaults (S_churn = 0)
         self.S_churn, self.S_min, self.S_max, self.S_noise = 0.0, 0.0, float("inf"), 1.0
@@ -198,11 +198,12 @@ class Diffusion(nn.Module):
 
     def _tables(self, steps):
         """The general sampler's tables for this module's settings, or None when they are the EDM sampler the reference wires
-        (edm / linear / none, alpha = 1, the default range): that one keeps its own path."""
+        (edm / linear / none, alpha = 1, the default range): that one keeps its own path.  'dpmpp_2m' always runs from tables."""
         g = lambda k, d: getattr(self, k, d)           # (modules pickled before these attributes existed)
         disc, sched, scal, alpha = g("discretization", "edm"), g("schedule", "linear"), g("scaling", "none"), g("alpha", 1)
         smin, smax, rho = g("sigma_min", None), g("sigma_max", None), g("rho", 7)
-        if (disc, sched, scal) == ("edm", "linear", "none") and alpha == 1 and smin is None and smax is None and rho == 7:
+        if (disc, sched, scal) == ("edm", "linear", "none") and alpha == 1 and smin is None and smax is None and rho == 7 \
+                and self.solver != "dpmpp_2m":
             return None
         from .edm import ablation_tables
         return ablation_tables(int(steps), self.solver, disc, sched, scal, sigma_min=smin, sigma_max=smax, rho=rho,

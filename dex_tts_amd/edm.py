@@ -107,6 +107,11 @@ class EDMLoss(nn.Module):
 # arguments into fp32 tables once (ablation_tables: cached per argument tuple); the device runs the sampler from them (dex_sample with
 # DexSampleArgs.tables, include/dex_amd.h).  The scalar arithmetic below repeats the reference's: torch CPU fp32 operations on 0-dim
 # tensors, one rounding per operation, with Python / numpy float64 scalars exactly where the reference has them.
+#
+# solver 'dpmpp_2m' is NOT in the reference: DPM-Solver++(2M) (Lu et al. 2022, arXiv:2211.01095, algorithm 2 with the data
+# prediction model), a two-step multistep exponential integrator in the (x, sigma) frame that reuses the previous step's denoised
+# output - second order at ONE network evaluation per step.  It runs on the noise levels of any discretisation; its rows are
+# computed in float64 from the fp32 levels and rounded once (_dpmpp_2m_rows).
 
 TABLES_SCALED, TABLES_CHURN = 1, 2        # DEX_TABLES_* of include/dex_amd.h
 
@@ -142,8 +147,8 @@ def _iddpm_levels(M, C_1, C_2):
 
 class AblationTables:
     """The fp32 tables of one ablation_sampler configuration, laid out as DexSamplerTables: ``sigma`` [E + 1] (the noise level of
-    every network evaluation, then 0; E = n_steps for Euler, 2 n_steps - 1 for Heun), ``coef`` [E, 8] (sigma, s, A, Bc, h, alpha h,
-    w0, w1), ``step`` [n_steps, 4] (r, k, c0 on row 0, 0).  ``flags``: DEX_TABLES_*; ``noise``: some step's k is not 0, so the
+    every network evaluation, then 0; E = n_steps for Euler and DPM-Solver++(2M), 2 n_steps - 1 for Heun), ``coef`` [E, 8] (sigma,
+    s, A, Bc, h, alpha h, w0, w1; for 'dpmpp_2m': sigma, 1, a, b, c, 0, 0, 0), ``step`` [n_steps, 4] (r, k, c0 on row 0, 0).  ``flags``: DEX_TABLES_*; ``noise``: some step's k is not 0, so the
     per-step randn_like draws change the result."""
 
     def __init__(self, solver, n_steps, sigma, coef, step, flags, noise):
@@ -174,6 +179,29 @@ class AblationTables:
         return self._dev[key]
 
 
+def _dpmpp_2m_rows(sigma):
+    """The (a, b, c) of x_{i+1} = a x_i + b D_i + c D_{i-1} for the fp32 noise levels sigma_0 > ... > sigma_{n-1} (> 0; sigma_n = 0),
+    in float64:  h_i = ln(sigma_i / sigma_{i+1}), r_i = h_{i-1} / h_i, e_i = -expm1(-h_i);  a = sigma_{i+1} / sigma_i,
+    b = e_i (1 + 1 / (2 r_i)), c = -e_i / (2 r_i);  first row: first order (b = e_0, c = 0);  last row (sigma -> 0): (0, 1, 0)."""
+    sg = np.asarray(sigma, dtype=np.float64)
+    n = len(sg)
+    if not (np.all(sg > 0) and np.all(np.diff(sg) < 0)):
+        raise ValueError("dpmpp_2m needs strictly decreasing positive noise levels (this discretisation repeats one at this num_steps)")
+    rows, h_prev = [], None
+    for i in range(n - 1):
+        h = np.log(sg[i] / sg[i + 1])
+        e = -np.expm1(-h)
+        if i == 0:
+            b, c = e, 0.0
+        else:
+            r = h_prev / h
+            b, c = e * (1 + 1 / (2 * r)), -e / (2 * r)
+        rows.append((sg[i + 1] / sg[i], b, c))
+        h_prev = h
+    rows.append((0.0, 1.0, 0.0))
+    return rows
+
+
 @functools.lru_cache(maxsize=64, typed=True)
 def ablation_tables(num_steps, solver, discretization, schedule, scaling, sigma_min=None, sigma_max=None, rho=7, epsilon_s=1e-3,
                     C_1=0.001, C_2=0.008, M=1000, alpha=1, S_churn=0, S_min=0, S_max=float("inf"), S_noise=1) -> AblationTables:
@@ -184,9 +212,13 @@ def ablation_tables(num_steps, solver, discretization, schedule, scaling, sigma_
     alpha h_i for its corrector): sigma(t), s(t), A = sigma'(t)/sigma(t) + s'(t)/s(t), Bc = sigma'(t) s(t)/sigma(t), h_i = t_{i+1} -
     t_hat_i, alpha h_i, w0 = 1 - 1/(2 alpha), w1 = 1/(2 alpha).  Row i of ``step``: r = s(t_hat)/s(t_cur) and k = (max(sigma(t_hat)^2
     - sigma(t_cur)^2, 0))^(1/2) s(t_hat) S_noise of x_hat = r x_cur + k randn_like(x_cur) (edm.py:196), and on row 0 c0 = sigma(t_0)
-    s(t_0) of x_0 = latents c0.  The network's range is the library EDMPrecond's, sigma_min = 0 and sigma_max = inf (edm.py:77-78)."""
-    if solver not in ("euler", "heun"):
-        raise ValueError(f"solver must be 'euler' or 'heun', got {solver!r}")
+    s(t_0) of x_0 = latents c0.  The network's range is the library EDMPrecond's, sigma_min = 0 and sigma_max = inf (edm.py:77-78).
+
+    ``solver='dpmpp_2m'`` (not in the reference): any discretisation and range - only the noise levels matter - with schedule
+    'linear', scaling 'none' and S_churn = 0 (the exponential integrator does not depend on the schedule, and fresh noise would
+    invalidate its history); ``alpha`` is ignored.  Row i of ``coef`` is [sigma_i, 1, a, b, c, 0, 0, 0] (_dpmpp_2m_rows)."""
+    if solver not in ("euler", "heun", "dpmpp_2m"):
+        raise ValueError(f"solver must be 'euler', 'heun' or 'dpmpp_2m', got {solver!r}")
     if discretization not in ("vp", "ve", "iddpm", "edm"):
         raise ValueError(f"discretization must be 'vp', 've', 'iddpm' or 'edm', got {discretization!r}")
     if schedule not in ("vp", "ve", "linear"):
@@ -196,6 +228,12 @@ def ablation_tables(num_steps, solver, discretization, schedule, scaling, sigma_
     n = int(num_steps)
     if n < 2:
         raise ValueError("num_steps must be >= 2 (the reference divides by num_steps - 1)")
+    if solver == "dpmpp_2m":
+        if schedule != "linear" or scaling != "none":
+            raise ValueError("dpmpp_2m runs in the (x, sigma) frame: schedule must be 'linear' and scaling 'none' (the exponential "
+                             f"integrator is the same under every schedule), got {schedule!r} / {scaling!r}")
+        if S_churn != 0:
+            raise ValueError("dpmpp_2m is a multistep solver: S_churn must be 0 (fresh noise invalidates the previous step's output)")
 
     # the range: the discretisation's defaults, clamped to what the network supports (edm.py:124-134)
     if sigma_min is None:
@@ -264,6 +302,14 @@ def ablation_tables(num_steps, solver, discretization, schedule, scaling, sigma_
 
     # time steps t_i = t(sigma_i) (the library's EDMPrecond.round_sigma is the identity), t_N = 0 (edm.py:184-185)
     t_steps = torch.cat([sigma_inv(sigma_steps), torch.zeros(1)])
+    if solver == "dpmpp_2m":
+        sg = t_steps[:n].to(torch.float32)                                    # (linear schedule: t IS sigma)
+        coef = torch.zeros(n, 8, dtype=torch.float32)
+        coef[:, 0], coef[:, 1] = sg, 1
+        coef[:, 2:5] = torch.tensor(_dpmpp_2m_rows(sg.numpy()), dtype=torch.float64).to(torch.float32)
+        step = torch.zeros(n, 4, dtype=torch.float32)
+        step[:, 0], step[0, 2] = 1, sg[0]
+        return AblationTables.from_arrays(solver, n, coef, step, False)
     heun = solver == "heun"
     w0, w1 = (1 - 1 / (2 * alpha), 1 / (2 * alpha)) if heun else (0.5, 0.5)
 

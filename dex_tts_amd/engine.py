@@ -122,7 +122,7 @@ class ScoreNetEngine:
                    solver="euler", noise=None, churn=None):
         """Fill the C argument block from inputs in the form ``_inputs`` returns; the list it returns keeps them alive."""
         if solver not in _lib.SOLVER:
-            raise ValueError(f"solver must be 'euler' or 'heun' (edm.py:107), got {solver!r}")
+            raise ValueError(f"solver must be 'euler', 'heun' (edm.py:107) or 'dpmpp_2m', got {solver!r}")
         B, F, T = mu.shape
         if F != 80:
             raise ValueError("mel dimension must be 80")
@@ -209,7 +209,8 @@ class ScoreNetEngine:
     def sample(self, z, mask, mu, n_steps, spk=None, ref=None, sty=None, sty_lengths=None, use_graph=False,
                solver="euler", noise=None, S_churn=0.0, S_min=0.0, S_max=float("inf"), S_noise=1.0, tables=None):
         """ablation_sampler(solver, edm, linear, none) for latent z — edm.py:109-216.  ``solver`` is 'euler' (what
-        Diffusion wires, diffusion.py:216) or 'heun' (edm.py:207-214; 2n-1 network evaluations).  Asynchronous.
+        Diffusion wires, diffusion.py:216), 'heun' (edm.py:207-214; 2n-1 network evaluations) or 'dpmpp_2m' (DPM-Solver++(2M), not in
+        the reference: second order at n evaluations; it runs from ``tables`` only).  Asynchronous.
         ``use_graph``: the whole call (conditioning tables + every network evaluation) is one cached hipGraph.
         Small grids (B x row tiles <= 64: the cluster form of the DiT block) have their in-launch hand-offs checked: asynchronously by
         default (``check_handoffs = "deferred"``: the verdict surfaces at the next call or at ``status()``), or before the mel is handed out

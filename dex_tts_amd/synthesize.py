@@ -14,7 +14,7 @@ The text encoder / duration model / vocoder are not part
 array (e.g. dumped from the reference, or synthetic).  CLI:
 
     python -m dex_tts_amd.synthesize --config <reference base.yaml> --mu mu_y.npy [--lengths 210,180] [--ckpt model.pth]
-           [--n_timesteps 50] [--temperature 1.5] [--seed 100] [--precision fp32|bf16|fp16] --out mel.npy
+           [--n_timesteps 50] [--temperature 1.5] [--seed 100] [--precision fp32|bf16|fp16] [--solver euler|heun|dpmpp_2m] --out mel.npy
            [--wav out.wav [--griffin_iters 60]]        (Griffin-Lim waveforms of the mels, dex_tts_amd.griffin_lim)
 """
 from __future__ import annotations
@@ -130,6 +130,8 @@ def main(argv=None):
     ap.add_argument("--temperature", type=float, default=1.5)
     ap.add_argument("--seed", type=int, default=100)
     ap.add_argument("--precision", default="fp32")
+    ap.add_argument("--solver", default="euler", choices=["euler", "heun", "dpmpp_2m"],
+                    help="euler: what the reference wires; heun: 2n - 1 network evaluations; dpmpp_2m: second order at n evaluations")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--out", required=True)
     ap.add_argument("--wav", default=None, help="also write each mel as a Griffin-Lim waveform (no vocoder weights needed): OUT.wav for "
@@ -156,6 +158,7 @@ def main(argv=None):
         model.load_state_dict(sd, strict=True)
     model = model.to(a.device).eval()
     model.precision = a.precision
+    model.solver = a.solver
     mu = torch.from_numpy(np.load(a.mu).astype(np.float32))
     if mu.dim() == 2:
         mu = mu[None]

@@ -51,8 +51,9 @@ typedef enum { DEX_PREC_FP32 = 0, DEX_PREC_BF16 = 1, DEX_PREC_FP16 = 2,
                DEX_PREC_FP16X2 = 3    /* fp16 operands with every weight as hi + lo (two MFMAs per product): the fast mode inside the
                                        * fp32-grade sampler bound */
 } DexPrecision;
-/* ablation_sampler's solver argument (edm.py:107). */
-typedef enum { DEX_SOLVER_EULER = 0, DEX_SOLVER_HEUN = 1 } DexSolver;
+/* ablation_sampler's solver argument (edm.py:107), and DPM-Solver++(2M): a two-step multistep solver that is not in the reference
+ * (second order at one network evaluation per step; DexSamplerTables below). */
+typedef enum { DEX_SOLVER_EULER = 0, DEX_SOLVER_HEUN = 1, DEX_SOLVER_DPMPP_2M = 2 } DexSolver;
 
 /* The general ablation_sampler (edm.py:109-216): every branch of discretization / schedule / scaling / alpha / range, as fp32 tables
  * the HOST computes in the reference's operation order (dex_tts_amd/edm.py: ablation_tables) and hands over in DEVICE memory (a
@@ -64,7 +65,14 @@ typedef enum { DEX_SOLVER_EULER = 0, DEX_SOLVER_HEUN = 1 } DexSolver;
  *     Heun corrector:     x_next = x_hat + h (w0 d_cur + w1 d')                      (edm.py:203-214)
  * every product and sum rounded on its own, like the reference's torch operations.  Each step starts from
  *     x_hat = r x_cur + k noise_i  (edm.py:196; only when DEX_TABLES_CHURN is set),   and the call from x_0 = z c0 (edm.py:189).
- * alpha needs no flag: the predictor's step alpha h and the corrector's weights are table columns. */
+ * alpha needs no flag: the predictor's step alpha h and the corrector's weights are table columns.
+ *
+ * DEX_SOLVER_DPMPP_2M runs through these tables ONLY (tables == NULL is refused, and so is either flag: the solver works in the
+ * (x, sigma) frame, s = 1, and fresh noise would invalidate its history).  n_rows = n_steps, and row e of coef_dev reads
+ *     [sigma, 1, a, b, c, 0, 0, 0]:      x_next = a x + b D + c D_prev      (every product and sum rounded on its own)
+ * with, for h_i = ln(sigma_i / sigma_{i+1}), r_i = h_{i-1} / h_i, e_i = -expm1(-h_i):  a = sigma_{i+1} / sigma_i,
+ * b = e_i (1 + 1 / (2 r_i)), c = -e_i / (2 r_i);  the first row is first order (b = e_0, c = 0: D_prev is not read), the last one
+ * (sigma -> 0) is (0, 1, 0).  sigma_dev and step_dev (c0 = sigma_0; r = 1, k = 0) keep their meaning. */
 enum {
     DEX_TABLES_SCALED = 1,  /* scaling 'vp': the network input x / s is kept in a buffer of its own (s = 1 otherwise: x_in IS x) */
     DEX_TABLES_CHURN = 2    /* some step has r != 1 or k != 0: every step begins with the x_hat update; noise_dev = [n_steps][B,80,T]
@@ -118,7 +126,7 @@ typedef struct {
     int32_t use_graph;          /* 1: the whole call (conditioning tables + every network evaluation + the final copy) is captured
                                  * once into a hipGraph, cached under (shapes, solver, precision, stream, every device pointer
                                  * above) and replayed with ONE hipGraphLaunch; needs a non-default stream */
-    int32_t solver;             /* DexSolver; 0 = Euler, what Diffusion wires (diffusion.py:216) */
+    int32_t solver;             /* DexSolver; 0 = Euler, what Diffusion wires (diffusion.py:216); DEX_SOLVER_DPMPP_2M needs `tables` */
     /* Stochastic sampler, ablation_sampler's S_churn / S_min / S_max / S_noise (edm.py:109,194-196).  Zero-initialised
      * fields = the deterministic sampler the reference wires (S_churn = 0: its per-step randn_like is multiplied by 0). */
     const float* noise_dev;     /* [n_steps][B,80,T]: step i's randn_like(x_cur) draw (the caller owns the RNG); required
@@ -176,7 +184,7 @@ int  dex_ctx_set_precision(DexCtx* ctx, int precision /* DexPrecision */);
 
 /* n_evals = number of network evaluations of the run: dex_num_evals(n_steps, solver); for dex_denoise_batch: B. */
 size_t dex_workspace_bytes(const DexCtx* ctx, int B, int T, int Tr, int Ts, int n_evals);
-/* Euler: n_steps.  Heun (edm.py:202-214): 2*n_steps - 1 (no corrector on the last step). */
+/* Euler and DPM-Solver++(2M): n_steps.  Heun (edm.py:202-214): 2*n_steps - 1 (no corrector on the last step). */
 int  dex_num_evals(int n_steps, int solver /* DexSolver */);
 int  dex_sample(DexCtx* ctx, const DexSampleArgs* args, dex_stream_t stream);
 int  dex_denoise_once(DexCtx* ctx, const DexDenoiseArgs* args, dex_stream_t stream);
