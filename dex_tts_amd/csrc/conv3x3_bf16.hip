@@ -4,13 +4,17 @@
 // A workgroup owns TH rows x 32 columns of output pixels.  The (TH+2) x 34 input patch is staged ONCE in LDS
 // as bf16 (1.6x halo overhead instead of the 9x re-gather of an im2col GEMM), with the producer's tail fused
 // into the staging:  x*mask   or   mask*(Mish(GroupNorm(x)) + time_bias)   (diffusion.py:49,67-69), so the
-// activated tensor of block1 never exists in HBM.  Two weight schedules:
-//   RESIDENT  (few workgroups, B=1): a workgroup owns a slice of NSL output channels and keeps ALL nine taps of
-//             its weights in LDS; every global load of the kernel is issued up front and the 9-tap MFMA chain
-//             runs without a single barrier — at one workgroup per CU dependent global round trips are the
-//             only cost that matters (measured: 9 streamed taps = 9 exposed round trips).
-//   STREAMED  (many workgroups, big batches): per-tap weight slices [Cout][CC] stream through a double-buffered
-//             LDS tile (small LDS footprint, 3 workgroups per CU).
+// activated tensor of block1 never exists in HBM.  Two weight schedules of the one kernel (template flag RW):
+//   STREAMED  (RW = false; every shape): per-tap weight slices [NSL][CC] travel global -> registers (a ring of RING taps in flight) ->
+//             a double-buffered LDS tile, one workgroup barrier per tap and channel chunk.  Small LDS footprint: 2 - 3 workgroups per
+//             CU at batch size, any Cin (chunks of 64 / 128), and the split-weight build's 18 taps.
+//   RESIDENT  (RW = true; Cin = 64 in one chunk, a grid of at most one round of the CUs: B = 1 at T <= 512): the workgroup keeps ALL
+//             nine taps of its NSL x 64 slice in LDS (9 x NSL padded rows behind the patch: 117 / 103 / 80 KB for the 5-row, 2-row and
+//             64 -> 128 forms).  Every global load of the workgroup - GroupNorm partials, patch, nine taps, the 1x1 shortcut slice - is
+//             requested at kernel entry, the taps are written to LDS behind the patch conversion, and ONE barrier stands between the
+//             staging and the 36-MFMA chain, which reads its fragments one K step ahead.  Same taps, K steps and MFMA per output
+//             element as the streamed forms: the same bits.  Chosen by the launcher (DEX_CONV_RESIDENT, default on) for every such
+//             launch but the ten-wave fused tail, which was no faster inside the sampler's step.
 // LDS rows are padded by 16 B so every ds_read_b128 / ds_write_b128 lane group covers 64 distinct banks.
 // Epilogue: +bias, GroupNorm partial statistics (workgroup-combined, one fp32 atomic pair per group into a
 // slot-spread buffer), fp32 channels-last store (128-B rows).
@@ -147,8 +151,8 @@ __device__ __forceinline__ void cv_res_store(const Conv3P& p, const f32x16 (&acc
 }
 
 // CC channels per chunk, output-channel slice [slice*NSL, +NSL) of COUT, TH rows (waves: TH x (NW/TH); wave = one row x NSL/(NW/TH)
-// channels).  grid.z = b * (COUT/NSL) + slice.
-template <int CC, int COUT, int NSL, int TH, bool PRO2 = false, bool RES = false, bool XB = false, int NW = 4>
+// channels).  grid.z = b * (COUT/NSL) + slice.  RW: the resident-weights schedule (Cin == CC, one chunk).
+template <int CC, int COUT, int NSL, int TH, bool PRO2 = false, bool RES = false, bool XB = false, int NW = 4, bool RW = false>
 __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
     constexpr int PW = 34, PH = TH + 2;
     constexpr int LDP = CC + 8;
@@ -166,9 +170,17 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
     // of 2: measured 16 -> 22 us at 40x256).  The 5-row one-round forms: at Cin 128 (five waves, 256 registers) the items per pass of
     // the 2-row forms; at Cin 64 (ten waves: three per SIMD, 168 registers) 1 / 2 / 3 items per pass for PRO2 / fp32 / bf16 input -
     // one pass more and the fused-tail form spills (16 - 124 B per lane), the fp32-input form of the split-weight build 16 B.
-    constexpr int NPASS = TH == 5 ? (CC == 128 ? (PRO2 ? 6 : 3) : (PRO2 ? 3 : XB ? 1 : 2))
+    // The resident forms have no weight ring to feed and every one of them fits its registers in ONE pass (the ten-wave fused tail:
+    // 132 / 142 of 168 registers for 16-bit / fp32 input, no scratch), so all their loads go out at kernel entry.
+    constexpr int NPASS = RW ? 1
+                        : TH == 5 ? (CC == 128 ? (PRO2 ? 6 : 3) : (PRO2 ? 3 : XB ? 1 : 2))
                                   : CC == 128 ? (TH == 8 ? (PRO2 ? 8 : 4) : (PRO2 ? 5 : 2)) : (PRO2 ? 3 : 1);
     constexpr int NIP = (NI + NPASS - 1) / NPASS;
+    // resident weights: all nine taps of the slice are 9 * WITEMS 16-byte items, dealt to the threads like the patch items and
+    // requested in the patch pass they are written to LDS behind (one pass: everything at kernel entry)
+    constexpr int RWI = 9 * WITEMS;
+    constexpr int RWPT = (RWI + NTHR - 1) / NTHR;
+    constexpr int RWB = (RWPT + NPASS - 1) / NPASS;
 #ifdef DEX_LP_WSPLIT
     // split weights: the nine taps run twice over the same patch - taps 9..17 are the lo halves of the weights, p.w_lo_off elements
     // behind their hi halves (same [COUT][9*Cin] layout); the 1x1 shortcut's lo half replaces its hi half in rbuf after the centre tap.
@@ -183,10 +195,11 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
     constexpr int NTAP = 9;
 #endif
     static_assert(NT >= 1 && WPT >= 1 && NW % TH == 0 && NTHR % (CC / 8) == 0, "tile");
+    static_assert(!RW || NTAP == 9, "the resident schedule holds nine taps");
     extern __shared__ __attribute__((aligned(16))) u16 smem[];
     u16* patch = smem;                                // [PH*PW][LDP]
-    u16* wbuf = smem + PH * PW * LDP;                 // [2][NSL][LDP]
-    u16* rbuf = wbuf + 2 * NSL * LDP;                 // [NSL][LDP]  1x1 shortcut weights of this chunk (RES)
+    u16* wbuf = smem + PH * PW * LDP;                 // [2][NSL][LDP]; RW: [9][NSL][LDP]
+    u16* rbuf = wbuf + (RW ? 9 : 2) * NSL * LDP;      // [NSL][LDP]  1x1 shortcut weights of this chunk (RES)
     __shared__ long long gnred[16];
     constexpr int COEF_N = (TH == 8) ? 128 : 256;        // the 8-row form fills the LDS to the last KB: its table covers Cin = 128 only
     __shared__ __attribute__((aligned(16))) float coef[3][COEF_N];
@@ -267,7 +280,7 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
 
     CvGnLoads gnl{};
     if (pro) gnl = cv_gn_issue(p, b, tid, step);
-    const int nchunk = p.Cin / CC;
+    const int nchunk = RW ? 1 : p.Cin / CC;
     for (int ch = 0; ch < nchunk; ++ch) {
         const int cbase = ch * CC;
         // ---- every global load of the chunk's first round goes out back to back: the patch FIRST (loads return in order and
@@ -309,6 +322,17 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
                 pmk[q] = inb ? mk : 0.f;
                 pin[q] = inb;
             }
+            u32x4 rwv[RW ? RWB : 1];                      // RW: this pass's share of the nine taps, requested behind its patch items
+            if constexpr (RW) {
+#pragma unroll
+                for (int j = 0; j < RWB; ++j) {
+                    const int it = tid + NTHR * (ps * RWB + j);
+                    if (ps * RWB + j < RWPT && (RWI % NTHR == 0 || it < RWI)) {
+                        const int r = it % WITEMS;
+                        rwv[j] = *reinterpret_cast<const u32x4*>(Wg + (r / (CC / 8)) * K + (it / WITEMS) * p.Cin + (r % (CC / 8)) * 8);
+                    }
+                }
+            }
             if (ps == 0) {
                 if constexpr (RES) {
                     const u16* Rg = reinterpret_cast<const u16*>(p.res_w) + (long)slice * NSL * p.Cin;      // [COUT][Cin]
@@ -322,16 +346,20 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
 #endif
                     }
                 }
+                if constexpr (!RW) {
 #pragma unroll
-                for (int j = 0; j < WPT; ++j) if (wok[j]) w0r[j] = *reinterpret_cast<const u32x4*>(Wg + wofs[j] + cbase);
+                    for (int j = 0; j < WPT; ++j) if (wok[j]) w0r[j] = *reinterpret_cast<const u32x4*>(Wg + wofs[j] + cbase);
 #pragma unroll
-                for (int s = 0; s < RING; ++s)
+                    for (int s = 0; s < RING; ++s)
 #pragma unroll
-                    for (int j = 0; j < WPT; ++j) if (wok[j]) wr[s][j] = *reinterpret_cast<const u32x4*>(Wg + wofs[j] + WS_TAPOFS(s + 1) + cbase);
+                        for (int j = 0; j < WPT; ++j) if (wok[j]) wr[s][j] = *reinterpret_cast<const u32x4*>(Wg + wofs[j] + WS_TAPOFS(s + 1) + cbase);
+                }
                 CSTAMP(0);
                 if (pro && ch == 0) cv_gn_finish<COEF_N>(p, gnl, tid, coef);
                 __builtin_amdgcn_sched_barrier(0);
-                lds_barrier();                            // GN coefficients visible; previous chunk's MFMAs done with patch/wbuf
+                // GN coefficients visible; previous chunk's MFMAs done with patch/wbuf  (resident, no prologue: one chunk and nothing
+                // published yet - the barrier behind the staging is the only one)
+                if (!RW || pro) lds_barrier();
                 CSTAMP(1);
                 if (pro) {
                     const int c = cbase + pc8;
@@ -383,14 +411,64 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
                 v.z = pack2_lp(f1.x * mk, f1.y * mk); v.w = pack2_lp(f1.z * mk, f1.w * mk);
                 if (it < ITEMS) *reinterpret_cast<uint4*>(patch + (it / (CC / 8)) * LDP + pc8) = v;
             }
-        }
+            if constexpr (RW) {                           // (the taps arrive behind the pass's patch items: written after their conversion)
 #pragma unroll
-        for (int j = 0; j < WPT; ++j) if (wok[j]) *reinterpret_cast<u32x4*>(wbuf + wlds[j]) = w0r[j];
+                for (int j = 0; j < RWB; ++j) {
+                    const int it = tid + NTHR * (ps * RWB + j);
+                    if (ps * RWB + j < RWPT && (RWI % NTHR == 0 || it < RWI)) {
+                        const int r = it % WITEMS;
+                        *reinterpret_cast<u32x4*>(wbuf + ((it / WITEMS) * NSL + r / (CC / 8)) * LDP + (r % (CC / 8)) * 8) = rwv[j];
+                    }
+                }
+            }
+        }
+        if constexpr (!RW) {
+#pragma unroll
+            for (int j = 0; j < WPT; ++j) if (wok[j]) *reinterpret_cast<u32x4*>(wbuf + wlds[j]) = w0r[j];
+        }
         if constexpr (RES) {
 #pragma unroll
             for (int j = 0; j < WPT; ++j) if (wok[j]) *reinterpret_cast<u32x4*>(rbuf + wlds[j]) = rwr[j];
         }
         CSTAMP(2);
+        if constexpr (RW) {
+            // ---- resident: ONE barrier behind patch and weights, then the 9 x CC/16 (tap, K-step) pairs of the current forms in their
+            // order; the fragments of pair s+1 are read from LDS before the MFMAs of pair s issue
+            lds_barrier();
+            constexpr int KS = CC / 16;
+            const u16* ap = patch + (wrow * PW + i) * LDP + hh * 8;
+            const u16* bp = wbuf + (wcol * NT * 32 + i) * LDP + hh * 8;
+            const u16* rp = rbuf + (wcol * NT * 32 + i) * LDP + hh * 8;
+            lp8 af[2], bf[2][NT], rf[2][RES ? NT : 1];
+            af[0] = *reinterpret_cast<const lp8*>(ap);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) bf[0][t] = *reinterpret_cast<const lp8*>(bp + t * 32 * LDP);
+#pragma unroll
+            for (int s = 0; s < 9 * KS; ++s) {
+                if (s + 1 < 9 * KS) {
+                    const int tap = (s + 1) / KS, ks = (s + 1) % KS, kh = tap / 3, kw = tap - kh * 3;
+                    af[(s + 1) & 1] = *reinterpret_cast<const lp8*>(ap + (kh * PW + kw) * LDP + ks * 16);
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) bf[(s + 1) & 1][t] = *reinterpret_cast<const lp8*>(bp + (tap * NSL + t * 32) * LDP + ks * 16);
+                    if constexpr (RES) {
+                        if (tap == 4) {
+#pragma unroll
+                            for (int t = 0; t < NT; ++t) rf[(s + 1) & 1][t] = *reinterpret_cast<const lp8*>(rp + t * 32 * LDP + ks * 16);
+                        }
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);        // (the scheduler otherwise sinks each read to right above its MFMA)
+#pragma unroll
+                for (int t = 0; t < NT; ++t) acc[t] = DEX_MFMA_LP(af[s & 1], bf[s & 1][t], acc[t], 0, 0, 0);
+                if constexpr (RES) {
+                    if (s / KS == 4) {                    // centre tap: the same A fragment feeds the 1x1 shortcut
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) accr[t] = DEX_MFMA_LP(af[s & 1], rf[s & 1][t], accr[t], 0, 0, 0);
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
         // ---- nine taps; tap t's weights sit in wbuf[t & 1], taps t+1 .. t+RING are in registers / in flight
 #pragma unroll
         for (int tt = 0; tt < NTAP; ++tt) {
@@ -438,6 +516,7 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
                 }
             }
         }
+        }
     }
     if constexpr (RES) cv_res_store<NT, COUT>(p, accr, b, h0 + wrow, w0, slice * NSL + wcol * NT * 32, lane);
     CSTAMP(3);
@@ -456,24 +535,25 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_lp_kernel(const Conv3P p) {
 #endif
 }
 
-template <int CC, int COUT, int NSL, int TH, bool PRO2 = false, bool RES = false, bool XB = false, int NW = 4>
+template <int CC, int COUT, int NSL, int TH, bool PRO2 = false, bool RES = false, bool XB = false, int NW = 4, bool RW = false>
 static void launch_c3(const Conv3P& p, hipStream_t st) {
     constexpr int LDP = CC + 8;
-    const size_t lds = ((size_t)(TH + 2) * 34 * LDP + (2 + (RES ? 1 : 0)) * NSL * LDP) * sizeof(u16);
+    const size_t lds = ((size_t)(TH + 2) * 34 * LDP + ((RW ? 9 : 2) + (RES ? 1 : 0)) * NSL * LDP) * sizeof(u16);
     static bool attr = false;
     if (!attr) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_lp_kernel<CC, COUT, NSL, TH, PRO2, RES, XB, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_lp_kernel<CC, COUT, NSL, TH, PRO2, RES, XB, NW, RW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr = true;
     }
     dim3 grid((p.W + 31) / 32, (p.H + TH - 1) / TH, p.B * (COUT / NSL));
+    if (RW && p.Cin != CC) { fprintf(stderr, "libdexamd: resident conv3x3 form needs Cin == %d in one chunk (got %d)\n", CC, p.Cin); abort(); }
     Conv3P q = p;
     // padding-only tiles are looked for at batch size only: the test is one more dependent load at the head of a launch, and the small
     // grids are latency chains (B = 1, where nothing is padded anyway: 25.5 -> 25.1 k frames/s with the test on; B = 32 fp16x2: +0.5 ... 2 %)
     q.skip_dead = (p.B >= 4 && (long)grid.x * grid.y * grid.z >= 1024 && knob_or("DEX_CONV_SKIP_DEAD", 1) != 0) ? 1 : 0;
     static char sym[96];
-    if (!sym[0]) snprintf(sym, sizeof sym, "conv3x3_lp_kernel<%d,%d,%d,%d,%d,%d,%d,%d>", CC, COUT, NSL, TH, (int)PRO2, (int)RES, (int)XB, NW);
+    if (!sym[0]) snprintf(sym, sizeof sym, "conv3x3_lp_kernel<%d,%d,%d,%d,%d,%d,%d,%d%s>", CC, COUT, NSL, TH, (int)PRO2, (int)RES, (int)XB, NW, RW ? ",resident" : "");
     g_last_symbol = sym;
-    hipLaunchKernelGGL((conv3x3_lp_kernel<CC, COUT, NSL, TH, PRO2, RES, XB, NW>), grid, dim3(64 * NW), lds, st, q);
+    hipLaunchKernelGGL((conv3x3_lp_kernel<CC, COUT, NSL, TH, PRO2, RES, XB, NW, RW>), grid, dim3(64 * NW), lds, st, q);
 }
 
 bool conv3x3_bf16_tail_supported(int C) {
@@ -536,6 +616,10 @@ bool conv3x3_cat_lp_in_supported(int H, int W, int B, int Cin, int Cout) {
 // on five waves: 13.6 -> 13.2 us back to back but 13.6 -> 14.2 in the sampler's step, and 15.6 -> 16.9 for the fused tail - one SIMD
 // holds two 72-MFMA waves, as on a doubled CU before) and, in the split-weight build, the 64 -> 64 fused tail (ten waves leave 168
 // registers, and its 18-tap form spills at that).
+// Resident weights (conv3x3_lp_kernel's RW schedule): DEX_CONV_RESIDENT=0 keeps the streamed forms.  Never the split-weight build
+// (18 taps do not fit the LDS), Cin = 128 chunks (147 KB of weights) or a grid of more than one round of the CUs.
+static bool conv3x3_resident_on() { return knob_or("DEX_CONV_RESIDENT", 1) != 0; }
+
 static bool launch_c3_round1(const Conv3P& p, bool small, hipStream_t st) {
     if (!knob_or("DEX_CONV_ROUND1", 1)) return false;
     const bool tail_ = p.pro_res != nullptr;
@@ -552,6 +636,17 @@ static bool launch_c3_round1(const Conv3P& p, bool small, hipStream_t st) {
     const long ncu = device_cus();
     if (cur <= ncu || one > ncu || one * 4 < ncu * 3) return false;      // (and it keeps three quarters of the CUs busy: 40x400 at T = 800
                                                                          // would put its 64 -> 64 convs on 104 CUs)
+#ifndef DEX_LP_WSPLIT
+    if (conv3x3_resident_on()) {         // one workgroup per CU (one <= ncu): the same tiles with all nine taps resident in LDS
+        // (not the ten-wave fused tail: resident it was 12.16 -> 11.97 us back to back but 12.64 -> 12.76 in the sampler's step - it keeps
+        // the streamed form below; tools/convbench b1 still has its resident instantiation)
+        if (c64 && !tail_) {
+            p.x_bf16 ? launch_c3<64, 64, 64, 5, false, false, true, 10, true>(p, st) : launch_c3<64, 64, 64, 5, false, false, false, 10, true>(p, st);
+            return true;
+        }
+        if (!c64) { launch_c3<64, 128, 32, 5, false, true, false, 5, true>(p, st); return true; }
+    }
+#endif
     if (c64) {
 #ifndef DEX_LP_WSPLIT
         if (tail_) { p.x_bf16 ? launch_c3<64, 64, 64, 5, true, false, true, 10>(p, st) : launch_c3<64, 64, 64, 5, true, false, false, 10>(p, st); return true; }
@@ -561,6 +656,20 @@ static bool launch_c3_round1(const Conv3P& p, bool small, hipStream_t st) {
         launch_c3<64, 128, 32, 5, false, true, false, 5>(p, st);
     }
     return true;
+}
+
+// The 2-row 64 -> 64 forms of a small grid that is at most one round of the CUs (40x256 at B = 1: 160 workgroups) with resident weights.
+static bool launch_c3_small_resident(const Conv3P& p, bool small, hipStream_t st) {
+#ifdef DEX_LP_WSPLIT
+    return false;
+#else
+    if (!small || !conv3x3_resident_on() || p.Cin != 64 || p.Cout != 64 || p.res_w) return false;
+    if ((long)((p.W + 31) / 32) * ((p.H + 1) / 2) * p.B > device_cus()) return false;
+    const bool tail_ = p.pro_res != nullptr;
+    if (tail_) { p.x_bf16 ? launch_c3<64, 64, 64, 2, true, false, true, 4, true>(p, st) : launch_c3<64, 64, 64, 2, true, false, false, 4, true>(p, st); }
+    else { p.x_bf16 ? launch_c3<64, 64, 64, 2, false, false, true, 4, true>(p, st) : launch_c3<64, 64, 64, 2, false, false, false, 4, true>(p, st); }
+    return true;
+#endif
 }
 
 void launch_conv3x3_lp(const Conv3P& p, hipStream_t st) {
@@ -604,6 +713,7 @@ void launch_conv3x3_lp(const Conv3P& p, hipStream_t st) {
         return;
     }
     if (launch_c3_round1(p, small, st)) return;
+    if (launch_c3_small_resident(p, small, st)) return;
     if (p.x_bf16) {       // raw conv output stored as bf16: the GroupNorm-prologue forms with Cin == Cout (conv3x3_bf16_xb_supported)
         if (tail_) {
             if (p.Cin == 64) { small ? launch_c3<64, 64, 64, 2, true, false, true>(p, st) : launch_c3<64, 64, 64, 4, true, false, true>(p, st); }

@@ -1,7 +1,7 @@
 // tools/convbench.hip — the 64->64 convolution kernels alone at batch size: timing + (with -DDEX_TIMING) the phase
 // cycle counters of the strip-streaming kernel.  `convbench b1`: the B = 1 patch-conv launches of the headline in their current
-// and one-round forms (bitwise comparison, timing, the current grid cut to one round), and with -DDEX_TIMING each workgroup's
-// phase counters next to the CU it ran on.  Build: see tools/convbench.sh
+// one-round and resident-weights forms (bitwise comparison, timing, the current grid cut to one round), and with -DDEX_TIMING each
+// workgroup's phase counters next to the CU it ran on.  Build: see tools/convbench.sh
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -196,6 +196,9 @@ int main_b1() {
         {"40x256 64->128 +1x1 shortcut", 64, 128, 40, 256, 0, 0, 0, 1},
         {"40x256 128->128 PRO bf16 in", 128, 128, 40, 256, 1, 0, 1, 0},
         {"40x256 128->128 PRO2 bf16 in", 128, 128, 40, 256, 1, 1, 1, 0},
+        {"40x256 64->64 PRO bf16 in", 64, 64, 40, 256, 1, 0, 1, 0},
+        {"40x256 64->64 PRO2 bf16 in", 64, 64, 40, 256, 1, 1, 1, 0},
+        {"40x256 64->64 plain fp32 in", 64, 64, 40, 256, 0, 0, 0, 0},
     };
     int bad = 0;
     for (const Case& c : cases) {
@@ -207,30 +210,47 @@ int main_b1() {
         if (c.res) { p.res_w = rw; p.res_b = (const float*)rb; p.res_y = bb.ry; }
         // the current form, its grid cut to 256 workgroups, and the one-round forms
         std::vector<std::pair<const char*, std::function<void(const Conv3P&)>>> forms;
-        int rows_old = 0, nwg_old = 0;
-        if (c.C == 64 && c.Co == 64) {
+        int rows_old = 0, nwg_old = 0, nwg_new = 256;
+        bool has_cut = true;
+        if (c.C == 64 && c.Co == 64 && c.H == 40) {          // 160 workgroups of the 2-row form: streamed vs resident weights
+            nwg_old = nwg_new = 160; has_cut = false;
+            if (c.pro2) {
+                forms.push_back({"current <64,64,64,2,PRO2,XB,4>", [](const Conv3P& q) { launch_c3<64, 64, 64, 2, true, false, true, 4>(q, 0); }});
+                forms.push_back({"resident", [](const Conv3P& q) { launch_c3<64, 64, 64, 2, true, false, true, 4, true>(q, 0); }});
+            } else if (c.xb) {
+                forms.push_back({"current <64,64,64,2,PRO,XB,4>", [](const Conv3P& q) { launch_c3<64, 64, 64, 2, false, false, true, 4>(q, 0); }});
+                forms.push_back({"resident", [](const Conv3P& q) { launch_c3<64, 64, 64, 2, false, false, true, 4, true>(q, 0); }});
+            } else {
+                forms.push_back({"current <64,64,64,2,plain,4>", [](const Conv3P& q) { launch_c3<64, 64, 64, 2, false, false, false, 4>(q, 0); }});
+                forms.push_back({"resident", [](const Conv3P& q) { launch_c3<64, 64, 64, 2, false, false, false, 4, true>(q, 0); }});
+            }
+        } else if (c.C == 64 && c.Co == 64) {
             rows_old = 20; nwg_old = 320;
             if (c.pro2) {
                 forms.push_back({"current <64,64,64,4,PRO2,XB,4>", [](const Conv3P& q) { launch_c3<64, 64, 64, 4, true, false, true, 4>(q, 0); }});
                 forms.push_back({"current cut to 16 x 16", [](const Conv3P& q) { launch_cut<64, 64, 64, 4, true, false, true, 4>(q, 16); }});
                 forms.push_back({"one round, 10 waves", [](const Conv3P& q) { launch_c3<64, 64, 64, 5, true, false, true, 10>(q, 0); }});
                 forms.push_back({"one round, 5 waves", [](const Conv3P& q) { launch_c3<64, 64, 64, 5, true, false, true, 5>(q, 0); }});
+                forms.push_back({"one round, 10 waves, resident", [](const Conv3P& q) { launch_c3<64, 64, 64, 5, true, false, true, 10, true>(q, 0); }});
             } else if (c.xb) {
                 forms.push_back({"current <64,64,64,4,PRO,XB,4>", [](const Conv3P& q) { launch_c3<64, 64, 64, 4, false, false, true, 4>(q, 0); }});
                 forms.push_back({"current cut to 16 x 16", [](const Conv3P& q) { launch_cut<64, 64, 64, 4, false, false, true, 4>(q, 16); }});
                 forms.push_back({"one round, 10 waves", [](const Conv3P& q) { launch_c3<64, 64, 64, 5, false, false, true, 10>(q, 0); }});
                 forms.push_back({"one round, 5 waves", [](const Conv3P& q) { launch_c3<64, 64, 64, 5, false, false, true, 5>(q, 0); }});
+                forms.push_back({"one round, 10 waves, resident", [](const Conv3P& q) { launch_c3<64, 64, 64, 5, false, false, true, 10, true>(q, 0); }});
             } else {
                 forms.push_back({"current <64,64,64,4,plain,4>", [](const Conv3P& q) { launch_c3<64, 64, 64, 4, false, false, false, 4>(q, 0); }});
                 forms.push_back({"current cut to 16 x 16", [](const Conv3P& q) { launch_cut<64, 64, 64, 4, false, false, false, 4>(q, 16); }});
                 forms.push_back({"one round, 10 waves", [](const Conv3P& q) { launch_c3<64, 64, 64, 5, false, false, false, 10>(q, 0); }});
                 forms.push_back({"one round, 5 waves", [](const Conv3P& q) { launch_c3<64, 64, 64, 5, false, false, false, 5>(q, 0); }});
+                forms.push_back({"one round, 10 waves, resident", [](const Conv3P& q) { launch_c3<64, 64, 64, 5, false, false, false, 10, true>(q, 0); }});
             }
         } else if (c.res) {
             rows_old = 20; nwg_old = 320;
             forms.push_back({"current <64,128,64,2,RES,4>", [](const Conv3P& q) { launch_c3<64, 128, 64, 2, false, true, false, 4>(q, 0); }});
             forms.push_back({"current cut to 8 x 16 x 2", [](const Conv3P& q) { launch_cut<64, 128, 64, 2, false, true, false, 4>(q, 16); }});
             forms.push_back({"one round <64,128,32,5,RES,5>", [](const Conv3P& q) { launch_c3<64, 128, 32, 5, false, true, false, 5>(q, 0); }});
+            forms.push_back({"one round <64,128,32,5,RES,5>, resident", [](const Conv3P& q) { launch_c3<64, 128, 32, 5, false, true, false, 5, true>(q, 0); }});
         } else {
             rows_old = 20; nwg_old = 320;
             if (c.pro2) {
@@ -247,22 +267,22 @@ int main_b1() {
         printf("%s\n", c.nm);
         std::vector<char> ref;
         for (size_t k = 0; k < forms.size(); ++k) {
-            const bool cut = k == 1;
+            const bool cut = has_cut && k == 1;
             if (!cut) {                                            // bitwise: every output of the full-grid forms, statistics included
                 clear(bb); forms[k].second(p); const std::vector<char> h = snap(bb);
                 if (k == 0) ref = h;
-                else { const bool same = h == ref; bad += !same; printf("   %-34s bitwise %s%s\n", forms[k].first, same ? "equal" : "DIFFERENT: ", same ? "" : diff_part(h, ref, bb.ny)); }
+                else { const bool same = h == ref; bad += !same; printf("   %-40s bitwise %s%s\n", forms[k].first, same ? "equal" : "DIFFERENT: ", same ? "" : diff_part(h, ref, bb.ny)); }
             }
             const float us = time_us([&] { forms[k].second(p); });
-            printf("   %-34s %7.2f us\n", forms[k].first, us);
+            printf("   %-40s %7.2f us\n", forms[k].first, us);
         }
 #ifdef DEX_TIMING
         stamps(forms[0].first, forms[0].second, p, nwg_old, bb);
-        for (size_t k = 2; k < forms.size(); ++k) stamps(forms[k].first, forms[k].second, p, 256, bb);
+        for (size_t k = has_cut ? 2 : 1; k < forms.size(); ++k) stamps(forms[k].first, forms[k].second, p, nwg_new, bb);
 #endif
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) { printf("HIP error %s\n", hipGetErrorString(e)); return 2; }
     }
-    printf("%s\n", bad ? "MISMATCH" : "all one-round forms bitwise equal to the current ones");
+    printf("%s\n", bad ? "MISMATCH" : "all one-round and resident forms bitwise equal to the current ones");
     return bad ? 1 : 0;
 }
