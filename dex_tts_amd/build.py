@@ -120,7 +120,32 @@ def build(force: bool = False, verbose: bool = True) -> str:
             raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
     if verbose:
         print(f"built {LIB} ({os.path.getsize(LIB) / 1e6:.1f} MB)")
+    build_kshim(force, verbose)
     return LIB
+
+
+# the test-only launch shim (tests/kshim/kshim.hip: host code that fills the kernels' parameter structs and calls the library's
+# launchers, one launch per call - tests/test_gpu_conv_kernels.py).  Built after the library it links against, by the same
+# incremental rule; it finds the library through an $ORIGIN-relative rpath, so the pair travels with the tree.
+KSHIM_SRC = os.path.join(HERE, "..", "tests", "kshim", "kshim.hip")
+KSHIM_LIB = os.path.join(HERE, "..", "tests", "kshim", "libkshim.so")
+
+
+def build_kshim(force: bool = False, verbose: bool = True):
+    if not os.path.exists(KSHIM_SRC):          # (a tree without its tests)
+        return None
+    deps = [KSHIM_SRC, LIB] + [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
+    if force or _stale(KSHIM_LIB, deps):
+        cmd = [HIPCC, *FLAGS, "-shared", KSHIM_SRC, "-o", KSHIM_LIB, "-L" + os.path.dirname(LIB), "-ldexamd",
+               "-Wl,-rpath,$ORIGIN/../../dex_tts_amd/lib"]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"hipcc failed for the test shim:\n{r.stdout}\n{r.stderr}")
+        if r.stderr.strip():
+            sys.stderr.write(r.stderr)
+    if verbose:
+        print(f"built {os.path.normpath(KSHIM_LIB)}")
+    return KSHIM_LIB
 
 
 if __name__ == "__main__":

@@ -1,0 +1,198 @@
+"""ctypes loader of the test-only launch shim (tests/kshim/kshim.hip, built by dex_tts_amd/build.py next to the library).
+
+The shim fills the library's parameter structs from flat descriptors and runs ONE launch.  This side mirrors the descriptors,
+checks every tensor against the extent its descriptor implies BEFORE the call (the shim sees pointers only), and returns the kernel
+instantiation the launcher picked.  A descriptor the shim rejects raises ShimError: a mistyped case is an error, never a launch."""
+import ctypes as C
+import os
+
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(HERE, "libkshim.so")
+PREC = {"bf16": 1, "fp16": 2, "fp16x2": 3}
+LP_DTYPE = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp16x2": torch.float16}
+ERRORS = {-1: "precision", -2: "null pointer", -3: "shape", -4: "unsupported by the library's predicates", -5: "no such form",
+          -6: "stride / offset"}
+PREDICATES = {"conv3x3_bf16_supported": 0, "conv3x3_bf16_tail_supported": 1, "conv3x3_bf16_res_supported": 2,
+              "conv3x3_bf16_xb_supported": 3, "conv3x3_plain_lp_in_supported": 4, "conv3x3_cat_lp_in_supported": 5,
+              "conv3x3_res2_form": 6, "conv_down_supported": 7, "convt_up_supported": 8}
+GN_SLOTS = 32
+
+
+class ShimError(RuntimeError):
+    pass
+
+
+def _ptrs(*names):
+    return [(n, C.c_void_p) for n in names]
+
+
+def _ints(*names):
+    return [(n, C.c_int32) for n in names]
+
+
+class KsConv3(C.Structure):
+    _fields_ = (_ptrs("X", "Wbf", "Wfrag", "bias", "mask", "Y", "pro_stats", "pro_gamma", "pro_beta", "pro_tadd", "pro_res", "pro_xout",
+                      "res2_w", "res2_b", "res2_mu", "res2_x", "res2_spk", "res2_scal", "res_w", "res_b", "res_wfrag", "res_y", "gn_stats")
+                + [("mask_bstride", C.c_int64), ("w_lo_off", C.c_int64), ("res_lo_off", C.c_int64)]
+                + _ints("precision", "H", "W", "Cin", "Cout", "B", "ldx", "x_coff", "mask_ws", "step", "row_bstride", "x_bf16", "y_bf16",
+                        "xout_lp", "res2_scal_stride", "res2_planes"))
+
+
+class KsConvDown(C.Structure):
+    _fields_ = (_ptrs("X", "Wfrag", "bias", "inmask", "Y") + [("xb", C.c_int64), ("mask_bstride", C.c_int64)]
+                + _ints("precision", "a_lp", "c_lp", "ldx", "x_coff", "H", "W", "ldy", "y_coff", "inmask_ws", "B", "C"))
+
+
+class KsConvTUp(C.Structure):
+    _fields_ = (_ptrs("X", "Wfrag0", "Wfrag1", "Wfrag2", "Wfrag3", "bias", "inmask", "Y") + [("xb", C.c_int64), ("mask_bstride", C.c_int64)]
+                + _ints("precision", "a_lp", "c_lp", "ldx", "x_coff", "H", "W", "ldy", "y_coff", "inmask_ws", "B", "C"))
+
+
+_lib = None
+
+
+def load():
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise RuntimeError(f"{LIB_PATH} not found: python -m dex_tts_amd.build builds it after the library")
+    from dex_tts_amd import _lib as dexlib
+    dexlib.load()                                     # torch's HIP runtime, then the library the shim links against
+    lib = C.CDLL(LIB_PATH)
+    lib.ks_struct_bytes.restype, lib.ks_struct_bytes.argtypes = C.c_int, [C.c_int]
+    for k, T in enumerate((KsConv3, KsConvDown, KsConvTUp)):
+        if lib.ks_struct_bytes(k) != C.sizeof(T):
+            raise RuntimeError(f"descriptor {T.__name__}: {C.sizeof(T)} bytes here, {lib.ks_struct_bytes(k)} in the shim")
+    lib.ks_predicate.restype, lib.ks_predicate.argtypes = C.c_int, [C.c_int] * 8
+    lib.ks_pack.restype = C.c_int
+    lib.ks_pack.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p]
+    for name, T in (("ks_conv3x3", KsConv3), ("ks_conv_down", KsConvDown), ("ks_convt_up", KsConvTUp)):
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = C.c_int, [C.POINTER(T), C.c_void_p, C.c_char_p, C.c_int]
+    lib.ks_conv3x3_strip_form.restype, lib.ks_conv3x3_strip_form.argtypes = C.c_int, [C.POINTER(KsConv3)]
+    _lib = lib
+    return lib
+
+
+def _check(rc, what):
+    if rc < 0:
+        raise ShimError(f"{what}: rejected by the shim ({ERRORS.get(rc, rc)})")
+    return rc
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def predicate(name, prec, *args):
+    a = list(args) + [0] * (6 - len(args))
+    return bool(_check(load().ks_predicate(PREDICATES[name], PREC[prec], *a), name))
+
+
+def _need(t, nbytes, name):
+    """Tensor t (or None) as a pointer, after checking it is a contiguous device tensor of at least nbytes."""
+    if t is None:
+        return None
+    if not (t.is_cuda and t.is_contiguous()):
+        raise ShimError(f"{name}: not a contiguous device tensor")
+    if t.numel() * t.element_size() < nbytes:
+        raise ShimError(f"{name}: {t.numel() * t.element_size()} bytes, the descriptor implies {nbytes}")
+    return t.data_ptr()
+
+
+def pack(kind, w_kn, prec):
+    """The library's packing of a device fp32 [K][N] matrix: kind "nk" (16-bit [N][K]) or "frag" (MFMA fragment order).
+    Returns (uint16 pack as an int16 tensor, lo_off): the split-weight mode's lo pack sits lo_off elements behind the hi pack."""
+    K, N = w_kn.shape
+    assert w_kn.is_cuda and w_kn.dtype == torch.float32 and w_kn.is_contiguous()
+    split = prec == "fp16x2"
+    lo_off = K * N if split else 0
+    dst = torch.zeros(K * N * (2 if split else 1), dtype=torch.int16, device=w_kn.device)
+    scratch = torch.zeros(K * N, dtype=torch.float32, device=w_kn.device) if split else None
+    _check(load().ks_pack({"nk": 0, "frag": 1}[kind], w_kn.data_ptr(), dst.data_ptr(), scratch.data_ptr() if split else None,
+                          K, N, lo_off, PREC[prec], _stream()), f"pack {kind}")
+    torch.cuda.current_stream().synchronize()         # (scratch is released on return)
+    return dst, lo_off
+
+
+def _conv3_desc(prec, t, H, W, Cin, Cout, B, ldx, x_coff, mask_ws, mask_bstride, step, row_bstride, x_bf16, y_bf16, xout_lp,
+                w_lo_off, res_lo_off, res2_scal_stride, res2_planes):
+    """t: dict of tensors by descriptor member name (absent / None = null)."""
+    d = KsConv3()
+    g = t.get
+    npix = B * H * W
+    last_row = step + (B - 1) * row_bstride
+    split = 2 if prec == "fp16x2" else 1
+    sizes = {
+        "X": npix * ldx * (2 if x_bf16 else 4), "Y": npix * Cout * (2 if y_bf16 else 4), "bias": Cout * 4,
+        "Wbf": (w_lo_off * (split - 1) + 9 * Cin * Cout) * 2, "Wfrag": (9 * Cin * Cout * split) * 2,
+        "mask": ((B - 1) * mask_bstride + (W - 1) * mask_ws + 1) * 4,
+        "pro_stats": B * 8 * GN_SLOTS * 2 * 8, "pro_gamma": Cin * 4, "pro_beta": Cin * 4, "pro_tadd": (last_row + 1) * Cin * 4,
+        "pro_res": npix * Cin * 4, "pro_xout": npix * Cin * (2 if xout_lp else 4),
+        "res2_w": max(res2_planes, 0) * 64 * 4, "res2_b": 64 * 4, "res2_mu": npix * 4, "res2_x": npix * 4, "res2_spk": B * H * 4,
+        "res2_scal": (last_row * max(res2_scal_stride, 0) + 3) * 4,
+        "res_w": (res_lo_off * (split - 1) + Cin * Cout) * 2, "res_wfrag": Cin * Cout * split * 2, "res_b": Cout * 4,
+        "res_y": npix * Cout * 4, "gn_stats": B * 8 * GN_SLOTS * 2 * 8,
+    }
+    if step < 0 or row_bstride < 0 or min(H, W, B, Cin, Cout, ldx) <= 0:
+        raise ShimError("conv3x3: negative or empty extent")
+    for name, nbytes in sizes.items():
+        setattr(d, name, _need(g(name), nbytes, name))
+    for name in t:
+        if name not in sizes:
+            raise ShimError(f"conv3x3: unknown tensor {name}")
+    d.mask_bstride, d.w_lo_off, d.res_lo_off = mask_bstride, w_lo_off, res_lo_off
+    d.precision = PREC[prec]
+    d.H, d.W, d.Cin, d.Cout, d.B, d.ldx, d.x_coff, d.mask_ws = H, W, Cin, Cout, B, ldx, x_coff, mask_ws
+    d.step, d.row_bstride, d.x_bf16, d.y_bf16, d.xout_lp = step, row_bstride, int(x_bf16), int(y_bf16), int(xout_lp)
+    d.res2_scal_stride, d.res2_planes = res2_scal_stride, res2_planes
+    return d
+
+
+def conv3x3(prec, tensors, *, H, W, Cin, Cout, B, ldx, x_coff=0, mask_ws=1, mask_bstride, step=0, row_bstride=0, x_bf16=False,
+            y_bf16=False, xout_lp=False, w_lo_off=0, res_lo_off=0, res2_scal_stride=0, res2_planes=0, dry=False):
+    """One launch_conv3x3_lp.  Returns the picked instantiation; dry=True launches nothing and returns whether the descriptor would
+    run on a strip-walking form."""
+    d = _conv3_desc(prec, tensors, H, W, Cin, Cout, B, ldx, x_coff, mask_ws, mask_bstride, step, row_bstride, x_bf16, y_bf16, xout_lp,
+                    w_lo_off, res_lo_off, res2_scal_stride, res2_planes)
+    if dry:
+        return bool(_check(load().ks_conv3x3_strip_form(C.byref(d)), "conv3x3"))
+    sym = C.create_string_buffer(128)
+    _check(load().ks_conv3x3(C.byref(d), _stream(), sym, 128), "conv3x3")
+    return sym.value.decode()
+
+
+def _strip_desc(T, prec, t, names_w, *, H, W, B, Cc, ldx, x_coff, ldy, y_coff, a_lp, c_lp, inmask_ws, mask_bstride, Ho, Wo, taps):
+    d = T()
+    split = 2 if prec == "fp16x2" else 1
+    if min(H, W, B, Cc, ldx, ldy) <= 0 or x_coff < 0 or y_coff < 0:
+        raise ShimError("negative or empty extent")
+    d.X = _need(t.get("X"), B * H * W * ldx * (2 if a_lp else 4), "X")
+    d.Y = _need(t.get("Y"), B * Ho * Wo * ldy * (2 if c_lp else 4), "Y")
+    d.bias = _need(t.get("bias"), Cc * 4, "bias")
+    d.inmask = _need(t.get("inmask"), ((B - 1) * mask_bstride + (W - 1) * inmask_ws + 1) * 4, "inmask")
+    for n in names_w:
+        setattr(d, n, _need(t.get(n), taps * Cc * Cc * split * 2, n))
+    d.xb, d.mask_bstride = H * W * ldx, mask_bstride
+    d.precision, d.a_lp, d.c_lp, d.ldx, d.x_coff, d.H, d.W = PREC[prec], int(a_lp), int(c_lp), ldx, x_coff, H, W
+    d.ldy, d.y_coff, d.inmask_ws, d.B, d.C = ldy, y_coff, inmask_ws, B, Cc
+    return d
+
+
+def conv_down(prec, tensors, *, H, W, B, ldx, x_coff=0, ldy, y_coff=0, a_lp=False, c_lp=False, inmask_ws=1, mask_bstride, Cc=64):
+    d = _strip_desc(KsConvDown, prec, tensors, ["Wfrag"], H=H, W=W, B=B, Cc=Cc, ldx=ldx, x_coff=x_coff, ldy=ldy, y_coff=y_coff, a_lp=a_lp,
+                    c_lp=c_lp, inmask_ws=inmask_ws, mask_bstride=mask_bstride, Ho=H // 2, Wo=W // 2, taps=9)
+    sym = C.create_string_buffer(128)
+    _check(load().ks_conv_down(C.byref(d), _stream(), sym, 128), "conv_down")
+    return sym.value.decode()
+
+
+def convt_up(prec, tensors, *, H, W, B, ldx, x_coff=0, ldy, y_coff=0, a_lp=False, c_lp=False, inmask_ws=1, mask_bstride, Cc=64):
+    d = _strip_desc(KsConvTUp, prec, tensors, ["Wfrag0", "Wfrag1", "Wfrag2", "Wfrag3"], H=H, W=W, B=B, Cc=Cc, ldx=ldx, x_coff=x_coff,
+                    ldy=ldy, y_coff=y_coff, a_lp=a_lp, c_lp=c_lp, inmask_ws=inmask_ws, mask_bstride=mask_bstride, Ho=2 * H, Wo=2 * W, taps=4)
+    sym = C.create_string_buffer(128)
+    _check(load().ks_convt_up(C.byref(d), _stream(), sym, 128), "convt_up")
+    return sym.value.decode()

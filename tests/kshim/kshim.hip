@@ -1,0 +1,236 @@
+// tests/kshim/kshim.hip — test-only launch shim: ONE launch of the reduced-precision convolution kernels of libdexamd.so from a
+// flat descriptor (tests/kshim/__init__.py mirrors the structs with ctypes).  Host code only, no kernels: every entry point fills
+// the library's parameter struct by member name, sets the split-weight flag as dex_api.hip does for a call, runs the library's own
+// launcher on the given stream and returns the instantiation it picked (dex::g_last_symbol).
+//
+// A descriptor the library's shape predicates reject, or one whose launcher would abort or pick a kernel built for another shape,
+// is an ERROR CODE (KS_E_*), never a launch: a mistyped test case must not reach the device.  Buffer sizes are the caller's side
+// of the contract (the Python loader checks every tensor against the extent the descriptor implies before it calls).
+#include "../../dex_tts_amd/csrc/kernels.h"
+#include <cstdio>
+#include <cstring>
+
+using namespace dex;
+
+namespace {
+
+enum { KS_OK = 0, KS_E_PREC = -1, KS_E_NULL = -2, KS_E_SHAPE = -3, KS_E_UNSUPPORTED = -4, KS_E_FORM = -5, KS_E_STRIDE = -6 };
+
+struct WsplitScope {          // the predicates of lp_dispatch.hip answer for the mode of the call being built on this thread
+    bool prev;
+    explicit WsplitScope(int precision) : prev(g_lp_wsplit) { g_lp_wsplit = prec_wsplit(precision); }
+    ~WsplitScope() { g_lp_wsplit = prev; }
+};
+
+bool lp_prec(int p) { return p == PREC_BF16 || p == PREC_FP16 || p == PREC_FP16X2; }
+
+void put_symbol(char* sym, int n) {
+    if (!sym || n <= 0) return;
+    const char* s = g_last_symbol ? g_last_symbol : "";
+    strncpy(sym, s, (size_t)n - 1);
+    sym[n - 1] = 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- descriptors (8-byte members first: no padding to mirror) --------------------------------------------------------------
+struct KsConv3 {
+    const void *X, *Wbf, *Wfrag, *bias, *mask; void* Y;
+    const void *pro_stats, *pro_gamma, *pro_beta, *pro_tadd, *pro_res; void* pro_xout;
+    const void *res2_w, *res2_b, *res2_mu, *res2_x, *res2_spk, *res2_scal;
+    const void *res_w, *res_b, *res_wfrag; void* res_y;
+    void* gn_stats;
+    long long mask_bstride, w_lo_off, res_lo_off;
+    int precision, H, W, Cin, Cout, B, ldx, x_coff, mask_ws, step, row_bstride, x_bf16, y_bf16, xout_lp, res2_scal_stride, res2_planes;
+};
+struct KsConvDown {
+    const void *X, *Wfrag, *bias, *inmask; void* Y;
+    long long xb, mask_bstride;
+    int precision, a_lp, c_lp, ldx, x_coff, H, W, ldy, y_coff, inmask_ws, B, C;
+};
+struct KsConvTUp {
+    const void *X, *Wfrag0, *Wfrag1, *Wfrag2, *Wfrag3, *bias, *inmask; void* Y;
+    long long xb, mask_bstride;
+    int precision, a_lp, c_lp, ldx, x_coff, H, W, ldy, y_coff, inmask_ws, B, C;
+};
+
+int ks_struct_bytes(int which) { return which == 0 ? (int)sizeof(KsConv3) : which == 1 ? (int)sizeof(KsConvDown) : (int)sizeof(KsConvTUp); }
+
+// ---- shape predicates of the library, for the mode `precision` -------------------------------------------------------------
+// which: 0 conv3x3_bf16_supported(a, b)   1 conv3x3_bf16_tail_supported(a)   2 conv3x3_bf16_res_supported(a, b)
+//        3 conv3x3_bf16_xb_supported(a, b)   4 conv3x3_plain_lp_in_supported(a, b, c, d, e)   5 conv3x3_cat_lp_in_supported(a, b, c, d, e)
+//        6 conv3x3_res2_form(a, b, c)   7 conv_down_supported(a, b, c, d, e, f)   8 convt_up_supported(a, b, c, d, e)
+int ks_predicate(int which, int precision, int a, int b, int c, int d, int e, int f) {
+    if (!lp_prec(precision)) return KS_E_PREC;
+    WsplitScope ws(precision);
+    switch (which) {
+        case 0: return conv3x3_bf16_supported(a, b);
+        case 1: return conv3x3_bf16_tail_supported(a);
+        case 2: return conv3x3_bf16_res_supported(a, b);
+        case 3: return conv3x3_bf16_xb_supported(a, b);
+        case 4: return conv3x3_plain_lp_in_supported(a, b, c, d, e);
+        case 5: return conv3x3_cat_lp_in_supported(a, b, c, d, e);
+        case 6: return conv3x3_res2_form(a, b, c);
+        case 7: return conv_down_supported(a, b, c, d, e, f);
+        case 8: return convt_up_supported(a, b, c, d, e);
+    }
+    return KS_E_SHAPE;
+}
+
+// ---- weight packing by the library's own code ------------------------------------------------------------------------------
+// kind: 0 launch_pack_lp_nk (fp32 [K][N] -> 16-bit [N][K])   1 launch_pack_lp_frag (fp32 [K][N] -> MFMA fragment order).
+// The split-weight mode packs the fp16 rounding of the weight, then what that rounding lost (through `scratch`, K*N floats), in the
+// same layout `lo_off` elements behind - dex_api.hip's pack3.  lo_off is ignored in the other modes.
+int ks_pack(int kind, const void* src, void* dst, void* scratch, int K, int N, long long lo_off, int precision, void* stream) {
+    if (!lp_prec(precision)) return KS_E_PREC;
+    if (!src || !dst || (precision == PREC_FP16X2 && !scratch)) return KS_E_NULL;
+    if (K <= 0 || N <= 0 || (kind != 0 && kind != 1)) return KS_E_SHAPE;
+    if (kind == 1 && (K % 16 != 0 || N % 32 != 0)) return KS_E_SHAPE;
+    if (precision == PREC_FP16X2 && lo_off < (long long)K * N) return KS_E_STRIDE;
+    hipStream_t st = (hipStream_t)stream;
+    const float* s = (const float*)src;
+    unsigned short* d = (unsigned short*)dst;
+    auto pack = [&](const float* from, unsigned short* to, int prec) {
+        if (kind == 0) launch_pack_lp_nk(from, to, K, N, prec, st); else launch_pack_lp_frag(from, to, K, N, prec, st);
+    };
+    if (precision != PREC_FP16X2) { pack(s, d, precision); return KS_OK; }
+    pack(s, d, PREC_FP16);
+    launch_f32_residual_lp(s, (float*)scratch, (long)K * N, PREC_FP16, st);
+    pack((const float*)scratch, d + lo_off, PREC_FP16);
+    return KS_OK;
+}
+
+// ---- 3x3 / s1 / p1 Block convolution ----------------------------------------------------------------------------------------
+static int conv3_fill(const KsConv3& d, Conv3P& p) {
+    if (!lp_prec(d.precision)) return KS_E_PREC;
+    if (d.H <= 0 || d.W <= 0 || d.B <= 0 || d.mask_ws < 1 || d.mask_bstride < 0) return KS_E_SHAPE;
+    if (!d.X || !d.Wbf || !d.bias || !d.mask || !d.Y) return KS_E_NULL;
+    if (d.ldx % 8 != 0 || d.x_coff % 8 != 0 || d.x_coff < 0 || d.ldx < d.x_coff + d.Cin) return KS_E_STRIDE;
+    if (!conv3x3_bf16_supported(d.Cin, d.Cout)) return KS_E_UNSUPPORTED;
+    if (d.Cin == 256 && d.Cout != 64) return KS_E_UNSUPPORTED;               // (256 input channels: the up path's 2C -> C only)
+    if (d.precision == PREC_FP16X2 && (d.w_lo_off < 9LL * d.Cin * d.Cout)) return KS_E_STRIDE;
+    const bool tail = d.pro_res || d.res2_w;
+    if (d.pro_stats) {      // GroupNorm prologue: the model's Cin == Cout convs only (no kernel form pairs it with the fused shortcut)
+        if (!d.pro_gamma || !d.pro_beta) return KS_E_NULL;
+        if (d.Cin != d.Cout || d.res_w || !conv3x3_bf16_tail_supported(d.Cin)) return KS_E_UNSUPPORTED;
+    } else if (tail || d.pro_tadd || d.pro_gamma || d.pro_beta) return KS_E_FORM;
+    if (d.pro_res && d.res2_w) return KS_E_FORM;
+    if (tail && d.pro_tadd) return KS_E_FORM;                                  // (the fused tail carries no time bias: diffusion.py:66-71)
+    if (tail && !d.pro_xout) return KS_E_NULL;
+    if (!tail && (d.pro_xout || d.xout_lp)) return KS_E_FORM;
+    if (d.res_w) {
+        if (!d.res_b || !d.res_y) return KS_E_NULL;
+        if (!conv3x3_bf16_res_supported(d.Cin, d.Cout)) return KS_E_UNSUPPORTED;
+        if (d.precision == PREC_FP16X2 && d.res_lo_off < (long long)d.Cin * d.Cout) return KS_E_STRIDE;
+    } else if (d.res_b || d.res_y || d.res_wfrag) return KS_E_FORM;
+    if (d.Cin != d.Cout && !d.res_w && !(d.Cin == 64 || d.Cin == 128 || d.Cin == 256)) return KS_E_UNSUPPORTED;
+
+    p = Conv3P{};
+    p.X = (const float*)d.X; p.ldx = d.ldx; p.x_coff = d.x_coff; p.H = d.H; p.W = d.W; p.Cin = d.Cin; p.Cout = d.Cout;
+    p.Wbf = d.Wbf; p.bias = (const float*)d.bias; p.Y = (float*)d.Y;
+    p.Wfrag = d.Wfrag;
+    p.mask = (const float*)d.mask; p.mask_ws = d.mask_ws; p.mask_bstride = (long)d.mask_bstride;
+    p.pro_stats = (const gnfix_t*)d.pro_stats; p.pro_gamma = (const float*)d.pro_gamma; p.pro_beta = (const float*)d.pro_beta;
+    p.pro_tadd = (const float*)d.pro_tadd;
+    p.pro_res = (const float*)d.pro_res; p.pro_xout = (float*)d.pro_xout;
+    p.xout_lp = d.xout_lp ? 1 : 0;
+    p.res2_w = (const float*)d.res2_w; p.res2_b = (const float*)d.res2_b; p.res2_mu = (const float*)d.res2_mu; p.res2_x = (const float*)d.res2_x;
+    p.res2_spk = (const float*)d.res2_spk; p.res2_scal = (const float*)d.res2_scal;
+    p.res2_scal_stride = d.res2_scal_stride; p.res2_planes = d.res2_planes;
+    p.res_w = d.res_w; p.res_b = (const float*)d.res_b; p.res_y = (float*)d.res_y;
+    p.res_wfrag = d.res_wfrag;
+    p.step = d.step; p.gn_stats = (gnfix_t*)d.gn_stats; p.B = d.B;
+    p.dbg = nullptr;
+    p.x_bf16 = d.x_bf16 ? 1 : 0; p.y_bf16 = d.y_bf16 ? 1 : 0;
+    p.w_lo_off = (long)d.w_lo_off; p.res_lo_off = (long)d.res_lo_off;
+    p.row_bstride = d.row_bstride;
+    p.skip_dead = 0;                                          // (set by the launchers)
+
+    // forms that exist at some grids only (the struct-level predicates above cannot see them)
+    if (d.res2_w) {         // the recomputed shortcut: the ping-pong strip form, contiguous 64-channel input
+        if (!d.res2_b || !d.res2_mu || !d.res2_x || !d.res2_scal) return KS_E_NULL;
+        if (d.res2_planes != 2 && d.res2_planes != 3) return KS_E_SHAPE;
+        if (d.res2_planes == 3 && !d.res2_spk) return KS_E_NULL;
+        if (d.res2_scal_stride < 3) return KS_E_STRIDE;
+        if (d.Cin != 64 || d.Cout != 64 || d.ldx != 64 || d.x_coff != 0) return KS_E_UNSUPPORTED;
+        if (!conv3x3_res2_form(d.H, d.W, d.B)) return KS_E_FORM;
+    }
+    if (p.xout_lp && !conv3x3_strip_form(p)) return KS_E_FORM;                // written by the strip forms only
+    if (p.x_bf16) {
+        if (d.pro_stats) { if (!conv3x3_bf16_xb_supported(d.Cin, d.Cout)) return KS_E_UNSUPPORTED; }
+        else if (d.res_w && d.Cout == 128) { if (!conv3x3_plain_lp_in_supported(d.H, d.W, d.B, d.Cin, d.Cout) && !conv3x3_strip_form(p)) return KS_E_FORM; }
+        else if (d.res_w) { if (!conv3x3_cat_lp_in_supported(d.H, d.W, d.B, d.Cin, d.Cout)) return KS_E_FORM; }
+        else if (!(d.Cin == 64 && d.Cout == 64 && conv3x3_strip_form(p))) return KS_E_FORM;      // plain 16-bit input: the ping-pong form
+    }
+    return KS_OK;
+}
+
+// 1 = this descriptor is valid AND runs on one of the strip-walking forms (conv3x3_strip_form); 0 = valid, a patch form; < 0 = error
+int ks_conv3x3_strip_form(const KsConv3* d) {
+    if (!d) return KS_E_NULL;
+    if (!lp_prec(d->precision)) return KS_E_PREC;
+    WsplitScope ws(d->precision);
+    Conv3P p;
+    const int rc = conv3_fill(*d, p);
+    if (rc != KS_OK) return rc;
+    return conv3x3_strip_form(p) ? 1 : 0;
+}
+
+int ks_conv3x3(const KsConv3* d, void* stream, char* sym, int sym_len) {
+    if (!d) return KS_E_NULL;
+    if (!lp_prec(d->precision)) return KS_E_PREC;
+    WsplitScope ws(d->precision);
+    Conv3P p;
+    const int rc = conv3_fill(*d, p);
+    if (rc != KS_OK) return rc;
+    g_last_symbol = nullptr;
+    launch_conv3x3_lp(p, d->precision, (hipStream_t)stream);
+    put_symbol(sym, sym_len);
+    return KS_OK;
+}
+
+// ---- Downsample: Conv2d(64, 64, 3, 2, 1) on x * mask ------------------------------------------------------------------------
+int ks_conv_down(const KsConvDown* d, void* stream, char* sym, int sym_len) {
+    if (!d) return KS_E_NULL;
+    if (!lp_prec(d->precision)) return KS_E_PREC;
+    WsplitScope ws(d->precision);
+    if (d->H <= 0 || d->W <= 0 || d->B <= 0 || d->inmask_ws < 1 || d->mask_bstride < 0) return KS_E_SHAPE;
+    if (!d->X || !d->Wfrag || !d->bias || !d->inmask || !d->Y) return KS_E_NULL;
+    if (d->x_coff < 0 || d->y_coff < 0 || d->y_coff % 8 != 0 || d->ldx < d->x_coff + d->C || d->ldy < d->y_coff + d->C) return KS_E_STRIDE;
+    if (d->xb < (long long)d->H * d->W * d->ldx) return KS_E_STRIDE;
+    if (!conv_down_supported(d->C, d->H, d->W, d->ldx, d->ldy, d->x_coff)) return KS_E_UNSUPPORTED;
+    ConvDownP p{};
+    p.X = d->X; p.a_lp = d->a_lp ? 1 : 0; p.ldx = d->ldx; p.xb = (long)d->xb; p.x_coff = d->x_coff; p.H = d->H; p.W = d->W;
+    p.Wfrag = d->Wfrag; p.bias = (const float*)d->bias;
+    p.Y = d->Y; p.c_lp = d->c_lp ? 1 : 0; p.ldy = d->ldy; p.y_coff = d->y_coff;
+    p.inmask = (const float*)d->inmask; p.inmask_ws = d->inmask_ws; p.mask_bstride = (long)d->mask_bstride; p.B = d->B;
+    g_last_symbol = nullptr;
+    launch_conv_down(p, d->precision, (hipStream_t)stream);
+    put_symbol(sym, sym_len);
+    return KS_OK;
+}
+
+// ---- Upsample: ConvTranspose2d(64, 64, 4, 2, 1) on x * mask -----------------------------------------------------------------
+int ks_convt_up(const KsConvTUp* d, void* stream, char* sym, int sym_len) {
+    if (!d) return KS_E_NULL;
+    if (!lp_prec(d->precision)) return KS_E_PREC;
+    WsplitScope ws(d->precision);
+    if (d->H <= 0 || d->W <= 0 || d->B <= 0 || d->inmask_ws < 1 || d->mask_bstride < 0) return KS_E_SHAPE;
+    if (!d->X || !d->Wfrag0 || !d->Wfrag1 || !d->Wfrag2 || !d->Wfrag3 || !d->bias || !d->inmask || !d->Y) return KS_E_NULL;
+    if (d->x_coff < 0 || d->y_coff < 0 || d->x_coff % 8 != 0 || d->y_coff % 8 != 0 || d->ldx < d->x_coff + d->C || d->ldy < d->y_coff + d->C) return KS_E_STRIDE;
+    if (d->xb < (long long)d->H * d->W * d->ldx) return KS_E_STRIDE;
+    if (!convt_up_supported(d->C, d->H, d->W, d->ldx, d->ldy)) return KS_E_UNSUPPORTED;
+    ConvTUpP p{};
+    p.X = d->X; p.a_lp = d->a_lp ? 1 : 0; p.ldx = d->ldx; p.xb = (long)d->xb; p.x_coff = d->x_coff; p.H = d->H; p.W = d->W;
+    p.Wfrag[0] = d->Wfrag0; p.Wfrag[1] = d->Wfrag1; p.Wfrag[2] = d->Wfrag2; p.Wfrag[3] = d->Wfrag3; p.bias = (const float*)d->bias;
+    p.Y = d->Y; p.c_lp = d->c_lp ? 1 : 0; p.ldy = d->ldy; p.y_coff = d->y_coff;
+    p.inmask = (const float*)d->inmask; p.inmask_ws = d->inmask_ws; p.mask_bstride = (long)d->mask_bstride; p.B = d->B;
+    g_last_symbol = nullptr;
+    launch_convt_up(p, d->precision, (hipStream_t)stream);
+    put_symbol(sym, sym_len);
+    return KS_OK;
+}
+
+}  // extern "C"

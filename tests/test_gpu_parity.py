@@ -375,7 +375,10 @@ def test_bf16_mfma_mode_tolerance(name, kw, prec):
 def test_bf16_mode_full_size_shapes(name, kw):
     """The BASELINE.json-sized shapes pick kernel variants the small oracle cases never reach (key-split attention
     partials merged by the row chain, the batch-regime attention kernel, multi-sub-tile context passes): single
-    EDMPrecond call in bf16 mode AND in fp32 mode, both against the CPU oracle."""
+    EDMPrecond call in bf16 mode AND in fp32 mode, both against the CPU oracle.  A single call records taps, which keeps the
+    16-bit intermediates off (dex_api.hip: lp_inter): the batch-regime convolution forms that read or write them (x_bf16 on a plain
+    input, y_bf16 / a_lp / c_lp between stages, xout_lp, the 16-bit concatenation buffer) are NOT reached here - sampler calls
+    reach them, and tests/test_gpu_conv_kernels.py runs each as one launch."""
     cfg, eng, w = U.engine_for(name)
     case = U.make_case(cfg, **kw)
     try:
