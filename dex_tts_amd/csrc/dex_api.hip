@@ -35,7 +35,7 @@ const char* const KNOB_NAMES[] = {
     "DEX_ATTN_SHARED_W8", "DEX_CONVT_MT", "DEX_CONVT_WGS", "DEX_CONV_DOWN_WGS", "DEX_CONV_REGW", "DEX_CONV_REGW_RES", "DEX_CONV_SMALL_MAX", "DEX_CONV_TH8",
     "DEX_CONV_W8", "DEX_DWCONV_CAP", "DEX_FINAL_CAP", "DEX_FIRST_CAP", "DEX_FIRST_MFMA", "DEX_GEMM_NWALK", "DEX_NWALK_SPLIT", "DEX_NWALK_BM", "DEX_POS_COL", "DEX_POS_COL_MIN",
     "DEX_POS_CT", "DEX_REGW_MIN_TILES", "DEX_REGW_WGS", "DEX_ROWCHAIN64", "DEX_ROWCHAIN64A", "DEX_TIV_CAP", "DEX_TV_CHAIN", "DEX_TIV_FOLD", "DEX_LINATTN_NSUB", "DEX_TV_FOLD", "DEX_OUT2_MIN", "DEX_NWALK_DMA",
-    "DEX_LINATTN_HEADWAVES", "DEX_LINATTN_OUT2_HW", "DEX_CONV_ROUND1", "DEX_CONV_RESIDENT"};
+    "DEX_LINATTN_HEADWAVES", "DEX_LINATTN_OUT2_HW", "DEX_CONV_ROUND1", "DEX_CONV_RESIDENT", "DEX_KVCTX_ROWS", "DEX_OUT2_ROWS"};
 constexpr int N_KNOBS = (int)(sizeof(KNOB_NAMES) / sizeof(KNOB_NAMES[0]));
 // value of one variable: a decimal integer; unset, empty or without digits ("true", "on") = KNOB_UNSET, so a typo leaves the default
 // form on instead of silently switching it off
@@ -1100,7 +1100,8 @@ struct Runner {
             // measured at 80x512, B=1: 320 / 160 / 80 workgroups -> context 19.9 / 13.7 / 19.4 us, merge 8.7 / 6.1 / 4.7 us
             // head-parallel form (tools/kvctx_stamps, back-to-back launches, nsub = 1 / 2 / 4): 80x512 C = 64 16.5 / 12.8 / 17.0 us (4-wave form
             // 18.1 / 16.8 / 23.1), 40x256 C = 128 11.9 / 17.5 / 28.8 (17.4 / 23.6 / 35.6), 40x256 C = 64 8.8 / 12.1 / 17.7 (13.0 / 16.1 / 22.8):
-            // the rule below still picks the fastest count
+            // the rule below still picks the fastest count; so it does with the rows moved as contiguous wave requests (DEX_KVCTX_ROWS):
+            // 15.5 / 11.7 / 16.1 us, 10.3 / 14.3 / 22.2, 8.2 / 10.5 / 15.8
             while (nsub < 4 && (npix + 128 * nsub - 1) / (128 * nsub) * B > 192) nsub *= 2;
             {
                 // Batch regime (round 5): the grid is several rounds of the chip's workgroup slots - two per CU at C = 64, ONE at C = 128
@@ -1129,6 +1130,8 @@ struct Runner {
             // the head-parallel form of the context pass (16 waves, one head each) while the grid fits in one round of the chip's CUs - the
             // latency regime (B = 1..3); the batch forms keep the 4-wave one.  DEX_LINATTN_HEADWAVES: 0 = never, 1 = always.
             k.headwaves = knob_or("DEX_LINATTN_HEADWAVES", (long)nblk * B <= device_cus() ? 1 : 0) != 0 ? 1 : 0;
+            // ... with its prologue rows moved as contiguous wave requests.  DEX_KVCTX_ROWS: 0 = lane = pixel.
+            k.rows = knob_or("DEX_KVCTX_ROWS", 1) != 0 ? 1 : 0;
             // x = the ResnetBlock output the context pass materialises has ONE reader, the tail kernel below, which rounds it to the
             // operand type for its q GEMM anyway and adds it back as the residual term: at batch size it is stored in that type
             // (half of the write + read; the residual term then carries the operand rounding - NOT bit-identical to the fp32
@@ -1144,6 +1147,8 @@ struct Runner {
             // the wave-split tail (4 waves per 32-pixel slot) wherever the direct form would run - the latency regime, B = 1..3 at 40x256;
             // the throughput form keeps the larger grids (and every 16-bit x / y).  DEX_LINATTN_OUT2_HW: 0 = never, 1 = wherever x and y are fp32.
             o.hw = knob_or("DEX_LINATTN_OUT2_HW", linattn_out2_lp_out_supported((int)npix, B) ? 0 : 1) != 0 ? 1 : 0;
+            // ... with x loaded and y stored as whole pixel rows.  DEX_OUT2_ROWS: 0 = lane = pixel.
+            o.rows = knob_or("DEX_OUT2_ROWS", 1) != 0 ? 1 : 0;
             run("linattn_out", 4.0 * npix * B * 128.0 * X.C, ((out_lp ? 6.0 : 8.0) - (xlp ? 2.0 : 0.0) + (out2_lp ? 2.0 : 0.0)) * npix * X.C * B, [&] { launch_linattn_out2(o, x->precision, st); });
             return;
         }

@@ -267,6 +267,7 @@ struct LinKvCtxP { const float* X; int ldx; int x_coff; long xb; int npix; int C
                    int res_lp;                              // res is stored in the mode's 16-bit type [npix][C] (written by Conv3P::xout_lp)
                    int xout_lp;     long wkv_lo_off = 0;        // split-weight mode: elements from a weight of Wkv to its lo half
                    int headwaves = 0;                       // the head-parallel form (small grids, linattn_fused.hip), where the build has it
+                   int rows = 0;                            // head-parallel form: the prologue's items dealt in memory order (contiguous wave requests)
                    long long* dbg = nullptr;                // optional phase stamps, DEX_TIMING builds only (tools/kvctx_stamps)
 };                          // Xout is written in the mode's 16-bit type (its one reader, the tail kernel, takes LinOut2P::x_lp)
 void launch_linattn_kvctx(const LinKvCtxP& p, int precision, hipStream_t st);
@@ -279,6 +280,7 @@ struct LinOut2P { const float* X; int ldx; int x_coff; long xb; int npix; int C;
                   void* Y2; int ldy2; int y2_coff; long y2b;   // optional second copy of Y in the mode's 16-bit type (throughput form only): the skip half of the up path's concatenation buffer
                   int x_lp;     long wq_lo_off = 0;         // split-weight mode: elements from a weight of Wq to its lo half
                   int hw = 0;                               // the wave-split latency form (fp32 X and Y only, linattn_fused.hip) instead of the direct one
+                  int rows = 0;                             // wave-split form: x loaded and y stored as whole pixel rows (contiguous wave requests)
                   long long* dbg = nullptr;                 // optional phase stamps, DEX_TIMING builds only (tools/out2_stamps)
                   };      // 1: X is stored in the mode's 16-bit type [npix][C] (throughput form only; written by LinKvCtxP::xout_lp)
 void launch_linattn_out2(const LinOut2P& p, int precision, hipStream_t st);

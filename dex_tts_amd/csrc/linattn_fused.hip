@@ -464,9 +464,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C == 64 ? 2
 // bits - and the LDS merge walks the same (h, d, e) space in the same wave order with four times the threads.
 // Not in the split-weight build at C = 128: two weight images (139 KB) and the x image do not fit in the 160 KB of LDS.
 // grid (nblk, B); 1024 threads.
-template <int C, bool PRO, int FL = -1>
+// ROWS (launcher: DEX_KVCTX_ROWS): the prologue's 8-channel items dealt in memory order instead of lane = pixel.  The slot's four
+// head-waves (256 lanes) take the sub-tile's 32 * C / 8 items as it = k * 256 + hd * 64 + lane, pixel it / (C / 8), channels
+// 8 * (it % (C / 8)): a wave instruction on 16-bit rows is one contiguous 1 KB (8 lines, all of each used) where lane = pixel touches 32
+// lines for 32 B of each - and so does each of the slot's other three head-waves.  The prologue is elementwise, so every element sees the
+// same operations, and the x image, Xout and everything after the barrier are the same bits.
+template <int C, bool PRO, int FL = -1, bool ROWS = false>
 __global__ __launch_bounds__(1024) void linattn_kvctx_hw_kernel(const LinKvCtxP p) {
-    constexpr int LDW = C + 8, KS = C / 16, KQ = KS / 4;      // KQ: K-steps of the prologue per head-wave
+    constexpr int LDW = C + 8, KS = C / 16, KQ = KS / 4;      // KQ: K-steps (ROWS: items) of the prologue per head-wave lane
+    constexpr int O8 = C / 8;                                  // 8-channel items per pixel row
 #ifdef DEX_LP_WSPLIT
     constexpr int NWI = 2;                                     // hi + lo weight images
 #else
@@ -520,47 +526,55 @@ __global__ __launch_bounds__(1024) void linattn_kvctx_hw_kernel(const LinKvCtxP 
     const float* mrow = PRO ? p.mask + (long)b * p.mask_bstride : nullptr;
     const int px_base = (blk * 4 + slot) * p.nsub * 32;
     const int ch0 = hd * KQ * 16 + hh * 8;                     // this lane's first prologue channel
+    // item k of this lane: pixel (of the sub-tile) and first channel
+    auto ipx = [&](int k) { return ROWS ? (hd * 64 + lane) / O8 + k * (256 / O8) : i; };
+    auto ich = [&](int k) { return ROWS ? 8 * (lane % O8) : ch0 + k * 16; };
 
     f32x16 ctxT;
     float m_run = -INFINITY, s_run = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) ctxT[r] = 0.f;
     float4 xa[KQ], xc[KQ], ra[PRO ? KQ : 1], rc[PRO ? KQ : 1];
-    float mkv = 1.f;
+    float mkv[ROWS ? KQ : 1];                                  // the mask value of each item's pixel (lane = pixel: one)
+#pragma unroll
+    for (int k = 0; k < (ROWS ? KQ : 1); ++k) mkv[k] = 1.f;
     const bool hb = FL >= 0 ? (FL & 1) != 0 : (PRO && p.h2_bf16 != 0);
     const bool rlp = FL >= 0 ? (FL & 2) != 0 : (PRO && p.res_lp != 0);
     const bool xlp = FL >= 0 ? (FL & 4) != 0 : (p.xout_lp != 0);
     const unsigned short* Rh = (PRO && p.res) ? reinterpret_cast<const unsigned short*>(p.res) + (long)b * p.resb : nullptr;
     const unsigned short* Xh = PRO ? reinterpret_cast<const unsigned short*>(p.H2) + (long)b * p.npix * C : nullptr;
-    // this lane's quarter of the raw rows of one sub-tile (pixel px0 + i, channels ch0 + 16 ks .. +8)
+    // this lane's items of the raw rows of one sub-tile (lane = pixel: pixel px0 + i, channels ch0 + 16 ks .. +8), addresses clamped
     auto load_rows = [&](int px0) {
-        const int pxr = min(px0 + i, p.npix - 1);
+        int pxr[KQ];
+#pragma unroll
+        for (int k = 0; k < KQ; ++k) pxr[k] = min(px0 + ipx(k), p.npix - 1);
         if (hb) {
 #pragma unroll
-            for (int ks = 0; ks < KQ; ++ks) { xa[ks] = *reinterpret_cast<const float4*>(Xh + (long)pxr * C + ch0 + ks * 16); xc[ks] = xa[ks]; }
+            for (int k = 0; k < KQ; ++k) { xa[k] = *reinterpret_cast<const float4*>(Xh + (long)pxr[k] * C + ich(k)); xc[k] = xa[k]; }
         } else {
-            const float* xr = X + (long)pxr * ldx + ch0;
 #pragma unroll
-            for (int ks = 0; ks < KQ; ++ks) {
-                xa[ks] = *reinterpret_cast<const float4*>(xr + ks * 16);
-                xc[ks] = *reinterpret_cast<const float4*>(xr + ks * 16 + 4);
+            for (int k = 0; k < KQ; ++k) {
+                const float* xr = X + (long)pxr[k] * ldx + ich(k);
+                xa[k] = *reinterpret_cast<const float4*>(xr);
+                xc[k] = *reinterpret_cast<const float4*>(xr + 4);
             }
         }
         if constexpr (PRO) {
             if (R) {
                 if (rlp) {
 #pragma unroll
-                    for (int ks = 0; ks < KQ; ++ks) { ra[ks] = *reinterpret_cast<const float4*>(Rh + (long)pxr * p.ldres + ch0 + ks * 16); rc[ks] = ra[ks]; }
+                    for (int k = 0; k < KQ; ++k) { ra[k] = *reinterpret_cast<const float4*>(Rh + (long)pxr[k] * p.ldres + ich(k)); rc[k] = ra[k]; }
                 } else {
-                    const float* rr = R + (long)pxr * p.ldres + ch0;
 #pragma unroll
-                    for (int ks = 0; ks < KQ; ++ks) {
-                        ra[ks] = *reinterpret_cast<const float4*>(rr + ks * 16);
-                        rc[ks] = *reinterpret_cast<const float4*>(rr + ks * 16 + 4);
+                    for (int k = 0; k < KQ; ++k) {
+                        const float* rr = R + (long)pxr[k] * p.ldres + ich(k);
+                        ra[k] = *reinterpret_cast<const float4*>(rr);
+                        rc[k] = *reinterpret_cast<const float4*>(rr + 4);
                     }
                 }
             }
-            mkv = mrow[(pxr % p.W) * p.mask_ws];
+#pragma unroll
+            for (int k = 0; k < (ROWS ? KQ : 1); ++k) mkv[k] = mrow[(pxr[k] % p.W) * p.mask_ws];
         }
     };
     load_rows(px_base);
@@ -593,20 +607,22 @@ __global__ __launch_bounds__(1024) void linattn_kvctx_hw_kernel(const LinKvCtxP 
     for (int sub = 0; sub < p.nsub; ++sub) {
         const int px0 = px_base + sub * 32;
         const bool act = px0 < p.npix;
-        u16* xs = Xs + ((slot * 2 + (sub & 1)) * 32 + i) * LDW;
+        u16* xsb = Xs + (slot * 2 + (sub & 1)) * 32 * LDW;     // the slot's image of this sub-tile; xs: this lane's fragment row
+        const u16* xs = xsb + i * LDW;
         if (act) {
             if constexpr (PRO) {
                 const bool under = FL >= 0 ? (FL & 8) != 0 : (p.res_under_mask != 0);
-                const bool live = px0 + i < p.npix;
-                const long orow = (long)b * p.npix + min(px0 + i, p.npix - 1);
 #pragma unroll
-                for (int ks = 0; ks < KQ; ++ks)
-                    kv_prologue8(p, xa[ks], xc[ks], ra[ks], rc[ks], gsc_s, gsh_s, ch0 + ks * 16, hb, rlp, R != nullptr, under, xlp, mkv, live, orow);
+                for (int k = 0; k < KQ; ++k) {
+                    const bool live = px0 + ipx(k) < p.npix;
+                    const long orow = (long)b * p.npix + min(px0 + ipx(k), p.npix - 1);
+                    kv_prologue8(p, xa[k], xc[k], ra[k], rc[k], gsc_s, gsh_s, ich(k), hb, rlp, R != nullptr, under, xlp, mkv[ROWS ? k : 0], live, orow);
+                }
             }
 #pragma unroll
-            for (int ks = 0; ks < KQ; ++ks)
-                *reinterpret_cast<uint4*>(xs + ch0 + ks * 16) =
-                    make_uint4(pack2_lp(xa[ks].x, xa[ks].y), pack2_lp(xa[ks].z, xa[ks].w), pack2_lp(xc[ks].x, xc[ks].y), pack2_lp(xc[ks].z, xc[ks].w));
+            for (int k = 0; k < KQ; ++k)
+                *reinterpret_cast<uint4*>(xsb + ipx(k) * LDW + ich(k)) =
+                    make_uint4(pack2_lp(xa[k].x, xa[k].y), pack2_lp(xa[k].z, xa[k].w), pack2_lp(xc[k].x, xc[k].y), pack2_lp(xc[k].z, xc[k].w));
             if (sub + 1 < p.nsub) load_rows(px0 + 32);
         }
         KSTAMP(2);
@@ -665,26 +681,32 @@ static bool kvctx_hw_supported(int C) {
     return C == 64 || C == 128;
 #endif
 }
-template <int CC>
+template <int CC, bool ROWS>
 static void launch_kvctx_hw(const LinKvCtxP& p, int fl, bool pro, dim3 grid, size_t lds, hipStream_t st) {
     constexpr int LDS_HW = 144 * 1024;
     static bool attr = false;
     if (!attr) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&linattn_kvctx_hw_kernel<CC, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HW);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&linattn_kvctx_hw_kernel<CC, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HW);
-#define KVHW_ATTR(F) hipFuncSetAttribute(reinterpret_cast<const void*>(&linattn_kvctx_hw_kernel<CC, true, F>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HW);
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&linattn_kvctx_hw_kernel<CC, false, -1, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HW);
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&linattn_kvctx_hw_kernel<CC, true, -1, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HW);
+#define KVHW_ATTR(F) hipFuncSetAttribute(reinterpret_cast<const void*>(&linattn_kvctx_hw_kernel<CC, true, F, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HW);
         KVHW_ATTR(1) KVHW_ATTR(3) KVHW_ATTR(5) KVHW_ATTR(7) KVHW_ATTR(9) KVHW_ATTR(11) KVHW_ATTR(13) KVHW_ATTR(15)
 #undef KVHW_ATTR
         attr = true;
     }
-#define KVHW_CASE(F) case F: hipLaunchKernelGGL((linattn_kvctx_hw_kernel<CC, true, F>), grid, dim3(1024), lds, st, p); break;
+#define KVHW_CASE(F) case F: hipLaunchKernelGGL((linattn_kvctx_hw_kernel<CC, true, F, ROWS>), grid, dim3(1024), lds, st, p); break;
     switch (fl) {
         KVHW_CASE(1) KVHW_CASE(3) KVHW_CASE(5) KVHW_CASE(7) KVHW_CASE(9) KVHW_CASE(11) KVHW_CASE(13) KVHW_CASE(15)
         default:
-            if (pro) hipLaunchKernelGGL((linattn_kvctx_hw_kernel<CC, true>), grid, dim3(1024), lds, st, p);
-            else hipLaunchKernelGGL((linattn_kvctx_hw_kernel<CC, false>), grid, dim3(1024), lds, st, p);
+            if (pro) hipLaunchKernelGGL((linattn_kvctx_hw_kernel<CC, true, -1, ROWS>), grid, dim3(1024), lds, st, p);
+            else hipLaunchKernelGGL((linattn_kvctx_hw_kernel<CC, false, -1, ROWS>), grid, dim3(1024), lds, st, p);
     }
 #undef KVHW_CASE
+}
+// p.rows (DEX_KVCTX_ROWS): the memory-order deal of the prologue's items; 0 = lane = pixel
+template <int CC>
+static void launch_kvctx_hw(const LinKvCtxP& p, int fl, bool pro, dim3 grid, size_t lds, hipStream_t st) {
+    if (p.rows) launch_kvctx_hw<CC, true>(p, fl, pro, grid, lds, st);
+    else launch_kvctx_hw<CC, false>(p, fl, pro, grid, lds, st);
 }
 
 void launch_linattn_kvctx(const LinKvCtxP& p, hipStream_t st) {
@@ -935,27 +957,47 @@ __global__ __launch_bounds__(256) void linattn_out2_direct_kernel(const LinOut2P
 // At 40x256 the grid covers the CUs instead of 80 of them.  (Four slots per 16-wave workgroup, the same 80 workgroups as the direct form,
 // measured slower: 10.4 against 6.4 us at 40x256 C = 128 - DESIGN.md section 8.)
 // fp32 X and Y only (no x_lp / y_lp / Y2: the direct form's regime).  grid (ceil(npix / 32), B), 256 threads.
-template <int C>
+// ROWS (launcher: DEX_OUT2_ROWS): x and y move as whole pixel rows.  Wave t takes pixels 8t .. 8t + 7 of the slot: lane = (pixel, channel
+// octet) in memory order, so a wave instruction covers contiguous rows (8 x 512 B at C = 128 in two instructions per half octet) where
+// lane = pixel touches 32 lines per instruction.  It rounds each octet with the same pack2_lp into the same fragment image (the halves of
+// a K-step 33 entries apart: the octets of one pixel land on different banks), keeps its fp32 rows as the residual, and the epilogue goes
+// the same way back: the co tiles are staged as an fp32 image [32 px][C + 4], then every wave forms (y + residual) + bias for its eight
+// rows and stores them as contiguous requests.  The GEMM chains are untouched, the sums are the direct form's in the direct form's order.
+template <int C, bool ROWS = false>
 __global__ __launch_bounds__(256) void linattn_out2_hw_kernel(const LinOut2P p) {
-    constexpr int KS1 = C / 16, CT = C / 32, KQ = KS1 / 4;     // KQ: x K-steps loaded per wave
-    __shared__ uint4 xs[KS1][64], qs[8][64];                   // lane-indexed fragment images: conflict-free b128
+    constexpr int KS1 = C / 16, CT = C / 32, KQ = KS1 / 4;     // KQ: x K-steps (ROWS: row octets) loaded per wave lane
+    constexpr int O8 = C / 8, XH = ROWS ? 33 : 32, LDY = C + 4;
+    __shared__ uint4 xs[KS1][2 * XH], qs[8][64];               // lane-indexed fragment images: conflict-free b128
+    __shared__ __attribute__((aligned(16))) float ys[ROWS ? 32 * LDY : 4];      // ROWS: the y^T tiles as pixel rows
     KSTAMP_DECL
     const int tid = threadIdx.x, lane = tid & 63;
     const int t = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 31, hh = lane >> 5;
+    const int fi = hh * XH + i;                                // this lane's entry of a fragment image row
     const int b = blockIdx.y;
     const int px0 = blockIdx.x * 32;
     if (px0 >= p.npix) return;
     const float* X = p.X + (long)b * p.xb + p.x_coff;
     const int px = min(px0 + i, p.npix - 1);
+    // ROWS: item k of this lane = pixel 8t + rp0 + k * (64 / O8) of the slot, channels rch .. rch + 7
+    const int rp0 = 8 * t + lane / O8, rch = 8 * (lane % O8);
     // every global load of the wave at entry: its x quarter, its Wq tile, its W2 co tile (+ C = 64: its residual rows), the bias
     float4 xa[KQ], xc[KQ];
-    const float* xr = X + (long)px * p.ldx + hh * 8;
+    if constexpr (ROWS) {
 #pragma unroll
-    for (int k = 0; k < KQ; ++k) {
-        const int ks = t * KQ + k;
-        xa[k] = *reinterpret_cast<const float4*>(xr + ks * 16);
-        xc[k] = *reinterpret_cast<const float4*>(xr + ks * 16 + 4);
+        for (int k = 0; k < KQ; ++k) {
+            const float* xr = X + (long)min(px0 + rp0 + k * (64 / O8), p.npix - 1) * p.ldx + rch;
+            xa[k] = *reinterpret_cast<const float4*>(xr);
+            xc[k] = *reinterpret_cast<const float4*>(xr + 4);
+        }
+    } else {
+        const float* xr = X + (long)px * p.ldx + hh * 8;
+#pragma unroll
+        for (int k = 0; k < KQ; ++k) {
+            const int ks = t * KQ + k;
+            xa[k] = *reinterpret_cast<const float4*>(xr + ks * 16);
+            xc[k] = *reinterpret_cast<const float4*>(xr + ks * 16 + 4);
+        }
     }
     const uint4* wq = reinterpret_cast<const uint4*>(p.Wq) + lane;                  // bf16, fragment order [he tile][K-step][lane][8]
     uint4 wqf[KS1];
@@ -977,6 +1019,12 @@ __global__ __launch_bounds__(256) void linattn_out2_hw_kernel(const LinOut2P p) 
     if (g2) {
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) w2f[ks] = w2[(ct * 8 + ks) * 64];
+    }
+    if constexpr (ROWS) {
+        // the bias of this lane's octet (every item of a lane has the same channels)
+        bia[0] = *reinterpret_cast<const float4*>(p.bias + rch);
+        bia[1] = *reinterpret_cast<const float4*>(p.bias + rch + 4);
+    } else if (g2) {
         if constexpr (C != 128) {
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) res[g4] = *reinterpret_cast<const float4*>(X + (long)px * p.ldx + ct * 32 + 8 * g4 + 4 * hh);
@@ -995,15 +1043,16 @@ __global__ __launch_bounds__(256) void linattn_out2_hw_kernel(const LinOut2P p) 
         }
     }
     KSTAMP(0);
-    // ---- x quarter -> the slot's fragment image
+    // ---- x quarter (ROWS: x rows) -> the slot's fragment image
 #pragma unroll
     for (int k = 0; k < KQ; ++k) {
         LFrag f;
         f.u.x = pack2_lp(xa[k].x, xa[k].y); f.u.y = pack2_lp(xa[k].z, xa[k].w);
         f.u.z = pack2_lp(xc[k].x, xc[k].y); f.u.w = pack2_lp(xc[k].z, xc[k].w);
-        xs[t * KQ + k][lane] = f.u;
+        if constexpr (ROWS) xs[rch >> 4][((rch >> 3) & 1) * XH + rp0 + k * (64 / O8)] = f.u;
+        else xs[t * KQ + k][fi] = f.u;
     }
-    if constexpr (C == 128) {
+    if constexpr (C == 128 && !ROWS) {
         // wave t's x quarter is channels 32t .. 32t + 31 of its pixel = the residual of co tile t: lane half hh holds channels
         // 16k + 8hh + 0..7 (k = 0, 1) and needs 8 g4 + 4hh + 0..3; the halves swap the 4 channels the other one needs (exact copies)
 #pragma unroll
@@ -1024,7 +1073,7 @@ __global__ __launch_bounds__(256) void linattn_out2_hw_kernel(const LinOut2P p) 
         for (int r = 0; r < 16; ++r) q[r] = 0.f;
 #pragma unroll
         for (int ks = 0; ks < KS1; ++ks) {
-            LFrag af, xf; af.u = wqf[ks]; xf.u = xs[ks][lane];
+            LFrag af, xf; af.u = wqf[ks]; xf.u = xs[ks][fi];
             q = DEX_MFMA_LP(af.v, xf.v, q, 0, 0, 0);
 #ifdef DEX_LP_WSPLIT
             LFrag al; al.u = wql[ks];
@@ -1042,19 +1091,41 @@ __global__ __launch_bounds__(256) void linattn_out2_hw_kernel(const LinOut2P p) 
     KSTAMP(2);
     lds_barrier();
     KSTAMP(3);
-    if (!g2) return;
+    if constexpr (!ROWS) { if (!g2) return; }
     // ---- GEMM2 + epilogue of co tile t: rows co = ct*32 + (r&3) + 8*(r>>2) + 4*hh  ->  4 consecutive channels per register quad
     f32x16 y;
+    if (g2) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) y[r] = 0.f;
+        for (int r = 0; r < 16; ++r) y[r] = 0.f;
 #pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-        LFrag af, qf; af.u = w2f[ks]; qf.u = qs[ks][lane];
-        y = DEX_MFMA_LP(af.v, qf.v, y, 0, 0, 0);
+        for (int ks = 0; ks < 8; ++ks) {
+            LFrag af, qf; af.u = w2f[ks]; qf.u = qs[ks][lane];
+            y = DEX_MFMA_LP(af.v, qf.v, y, 0, 0, 0);
+        }
     }
     KSTAMP(4);
     float* Y = p.Y + (long)b * p.yb + p.y_coff;
-    if (px0 + i < p.npix) {
+    if constexpr (ROWS) {
+        if (g2) {
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4)
+                *reinterpret_cast<float4*>(ys + i * LDY + ct * 32 + 8 * g4 + 4 * hh) = make_float4(y[g4 * 4 + 0], y[g4 * 4 + 1], y[g4 * 4 + 2], y[g4 * 4 + 3]);
+        }
+        lds_barrier();                                         // the slot's y image is complete
+#pragma unroll
+        for (int k = 0; k < KQ; ++k) {
+            const int rp = rp0 + k * (64 / O8);
+            const float4 ya = *reinterpret_cast<const float4*>(ys + rp * LDY + rch), yc = *reinterpret_cast<const float4*>(ys + rp * LDY + rch + 4);
+            if (px0 + rp < p.npix) {
+                float4 oa, oc;
+                oa.x = ya.x + xa[k].x + bia[0].x; oa.y = ya.y + xa[k].y + bia[0].y; oa.z = ya.z + xa[k].z + bia[0].z; oa.w = ya.w + xa[k].w + bia[0].w;
+                oc.x = yc.x + xc[k].x + bia[1].x; oc.y = yc.y + xc[k].y + bia[1].y; oc.z = yc.z + xc[k].z + bia[1].z; oc.w = yc.w + xc[k].w + bia[1].w;
+                float* yr = Y + (long)(px0 + rp) * p.ldy + rch;
+                *reinterpret_cast<float4*>(yr) = oa;
+                *reinterpret_cast<float4*>(yr + 4) = oc;
+            }
+        }
+    } else if (px0 + i < p.npix) {
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
             const int co = ct * 32 + 8 * g4 + 4 * hh;
@@ -1226,8 +1297,13 @@ void launch_linattn_out2(const LinOut2P& p, hipStream_t st) {
     if (p.hw && !lp_io) {                              // the wave-split latency form (launcher: DEX_LINATTN_OUT2_HW)
         g_last_symbol = "linattn_out2_hw_kernel";
         const dim3 g1((p.npix + 31) / 32, p.B);
-        if (p.C == 64) hipLaunchKernelGGL(linattn_out2_hw_kernel<64>, g1, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(linattn_out2_hw_kernel<128>, g1, dim3(256), 0, st, p);
+        if (p.rows) {                                  // x and y as whole pixel rows (launcher: DEX_OUT2_ROWS)
+            if (p.C == 64) hipLaunchKernelGGL((linattn_out2_hw_kernel<64, true>), g1, dim3(256), 0, st, p);
+            else hipLaunchKernelGGL((linattn_out2_hw_kernel<128, true>), g1, dim3(256), 0, st, p);
+            return;
+        }
+        if (p.C == 64) hipLaunchKernelGGL((linattn_out2_hw_kernel<64, false>), g1, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((linattn_out2_hw_kernel<128, false>), g1, dim3(256), 0, st, p);
         return;
     }
     if ((long)grid.x * p.B < out2_min_wgs()) {        // latency regime: the direct form

@@ -1,6 +1,7 @@
 // kvctx_stamps: the linear-attention context pass (linattn_fused.hip) at the three B = 1 shapes of GeDEX-LJ, both forms (4-wave /
 // head-parallel), with the PRO prologue of the preceding ResnetBlock: event time per launch, the -DDEX_TIMING phase stamps of thread 0
-// of every workgroup (mean over workgroups, in counter ticks), an nsub sweep, and a bitwise check of the two forms (partials + Xout).
+// of every workgroup (mean over workgroups, in counter ticks), an nsub sweep, and a bitwise check of the forms (partials + Xout).  The
+// head-parallel form runs with both deals of its prologue rows: lane = pixel, and the items in memory order (LinKvCtxP::rows).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DDEX_TIMING -DDEX_LP_NS_OVERRIDE=kvst -I dex_tts_amd/csrc \
 //         tools/kvctx_stamps.hip dex_tts_amd/csrc/linattn_fused.hip -o tools/kvctx_stamps
 #include <hip/hip_runtime.h>
@@ -50,11 +51,12 @@ int main() {
         k.mask = upload(mask); k.mask_ws = 1; k.mask_bstride = s.W; k.W = s.W; k.Xout = reinterpret_cast<float*>(xo);
         k.h2_bf16 = (s.fl & 1) ? 1 : 0; k.res_lp = 0; k.xout_lp = (s.fl & 4) ? 1 : 0;
         printf("== %s\n", s.name);
-        std::vector<float> ref[2];
+        std::vector<float> ref[3];
         for (int nsub : {1, 2, 4}) {
             k.nsub = nsub; k.nblk = (npix + 128 * nsub - 1) / (128 * nsub);
-            for (int hw : {0, 1}) {
-                k.headwaves = hw; k.dbg = nullptr;
+            for (int form : {0, 1, 2}) {                   // 4-wave, head-parallel lane = pixel, head-parallel rows in memory order
+                const int hw = form > 0;
+                k.headwaves = hw; k.rows = form == 2; k.dbg = nullptr;
                 hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
                 for (int i = 0; i < 5; ++i) kvst::launch_linattn_kvctx(k, 0);
                 hipDeviceSynchronize();
@@ -62,7 +64,7 @@ int main() {
                 for (int i = 0; i < 100; ++i) kvst::launch_linattn_kvctx(k, 0);
                 hipEventRecord(b, 0); hipEventSynchronize(b);
                 float ms; hipEventElapsedTime(&ms, a, b);
-                printf("  nsub=%d %-13s %4d wgs  %7.2f us/launch (back to back)\n", nsub, hw ? "head-parallel" : "4-wave", k.nblk, ms * 10.f);
+                printf("  nsub=%d %-14s %4d wgs  %7.2f us/launch (back to back)\n", nsub, form == 2 ? "head-par. rows" : hw ? "head-parallel" : "4-wave", k.nblk, ms * 10.f);
                 if (nsub != s.nsub) continue;
                 hipMemset(dbg, 0, (size_t)maxblk * 64);
                 k.dbg = dbg; kvst::launch_linattn_kvctx(k, 0); hipDeviceSynchronize(); k.dbg = nullptr;
@@ -79,12 +81,13 @@ int main() {
                 hipMemcpy(out.data() + nc, pm, nm * 4, hipMemcpyDeviceToHost);
                 hipMemcpy(out.data() + nc + nm, ps, nm * 4, hipMemcpyDeviceToHost);
                 hipMemcpy(out.data() + nc + 2 * nm, xo, nx * (k.xout_lp ? 2 : 4), hipMemcpyDeviceToHost);
-                ref[hw] = out;
+                ref[form] = out;
             }
         }
-        const bool same = ref[0].size() == ref[1].size() && memcmp(ref[0].data(), ref[1].data(), ref[0].size() * 4) == 0;
-        printf("  bitwise partials + Xout, head-parallel vs 4-wave at nsub=%d: %s\n", s.nsub, same ? "IDENTICAL" : "DIFFERENT");
-        if (!same) {
+        for (int form : {1, 2}) {
+            const bool same = ref[0].size() == ref[form].size() && memcmp(ref[0].data(), ref[form].data(), ref[0].size() * 4) == 0;
+            printf("  bitwise partials + Xout, %s vs 4-wave at nsub=%d: %s\n", form == 2 ? "head-parallel rows" : "head-parallel", s.nsub, same ? "IDENTICAL" : "DIFFERENT");
+            if (same) continue;
             const int nblk = (npix + 128 * s.nsub - 1) / (128 * s.nsub);
             const size_t nc = (size_t)4 * nblk * 1024, nm = (size_t)4 * nblk * 32;
             const size_t cut[5] = {0, nc, nc + nm, nc + 2 * nm, ref[0].size()};
@@ -92,7 +95,7 @@ int main() {
             for (int q = 0; q < 4; ++q) {
                 size_t n = 0, first = 0; double mx = 0;
                 for (size_t j = cut[q]; j < cut[q + 1]; ++j)
-                    if (memcmp(&ref[0][j], &ref[1][j], 4)) { if (!n++) first = j - cut[q]; mx = std::max(mx, (double)fabsf(ref[0][j] - ref[1][j])); }
+                    if (memcmp(&ref[0][j], &ref[form][j], 4)) { if (!n++) first = j - cut[q]; mx = std::max(mx, (double)fabsf(ref[0][j] - ref[form][j])); }
                 printf("    %s: %zu of %zu differ, first %zu, max |d| %.3e\n", part[q], n, cut[q + 1] - cut[q], first, mx);
             }
             bad = 1;

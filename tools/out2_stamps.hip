@@ -1,5 +1,6 @@
 // out2_stamps: the linear-attention tail (linattn_fused.hip) at the three B = 1 shapes of GeDEX-LJ, fp32 x and y (the latency regime's
-// operands): the direct form, the wave-split form (one 32-pixel slot per 4-wave workgroup) and at 80x512 the throughput form.  Event
+// operands): the direct form, the wave-split form (one 32-pixel slot per 4-wave workgroup; lane = pixel, and x / y as whole pixel rows:
+// LinOut2P::rows) and at 80x512 the throughput form.  Event
 // time per launch (back to back), the -DDEX_TIMING phase stamps of thread 0 of every workgroup (mean over workgroups, counter ticks: thread 0 = the wave of he tile 0 / co tile 0), and a bitwise check against the direct form.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DDEX_TIMING -DDEX_LP_NS_OVERRIDE=o2st -I dex_tts_amd/csrc \
 //         tools/out2_stamps.hip dex_tts_amd/csrc/linattn_fused.hip -o tools/out2_stamps
@@ -22,12 +23,12 @@ template <class T> static T* upload(const std::vector<T>& h) { T* d; hipMalloc(&
 static float val(size_t i, float s) { return s * ((float)((i * 2654435761u) % 1000) / 1000.f - 0.5f); }
 
 struct Shape { const char* name; int H, W, C; };
-struct Form { const char* name; int hw, out2_min; };
+struct Form { const char* name; int hw, out2_min, rows; };
 
 int main() {
     int bad = 0;
     const Shape shapes[] = {{"40x256 C=128", 40, 256, 128}, {"40x256 C=64", 40, 256, 64}, {"80x512 C=64", 80, 512, 64}};
-    const Form forms[] = {{"direct", 0, 1 << 30}, {"wave-split", 1, 1 << 30}, {"throughput", 0, 0}};
+    const Form forms[] = {{"direct", 0, 1 << 30, 0}, {"wave-split", 1, 1 << 30, 0}, {"wave-split rows", 1, 1 << 30, 1}, {"throughput", 0, 0, 0}};
     const char* phase[6] = {"loads issued", "x exchange", "GEMM1", "q exchange", "GEMM2", "epilogue"};
     for (const Shape& s : shapes) {
         const int npix = s.H * s.W, C = s.C, CT = C / 32;
@@ -47,7 +48,7 @@ int main() {
         for (const Form& f : forms) {
             if (f.out2_min == 0 && s.H != 80) continue;
             char mn[32]; snprintf(mn, sizeof mn, "%d", f.out2_min); setenv("DEX_OUT2_MIN", mn, 1);
-            o.hw = f.hw; o.dbg = nullptr;
+            o.hw = f.hw; o.rows = f.rows; o.dbg = nullptr;
             const int wgs = f.hw ? (npix + 31) / 32 : (npix + 127) / 128;
             hipMemset(y, 0, (size_t)npix * C * 4);
             hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
