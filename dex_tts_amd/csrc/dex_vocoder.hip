@@ -18,6 +18,13 @@
 // bands: 48 and 24; HiFi-GAN V2: 16 and 8) runs its ResBlock convs and the transposed conv into it on direct exact-fp32 kernels, and
 // its anti-aliased activations on the lane-packed aa_snake; those kernels stay fp32 in the bf16 / fp16 modes.  Every other width
 // takes the implicit GEMM as before.
+//
+// Ragged batches (dex_vocode_ragged): utterance b of a batch ends at lengths[b] frames, i.e. at Lb = lengths[b] * R samples in a layer
+// whose cumulative rate is R, and is vocoded as if it had been passed alone.  Every producer stores zeros at positions >= Lb - the
+// implicit GEMMs through their output mask (one 0 / 1 row per rate, built on the device from the lengths), the element-wise and narrow
+// kernels from the lengths themselves - so the next layer's taps read the zero padding the alone run sees (leaky_relu(0) = 0, the
+// residual is zero there too); the anti-aliased activation also ends its two replicate paddings at Lb.  Same kernels, same per-element
+// operation order as dex_vocode, which is this call without lengths.
 #include <hip/hip_runtime.h>
 #include <string>
 #include <vector>
@@ -199,8 +206,8 @@ int dex_voc_set_precision(DexVoc* v, int precision) {
 }  // extern "C"
 
 namespace {
-struct VPlan { float *mel, *x, *y, *a, *q, *s, *p[3]; size_t bytes; };
-void voc_plan(const DexVoc* v, int B, int T, void* ws, VPlan& P) {
+struct VPlan { float *mel, *x, *y, *a, *q, *s, *p[3], *mask[7]; size_t bytes; };      // mask[i]: [B][T R_i], R_0 = 1 (conv_pre), R_i = rate of stage i - 1
+void voc_plan(const DexVoc* v, int B, int T, bool ragged, void* ws, VPlan& P) {
     const DexVocoderConfig& c = v->cfg;
     // largest activation [B][L][C] and ConvTranspose GEMM output [B][L_in][k*Cout] over the stages
     size_t act = (size_t)B * T * c.upsample_initial_channel, ymax = 0;
@@ -218,13 +225,19 @@ void voc_plan(const DexVoc* v, int B, int T, void* ws, VPlan& P) {
     P.s = v->big() ? take(act) : nullptr;                 // output of the anti-aliased activation in front of a conv
     for (int j = 0; j < 3; ++j) P.p[j] = take(act);
     P.y = take(ymax);
+    long R = 1;
+    for (int i = 0; i <= 6; ++i) {                         // (behind everything else: the plain call's plan is a prefix of the ragged one)
+        const bool used = ragged && i <= c.n_upsamples && (i == 0 || !voc_narrow_width(stage_ch(c, i - 1)));
+        if (i > 0 && i <= c.n_upsamples) R *= c.upsample_rates[i - 1];
+        P.mask[i] = used ? take((size_t)B * T * R) : nullptr;
+    }
     P.bytes = (off + 255) & ~size_t(255);
 }
 // the weight operands of a GEMM in mode `prec`: the fp32 pack, and in the bf16 / fp16 modes its 16-bit copy
 void voc_weight(IGemmP& g, const PackedW& w, int prec) {
     g.W = w.f32; g.Wbf = prec == DEX_PREC_BF16 ? w.nk[0].p : prec == DEX_PREC_FP16 ? w.nk[1].p : nullptr;
 }
-IGemmP conv1d(const float* X, int L, int B, const VConv& c, float slope, float* out, const float* res, int prec) {
+IGemmP conv1d(const float* X, int L, int B, const VConv& c, float slope, float* out, const float* res, int prec, const float* mask) {
     IGemmP g{};
     g.A = X; g.lda = c.cin; g.a_bstride = (long)L * c.cin; g.a_coff = 0;
     g.Hi = 1; g.Wi = L; g.Cin = c.cin;
@@ -235,18 +248,21 @@ IGemmP conv1d(const float* X, int L, int B, const VConv& c, float slope, float* 
     g.C = out; g.ldc = c.cout; g.c_bstride = (long)L * c.cout; g.c_coff = 0;
     g.OHf = 1; g.OWf = L; g.osh = 1; g.osw = 1;
     g.inmask_ws = 1; g.outmask_ws = 1; g.gate_nstride = 1;
+    g.outmask = mask; g.mask_bstride = L;               // ragged: zeros past the utterance's end (applied after bias and residual)
     g.act_in_slope = slope;
     g.res = res; g.ldres = c.cout; g.res_bstride = (long)L * c.cout;
     g.B = B;
     return g;
 }
+// a ragged batch's lengths at one layer: the device frame counts (null: full length), the layer's rate, its GEMM output mask
+struct VLen { const int* len; int R; const float* mask; };
 // one ResBlock conv: the implicit GEMM, or the direct kernel at a narrow width
-void voc_conv(const float* X, int L, int B, const VConv& c, float slope, float* out, const float* res, int prec, hipStream_t st) {
+void voc_conv(const float* X, int L, int B, const VConv& c, float slope, float* out, const float* res, int prec, const VLen& vl, hipStream_t st) {
     if (c.narrow) {
-        NarrowConvP n{X, c.w.f32, c.b, res, out, L, c.cout, c.k, c.dil, B, slope};
+        NarrowConvP n{X, c.w.f32, c.b, res, out, L, c.cout, c.k, c.dil, B, slope, vl.len, vl.R};
         launch_narrow_conv1d(n, st);
     } else {
-        launch_igemm(conv1d(X, L, B, c, slope, out, res, prec), prec, st);
+        launch_igemm(conv1d(X, L, B, c, slope, out, res, prec, vl.mask), prec, st);
     }
 }
 void voc_aa_snake(const AaSnakeP& s, hipStream_t st) {
@@ -258,28 +274,48 @@ extern "C" {
 
 size_t dex_voc_workspace_bytes(const DexVoc* v, int B, int T) {
     if (!v || B < 1 || T < 1) return 0;
-    VPlan P; voc_plan(v, B, T, nullptr, P);
+    VPlan P; voc_plan(v, B, T, false, nullptr, P);
+    return P.bytes;
+}
+
+size_t dex_voc_ragged_workspace_bytes(const DexVoc* v, int B, int T) {
+    if (!v || B < 1 || T < 1) return 0;
+    VPlan P; voc_plan(v, B, T, true, nullptr, P);
     return P.bytes;
 }
 
 int dex_vocode(DexVoc* v, const float* mel_dev, int B, int T, float* wav_dev, void* ws, size_t ws_bytes, dex_stream_t stream) {
+    return dex_vocode_ragged(v, mel_dev, nullptr, B, T, wav_dev, ws, ws_bytes, stream);
+}
+
+int dex_vocode_ragged(DexVoc* v, const float* mel_dev, const int32_t* len, int B, int T, float* wav_dev, void* ws, size_t ws_bytes,
+                      dex_stream_t stream) {
     if (!v || !mel_dev || !wav_dev || !ws) return DEX_ERR_ARG;
     if (!v->finalized) return v->fail(DEX_ERR_STATE, "dex_voc_finalize has not been called");
     if (B < 1 || T < 1) return v->fail(DEX_ERR_ARG, "B and T must be >= 1");
     if (((uintptr_t)ws & 255) != 0) return v->fail(DEX_ERR_ARG, "workspace must be 256-byte aligned");
-    VPlan P; voc_plan(v, B, T, nullptr, P);
+    const bool ragged = len != nullptr;
+    VPlan P; voc_plan(v, B, T, ragged, nullptr, P);
     if (P.bytes > ws_bytes) return v->fail(DEX_ERR_WORKSPACE, "vocoder workspace too small: need %zu bytes, got %zu", P.bytes, ws_bytes);
-    voc_plan(v, B, T, ws, P);
+    voc_plan(v, B, T, ragged, ws, P);
     hipStream_t st = (hipStream_t)stream;
     const DexVocoderConfig& c = v->cfg;
     const int prec = v->precision;
-    launch_mel_to_cl(mel_dev, P.mel, B, c.num_mels, T, MEL_LD, st);
-    launch_igemm(conv1d(P.mel, T, B, v->pre, 0.f, P.x, nullptr, prec), prec, st);                  // conv_pre
+    if (ragged) {          // the GEMMs' output masks, one per rate (the narrow stages read the lengths themselves)
+        int R = 1;
+        for (int i = 0; i <= c.n_upsamples; ++i) {
+            if (i > 0) R *= c.upsample_rates[i - 1];
+            if (P.mask[i]) launch_voc_len_mask(len, P.mask[i], B, T, R, st);
+        }
+    }
+    launch_mel_to_cl(mel_dev, P.mel, B, c.num_mels, T, MEL_LD, st, len);
+    launch_igemm(conv1d(P.mel, T, B, v->pre, 0.f, P.x, nullptr, prec, P.mask[0]), prec, st);       // conv_pre
     long L = T;
+    int R = 1;               // cumulative rate: the layer holds L = T * R samples, utterance b's end at lengths[b] * R
     for (int i = 0; i < c.n_upsamples; ++i) {
         const VUp& up = v->ups[i];
         if (up.narrow) {     // ConvTranspose1d into a narrow stage: one direct kernel
-            NarrowConvTP n{P.x, up.w.f32, up.b, P.a, (int)L, up.cin, up.cout, up.k, up.u, up.pad, B, v->big() ? 0.f : 0.1f};
+            NarrowConvTP n{P.x, up.w.f32, up.b, P.a, (int)L, up.cin, up.cout, up.k, up.u, up.pad, B, v->big() ? 0.f : 0.1f, len, R};
             launch_narrow_convt(n, st);
         } else {   // ConvTranspose1d(leaky_relu(x, 0.1)): GEMM + overlap-add
             IGemmP g{};
@@ -288,11 +324,12 @@ int dex_vocode(DexVoc* v, const float* mel_dev, int B, int T, float* wav_dev, vo
             voc_weight(g, up.w, prec); g.N = up.k * up.cout; g.K = up.cin; g.ksplit = 1; g.groups = 1;
             g.C = P.y; g.ldc = g.N; g.c_bstride = L * g.N; g.OHf = 1; g.OWf = (int)L; g.osh = 1; g.osw = 1;
             g.inmask_ws = 1; g.outmask_ws = 1; g.gate_nstride = 1; g.act_in_slope = v->big() ? 0.f : 0.1f; g.B = B;     // BigVGAN: no activation here
-            launch_igemm(g, prec, st);
-            ConvTFoldP f{P.y, up.b, P.a, (int)L, up.cout, up.k, up.u, up.pad, B};
+            launch_igemm(g, prec, st);          // (ragged: x is zero past the utterance's end and the GEMM has no bias, so Y is zero there)
+            ConvTFoldP f{P.y, up.b, P.a, (int)L, up.cout, up.k, up.u, up.pad, B, len, R};
             launch_convt_fold(f, st);
         }
-        L *= up.u;
+        L *= up.u; R *= up.u;
+        const VLen vl{len, R, P.mask[i + 1]};
         // three ResBlocks on the stage input P.a; block j's result ends in P.p[j]
         for (int j = 0; j < 3; ++j) {
             const VConv* cv = &v->rb[(size_t)(i * 3 + j) * 6];
@@ -301,15 +338,15 @@ int dex_vocode(DexVoc* v, const float* mel_dev, int B, int T, float* wav_dev, vo
                 float* dst = (m == 1) ? P.q : P.p[j];                   // x -> p[j] -> q -> p[j]
                 if (v->big()) {      // AMPBlock1 (bigvgan/models.py:76-85): xt = c1(a_{2m}(x)); x = c2(a_{2m+1}(xt)) + x
                     const size_t ai = ((size_t)(i * 3 + j) * 6) + 2 * m;
-                    AaSnakeP s1{cur, P.s, (int)L, up.cout, B, v->act_a[ai], v->act_ib[ai], v->filt};
+                    AaSnakeP s1{cur, P.s, (int)L, up.cout, B, v->act_a[ai], v->act_ib[ai], v->filt, len, R};
                     voc_aa_snake(s1, st);
-                    voc_conv(P.s, (int)L, B, cv[2 * m], 0.f, P.x, nullptr, prec, st);
-                    AaSnakeP s2{P.x, P.s, (int)L, up.cout, B, v->act_a[ai + 1], v->act_ib[ai + 1], v->filt};
+                    voc_conv(P.s, (int)L, B, cv[2 * m], 0.f, P.x, nullptr, prec, vl, st);
+                    AaSnakeP s2{P.x, P.s, (int)L, up.cout, B, v->act_a[ai + 1], v->act_ib[ai + 1], v->filt, len, R};
                     voc_aa_snake(s2, st);
-                    voc_conv(P.s, (int)L, B, cv[2 * m + 1], 0.f, dst, cur, prec, st);
+                    voc_conv(P.s, (int)L, B, cv[2 * m + 1], 0.f, dst, cur, prec, vl, st);
                 } else {
-                    voc_conv(cur, (int)L, B, cv[2 * m], 0.1f, P.x, nullptr, prec, st);           // xt = c1(lrelu(x))
-                    voc_conv(P.x, (int)L, B, cv[2 * m + 1], 0.1f, dst, cur, prec, st);           // x = c2(lrelu(xt)) + x
+                    voc_conv(cur, (int)L, B, cv[2 * m], 0.1f, P.x, nullptr, prec, vl, st);          // xt = c1(lrelu(x))
+                    voc_conv(P.x, (int)L, B, cv[2 * m + 1], 0.1f, dst, cur, prec, vl, st);          // x = c2(lrelu(xt)) + x
                 }
                 cur = dst;
             }
@@ -318,11 +355,11 @@ int dex_vocode(DexVoc* v, const float* mel_dev, int B, int T, float* wav_dev, vo
     }
     const float* xin = P.x;
     if (v->big()) {          // activation_post (models.py:205) replaces the leaky_relu in front of conv_post
-        AaSnakeP sp{P.x, P.s, (int)L, stage_ch(c, c.n_upsamples - 1), B, v->act_a.back(), v->act_ib.back(), v->filt};
+        AaSnakeP sp{P.x, P.s, (int)L, stage_ch(c, c.n_upsamples - 1), B, v->act_a.back(), v->act_ib.back(), v->filt, len, R};
         voc_aa_snake(sp, st);
         xin = P.s;
     }
-    ConvPostP cp{xin, v->post_w, v->post_b, wav_dev, (int)L, stage_ch(c, c.n_upsamples - 1), B, v->big() ? 1.f : 0.01f};
+    ConvPostP cp{xin, v->post_w, v->post_b, wav_dev, (int)L, stage_ch(c, c.n_upsamples - 1), B, v->big() ? 1.f : 0.01f, len, R};
     launch_conv_post_tanh(cp, st);
     DEX_HIPCHK(v, hipGetLastError());
     return DEX_OK;

@@ -486,30 +486,37 @@ void launch_tv_chain(const TvChainP& p, int precision, hipStream_t st);
 void launch_transpose_cl(const float* src, float* dst, int B, int C, int L, int row_off, long dst_bstride, hipStream_t st);
 
 // HiFi-GAN generator pieces (dex_vocoder.hip; reference hifigan/models.py:112-173) --------------------
-// mel [B,80,T] -> channels-last [B,T,ldc] with the channels past 80 zeroed (the implicit GEMM wants Cin % 32 == 0)
-void launch_mel_to_cl(const float* mel, float* out, int B, int C, int T, int ldc, hipStream_t st);
+// Ragged batches (dex_vocode_ragged): `len` = B device int32 frame counts, or null for "every utterance is full length"; `R` = the
+// layer's cumulative up-sampling rate.  Utterance b ends at Lb = clamp(len[b], 0, L / R) * R (vocoder_len.h): taps at or past Lb read
+// as the zero padding a run of that utterance alone would see, outputs at or past Lb are stored as 0.
+// mel [B,80,T] -> channels-last [B,T,ldc] with the channels past 80 zeroed (the implicit GEMM wants Cin % 32 == 0); frames at or past
+// len[b] are zeros whatever the caller left there
+void launch_mel_to_cl(const float* mel, float* out, int B, int C, int T, int ldc, hipStream_t st, const int* len = nullptr);
+// mask[b][t] = t < Lb ? 1 : 0 for t in [0, T R): the implicit GEMM's output mask (IGemmP::outmask) of a layer at rate R
+void launch_voc_len_mask(const int* len, float* mask, int B, int T, int R, hipStream_t st);
 // ConvTranspose1d(k, stride u, padding (k-u)/2) after its GEMM Y[l][j*Cout + co] = sum_ci x[l][ci] w[ci][co][j]:
 // out[t][co] = bias[co] + sum_{j = (t+pad) mod u, +u, .. < k} Y[(t+pad-j)/u][j][co]   (0 <= (t+pad-j)/u < L)
-struct ConvTFoldP { const float* Y; const float* bias; float* out; int L, Cout, k, u, pad, B; };
+struct ConvTFoldP { const float* Y; const float* bias; float* out; int L, Cout, k, u, pad, B; const int* len; int R; };   // R: rate of the INPUT (length L)
 void launch_convt_fold(const ConvTFoldP& p, hipStream_t st);
 // x = (a + b + c) * (1/3)  (the three ResBlocks of a stage, models.py:158-164); n floats
 void launch_avg3(const float* a, const float* b, const float* c, float* out, long n, hipStream_t st);
 // wav[t] = tanh(bias + sum_{tap<7} sum_{c<C} w[tap][c] * leaky_relu(x[t+tap-3][c], 0.01))   (models.py:165-167)
-struct ConvPostP { const float* X; const float* W; const float* bias; float* wav; int L, C, B; float slope; };   // leaky_relu slope on the input (1 = none)
+struct ConvPostP { const float* X; const float* W; const float* bias; float* wav; int L, C, B; float slope; const int* len; int R; };   // leaky_relu slope on the input (1 = none)
 // BigVGAN anti-aliased periodic activation (alias_free_torch/act.py:23-28): y = downsample2(snake(upsample2(x))) per channel, channels-last
 // [B][L][C]; a[c] = frequency, inv_b[c] = 1 / (magnitude + 1e-9) (already exponentiated when the checkpoint is log-scale); filt = the 12-tap
 // Kaiser-sinc low-pass of both resamplers
-struct AaSnakeP { const float* X; float* Y; int L, C, B; const float* a; const float* inv_b; const float* filt; };
+// ragged: both replicate paddings end at the utterance's own last sample (Lb - 1, 2 Lb - 1)
+struct AaSnakeP { const float* X; float* Y; int L, C, B; const float* a; const float* inv_b; const float* filt; const int* len; int R; };
 void launch_aa_snake(const AaSnakeP& p, hipStream_t st);
 void launch_snake_coeffs(const float* alpha, const float* beta, float* a, float* inv_b, int C, int logscale, hipStream_t st);
 void launch_conv_post_tanh(const ConvPostP& p, hipStream_t st);
 // narrow stages (vocoder_narrow.hip): C % 8 == 0, C <= 64, C % 32 != 0 — direct exact-fp32 kernels in every precision mode.
 bool voc_narrow_width(int C);
 // Conv1d(C -> C, k, dil, same padding) on leaky_relu(X, slope) (0: X as stored) + bias (+ res); W packed [tap][ci][co]
-struct NarrowConvP { const float* X; const float* W; const float* bias; const float* res; float* Y; int L, C, k, dil, B; float slope; };
+struct NarrowConvP { const float* X; const float* W; const float* bias; const float* res; float* Y; int L, C, k, dil, B; float slope; const int* len; int R; };
 void launch_narrow_conv1d(const NarrowConvP& p, hipStream_t st);
 // ConvTranspose1d(Cin -> C, k, stride u, pad) on leaky_relu(X, slope), GEMM and overlap-add fused; W packed [ci][j][co]; X [B][L][Cin] -> Y [B][L u][C]
-struct NarrowConvTP { const float* X; const float* W; const float* bias; float* Y; int L, Cin, C, k, u, pad, B; float slope; };
+struct NarrowConvTP { const float* X; const float* W; const float* bias; float* Y; int L, Cin, C, k, u, pad, B; float slope; const int* len; int R; };   // R: rate of the INPUT
 void launch_narrow_convt(const NarrowConvTP& p, hipStream_t st);
 // aa_snake with the channel lanes packed (256 / C groups per block); the same per-element arithmetic as launch_aa_snake
 void launch_aa_snake_narrow(const AaSnakeP& p, hipStream_t st);

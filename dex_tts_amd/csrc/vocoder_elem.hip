@@ -2,21 +2,35 @@
 // implicit-GEMM convolutions: mel layout change, ConvTranspose1d overlap-add, ResBlock average, conv_post + tanh.
 // Activations are channels-last fp32 [B][L][C].
 #include "kernels.h"
+#include "vocoder_len.h"
 
 namespace dex {
 
-__global__ __launch_bounds__(256) void mel_to_cl_kernel(const float* mel, float* out, int B, int C, int T, int ldc) {
+__global__ __launch_bounds__(256) void mel_to_cl_kernel(const float* mel, float* out, int B, int C, int T, int ldc, const int* len) {
     const long total = (long)B * T * ldc;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const int c = (int)(i % ldc);
         const long bt = i / ldc;
         const int t = (int)(bt % T), b = (int)(bt / T);
-        out[i] = c < C ? mel[((long)b * C + c) * T + t] : 0.f;
+        // a select, not a product: whatever the caller left past the utterance's length (NaN included) is not read into the result
+        out[i] = (c < C && t < voc_valid_len(len, b, 1, T)) ? mel[((long)b * C + c) * T + t] : 0.f;
     }
 }
-void launch_mel_to_cl(const float* mel, float* out, int B, int C, int T, int ldc, hipStream_t st) {
+void launch_mel_to_cl(const float* mel, float* out, int B, int C, int T, int ldc, hipStream_t st, const int* len) {
     long blocks = ((long)B * T * ldc + 255) / 256; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(mel_to_cl_kernel, dim3((unsigned)blocks), dim3(256), 0, st, mel, out, B, C, T, ldc);
+    hipLaunchKernelGGL(mel_to_cl_kernel, dim3((unsigned)blocks), dim3(256), 0, st, mel, out, B, C, T, ldc, len);
+}
+
+__global__ __launch_bounds__(256) void voc_len_mask_kernel(const int* len, float* mask, int B, int T, int R) {
+    const long L = (long)T * R, total = (long)B * L;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int b = (int)(i / L);
+        mask[i] = (i - b * L) < voc_valid_len(len, b, R, (int)L) ? 1.f : 0.f;
+    }
+}
+void launch_voc_len_mask(const int* len, float* mask, int B, int T, int R, hipStream_t st) {
+    long blocks = ((long)B * T * R + 255) / 256; if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(voc_len_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, st, len, mask, B, T, R);
 }
 
 // one thread = 4 consecutive output channels of one output position
@@ -29,17 +43,20 @@ __global__ __launch_bounds__(256) void convt_fold_kernel(const ConvTFoldP p) {
         const long bt = i / C4;
         const long t = bt % Lo;
         const int b = (int)(bt / Lo);
+        const int Lb = voc_valid_len(p.len, b, p.R, p.L);               // the utterance's input samples; its output ends at Lb * u
+        float4* dst = reinterpret_cast<float4*>(p.out + ((long)b * Lo + t) * p.Cout + c);
+        if (t >= (long)Lb * p.u) { *dst = make_float4(0.f, 0.f, 0.f, 0.f); continue; }
         float4 acc = *reinterpret_cast<const float4*>(p.bias + c);
         const float* Yb = p.Y + (long)b * p.L * p.k * p.Cout;
         // taps in ascending j, the order torch's col2im accumulates them in is not specified; two terms: commutative
         for (int j = (int)((t + p.pad) % p.u); j < p.k; j += p.u) {
             const long l = (t + p.pad - j) / p.u;
-            if (l >= 0 && l < p.L) {
+            if (l >= 0 && l < Lb) {
                 const float4 y = *reinterpret_cast<const float4*>(Yb + (l * p.k + j) * p.Cout + c);
                 acc.x += y.x; acc.y += y.y; acc.z += y.z; acc.w += y.w;
             }
         }
-        *reinterpret_cast<float4*>(p.out + ((long)b * Lo + t) * p.Cout + c) = acc;
+        *dst = acc;
     }
 }
 void launch_convt_fold(const ConvTFoldP& p, hipStream_t st) {
@@ -70,10 +87,12 @@ __global__ __launch_bounds__(256) void conv_post_tanh_kernel(const ConvPostP p) 
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long t = i % p.L;
         const int b = (int)(i / p.L);
+        const int Lb = voc_valid_len(p.len, b, p.R, p.L);
+        if (t >= Lb) { p.wav[i] = 0.f; continue; }                      // past the utterance: silence, not tanh(bias)
         float acc = p.bias[0];
         for (int tap = 0; tap < 7; ++tap) {
             const long tt = t + tap - 3;
-            if (tt < 0 || tt >= p.L) continue;
+            if (tt < 0 || tt >= Lb) continue;
             const float* x = p.X + ((long)b * p.L + tt) * p.C;
             for (int c = 0; c < p.C; c += 4) {
                 float4 v = *reinterpret_cast<const float4*>(x + c);
@@ -103,12 +122,18 @@ __global__ __launch_bounds__(256) void aa_snake_kernel(const AaSnakeP p) {
     __shared__ float f[12];
     const int tid = threadIdx.x, c = tid & 63, tl = tid >> 6;
     const int c0 = blockIdx.x * 64, t0 = blockIdx.y * AS_T, b = blockIdx.z;
+    const bool cok = c0 + c < p.C;
+    const int Lb = voc_valid_len(p.len, b, p.R, p.L);                 // both replicate paddings end at the utterance's own last sample
+    if (t0 >= Lb) {        // (uniform, before any barrier) a tile wholly past the utterance's end: zeros
+        if (cok)
+            for (int t = t0 + tl; t < min(t0 + AS_T, p.L); t += 4) p.Y[((long)b * p.L + t) * p.C + c0 + c] = 0.f;
+        return;
+    }
     if (tid < 12) f[tid] = p.filt[tid];
     __syncthreads();
-    const bool cok = c0 + c < p.C;
     const float a = cok ? p.a[c0 + c] : 0.f, ib = cok ? p.inv_b[c0 + c] : 0.f;
     const float* X = p.X + (long)b * p.L * p.C + (cok ? c0 + c : 0);
-    const int L2 = 2 * p.L;
+    const int L2 = 2 * Lb;
     for (int q = tl; q < AS_S; q += 4) {
         const int m = min(max(2 * t0 - 5 + q, 0), L2 - 1);            // the down-sampler's replicate padding
         float up = 0.f;
@@ -116,7 +141,7 @@ __global__ __launch_bounds__(256) void aa_snake_kernel(const AaSnakeP p) {
 #pragma unroll
         for (int jj = 0; jj < 6; ++jj) {
             const int j = j0 + jj, k = m + 15 - 2 * j;                // k in [0, 11] for these six j (m + 15 - 2 j0 is 10 or 11)
-            const int xi = min(max(j - 5, 0), p.L - 1);
+            const int xi = min(max(j - 5, 0), Lb - 1);
             if (k >= 0) up = fmaf(X[(long)xi * p.C], f[k], up);
         }
         up *= 2.f;
@@ -132,7 +157,7 @@ __global__ __launch_bounds__(256) void aa_snake_kernel(const AaSnakeP p) {
         float acc = 0.f;
 #pragma unroll
         for (int k = 0; k < 12; ++k) acc = fmaf(s[2 * tt + k][c], f[k], acc);
-        Y[(long)t * p.C] = acc;
+        Y[(long)t * p.C] = t < Lb ? acc : 0.f;
     }
 }
 void launch_aa_snake(const AaSnakeP& p, hipStream_t st) {

@@ -8,6 +8,7 @@
 // so they come through scalar loads into SGPRs — feed fmaf chains in (tap, input channel) order.  Exact fp32 in every precision
 // mode (dex_voc_set_precision's bf16 / fp16 modes round only the wide stages' operands); no atomics, so bitwise repeatable.
 #include "kernels.h"
+#include "vocoder_len.h"
 
 namespace dex {
 
@@ -24,19 +25,29 @@ __device__ __forceinline__ float lrelu(float v, float sl) { return v > 0.f ? v :
 // W packed [tap][ci][co] (dex_voc_finalize).  Grid: x = sample tiles of 256, y = C / CO output-channel chunks, z = batch.
 template <int C>
 __global__ __launch_bounds__(256) void narrow_conv1d_kernel(const float* __restrict__ X, const float* __restrict__ W, const float* __restrict__ bias,
-                                                            const float* __restrict__ res, float* __restrict__ Y, int L, int k, int dil, float slope) {
+                                                            const float* __restrict__ res, float* __restrict__ Y, int L, int k, int dil, float slope,
+                                                            const int* __restrict__ len, int R) {
     constexpr int CO = narrow_co<C>();
     static_assert(C % 8 == 0 && CO % 4 == 0, "narrow widths");
     const int l = blockIdx.x * 256 + threadIdx.x;
     const int co0 = blockIdx.y * CO, b = blockIdx.z;
     const float* Xb = X + (long)b * L * C;
+    const int Lb = voc_valid_len(len, b, R, L);                       // ragged batch: the utterance ends here (kernels.h)
+    const long row = ((long)b * L + l) * C + co0;
+    if (l >= Lb) {         // past the utterance's end: zeros, nothing loaded (a block wholly past it leaves here as one)
+        if (l < L) {
+#pragma unroll
+            for (int o = 0; o < CO; o += 4) *reinterpret_cast<float4*>(Y + row + o) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        return;
+    }
     const int half = dil * ((k - 1) / 2);
     float acc[CO];
 #pragma unroll
     for (int o = 0; o < CO; ++o) acc[o] = 0.f;
     for (int tap = 0; tap < k; ++tap) {
         const int li = l + tap * dil - half;
-        const bool ok = l < L && (unsigned)li < (unsigned)L;          // zero padding outside [0, L)
+        const bool ok = (unsigned)li < (unsigned)Lb;                  // zero padding outside [0, Lb)  (l < Lb <= L here)
         const float* xr = Xb + (long)(ok ? li : 0) * C;
         const float* wt = W + (long)tap * C * C + co0;
 #pragma unroll 1
@@ -50,8 +61,6 @@ __global__ __launch_bounds__(256) void narrow_conv1d_kernel(const float* __restr
                 for (int o = 0; o < CO; ++o) acc[o] = fmaf(xv[q], wt[(c4 + q) * C + o], acc[o]);
         }
     }
-    if (l >= L) return;
-    const long row = ((long)b * L + l) * C + co0;
 #pragma unroll
     for (int o = 0; o < CO; o += 4) {
         float4 r = make_float4(acc[o] + bias[co0 + o], acc[o + 1] + bias[co0 + o + 1], acc[o + 2] + bias[co0 + o + 2], acc[o + 3] + bias[co0 + o + 3]);
@@ -70,7 +79,8 @@ __global__ __launch_bounds__(256) void narrow_conv1d_kernel(const float* __restr
 // computes t = q u + r - pad.  Grid: x = q tiles of 256, y = u * (C / CO) (phase fastest), z = batch.
 template <int C>
 __global__ __launch_bounds__(256) void narrow_convt_kernel(const float* __restrict__ X, const float* __restrict__ W, const float* __restrict__ bias,
-                                                           float* __restrict__ Y, int L, int Cin, int k, int u, int pad, float slope) {
+                                                           float* __restrict__ Y, int L, int Cin, int k, int u, int pad, float slope,
+                                                           const int* __restrict__ len, int R) {
     constexpr int CO = narrow_co<C>();
     const int q = blockIdx.x * 256 + threadIdx.x;
     const int r = blockIdx.y % u, co0 = (blockIdx.y / u) * CO, b = blockIdx.z;
@@ -78,12 +88,21 @@ __global__ __launch_bounds__(256) void narrow_convt_kernel(const float* __restri
     const long t = (long)q * u + r - pad;
     const bool valid = t >= 0 && t < Lo;
     const float* Xb = X + (long)b * L * Cin;
+    const int Lb = voc_valid_len(len, b, R, L);                       // the utterance's input samples; its output ends at Lb * u
+    float* yr = Y + ((long)b * Lo + t) * C + co0;
+    if (t >= (long)Lb * u) {          // past the utterance's end: zeros, nothing loaded
+        if (valid) {
+#pragma unroll
+            for (int o = 0; o < CO; o += 4) *reinterpret_cast<float4*>(yr + o) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        return;
+    }
     float acc[CO];
 #pragma unroll
     for (int o = 0; o < CO; ++o) acc[o] = bias[co0 + o];
     for (int j = r; j < k; j += u) {
         const int l = q - (j - r) / u;
-        const bool ok = valid && l >= 0 && l < L;
+        const bool ok = valid && l >= 0 && l < Lb;
         const float* xr = Xb + (long)(ok ? l : 0) * Cin;
         const float* wj = W + (long)j * C + co0;
         float s[CO];
@@ -107,7 +126,6 @@ __global__ __launch_bounds__(256) void narrow_convt_kernel(const float* __restri
         }
     }
     if (!valid) return;
-    float* yr = Y + ((long)b * Lo + t) * C + co0;
 #pragma unroll
     for (int o = 0; o < CO; o += 4) *reinterpret_cast<float4*>(yr + o) = make_float4(acc[o], acc[o + 1], acc[o + 2], acc[o + 3]);
 }
@@ -122,12 +140,18 @@ __global__ __launch_bounds__(256) void aa_snake_narrow_kernel(const AaSnakeP p) 
     __shared__ float f[12];
     const int tid = threadIdx.x, c = tid % C, grp = tid / C;
     const int t0 = blockIdx.x * ASN_T, b = blockIdx.y;
+    const bool act = grp < G;
+    const int Lb = voc_valid_len(p.len, b, p.R, p.L);
+    if (t0 >= Lb) {        // (uniform, before any barrier) a tile wholly past the utterance's end: zeros
+        if (act)
+            for (int t = t0 + grp; t < min(t0 + ASN_T, p.L); t += G) p.Y[((long)b * p.L + t) * C + c] = 0.f;
+        return;
+    }
     if (tid < 12) f[tid] = p.filt[tid];
     __syncthreads();
-    const bool act = grp < G;
     const float a = p.a[c], ib = p.inv_b[c];
     const float* X = p.X + (long)b * p.L * C + c;
-    const int L2 = 2 * p.L;
+    const int L2 = 2 * Lb;
     if (act)
         for (int qi = grp; qi < ASN_S; qi += G) {
             const int m = min(max(2 * t0 - 5 + qi, 0), L2 - 1);
@@ -136,7 +160,7 @@ __global__ __launch_bounds__(256) void aa_snake_narrow_kernel(const AaSnakeP p) 
 #pragma unroll
             for (int jj = 0; jj < 6; ++jj) {
                 const int j = j0 + jj, kk = m + 15 - 2 * j;
-                const int xi = min(max(j - 5, 0), p.L - 1);
+                const int xi = min(max(j - 5, 0), Lb - 1);
                 if (kk >= 0) up = fmaf(X[(long)xi * C], f[kk], up);
             }
             up *= 2.f;
@@ -152,7 +176,7 @@ __global__ __launch_bounds__(256) void aa_snake_narrow_kernel(const AaSnakeP p) 
         float acc = 0.f;
 #pragma unroll
         for (int kk = 0; kk < 12; ++kk) acc = fmaf(s[2 * tt + kk][c], f[kk], acc);
-        Y[(long)t * C] = acc;
+        Y[(long)t * C] = t < Lb ? acc : 0.f;
     }
 }
 
@@ -160,14 +184,14 @@ template <int C>
 void conv1d_w(const NarrowConvP& p, hipStream_t st) {
     constexpr int CO = narrow_co<C>();
     hipLaunchKernelGGL(narrow_conv1d_kernel<C>, dim3((unsigned)((p.L + 255) / 256), C / CO, p.B), dim3(256), 0, st,
-                       p.X, p.W, p.bias, p.res, p.Y, p.L, p.k, p.dil, p.slope);
+                       p.X, p.W, p.bias, p.res, p.Y, p.L, p.k, p.dil, p.slope, p.len, p.R);
 }
 template <int C>
 void convt_w(const NarrowConvTP& p, hipStream_t st) {
     constexpr int CO = narrow_co<C>();
     const long nq = (long)p.L + (p.pad + p.u - 1) / p.u + 1;      // q = (t + pad - r) / u over t in [0, L u)
     hipLaunchKernelGGL(narrow_convt_kernel<C>, dim3((unsigned)((nq + 255) / 256), p.u * (C / CO), p.B), dim3(256), 0, st,
-                       p.X, p.W, p.bias, p.Y, p.L, p.Cin, p.k, p.u, p.pad, p.slope);
+                       p.X, p.W, p.bias, p.Y, p.L, p.Cin, p.k, p.u, p.pad, p.slope, p.len, p.R);
 }
 template <int C>
 void aa_w(const AaSnakeP& p, hipStream_t st) {

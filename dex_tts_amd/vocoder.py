@@ -152,9 +152,19 @@ class Generator(NativeModule):
         return sd
 
     @torch.no_grad()
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """mel [B, num_mels, T] -> wav [B, 1, T * prod(upsample_rates)] (models.py:150-167)."""
+    def forward(self, x: torch.Tensor, lengths=None) -> torch.Tensor:
+        """mel [B, num_mels, T] -> wav [B, 1, T * prod(upsample_rates)] (models.py:150-167).
+
+        ``lengths`` (a sequence or an integer tensor of B frame counts, on any device): a ragged batch.  Utterance b is vocoded exactly
+        as if it had been passed alone as ``x[b:b+1, :, :lengths[b]]`` (``dex_vocode_ragged``): its waveform ends at ``lengths[b] * hop``
+        and is exactly zero behind that, and whatever ``x`` holds past ``lengths[b]`` is ignored.  Without it the padded batch is
+        vocoded as one [B, T] tensor, and the padding (a log-mel of 0 is a loud frame) reaches the last frames of every shorter
+        utterance.  The lengths stay on the device: no host synchronisation."""
         dev = x.device
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths)
+            if lengths.numel() != x.shape[0] or lengths.is_floating_point():
+                raise ValueError(f"lengths must hold B = {x.shape[0]} integer frame counts, got {tuple(lengths.shape)} {lengths.dtype}")
         self._engine(dev)
         with torch.cuda.device(dev):
             # operand precision of the convolutions: 'fp32' (default, the parity mode), 'bf16' or 'fp16' (attribute ``precision``)
@@ -164,13 +174,20 @@ class Generator(NativeModule):
             if M != int(_get(self.h, "num_mels", 80)):
                 raise ValueError(f"mel has {M} channels, the generator expects {_get(self.h, 'num_mels', 80)}")
             n = int(self._lib.dex_voc_samples(self._ctx, T))
-            need = int(self._lib.dex_voc_workspace_bytes(self._ctx, B, T))
-            base, nbytes = self._workspace(need, dev)
             wav = torch.empty(B, 1, n, dtype=torch.float32, device=dev)
-            st = stream(dev)
-            self._check(self._lib.dex_vocode(self._ctx, C.c_void_p(mel.data_ptr()), B, T, C.c_void_p(wav.data_ptr()), C.c_void_p(base),
-                                             nbytes, st))
-            self._keep = mel
+            if lengths is None:
+                need = int(self._lib.dex_voc_workspace_bytes(self._ctx, B, T))
+                base, nbytes = self._workspace(need, dev)
+                self._check(self._lib.dex_vocode(self._ctx, C.c_void_p(mel.data_ptr()), B, T, C.c_void_p(wav.data_ptr()), C.c_void_p(base),
+                                                 nbytes, stream(dev)))
+                self._keep = mel
+            else:
+                ln = lengths.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+                need = int(self._lib.dex_voc_ragged_workspace_bytes(self._ctx, B, T))
+                base, nbytes = self._workspace(need, dev)
+                self._check(self._lib.dex_vocode_ragged(self._ctx, C.c_void_p(mel.data_ptr()), C.c_void_p(ln.data_ptr()), B, T,
+                                                        C.c_void_p(wav.data_ptr()), C.c_void_p(base), nbytes, stream(dev)))
+                self._keep = (mel, ln)
             return wav
 
 

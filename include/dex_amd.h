@@ -357,6 +357,15 @@ int  dex_voc_set_precision(DexVoc* voc, int precision);
  * Exact-fp32 MFMA contractions (the reference's arithmetic).  Asynchronous on `stream`. */
 int  dex_vocode(DexVoc* voc, const float* mel_dev, int B, int T, float* wav_dev, void* workspace_dev, size_t workspace_bytes,
                 dex_stream_t stream);
+/* Ragged batches: utterance b is vocoded exactly as if it had been passed alone at lengths_dev[b] frames - at every layer its sequence
+ * ends at lengths_dev[b] * R samples (R = the layer's cumulative up-sampling rate: zero padding for the convolutions, the anti-aliased
+ * activations' replicate padding from its own last sample) - and wav_dev[b, lengths_dev[b] * hop:] is exactly zero.  The content of
+ * mel_dev past an utterance's length is ignored (NaN included).  lengths_dev: B int32 frame counts ON THE DEVICE, each clamped to
+ * [0, T] by the kernels; nothing is copied to the host and nothing synchronises.  lengths_dev == NULL: every utterance is T frames
+ * long, the result is dex_vocode's.  Needs dex_voc_ragged_workspace_bytes (>= dex_voc_workspace_bytes; 0 for B < 1 or T < 1). */
+size_t dex_voc_ragged_workspace_bytes(const DexVoc* voc, int B, int T);
+int  dex_vocode_ragged(DexVoc* voc, const float* mel_dev, const int32_t* lengths_dev, int B, int T, float* wav_dev, void* workspace_dev,
+                       size_t workspace_bytes, dex_stream_t stream);
 
 /* ---- DEX style encoders (DEX-TTS/model/ref_encoder.py TVEncoder :110-140 + VQEmbeddingEMA :199-237, LF0Encoder
  * :36-55, TIVEncoder :83-108, DeXTTS.conv_sty tts.py:31) and the part of DeXTTS.forward that feeds the decoder (tts.py:55-66):

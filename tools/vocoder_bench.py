@@ -4,7 +4,11 @@ mode, with bench.py:vocoder_block's formula (every Conv1d / ConvTranspose1d as 2
 helper.  One JSON line per case on stdout; --out also writes them all to a file.
 
     python tools/vocoder_bench.py [--models hifigan_v1,bigvgan_base,bigvgan_22khz] [--batches 1,8] [--precisions fp32,bf16,fp16]
-                                  [--T 512] [--steps 10] [--warmup 3] [--out FILE]
+                                  [--T 512] [--steps 10] [--warmup 3] [--lengths LO:HI] [--out FILE]
+
+--lengths LO:HI: a ragged batch, utterance i holding int(T * (LO + (HI - LO) * ((7 i) % 11) / 10)) frames (0.6:1.0 is bench.py's ragged
+batch).  Each case is then timed twice on the same mel - the padded call ``gen(mel)`` and the ragged call ``gen(mel, lengths)``
+(dex_vocode_ragged, lengths on the device) - with ``valid_frames_per_s`` next to ``mel_frames_per_s`` (which counts the padding).
 """
 import argparse
 import json
@@ -37,16 +41,22 @@ def algorithmic_flops(h, T):
     return fl, stages
 
 
-def run(name, B, T, prec, steps, warmup, device):
+def ragged_lengths(B, T, lo, hi):
+    return [max(1, min(T, int(T * (lo + (hi - lo) * ((7 * i) % 11) / 10.0)))) for i in range(B)]
+
+
+def run(name, B, T, prec, steps, warmup, device, lengths=None):
+    """One case; ``lengths`` (B frame counts): the ragged call, else the padded one."""
     h = MODELS[name]
     gen = V.Generator(V.AttrDict(h))
     gen.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_vocoder_weights(V.param_shapes(h)).items()})
     gen = gen.to(device).eval()
     gen.precision = prec
     mel = torch.from_numpy(synth.make_inputs(B, T, None, seed=1234)[0]).to(device)
+    ln = None if lengths is None else torch.tensor(lengths, dtype=torch.int32, device=device)     # on the device once: no copy per call
     stream = torch.cuda.Stream(device)
     with torch.cuda.stream(stream):
-        dt, ev, wav = timed_calls(lambda: gen(mel), steps, warmup, device)
+        dt, ev, wav = timed_calls((lambda: gen(mel)) if ln is None else (lambda: gen(mel, ln)), steps, warmup, device)
     assert torch.isfinite(wav).all()
     fl, stages = algorithmic_flops(h, T)
     sec = dt / steps
@@ -55,6 +65,8 @@ def run(name, B, T, prec, steps, warmup, device):
            "hip_event_median_ms": round(statistics.median(ev), 3), "algorithmic_GFLOP": round(B * fl / 1e9, 1),
            "TFLOP_per_s": round(B * fl / sec / 1e12, 1), f"frac_of_{DTYPE_KEY[prec]}_mfma_peak": round(B * fl / sec / 1e12 / peak, 3),
            "stage_GFLOP": [round(B * s / 1e9, 1) for s in stages]}
+    if lengths is not None:
+        out.update(call="ragged", lengths=list(lengths), valid_frames_per_s=round(sum(lengths) / sec, 1))
     del gen
     torch.cuda.empty_cache()
     return out
@@ -68,16 +80,30 @@ def main():
     ap.add_argument("--T", type=int, default=512)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--lengths", default=None, metavar="LO:HI", help="ragged batch: lengths between LO * T and HI * T frames (bench.py's "
+                                                                     "ragged batch is 0.6:1.0); times the padded and the ragged call")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    frac = None
+    if a.lengths:
+        frac = tuple(float(v) for v in a.lengths.split(":"))
+        if len(frac) != 2 or not 0.0 <= frac[0] <= frac[1] <= 1.0:
+            ap.error("--lengths wants LO:HI with 0 <= LO <= HI <= 1")
     device = torch.device("cuda", 0)
     rows = []
     for name in a.models.split(","):
         for B in (int(b) for b in a.batches.split(",")):
             for prec in a.precisions.split(","):
                 r = run(name, B, a.T, prec, a.steps, a.warmup, device)
+                if frac:
+                    ln = ragged_lengths(B, a.T, *frac)
+                    r.update(call="padded", lengths=ln, valid_frames_per_s=round(sum(ln) * r["mel_frames_per_s"] / (B * a.T), 1))
                 print(json.dumps(r), flush=True)
                 rows.append(r)
+                if frac:
+                    r = run(name, B, a.T, prec, a.steps, a.warmup, device, ln)
+                    print(json.dumps(r), flush=True)
+                    rows.append(r)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
