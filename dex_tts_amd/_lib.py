@@ -149,6 +149,10 @@ SYMBOLS = [
     ("dex_vocode", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("dex_voc_ragged_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     ("dex_vocode_ragged", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("dex_voc_halo_frames", C.c_int, [C.c_void_p]),
+    ("dex_voc_window_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    ("dex_vocode_window", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                    C.c_size_t, C.c_void_p]),
     ("dex_style_create", C.c_int, [C.POINTER(DexStyleConfig), C.POINTER(C.c_void_p)]),
     ("dex_style_destroy", None, [C.c_void_p]),
     ("dex_style_last_error", C.c_char_p, [C.c_void_p]),

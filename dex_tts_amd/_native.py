@@ -92,10 +92,8 @@ class NativeModule(nn.Module):
             msg = self._fn("last_error")(self._ctx)
             raise RuntimeError(f"libdexamd {self.noun} error {rc}: {msg.decode() if msg else '?'}")
 
-    def _engine(self, device):
-        """Create the context once; upload the weights the library lists and finalize whenever a buffer changed since the last upload."""
-        if device.type != "cuda":
-            raise RuntimeError("dex_tts_amd runs on an AMD GPU (torch device 'cuda' on ROCm); no CPU path exists")
+    def _create(self):
+        """The context itself (host only: the configuration is checked, the weight inventory laid out; nothing touches a device)."""
         if self._ctx is None:
             self._lib = _lib.load()
             c = self._config()
@@ -103,6 +101,12 @@ class NativeModule(nn.Module):
             rc = self._fn("create")(C.byref(c), C.byref(ctx))
             self._ctx = ctx
             self._check(rc)
+
+    def _engine(self, device):
+        """Create the context once; upload the weights the library lists and finalize whenever a buffer changed since the last upload."""
+        if device.type != "cuda":
+            raise RuntimeError("dex_tts_amd runs on an AMD GPU (torch device 'cuda' on ROCm); no CPU path exists")
+        self._create()
         bufs = [getattr(self, k.replace(".", "__")) for k in self.shapes]
         key = (str(device),) + tuple((b._version, b.data_ptr()) for b in bufs)
         if key != self._loaded_key:

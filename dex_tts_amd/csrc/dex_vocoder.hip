@@ -268,37 +268,10 @@ void voc_conv(const float* X, int L, int B, const VConv& c, float slope, float* 
 void voc_aa_snake(const AaSnakeP& s, hipStream_t st) {
     if (voc_narrow_width(s.C)) launch_aa_snake_narrow(s, st); else launch_aa_snake(s, st);
 }
-}  // namespace
-
-extern "C" {
-
-size_t dex_voc_workspace_bytes(const DexVoc* v, int B, int T) {
-    if (!v || B < 1 || T < 1) return 0;
-    VPlan P; voc_plan(v, B, T, false, nullptr, P);
-    return P.bytes;
-}
-
-size_t dex_voc_ragged_workspace_bytes(const DexVoc* v, int B, int T) {
-    if (!v || B < 1 || T < 1) return 0;
-    VPlan P; voc_plan(v, B, T, true, nullptr, P);
-    return P.bytes;
-}
-
-int dex_vocode(DexVoc* v, const float* mel_dev, int B, int T, float* wav_dev, void* ws, size_t ws_bytes, dex_stream_t stream) {
-    return dex_vocode_ragged(v, mel_dev, nullptr, B, T, wav_dev, ws, ws_bytes, stream);
-}
-
-int dex_vocode_ragged(DexVoc* v, const float* mel_dev, const int32_t* len, int B, int T, float* wav_dev, void* ws, size_t ws_bytes,
-                      dex_stream_t stream) {
-    if (!v || !mel_dev || !wav_dev || !ws) return DEX_ERR_ARG;
-    if (!v->finalized) return v->fail(DEX_ERR_STATE, "dex_voc_finalize has not been called");
-    if (B < 1 || T < 1) return v->fail(DEX_ERR_ARG, "B and T must be >= 1");
-    if (((uintptr_t)ws & 255) != 0) return v->fail(DEX_ERR_ARG, "workspace must be 256-byte aligned");
+// the generator from conv_pre to the tanh on the channels-last mel in P.mel ([B][T][MEL_LD], zero past each utterance's length);
+// wav [B][T * hop].  `len` null: the plain call.
+void voc_layers(const DexVoc* v, const VPlan& P, int B, int T, const int* len, float* wav_dev, hipStream_t st) {
     const bool ragged = len != nullptr;
-    VPlan P; voc_plan(v, B, T, ragged, nullptr, P);
-    if (P.bytes > ws_bytes) return v->fail(DEX_ERR_WORKSPACE, "vocoder workspace too small: need %zu bytes, got %zu", P.bytes, ws_bytes);
-    voc_plan(v, B, T, ragged, ws, P);
-    hipStream_t st = (hipStream_t)stream;
     const DexVocoderConfig& c = v->cfg;
     const int prec = v->precision;
     if (ragged) {          // the GEMMs' output masks, one per rate (the narrow stages read the lengths themselves)
@@ -308,7 +281,6 @@ int dex_vocode_ragged(DexVoc* v, const float* mel_dev, const int32_t* len, int B
             if (P.mask[i]) launch_voc_len_mask(len, P.mask[i], B, T, R, st);
         }
     }
-    launch_mel_to_cl(mel_dev, P.mel, B, c.num_mels, T, MEL_LD, st, len);
     launch_igemm(conv1d(P.mel, T, B, v->pre, 0.f, P.x, nullptr, prec, P.mask[0]), prec, st);       // conv_pre
     long L = T;
     int R = 1;               // cumulative rate: the layer holds L = T * R samples, utterance b's end at lengths[b] * R
@@ -361,6 +333,116 @@ int dex_vocode_ragged(DexVoc* v, const float* mel_dev, const int32_t* len, int B
     }
     ConvPostP cp{xin, v->post_w, v->post_b, wav_dev, (int)L, stage_ch(c, c.n_upsamples - 1), B, v->big() ? 1.f : 0.01f, len, R};
     launch_conv_post_tanh(cp, st);
+}
+
+long floor_div(long a, long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+long ceil_div(long a, long b) { return -floor_div(-a, b); }
+// The receptive field in mel frames: the generator is walked from conv_post back to conv_pre with the radius (l, r), in
+// samples of the current layer, of the inputs one output sample depends on.  A Conv1d(k, dilation d, same padding) adds d (k - 1) / 2 to
+// both; a stage adds its widest ResBlock; ConvTranspose1d(k, u, p) maps outputs [n u + phi - l, n u + phi + r] of input sample n's u
+// outputs to inputs [ceil((n u + phi - l + p - k + 1) / u), floor((n u + phi + r + p) / u)], worst at phi = 0 on the left and phi = u - 1
+// on the right; the anti-aliased activation adds the reach of its up-sampler and low-pass, from the two filters' lengths.
+int voc_halo(const DexVoc* v) {
+    const DexVocoderConfig& c = v->cfg;
+    long aa_l = 0, aa_r = 0;
+    if (v->big()) {
+        // y[t] = sum_k s[2 t + k - (Kd / 2 - 1)], k < Kd;  s[m] = 2 sum_j x[j - pad] f[m + pl - 2 j], 0 <= m + pl - 2 j < Ku
+        const long Ku = v->raw.at("activation_post.upsample.filter").shape.back(), Kd = v->raw.at("activation_post.downsample.lowpass.filter").shape.back();
+        const long pad = Ku / 2 - 1, pl = 2 * pad + (Ku - 2) / 2;
+        aa_l = pad - ceil_div(-(Kd / 2 - 1) + pl - Ku + 1, 2);
+        aa_r = floor_div(Kd / 2 + pl, 2) - pad;
+    }
+    long l = 3 + aa_l, r = 3 + aa_r;                      // conv_post: 7 taps behind leaky_relu / activation_post
+    for (int i = c.n_upsamples - 1; i >= 0; --i) {
+        long conv = 0;                                   // the widest ResBlock: three dilated and three plain convs
+        for (int j = 0; j < 3; ++j) {
+            long s = 0;
+            for (int m = 0; m < 3; ++m) s += (long)(c.resblock_dilation_sizes[j][m] + 1) * (c.resblock_kernel_sizes[j] - 1) / 2;
+            conv = std::max(conv, s);
+        }
+        l += conv + 6 * aa_l; r += conv + 6 * aa_r;
+        const long k = c.upsample_kernel_sizes[i], u = c.upsample_rates[i], p = (k - u) / 2;
+        l = floor_div(l + k - 1 - p, u);
+        r = floor_div(r + p + u - 1, u);
+    }
+    return (int)(std::max(l, r) + 3);                    // conv_pre: 7 taps
+}
+// workspace of a window of W frames: the ragged plan of a [B, W] call, the window-local lengths, the window's waveform
+struct VWin { VPlan P; int* len; float* wav; size_t bytes; };
+void voc_window_plan(const DexVoc* v, int B, long W, void* ws, VWin& w) {
+    voc_plan(v, B, (int)W, true, ws, w.P);
+    size_t off = w.P.bytes;
+    w.len = ws ? (int*)((char*)ws + off) : nullptr;
+    off += ((size_t)B * sizeof(int) + 255) & ~size_t(255);
+    w.wav = ws ? (float*)((char*)ws + off) : nullptr;
+    off += ((size_t)B * W * total_up(v->cfg) * sizeof(float) + 255) & ~size_t(255);
+    w.bytes = off;
+}
+}  // namespace
+
+extern "C" {
+
+size_t dex_voc_workspace_bytes(const DexVoc* v, int B, int T) {
+    if (!v || B < 1 || T < 1) return 0;
+    VPlan P; voc_plan(v, B, T, false, nullptr, P);
+    return P.bytes;
+}
+
+size_t dex_voc_ragged_workspace_bytes(const DexVoc* v, int B, int T) {
+    if (!v || B < 1 || T < 1) return 0;
+    VPlan P; voc_plan(v, B, T, true, nullptr, P);
+    return P.bytes;
+}
+
+int dex_vocode(DexVoc* v, const float* mel_dev, int B, int T, float* wav_dev, void* ws, size_t ws_bytes, dex_stream_t stream) {
+    return dex_vocode_ragged(v, mel_dev, nullptr, B, T, wav_dev, ws, ws_bytes, stream);
+}
+
+int dex_vocode_ragged(DexVoc* v, const float* mel_dev, const int32_t* len, int B, int T, float* wav_dev, void* ws, size_t ws_bytes,
+                      dex_stream_t stream) {
+    if (!v || !mel_dev || !wav_dev || !ws) return DEX_ERR_ARG;
+    if (!v->finalized) return v->fail(DEX_ERR_STATE, "dex_voc_finalize has not been called");
+    if (B < 1 || T < 1) return v->fail(DEX_ERR_ARG, "B and T must be >= 1");
+    if (((uintptr_t)ws & 255) != 0) return v->fail(DEX_ERR_ARG, "workspace must be 256-byte aligned");
+    const bool ragged = len != nullptr;
+    VPlan P; voc_plan(v, B, T, ragged, nullptr, P);
+    if (P.bytes > ws_bytes) return v->fail(DEX_ERR_WORKSPACE, "vocoder workspace too small: need %zu bytes, got %zu", P.bytes, ws_bytes);
+    voc_plan(v, B, T, ragged, ws, P);
+    hipStream_t st = (hipStream_t)stream;
+    launch_mel_to_cl(mel_dev, P.mel, B, v->cfg.num_mels, T, MEL_LD, st, len);
+    voc_layers(v, P, B, T, len, wav_dev, st);
+    DEX_HIPCHK(v, hipGetLastError());
+    return DEX_OK;
+}
+
+int dex_voc_halo_frames(const DexVoc* v) { return v ? voc_halo(v) : 0; }
+
+size_t dex_voc_window_workspace_bytes(const DexVoc* v, int B, int n_frames) {
+    if (!v || B < 1 || n_frames < 1) return 0;
+    VWin w; voc_window_plan(v, B, (long)n_frames + 2L * voc_halo(v), nullptr, w);
+    return w.bytes;
+}
+
+int dex_vocode_window(DexVoc* v, const float* mel_dev, const int32_t* len, int B, int T, int t0, int n_frames, float* wav_dev,
+                      int64_t wav_bstride, void* ws, size_t ws_bytes, dex_stream_t stream) {
+    if (!v || !mel_dev || !wav_dev || !ws) return DEX_ERR_ARG;
+    if (!v->finalized) return v->fail(DEX_ERR_STATE, "dex_voc_finalize has not been called");
+    if (B < 1 || T < 1) return v->fail(DEX_ERR_ARG, "B and T must be >= 1");
+    if (t0 < 0 || n_frames < 1 || (long)t0 + n_frames > T)
+        return v->fail(DEX_ERR_ARG, "window [%d, %ld) is not inside the %d frames of the mel", t0, (long)t0 + n_frames, T);
+    const long hop = total_up(v->cfg);
+    if (wav_bstride < n_frames * hop) return v->fail(DEX_ERR_ARG, "wav_bstride %lld is less than the window's %ld samples", (long long)wav_bstride, n_frames * hop);
+    if (((uintptr_t)ws & 255) != 0) return v->fail(DEX_ERR_ARG, "workspace must be 256-byte aligned");
+    const size_t need = dex_voc_window_workspace_bytes(v, B, n_frames);
+    if (need > ws_bytes) return v->fail(DEX_ERR_ARG, "vocoder window workspace too small: need %zu bytes, got %zu", need, ws_bytes);
+    const int H = voc_halo(v);
+    const int lo = std::max(0, t0 - H), hi = (int)std::min((long)T, (long)t0 + n_frames + H), W = hi - lo;       // W <= n_frames + 2 H
+    VWin w; voc_window_plan(v, B, W, ws, w);
+    hipStream_t st = (hipStream_t)stream;
+    launch_voc_window_len(len, w.len, B, T, lo, W, st);
+    launch_mel_window_to_cl(mel_dev, w.P.mel, B, v->cfg.num_mels, T, lo, W, MEL_LD, w.len, st);
+    voc_layers(v, w.P, B, W, w.len, w.wav, st);       // always with lengths: the window's own ends are the true ends only at lo = 0 and hi = T
+    launch_voc_window_crop(w.wav, W * hop, (t0 - lo) * hop, wav_dev, wav_bstride, n_frames * hop, B, st);
     DEX_HIPCHK(v, hipGetLastError());
     return DEX_OK;
 }

@@ -494,6 +494,13 @@ void launch_transpose_cl(const float* src, float* dst, int B, int C, int L, int 
 void launch_mel_to_cl(const float* mel, float* out, int B, int C, int T, int ldc, hipStream_t st, const int* len = nullptr);
 // mask[b][t] = t < Lb ? 1 : 0 for t in [0, T R): the implicit GEMM's output mask (IGemmP::outmask) of a layer at rate R
 void launch_voc_len_mask(const int* len, float* mask, int B, int T, int R, hipStream_t st);
+// Windowed calls (dex_vocode_window): frames [lo, lo + W) of the mel as a ragged batch of W-frame utterances.
+// wlen[b] = clamp(clamp(len[b], 0, T) - lo, 0, W)  (len null: every utterance has T frames)
+void launch_voc_window_len(const int* len, int* wlen, int B, int T, int lo, int W, hipStream_t st);
+// launch_mel_to_cl on the window: mel [B,C,T] -> out [B,W,ldc], frames at or past wlen[b] and channels past C zeroed; reads no other frame
+void launch_mel_window_to_cl(const float* mel, float* out, int B, int C, int T, int lo, int W, int ldc, const int* wlen, hipStream_t st);
+// dst[b * dst_bstride + i] = src[b * src_bstride + off + i], i < n: the window's interior samples into the caller's waveform
+void launch_voc_window_crop(const float* src, long src_bstride, long off, float* dst, long dst_bstride, long n, int B, hipStream_t st);
 // ConvTranspose1d(k, stride u, padding (k-u)/2) after its GEMM Y[l][j*Cout + co] = sum_ci x[l][ci] w[ci][co][j]:
 // out[t][co] = bias[co] + sum_{j = (t+pad) mod u, +u, .. < k} Y[(t+pad-j)/u][j][co]   (0 <= (t+pad-j)/u < L)
 struct ConvTFoldP { const float* Y; const float* bias; float* out; int L, Cout, k, u, pad, B; const int* len; int R; };   // R: rate of the INPUT (length L)

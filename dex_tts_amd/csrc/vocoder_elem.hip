@@ -33,6 +33,45 @@ void launch_voc_len_mask(const int* len, float* mask, int B, int T, int R, hipSt
     hipLaunchKernelGGL(voc_len_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, st, len, mask, B, T, R);
 }
 
+// ---- windowed calls (dex_vocode_window): the frames [lo, lo + W) of a [B][C][T] mel are vocoded as a batch of W-frame utterances.
+// wlen[b] = the part of utterance b inside the window, clamp(len[b] - lo, 0, W) with len[b] itself clamped to [0, T] (null: T)
+__global__ __launch_bounds__(256) void voc_window_len_kernel(const int* len, int* wlen, int B, int T, int lo, int W) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b < B) wlen[b] = min(max(voc_valid_len(len, b, 1, T) - lo, 0), W);
+}
+void launch_voc_window_len(const int* len, int* wlen, int B, int T, int lo, int W, hipStream_t st) {
+    hipLaunchKernelGGL(voc_window_len_kernel, dim3((B + 255) / 256), dim3(256), 0, st, len, wlen, B, T, lo, W);
+}
+
+// mel_to_cl on the window: out[b][t][c] = mel[b][c][lo + t] for t < wlen[b], c < C, else 0.  A select, as in mel_to_cl: no frame outside
+// the window or at or past an utterance's length is loaded
+__global__ __launch_bounds__(256) void mel_window_to_cl_kernel(const float* mel, float* out, int B, int C, int T, int lo, int W, int ldc, const int* wlen) {
+    const long total = (long)B * W * ldc;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int c = (int)(i % ldc);
+        const long bt = i / ldc;
+        const int t = (int)(bt % W), b = (int)(bt / W);
+        out[i] = (c < C && t < wlen[b]) ? mel[((long)b * C + c) * T + lo + t] : 0.f;
+    }
+}
+void launch_mel_window_to_cl(const float* mel, float* out, int B, int C, int T, int lo, int W, int ldc, const int* wlen, hipStream_t st) {
+    long blocks = ((long)B * W * ldc + 255) / 256; if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(mel_window_to_cl_kernel, dim3((unsigned)blocks), dim3(256), 0, st, mel, out, B, C, T, lo, W, ldc, wlen);
+}
+
+// the window's interior: dst[b * dst_bstride + i] = src[b * src_bstride + off + i] for i < n
+__global__ __launch_bounds__(256) void voc_window_crop_kernel(const float* src, long src_bstride, long off, float* dst, long dst_bstride, long n, int B) {
+    const long total = (long)B * n;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const long b = i / n, t = i - b * n;
+        dst[b * dst_bstride + t] = src[b * src_bstride + off + t];
+    }
+}
+void launch_voc_window_crop(const float* src, long src_bstride, long off, float* dst, long dst_bstride, long n, int B, hipStream_t st) {
+    long blocks = ((long)B * n + 255) / 256; if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(voc_window_crop_kernel, dim3((unsigned)blocks), dim3(256), 0, st, src, src_bstride, off, dst, dst_bstride, n, B);
+}
+
 // one thread = 4 consecutive output channels of one output position
 __global__ __launch_bounds__(256) void convt_fold_kernel(const ConvTFoldP p) {
     const int C4 = p.Cout >> 2;

@@ -103,7 +103,7 @@ MAX_VALUE = 32768.0          # synthesize.py:13-14
 @torch.no_grad()
 def synthesize_tokens(model, vocoder, x: torch.Tensor, x_lengths: torch.Tensor, n_timesteps: int = 50, temperature: float = 1.5,
                       spk: Optional[torch.Tensor] = None, length_scale: float = 1.0, style: Optional[dict] = None,
-                      exact_lengths: bool = False):
+                      exact_lengths: bool = False, chunk_frames: Optional[int] = None):
     """synthesize.py:31-38 from the token sequence on (the text front-end - cleaners, CMU dictionary, ``intersperse`` - is the
     reference's and stays on the host): ``model`` a ``dex_tts_amd.tts.GeDEXTTS`` / ``DeXTTS``, ``vocoder`` a
     ``dex_tts_amd.vocoder.Generator``; DEX takes ``style = dict(ref, ref_lengths, sty, sty_lengths, lf0, lf0_lengths)``
@@ -114,14 +114,18 @@ def synthesize_tokens(model, vocoder, x: torch.Tensor, x_lengths: torch.Tensor, 
     log-mel of 0 is a loud broadband frame, and the generator's convolutions carry it 6 to 23 frames back into the valid tail, where the
     error against the utterance vocoded alone is as large as the signal (0.16 - 0.40 against a signal std of 0.15 - 0.27 in the
     project's four test geometries).  The reference synthesises at B = 1 and never meets this.  The default stays False, the padded
-    call cut afterwards, so that existing results do not change; at B = 1 the two are the same."""
+    call cut afterwards, so that existing results do not change; at B = 1 the two are the same.
+
+    ``chunk_frames`` = N: vocode window by window of N mel frames (``Generator.forward(..., chunk_frames=N)``): the same waveforms, with
+    a vocoder workspace that does not grow with the utterance.  Composes with ``exact_lengths``."""
     if style is not None:
         y_enc, y_dec, attn = model(x, x_lengths, style["ref"], style["ref_lengths"], style["sty"], style["sty_lengths"], style["lf0"],
                                    style["lf0_lengths"], n_timesteps=n_timesteps, temperature=temperature, spk=spk, length_scale=length_scale)
     else:
         y_enc, y_dec, attn = model(x, x_lengths, n_timesteps=n_timesteps, temperature=temperature, spk=spk, length_scale=length_scale)
     y_len = model.encoder._last["y_len"]
-    wav = (vocoder(y_dec, y_len) if exact_lengths else vocoder(y_dec)).squeeze(1).clamp(-1, 1)      # [B, Ty * hop]
+    chunk = {} if chunk_frames is None else {"chunk_frames": chunk_frames}
+    wav = (vocoder(y_dec, y_len, **chunk) if exact_lengths else vocoder(y_dec, **chunk)).squeeze(1).clamp(-1, 1)      # [B, Ty * hop]
     hop = wav.shape[-1] // y_dec.shape[-1]
     y_len = y_len.to(torch.int64).cpu()
     audio = (wav.cpu().numpy() * MAX_VALUE).astype(np.int16)

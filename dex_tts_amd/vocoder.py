@@ -151,15 +151,15 @@ class Generator(NativeModule):
                 raise RuntimeError(f"{k} differs from activation_post.upsample.filter: per-layer resampling filters are not supported")
         return sd
 
-    @torch.no_grad()
-    def forward(self, x: torch.Tensor, lengths=None) -> torch.Tensor:
-        """mel [B, num_mels, T] -> wav [B, 1, T * prod(upsample_rates)] (models.py:150-167).
+    @property
+    def halo_frames(self) -> int:
+        """Mel frames of context a window needs on each side (``dex_voc_halo_frames``): every sample of the frames [t0, t0 + n) depends on
+        nothing outside [t0 - H, t0 + n + H).  A function of the configuration alone; needs no device."""
+        self._create()
+        return int(self._lib.dex_voc_halo_frames(self._ctx))
 
-        ``lengths`` (a sequence or an integer tensor of B frame counts, on any device): a ragged batch.  Utterance b is vocoded exactly
-        as if it had been passed alone as ``x[b:b+1, :, :lengths[b]]`` (``dex_vocode_ragged``): its waveform ends at ``lengths[b] * hop``
-        and is exactly zero behind that, and whatever ``x`` holds past ``lengths[b]`` is ignored.  Without it the padded batch is
-        vocoded as one [B, T] tensor, and the padding (a log-mel of 0 is a loud frame) reaches the last frames of every shorter
-        utterance.  The lengths stay on the device: no host synchronisation."""
+    def _inputs(self, x, lengths):
+        """(mel fp32 contiguous, lengths as device int32 or None) of a call, checked; the engine is up and the precision mode set."""
         dev = x.device
         if lengths is not None:
             lengths = torch.as_tensor(lengths)
@@ -170,25 +170,84 @@ class Generator(NativeModule):
             # operand precision of the convolutions: 'fp32' (default, the parity mode), 'bf16' or 'fp16' (attribute ``precision``)
             self._check(self._lib.dex_voc_set_precision(self._ctx, _lib.PRECISION[getattr(self, "precision", "fp32")]))
             mel = x.to(dtype=torch.float32).contiguous()
-            B, M, T = mel.shape
-            if M != int(_get(self.h, "num_mels", 80)):
-                raise ValueError(f"mel has {M} channels, the generator expects {_get(self.h, 'num_mels', 80)}")
+            if mel.shape[1] != int(_get(self.h, "num_mels", 80)):
+                raise ValueError(f"mel has {mel.shape[1]} channels, the generator expects {_get(self.h, 'num_mels', 80)}")
+            ln = None if lengths is None else lengths.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+        return mel, ln
+
+    @staticmethod
+    def _chunk(chunk_frames, T):
+        n = int(chunk_frames)
+        if n != chunk_frames or n < 1:
+            raise ValueError(f"chunk_frames must be a positive integer, got {chunk_frames!r}")
+        return min(n, T)
+
+    def _window(self, mel, ln, t0, n, out_ptr, out_bstride, N):
+        """Enqueue ``dex_vocode_window`` for the frames [t0, t0 + n) on the current stream (workspace: that of N-frame windows)."""
+        dev = mel.device
+        B, _, T = mel.shape
+        need = int(self._lib.dex_voc_window_workspace_bytes(self._ctx, B, N))
+        base, nbytes = self._workspace(need, dev)
+        self._check(self._lib.dex_vocode_window(self._ctx, C.c_void_p(mel.data_ptr()), C.c_void_p(ln.data_ptr() if ln is not None else None), B, T,
+                                                t0, n, C.c_void_p(out_ptr), out_bstride, C.c_void_p(base), nbytes, stream(dev)))
+
+    @torch.no_grad()
+    def forward(self, x: torch.Tensor, lengths=None, chunk_frames=None) -> torch.Tensor:
+        """mel [B, num_mels, T] -> wav [B, 1, T * prod(upsample_rates)] (models.py:150-167).
+
+        ``lengths`` (a sequence or an integer tensor of B frame counts, on any device): a ragged batch.  Utterance b is vocoded exactly
+        as if it had been passed alone as ``x[b:b+1, :, :lengths[b]]`` (``dex_vocode_ragged``): its waveform ends at ``lengths[b] * hop``
+        and is exactly zero behind that, and whatever ``x`` holds past ``lengths[b]`` is ignored.  Without it the padded batch is
+        vocoded as one [B, T] tensor, and the padding (a log-mel of 0 is a loud frame) reaches the last frames of every shorter
+        utterance.  The lengths stay on the device: no host synchronisation.
+
+        ``chunk_frames`` = N: the same tensor (in fp32 bit for bit), computed window by window of N frames into the output
+        (``dex_vocode_window``): the workspace is that of one window of min(N, T) frames plus ``halo_frames`` on each side, whatever T
+        is, at the price of recomputing the halo per window.  ``stream()`` hands the windows out one by one."""
+        mel, ln = self._inputs(x, lengths)
+        dev = mel.device
+        B, M, T = mel.shape
+        with torch.cuda.device(dev):
             n = int(self._lib.dex_voc_samples(self._ctx, T))
             wav = torch.empty(B, 1, n, dtype=torch.float32, device=dev)
-            if lengths is None:
+            if chunk_frames is not None:
+                N, hop = self._chunk(chunk_frames, T), n // T
+                for t0 in range(0, T, N):
+                    self._window(mel, ln, t0, min(N, T - t0), wav.data_ptr() + 4 * t0 * hop, n, N)
+                self._keep = (mel, ln)
+            elif ln is None:
                 need = int(self._lib.dex_voc_workspace_bytes(self._ctx, B, T))
                 base, nbytes = self._workspace(need, dev)
                 self._check(self._lib.dex_vocode(self._ctx, C.c_void_p(mel.data_ptr()), B, T, C.c_void_p(wav.data_ptr()), C.c_void_p(base),
                                                  nbytes, stream(dev)))
                 self._keep = mel
             else:
-                ln = lengths.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
                 need = int(self._lib.dex_voc_ragged_workspace_bytes(self._ctx, B, T))
                 base, nbytes = self._workspace(need, dev)
                 self._check(self._lib.dex_vocode_ragged(self._ctx, C.c_void_p(mel.data_ptr()), C.c_void_p(ln.data_ptr()), B, T,
                                                         C.c_void_p(wav.data_ptr()), C.c_void_p(base), nbytes, stream(dev)))
                 self._keep = (mel, ln)
             return wav
+
+    def stream(self, x: torch.Tensor, lengths=None, chunk_frames: int = 64):
+        """``forward(x, lengths)`` handed out as it is computed: yields ``(t0, wav_chunk [B, 1, n * hop], event)`` per window of
+        ``chunk_frames`` mel frames, in order (the last one may be shorter); the chunks' concatenation is ``forward``'s tensor.  Each
+        chunk is enqueued on the current stream when the generator is advanced, and ``event`` (a ``torch.cuda.Event``) is recorded
+        behind it: a consumer waits for the event - ``event.synchronize()``, or ``other_stream.wait_event(event)`` in front of its copy -
+        and takes chunk i while chunk i + 1 computes.  Nothing here synchronises."""
+        mel, ln = self._inputs(x, lengths)
+        dev = mel.device
+        B, M, T = mel.shape
+        N = self._chunk(chunk_frames, T)
+        hop = int(self._lib.dex_voc_samples(self._ctx, 1))
+        for t0 in range(0, T, N):
+            n = min(N, T - t0)
+            with torch.cuda.device(dev):
+                chunk = torch.empty(B, 1, n * hop, dtype=torch.float32, device=dev)
+                self._window(mel, ln, t0, n, chunk.data_ptr(), n * hop, N)
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(dev))
+            yield t0, chunk, ev
 
 
 def get_vocoder(config_path: Optional[str] = None, ckpt: Optional[dict] = None, device="cuda") -> Generator:

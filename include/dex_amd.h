@@ -366,6 +366,22 @@ int  dex_vocode(DexVoc* voc, const float* mel_dev, int B, int T, float* wav_dev,
 size_t dex_voc_ragged_workspace_bytes(const DexVoc* voc, int B, int T);
 int  dex_vocode_ragged(DexVoc* voc, const float* mel_dev, const int32_t* lengths_dev, int B, int T, float* wav_dev, void* workspace_dev,
                        size_t workspace_bytes, dex_stream_t stream);
+/* Windowed calls: long utterances in bounded memory, audio handed out as it is computed.  The generator has a finite receptive field:
+ * with dex_voc_halo_frames() = H frames of context on each side, the samples of the frames [t0, t0 + n_frames) depend on nothing outside
+ * [t0 - H, t0 + n_frames + H).  H follows from the configuration alone (kernel sizes, dilations, rates, the resampling filters' lengths);
+ * it is valid right after dex_voc_create.
+ * dex_vocode_window writes, for every utterance b, the samples [t0 * hop, (t0 + n_frames) * hop) that dex_vocode_ragged(mel_dev,
+ * lengths_dev, B, T) writes - in fp32 bit for bit - to wav_dev[b * wav_bstride + 0 .. n_frames * hop): a pointer t0 * hop samples into
+ * the full [B, T * hop] waveform with wav_bstride = T * hop assembles the whole result in place.  lengths_dev == NULL: every utterance
+ * has T frames (dex_vocode's result); samples past lengths_dev[b] * hop are exactly zero.  mel_dev [B,num_mels,T] is read only in the
+ * frames [max(0, t0 - H), min(T, t0 + n_frames + H)) and, of those, below each utterance's length.  Asynchronous on `stream`; nothing is
+ * copied to the host.  DEX_ERR_ARG, with nothing enqueued, for t0 < 0, n_frames < 1, t0 + n_frames > T, B < 1, wav_bstride <
+ * n_frames * hop, or a workspace below dex_voc_window_workspace_bytes(B, n_frames) - which does not depend on T (0 for B < 1 or
+ * n_frames < 1). */
+int    dex_voc_halo_frames(const DexVoc* voc);
+size_t dex_voc_window_workspace_bytes(const DexVoc* voc, int B, int n_frames);
+int    dex_vocode_window(DexVoc* voc, const float* mel_dev, const int32_t* lengths_dev, int B, int T, int t0, int n_frames, float* wav_dev,
+                         int64_t wav_bstride, void* workspace_dev, size_t workspace_bytes, dex_stream_t stream);
 
 /* ---- DEX style encoders (DEX-TTS/model/ref_encoder.py TVEncoder :110-140 + VQEmbeddingEMA :199-237, LF0Encoder
  * :36-55, TIVEncoder :83-108, DeXTTS.conv_sty tts.py:31) and the part of DeXTTS.forward that feeds the decoder (tts.py:55-66):

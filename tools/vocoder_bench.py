@@ -4,17 +4,23 @@ mode, with bench.py:vocoder_block's formula (every Conv1d / ConvTranspose1d as 2
 helper.  One JSON line per case on stdout; --out also writes them all to a file.
 
     python tools/vocoder_bench.py [--models hifigan_v1,bigvgan_base,bigvgan_22khz] [--batches 1,8] [--precisions fp32,bf16,fp16]
-                                  [--T 512] [--steps 10] [--warmup 3] [--lengths LO:HI] [--out FILE]
+                                  [--T 512] [--steps 10] [--warmup 3] [--lengths LO:HI] [--chunk N] [--out FILE]
 
 --lengths LO:HI: a ragged batch, utterance i holding int(T * (LO + (HI - LO) * ((7 i) % 11) / 10)) frames (0.6:1.0 is bench.py's ragged
 batch).  Each case is then timed twice on the same mel - the padded call ``gen(mel)`` and the ragged call ``gen(mel, lengths)``
 (dex_vocode_ragged, lengths on the device) - with ``valid_frames_per_s`` next to ``mel_frames_per_s`` (which counts the padding).
+
+--chunk N: next to the whole call, the windowed one (``Generator.stream``, dex_vocode_window, N mel frames per window) on the same mel:
+``first_chunk_ms`` - host time from the call to the first window's event, the time to first audio - against ``whole_call_ms`` (the
+whole call's first audio is its last sample), ``chunked_total_ms`` for all windows, and both workspaces.  Medians over --steps runs,
+each synchronised on both sides.
 """
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -45,7 +51,37 @@ def ragged_lengths(B, T, lo, hi):
     return [max(1, min(T, int(T * (lo + (hi - lo) * ((7 * i) % 11) / 10.0)))) for i in range(B)]
 
 
-def run(name, B, T, prec, steps, warmup, device, lengths=None):
+def host_ms(device, work):
+    """Host milliseconds of ``work()`` from an idle device; ``work`` returns once what it measures is complete on the device."""
+    torch.cuda.synchronize(device)
+    t = time.perf_counter()
+    work()
+    return (time.perf_counter() - t) * 1e3
+
+
+def chunked(gen, mel, ln, N, steps, warmup, device):
+    """The windowed call next to the whole one, each from an idle device: median host ms of the whole call, to the first window's
+    event, and for all windows (a run of its own: waiting for the first event stalls the host's launches); the number of windows."""
+    def whole():
+        gen(mel) if ln is None else gen(mel, ln)
+        torch.cuda.synchronize(device)
+
+    def first():
+        it = gen.stream(mel, ln, chunk_frames=N)
+        next(it)[2].synchronize()
+        it.close()
+
+    n = [0]
+
+    def total():
+        n[0] = sum(1 for _ in gen.stream(mel, ln, chunk_frames=N))
+        torch.cuda.synchronize(device)
+    ms = {f.__name__: statistics.median([host_ms(device, f) for _ in range(warmup + steps)][warmup:]) for f in (whole, first, total)}
+    torch.cuda.synchronize(device)
+    return ms["whole"], ms["first"], ms["total"], n[0]
+
+
+def run(name, B, T, prec, steps, warmup, device, lengths=None, chunk=None):
     """One case; ``lengths`` (B frame counts): the ragged call, else the padded one."""
     h = MODELS[name]
     gen = V.Generator(V.AttrDict(h))
@@ -67,6 +103,15 @@ def run(name, B, T, prec, steps, warmup, device, lengths=None):
            "stage_GFLOP": [round(B * s / 1e9, 1) for s in stages]}
     if lengths is not None:
         out.update(call="ragged", lengths=list(lengths), valid_frames_per_s=round(sum(lengths) / sec, 1))
+    if chunk:
+        with torch.cuda.stream(stream):
+            whole_ms, first_ms, total_ms, windows = chunked(gen, mel, ln, chunk, steps, warmup, device)
+        H = gen.halo_frames
+        N = min(chunk, T)
+        out.update(chunk_frames=N, halo_frames=H, windows=windows, whole_call_ms=round(whole_ms, 3), first_chunk_ms=round(first_ms, 3),
+                   chunked_total_ms=round(total_ms, 3), chunked_over_whole=round(total_ms / whole_ms, 3), halo_model=round((N + 2 * H) / N, 3),
+                   whole_workspace_MB=round((gen._lib.dex_voc_workspace_bytes if ln is None else gen._lib.dex_voc_ragged_workspace_bytes)(gen._ctx, B, T) / 2**20, 1),
+                   window_workspace_MB=round(gen._lib.dex_voc_window_workspace_bytes(gen._ctx, B, N) / 2**20, 1))
     del gen
     torch.cuda.empty_cache()
     return out
@@ -82,6 +127,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--lengths", default=None, metavar="LO:HI", help="ragged batch: lengths between LO * T and HI * T frames (bench.py's "
                                                                      "ragged batch is 0.6:1.0); times the padded and the ragged call")
+    ap.add_argument("--chunk", type=int, default=None, metavar="N", help="also time the windowed call with N mel frames per window: time to "
+                                                                         "the first window's event, the total of all windows, both workspaces")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     frac = None
@@ -89,19 +136,21 @@ def main():
         frac = tuple(float(v) for v in a.lengths.split(":"))
         if len(frac) != 2 or not 0.0 <= frac[0] <= frac[1] <= 1.0:
             ap.error("--lengths wants LO:HI with 0 <= LO <= HI <= 1")
+    if a.chunk is not None and a.chunk < 1:
+        ap.error("--chunk wants a positive number of mel frames")
     device = torch.device("cuda", 0)
     rows = []
     for name in a.models.split(","):
         for B in (int(b) for b in a.batches.split(",")):
             for prec in a.precisions.split(","):
-                r = run(name, B, a.T, prec, a.steps, a.warmup, device)
+                r = run(name, B, a.T, prec, a.steps, a.warmup, device, chunk=a.chunk)
                 if frac:
                     ln = ragged_lengths(B, a.T, *frac)
                     r.update(call="padded", lengths=ln, valid_frames_per_s=round(sum(ln) * r["mel_frames_per_s"] / (B * a.T), 1))
                 print(json.dumps(r), flush=True)
                 rows.append(r)
                 if frac:
-                    r = run(name, B, a.T, prec, a.steps, a.warmup, device, ln)
+                    r = run(name, B, a.T, prec, a.steps, a.warmup, device, ln, chunk=a.chunk)
                     print(json.dumps(r), flush=True)
                     rows.append(r)
     if a.out:
