@@ -224,6 +224,18 @@ SYMBOLS = [
     ("dex_griffin_lim", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_size_t, C.c_void_p]),
     ("dex_mel_to_linear", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("dex_spk_create", C.c_int, [C.POINTER(C.c_void_p)]),
+    ("dex_spk_destroy", None, [C.c_void_p]),
+    ("dex_spk_last_error", C.c_char_p, [C.c_void_p]),
+    ("dex_spk_load", C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
+    ("dex_spk_forward_workspace_bytes", C.c_size_t, [C.c_int, C.c_int]),
+    ("dex_spk_workspace_bytes", C.c_size_t, [C.c_int, C.c_int]),
+    ("dex_spk_mel", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("dex_spk_forward", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("dex_spk_embed", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("dex_spk_normalize_volume", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
+    ("dex_spk_cosine", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 ]
 
 _lib = None

@@ -132,6 +132,14 @@ def synthesize_tokens(model, vocoder, x: torch.Tensor, x_lengths: torch.Tensor, 
     return [audio[b, : int(y_len[b]) * hop] for b in range(audio.shape[0])], y_dec, attn
 
 
+def speaker_scores(encoder, audio, ref_wavs, sr: int = 22050, ref_sr: Optional[int] = None):
+    """The reference's speaker-similarity score (src/metric.py:69-95) of ``synthesize_tokens``' list of int16 waveforms against the
+    reference wavs, in the same order, on the device -> (cos [B], mean, stderr).  ``encoder`` is a ``speaker.VoiceEncoder`` with
+    resemblyzer's weights loaded (speaker.py states what the score leaves out: the VAD trim)."""
+    from . import speaker
+    return speaker.score_synthesis(audio, ref_wavs, sr, ref_sr, encoder=encoder)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--config", required=True, help="a reference base.yaml (GeDEX-TTS/config/*/base.yaml, DEX-TTS/config/*/base.yaml)")

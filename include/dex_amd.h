@@ -538,6 +538,45 @@ int  dex_griffin_lim(DexGl* gl, const float* mag_dev, const float* angles_dev, c
 int  dex_mel_to_linear(DexGl* gl, const float* mel_dev, const int32_t* mel_frames_host, int B, int T, float* spec_dev,
                        dex_stream_t stream);
 
+/* ---- Speaker similarity (the reference's src/metric.py:69-95, 115-142, Evaluater.calculate_accept / calculate_asv_score): the d-vector of
+ * resemblyzer's VoiceEncoder - 16 kHz, 25 ms window (n_fft 400), hop 160, 40 Slaney mels of the POWER spectrogram (no logarithm),
+ * partials of 160 frames, LSTM(40, 256, 3) with gates i | f | g | o, Linear(256, 256), ReLU, L2 normalisation - and the cosine of two
+ * of them.  The network is fp32 throughout.  Lengths and the slice table are HOST arrays; bad arguments return an error code, with a
+ * message in the handle's last error, before anything is enqueued.  No compute call synchronises or allocates; a row's result does
+ * not depend on its batch.  trim_long_silences (webrtcvad) is not part of the library. */
+typedef struct DexSpk DexSpk;
+#define DEX_SPK_MELS 40
+#define DEX_SPK_EMBED 256
+#define DEX_SPK_PARTIAL_FRAMES 160
+int  dex_spk_create(DexSpk** out);                 /* the handle's tables: DFT twiddles, window and mel basis (fp64) */
+void dex_spk_destroy(DexSpk* spk);
+const char* dex_spk_last_error(const DexSpk* spk);
+/* one weight under resemblyzer's checkpoint key (lstm.weight_ih_l0 [1024,40], lstm.weight_hh_l0 [1024,256], lstm.bias_ih_l0 [1024], ...,
+ * linear.weight [256,256], linear.bias [256]); stream-ordered.  The call that loads the last missing key also packs the operands;
+ * compute calls return DEX_ERR_STATE until then. */
+int  dex_spk_load(DexSpk* spk, const char* key, const float* w_dev, const int64_t* shape, int ndim, dex_stream_t stream);
+size_t dex_spk_forward_workspace_bytes(int P, int T);      /* P rows of T frames; 0 for bad arguments */
+size_t dex_spk_workspace_bytes(int P, int max_samples);    /* the embedding of P partials in all; 0 for bad arguments */
+/* wav_to_mel_spectrogram: wav_dev [B, n_samples], row b lengths_host[b] samples (1 .. n_samples) -> mel_dev [B, n_samples / 160 + 1, 40]
+ * (frames x channels); row b fills lengths_host[b] / 160 + 1 frames and 0 past them.  center = True with zero padding. */
+int  dex_spk_mel(DexSpk* spk, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, float* mel_dev, dex_stream_t stream);
+/* VoiceEncoder.forward: mels_dev [P, T, 40] -> embeds_dev [P, 256] (unit rows), T >= 1. */
+int  dex_spk_forward(DexSpk* spk, const float* mels_dev, int P, int T, float* embeds_dev, void* workspace_dev, size_t workspace_bytes,
+                     dex_stream_t stream);
+/* embed_utterance for a ragged batch: wav_dev [B, n_samples], row b lengths_host[b] samples; utterance b owns slices_host[b] >= 1
+ * consecutive entries of slice_start_host (first mel frame of each 160-frame partial, P entries in all; samples past the row's length
+ * count as 0, which is the zero padding to the last slice's end).  Mel, slicing, network, the mean over an utterance's partials and its
+ * normalisation run in one stream-ordered sequence -> embeds_dev [B, 256]; partials_dev [P, 256] (optional) receives the partial embeddings. */
+int  dex_spk_embed(DexSpk* spk, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, const int32_t* slices_host,
+                   const int32_t* slice_start_host, int P, float* embeds_dev, float* partials_dev, void* workspace_dev,
+                   size_t workspace_bytes, dex_stream_t stream);
+/* normalize_volume(wav, target_dBFS, increase_only = True): row b times 10^((target - dBFS_b) / 20) where that is >= 1, unchanged
+ * otherwise; dBFS_b = 10 log10(mean(wav_b^2)) with the mean in fp64.  out_dev [B, n_samples] (may be wav_dev), 0 past a row's length. */
+int  dex_spk_normalize_volume(DexSpk* spk, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, double target_dbfs,
+                              float* out_dev, dex_stream_t stream);
+/* calculate_accept: cos_dev [B] = <a_b, b_b> / (|a_b| |b_b|) of rows of a_dev, b_dev [B, D]. */
+int  dex_spk_cosine(DexSpk* spk, const float* a_dev, const float* b_dev, int B, int D, float* cos_dev, dex_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
