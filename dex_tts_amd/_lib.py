@@ -236,6 +236,20 @@ SYMBOLS = [
                                 C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("dex_spk_normalize_volume", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     ("dex_spk_cosine", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("dex_asr_create", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("dex_asr_destroy", None, [C.c_void_p]),
+    ("dex_asr_last_error", C.c_char_p, [C.c_void_p]),
+    ("dex_asr_load", C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
+    ("dex_asr_finalize", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("dex_asr_num_weights", C.c_int, [C.c_void_p]),
+    ("dex_asr_weight_info", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    ("dex_asr_num_frames", C.c_int, [C.c_void_p, C.c_int]),
+    ("dex_asr_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    ("dex_asr_normalize", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("dex_asr_logits", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("dex_asr_transcribe", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_size_t, C.c_void_p]),
+    ("dex_asr_ctc", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 ]
 
 _lib = None

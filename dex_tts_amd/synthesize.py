@@ -140,6 +140,19 @@ def speaker_scores(encoder, audio, ref_wavs, sr: int = 22050, ref_sr: Optional[i
     return speaker.score_synthesis(audio, ref_wavs, sr, ref_sr, encoder=encoder)
 
 
+def asr_scores(model, audio, texts, sr: int = 22050):
+    """The reference's ASR score (src/metric.py:21-67) of ``synthesize_tokens``' list of int16 waveforms (``sr`` Hz) against the
+    input texts, in the same order -> (transcripts, cer_mean, cer_stderr, wer_mean, wer_stderr).  ``model`` is an
+    ``asr.Wav2Vec2CTC`` with the checkpoint's weights loaded (asr.py states the one departure: the resampler)."""
+    from . import asr
+    if len(audio) != len(texts) or len(audio) < 1:
+        raise ValueError(f"asr_scores: {len(audio)} waveforms against {len(texts)} texts")
+    if not isinstance(model, asr.Wav2Vec2CTC):
+        raise ValueError("asr_scores: pass an asr.Wav2Vec2CTC with the checkpoint's weights loaded (the library ships none)")
+    preds = model.transcribe(list(audio), None, sr)
+    return (preds, *asr.score_transcripts(texts, preds))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--config", required=True, help="a reference base.yaml (GeDEX-TTS/config/*/base.yaml, DEX-TTS/config/*/base.yaml)")

@@ -577,6 +577,54 @@ int  dex_spk_normalize_volume(DexSpk* spk, const float* wav_dev, const int32_t* 
 /* calculate_accept: cos_dev [B] = <a_b, b_b> / (|a_b| |b_b|) of rows of a_dev, b_dev [B, D]. */
 int  dex_spk_cosine(DexSpk* spk, const float* a_dev, const float* b_dev, int B, int D, float* cos_dev, dex_stream_t stream);
 
+/* ---- ASR score (the reference's src/metric.py:21-67, Evaluater.transcribe / calculate_asr_score): the forward pass of HF's
+ * Wav2Vec2ForCTC in eval mode (facebook/wav2vec2-large-960h-lv60-self and its family: layer-norm feature extractor, stable layer
+ * norm, head_dim 64) and greedy CTC, in fp32.  Input normalisation (Wav2Vec2FeatureExtractor, do_normalize) is part of the call.
+ * Lengths are HOST arrays; bad arguments return an error code, with a message in the handle's last error, before anything is
+ * enqueued.  No compute call synchronises or allocates; a row's logits do not depend on its batch.  Edit distance and string work
+ * (WER / CER) are the caller's: dex_tts_amd/asr.py. */
+typedef struct DexAsr DexAsr;
+#define DEX_ASR_MAX_CONV 8
+typedef struct {
+    int32_t n_conv;                                   /* feature-extractor layers (7) */
+    int32_t conv_dim[DEX_ASR_MAX_CONV], conv_kernel[DEX_ASR_MAX_CONV], conv_stride[DEX_ASR_MAX_CONV];
+    int32_t conv_bias;                                /* 1: the convolutions carry a bias */
+    int32_t feat_extract_norm_layer;                  /* 1 = 'layer' (the only one built) */
+    int32_t hidden, n_layers, n_heads, intermediate;
+    int32_t do_stable_layer_norm;                     /* 1 (the only one built) */
+    int32_t num_conv_pos_embeddings, num_conv_pos_embedding_groups;
+    float   layer_norm_eps;
+    int32_t vocab;
+} DexAsrConfig;
+/* NULL = the large-lv60-self values.  DEX_ERR_ARG (and *out = NULL) for a config outside the family that is built. */
+int  dex_asr_create(const DexAsrConfig* cfg, DexAsr** out);
+void dex_asr_destroy(DexAsr* asr);
+const char* dex_asr_last_error(const DexAsr* asr);
+/* one weight under its HF state-dict key (wav2vec2.feature_extractor.conv_layers.0.conv.weight ..., lm_head.bias; the positional
+ * convolution as ...pos_conv_embed.conv.weight_g [1,1,k] / weight_v [hidden, hidden / groups, k]); stream-ordered */
+int  dex_asr_load(DexAsr* asr, const char* key, const float* w_dev, const int64_t* shape, int ndim, dex_stream_t stream);
+/* packs the operands (weight norm folded in fp64); DEX_ERR_STATE names the first key that was never loaded */
+int  dex_asr_finalize(DexAsr* asr, dex_stream_t stream);
+int  dex_asr_num_weights(const DexAsr* asr);
+int  dex_asr_weight_info(const DexAsr* asr, int i, const char** key, int64_t shape[4], int* ndim);
+/* host only: frames of n_samples samples, floor((L - k) / s) + 1 chained over the layers (0 below the receptive field; NULL = default config) */
+int  dex_asr_num_frames(const DexAsrConfig* cfg, int n_samples);
+size_t dex_asr_workspace_bytes(const DexAsr* asr, int B, int max_samples);     /* 0 for bad arguments */
+/* (x - mean) / sqrt(var + 1e-7) per row over its own length, biased variance, statistics in fp64; out_dev [B, n_samples] (may be
+ * wav_dev), 0 past a row's length */
+int  dex_asr_normalize(DexAsr* asr, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, float* out_dev, dex_stream_t stream);
+/* wav_dev [B, n_samples] raw samples, row b lengths_host[b] samples (every row at least one frame long) -> logits_dev [B, T, vocab],
+ * T = dex_asr_num_frames(n_samples); row b fills dex_asr_num_frames(lengths_host[b]) frames and 0 past them */
+int  dex_asr_logits(DexAsr* asr, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, float* logits_dev,
+                    void* workspace_dev, size_t workspace_bytes, dex_stream_t stream);
+/* dex_asr_logits + dex_asr_ctc with the logits kept in the workspace: ids_dev [B, T] int32, counts_dev [B] int32 */
+int  dex_asr_transcribe(DexAsr* asr, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, int32_t* ids_dev,
+                        int32_t* counts_dev, void* workspace_dev, size_t workspace_bytes, dex_stream_t stream);
+/* greedy CTC: per frame the FIRST index of the maximum (torch.argmax), repeats collapsed, blank (id 0) dropped.  logits_dev [B, T, V],
+ * row b frames_host[b] frames (0 .. T) -> ids_dev [B, T] (the first counts_dev[b] entries of a row; the rest 0), counts_dev [B] */
+int  dex_asr_ctc(DexAsr* asr, const float* logits_dev, const int32_t* frames_host, int B, int T, int V, int32_t* ids_dev,
+                 int32_t* counts_dev, dex_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
