@@ -50,6 +50,12 @@ class KsConvTUp(C.Structure):
                 + _ints("precision", "a_lp", "c_lp", "ldx", "x_coff", "H", "W", "ldy", "y_coff", "inmask_ws", "B", "C"))
 
 
+class KsAttn(C.Structure):
+    _fields_ = (_ptrs("Qh", "Kh", "Vt", "O", "ml") + [("o_sstride", C.c_int64)]
+                + _ints("N", "Npad", "B", "ksplit", "o_lp", "tail_g", "tail_ks", "half_g", "half_n", "precision"))
+
+
+ATTN_PLANS = {"attention_direct_batch_regime": 0, "attention_direct_ksplit": 1, "attention_q64_ksplit": 2}
 _lib = None
 
 
@@ -63,13 +69,15 @@ def load():
     dexlib.load()                                     # torch's HIP runtime, then the library the shim links against
     lib = C.CDLL(LIB_PATH)
     lib.ks_struct_bytes.restype, lib.ks_struct_bytes.argtypes = C.c_int, [C.c_int]
-    for k, T in enumerate((KsConv3, KsConvDown, KsConvTUp)):
+    for k, T in enumerate((KsConv3, KsConvDown, KsConvTUp, KsAttn)):
         if lib.ks_struct_bytes(k) != C.sizeof(T):
             raise RuntimeError(f"descriptor {T.__name__}: {C.sizeof(T)} bytes here, {lib.ks_struct_bytes(k)} in the shim")
     lib.ks_predicate.restype, lib.ks_predicate.argtypes = C.c_int, [C.c_int] * 8
     lib.ks_pack.restype = C.c_int
     lib.ks_pack.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p]
-    for name, T in (("ks_conv3x3", KsConv3), ("ks_conv_down", KsConvDown), ("ks_convt_up", KsConvTUp)):
+    lib.ks_attn_plan.restype, lib.ks_attn_plan.argtypes = C.c_int, [C.c_int] * 5
+    for name, T in (("ks_conv3x3", KsConv3), ("ks_conv_down", KsConvDown), ("ks_convt_up", KsConvTUp), ("ks_attn_direct", KsAttn),
+                    ("ks_attn_q64", KsAttn)):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = C.c_int, [C.POINTER(T), C.c_void_p, C.c_char_p, C.c_int]
     lib.ks_conv3x3_strip_form.restype, lib.ks_conv3x3_strip_form.argtypes = C.c_int, [C.POINTER(KsConv3)]
@@ -196,3 +204,45 @@ def convt_up(prec, tensors, *, H, W, B, ldx, x_coff=0, ldy, y_coff=0, a_lp=False
     sym = C.create_string_buffer(128)
     _check(load().ks_convt_up(C.byref(d), _stream(), sym, 128), "convt_up")
     return sym.value.decode()
+
+
+def attn_plan(name, prec, N, B, a=0):
+    """The library's own attention plan functions: attention_direct_batch_regime(N, B), attention_direct_ksplit(N, B),
+    attention_q64_ksplit(N, B, max_split)."""
+    return _check(load().ks_attn_plan(ATTN_PLANS[name], PREC[prec], N, B, a), name)
+
+
+def _attn(entry, prec, t, *, N, Npad, B, ksplit, o_sstride, o_lp, tail_g, tail_ks, half_g, half_n):
+    """t: Qh, Kh, Vt (16-bit, fragment order), O (fp32 slots; 16-bit rows in slot 0 when o_lp), ml (or absent)."""
+    if min(N, Npad, B) <= 0 or ksplit < 0 or tail_ks < 0 or o_sstride < 0:
+        raise ShimError(f"{entry}: negative or empty extent")
+    splits = max(ksplit, 1)
+    slots = 1 + tail_ks if tail_ks > 1 else splits
+    d = KsAttn()
+    for n in ("Qh", "Kh", "Vt"):
+        setattr(d, n, _need(t.get(n), B * 2 * Npad * 128 * 2, n))
+        if t.get(n) is not None and t[n].dtype != LP_DTYPE[prec]:
+            raise ShimError(f"{entry}: {n} is {t[n].dtype}, the mode's operands are {LP_DTYPE[prec]}")
+    d.O = _need(t.get("O"), ((slots - 1) * o_sstride + B * N * 256) * 4, "O")
+    d.ml = _need(t.get("ml"), max(splits, tail_ks) * B * 2 * N * 2 * 4, "ml")
+    for n in t:
+        if n not in ("Qh", "Kh", "Vt", "O", "ml"):
+            raise ShimError(f"{entry}: unknown tensor {n}")
+    d.o_sstride, d.N, d.Npad, d.B, d.ksplit, d.o_lp = o_sstride, N, Npad, B, ksplit, int(o_lp)
+    d.tail_g, d.tail_ks, d.half_g, d.half_n, d.precision = tail_g, tail_ks, half_g, half_n, PREC[prec]
+    form = C.create_string_buffer(192)
+    _check(getattr(load(), entry)(C.byref(d), _stream(), form, 192), entry)
+    return form.value.decode()
+
+
+def attn_direct(prec, tensors, *, N, Npad, B, ksplit=1, o_sstride, o_lp=False, tail_g=0, tail_ks=0, half_g=0, half_n=0):
+    """One launch_attention_direct.  Returns "attn_direct_kernel" or "attn_direct_ring_kernel xcd_map=<0|1>"."""
+    return _attn("ks_attn_direct", prec, tensors, N=N, Npad=Npad, B=B, ksplit=ksplit, o_sstride=o_sstride, o_lp=o_lp, tail_g=tail_g,
+                 tail_ks=tail_ks, half_g=half_g, half_n=half_n)
+
+
+def attn_q64(prec, tensors, *, N, Npad, B, ksplit=1, o_sstride, o_lp=False, tail_g=0, tail_ks=0, half_g=0, half_n=-1):
+    """One launch_attention_q64.  half_n < 0: whole units only, 0: the launcher's automatic half plan, > 0: forced.  Returns the
+    plan launched: "attn_q64_kernel nunits=.. grid=.. ks=.. tail_g=.. tail_ks=.. half_g=.. half_n=.. xcd_mode=.."."""
+    return _attn("ks_attn_q64", prec, tensors, N=N, Npad=Npad, B=B, ksplit=ksplit, o_sstride=o_sstride, o_lp=o_lp, tail_g=tail_g,
+                 tail_ks=tail_ks, half_g=half_g, half_n=half_n)

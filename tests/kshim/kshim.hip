@@ -1,7 +1,8 @@
-// tests/kshim/kshim.hip — test-only launch shim: ONE launch of the reduced-precision convolution kernels of libdexamd.so from a
-// flat descriptor (tests/kshim/__init__.py mirrors the structs with ctypes).  Host code only, no kernels: every entry point fills
-// the library's parameter struct by member name, sets the split-weight flag as dex_api.hip does for a call, runs the library's own
-// launcher on the given stream and returns the instantiation it picked (dex::g_last_symbol).
+// tests/kshim/kshim.hip — test-only launch shim: ONE launch of the reduced-precision convolution kernels and of the fragment-operand
+// softmax attention kernels of libdexamd.so from a flat descriptor (tests/kshim/__init__.py mirrors the structs with ctypes).  Host
+// code only, no kernels: every entry point fills the library's parameter struct by member name, sets the split-weight flag as
+// dex_api.hip does for a call, runs the library's own launcher on the given stream and returns the instantiation it picked
+// (dex::g_last_symbol; the attention launchers leave none: their entries return the kernel and the plan, recomputed here).
 //
 // A descriptor the library's shape predicates reject, or one whose launcher would abort or pick a kernel built for another shape,
 // is an ERROR CODE (KS_E_*), never a launch: a mistyped test case must not reach the device.  Buffer sizes are the caller's side
@@ -56,7 +57,15 @@ struct KsConvTUp {
     int precision, a_lp, c_lp, ldx, x_coff, H, W, ldy, y_coff, inmask_ws, B, C;
 };
 
-int ks_struct_bytes(int which) { return which == 0 ? (int)sizeof(KsConv3) : which == 1 ? (int)sizeof(KsConvDown) : (int)sizeof(KsConvTUp); }
+struct KsAttn {               // mirrors AttnDirectP (csrc/kernels.h); xcd_map, half plans of the automatic kind and dbg are the launchers' own
+    const void *Qh, *Kh, *Vt; void *O, *ml;
+    long long o_sstride;
+    int N, Npad, B, ksplit, o_lp, tail_g, tail_ks, half_g, half_n, precision;
+};
+
+int ks_struct_bytes(int which) {
+    return which == 0 ? (int)sizeof(KsConv3) : which == 1 ? (int)sizeof(KsConvDown) : which == 2 ? (int)sizeof(KsConvTUp) : (int)sizeof(KsAttn);
+}
 
 // ---- shape predicates of the library, for the mode `precision` -------------------------------------------------------------
 // which: 0 conv3x3_bf16_supported(a, b)   1 conv3x3_bf16_tail_supported(a)   2 conv3x3_bf16_res_supported(a, b)
@@ -230,6 +239,101 @@ int ks_convt_up(const KsConvTUp* d, void* stream, char* sym, int sym_len) {
     g_last_symbol = nullptr;
     launch_convt_up(p, d->precision, (hipStream_t)stream);
     put_symbol(sym, sym_len);
+    return KS_OK;
+}
+
+// ---- softmax attention on fragment-ordered 16-bit operands (attention_direct.hip, attention_q64.hip) ---------------------------
+// Every plan outside what the launchers document is an error code: a workgroup whose waves disagree on barrier counts, or a split
+// without key tiles, must not be tried on the device.  nt32 = 32-key tiles, nT = 64-key tiles, ng = groups of 256 queries.
+static int attn_fill(const KsAttn& d, AttnDirectP& p, int& ks) {
+    if (!lp_prec(d.precision)) return KS_E_PREC;
+    if (!d.Qh || !d.Kh || !d.Vt || !d.O) return KS_E_NULL;
+    if (d.N <= 0 || d.B <= 0 || d.N > (1 << 16) || d.B > (1 << 12) || d.ksplit < 0) return KS_E_SHAPE;
+    if (d.Npad != (d.N + 31) / 32 * 32) return KS_E_SHAPE;
+    ks = d.ksplit > 1 ? d.ksplit : 1;
+    if (ks > 1 && !d.ml) return KS_E_NULL;
+    if (d.o_lp && ks > 1) return KS_E_FORM;                                     // 16-bit rows exist for a single split only
+    if (d.o_sstride < (long long)d.B * d.N * 256) return KS_E_STRIDE;
+    p = AttnDirectP{};
+    p.Qh = d.Qh; p.Kh = d.Kh; p.Vt = d.Vt; p.N = d.N; p.Npad = d.Npad; p.B = d.B;
+    p.O = (float*)d.O; p.o_sstride = (long)d.o_sstride; p.ml = (float*)d.ml; p.ksplit = d.ksplit; p.dbg = nullptr;
+    p.o_lp = d.o_lp ? 1 : 0; p.xcd_map = 0;
+    p.tail_g = d.tail_g; p.tail_ks = d.tail_ks; p.half_g = d.half_g; p.half_n = d.half_n;
+    return KS_OK;
+}
+
+// which: 0 attention_direct_batch_regime(N, B)   1 attention_direct_ksplit(N, B)   2 attention_q64_ksplit(N, B, a)
+int ks_attn_plan(int which, int precision, int N, int B, int a) {
+    if (!lp_prec(precision)) return KS_E_PREC;
+    if (N <= 0 || B <= 0) return KS_E_SHAPE;
+    WsplitScope ws(precision);
+    switch (which) {
+        case 0: return attention_direct_batch_regime(N, B);
+        case 1: return attention_direct_ksplit(N, B);
+        case 2: return attention_q64_ksplit(N, B, a);
+    }
+    return KS_E_SHAPE;
+}
+
+// launch_attention_direct: the key-splitting waves (few query tiles) or the shared-ring kernel (many).  form: the kernel, and the
+// ring kernel's xcd_map as the launcher computes it.
+int ks_attn_direct(const KsAttn* d, void* stream, char* form, int form_len) {
+    if (!d) return KS_E_NULL;
+    if (!lp_prec(d->precision)) return KS_E_PREC;
+    WsplitScope ws(d->precision);
+    AttnDirectP p; int ks = 1;
+    const int rc = attn_fill(*d, p, ks);
+    if (rc != KS_OK) return rc;
+    const int nt32 = (d->N + 31) / 32;
+    if (d->tail_g || d->tail_ks || d->half_g || d->half_n) return KS_E_FORM;    // the 64-query form's plans
+    if (ks > nt32) return KS_E_SHAPE;                                           // (these kernels split by 32-key tiles)
+    const bool ring = attention_direct_batch_regime(d->N, d->B);
+    if (ring && ks != 1 && ks != attention_direct_ksplit(d->N, d->B)) return KS_E_FORM;
+    if (!ring && d->o_lp) return KS_E_FORM;                                     // 16-bit rows: the ring kernel only
+    const int xcd_map = (2 * d->B * ks) % 8 == 0 && !knob_off("DEX_XCD_MAP") ? 1 : 0;
+    launch_attention_direct(p, d->precision, (hipStream_t)stream);
+    if (form && form_len > 0) {
+        if (ring) snprintf(form, (size_t)form_len, "attn_direct_ring_kernel xcd_map=%d", xcd_map);
+        else snprintf(form, (size_t)form_len, "attn_direct_kernel");
+    }
+    return KS_OK;
+}
+
+// launch_attention_q64.  half_n < 0: whole units only; 0: the launcher's automatic half plan; > 0: that plan, forced.
+// form: the unit plan as launch_attention_q64 derives it, recomputed here from the library's public functions.
+int ks_attn_q64(const KsAttn* d, void* stream, char* form, int form_len) {
+    if (!d) return KS_E_NULL;
+    if (!lp_prec(d->precision)) return KS_E_PREC;
+    WsplitScope ws(d->precision);
+    AttnDirectP p; int ks = 1;
+    const int rc = attn_fill(*d, p, ks);
+    if (rc != KS_OK) return rc;
+    const int nt32 = (d->N + 31) / 32, nT = (nt32 + 1) / 2, ng = (nt32 + 7) / 8;
+    if (ks > nT) return KS_E_SHAPE;
+    int tks = 1, tg = ng;
+    if (d->tail_ks > 1) {
+        if (d->tail_ks > (nT < 4 ? nT : 4) || d->tail_g < 1 || d->tail_g > ng - 1) return KS_E_SHAPE;
+        if (ks > 1) return KS_E_FORM;
+        if (!d->ml) return KS_E_NULL;
+        tks = d->tail_ks; tg = d->tail_g;
+    } else if (d->tail_ks < 0 || d->tail_g != 0) return KS_E_SHAPE;
+    int hg = 0, hn = 0;
+    if (d->half_n > 0) {
+        if (ks > 1 || tks > 1) return KS_E_FORM;
+        if (d->half_g < 0 || d->half_g > nt32 / 8 || d->half_n != (nt32 - 8 * d->half_g + 3) / 4) return KS_E_SHAPE;
+        hg = d->half_g; hn = d->half_n;
+    } else {
+        if (d->half_g != 0) return KS_E_SHAPE;
+        const bool automatic = d->half_n == 0 && ks == 1 && tks == 1 && knob_or("DEX_ATTN_Q64_HALF", 1);
+        if (!(automatic && attention_q64_half_plan(d->N, d->B, &hg, &hn))) hg = hn = 0;
+    }
+    const long nunits = hn > 0 ? 2L * d->B * (hg + hn) : 2L * d->B * ((long)tg * ks + (long)(ng - tg) * tks);
+    if (nunits >= (1L << 22) || (long)tg * ks >= 4096 || (long)(ng - tg) * tks >= 4096) return KS_E_SHAPE;      // (the kernel's division-free unit decode)
+    const int xcd_mode = (2 * d->B) % 8 == 0 ? 1 : 0;
+    launch_attention_q64(p, d->precision, (hipStream_t)stream);
+    if (form && form_len > 0)
+        snprintf(form, (size_t)form_len, "attn_q64_kernel nunits=%ld grid=%ld ks=%d tail_g=%d tail_ks=%d half_g=%d half_n=%d xcd_mode=%d",
+                 nunits, nunits < 256 ? nunits : 256L, ks, tg, tks, hg, hn, xcd_mode);
     return KS_OK;
 }
 
