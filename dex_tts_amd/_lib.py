@@ -10,6 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DEX_AMD_LIB") or os.path.join(HERE, "lib", "libdexamd.so")
 
 DEX_OK = 0
+DEX_ERR_ARG, DEX_ERR_STATE = -1, -2                  # a refused argument; a handle not ready (weights not loaded)
 DEX_ERR_HANDOFF, DEX_ERR_HANDOFF_XCD = -5, -6        # include/dex_amd.h: dex_call_status
 DEX_PENDING = 1                                   # dex_call_status_poll(wait = 0)
 VARIANT = {"gedex": 0, "dex": 1}

@@ -30,7 +30,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._native import stream
+from ._native import (Handle, device_index, device_rows, host_lengths, i32_ptr, on_device, pad_wavs, per_device, resample_to_16k, stream,
+                      upload_weights)
 
 SAMPLING_RATE = 16000
 VOCAB = ("<pad>", "<s>", "</s>", "<unk>", "|", "E", "T", "A", "O", "N", "I", "H", "S", "R", "D", "L", "U", "M", "W", "C", "F", "G", "Y", "P",
@@ -103,74 +104,14 @@ _HF_PARAM = {"parametrizations.weight.original0": "weight_g", "parametrizations.
 _IGNORED = ("wav2vec2.masked_spec_embed",)
 
 
-def _i32(values) -> C.Array:
-    return (C.c_int32 * len(values))(*[int(v) for v in values])
+class _Asr(Handle):
+    """One DexAsr handle (the config, and once loaded the packed weights); its workspace is the network's."""
 
+    def __init__(self, cfg: Wav2Vec2Config, device):
+        super().__init__("dex_asr", device, C.byref(_c_config(cfg)))
 
-def _device_index(device: torch.device) -> int:
-    return device.index if device.index is not None else torch.cuda.current_device()
-
-
-def _rows(wav, lengths, what: str):
-    """wav [n] or [B, n] CUDA tensor, lengths -> (fp32 contiguous [B, n], host lengths list, was one-dimensional)."""
-    if not isinstance(wav, torch.Tensor) or not wav.is_cuda:
-        raise ValueError(f"{what} runs on an MI355X only (no CPU path): pass CUDA tensors")
-    if wav.dim() not in (1, 2):
-        raise ValueError(f"{what}: expected a wav [n] or [B, n], got {tuple(wav.shape)}")
-    one = wav.dim() == 1
-    x = (wav[None] if one else wav).to(torch.float32).contiguous()
-    B, n = x.shape
-    if B < 1 or n < 1:
-        raise ValueError(f"{what}: a wav needs at least one sample, got {tuple(wav.shape)}")
-    ln = [n] * B if lengths is None else [int(v) for v in (lengths.tolist() if isinstance(lengths, (torch.Tensor, np.ndarray)) else lengths)]
-    if len(ln) != B:
-        raise ValueError(f"{what}: {len(ln)} lengths for {B} rows")
-    if any(v < 1 or v > n for v in ln):
-        raise ValueError(f"{what}: every length must lie in [1, {n}], got {ln}")
-    return x, ln, one
-
-
-def _pad_list(wavs, device):
-    """list of 1-D wavs (tensors or numpy arrays; int16 is scaled by 1 / 32768) -> (fp32 [B, max n] on the device, lengths)."""
-    rows = []
-    for w in wavs:
-        a = np.asarray(w.cpu() if isinstance(w, torch.Tensor) else w).reshape(-1)
-        rows.append(torch.from_numpy(a.astype(np.float32) / 32768.0 if a.dtype == np.int16 else a.astype(np.float32)))
-    if not rows or min(len(r) for r in rows) < 1:
-        raise ValueError("every wav needs at least one sample")
-    out = torch.zeros(len(rows), max(len(r) for r in rows), dtype=torch.float32)
-    for b, r in enumerate(rows):
-        out[b, : len(r)] = r
-    return out.to(device), [len(r) for r in rows]
-
-
-class _Context:
-    """One DexAsr handle (the config, and once loaded the packed weights) and a growing workspace."""
-
-    def __init__(self, cfg: Wav2Vec2Config, device: torch.device):
-        self.device = device
-        self.lib = _lib.load()
-        c = _c_config(cfg)
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            rc = self.lib.dex_asr_create(C.byref(c), C.byref(h))
-        if rc != _lib.DEX_OK:
-            raise NotImplementedError(f"Wav2Vec2Config.{self.lib.dex_asr_last_error(None).decode()}")
-        self.h = h
-        self._ws = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self.lib.dex_asr_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    def check(self, rc: int, what: str):
-        if rc != _lib.DEX_OK:
-            msg = self.lib.dex_asr_last_error(self.h).decode()
-            raise (ValueError if rc in (-1, -2) else RuntimeError)(f"{what}: {msg} ({rc})")     # -1 a refused argument, -2 weights not loaded
+    def create_failed(self, rc):
+        return NotImplementedError(f"Wav2Vec2Config.{self.lib.dex_asr_last_error(None).decode()}")
 
     def shapes(self) -> dict:
         out = {}
@@ -184,30 +125,20 @@ class _Context:
         need = int(self.lib.dex_asr_workspace_bytes(self.h, B, n))
         if need == 0:
             raise ValueError(f"{B} rows of {n} samples: too short for one frame, or more than one call takes")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return super().workspace(need)
 
 
-_contexts = {}
-
-
-def _default_context(device: torch.device) -> _Context:
-    key = _device_index(device)
-    if key not in _contexts:
-        _contexts[key] = _Context(Wav2Vec2Config(), torch.device("cuda", key))
-    return _contexts[key]
+_default_context = per_device(lambda device: _Asr(Wav2Vec2Config(), device))
 
 
 def normalize_input(wav: torch.Tensor, lengths=None) -> torch.Tensor:
     """``Wav2Vec2FeatureExtractor`` with ``do_normalize``: per row over its own length ``(x - mean) / sqrt(var + 1e-7)`` with the
     biased variance; the statistics are fp64, the result is rounded to fp32 once; 0 past a row's length.  wav [n] or [B, n]."""
-    x, ln, one = _rows(wav, lengths, "normalize_input")
+    x, ln, one = device_rows(wav, lengths, "normalize_input", refuse=ValueError)
     ctx = _default_context(x.device)
     out = torch.empty_like(x)
     with torch.cuda.device(x.device):
-        rc = ctx.lib.dex_asr_normalize(ctx.h, x.data_ptr(), _i32(ln), x.shape[0], x.shape[1], out.data_ptr(), stream(x.device))
+        rc = ctx.lib.dex_asr_normalize(ctx.h, x.data_ptr(), i32_ptr(ln), x.shape[0], x.shape[1], out.data_ptr(), stream(x.device))
     ctx.check(rc, "dex_asr_normalize")
     return out[0] if one else out
 
@@ -216,8 +147,7 @@ def ctc_greedy(logits: torch.Tensor, frames=None):
     """Greedy CTC of logits [B, T, V] (or [T, V]) on the device, row b over its first ``frames[b]`` frames (default T): per frame the
     first index of the maximum (``torch.argmax``'s tie rule), repeats collapsed, blank (id 0) dropped -> a list of id lists.  One
     device-to-host copy carries ids and counts."""
-    if not isinstance(logits, torch.Tensor) or not logits.is_cuda:
-        raise ValueError("ctc_greedy runs on an MI355X only (no CPU path): pass CUDA tensors")
+    on_device(logits, "ctc_greedy", ValueError)
     if logits.dim() not in (2, 3):
         raise ValueError(f"ctc_greedy: expected logits [T, V] or [B, T, V], got {tuple(logits.shape)}")
     one = logits.dim() == 2
@@ -225,13 +155,11 @@ def ctc_greedy(logits: torch.Tensor, frames=None):
     B, T, V = x.shape
     if B < 1 or T < 1 or V < 1:
         raise ValueError(f"ctc_greedy: empty logits {tuple(logits.shape)}")
-    fr = [T] * B if frames is None else [int(v) for v in (frames.tolist() if isinstance(frames, (torch.Tensor, np.ndarray)) else frames)]
-    if len(fr) != B:
-        raise ValueError(f"ctc_greedy: {len(fr)} frame counts for {B} rows")
+    fr = host_lengths(frames, B, T, lo=0, what="ctc_greedy")
     ctx = _default_context(x.device)
     buf = torch.empty(B * T + B, dtype=torch.int32, device=x.device)
     with torch.cuda.device(x.device):
-        rc = ctx.lib.dex_asr_ctc(ctx.h, x.data_ptr(), _i32(fr), B, T, V, buf.data_ptr(), buf.data_ptr() + 4 * B * T, stream(x.device))
+        rc = ctx.lib.dex_asr_ctc(ctx.h, x.data_ptr(), i32_ptr(fr), B, T, V, buf.data_ptr(), buf.data_ptr() + 4 * B * T, stream(x.device))
     ctx.check(rc, "dex_asr_ctc")
     out = _unpack(buf, B, T)
     return out[0] if one else out
@@ -296,8 +224,8 @@ class Wav2Vec2CTC:
         self.vocab = tuple(VOCAB if vocab is None else vocab)
         if len(self.vocab) != self.config.vocab_size:
             raise ValueError(f"Wav2Vec2CTC: {len(self.vocab)} symbols for vocab_size {self.config.vocab_size}")
-        self.device = torch.device("cuda", _device_index(device))
-        self._ctx = _Context(self.config, self.device)
+        self.device = torch.device("cuda", device_index(device))
+        self._ctx = _Asr(self.config, self.device)
         self._loaded = False
 
     def state_dict_shapes(self) -> dict:
@@ -329,17 +257,11 @@ class Wav2Vec2CTC:
                 if tuple(v.shape) != shape:
                     raise RuntimeError(f"{k}: expected shape {shape}, got {tuple(v.shape)}")
                 tensors[k] = v
-        ctx, keep = self._ctx, []
         self._loaded = False
-        with torch.cuda.device(self.device):
-            for k, v in tensors.items():
-                t = v.detach().to(device=self.device, dtype=torch.float32).contiguous()
-                keep.append(t)
-                shape = (C.c_int64 * t.dim())(*t.shape)
-                ctx.check(ctx.lib.dex_asr_load(ctx.h, k.encode(), t.data_ptr(), shape, t.dim(), stream(self.device)), f"dex_asr_load({k})")
-            if not missing:
-                self.finalize()
-            torch.cuda.current_stream(self.device).synchronize()        # the uploads read `keep`
+        upload_weights(self._ctx, self._ctx.lib.dex_asr_load, tensors, self.device)
+        if not missing:
+            self.finalize()
+            torch.cuda.current_stream(self.device).synchronize()        # the operands are packed when this returns
         return self
 
     def finalize(self):
@@ -356,7 +278,7 @@ class Wav2Vec2CTC:
 
     def _inputs(self, wav, lengths, what: str):
         self._need_weights(what)
-        x, ln, one = _rows(wav, lengths, what)
+        x, ln, one = device_rows(wav, lengths, what, refuse=ValueError)
         short = [v for v in ln if num_frames(v, self.config) < 1]
         if short:
             raise ValueError(f"{what}: {short[0]} samples are too short for one frame of the feature extractor")
@@ -372,7 +294,7 @@ class Wav2Vec2CTC:
         ws = ctx.workspace(B, n)
         out = torch.empty(B, num_frames(n, self.config), self.config.vocab_size, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            rc = ctx.lib.dex_asr_logits(ctx.h, x.data_ptr(), _i32(ln), B, n, out.data_ptr(), ws.data_ptr(), ws.numel(), stream(self.device))
+            rc = ctx.lib.dex_asr_logits(ctx.h, x.data_ptr(), i32_ptr(ln), B, n, out.data_ptr(), ws.data_ptr(), ws.numel(), stream(self.device))
         ctx.check(rc, "dex_asr_logits")
         return out[0] if one else out
 
@@ -387,7 +309,7 @@ class Wav2Vec2CTC:
         ws = ctx.workspace(B, n)
         buf = torch.empty(B * T + B, dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            rc = ctx.lib.dex_asr_transcribe(ctx.h, x.data_ptr(), _i32(ln), B, n, buf.data_ptr(), buf.data_ptr() + 4 * B * T, ws.data_ptr(),
+            rc = ctx.lib.dex_asr_transcribe(ctx.h, x.data_ptr(), i32_ptr(ln), B, n, buf.data_ptr(), buf.data_ptr() + 4 * B * T, ws.data_ptr(),
                                             ws.numel(), stream(self.device))
         ctx.check(rc, "dex_asr_transcribe")
         return _unpack(buf, B, T)
@@ -398,12 +320,10 @@ class Wav2Vec2CTC:
         if int(sr) <= 0:
             raise ValueError(f"Wav2Vec2CTC.transcribe: sr must be positive, got {sr}")
         if not isinstance(wavs, torch.Tensor):
-            wavs, lengths = _pad_list(wavs, self.device)
+            wavs, lengths = pad_wavs(wavs, self.device, scale_int16=True)
         if int(sr) != SAMPLING_RATE:
-            from . import wavprep
-            x, ln, _ = _rows(wavs, lengths, "Wav2Vec2CTC.transcribe")
-            y, lo = wavprep.resample(x, int(sr), SAMPLING_RATE, lengths=ln)
-            wavs, lengths = y.to(torch.float32), [int(v) for v in lo]
+            x, ln, _ = device_rows(wavs, lengths, "Wav2Vec2CTC.transcribe", refuse=ValueError)
+            wavs, lengths = resample_to_16k(x, ln, sr)
         return [decode(ids, self.vocab) for ids in self.transcribe_ids(wavs, lengths)]
 
 

@@ -8,13 +8,11 @@ Only the reference's fixed configuration 1024/256/1024/80/22050/0/8000 (config/*
 supported.  There is no CPU path."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib
-from ._native import stream
+from ._native import Handle, on_device, stream
 from .griffin_lim import STFT
 
 _FIXED = (1024, 256, 1024, 80, 22050, 0, 8000)
@@ -30,42 +28,24 @@ class TacotronSTFT:
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if self.device.type != "cuda":
             raise RuntimeError("the mel front-end runs on an MI355X only (no CPU path)")
-        self._lib = _lib.load()
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            rc = self._lib.dex_mel_create(C.byref(h))
-        if rc != _lib.DEX_OK:
-            raise RuntimeError(f"dex_mel_create failed ({rc})")
-        self._h = h
-        self._ws = None
+        self._ctx = Handle("dex_mel", self.device, arg_errors=())          # every library error of the front-end is a RuntimeError
         # audio/stft.py:137; the reference's inv_mel_spec reads `_stft_fn` (tools.py:28), which its own class never defines: the alias
         # lets dex_tts_amd.griffin_lim.inv_mel_spec take this object
         self.stft_fn = STFT(filter_length, hop_length, win_length)
         self._stft_fn = self.stft_fn
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.dex_mel_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
     def _run(self, y: torch.Tensor):
         """y [B, L] on any device -> (mel [B,80,frames], energy [B,frames]) on self.device; rows are clipped to [-1, 1] in the kernel."""
+        ctx = self._ctx
         with torch.cuda.device(self.device):
             y = y.to(device=self.device, dtype=torch.float32).contiguous()
             B, L = y.shape
-            frames = self._lib.dex_mel_frames(L)
-            need = int(self._lib.dex_mel_workspace_bytes(B, L))
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            frames = ctx.lib.dex_mel_frames(L)
+            ws = ctx.workspace(int(ctx.lib.dex_mel_workspace_bytes(B, L)))
             mel = torch.empty(B, 80, frames, dtype=torch.float32, device=self.device)
             energy = torch.empty(B, frames, dtype=torch.float32, device=self.device)
-            rc = self._lib.dex_mel_spectrogram(self._h, y.data_ptr(), B, L, mel.data_ptr(), energy.data_ptr(), self._ws.data_ptr(),
-                                               self._ws.numel(), stream(self.device))
-            if rc != _lib.DEX_OK:
-                raise RuntimeError(f"dex_mel_spectrogram: {self._lib.dex_mel_last_error(self._h).decode()} ({rc})")
+            ctx.check(ctx.lib.dex_mel_spectrogram(ctx.h, y.data_ptr(), B, L, mel.data_ptr(), energy.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                  stream(self.device)), "dex_mel_spectrogram")
             return mel, energy
 
     def mel_spectrogram(self, y: torch.Tensor):
@@ -87,10 +67,8 @@ def lf0_from_f0(f0: torch.Tensor, lengths: torch.Tensor = None) -> torch.Tensor:
     """DEX-TTS/synthesize.py:55-58 + normalize_lf0 (:26-38) on the device: f0 [B,T] (or [T]) in Hz, 0 = unvoiced — the output of
     the host's DIO/StoneMask — -> normalised log-f0 of the same shape, the ``lf0`` input of the style encoders.  ``lengths`` [B]:
     frames past an utterance's length are excluded from the statistics and come back 0."""
+    one = on_device(f0, "lf0_from_f0").dim() == 1
     lib = _lib.load()
-    one = f0.dim() == 1
-    if not f0.is_cuda:
-        raise RuntimeError("lf0_from_f0 runs on an MI355X only (no CPU path)")
     with torch.cuda.device(f0.device):
         x = f0.to(torch.float32).reshape(1, -1).contiguous() if one else f0.to(torch.float32).contiguous()
         B, T = x.shape

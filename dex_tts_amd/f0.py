@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._native import check, device_rows, i32_ptr, stream
+from ._native import check, device_rows, i32_ptr, per_device, stream
 from .audio import TacotronSTFT, lf0_from_f0
 
 SR = 22050
@@ -32,8 +32,8 @@ def dio(x, fs, f0_floor=71.0, f0_ceil=800.0, channels_in_octave=2.0, frame_perio
     [B, F] float64 with F = frames(L), 0 past each row's own frame count; t [F] float64 = i * frame_period / 1000."""
     if speed != 1:
         raise ValueError("only speed = 1 is built (DIO's decimation is not)")
+    x, ln, one = device_rows(x, lengths, "dio")
     lib = _lib.load()
-    x, ln, one = device_rows(x, lengths)
     B, L = x.shape
     o = _opts(fs, frame_period, f0_floor, f0_ceil, channels_in_octave, allowed_range)
     F = lib.dex_f0_frames(L, C.byref(o))
@@ -53,8 +53,8 @@ def dio(x, fs, f0_floor=71.0, f0_ceil=800.0, channels_in_octave=2.0, frame_perio
 def stonemask(x, f0, t, fs, lengths=None, frame_period=None):
     """pw.stonemask on the device: x as for ``dio``, f0 [F] / [B, F] from ``dio``, t its frame times (i * frame_period / 1000;
     frame_period is taken from t unless given) -> refined f0 of f0's shape, float64."""
+    x, ln, one = device_rows(x, lengths, "stonemask")
     lib = _lib.load()
-    x, ln, one = device_rows(x, lengths)
     B, L = x.shape
     t = torch.as_tensor(t, dtype=torch.float64).cpu().reshape(-1)
     if frame_period is None:
@@ -79,8 +79,8 @@ def stonemask(x, f0, t, fs, lengths=None, frame_period=None):
 
 def peak_normalize(x, lengths=None):
     """synthesize.py:46 ``wav / max(abs(wav))`` per row, in fp64 on the device, rounded to fp32 (0 past a row's length)."""
+    x, ln, one = device_rows(x, lengths, "peak_normalize")
     lib = _lib.load()
-    x, ln, one = device_rows(x, lengths)
     B, L = x.shape
     with torch.cuda.device(x.device):
         out = torch.empty_like(x)
@@ -88,14 +88,7 @@ def peak_normalize(x, lengths=None):
     return out[0] if one else out
 
 
-_STFT = {}
-
-
-def _stft(dev):
-    """One mel front-end per device (its DFT basis and filterbank are built once)."""
-    if dev not in _STFT:
-        _STFT[dev] = TacotronSTFT(device=dev)
-    return _STFT[dev]
+_stft = per_device(lambda dev: TacotronSTFT(device=dev))     # one mel front-end per device (its DFT basis and filterbank are built once)
 
 
 def reference_features(wav, lengths=None, sr=SR, stft: TacotronSTFT = None):
@@ -106,7 +99,7 @@ def reference_features(wav, lengths=None, sr=SR, stft: TacotronSTFT = None):
     dex_tts_amd.wavprep.preprocess_wav does the trim and the resampler too."""
     if sr != SR:
         raise ValueError(f"reference_features needs {SR} Hz audio (there is no resampler), got {sr}")
-    x, ln, _ = device_rows(wav, lengths)
+    x, ln, _ = device_rows(wav, lengths, "reference_features")
     return features(peak_normalize(x, ln), ln, stft)
 
 

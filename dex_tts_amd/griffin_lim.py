@@ -14,71 +14,22 @@ Every frame is a 1024-point real FFT in LDS (``csrc/griffin_lim.hip``, C ABI ``d
 """
 from __future__ import annotations
 
-import ctypes as C
-from typing import Optional, Sequence
+from typing import Optional
 
 import numpy as np
 import torch
 
-from . import _lib
-from ._native import stream
+from ._native import Handle, device_rows, host_lengths, i32_ptr, on_device, per_device, stream
 
 FILTER_LENGTH, HOP_LENGTH, WIN_LENGTH, N_BINS, N_MELS, SAMPLING_RATE = 1024, 256, 1024, 513, 80, 22050
 MIN_FRAMES = 4            # the transform's reflect pad needs 256 (F - 1) > 512 samples (the reference's F.pad fails below)
 
 
-class _Context:
-    """One DexGl handle (FFT twiddles, window, mel basis on the device) and a growing workspace per device."""
-
-    def __init__(self, device: torch.device):
-        self.device = device
-        self.lib = _lib.load()
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            rc = self.lib.dex_gl_create(C.byref(h))
-        if rc != _lib.DEX_OK:
-            raise RuntimeError(f"dex_gl_create failed ({rc})")
-        self.h = h
-        self._ws = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self.lib.dex_gl_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    def check(self, rc: int, what: str):
-        if rc != _lib.DEX_OK:
-            msg = self.lib.dex_gl_last_error(self.h).decode()
-            raise (ValueError if rc == -1 else RuntimeError)(f"{what}: {msg} ({rc})")       # -1: DEX_ERR_ARG, a refused argument
-
-    def workspace(self, B: int, max_frames: int) -> torch.Tensor:
-        need = int(self.lib.dex_gl_workspace_bytes(B, max_frames))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+_context = per_device(lambda device: Handle("dex_gl", device))     # one DexGl handle (FFT twiddles, window, mel basis) per device
 
 
-_contexts = {}
-
-
-def _context(device: torch.device) -> _Context:
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    if key not in _contexts:
-        _contexts[key] = _Context(torch.device("cuda", key))
-    return _contexts[key]
-
-
-def _on_device(x: torch.Tensor, what: str) -> torch.Tensor:
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise RuntimeError(f"{what} runs on an MI355X only (no CPU path): pass CUDA tensors")
-    return x
-
-
-def _i32(values) -> C.Array:
-    return (C.c_int32 * len(values))(*[int(v) for v in values])
+def _workspace(ctx: Handle, B: int, max_frames: int) -> torch.Tensor:
+    return ctx.workspace(int(ctx.lib.dex_gl_workspace_bytes(B, max_frames)))
 
 
 def _random_angles(shape) -> np.ndarray:
@@ -93,25 +44,16 @@ def _check_spec(S: torch.Tensor, what: str, min_frames: int = MIN_FRAMES):
         raise ValueError(f"{what}: a spectrogram needs at least {min_frames} frames, got {S.shape[2]}")
 
 
-def _frame_counts(lengths, B: int, T: int, lo: int, what: str) -> list:
-    n = [T] * B if lengths is None else [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
-    if len(n) != B:
-        raise ValueError(f"{what}: {len(n)} lengths for {B} rows")
-    if any(v < lo or v > T for v in n):
-        raise ValueError(f"{what}: every length must lie in [{lo}, {T}], got {n}")
-    return n
-
-
-def _griffin_lim(S: torch.Tensor, angles: torch.Tensor, frames: Sequence[int], n_iters: int) -> torch.Tensor:
-    """S, angles [B, 513, F] on one device, row b frames[b] frames -> [B, 256 (F - 1)] fp32, 0 past 256 (frames[b] - 1)."""
+def _griffin_lim(S: torch.Tensor, angles: torch.Tensor, frames: np.ndarray, n_iters: int) -> torch.Tensor:
+    """S, angles [B, 513, F] on one device, row b frames[b] frames (host int32) -> [B, 256 (F - 1)] fp32, 0 past 256 (frames[b] - 1)."""
     ctx = _context(S.device)
     B, _, F = S.shape
     S = S.to(torch.float32).contiguous()
     angles = angles.to(device=S.device, dtype=torch.float32).contiguous()
     out = torch.empty(B, HOP_LENGTH * (F - 1), dtype=torch.float32, device=S.device)
-    ws = ctx.workspace(B, F)
+    ws = _workspace(ctx, B, F)
     with torch.cuda.device(S.device):
-        rc = ctx.lib.dex_griffin_lim(ctx.h, S.data_ptr(), angles.data_ptr(), _i32(frames), B, F, int(n_iters), out.data_ptr(),
+        rc = ctx.lib.dex_griffin_lim(ctx.h, S.data_ptr(), angles.data_ptr(), i32_ptr(frames), B, F, int(n_iters), out.data_ptr(),
                                      ws.data_ptr(), ws.numel(), stream(S.device))
     ctx.check(rc, "dex_griffin_lim")
     return out
@@ -135,14 +77,14 @@ class STFT:
         B, L = input_data.shape
         if L <= FILTER_LENGTH // 2:
             raise ValueError(f"STFT.transform: the reflect pad needs more than {FILTER_LENGTH // 2} samples, got {L}")
-        y = _on_device(input_data, "STFT.transform").to(torch.float32).contiguous()
+        y, ln, _ = device_rows(input_data, None, "STFT.transform")
         self.num_samples = L
         ctx = _context(y.device)
         F = L // HOP_LENGTH + 1
         mag = torch.empty(B, N_BINS, F, dtype=torch.float32, device=y.device)
         phase = torch.empty_like(mag)
         with torch.cuda.device(y.device):
-            rc = ctx.lib.dex_stft_transform(ctx.h, y.data_ptr(), _i32([L] * B), B, L, mag.data_ptr(), phase.data_ptr(), stream(y.device))
+            rc = ctx.lib.dex_stft_transform(ctx.h, y.data_ptr(), i32_ptr(ln), B, L, mag.data_ptr(), phase.data_ptr(), stream(y.device))
         ctx.check(rc, "dex_stft_transform")
         return mag, phase
 
@@ -150,15 +92,15 @@ class STFT:
         _check_spec(magnitude, "STFT.inverse", 2)
         if tuple(phase.shape) != tuple(magnitude.shape):
             raise ValueError(f"STFT.inverse: phase {tuple(phase.shape)} does not match magnitude {tuple(magnitude.shape)}")
-        S = _on_device(magnitude, "STFT.inverse").to(torch.float32).contiguous()
-        ph = _on_device(phase, "STFT.inverse").to(device=S.device, dtype=torch.float32).contiguous()
+        S = on_device(magnitude, "STFT.inverse").to(torch.float32).contiguous()
+        ph = on_device(phase, "STFT.inverse").to(device=S.device, dtype=torch.float32).contiguous()
         ctx = _context(S.device)
         B, _, F = S.shape
         out = torch.empty(B, HOP_LENGTH * (F - 1), dtype=torch.float32, device=S.device)
-        ws = ctx.workspace(B, F)
+        ws = _workspace(ctx, B, F)
         with torch.cuda.device(S.device):
-            rc = ctx.lib.dex_stft_inverse(ctx.h, S.data_ptr(), ph.data_ptr(), _i32([F] * B), B, F, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                          stream(S.device))
+            rc = ctx.lib.dex_stft_inverse(ctx.h, S.data_ptr(), ph.data_ptr(), i32_ptr(host_lengths(None, B, F)), B, F, out.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), stream(S.device))
         ctx.check(rc, "dex_stft_inverse")
         return out.unsqueeze(1)
 
@@ -181,12 +123,12 @@ def griffin_lim(magnitudes: torch.Tensor, stft_fn: STFT, n_iters: int = 30, angl
         raise ValueError(f"griffin_lim: n_iters must be >= 0, got {n_iters}")
     if angles is not None and tuple(angles.shape) != tuple(magnitudes.shape):
         raise ValueError(f"griffin_lim: angles {tuple(angles.shape)} do not match magnitudes {tuple(magnitudes.shape)}")
-    S = _on_device(magnitudes, "griffin_lim")
+    S = on_device(magnitudes, "griffin_lim")
     if angles is None:
         angles = torch.from_numpy(_random_angles(magnitudes.size()))
     elif not isinstance(angles, torch.Tensor):
         angles = torch.as_tensor(np.asarray(angles, dtype=np.float32))
-    return _griffin_lim(S, angles, [S.shape[2]] * S.shape[0], n_iters)
+    return _griffin_lim(S, angles, host_lengths(None, S.shape[0], S.shape[2]), n_iters)
 
 
 def mel_to_linear(mel: torch.Tensor, lengths=None) -> torch.Tensor:
@@ -198,12 +140,12 @@ def mel_to_linear(mel: torch.Tensor, lengths=None) -> torch.Tensor:
     if m.dim() != 3 or m.shape[1] != N_MELS:
         raise ValueError(f"mel_to_linear: expected a mel [B, {N_MELS}, T], got {tuple(mel.shape)}")
     B, _, T = m.shape
-    n = _frame_counts(lengths, B, T, 2, "mel_to_linear")
-    m = _on_device(m, "mel_to_linear").to(torch.float32).contiguous()
+    n = host_lengths(lengths, B, T, lo=2, what="mel_to_linear")
+    m = on_device(m, "mel_to_linear").to(torch.float32).contiguous()
     ctx = _context(m.device)
     spec = torch.empty(B, N_BINS, T - 1, dtype=torch.float32, device=m.device)
     with torch.cuda.device(m.device):
-        rc = ctx.lib.dex_mel_to_linear(ctx.h, m.data_ptr(), _i32(n), B, T, spec.data_ptr(), stream(m.device))
+        rc = ctx.lib.dex_mel_to_linear(ctx.h, m.data_ptr(), i32_ptr(n), B, T, spec.data_ptr(), stream(m.device))
     ctx.check(rc, "dex_mel_to_linear")
     return spec[0] if one else spec
 
@@ -220,19 +162,19 @@ def mel_to_wav(mel: torch.Tensor, lengths=None, n_iters: int = 60, angles: Optio
     if m.dim() != 3 or m.shape[1] != N_MELS:
         raise ValueError(f"mel_to_wav: expected a mel [B, {N_MELS}, T], got {tuple(mel.shape)}")
     B, _, T = m.shape
-    n = _frame_counts(lengths, B, T, MIN_FRAMES + 1, "mel_to_wav")
+    n = host_lengths(lengths, B, T, lo=MIN_FRAMES + 1, what="mel_to_wav")
     if int(n_iters) < 0:
         raise ValueError(f"mel_to_wav: n_iters must be >= 0, got {n_iters}")
     if angles is not None and tuple(angles.shape) != (B, N_BINS, T - 1):
         raise ValueError(f"mel_to_wav: angles must be [{B}, {N_BINS}, {T - 1}], got {tuple(angles.shape)}")
-    m = _on_device(m, "mel_to_wav")
+    m = on_device(m, "mel_to_wav")
     S = mel_to_linear(m, n)
     if angles is None:
         a = np.zeros((B, N_BINS, T - 1), dtype=np.float32)
         for b in range(B):
             a[b, :, : n[b] - 1] = _random_angles((N_BINS, n[b] - 1))
         angles = torch.from_numpy(a)
-    wav = _griffin_lim(S, angles, [v - 1 for v in n], n_iters)
+    wav = _griffin_lim(S, angles, n - 1, n_iters)
     return wav[0] if one else wav
 
 
@@ -247,6 +189,6 @@ def inv_mel_spec(mel: torch.Tensor, out_filename: str, _stft, griffin_iters: int
         raise ValueError(f"inv_mel_spec: expected a mel [{N_MELS}, T], got {tuple(mel.shape)}")
     if mel.shape[1] < MIN_FRAMES + 1:
         raise ValueError(f"inv_mel_spec: a mel needs at least {MIN_FRAMES + 1} frames, got {mel.shape[1]}")
-    spec = mel_to_linear(_on_device(mel, "inv_mel_spec")[None])
+    spec = mel_to_linear(on_device(mel, "inv_mel_spec")[None])
     audio = griffin_lim(spec, _stft._stft_fn, griffin_iters).squeeze()
     write(out_filename, _stft.sampling_rate, audio.cpu().numpy())

@@ -20,15 +20,13 @@ Two departures from the reference's number, both stated here so nobody compares 
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional, Sequence
 
 import numpy as np
 import torch
 
-from . import _lib
-from ._native import stream
+from ._native import Handle, device_index, device_rows, i32_ptr, on_device, pad_wavs, per_device, resample_to_16k, stream, upload_weights
 
 SAMPLING_RATE, N_FFT, HOP, N_MELS, PARTIALS_N_FRAMES, EMBED, HIDDEN, LAYERS = 16000, 400, 160, 40, 160, 256, 256, 3
 AUDIO_NORM_TARGET_DBFS = -30.0
@@ -96,77 +94,20 @@ def compute_partial_slices(n_samples: int, rate: float = 1.3, min_coverage: floa
     return wav_slices, mel_slices
 
 
-class _Context:
-    """One DexSpk handle (DFT twiddles, window, mel basis on the device; optionally the weights) and a growing workspace."""
+class _Spk(Handle):
+    """One DexSpk handle (DFT twiddles, window, mel basis on the device; optionally the weights); its workspace is the network's."""
 
-    def __init__(self, device: torch.device):
-        self.device = device
-        self.lib = _lib.load()
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            rc = self.lib.dex_spk_create(C.byref(h))
-        if rc != _lib.DEX_OK:
-            raise RuntimeError(f"dex_spk_create failed ({rc})")
-        self.h = h
-        self._ws = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self.lib.dex_spk_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    def check(self, rc: int, what: str):
-        if rc != _lib.DEX_OK:
-            msg = self.lib.dex_spk_last_error(self.h).decode()
-            raise (ValueError if rc in (-1, -2) else RuntimeError)(f"{what}: {msg} ({rc})")     # -1 a refused argument, -2 weights not loaded
+    def __init__(self, device):
+        super().__init__("dex_spk", device)
 
     def workspace(self, P: int, T: int) -> torch.Tensor:
         need = int(self.lib.dex_spk_forward_workspace_bytes(P, T))
         if need == 0:
             raise ValueError(f"{P} rows of {T} frames are more than one call takes")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return super().workspace(need)
 
 
-_contexts = {}
-
-
-def _device_index(device: torch.device) -> int:
-    return device.index if device.index is not None else torch.cuda.current_device()
-
-
-def _context(device: torch.device) -> _Context:
-    key = _device_index(device)
-    if key not in _contexts:
-        _contexts[key] = _Context(torch.device("cuda", key))
-    return _contexts[key]
-
-
-def _i32(values) -> C.Array:
-    return (C.c_int32 * len(values))(*[int(v) for v in values])
-
-
-def _rows(wav, lengths, what: str):
-    """wav [n] or [B, n] CUDA tensor, lengths -> (fp32 contiguous [B, n], host lengths list, was one-dimensional)."""
-    if not isinstance(wav, torch.Tensor) or not wav.is_cuda:
-        raise ValueError(f"{what} runs on an MI355X only (no CPU path): pass CUDA tensors")
-    if wav.dim() not in (1, 2):
-        raise ValueError(f"{what}: expected a wav [n] or [B, n], got {tuple(wav.shape)}")
-    one = wav.dim() == 1
-    x = (wav[None] if one else wav).to(torch.float32).contiguous()
-    B, n = x.shape
-    if B < 1 or n < 1:
-        raise ValueError(f"{what}: a wav needs at least one sample, got {tuple(wav.shape)}")
-    ln = [n] * B if lengths is None else [int(v) for v in (lengths.tolist() if isinstance(lengths, (torch.Tensor, np.ndarray)) else lengths)]
-    if len(ln) != B:
-        raise ValueError(f"{what}: {len(ln)} lengths for {B} rows")
-    if any(v < 1 or v > n for v in ln):
-        raise ValueError(f"{what}: every length must lie in [1, {n}], got {ln}")
-    return x, ln, one
+_context = per_device(_Spk)
 
 
 def normalize_volume(wav: torch.Tensor, target_dBFS: float = AUDIO_NORM_TARGET_DBFS, increase_only: bool = True, lengths=None) -> torch.Tensor:
@@ -177,11 +118,11 @@ def normalize_volume(wav: torch.Tensor, target_dBFS: float = AUDIO_NORM_TARGET_D
         raise ValueError("normalize_volume: only increase_only=True (the reference's call) is built")
     if not math.isfinite(float(target_dBFS)):
         raise ValueError(f"normalize_volume: target_dBFS must be finite, got {target_dBFS}")
-    x, ln, one = _rows(wav, lengths, "normalize_volume")
+    x, ln, one = device_rows(wav, lengths, "normalize_volume", refuse=ValueError)
     ctx = _context(x.device)
     out = torch.empty_like(x)
     with torch.cuda.device(x.device):
-        rc = ctx.lib.dex_spk_normalize_volume(ctx.h, x.data_ptr(), _i32(ln), x.shape[0], x.shape[1], float(target_dBFS), out.data_ptr(),
+        rc = ctx.lib.dex_spk_normalize_volume(ctx.h, x.data_ptr(), i32_ptr(ln), x.shape[0], x.shape[1], float(target_dBFS), out.data_ptr(),
                                               stream(x.device))
     ctx.check(rc, "dex_spk_normalize_volume")
     return out[0] if one else out
@@ -191,12 +132,12 @@ def wav_to_mel_spectrogram(wav: torch.Tensor, lengths=None) -> torch.Tensor:
     """resemblyzer's ``wav_to_mel_spectrogram``: ``librosa.feature.melspectrogram(y, sr=16000, n_fft=400, hop_length=160, n_mels=40).T``
     (center=True with zero padding, periodic Hann, POWER spectrogram, Slaney mels with area normalisation, no logarithm) for wav [n] or
     a ragged batch [B, n] -> float32 [1 + n // 160, 40] or [B, 1 + n // 160, 40]; row b fills 1 + lengths[b] // 160 frames, 0 past them."""
-    x, ln, one = _rows(wav, lengths, "wav_to_mel_spectrogram")
+    x, ln, one = device_rows(wav, lengths, "wav_to_mel_spectrogram", refuse=ValueError)
     ctx = _context(x.device)
     B, n = x.shape
     mel = torch.empty(B, n // HOP + 1, N_MELS, dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        rc = ctx.lib.dex_spk_mel(ctx.h, x.data_ptr(), _i32(ln), B, n, mel.data_ptr(), stream(x.device))
+        rc = ctx.lib.dex_spk_mel(ctx.h, x.data_ptr(), i32_ptr(ln), B, n, mel.data_ptr(), stream(x.device))
     ctx.check(rc, "dex_spk_mel")
     return mel[0] if one else mel
 
@@ -206,15 +147,12 @@ def preprocess_wav(wav: torch.Tensor, source_sr: Optional[int] = None, lengths=N
     (``wavprep.resample``: resampy's kaiser_best in fp64, rounded to fp32 once; current librosa resamples with soxr), then
     ``normalize_volume(wav, -30, increase_only=True)``.  ``trim_long_silences`` (webrtcvad) is LEFT OUT: trim on the host first for
     the reference's exact number.  Returns (wav fp32 [n'] or [B, max n'], host int32 lengths)."""
-    x, ln, one = _rows(wav, lengths, "preprocess_wav")
+    x, ln, one = device_rows(wav, lengths, "preprocess_wav", refuse=ValueError)
     if source_sr is not None and int(source_sr) <= 0:
         raise ValueError(f"preprocess_wav: source_sr must be positive, got {source_sr}")
-    if source_sr is not None and int(source_sr) != SAMPLING_RATE:
-        from . import wavprep
-        y, lo = wavprep.resample(x, int(source_sr), SAMPLING_RATE, lengths=ln)
-        x, ln = y.to(torch.float32), [int(v) for v in lo]
+    x, ln = resample_to_16k(x, ln, source_sr)
     out = normalize_volume(x, AUDIO_NORM_TARGET_DBFS, True, ln)
-    return (out[0] if one else out), np.asarray(ln, dtype=np.int32)
+    return (out[0] if one else out), ln
 
 
 class VoiceEncoder:
@@ -224,21 +162,12 @@ class VoiceEncoder:
         device = torch.device(device)
         if device.type != "cuda":
             raise ValueError("VoiceEncoder runs on an MI355X only (no CPU path)")
-        self.device = torch.device("cuda", _device_index(device))
-        self._ctx = _Context(self.device)
+        self.device = torch.device("cuda", device_index(device))
+        self._ctx = _Spk(self.device)
         self._loaded = False
 
     def load_state_dict(self, sd, strict: bool = True):
-        routed = route_state_dict(sd)
-        ctx = self._ctx
-        keep = []
-        with torch.cuda.device(self.device):
-            for k, v in routed.items():
-                t = v.detach().to(device=self.device, dtype=torch.float32).contiguous()
-                keep.append(t)
-                shape = (C.c_int64 * t.dim())(*t.shape)
-                ctx.check(ctx.lib.dex_spk_load(ctx.h, k.encode(), t.data_ptr(), shape, t.dim(), stream(self.device)), f"dex_spk_load({k})")
-            torch.cuda.current_stream(self.device).synchronize()        # the uploads read `keep`
+        upload_weights(self._ctx, self._ctx.lib.dex_spk_load, route_state_dict(sd), self.device)
         self._loaded = True
         return self
 
@@ -249,8 +178,7 @@ class VoiceEncoder:
     def forward(self, mels: torch.Tensor) -> torch.Tensor:
         """mels [P, T, 40] (T >= 1) -> unit-norm embeddings [P, 256]."""
         self._need_weights("VoiceEncoder.forward")
-        if not isinstance(mels, torch.Tensor) or not mels.is_cuda:
-            raise ValueError("VoiceEncoder.forward runs on an MI355X only (no CPU path): pass CUDA tensors")
+        on_device(mels, "VoiceEncoder.forward", ValueError)
         if mels.dim() != 3 or mels.shape[2] != N_MELS or mels.shape[0] < 1 or mels.shape[1] < 1:
             raise ValueError(f"VoiceEncoder.forward: expected mels [P, T, {N_MELS}] with P, T >= 1, got {tuple(mels.shape)}")
         x = mels.to(device=self.device, dtype=torch.float32).contiguous()
@@ -267,8 +195,8 @@ class VoiceEncoder:
 
     def _embed(self, x: torch.Tensor, ln: Sequence[int], rate: float, min_coverage: float, want_partials: bool):
         slices = [compute_partial_slices(n, rate, min_coverage) for n in ln]
-        counts = [len(m) for _, m in slices]
-        starts = [m.start for _, ms in slices for m in ms]
+        counts = np.array([len(m) for _, m in slices], dtype=np.int32)
+        starts = np.array([m.start for _, ms in slices for m in ms], dtype=np.int32)
         B, n = x.shape
         P = len(starts)
         ctx = self._ctx
@@ -276,7 +204,7 @@ class VoiceEncoder:
         out = torch.empty(B, EMBED, dtype=torch.float32, device=self.device)
         partials = torch.empty(P, EMBED, dtype=torch.float32, device=self.device) if want_partials else None
         with torch.cuda.device(self.device):
-            rc = ctx.lib.dex_spk_embed(ctx.h, x.data_ptr(), _i32(ln), B, n, _i32(counts), _i32(starts), P, out.data_ptr(),
+            rc = ctx.lib.dex_spk_embed(ctx.h, x.data_ptr(), i32_ptr(ln), B, n, i32_ptr(counts), i32_ptr(starts), P, out.data_ptr(),
                                        partials.data_ptr() if want_partials else None, ws.data_ptr(), ws.numel(), stream(self.device))
         ctx.check(rc, "dex_spk_embed")
         return out, partials, slices
@@ -287,7 +215,7 @@ class VoiceEncoder:
         self._need_weights("VoiceEncoder.embed_utterance")
         if isinstance(wav, torch.Tensor) and wav.dim() != 1:
             raise ValueError(f"VoiceEncoder.embed_utterance: expected a wav [n], got {tuple(wav.shape)}")
-        x, ln, _ = _rows(wav, None, "VoiceEncoder.embed_utterance")
+        x, ln, _ = device_rows(wav, None, "VoiceEncoder.embed_utterance", refuse=ValueError)
         out, partials, slices = self._embed(x.to(self.device), ln, rate, min_coverage, return_partials)
         return (out[0], partials, slices[0][0]) if return_partials else out[0]
 
@@ -297,35 +225,23 @@ class VoiceEncoder:
         self._need_weights("VoiceEncoder.embed_utterances")
         if isinstance(wavs, torch.Tensor) and wavs.dim() != 2:
             raise ValueError(f"VoiceEncoder.embed_utterances: expected wavs [B, n], got {tuple(wavs.shape)}")
-        x, ln, _ = _rows(wavs, lengths, "VoiceEncoder.embed_utterances")
+        x, ln, _ = device_rows(wavs, lengths, "VoiceEncoder.embed_utterances", refuse=ValueError)
         return self._embed(x.to(self.device), ln, rate, min_coverage, False)[0]
 
     def embed_speaker(self, wavs, lengths=None, **kwargs) -> torch.Tensor:
         """resemblyzer's ``embed_speaker``: the L2-normalised mean of the utterance embeddings.  ``wavs`` is [B, n] with ``lengths``
         or a list of wavs [n_b]."""
         if not isinstance(wavs, torch.Tensor):
-            wavs, lengths = _pad_list(wavs, self.device)
+            wavs, lengths = pad_wavs(wavs, self.device)
         e = self.embed_utterances(wavs, lengths, **kwargs)
         m = e.mean(dim=0)
         return m / torch.linalg.vector_norm(m)
 
 
-def _pad_list(wavs, device):
-    """list of 1-D wavs (tensors or numpy arrays, any integer or float type) -> (fp32 [B, max n] on the device, lengths)."""
-    rows = [torch.as_tensor(np.asarray(w.cpu() if isinstance(w, torch.Tensor) else w)).reshape(-1) for w in wavs]
-    if not rows or min(len(r) for r in rows) < 1:
-        raise ValueError("every wav needs at least one sample")
-    out = torch.zeros(len(rows), max(len(r) for r in rows), dtype=torch.float32)
-    for b, r in enumerate(rows):
-        out[b, : len(r)] = r.to(torch.float32)
-    return out.to(device), [len(r) for r in rows]
-
-
 def cosine(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """calculate_accept (metric.py:69-79): <a, b> / (|a| |b|) per row of a, b [B, D] -> [B]."""
     for t in (a, b):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError("cosine runs on an MI355X only (no CPU path): pass CUDA tensors")
+        on_device(t, "cosine", ValueError)
     if a.dim() != 2 or tuple(a.shape) != tuple(b.shape) or a.shape[0] < 1 or a.shape[1] < 1:
         raise ValueError(f"cosine: expected two [B, D] tensors, got {tuple(a.shape)} and {tuple(b.shape)}")
     a = a.to(torch.float32).contiguous()
@@ -345,28 +261,37 @@ def _encoder(encoder, what: str) -> "VoiceEncoder":
     return encoder
 
 
-def speaker_similarity(syn: torch.Tensor, trg: torch.Tensor, syn_lengths=None, trg_lengths=None, source_sr: Optional[int] = 22050,
-                       encoder: Optional[VoiceEncoder] = None) -> torch.Tensor:
-    """metric.py:69-79 for a batch: syn, trg [B, n] (or [n]) at ``source_sr`` Hz, rows of ``*_lengths`` samples -> cos [B] on the
-    device.  Both sides go through ``preprocess_wav`` and are embedded in ONE ``embed_utterances`` call of 2 B utterances."""
-    encoder = _encoder(encoder, "speaker_similarity")
-    s, sl = preprocess_wav(syn, source_sr, syn_lengths)
-    t, tl = preprocess_wav(trg, source_sr, trg_lengths)
+def _similarity(what, encoder, syn, syn_lengths, syn_sr, trg, trg_lengths, trg_sr) -> torch.Tensor:
+    """Both sides through ``preprocess_wav``, stacked as 2 B rows, embedded in ONE ``embed_utterances`` call -> cos [B]."""
+    encoder = _encoder(encoder, what)
+    s, sl = preprocess_wav(syn, syn_sr, syn_lengths)
+    t, tl = preprocess_wav(trg, trg_sr, trg_lengths)
     s, t = (v[None] if v.dim() == 1 else v for v in (s, t))
     if s.shape[0] != t.shape[0]:
-        raise ValueError(f"speaker_similarity: {s.shape[0]} synthesised rows against {t.shape[0]} reference rows")
+        raise ValueError(f"{what}: {s.shape[0]} synthesised rows against {t.shape[0]} reference rows")
     B, n = s.shape[0], max(s.shape[1], t.shape[1])
     both = torch.zeros(2 * B, n, dtype=torch.float32, device=s.device)
     both[:B, : s.shape[1]] = s
     both[B:, : t.shape[1]] = t
-    e = encoder.embed_utterances(both, list(sl) + list(tl))
+    e = encoder.embed_utterances(both, np.concatenate([sl, tl]))
     return cosine(e[:B], e[B:])
+
+
+def _mean_stderr(cos: torch.Tensor):
+    c = cos.double().cpu().numpy()
+    return float(np.mean(c)), float(np.std(c) / np.sqrt(len(c)))
+
+
+def speaker_similarity(syn: torch.Tensor, trg: torch.Tensor, syn_lengths=None, trg_lengths=None, source_sr: Optional[int] = 22050,
+                       encoder: Optional[VoiceEncoder] = None) -> torch.Tensor:
+    """metric.py:69-79 for a batch: syn, trg [B, n] (or [n]) at ``source_sr`` Hz, rows of ``*_lengths`` samples -> cos [B] on the
+    device.  Both sides go through ``preprocess_wav`` and are embedded in ONE ``embed_utterances`` call of 2 B utterances."""
+    return _similarity("speaker_similarity", encoder, syn, syn_lengths, source_sr, trg, trg_lengths, source_sr)
 
 
 def asv_score(syn, trg, syn_lengths=None, trg_lengths=None, source_sr: Optional[int] = 22050, encoder: Optional[VoiceEncoder] = None):
     """calculate_asv_score (metric.py:81-95): (mean, std / sqrt(n)) of the pairs' cosines, with numpy's population std."""
-    cos = speaker_similarity(syn, trg, syn_lengths, trg_lengths, source_sr, encoder).double().cpu().numpy()
-    return float(np.mean(cos)), float(np.std(cos) / np.sqrt(len(cos)))
+    return _mean_stderr(speaker_similarity(syn, trg, syn_lengths, trg_lengths, source_sr, encoder))
 
 
 def score_synthesis(audio: Sequence, ref_wavs: Sequence, sr: int = 22050, ref_sr: Optional[int] = None,
@@ -377,15 +302,7 @@ def score_synthesis(audio: Sequence, ref_wavs: Sequence, sr: int = 22050, ref_sr
     if len(audio) != len(ref_wavs) or len(audio) < 1:
         raise ValueError(f"score_synthesis: {len(audio)} waveforms against {len(ref_wavs)} reference wavs")
     encoder = _encoder(encoder, "score_synthesis")
-    syn, sl = _pad_list([np.asarray(a, dtype=np.float32) / 32768.0 if np.asarray(a).dtype == np.int16 else a for a in audio], encoder.device)
-    trg, tl = _pad_list(ref_wavs, encoder.device)
-    s, sl = preprocess_wav(syn, sr, sl)
-    t, tl = preprocess_wav(trg, ref_sr or sr, tl)
-    B, n = s.shape[0], max(s.shape[1], t.shape[1])
-    both = torch.zeros(2 * B, n, dtype=torch.float32, device=s.device)
-    both[:B, : s.shape[1]] = s
-    both[B:, : t.shape[1]] = t
-    e = encoder.embed_utterances(both, list(sl) + list(tl))
-    cos = cosine(e[:B], e[B:])
-    c = cos.double().cpu().numpy()
-    return cos, float(np.mean(c)), float(np.std(c) / np.sqrt(len(c)))
+    syn, sl = pad_wavs(audio, encoder.device, scale_int16=True)
+    trg, tl = pad_wavs(ref_wavs, encoder.device, scale_int16=True)
+    cos = _similarity("score_synthesis", encoder, syn, sl, sr, trg, tl, ref_sr or sr)
+    return (cos,) + _mean_stderr(cos)

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from . import f0 as F0
-from ._native import check, device_rows, i32_ptr, stream
+from ._native import check, device_rows, host_lengths, i32_ptr, pad_wavs, per_device, stream
 
 SR = F0.SR
 
@@ -48,23 +48,17 @@ def _trim_opts(top_db, frame_length, hop_length, pad_mode):
     return _lib.DexWavTrimOpts(float(top_db), int(frame_length), int(hop_length), _lib.WAV_PAD[pad_mode])
 
 
-def _i32(v):
-    return np.ascontiguousarray(np.asarray(v, dtype=np.int32))
-
-
 def _rates(sr, B):
-    srs = np.full(B, sr, dtype=np.int64) if np.ndim(sr) == 0 else np.asarray(sr, dtype=np.int64).reshape(-1)
-    if srs.shape != (B,) or (srs <= 0).any() or (srs > np.iinfo(np.int32).max).any():
-        raise ValueError(f"sample rates must be {B} positive integers, got {sr}")
-    return _i32(srs)
+    """One sample rate, or one per row -> host int32 [B] of positive rates."""
+    return host_lengths(np.full(B, sr) if np.ndim(sr) == 0 else sr, B, np.iinfo(np.int32).max, what="sample rates")
 
 
 def trim(wav, lengths=None, top_db=30.0, frame_length=2048, hop_length=512, pad_mode="constant", return_mse=False):
     """librosa.effects.trim(wav, top_db)[1] per row: wav [L] or [B, L] (a CUDA tensor; rows of ``lengths`` samples) -> bounds
     [2] or [B, 2] int32 on the device, (start, end) of the non-silent part.  return_mse: also each frame's mean square, float64
     [F] or [B, F] with F = 1 + L // hop_length (0 past a row's own frames)."""
+    x, ln, one = device_rows(wav, lengths, "trim")
     lib = _lib.load()
-    x, ln, one = device_rows(wav, lengths)
     B, L = x.shape
     o = _trim_opts(top_db, frame_length, hop_length, pad_mode)
     need = int(lib.dex_wav_trim_workspace_bytes(B, i32_ptr(ln), C.byref(o)))
@@ -89,27 +83,23 @@ def resampled_length(n_samples, sr_orig, sr_new):
     return n
 
 
-_TABLE = {}
-
-
+@per_device
 def _table(dev):
     """The kaiser_best window table of one device, built once (dex_wav_resample_table) and kept."""
-    if dev not in _TABLE:
-        lib = _lib.load()
-        need = int(lib.dex_wav_resample_table_bytes(None))
-        with torch.cuda.device(dev):
-            tab = torch.empty(need, dtype=torch.uint8, device=dev)
-            check(lib.dex_wav_resample_table(None, tab.data_ptr(), need, stream(dev)), "dex_wav_resample_table")
-            torch.cuda.current_stream(dev).synchronize()          # ready for calls on any stream
-        _TABLE[dev] = tab
-    return _TABLE[dev]
+    lib = _lib.load()
+    need = int(lib.dex_wav_resample_table_bytes(None))
+    with torch.cuda.device(dev):
+        tab = torch.empty(need, dtype=torch.uint8, device=dev)
+        check(lib.dex_wav_resample_table(None, tab.data_ptr(), need, stream(dev)), "dex_wav_resample_table")
+        torch.cuda.current_stream(dev).synchronize()          # ready for calls on any stream
+    return tab
 
 
 def _resample(x, offsets, lengths, srs, sr_new):
     """x fp32 [B, Ls] (device), host int32 offsets / lengths / rates -> (fp64 [B, max L_out] on the device, host int32 L_out)."""
     lib = _lib.load()
     B, Ls = x.shape
-    lo = _i32([resampled_length(int(n), int(s), sr_new) for n, s in zip(lengths, srs)])
+    lo = np.array([resampled_length(int(n), int(s), sr_new) for n, s in zip(lengths, srs)], dtype=np.int32)
     Lm = int(lo.max())
     tab = _table(x.device)
     with torch.cuda.device(x.device):
@@ -124,12 +114,11 @@ def resample(wav, sr_orig, sr_new, lengths=None, offsets=None):
     ``lengths[b]`` samples from ``offsets[b]`` (default 0) at ``sr_orig`` Hz (an int or one per row) -> (y, lengths_out): y [L_out]
     or [B, max L_out] float64 on the device (0 past a row's length), lengths_out a host int32 array.  A row already at sr_new is
     copied."""
-    x, _, one = device_rows(wav, None)
+    x, ln, one = device_rows(wav, lengths, "resample")
     B, L = x.shape
-    ln = np.full(B, L, np.int32) if lengths is None else _i32(torch.as_tensor(lengths).cpu()).reshape(-1)
-    off = np.zeros(B, np.int32) if offsets is None else _i32(torch.as_tensor(offsets).cpu()).reshape(-1)
-    if ln.shape != (B,) or off.shape != (B,) or (ln < 1).any() or (off < 0).any() or (off.astype(np.int64) + ln > L).any():
-        raise ValueError(f"offsets / lengths must describe B = {B} non-empty spans inside rows of {L} samples")
+    off = np.zeros(B, np.int32) if offsets is None else host_lengths(offsets, B, L - 1, lo=0, what="resample offsets")
+    if (off.astype(np.int64) + ln > L).any():
+        raise ValueError(f"resample: offsets / lengths must describe B = {B} non-empty spans inside rows of {L} samples")
     if int(sr_new) <= 0:
         raise ValueError(f"sr_new must be positive, got {sr_new}")
     y, lo = _resample(x, off, ln, _rates(sr_orig, B), int(sr_new))
@@ -139,18 +128,9 @@ def resample(wav, sr_orig, sr_new, lengths=None, offsets=None):
 def peak_normalize_f64(y, lengths=None):
     """synthesize.py:46 on fp64 rows: y [L] or [B, L] (a CUDA tensor; promoted to float64 if it is not), rows of ``lengths`` samples
     -> float(y / max|y|) fp32 of y's shape (0 past a row's length and for a silent row)."""
+    y, ln, one = device_rows(y, lengths, "peak_normalize_f64", dtype=torch.float64)
     lib = _lib.load()
-    if not torch.is_tensor(y) or not y.is_cuda:
-        raise RuntimeError("peak_normalize_f64 runs on an MI355X only (no CPU path): pass a CUDA tensor")
-    one = y.dim() == 1
-    y = y.reshape(1, -1) if one else y
-    if y.dim() != 2 or y.shape[1] < 1:
-        raise ValueError("y must be [L] or [B, L]")
     B, L = y.shape
-    ln = np.full(B, L, np.int32) if lengths is None else _i32(torch.as_tensor(lengths).cpu()).reshape(-1)
-    if ln.shape != (B,) or (ln < 1).any() or (ln > L).any():
-        raise ValueError(f"lengths must hold B = {B} values in [1, {L}]")
-    y = y.to(torch.float64).contiguous()
     need = int(lib.dex_wav_peak_workspace_bytes(B, L))
     with torch.cuda.device(y.device):
         ws = torch.empty(max(need, 1), dtype=torch.uint8, device=y.device)
@@ -162,30 +142,28 @@ def peak_normalize_f64(y, lengths=None):
 
 def _load(paths):
     rows, srs = zip(*(read_wav(p) for p in paths))
-    L = max(len(r) for r in rows)
-    if min(len(r) for r in rows) < 1:
-        raise ValueError("empty wav")
-    x = np.zeros((len(rows), L), np.float32)
-    for b, r in enumerate(rows):
-        x[b, : len(r)] = r
-    dev = torch.device("cuda", torch.cuda.current_device())
-    return torch.from_numpy(x).to(dev), [len(r) for r in rows], list(srs)
+    x, ln = pad_wavs(rows, torch.device("cuda", torch.cuda.current_device()))
+    return x, ln, list(srs)
+
+
+def _prepare(wav, sr, lengths, top_db, pad_mode, what):
+    if isinstance(wav, (str, os.PathLike)) or (isinstance(wav, (list, tuple)) and wav and isinstance(wav[0], (str, os.PathLike))):
+        wav, lengths, sr = _load([wav] if isinstance(wav, (str, os.PathLike)) else list(wav))
+    elif sr is None:
+        raise ValueError(f"{what}: pass the sample rate of the tensor's rows")
+    x, ln, _ = device_rows(wav, lengths, what)
+    B = x.shape[0]
+    srs = _rates(sr, B)
+    bounds = trim(x, ln, top_db=top_db, pad_mode=pad_mode).cpu().numpy().reshape(B, 2)
+    y, lo = _resample(x, np.ascontiguousarray(bounds[:, 0]), bounds[:, 1] - bounds[:, 0], srs, SR)
+    return peak_normalize_f64(y, lo), lo
 
 
 def prepare(wav, sr=None, lengths=None, top_db=30.0, pad_mode="constant"):
     """synthesize.py:41-46 on the device: ``wav`` as for ``preprocess_wav`` -> (xn, lengths): the trimmed, resampled (to 22050 Hz
     where the rate differs) and peak-normalised rows as fp32 [B, max length] on the device (computed in fp64, rounded once; 0 past a
     row's length) and their host int32 lengths.  The one host synchronisation reads the trim bounds back."""
-    if isinstance(wav, (str, os.PathLike)) or (isinstance(wav, (list, tuple)) and wav and isinstance(wav[0], (str, os.PathLike))):
-        wav, lengths, sr = _load([wav] if isinstance(wav, (str, os.PathLike)) else list(wav))
-    elif sr is None:
-        raise ValueError("pass the sample rate of the tensor's rows")
-    x, ln, _ = device_rows(wav, lengths)
-    B = x.shape[0]
-    srs = _rates(sr, B)
-    bounds = trim(x, ln, top_db=top_db, pad_mode=pad_mode).cpu().numpy().reshape(B, 2)
-    y, lo = _resample(x, _i32(bounds[:, 0]), _i32(bounds[:, 1] - bounds[:, 0]), srs, SR)
-    return peak_normalize_f64(y, lo), lo
+    return _prepare(wav, sr, lengths, top_db, pad_mode, "prepare")
 
 
 def preprocess_wav(wav, sr=None, lengths=None, stft=None, top_db=30.0, pad_mode="constant"):
@@ -194,4 +172,4 @@ def preprocess_wav(wav, sr=None, lengths=None, stft=None, top_db=30.0, pad_mode=
     Hz (an int or one per row).  Trim at the source rate, resample to 22050 Hz in fp64 where the rate differs, peak-normalise in fp64,
     round to fp32 once (``prepare``), then the mel and the f0 tracker -> the dict of ``dex_tts_amd.f0.reference_features`` (which
     DeXTTS.forward / synthesize_tokens(style=...) take)."""
-    return F0.features(*prepare(wav, sr, lengths, top_db, pad_mode), stft)
+    return F0.features(*_prepare(wav, sr, lengths, top_db, pad_mode, "preprocess_wav"), stft)
