@@ -251,6 +251,21 @@ SYMBOLS = [
     ("dex_asr_transcribe", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_size_t, C.c_void_p]),
     ("dex_asr_ctc", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("dex_wavlm_create", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("dex_wavlm_destroy", None, [C.c_void_p]),
+    ("dex_wavlm_last_error", C.c_char_p, [C.c_void_p]),
+    ("dex_wavlm_load", C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
+    ("dex_wavlm_finalize", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("dex_wavlm_num_weights", C.c_int, [C.c_void_p]),
+    ("dex_wavlm_weight_info", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    ("dex_wavlm_num_frames", C.c_int, [C.c_void_p, C.c_int]),
+    ("dex_wavlm_min_samples", C.c_int, [C.c_void_p]),
+    ("dex_wavlm_rel_buckets", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]),
+    ("dex_wavlm_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    ("dex_wavlm_hidden", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                   C.c_void_p]),
+    ("dex_wavlm_embed", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                  C.c_void_p]),
 ]
 
 _lib = None

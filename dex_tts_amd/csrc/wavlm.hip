@@ -1,0 +1,908 @@
+// wavlm.hip — WavLM x-vector speaker similarity on the device: the embeddings of HF's WavLMForXVector in eval mode with no attention
+// mask (microsoft/wavlm-base-plus-sv: group-norm feature extractor, post-layer-norm encoder, head_dim 64, gated relative-position
+// bias, TDNN / statistics-pooling head).  fp32 throughout, channels-last [B][T][C].  C ABI dex_wavlm_*.  Row b of a batch is the
+// network applied to row b alone at its own length.
+//
+//   wavlm_conv0_kernel     the first convolution (Cin = 1), raw: 8 frames x all channels per workgroup, the sample window in LDS.
+//   wavlm_gn_part_kernel,  GroupNorm(C, C) of layer 0: per (row, channel) over the row's OWN frames, two passes - the sums of 512-frame
+//   wavlm_gn_final_kernel, chunks in fp64, added in chunk order, first of x (mean), then of (x - mean)^2 (biased variance): a DC offset
+//   wavlm_gn_apply_kernel  cancels nothing; then (x - mean) * rstd * gamma + beta -> GELU in place, 0 at or past the row's frames.
+//   launch_igemm           (igemm.hip, exact-fp32 MFMA) the convolutions of layers 1 .. (GELU in the epilogue), the feature projection,
+//                          the grouped positional convolution, q|k|v, out_proj, fc1, fc2 (k-split as in asr.hip), the projector, the
+//                          TDNN layers (a dilated unpadded 1 x k convolution with ReLU) and the embedding Linear.  Groups of the
+//                          positional convolution that are no multiple of 32 channels wide (768 / 16 = 48) are padded to 64.
+//   wavlm_gate_kernel      gate[b][h][t] = a (b const[h] - 1) + 2 with (a, b) = sigmoid of the two grouped sums of
+//                          gru_rel_pos_linear(x[t][64 h .. 64 h + 64]) - the layer INPUT, one thread per (frame, head).
+//   wavlm_rel_kernel       rel[h][d + N - 1] = rel_attn_embed[bucket(d)][h], d = -(N - 1) .. N - 1, once per call from the bucket table
+//                          the host computed at finalize.
+//   wavlm_attn_kernel      softmax((q / 8) k^T + gate[b][h][i] rel[h][j - i]) v on v_mfma_f32_32x32x2_f32 in the transposed flash
+//                          formulation of attention.hip's generic kernel; the bias is formed in registers from the two tables - no
+//                          [B H][N][N] tensor exists.
+//   asr_ln_kernel          (wav_encoder.h) every LayerNorm; the post-norm order h = LN(h + attn(h)); h = LN(h + ffn(h)).
+//   wavlm_mix_kernel       the softmax(layer_weights)-weighted sum of the hidden states, accumulated as the layers finish (one buffer).
+//   wavlm_pool_kernel      statistics pooling: mean and unbiased deviation per channel over the row's own TDNN frames, two passes in
+//                          fp64; a channel that is 0 on every frame has deviation exactly 0.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/dex_amd.h"
+#include "kernels.h"
+#include "wav_encoder.h"
+#include "weight_store.h"
+
+using namespace dex::wavenc;
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+static_assert(MAXC == DEX_WAVLM_MAX_CONV, "ConvSpec holds DEX_WAVLM_MAX_CONV layers");
+constexpr int MAXT = DEX_WAVLM_MAX_TDNN;
+constexpr int MAXF = DEX_WAVLM_MAX_FRAMES;
+constexpr int F0 = 8;                    // frames per workgroup of the first convolution
+constexpr int K0_MAX = 16, S0_MAX = 16;  // its kernel and stride bounds (taps in registers, window in LDS)
+constexpr int C0_MAX = 512;              // its channels: two per thread
+constexpr int MAX_B = 1024;
+constexpr long MAX_ROWS = 1L << 26;      // B x frames of the first layer
+constexpr int GN_CHUNK = 512;            // frames per partial sum of the group norm
+
+struct Conv0P { const float* x; long x_ld; const float* w; const float* bias; float* out; int T0, C, k, s; };
+
+// frames [F0 blockIdx.x, + F0) of utterance blockIdx.y: out[b][t][c] = bias[c] + sum_j w[c][j] x[b][t s + j] (taps ascending, fmaf)
+__global__ __launch_bounds__(256) void wavlm_conv0_kernel(const Conv0P p) {
+    __shared__ float xs[(F0 - 1) * S0_MAX + K0_MAX];
+    const int tid = threadIdx.x, b = blockIdx.y, t0 = blockIdx.x * F0;
+    const int nwin = (F0 - 1) * p.s + p.k;
+    const float* x = p.x + (long)b * p.x_ld;
+    for (int i = tid; i < nwin; i += 256) {
+        const long idx = (long)t0 * p.s + i;
+        xs[i] = idx < p.x_ld ? x[idx] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ci = 0; ci < 2; ++ci) {
+        const int c = tid + 256 * ci;
+        if (c >= p.C) continue;
+        float w[K0_MAX];
+#pragma unroll
+        for (int j = 0; j < K0_MAX; ++j) w[j] = j < p.k ? p.w[(long)c * p.k + j] : 0.f;
+        const float bs = p.bias ? p.bias[c] : 0.f;
+#pragma unroll
+        for (int f = 0; f < F0; ++f) {
+            float v = bs;
+#pragma unroll
+            for (int j = 0; j < K0_MAX; ++j)
+                if (j < p.k) v = fmaf(w[j], xs[f * p.s + j], v);
+            if (t0 + f < p.T0) p.out[((long)b * p.T0 + t0 + f) * p.C + c] = v;
+        }
+    }
+}
+
+// part[b][chunk][c] = sum over the chunk's frames below len0[b] of x (SQ: of (x - mean[b][c])^2), fp64; 64 channels x 4 frame lanes
+// per workgroup, the four lanes added in a fixed order.  grid (chunks, ceil(C / 64), B)
+template <bool SQ>
+__global__ __launch_bounds__(256) void wavlm_gn_part_kernel(const float* X, int T0, int C, const int* len0, const double* mean, double* part) {
+    __shared__ double red[4][64];
+    const int cl = threadIdx.x & 63, ts = threadIdx.x >> 6;
+    const int c = blockIdx.y * 64 + cl, b = blockIdx.z, ch = blockIdx.x;
+    const int L = min(len0[b], T0);
+    const int tbeg = ch * GN_CHUNK, tend = min(tbeg + GN_CHUNK, L);
+    double s = 0.0;
+    if (c < C) {
+        const double m = SQ ? mean[(long)b * C + c] : 0.0;
+        const float* x = X + (long)b * T0 * C + c;
+        for (int t = tbeg + ts; t < tend; t += 4) {
+            const double v = (double)x[(long)t * C] - m;
+            s = SQ ? fma(v, v, s) : s + v;
+        }
+    }
+    red[ts][cl] = s;
+    __syncthreads();
+    if (ts == 0 && c < C) part[((long)b * gridDim.x + ch) * C + c] = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
+}
+
+// the chunks of a row in order: mean[b][c] = sum / L (SQ: rstd[b][c] = 1 / sqrt(sum / L + eps))
+template <bool SQ>
+__global__ __launch_bounds__(256) void wavlm_gn_final_kernel(const double* part, int nchunk, int T0, int C, const int* len0, double* mean, float* rstd,
+                                                            float eps) {
+    const int c = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    if (c >= C) return;
+    const int L = min(len0[b], T0), nc = (L + GN_CHUNK - 1) / GN_CHUNK;
+    double s = 0.0;
+    for (int ch = 0; ch < nc; ++ch) s += part[((long)b * nchunk + ch) * C + c];
+    if (SQ) rstd[(long)b * C + c] = (float)(1.0 / sqrt(s / (double)L + (double)eps));
+    else mean[(long)b * C + c] = s / (double)L;
+}
+
+// X [B][T0][C] in place: GELU((x - mean) rstd gamma + beta), the difference in fp64; 0 at or past len0[b]
+__global__ __launch_bounds__(256) void wavlm_gn_apply_kernel(float* X, int T0, int C, const int* len0, const double* mean, const float* rstd,
+                                                            const float* gamma, const float* beta, long n4) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    const long e = i * 4, row = e / C;
+    const int c = (int)(e - row * C);
+    const int b = (int)(row / T0), t = (int)(row - (long)b * T0);
+    float4* x4 = reinterpret_cast<float4*>(X) + i;
+    if (t >= len0[b]) { *x4 = make_float4(0.f, 0.f, 0.f, 0.f); return; }
+    const float4 v = *x4;
+    const float xv[4] = {v.x, v.y, v.z, v.w};
+    float r[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const long sc = (long)b * C + c + u;
+        const float d = (float)((double)xv[u] - mean[sc]);
+        r[u] = gelu_erf_(d * rstd[sc] * gamma[c + u] + beta[c + u]);
+    }
+    *x4 = make_float4(r[0], r[1], r[2], r[3]);
+}
+
+// h[row][g cg + c] = y[row][g cg + c] + pp[row][g cgp + c]: the padded groups of the positional convolution back onto the residual
+__global__ __launch_bounds__(256) void wavlm_unpad_add_kernel(const float* y, const float* pp, float* h, long rows, int G, int cg, int cgp) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const int H = G * cg;
+    if (i >= rows * H) return;
+    const long row = i / H;
+    const int ch = (int)(i - row * H), g = ch / cg, c = ch - g * cg;
+    h[i] = y[i] + pp[(row * G + g) * cgp + c];
+}
+
+// one thread per (frame, head): gw [8][64], gb [8], gc [heads] -> gate [B][heads][T]
+__global__ __launch_bounds__(256) void wavlm_gate_kernel(const float* X, const float* gw, const float* gb, const float* gc, float* gate, int B, int T,
+                                                        int heads) {
+    __shared__ float w[8 * 64 + 8];
+    for (int i = threadIdx.x; i < 8 * 64 + 8; i += 256) w[i] = i < 512 ? gw[i] : gb[i - 512];
+    __syncthreads();
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)B * T * heads) return;
+    const int hd = (int)(idx % heads);
+    const long row = idx / heads;
+    const int b = (int)(row / T), t = (int)(row - (long)b * T);
+    const float4* x = reinterpret_cast<const float4*>(X + row * heads * 64 + hd * 64);
+    float acc[8];
+#pragma unroll
+    for (int o = 0; o < 8; ++o) acc[o] = w[512 + o];
+#pragma unroll
+    for (int k4 = 0; k4 < 16; ++k4) {
+        const float4 v = x[k4];
+#pragma unroll
+        for (int o = 0; o < 8; ++o) {
+            const float* wo = w + o * 64 + k4 * 4;
+            acc[o] = fmaf(v.w, wo[3], fmaf(v.z, wo[2], fmaf(v.y, wo[1], fmaf(v.x, wo[0], acc[o]))));
+        }
+    }
+    const float ga = 1.f / (1.f + expf(-((acc[0] + acc[1]) + (acc[2] + acc[3]))));
+    const float gbv = 1.f / (1.f + expf(-((acc[4] + acc[5]) + (acc[6] + acc[7]))));
+    gate[((long)b * heads + hd) * T + t] = ga * (gbv * gc[hd] - 1.f) + 2.f;
+}
+
+// rel [heads][2 N - 1]: entry d + N - 1 = embed[bucket(d)][h]; buckets holds d = -(MAXF - 1) .. MAXF - 1
+__global__ __launch_bounds__(256) void wavlm_rel_kernel(const float* embed, const int* buckets, float* rel, int N, int heads) {
+    const int j = blockIdx.x * 256 + threadIdx.x, h = blockIdx.y;
+    if (j >= 2 * N - 1) return;
+    rel[(long)h * (2 * N - 1) + j] = embed[(long)buckets[j - (N - 1) + (MAXF - 1)] * heads + h];
+}
+
+// ---- attention with the gated relative-position bias.  The transposed flash formulation of attention.hip's generic kernel at
+// head_dim 64: S^T = K Q^T (A = the K^T tile in wave-private LDS, B = the pre-scaled Q tile), O^T = V^T P^T with P^T the S^T
+// accumulator registers themselves.  C-layout of a 32 x 32 tile: col = lane & 31 (query), row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+// (key) - so a lane's 16 scores belong to ONE query: its gate is one register, and rel is read at 16 distances key - query.
+constexpr int AT_NW = 4;                   // waves per workgroup: wave w takes key tiles w, w + 4, ...
+constexpr int AT_KT_LD = 33;               // K^T tile [64 d][32 keys + 1]
+constexpr int AT_V_LD = 64 + 8;            // V tile [32 keys][64 d + 8]; also the merged O tile [32 queries][64 d + 8]
+constexpr int AT_WAVE_LDS = 32 * AT_V_LD;  // 2304 floats >= 64 * 33
+constexpr int AT_Q_LD = 65;
+struct AttnBiasP { const float* qkv; int ld; long bstride; float* O; int ldo; long ob; int N; const int* kv_len; int heads;
+                   const float* rel; const float* gate; };
+
+__global__ __launch_bounds__(AT_NW * 64) void wavlm_attn_kernel(const AttnBiasP p) {
+    __shared__ __attribute__((aligned(16))) float smem[AT_NW * AT_WAVE_LDS + AT_NW * 64 + 32 * AT_Q_LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i = lane & 31, hh = lane >> 5;
+    const int q0 = blockIdx.x * 32, h = blockIdx.y, b = blockIdx.z;
+    float* wt = smem + wave * AT_WAVE_LDS;                  // wave-private tile
+    float* stat = smem + AT_NW * AT_WAVE_LDS;               // [NW][2][32]
+    float* qS = stat + AT_NW * 64;                          // [32 queries][AT_Q_LD] pre-scaled Q
+    const int Nk = max(1, min(p.N, p.kv_len[b]));
+    const int H = p.heads * 64;
+    const float* Qb = p.qkv + (long)b * p.bstride + h * 64;
+    const float* Kb = Qb + H;
+    const float* Vb = Qb + 2 * H;
+    for (int it = tid; it < 32 * 16; it += AT_NW * 64) {
+        const int qi = it >> 4, d4 = (it & 15) * 4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (q0 + qi < p.N) v = *reinterpret_cast<const float4*>(Qb + (long)(q0 + qi) * p.ld + d4);
+        float* d = qS + qi * AT_Q_LD + d4;
+        d[0] = v.x * 0.125f; d[1] = v.y * 0.125f; d[2] = v.z * 0.125f; d[3] = v.w * 0.125f;
+    }
+    // this lane's query (clamped at the tail of the last tile: its result is not stored), its gate and its row of the distance table
+    const int qi = min(q0 + i, p.N - 1);
+    const float gq = p.gate[((long)b * p.heads + h) * p.N + qi];
+    const float* relq = p.rel + (long)h * (2 * p.N - 1) + (p.N - 1) - qi;      // relq[key], key in [0, N): index in [0, 2 N - 2]
+    f32x16 o[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;
+    const int ntiles = (Nk + 31) / 32;
+    __syncthreads();
+    for (int kt = wave; kt < ntiles; kt += AT_NW) {
+        const int k0 = kt * 32;
+        float rb[16];                                       // the 16 table entries, in flight under the S^T MFMAs
+#pragma unroll
+        for (int r = 0; r < 16; ++r) rb[r] = relq[min(k0 + (r & 3) + 8 * (r >> 2) + 4 * hh, Nk - 1)];
+        f32x16 sT;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sT[r] = 0.f;
+        // K tile [32 keys][64 d] -> K^T[d][key] (16 lanes per key row)
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int it = 0; it < 8; ++it) {
+            const int key = it * 4 + (lane >> 4), dd = (lane & 15) * 4;
+            const float4 v = *reinterpret_cast<const float4*>(Kb + (long)min(k0 + key, Nk - 1) * p.ld + dd);
+            float* d = wt + dd * AT_KT_LD + key;
+            d[0] = v.x; d[AT_KT_LD] = v.y; d[2 * AT_KT_LD] = v.z; d[3 * AT_KT_LD] = v.w;
+        }
+        __builtin_amdgcn_s_waitcnt(0xc07f);                 // lgkmcnt(0): this wave's LDS writes landed (wave-private tile)
+        __builtin_amdgcn_wave_barrier();
+        {
+            const float* ka = wt + (hh * 32) * AT_KT_LD + i;
+            const float* qa = qS + i * AT_Q_LD + hh * 32;
+#pragma unroll
+            for (int kk = 0; kk < 32; ++kk) sT = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[kk * AT_KT_LD], qa[kk], sT, 0, 0, 0);
+        }
+        float mx = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+            sT[r] = key >= Nk ? -INFINITY : fmaf(gq, rb[r], sT[r]);
+            mx = fmaxf(mx, sT[r]);
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        if (__builtin_amdgcn_ballot_w64(mx > m_run + 8.f) != 0) {         // lazy rescale, as in attention.hip
+            const float m_new = fmaxf(m_run, mx);
+            const float alpha = __expf(m_run - m_new);
+            l_run *= alpha;
+            m_run = m_new;
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) o[t][r] *= alpha;
+        }
+        float psum = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { sT[r] = __expf(sT[r] - m_run); psum += sT[r]; }
+        l_run += psum;
+        // V tile [32 keys][64 d] over the K^T image
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int it = 0; it < 8; ++it) {
+            const int key = it * 4 + (lane >> 4), dd = (lane & 15) * 4;
+            *reinterpret_cast<float4*>(wt + key * AT_V_LD + dd) = *reinterpret_cast<const float4*>(Vb + (long)min(k0 + key, Nk - 1) * p.ld + dd);
+        }
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            const float* vp = wt + ((s & 3) + 8 * (s >> 2) + 4 * hh) * AT_V_LD + i;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) o[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[t * 32], sT[s], o[t], 0, 0, 0);
+        }
+    }
+    l_run += __shfl_xor(l_run, 32);
+    if (hh == 0) { stat[(wave * 2 + 0) * 32 + i] = m_run; stat[(wave * 2 + 1) * 32 + i] = l_run; }
+    __syncthreads();                                        // every wave done with its tile
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int rq = 0; rq < 4; ++rq)
+            *reinterpret_cast<float4*>(wt + i * AT_V_LD + t * 32 + 8 * rq + 4 * hh) =
+                make_float4(o[t][rq * 4 + 0], o[t][rq * 4 + 1], o[t][rq * 4 + 2], o[t][rq * 4 + 3]);
+    __syncthreads();
+    const int d4 = (tid & 15) * 4;
+    for (int q = tid >> 4; q < 32; q += AT_NW * 4) {
+        if (q0 + q >= p.N) continue;
+        float M = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < AT_NW; ++w) M = fmaxf(M, stat[(w * 2) * 32 + q]);
+        float L = 0.f;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int w = 0; w < AT_NW; ++w) {
+            const float mw = stat[(w * 2) * 32 + q];
+            const float f = (mw == -INFINITY) ? 0.f : __expf(mw - M);
+            L += f * stat[(w * 2 + 1) * 32 + q];
+            const float4 v = *reinterpret_cast<const float4*>(smem + w * AT_WAVE_LDS + q * AT_V_LD + d4);
+            acc.x = fmaf(f, v.x, acc.x); acc.y = fmaf(f, v.y, acc.y); acc.z = fmaf(f, v.z, acc.z); acc.w = fmaf(f, v.w, acc.w);
+        }
+        const float inv = 1.f / L;
+        float* op = p.O + (long)b * p.ob + (long)(q0 + q) * p.ldo + h * 64 + d4;
+        *reinterpret_cast<float4*>(op) = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
+    }
+}
+
+// dst = (first ? 0 : acc) + lw[l] h (lw null: weight 1); mask given (the last step): rows whose mask is 0 are stored as 0.  dst may be acc.
+__global__ __launch_bounds__(256) void wavlm_mix_kernel(const float4* h, const float4* acc, float4* dst, const float* lw, int l, int first,
+                                                       const float* mask, long n4, int H4) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    const float w = lw ? lw[l] : 1.f;
+    const float4 v = h[i];
+    float4 a = first ? make_float4(0.f, 0.f, 0.f, 0.f) : acc[i];
+    a.x += w * v.x; a.y += w * v.y; a.z += w * v.z; a.w += w * v.w;
+    if (mask && mask[i / H4] == 0.f) a = make_float4(0.f, 0.f, 0.f, 0.f);
+    dst[i] = a;
+}
+
+// lw = softmax(w [n]) in fp64, one thread
+__global__ void wavlm_softmax_kernel(const float* w, float* lw, int n) {
+    if (threadIdx.x || blockIdx.x) return;
+    double m = w[0], s = 0.0;
+    for (int i = 1; i < n; ++i) m = fmax(m, (double)w[i]);
+    for (int i = 0; i < n; ++i) s += exp((double)w[i] - m);
+    for (int i = 0; i < n; ++i) lw[i] = (float)(exp((double)w[i] - m) / s);
+}
+
+constexpr int POOL_TL = 16;              // frame lanes of the pooling workgroup (x 64 channels)
+
+// X [B][Tt][C] -> out [B][2 C]: mean | unbiased deviation per channel over the first len[b] - shrink frames (>= 2), two passes in fp64,
+// the 16 frame lanes added in order.  grid (ceil(C / 64), B)
+__global__ __launch_bounds__(POOL_TL * 64) void wavlm_pool_kernel(const float* X, int Tt, int C, const int* len, int shrink, float* out) {
+    __shared__ double red[POOL_TL][64];
+    const int cl = threadIdx.x & 63, ts = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + cl, b = blockIdx.y;
+    const int n = min(len[b] - shrink, Tt);
+    const float* x = X + (long)b * Tt * C + min(c, C - 1);
+    double s = 0.0;
+    for (int t = ts; t < n; t += POOL_TL) s += (double)x[(long)t * C];
+    red[ts][cl] = s;
+    __syncthreads();
+    double tot = 0.0;
+    for (int u = 0; u < POOL_TL; ++u) tot += red[u][cl];
+    const double mean = tot / (double)n;
+    __syncthreads();
+    double q = 0.0;
+    for (int t = ts; t < n; t += POOL_TL) { const double d = (double)x[(long)t * C] - mean; q = fma(d, d, q); }
+    red[ts][cl] = q;
+    __syncthreads();
+    if (ts == 0 && c < C) {
+        double qt = 0.0;
+        for (int u = 0; u < POOL_TL; ++u) qt += red[u][cl];
+        out[(long)b * 2 * C + c] = (float)mean;
+        out[(long)b * 2 * C + C + c] = (float)sqrt(qt / (double)(n - 1));
+    }
+}
+
+// Linear weight src [N][nseg seg] -> the GEMM operand dst [nseg segpad][Npad] (row = s segpad + c), zeros in the padding
+__global__ __launch_bounds__(256) void wavlm_pack_pad_kernel(const float* src, float* dst, int N, int Npad, int seg, int segpad, int nseg) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)nseg * segpad * Npad) return;
+    const int n = (int)(idx % Npad);
+    const long kd = idx / Npad;
+    const int sg = (int)(kd / segpad), c = (int)(kd - (long)sg * segpad);
+    dst[idx] = (n < N && c < seg) ? src[(long)n * nseg * seg + (long)sg * seg + c] : 0.f;
+}
+
+// positional convolution v [G cg][cg][k] times scale[tap] (fp64) -> per group [k cgp][cgp] (row = tap cgp + ci), zeros in the padding
+__global__ __launch_bounds__(256) void wavlm_pack_pos_kernel(const float* v, const double* scale, float* dst, int G, int cg, int cgp, int k) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)G * k * cgp * cgp) return;
+    const int co = (int)(idx % cgp);
+    long r = idx / cgp;
+    const int ci = (int)(r % cgp); r /= cgp;
+    const int tap = (int)(r % k), g = (int)(r / k);
+    dst[idx] = (co < cg && ci < cg) ? (float)((double)v[((long)(g * cg + co) * cg + ci) * k + tap] * scale[tap]) : 0.f;
+}
+
+// dst [G cgp] = src [G cg] with zeros in the padding
+__global__ __launch_bounds__(256) void wavlm_pad_vec_kernel(const float* src, float* dst, int G, int cg, int cgp) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= G * cgp) return;
+    const int g = i / cgp, c = i - g * cgp;
+    dst[i] = c < cg ? src[g * cg + c] : 0.f;
+}
+
+thread_local std::string g_create_err;
+
+int create_fail(const char* fmt, const char* field) {
+    char buf[256];
+    snprintf(buf, sizeof buf, fmt, field);
+    g_create_err = buf;
+    return DEX_ERR_ARG;
+}
+
+DexWavlmConfig default_config() {
+    DexWavlmConfig c;
+    std::memset(&c, 0, sizeof c);
+    const int k[7] = {10, 3, 3, 3, 3, 2, 2}, s[7] = {5, 2, 2, 2, 2, 2, 2};
+    c.n_conv = 7;
+    for (int i = 0; i < 7; ++i) { c.conv_dim[i] = 512; c.conv_kernel[i] = k[i]; c.conv_stride[i] = s[i]; }
+    c.conv_bias = 0; c.feat_extract_norm_group = 1;
+    c.hidden = 768; c.n_layers = 12; c.n_heads = 12; c.intermediate = 3072; c.do_stable_layer_norm = 0;
+    c.num_conv_pos_embeddings = 128; c.num_conv_pos_embedding_groups = 16; c.layer_norm_eps = 1e-5f;
+    c.num_buckets = 320; c.max_bucket_distance = 800; c.use_weighted_layer_sum = 1;
+    const int td[5] = {512, 512, 512, 512, 1500}, tk[5] = {5, 3, 3, 1, 1}, tl[5] = {1, 2, 3, 1, 1};
+    c.n_tdnn = 5;
+    for (int i = 0; i < 5; ++i) { c.tdnn_dim[i] = td[i]; c.tdnn_kernel[i] = tk[i]; c.tdnn_dilation[i] = tl[i]; }
+    c.xvector_output_dim = 512;
+    return c;
+}
+
+// the family that is built; names the first field outside it
+int check_config(const DexWavlmConfig& c) {
+    if (c.feat_extract_norm_group != 1) return create_fail("%s: only 'group' is built", "feat_extract_norm");
+    if (c.do_stable_layer_norm != 0) return create_fail("%s: only False is built", "do_stable_layer_norm");
+    if (c.n_conv < 1 || c.n_conv > MAXC) return create_fail("%s: 1 .. 8 feature-extractor layers", "conv_dim");
+    for (int l = 0; l < c.n_conv; ++l) {
+        if (c.conv_dim[l] < 32 || c.conv_dim[l] % 32 || c.conv_dim[l] > 4096) return create_fail("%s: every width a multiple of 32 in 32 .. 4096", "conv_dim");
+        if (c.conv_kernel[l] < 1 || c.conv_kernel[l] > 64) return create_fail("%s: 1 .. 64", "conv_kernel");
+        if (c.conv_stride[l] < 1 || c.conv_stride[l] > 64) return create_fail("%s: 1 .. 64", "conv_stride");
+    }
+    if (c.conv_dim[0] > C0_MAX) return create_fail("%s: the first layer has at most 512 channels", "conv_dim");
+    if (c.conv_kernel[0] > K0_MAX) return create_fail("%s: the first layer's kernel is at most 16", "conv_kernel");
+    if (c.conv_stride[0] > S0_MAX) return create_fail("%s: the first layer's stride is at most 16", "conv_stride");
+    if (c.n_heads < 1 || c.n_heads > 1024) return create_fail("%s: 1 .. 1024", "num_attention_heads");
+    if (c.hidden < 64 || c.hidden > 16384 || c.hidden != 64 * c.n_heads) return create_fail("%s: hidden_size / num_attention_heads must be 64", "hidden_size");
+    if (c.n_layers < 1 || c.n_layers > 256) return create_fail("%s: 1 .. 256", "num_hidden_layers");
+    if (c.intermediate < 32 || c.intermediate % 32 || c.intermediate > 65536) return create_fail("%s: a multiple of 32 up to 65536", "intermediate_size");
+    const int G = c.num_conv_pos_embedding_groups, K = c.num_conv_pos_embeddings;
+    if (G < 1 || G > 16 || c.hidden % G || (c.hidden / G) % 4) return create_fail("%s: 1 .. 16 groups of a multiple of 4 channels", "num_conv_pos_embedding_groups");
+    if (K < 2 || K % 2 || K > 1024) return create_fail("%s: even, 2 .. 1024", "num_conv_pos_embeddings");
+    if (!(c.layer_norm_eps > 0.f) || !(c.layer_norm_eps < 1.f)) return create_fail("%s: in (0, 1)", "layer_norm_eps");
+    if (c.num_buckets < 4 || c.num_buckets % 4 || c.num_buckets > 65536) return create_fail("%s: a multiple of 4 in 4 .. 65536", "num_buckets");
+    if (c.max_bucket_distance <= c.num_buckets / 4 || c.max_bucket_distance > (1 << 24)) return create_fail("%s: above num_buckets / 4", "max_bucket_distance");
+    if (c.n_tdnn < 1 || c.n_tdnn > MAXT) return create_fail("%s: 1 .. 8 TDNN layers", "tdnn_dim");
+    for (int i = 0; i < c.n_tdnn; ++i) {
+        if (c.tdnn_dim[i] < 1 || c.tdnn_dim[i] > 8192 || (i + 1 < c.n_tdnn && c.tdnn_dim[i] % 32))
+            return create_fail("%s: every width but the last a multiple of 32, all in 1 .. 8192", "tdnn_dim");
+        if (c.tdnn_kernel[i] < 1 || c.tdnn_kernel[i] > 16) return create_fail("%s: 1 .. 16", "tdnn_kernel");
+        if (c.tdnn_dilation[i] < 1 || c.tdnn_dilation[i] > 16) return create_fail("%s: 1 .. 16", "tdnn_dilation");
+    }
+    if (c.xvector_output_dim < 32 || c.xvector_output_dim % 32 || c.xvector_output_dim > 8192) return create_fail("%s: a multiple of 32 up to 8192", "xvector_output_dim");
+    return DEX_OK;
+}
+
+// the geometry alone (the host-only entry points take configs that were never created)
+bool geometry_ok(const DexWavlmConfig& c) {
+    if (c.n_conv < 1 || c.n_conv > MAXC || c.n_tdnn < 1 || c.n_tdnn > MAXT) return false;
+    for (int l = 0; l < c.n_conv; ++l)
+        if (c.conv_kernel[l] < 1 || c.conv_stride[l] < 1) return false;
+    for (int i = 0; i < c.n_tdnn; ++i)
+        if (c.tdnn_kernel[i] < 1 || c.tdnn_dilation[i] < 1) return false;
+    return true;
+}
+
+int fc2_ksplit(const DexWavlmConfig& c) {
+    const int r = c.intermediate / c.hidden;
+    return (r * c.hidden == c.intermediate && (r == 2 || r == 4 || r == 8) && (c.intermediate / r) % 32 == 0) ? r : 1;
+}
+
+int frames_of(const DexWavlmConfig& c, long n, int upto) {
+    for (int l = 0; l < upto; ++l) n = n >= c.conv_kernel[l] ? (n - c.conv_kernel[l]) / c.conv_stride[l] + 1 : 0;
+    return (int)n;
+}
+// frames the TDNN layers take off a row
+int tdnn_shrink(const DexWavlmConfig& c) {
+    int s = 0;
+    for (int i = 0; i < c.n_tdnn; ++i) s += (c.tdnn_kernel[i] - 1) * c.tdnn_dilation[i];
+    return s;
+}
+long min_samples(const DexWavlmConfig& c) {
+    long n = tdnn_shrink(c) + 2;                            // two frames after the TDNN layers: the unbiased deviation exists
+    for (int l = c.n_conv - 1; l >= 0; --l) n = (n - 1) * c.conv_stride[l] + c.conv_kernel[l];
+    return n;
+}
+// _relative_positions_bucket of the distance d = key - query, in fp64
+int bucket_of(const DexWavlmConfig& c, long d) {
+    const int nb = c.num_buckets / 2, max_exact = nb / 2;
+    const int side = d > 0 ? nb : 0;
+    const long a = d < 0 ? -d : d;
+    if (a < max_exact) return side + (int)a;
+    const double v = std::log((double)a / max_exact) / std::log((double)c.max_bucket_distance / max_exact) * (nb - max_exact);
+    const long big = max_exact + (long)v;
+    return side + (int)(big < nb - 1 ? big : nb - 1);
+}
+int pad32(int n) { return (n + 31) & ~31; }
+// channels of a positional-convolution group as the GEMM takes them
+int pos_group_pad(const DexWavlmConfig& c) { const int cg = c.hidden / c.num_conv_pos_embedding_groups; return cg % 32 ? (cg + 63) & ~63 : cg; }
+
+}  // namespace
+
+struct DexWavlm : dex::WeightStore {
+    DexWavlm() : WeightStore("wavlm ") {}
+    DexWavlmConfig c;
+    const float* conv_w[MAXC] = {}; const float* conv_b[MAXC] = {};
+    const float *gn_g = nullptr, *gn_b = nullptr;
+    const float *fp_g = nullptr, *fp_be = nullptr, *fp_w = nullptr, *fp_b = nullptr, *pos_w = nullptr, *pos_b = nullptr;
+    const float *enc_g = nullptr, *enc_be = nullptr, *rel_embed = nullptr, *lw = nullptr;
+    const int* buckets = nullptr;
+    std::vector<int32_t> buckets_host;
+    struct Layer { const float *gw, *gb, *gc, *wqkv, *bqkv, *wo, *bo, *ln1g, *ln1b, *w1, *b1, *w2, *b2, *ln2g, *ln2b; };
+    std::vector<Layer> layers;
+    const float *proj_w = nullptr, *proj_b = nullptr, *emb_w = nullptr, *emb_b = nullptr;
+    const float* tdnn_w[MAXT] = {}; const float* tdnn_b[MAXT] = {};
+};
+
+namespace {
+
+const std::string FE = "wavlm.feature_extractor.conv_layers.", ENC = "wavlm.encoder.", FP = "wavlm.feature_projection.";
+std::string lk(int l, const char* what) { return ENC + "layers." + std::to_string(l) + "." + what; }
+std::string ck(int l, const char* what) { return FE + std::to_string(l) + "." + what; }
+std::string tk(int i, const char* what) { return "tdnn." + std::to_string(i) + ".kernel." + what; }
+
+void register_keys(DexWavlm* s) {
+    const DexWavlmConfig& c = s->c;
+    for (int l = 0; l < c.n_conv; ++l) {
+        s->add(ck(l, "conv.weight"), {c.conv_dim[l], l ? c.conv_dim[l - 1] : 1, c.conv_kernel[l]});
+        if (c.conv_bias) s->add(ck(l, "conv.bias"), {c.conv_dim[l]});
+        if (l == 0) { s->add(ck(0, "layer_norm.weight"), {c.conv_dim[0]}); s->add(ck(0, "layer_norm.bias"), {c.conv_dim[0]}); }
+    }
+    const int C = c.conv_dim[c.n_conv - 1], H = c.hidden, I = c.intermediate;
+    s->add(FP + "layer_norm.weight", {C}); s->add(FP + "layer_norm.bias", {C});
+    s->add(FP + "projection.weight", {H, C}); s->add(FP + "projection.bias", {H});
+    s->add(ENC + "pos_conv_embed.conv.bias", {H});
+    s->add(ENC + "pos_conv_embed.conv.weight_g", {1, 1, c.num_conv_pos_embeddings});
+    s->add(ENC + "pos_conv_embed.conv.weight_v", {H, H / c.num_conv_pos_embedding_groups, c.num_conv_pos_embeddings});
+    s->add(ENC + "layer_norm.weight", {H}); s->add(ENC + "layer_norm.bias", {H});
+    for (int l = 0; l < c.n_layers; ++l) {
+        for (const char* pr : {"attention.q_proj", "attention.k_proj", "attention.v_proj", "attention.out_proj"}) {
+            s->add(lk(l, pr) + ".weight", {H, H}); s->add(lk(l, pr) + ".bias", {H});
+        }
+        s->add(lk(l, "attention.gru_rel_pos_const"), {1, c.n_heads, 1, 1});
+        s->add(lk(l, "attention.gru_rel_pos_linear.weight"), {8, 64}); s->add(lk(l, "attention.gru_rel_pos_linear.bias"), {8});
+        if (l == 0) s->add(lk(0, "attention.rel_attn_embed.weight"), {c.num_buckets, c.n_heads});
+        s->add(lk(l, "layer_norm.weight"), {H}); s->add(lk(l, "layer_norm.bias"), {H});
+        s->add(lk(l, "feed_forward.intermediate_dense.weight"), {I, H}); s->add(lk(l, "feed_forward.intermediate_dense.bias"), {I});
+        s->add(lk(l, "feed_forward.output_dense.weight"), {H, I}); s->add(lk(l, "feed_forward.output_dense.bias"), {H});
+        s->add(lk(l, "final_layer_norm.weight"), {H}); s->add(lk(l, "final_layer_norm.bias"), {H});
+    }
+    if (c.use_weighted_layer_sum) s->add("layer_weights", {c.n_layers + 1});
+    s->add("projector.weight", {c.tdnn_dim[0], H}); s->add("projector.bias", {c.tdnn_dim[0]});
+    for (int i = 0; i < c.n_tdnn; ++i) {
+        const int din = c.tdnn_dim[i ? i - 1 : 0];
+        s->add(tk(i, "weight"), {c.tdnn_dim[i], din * c.tdnn_kernel[i]}); s->add(tk(i, "bias"), {c.tdnn_dim[i]});
+    }
+    s->add("feature_extractor.weight", {c.xvector_output_dim, 2 * c.tdnn_dim[c.n_tdnn - 1]}); s->add("feature_extractor.bias", {c.xvector_output_dim});
+}
+
+// Linear [N][nseg seg] -> operand [nseg segpad][Npad]
+const float* pack_pad(DexWavlm* s, const std::string& key, int N, int Npad, int seg, int segpad, int nseg, hipStream_t st) {
+    const long n = (long)nseg * segpad * Npad;
+    float* d = s->alloc(n);
+    if (d) hipLaunchKernelGGL(wavlm_pack_pad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s->R(key), d, N, Npad, seg, segpad, nseg);
+    return d;
+}
+const float* pad_vec(DexWavlm* s, const std::string& key, int G, int cg, int cgp, hipStream_t st) {
+    if (cg == cgp) return s->R(key);
+    float* d = s->alloc((long)G * cgp);
+    if (d) hipLaunchKernelGGL(wavlm_pad_vec_kernel, dim3((G * cgp + 255) / 256), dim3(256), 0, st, s->R(key), d, G, cg, cgp);
+    return d;
+}
+
+int finalize(DexWavlm* s, hipStream_t st) {
+    if (int rc = s->begin_finalize()) return rc;
+    const DexWavlmConfig& c = s->c;
+    const int H = c.hidden, I = c.intermediate, C = c.conv_dim[c.n_conv - 1];
+    for (int l = 0; l < c.n_conv; ++l) {
+        s->conv_w[l] = l ? pack(s, ck(l, "conv.weight"), 1, c.conv_dim[l], c.conv_dim[l - 1], c.conv_kernel[l], nullptr, st) : s->R(ck(0, "conv.weight"));
+        s->conv_b[l] = c.conv_bias ? s->R(ck(l, "conv.bias")) : nullptr;
+    }
+    s->gn_g = s->R(ck(0, "layer_norm.weight")); s->gn_b = s->R(ck(0, "layer_norm.bias"));
+    s->fp_g = s->R(FP + "layer_norm.weight"); s->fp_be = s->R(FP + "layer_norm.bias");
+    s->fp_w = pack(s, FP + "projection.weight", 1, H, C, 1, nullptr, st); s->fp_b = s->R(FP + "projection.bias");
+    {
+        const int G = c.num_conv_pos_embedding_groups, K = c.num_conv_pos_embeddings, cg = H / G, cgp = pos_group_pad(c);
+        double* scale = (double*)s->alloc(2L * K);
+        float* pw = s->alloc((long)G * K * cgp * cgp);
+        if (scale && pw) {
+            hipLaunchKernelGGL(asr_wn_scale_kernel, dim3(K), dim3(256), 0, st, s->R(ENC + "pos_conv_embed.conv.weight_v"),
+                               s->R(ENC + "pos_conv_embed.conv.weight_g"), scale, (long)H * cg, K);
+            const long n = (long)G * K * cgp * cgp;
+            hipLaunchKernelGGL(wavlm_pack_pos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s->R(ENC + "pos_conv_embed.conv.weight_v"), scale,
+                               pw, G, cg, cgp, K);
+        }
+        s->pos_w = pw;
+        s->pos_b = pad_vec(s, ENC + "pos_conv_embed.conv.bias", G, cg, cgp, st);
+    }
+    s->enc_g = s->R(ENC + "layer_norm.weight"); s->enc_be = s->R(ENC + "layer_norm.bias");
+    s->rel_embed = s->R(lk(0, "attention.rel_attn_embed.weight"));
+    s->layers.assign(c.n_layers, DexWavlm::Layer{});
+    for (int l = 0; l < c.n_layers && s->alloc_rc == DEX_OK; ++l) {
+        DexWavlm::Layer& L = s->layers[l];
+        float* wqkv = s->alloc(3L * H * H); float* bqkv = s->alloc(3L * H);
+        if (!wqkv || !bqkv) break;
+        const char* pr[3] = {"attention.q_proj", "attention.k_proj", "attention.v_proj"};
+        for (int j = 0; j < 3; ++j) {
+            pack_into(s->R(lk(l, pr[j]) + ".weight"), wqkv, 1, H, H, 1, 3 * H, j * H, nullptr, st);
+            DEX_HIPCHK(s, hipMemcpyAsync(bqkv + (long)j * H, s->R(lk(l, pr[j]) + ".bias"), H * sizeof(float), hipMemcpyDeviceToDevice, st));
+        }
+        L.wqkv = wqkv; L.bqkv = bqkv;
+        L.gw = s->R(lk(l, "attention.gru_rel_pos_linear.weight")); L.gb = s->R(lk(l, "attention.gru_rel_pos_linear.bias"));
+        L.gc = s->R(lk(l, "attention.gru_rel_pos_const"));
+        L.wo = pack(s, lk(l, "attention.out_proj") + ".weight", 1, H, H, 1, nullptr, st); L.bo = s->R(lk(l, "attention.out_proj") + ".bias");
+        L.ln1g = s->R(lk(l, "layer_norm.weight")); L.ln1b = s->R(lk(l, "layer_norm.bias"));
+        L.w1 = pack(s, lk(l, "feed_forward.intermediate_dense.weight"), 1, I, H, 1, nullptr, st); L.b1 = s->R(lk(l, "feed_forward.intermediate_dense.bias"));
+        L.w2 = pack(s, lk(l, "feed_forward.output_dense.weight"), 1, H, I, 1, nullptr, st); L.b2 = s->R(lk(l, "feed_forward.output_dense.bias"));
+        L.ln2g = s->R(lk(l, "final_layer_norm.weight")); L.ln2b = s->R(lk(l, "final_layer_norm.bias"));
+    }
+    if (c.use_weighted_layer_sum) {
+        float* lw = s->alloc(up64(c.n_layers + 1));
+        if (lw) hipLaunchKernelGGL(wavlm_softmax_kernel, dim3(1), dim3(64), 0, st, s->R("layer_weights"), lw, c.n_layers + 1);
+        s->lw = lw;
+    } else {
+        s->lw = nullptr;
+    }
+    {   // the bucket of every distance one call can meet, computed here on the host
+        s->buckets_host.resize(2 * MAXF - 1);
+        for (int d = -(MAXF - 1); d <= MAXF - 1; ++d) s->buckets_host[d + MAXF - 1] = bucket_of(c, d);
+        int* bk = (int*)s->alloc(up64(2 * MAXF - 1));
+        if (bk) DEX_HIPCHK(s, hipMemcpyAsync(bk, s->buckets_host.data(), (2 * MAXF - 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        s->buckets = bk;
+    }
+    s->proj_w = pack_pad(s, "projector.weight", c.tdnn_dim[0], c.tdnn_dim[0], H, H, 1, st); s->proj_b = s->R("projector.bias");
+    for (int i = 0; i < c.n_tdnn; ++i) {
+        const int din = c.tdnn_dim[i ? i - 1 : 0], K = din * c.tdnn_kernel[i], N = c.tdnn_dim[i], Np = pad32(N);
+        s->tdnn_w[i] = pack_pad(s, tk(i, "weight"), N, Np, K, K, 1, st);
+        s->tdnn_b[i] = pad_vec(s, tk(i, "bias"), 1, N, Np, st);
+    }
+    {
+        const int Cl = c.tdnn_dim[c.n_tdnn - 1];
+        s->emb_w = pack_pad(s, "feature_extractor.weight", c.xvector_output_dim, c.xvector_output_dim, Cl, pad32(Cl), 2, st);
+        s->emb_b = s->R("feature_extractor.bias");
+    }
+    if (s->alloc_rc != DEX_OK) return s->alloc_rc;
+    if (hipGetLastError() != hipSuccess) return s->fail(DEX_ERR_HIP, "packing the wavlm weights failed");
+    s->finalized = true;
+    return DEX_OK;
+}
+
+// workspace (floats, every piece a multiple of 64): xn [B][n] | fa (even layers) | fb (odd layers) | h, y, mix [B][T][H] | qkv [B][T][3H] |
+// ff [B][T][I] | part [ksplit][B][T][H] | yp, pp [B][T][G cgp] (padded positional groups) | gate [B][heads][T] | rel [heads][2T - 1] |
+// mask [B][T] | gnpart (fp64) [B][chunks][C_0] | gnmean (fp64) [B][C_0] | gnrstd [B][C_0] | ta, tb [B][T][max tdnn width] |
+// stats [B][2 Cpad] | lens (int) [n_conv + 1][B]
+struct Ws { float *xn, *fa, *fb, *h, *y, *mix, *qkv, *ff, *part, *yp, *pp, *gate, *rel, *mask, *gnrstd, *ta, *tb, *stats; double *gnpart, *gnmean;
+            int* lens; size_t bytes; int Tl[MAXC]; int T, nchunk; };
+Ws plan(const DexWavlmConfig& c, void* ws, long B, long n) {
+    Ws w{};
+    long fa = 0, fb = 0;
+    for (int l = 0; l < c.n_conv; ++l) {
+        w.Tl[l] = frames_of(c, n, l + 1);
+        long& m = (l & 1) ? fb : fa;
+        const long sz = (long)w.Tl[l] * c.conv_dim[l];
+        m = sz > m ? sz : m;
+    }
+    w.T = w.Tl[c.n_conv - 1];
+    w.nchunk = (w.Tl[0] + GN_CHUNK - 1) / GN_CHUNK;
+    const long T = w.T, H = c.hidden;
+    const long last = T * c.conv_dim[c.n_conv - 1];        // the LayerNorm of the feature projection writes the OTHER ping-pong buffer
+    fa = fa > last ? fa : last; fb = fb > last ? fb : last;
+    long tdw = 0;
+    for (int i = 0; i < c.n_tdnn; ++i) tdw = pad32(c.tdnn_dim[i]) > tdw ? pad32(c.tdnn_dim[i]) : tdw;
+    const long cgp = pos_group_pad(c), G = c.num_conv_pos_embedding_groups, padded = cgp * G != H;
+    float* f = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    long off = 0;
+    auto take = [&](long cnt) { float* p = f + off; off += up64(cnt); return p; };
+    w.xn = take(B * n); w.fa = take(B * fa); w.fb = take(B * fb);
+    w.h = take(B * T * H); w.y = take(B * T * H); w.mix = take(B * T * H); w.qkv = take(B * T * 3 * H); w.ff = take(B * T * c.intermediate);
+    w.part = take(fc2_ksplit(c) > 1 ? fc2_ksplit(c) * B * T * H : 0);
+    w.yp = take(padded ? B * T * G * cgp : 0); w.pp = take(padded ? B * T * G * cgp : 0);
+    w.gate = take(B * c.n_heads * T); w.rel = take((long)c.n_heads * (2 * T - 1)); w.mask = take(B * T);
+    w.gnpart = (double*)take(2 * B * w.nchunk * c.conv_dim[0]); w.gnmean = (double*)take(2 * B * c.conv_dim[0]); w.gnrstd = take(B * c.conv_dim[0]);
+    w.ta = take(B * T * tdw); w.tb = take(B * T * tdw); w.stats = take(B * 2 * pad32(c.tdnn_dim[c.n_tdnn - 1]));
+    w.lens = (int*)take((long)(c.n_conv + 1) * B);
+    w.bytes = (size_t)off * sizeof(float) + 256;
+    return w;
+}
+
+// the shared argument checks of the calls that take wavs; frames of the padded batch into *T
+int check_wavs(DexWavlm* s, const void* wav, const int32_t* lengths_host, int B, int n_samples, int* T) {
+    if (!wav || !lengths_host) return s->fail(DEX_ERR_ARG, "null pointer argument");
+    if (B < 1 || B > MAX_B) return s->fail(DEX_ERR_ARG, "B must lie in [1, %d]", MAX_B);
+    if (n_samples < 1) return s->fail(DEX_ERR_ARG, "n_samples must be >= 1");
+    *T = frames_of(s->c, n_samples, s->c.n_conv);
+    if (*T > MAXF) return s->fail(DEX_ERR_ARG, "%d samples are %d frames: one call takes at most %d", n_samples, *T, MAXF);
+    const long need = min_samples(s->c);
+    for (int b = 0; b < B; ++b) {
+        if (lengths_host[b] < 1 || lengths_host[b] > n_samples) return s->fail(DEX_ERR_ARG, "row lengths must lie in [1, n_samples]");
+        if (lengths_host[b] < need)
+            return s->fail(DEX_ERR_ARG, "row %d has %d samples: too short, statistics pooling needs two TDNN frames (%ld samples)", b, lengths_host[b], need);
+    }
+    if ((long)B * frames_of(s->c, n_samples, 1) > MAX_ROWS) return s->fail(DEX_ERR_ARG, "B x frames must not exceed %ld", MAX_ROWS);
+    return DEX_OK;
+}
+
+// everything up to the layer-mixed hidden states, stored at `hidden` [B][T][H] (0 past a row's frames)
+int enqueue_encoder(DexWavlm* s, const float* wav, const int32_t* lengths_host, int B, int n, int do_normalize, float* hidden, const Ws& w, hipStream_t st) {
+    const DexWavlmConfig& c = s->c;
+    const int T = w.T, H = c.hidden, nc = c.n_conv;
+    ConvSpec cs;
+    std::memset(&cs, 0, sizeof cs);
+    cs.n = nc;
+    for (int l = 0; l < nc; ++l) { cs.k[l] = c.conv_kernel[l]; cs.s[l] = c.conv_stride[l]; }
+    enqueue_plan(cs, lengths_host, B, T, w.lens, w.mask, st);
+    if (do_normalize) enqueue_norm(wav, lengths_host, B, n, w.xn, st);
+    // feature extractor: layer l lives in fa (l even) / fb (l odd)
+    {
+        const int T0 = w.Tl[0], C0 = c.conv_dim[0];
+        const int* len0 = w.lens + B;
+        const Conv0P p{do_normalize ? w.xn : wav, (long)n, s->conv_w[0], s->conv_b[0], w.fa, T0, C0, c.conv_kernel[0], c.conv_stride[0]};
+        hipLaunchKernelGGL(wavlm_conv0_kernel, dim3((T0 + F0 - 1) / F0, B), dim3(256), 0, st, p);
+        const dim3 pg(w.nchunk, (C0 + 63) / 64, B), fg((C0 + 255) / 256, B);
+        hipLaunchKernelGGL(wavlm_gn_part_kernel<false>, pg, dim3(256), 0, st, w.fa, T0, C0, len0, nullptr, w.gnpart);
+        hipLaunchKernelGGL(wavlm_gn_final_kernel<false>, fg, dim3(256), 0, st, w.gnpart, w.nchunk, T0, C0, len0, w.gnmean, nullptr, 0.f);
+        hipLaunchKernelGGL(wavlm_gn_part_kernel<true>, pg, dim3(256), 0, st, w.fa, T0, C0, len0, w.gnmean, w.gnpart);
+        hipLaunchKernelGGL(wavlm_gn_final_kernel<true>, fg, dim3(256), 0, st, w.gnpart, w.nchunk, T0, C0, len0, nullptr, w.gnrstd, 1e-5f);
+        const long n4 = (long)B * T0 * C0 / 4;
+        hipLaunchKernelGGL(wavlm_gn_apply_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, w.fa, T0, C0, len0, w.gnmean, w.gnrstd, s->gn_g,
+                           s->gn_b, n4);
+    }
+    float* cur = w.fa;
+    for (int l = 1; l < nc; ++l) {
+        float* nxt = (l & 1) ? w.fb : w.fa;
+        gemm(cur, c.conv_dim[l - 1], w.Tl[l - 1], c.conv_dim[l - 1], c.conv_kernel[l], c.conv_stride[l], 0, w.Tl[l], s->conv_w[l], c.conv_dim[l], 1,
+             s->conv_b[l], nxt, 1, nullptr, nullptr, B, st);
+        cur = nxt;
+    }
+    const long rows = (long)B * T;
+    const int C = c.conv_dim[nc - 1];
+    float* fpn = cur == w.fa ? w.fb : w.fa;
+    layer_norm<false>(cur, fpn, rows, T, C, s->fp_g, s->fp_be, c.layer_norm_eps, nullptr, st);
+    linear(fpn, C, s->fp_w, H, s->fp_b, w.y, 0, nullptr, w.mask, T, B, st);            // rows at or past the frame count: 0
+    // h = LN(y + GELU(pos_conv(y)) without its last frame)
+    {
+        const int G = c.num_conv_pos_embedding_groups, K = c.num_conv_pos_embeddings, cg = H / G, cgp = pos_group_pad(c);
+        if (cgp == cg) {
+            gemm(w.y, H, T, cg, K, 1, -(K / 2), T, s->pos_w, cg, G, s->pos_b, w.h, 1, w.y, nullptr, B, st);
+        } else {
+            dex::launch_group_pad(w.y, w.yp, rows, G, cg, cgp, st);
+            gemm(w.yp, G * cgp, T, cgp, K, 1, -(K / 2), T, s->pos_w, cgp, G, s->pos_b, w.pp, 1, nullptr, nullptr, B, st);
+            hipLaunchKernelGGL(wavlm_unpad_add_kernel, dim3((unsigned)((rows * H + 255) / 256)), dim3(256), 0, st, w.y, w.pp, w.h, rows, G, cg, cgp);
+        }
+    }
+    layer_norm<false>(w.h, w.h, rows, T, H, s->enc_g, s->enc_be, c.layer_norm_eps, nullptr, st);
+    const long n4 = rows * H / 4;
+    const dim3 mg((unsigned)((n4 + 255) / 256));
+    auto mix = [&](int l, bool last) {
+        if (!c.use_weighted_layer_sum && !last) return;
+        const bool first = l == 0 || !c.use_weighted_layer_sum;
+        hipLaunchKernelGGL(wavlm_mix_kernel, mg, dim3(256), 0, st, (const float4*)w.h, (const float4*)w.mix, (float4*)(last ? hidden : w.mix), s->lw, l,
+                           first ? 1 : 0, last ? w.mask : nullptr, n4, H / 4);
+    };
+    mix(0, false);
+    hipLaunchKernelGGL(wavlm_rel_kernel, dim3((2 * T - 1 + 255) / 256, c.n_heads), dim3(256), 0, st, s->rel_embed, s->buckets, w.rel, T, c.n_heads);
+    const int* kv_len = w.lens + (long)nc * B;
+    const int ks = fc2_ksplit(c);
+    for (int l = 0; l < c.n_layers; ++l) {
+        const DexWavlm::Layer& L = s->layers[l];
+        hipLaunchKernelGGL(wavlm_gate_kernel, dim3((unsigned)((rows * c.n_heads + 255) / 256)), dim3(256), 0, st, w.h, L.gw, L.gb, L.gc, w.gate, B, T,
+                           c.n_heads);
+        linear(w.h, H, L.wqkv, 3 * H, L.bqkv, w.qkv, 0, nullptr, nullptr, T, B, st);
+        const AttnBiasP a{w.qkv, 3 * H, (long)T * 3 * H, w.y, H, (long)T * H, T, kv_len, c.n_heads, w.rel, w.gate};
+        hipLaunchKernelGGL(wavlm_attn_kernel, dim3((T + 31) / 32, c.n_heads, B), dim3(AT_NW * 64), 0, st, a);
+        linear(w.y, H, L.wo, H, L.bo, w.h, 0, w.h, nullptr, T, B, st);                  // h += out_proj(attn)
+        layer_norm<false>(w.h, w.h, rows, T, H, L.ln1g, L.ln1b, c.layer_norm_eps, nullptr, st);
+        linear(w.h, H, L.w1, c.intermediate, L.b1, w.ff, 1, nullptr, nullptr, T, B, st);
+        if (ks > 1) {                                                                   // h += fc2(GELU(fc1)), K in ks slabs
+            gemm(w.ff, c.intermediate, T, c.intermediate, 1, 1, 0, T, L.w2, H, 1, nullptr, w.part, 0, nullptr, nullptr, B, st, ks);
+            hipLaunchKernelGGL(asr_ksum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, (const float4*)w.part, n4, ks, (const float4*)L.b2,
+                               H / 4, (float4*)w.h);
+        } else {
+            linear(w.ff, c.intermediate, L.w2, H, L.b2, w.h, 0, w.h, nullptr, T, B, st);
+        }
+        layer_norm<false>(w.h, w.h, rows, T, H, L.ln2g, L.ln2b, c.layer_norm_eps, nullptr, st);
+        mix(l + 1, l + 1 == c.n_layers);
+    }
+    return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
+}
+
+// projector, TDNN layers, statistics pooling, the embedding Linear: hidden [B][T][H] -> embed [B][xvector_output_dim]
+int enqueue_head(DexWavlm* s, const float* hidden, int B, float* embed, const Ws& w, hipStream_t st) {
+    const DexWavlmConfig& c = s->c;
+    const int T = w.T, H = c.hidden;
+    linear(hidden, H, s->proj_w, c.tdnn_dim[0], s->proj_b, w.ta, 0, nullptr, nullptr, T, B, st);
+    float* cur = w.ta;
+    int Ti = T, din = c.tdnn_dim[0];
+    for (int i = 0; i < c.n_tdnn; ++i) {
+        float* nxt = cur == w.ta ? w.tb : w.ta;
+        const int k = c.tdnn_kernel[i], dil = c.tdnn_dilation[i], To = Ti - (k - 1) * dil, Np = pad32(c.tdnn_dim[i]);
+        gemm(cur, din, Ti, din, k, 1, 0, To, s->tdnn_w[i], Np, 1, s->tdnn_b[i], nxt, 2, nullptr, nullptr, B, st, 1, dil);
+        cur = nxt; Ti = To; din = Np;
+    }
+    hipLaunchKernelGGL(wavlm_pool_kernel, dim3((din + 63) / 64, B), dim3(POOL_TL * 64), 0, st, cur, Ti, din, w.lens + (long)c.n_conv * B, tdnn_shrink(c),
+                       w.stats);
+    linear(w.stats, 2 * din, s->emb_w, c.xvector_output_dim, s->emb_b, embed, 0, nullptr, nullptr, B, 1, st);
+    return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
+}
+
+int run(DexWavlm* s, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, int do_normalize, float* hidden_dev, float* embed_dev,
+        void* workspace_dev, size_t workspace_bytes, hipStream_t st) {
+    int T = 0;
+    if (int rc = check_wavs(s, wav_dev, lengths_host, B, n_samples, &T)) return rc;
+    if ((!hidden_dev && !embed_dev) || !workspace_dev) return s->fail(DEX_ERR_ARG, "null pointer argument");
+    if (!s->finalized) return s->fail(DEX_ERR_STATE, "the wavlm weights are not finalized (dex_wavlm_finalize)");
+    const Ws w = plan(s->c, workspace_dev, B, n_samples);
+    if (workspace_bytes < w.bytes) return s->fail(DEX_ERR_WORKSPACE, "workspace too small (dex_wavlm_workspace_bytes)");
+    float* hidden = hidden_dev ? hidden_dev : w.mix;
+    int rc = enqueue_encoder(s, wav_dev, lengths_host, B, n_samples, do_normalize, hidden, w, st);
+    if (rc == DEX_OK && embed_dev) rc = enqueue_head(s, hidden, B, embed_dev, w, st);
+    return rc ? s->fail(rc, "kernel launch failed") : DEX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dex_wavlm_create(const DexWavlmConfig* cfg, DexWavlm** out) {
+    if (!out) return DEX_ERR_ARG;
+    *out = nullptr;
+    const DexWavlmConfig c = cfg ? *cfg : default_config();
+    if (int rc = check_config(c)) return rc;
+    DexWavlm* s = new DexWavlm();
+    s->c = c;
+    register_keys(s);
+    *out = s;
+    return DEX_OK;
+}
+
+void dex_wavlm_destroy(DexWavlm* s) {
+    if (!s) return;
+    s->release();
+    delete s;
+}
+
+const char* dex_wavlm_last_error(const DexWavlm* s) { return s ? s->err.c_str() : g_create_err.c_str(); }
+
+int dex_wavlm_load(DexWavlm* s, const char* key, const float* w_dev, const int64_t* shape, int ndim, dex_stream_t stream) {
+    if (!s) return DEX_ERR_ARG;
+    if (!key || !w_dev || !shape) return s->fail(DEX_ERR_ARG, "null pointer argument");
+    return s->load(key, w_dev, shape, ndim, (hipStream_t)stream, false);
+}
+
+int dex_wavlm_finalize(DexWavlm* s, dex_stream_t stream) { return s ? finalize(s, (hipStream_t)stream) : DEX_ERR_ARG; }
+int dex_wavlm_num_weights(const DexWavlm* s) { return s ? (int)s->keys.size() : 0; }
+int dex_wavlm_weight_info(const DexWavlm* s, int i, const char** key, int64_t shape[4], int* ndim) { return s ? s->info(i, key, shape, ndim) : DEX_ERR_ARG; }
+
+int dex_wavlm_num_frames(const DexWavlmConfig* cfg, int n_samples) {
+    const DexWavlmConfig c = cfg ? *cfg : default_config();
+    if (n_samples < 0 || !geometry_ok(c)) return DEX_ERR_ARG;
+    return frames_of(c, n_samples, c.n_conv);
+}
+
+int dex_wavlm_min_samples(const DexWavlmConfig* cfg) {
+    const DexWavlmConfig c = cfg ? *cfg : default_config();
+    if (!geometry_ok(c)) return DEX_ERR_ARG;
+    const long n = min_samples(c);
+    return n > 0x7fffffffL ? DEX_ERR_ARG : (int)n;
+}
+
+int dex_wavlm_rel_buckets(const DexWavlmConfig* cfg, int n, int32_t* out) {
+    const DexWavlmConfig c = cfg ? *cfg : default_config();
+    if (!out || n < 1 || n > (1 << 24) || c.num_buckets < 4 || c.num_buckets % 4 || c.max_bucket_distance <= c.num_buckets / 4) return DEX_ERR_ARG;
+    for (int d = -(n - 1); d <= n - 1; ++d) out[d + n - 1] = bucket_of(c, d);
+    return DEX_OK;
+}
+
+size_t dex_wavlm_workspace_bytes(const DexWavlm* s, int B, int max_samples) {
+    if (!s || B < 1 || B > MAX_B || max_samples < min_samples(s->c)) return 0;
+    if (frames_of(s->c, max_samples, s->c.n_conv) > MAXF || (long)B * frames_of(s->c, max_samples, 1) > MAX_ROWS) return 0;
+    return plan(s->c, nullptr, B, max_samples).bytes;
+}
+
+int dex_wavlm_hidden(DexWavlm* s, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, int do_normalize, float* hidden_dev,
+                     void* workspace_dev, size_t workspace_bytes, dex_stream_t stream) {
+    if (!s) return DEX_ERR_ARG;
+    if (!hidden_dev) return s->fail(DEX_ERR_ARG, "null pointer argument");
+    return run(s, wav_dev, lengths_host, B, n_samples, do_normalize, hidden_dev, nullptr, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+
+int dex_wavlm_embed(DexWavlm* s, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, int do_normalize, float* embed_dev,
+                    void* workspace_dev, size_t workspace_bytes, dex_stream_t stream) {
+    if (!s) return DEX_ERR_ARG;
+    if (!embed_dev) return s->fail(DEX_ERR_ARG, "null pointer argument");
+    return run(s, wav_dev, lengths_host, B, n_samples, do_normalize, nullptr, embed_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -140,6 +140,14 @@ def speaker_scores(encoder, audio, ref_wavs, sr: int = 22050, ref_sr: Optional[i
     return speaker.score_synthesis(audio, ref_wavs, sr, ref_sr, encoder=encoder)
 
 
+def sim_scores(model, audio, ref_wavs, sr: int = 22050, ref_sr: Optional[int] = None):
+    """The WavLM x-vector speaker similarity (SIM) of ``synthesize_tokens``' list of int16 waveforms against the reference wavs, in
+    the same order, on the device -> (cos [B], mean, stderr).  ``model`` is a ``wavlm.WavLMXVector`` with the checkpoint's weights
+    loaded (wavlm.py states what the score is and its departures: the row-alone batching, the resampler, ``do_normalize``)."""
+    from . import wavlm
+    return wavlm.score_synthesis(model, audio, ref_wavs, sr, ref_sr)
+
+
 def asr_scores(model, audio, texts, sr: int = 22050):
     """The reference's ASR score (src/metric.py:21-67) of ``synthesize_tokens``' list of int16 waveforms (``sr`` Hz) against the
     input texts, in the same order -> (transcripts, cer_mean, cer_stderr, wer_mean, wer_stderr).  ``model`` is an

@@ -625,6 +625,60 @@ int  dex_asr_transcribe(DexAsr* asr, const float* wav_dev, const int32_t* length
 int  dex_asr_ctc(DexAsr* asr, const float* logits_dev, const int32_t* frames_host, int B, int T, int V, int32_t* ids_dev,
                  int32_t* counts_dev, dex_stream_t stream);
 
+/* ---- WavLM x-vector speaker similarity (SIM): the embeddings of HF's WavLMForXVector in eval mode with attention_mask = None
+ * (microsoft/wavlm-base-plus-sv and its family: group-norm feature extractor, post-layer-norm encoder, head_dim 64, softmax attention
+ * with the gated relative-position bias, TDNN / statistics-pooling head), in fp32.  Row b of a batch is the network applied to row b
+ * alone at its own length (a zero-padded batch through HF without a mask is not: its group norm sees the padding).  The cosine of two
+ * embeddings is dex_spk_cosine.  Lengths are HOST arrays; bad arguments return an error code, with a message in the handle's last
+ * error, before anything is enqueued.  No compute call synchronises or allocates; a row's result does not depend on its batch.
+ * One call takes rows of at most DEX_WAVLM_MAX_FRAMES encoder frames (81 s at 16 kHz); every row needs at least two frames after the
+ * TDNN layers (dex_wavlm_min_samples: the unbiased deviation over one frame is undefined). */
+typedef struct DexWavlm DexWavlm;
+#define DEX_WAVLM_MAX_CONV 8
+#define DEX_WAVLM_MAX_TDNN 8
+#define DEX_WAVLM_MAX_FRAMES 4096
+typedef struct {
+    int32_t n_conv;                                   /* feature-extractor layers (7) */
+    int32_t conv_dim[DEX_WAVLM_MAX_CONV], conv_kernel[DEX_WAVLM_MAX_CONV], conv_stride[DEX_WAVLM_MAX_CONV];
+    int32_t conv_bias;                                /* 1: the convolutions carry a bias (0 in base-plus-sv) */
+    int32_t feat_extract_norm_group;                  /* 1 = 'group' (the only one built) */
+    int32_t hidden, n_layers, n_heads, intermediate;
+    int32_t do_stable_layer_norm;                     /* 0 (the only one built) */
+    int32_t num_conv_pos_embeddings, num_conv_pos_embedding_groups;
+    float   layer_norm_eps;
+    int32_t num_buckets, max_bucket_distance;         /* relative-position buckets (320, 800) */
+    int32_t use_weighted_layer_sum;                   /* 1: softmax(layer_weights)-weighted sum of the n_layers + 1 hidden states */
+    int32_t n_tdnn;                                   /* TDNN layers (5) */
+    int32_t tdnn_dim[DEX_WAVLM_MAX_TDNN], tdnn_kernel[DEX_WAVLM_MAX_TDNN], tdnn_dilation[DEX_WAVLM_MAX_TDNN];
+    int32_t xvector_output_dim;
+} DexWavlmConfig;
+/* NULL = the base-plus-sv values.  DEX_ERR_ARG (and *out = NULL) for a config outside the family that is built. */
+int  dex_wavlm_create(const DexWavlmConfig* cfg, DexWavlm** out);
+void dex_wavlm_destroy(DexWavlm* w);
+const char* dex_wavlm_last_error(const DexWavlm* w);
+/* one weight under its HF state-dict key (wavlm.feature_extractor.conv_layers.0.conv.weight ..., feature_extractor.bias; the positional
+ * convolution as ...pos_conv_embed.conv.weight_g [1,1,k] / weight_v [hidden, hidden / groups, k]); stream-ordered */
+int  dex_wavlm_load(DexWavlm* w, const char* key, const float* w_dev, const int64_t* shape, int ndim, dex_stream_t stream);
+/* packs the operands (weight norm folded in fp64, the layer weights' softmax, the bucket table); DEX_ERR_STATE names the first key
+ * that was never loaded */
+int  dex_wavlm_finalize(DexWavlm* w, dex_stream_t stream);
+int  dex_wavlm_num_weights(const DexWavlm* w);
+int  dex_wavlm_weight_info(const DexWavlm* w, int i, const char** key, int64_t shape[4], int* ndim);
+/* host only (NULL = default config): encoder frames of n_samples samples; the fewest samples a row may have (5200 by default) */
+int  dex_wavlm_num_frames(const DexWavlmConfig* cfg, int n_samples);
+int  dex_wavlm_min_samples(const DexWavlmConfig* cfg);
+/* host only: out[d + n - 1] = _relative_positions_bucket(d) for the key-minus-query distances d = -(n - 1) .. n - 1 */
+int  dex_wavlm_rel_buckets(const DexWavlmConfig* cfg, int n, int32_t* out);
+size_t dex_wavlm_workspace_bytes(const DexWavlm* w, int B, int max_samples);     /* 0 for bad arguments */
+/* wav_dev [B, n_samples] raw samples, row b lengths_host[b] samples; do_normalize != 0: Wav2Vec2FeatureExtractor's normalisation
+ * first (dex_asr_normalize) -> hidden_dev [B, T, hidden], T = dex_wavlm_num_frames(n_samples): the layer-mixed hidden states the
+ * head reads; row b fills dex_wavlm_num_frames(lengths_host[b]) frames and 0 past them */
+int  dex_wavlm_hidden(DexWavlm* w, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, int do_normalize,
+                      float* hidden_dev, void* workspace_dev, size_t workspace_bytes, dex_stream_t stream);
+/* the same inputs -> embed_dev [B, xvector_output_dim]: WavLMForXVector.forward(...).embeddings of every row alone */
+int  dex_wavlm_embed(DexWavlm* w, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, int do_normalize,
+                     float* embed_dev, void* workspace_dev, size_t workspace_bytes, dex_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
