@@ -30,13 +30,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._native import (Handle, device_index, device_rows, host_lengths, i32_ptr, on_device, pad_wavs, per_device, resample_to_16k, stream,
-                      upload_weights)
+from ._native import device_rows, host_lengths, i32_ptr, on_device, per_device, stream
+from ._wavnet import MAX_CONV, SAMPLING_RATE, NetHandle, WaveformNet, fill_trunk_config
 
-SAMPLING_RATE = 16000
 VOCAB = ("<pad>", "<s>", "</s>", "<unk>", "|", "E", "T", "A", "O", "N", "I", "H", "S", "R", "D", "L", "U", "M", "W", "C", "F", "G", "Y", "P",
          "B", "V", "K", "'", "X", "J", "Q", "Z")
-MAX_CONV = 8
 
 
 @dataclasses.dataclass(frozen=True)
@@ -70,23 +68,9 @@ class DexAsrConfig(C.Structure):
 
 def _c_config(cfg: Wav2Vec2Config) -> DexAsrConfig:
     """The C struct of a config; ``NotImplementedError`` for what the struct cannot even express."""
-    for name in ("hidden_act", "feat_extract_activation"):
-        if getattr(cfg, name) != "gelu":
-            raise NotImplementedError(f"{name}={getattr(cfg, name)!r}: only 'gelu' (erf) is built")
-    n = len(cfg.conv_dim)
-    if not (1 <= n <= MAX_CONV) or len(cfg.conv_kernel) != n or len(cfg.conv_stride) != n:
-        raise NotImplementedError(f"conv_dim / conv_kernel / conv_stride: 1 .. {MAX_CONV} layers of equal count, got "
-                                  f"{n} / {len(cfg.conv_kernel)} / {len(cfg.conv_stride)}")
-    c = DexAsrConfig()
-    c.n_conv = n
-    for i in range(n):
-        c.conv_dim[i], c.conv_kernel[i], c.conv_stride[i] = int(cfg.conv_dim[i]), int(cfg.conv_kernel[i]), int(cfg.conv_stride[i])
-    c.conv_bias = int(bool(cfg.conv_bias))
+    c = fill_trunk_config(DexAsrConfig(), cfg)
     c.feat_extract_norm_layer = int(cfg.feat_extract_norm == "layer")
-    c.hidden, c.n_layers, c.n_heads, c.intermediate = int(cfg.hidden_size), int(cfg.num_hidden_layers), int(cfg.num_attention_heads), int(cfg.intermediate_size)
-    c.do_stable_layer_norm = int(bool(cfg.do_stable_layer_norm))
-    c.num_conv_pos_embeddings, c.num_conv_pos_embedding_groups = int(cfg.num_conv_pos_embeddings), int(cfg.num_conv_pos_embedding_groups)
-    c.layer_norm_eps, c.vocab = float(cfg.layer_norm_eps), int(cfg.vocab_size)
+    c.vocab = int(cfg.vocab_size)
     return c
 
 
@@ -100,35 +84,10 @@ def num_frames(n_samples: int, config: Optional[Wav2Vec2Config] = None) -> int:
     return n
 
 
-_HF_PARAM = {"parametrizations.weight.original0": "weight_g", "parametrizations.weight.original1": "weight_v"}
-_IGNORED = ("wav2vec2.masked_spec_embed",)
+_NO_WORKSPACE = "too short for one frame, or more than one call takes"
 
-
-class _Asr(Handle):
-    """One DexAsr handle (the config, and once loaded the packed weights); its workspace is the network's."""
-
-    def __init__(self, cfg: Wav2Vec2Config, device):
-        super().__init__("dex_asr", device, C.byref(_c_config(cfg)))
-
-    def create_failed(self, rc):
-        return NotImplementedError(f"Wav2Vec2Config.{self.lib.dex_asr_last_error(None).decode()}")
-
-    def shapes(self) -> dict:
-        out = {}
-        key, shape, nd = C.c_char_p(), (C.c_int64 * 4)(), C.c_int()
-        for i in range(self.lib.dex_asr_num_weights(self.h)):
-            self.lib.dex_asr_weight_info(self.h, i, C.byref(key), shape, C.byref(nd))
-            out[key.value.decode()] = tuple(int(shape[k]) for k in range(nd.value))
-        return out
-
-    def workspace(self, B: int, n: int) -> torch.Tensor:
-        need = int(self.lib.dex_asr_workspace_bytes(self.h, B, n))
-        if need == 0:
-            raise ValueError(f"{B} rows of {n} samples: too short for one frame, or more than one call takes")
-        return super().workspace(need)
-
-
-_default_context = per_device(lambda device: _Asr(Wav2Vec2Config(), device))
+# the handle the stateless entry points run on (no weights)
+_default_context = per_device(lambda device: NetHandle("dex_asr", _c_config(Wav2Vec2Config()), device, "Wav2Vec2Config", _NO_WORKSPACE))
 
 
 def normalize_input(wav: torch.Tensor, lengths=None) -> torch.Tensor:
@@ -213,117 +172,47 @@ def cer(gt: str, pred: str) -> float:
     return _levenshtein(gt, pred) / len(gt)
 
 
-class Wav2Vec2CTC:
-    """HF's ``Wav2Vec2ForCTC`` in eval mode on one MI355X, fp32.  ``load_state_dict`` takes the HF checkpoint's state dict."""
+class Wav2Vec2CTC(WaveformNet):
+    """HF's ``Wav2Vec2ForCTC`` in eval mode on one MI355X, fp32.  ``load_state_dict`` takes the HF checkpoint's state dict;
+    ``wav2vec2.masked_spec_embed`` is ignored."""
+    _prefix, _config_name, _no_workspace = "dex_asr", "Wav2Vec2Config", _NO_WORKSPACE
+    _c_config = staticmethod(_c_config)
+    _ignored = staticmethod(lambda key: key == "wav2vec2.masked_spec_embed")
 
     def __init__(self, config: Optional[Wav2Vec2Config] = None, device="cuda", vocab: Optional[Sequence[str]] = None):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise ValueError("Wav2Vec2CTC runs on an MI355X only (no CPU path)")
-        self.config = config or Wav2Vec2Config()
+        super().__init__(config or Wav2Vec2Config(), device)
         self.vocab = tuple(VOCAB if vocab is None else vocab)
         if len(self.vocab) != self.config.vocab_size:
             raise ValueError(f"Wav2Vec2CTC: {len(self.vocab)} symbols for vocab_size {self.config.vocab_size}")
-        self.device = torch.device("cuda", device_index(device))
-        self._ctx = _Asr(self.config, self.device)
-        self._loaded = False
-
-    def state_dict_shapes(self) -> dict:
-        """The HF state-dict keys the network needs, with their shapes (weight norm in its ``weight_g`` / ``weight_v`` spelling)."""
-        return self._ctx.shapes()
-
-    def load_state_dict(self, sd, strict: bool = True):
-        """HF keys.  The positional convolution is taken as ``...conv.weight_g`` / ``weight_v`` or as ``...conv.parametrizations.
-        weight.original0`` / ``original1``; ``wav2vec2.masked_spec_embed`` is ignored.  A wrong shape or (``strict``) a missing or
-        unexpected key raises ``RuntimeError`` before anything is uploaded; with ``strict=False`` the network stays unusable until
-        every key has arrived."""
-        want = self.state_dict_shapes()
-        routed = {}
-        for k, v in sd.items():
-            for old, new in _HF_PARAM.items():
-                if k.endswith(old):
-                    k = k[: -len(old)] + new
-            routed[k] = v
-        missing = [k for k in want if k not in routed]
-        extra = [k for k in routed if k not in want and k not in _IGNORED]
-        if strict and missing:
-            raise RuntimeError(f"missing keys {missing[:4]}")
-        if strict and extra:
-            raise RuntimeError(f"unexpected keys {sorted(extra)[:4]}")
-        tensors = {}
-        for k, shape in want.items():
-            if k in routed:
-                v = torch.as_tensor(routed[k])
-                if tuple(v.shape) != shape:
-                    raise RuntimeError(f"{k}: expected shape {shape}, got {tuple(v.shape)}")
-                tensors[k] = v
-        self._loaded = False
-        upload_weights(self._ctx, self._ctx.lib.dex_asr_load, tensors, self.device)
-        if not missing:
-            self.finalize()
-            torch.cuda.current_stream(self.device).synchronize()        # the operands are packed when this returns
-        return self
-
-    def finalize(self):
-        """Pack the operands (``dex_asr_finalize``); ``ValueError`` naming the first key that was never loaded."""
-        ctx = self._ctx
-        with torch.cuda.device(self.device):
-            ctx.check(ctx.lib.dex_asr_finalize(ctx.h, stream(self.device)), "dex_asr_finalize")
-        self._loaded = True
-        return self
-
-    def _need_weights(self, what: str):
-        if not self._loaded:
-            raise ValueError(f"{what}: the network's weights are not loaded (load_state_dict)")
 
     def _inputs(self, wav, lengths, what: str):
-        self._need_weights(what)
-        x, ln, one = device_rows(wav, lengths, what, refuse=ValueError)
+        x, ln, one = self._rows(wav, lengths, what)
         short = [v for v in ln if num_frames(v, self.config) < 1]
         if short:
             raise ValueError(f"{what}: {short[0]} samples are too short for one frame of the feature extractor")
-        return x.to(self.device), ln, one
+        return x, ln, one
 
     def forward(self, input_values: torch.Tensor, lengths=None) -> torch.Tensor:
         """Raw 16 kHz samples [B, n] (or [n]), row b ``lengths[b]`` samples (what is stored past them is not read into any result)
         -> logits [B, T, V] with T = ``num_frames(n)``; row b fills ``num_frames(lengths[b])`` frames and is 0 past them.  The input
         normalisation is part of the call.  A row's logits are bitwise those of the row alone."""
         x, ln, one = self._inputs(input_values, lengths, "Wav2Vec2CTC.forward")
-        B, n = x.shape
-        ctx = self._ctx
-        ws = ctx.workspace(B, n)
-        out = torch.empty(B, num_frames(n, self.config), self.config.vocab_size, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = ctx.lib.dex_asr_logits(ctx.h, x.data_ptr(), i32_ptr(ln), B, n, out.data_ptr(), ws.data_ptr(), ws.numel(), stream(self.device))
-        ctx.check(rc, "dex_asr_logits")
-        return out[0] if one else out
+        out = torch.empty(x.shape[0], num_frames(x.shape[1], self.config), self.config.vocab_size, dtype=torch.float32, device=self.device)
+        return self._run("logits", x, ln, out, out.data_ptr(), one=one)
 
     __call__ = forward
 
     def transcribe_ids(self, wavs: torch.Tensor, lengths=None):
         """forward + greedy CTC in one stream-ordered sequence -> a list of id lists; one device-to-host copy of ids and counts."""
         x, ln, _ = self._inputs(wavs, lengths, "Wav2Vec2CTC.transcribe")
-        B, n = x.shape
-        T = num_frames(n, self.config)
-        ctx = self._ctx
-        ws = ctx.workspace(B, n)
+        B, T = x.shape[0], num_frames(x.shape[1], self.config)
         buf = torch.empty(B * T + B, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = ctx.lib.dex_asr_transcribe(ctx.h, x.data_ptr(), i32_ptr(ln), B, n, buf.data_ptr(), buf.data_ptr() + 4 * B * T, ws.data_ptr(),
-                                            ws.numel(), stream(self.device))
-        ctx.check(rc, "dex_asr_transcribe")
-        return _unpack(buf, B, T)
+        return _unpack(self._run("transcribe", x, ln, buf, buf.data_ptr(), buf.data_ptr() + 4 * B * T), B, T)
 
     def transcribe(self, wavs, lengths=None, sr: int = SAMPLING_RATE):
         """metric.py:24-35 for a batch: ``wavs`` [B, n] (or [n]) with ``lengths``, or a list of wavs, at ``sr`` Hz -> a list of
         transcripts.  Where ``sr`` is not 16000 the wavs are resampled by ``wavprep.resample`` (kaiser_best; librosa uses soxr)."""
-        if int(sr) <= 0:
-            raise ValueError(f"Wav2Vec2CTC.transcribe: sr must be positive, got {sr}")
-        if not isinstance(wavs, torch.Tensor):
-            wavs, lengths = pad_wavs(wavs, self.device, scale_int16=True)
-        if int(sr) != SAMPLING_RATE:
-            x, ln, _ = device_rows(wavs, lengths, "Wav2Vec2CTC.transcribe", refuse=ValueError)
-            wavs, lengths = resample_to_16k(x, ln, sr)
+        wavs, lengths = self._at_16k(wavs, lengths, sr, "Wav2Vec2CTC.transcribe")
         return [decode(ids, self.vocab) for ids in self.transcribe_ids(wavs, lengths)]
 
 

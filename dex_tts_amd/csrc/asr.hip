@@ -23,31 +23,27 @@
 //   asr_ctc_kernel       greedy CTC, one workgroup per utterance: the first index of each frame's maximum, repeats collapsed, blanks
 //                        dropped, compacted with a block scan; ids and counts are all that travels to the host.
 // Every per-row sum has a fixed order that does not depend on the batch: a row's logits are bitwise the row run alone.
-// What the WavLM x-vector network (wavlm.hip) shares - asr_norm / plan / ln / wn_scale / pack / ksum and the launch_igemm wrappers -
-// lives in wav_encoder.h; the first convolution and the CTC kernel are here.
+// This file holds what is wav2vec 2.0's own: the first convolution with its LayerNorm, the CTC kernel, the checks of the layer-norm
+// family, lm_head and the pre-norm layer loop.  The trunk it shares with the WavLM x-vector network (wavlm.hip) is elsewhere:
+// asr_norm / plan / ln / wn_scale / pack / ksum and the launch_igemm wrappers in wav_encoder.h; geometry, key inventory, packing,
+// workspace prefix, the enqueue steps around the layer loop and the boilerplate entry points in wav_trunk.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 #include <string>
-#include <vector>
 
 #include "../../include/dex_amd.h"
 #include "kernels.h"
-#include "wav_encoder.h"
+#include "wav_trunk.h"
 #include "weight_store.h"
 
-using namespace dex::wavenc;      // the pieces shared with wavlm.hip: norm, plan, LayerNorm, packing, the GEMM wrappers
+using namespace dex::wavenc;      // the trunk shared with wavlm.hip
 
 namespace {
 
 static_assert(MAXC == DEX_ASR_MAX_CONV, "ConvSpec holds DEX_ASR_MAX_CONV layers");
-constexpr int F0 = 8;                   // frames per workgroup of the first convolution
-constexpr int K0_MAX = 16, S0_MAX = 16;  // its kernel and stride bounds (taps in registers, window in LDS)
-constexpr int C0_MAX = 512;              // its channels: two per thread
-constexpr int MAX_B = 1024;              // grid z = B x 16 groups stays inside 65535
 constexpr int MAX_SAMPLES = 1 << 24;     // 17 minutes at 16 kHz
-constexpr long MAX_ROWS = 1L << 26;      // B x frames of the first layer: every grid inside 2^31, every element index inside 2^63
 
 struct Conv0P { const float* x; long x_ld; const float* w; const float* bias; const float* gamma; const float* beta; float eps;
                 float* out; int T0, C, k, s; const int* len1; };
@@ -162,24 +158,13 @@ __global__ __launch_bounds__(256) void asr_ctc_kernel(const float* logits, int T
     if (tid == 0) counts[b] = base;
 }
 
-thread_local std::string g_create_err;
-
-int create_fail(const char* fmt, const char* field) {
-    char buf[256];
-    snprintf(buf, sizeof buf, fmt, field);
-    g_create_err = buf;
-    return DEX_ERR_ARG;
-}
-
 DexAsrConfig default_config() {
     DexAsrConfig c;
     std::memset(&c, 0, sizeof c);
-    const int k[7] = {10, 3, 3, 3, 3, 2, 2}, s[7] = {5, 2, 2, 2, 2, 2, 2};
-    c.n_conv = 7;
-    for (int i = 0; i < 7; ++i) { c.conv_dim[i] = 512; c.conv_kernel[i] = k[i]; c.conv_stride[i] = s[i]; }
+    default_trunk_geometry(c);
     c.conv_bias = 1; c.feat_extract_norm_layer = 1;
     c.hidden = 1024; c.n_layers = 24; c.n_heads = 16; c.intermediate = 4096; c.do_stable_layer_norm = 1;
-    c.num_conv_pos_embeddings = 128; c.num_conv_pos_embedding_groups = 16; c.layer_norm_eps = 1e-5f; c.vocab = 32;
+    c.vocab = 32;
     return c;
 }
 
@@ -187,209 +172,76 @@ DexAsrConfig default_config() {
 int check_config(const DexAsrConfig& c) {
     if (c.feat_extract_norm_layer != 1) return create_fail("%s: only 'layer' is built", "feat_extract_norm");
     if (c.do_stable_layer_norm != 1) return create_fail("%s: only True is built", "do_stable_layer_norm");
-    if (c.n_conv < 1 || c.n_conv > MAXC) return create_fail("%s: 1 .. 8 feature-extractor layers", "conv_dim");
-    for (int l = 0; l < c.n_conv; ++l) {
-        if (c.conv_dim[l] < 32 || c.conv_dim[l] % 32 || c.conv_dim[l] > 4096) return create_fail("%s: every width a multiple of 32 in 32 .. 4096", "conv_dim");
-        if (c.conv_kernel[l] < 1 || c.conv_kernel[l] > 64) return create_fail("%s: 1 .. 64", "conv_kernel");
-        if (c.conv_stride[l] < 1 || c.conv_stride[l] > 64) return create_fail("%s: 1 .. 64", "conv_stride");
-    }
-    if (c.conv_dim[0] > C0_MAX) return create_fail("%s: the first layer has at most 512 channels", "conv_dim");
-    if (c.conv_kernel[0] > K0_MAX) return create_fail("%s: the first layer's kernel is at most 16", "conv_kernel");
-    if (c.conv_stride[0] > S0_MAX) return create_fail("%s: the first layer's stride is at most 16", "conv_stride");
-    if (c.n_heads < 1 || c.n_heads > 1024) return create_fail("%s: 1 .. 1024", "num_attention_heads");
-    if (c.hidden < 64 || c.hidden > 16384 || c.hidden != 64 * c.n_heads) return create_fail("%s: hidden_size / num_attention_heads must be 64", "hidden_size");
-    if (c.n_layers < 1 || c.n_layers > 256) return create_fail("%s: 1 .. 256", "num_hidden_layers");
-    if (c.intermediate < 32 || c.intermediate % 32 || c.intermediate > 65536) return create_fail("%s: a multiple of 32 up to 65536", "intermediate_size");
-    const int G = c.num_conv_pos_embedding_groups, K = c.num_conv_pos_embeddings;
-    if (G < 1 || G > 16 || c.hidden % G || (c.hidden / G) % 32) return create_fail("%s: 1 .. 16 groups of a multiple of 32 channels", "num_conv_pos_embedding_groups");
-    if (K < 2 || K % 2 || K > 1024) return create_fail("%s: even, 2 .. 1024", "num_conv_pos_embeddings");
-    if (!(c.layer_norm_eps > 0.f) || !(c.layer_norm_eps < 1.f)) return create_fail("%s: in (0, 1)", "layer_norm_eps");
+    if (int rc = check_trunk(trunk_of(c), 32)) return rc;
     if (c.vocab < 32 || c.vocab % 32 || c.vocab > 4096) return create_fail("%s: a multiple of 32 up to 4096", "vocab_size");
     return DEX_OK;
 }
 
-// the k-split of fc2: intermediate / hidden where that is 2, 4 or 8 (and the slices stay multiples of the GEMM's K tile), else none
-int fc2_ksplit(const DexAsrConfig& c) {
-    const int r = c.intermediate / c.hidden;
-    return (r * c.hidden == c.intermediate && (r == 2 || r == 4 || r == 8) && (c.intermediate / r) % 32 == 0) ? r : 1;
-}
-
-int frames_of(const DexAsrConfig& c, long n, int upto) {
-    for (int l = 0; l < upto; ++l) n = n >= c.conv_kernel[l] ? (n - c.conv_kernel[l]) / c.conv_stride[l] + 1 : 0;
-    return (int)n;
-}
+const TrunkKeys KEYS("wav2vec2.");
 
 }  // namespace
 
 struct DexAsr : dex::WeightStore {
     DexAsr() : WeightStore("wav2vec2 ") {}
     DexAsrConfig c;
-    const float* conv_w[MAXC] = {}; const float* conv_b[MAXC] = {}; const float* conv_g[MAXC] = {}; const float* conv_be[MAXC] = {};
-    const float *fp_g = nullptr, *fp_be = nullptr, *fp_w = nullptr, *fp_b = nullptr, *pos_w = nullptr, *pos_b = nullptr;
-    const float *enc_g = nullptr, *enc_be = nullptr, *lm_w = nullptr, *lm_b = nullptr;
-    struct Layer { const float *ln1g, *ln1b, *wqkv, *bqkv, *wo, *bo, *ln2g, *ln2b, *w1, *b1, *w2, *b2; };
-    std::vector<Layer> layers;
+    Trunk t;
+    TrunkWeights w;
+    const float *lm_w = nullptr, *lm_b = nullptr;
 };
 
 namespace {
 
-const std::string FE = "wav2vec2.feature_extractor.conv_layers.", ENC = "wav2vec2.encoder.", FP = "wav2vec2.feature_projection.";
-std::string lk(int l, const char* what) { return ENC + "layers." + std::to_string(l) + "." + what; }
-std::string ck(int l, const char* what) { return FE + std::to_string(l) + "." + what; }
-
 void register_keys(DexAsr* s) {
-    const DexAsrConfig& c = s->c;
-    for (int l = 0; l < c.n_conv; ++l) {
-        s->add(ck(l, "conv.weight"), {c.conv_dim[l], l ? c.conv_dim[l - 1] : 1, c.conv_kernel[l]});
-        if (c.conv_bias) s->add(ck(l, "conv.bias"), {c.conv_dim[l]});
-        s->add(ck(l, "layer_norm.weight"), {c.conv_dim[l]});
-        s->add(ck(l, "layer_norm.bias"), {c.conv_dim[l]});
-    }
-    const int C = c.conv_dim[c.n_conv - 1], H = c.hidden, I = c.intermediate;
-    s->add(FP + "layer_norm.weight", {C}); s->add(FP + "layer_norm.bias", {C});
-    s->add(FP + "projection.weight", {H, C}); s->add(FP + "projection.bias", {H});
-    s->add(ENC + "pos_conv_embed.conv.bias", {H});
-    s->add(ENC + "pos_conv_embed.conv.weight_g", {1, 1, c.num_conv_pos_embeddings});
-    s->add(ENC + "pos_conv_embed.conv.weight_v", {H, H / c.num_conv_pos_embedding_groups, c.num_conv_pos_embeddings});
-    s->add(ENC + "layer_norm.weight", {H}); s->add(ENC + "layer_norm.bias", {H});
-    for (int l = 0; l < c.n_layers; ++l) {
-        for (const char* pr : {"attention.q_proj", "attention.k_proj", "attention.v_proj", "attention.out_proj"}) {
-            s->add(lk(l, pr) + ".weight", {H, H}); s->add(lk(l, pr) + ".bias", {H});
-        }
-        s->add(lk(l, "layer_norm.weight"), {H}); s->add(lk(l, "layer_norm.bias"), {H});
-        s->add(lk(l, "feed_forward.intermediate_dense.weight"), {I, H}); s->add(lk(l, "feed_forward.intermediate_dense.bias"), {I});
-        s->add(lk(l, "feed_forward.output_dense.weight"), {H, I}); s->add(lk(l, "feed_forward.output_dense.bias"), {H});
-        s->add(lk(l, "final_layer_norm.weight"), {H}); s->add(lk(l, "final_layer_norm.bias"), {H});
-    }
-    s->add("lm_head.weight", {c.vocab, H}); s->add("lm_head.bias", {c.vocab});
+    s->t = trunk_of(s->c);
+    register_trunk_keys(s, KEYS, s->t, true, [](int) {});
+    s->add("lm_head.weight", {s->c.vocab, s->c.hidden}); s->add("lm_head.bias", {s->c.vocab});
 }
 
-int finalize(DexAsr* s, hipStream_t st) {
-    if (int rc = s->begin_finalize()) return rc;
-    const DexAsrConfig& c = s->c;
-    const int H = c.hidden, I = c.intermediate, C = c.conv_dim[c.n_conv - 1];
-    for (int l = 0; l < c.n_conv; ++l) {
-        s->conv_w[l] = l ? pack(s, ck(l, "conv.weight"), 1, c.conv_dim[l], c.conv_dim[l - 1], c.conv_kernel[l], nullptr, st) : s->R(ck(0, "conv.weight"));
-        s->conv_b[l] = c.conv_bias ? s->R(ck(l, "conv.bias")) : nullptr;
-        s->conv_g[l] = s->R(ck(l, "layer_norm.weight")); s->conv_be[l] = s->R(ck(l, "layer_norm.bias"));
-    }
-    s->fp_g = s->R(FP + "layer_norm.weight"); s->fp_be = s->R(FP + "layer_norm.bias");
-    s->fp_w = pack(s, FP + "projection.weight", 1, H, C, 1, nullptr, st); s->fp_b = s->R(FP + "projection.bias");
-    {
-        const int G = c.num_conv_pos_embedding_groups, K = c.num_conv_pos_embeddings;
-        double* scale = (double*)s->alloc(2L * K);
-        if (scale) {
-            hipLaunchKernelGGL(asr_wn_scale_kernel, dim3(K), dim3(256), 0, st, s->R(ENC + "pos_conv_embed.conv.weight_v"),
-                               s->R(ENC + "pos_conv_embed.conv.weight_g"), scale, (long)H * (H / G), K);
-            s->pos_w = pack(s, ENC + "pos_conv_embed.conv.weight_v", G, H / G, H / G, K, scale, st);
-        }
-        s->pos_b = s->R(ENC + "pos_conv_embed.conv.bias");
-    }
-    s->enc_g = s->R(ENC + "layer_norm.weight"); s->enc_be = s->R(ENC + "layer_norm.bias");
-    s->layers.assign(c.n_layers, DexAsr::Layer{});
-    for (int l = 0; l < c.n_layers && s->alloc_rc == DEX_OK; ++l) {
-        DexAsr::Layer& L = s->layers[l];
-        float* wqkv = s->alloc(3L * H * H); float* bqkv = s->alloc(3L * H);
-        if (!wqkv || !bqkv) break;
-        const char* pr[3] = {"attention.q_proj", "attention.k_proj", "attention.v_proj"};
-        for (int j = 0; j < 3; ++j) {
-            pack_into(s->R(lk(l, pr[j]) + ".weight"), wqkv, 1, H, H, 1, 3 * H, j * H, nullptr, st);
-            DEX_HIPCHK(s, hipMemcpyAsync(bqkv + (long)j * H, s->R(lk(l, pr[j]) + ".bias"), H * sizeof(float), hipMemcpyDeviceToDevice, st));
-        }
-        L.wqkv = wqkv; L.bqkv = bqkv;
-        L.wo = pack(s, lk(l, "attention.out_proj") + ".weight", 1, H, H, 1, nullptr, st); L.bo = s->R(lk(l, "attention.out_proj") + ".bias");
-        L.ln1g = s->R(lk(l, "layer_norm.weight")); L.ln1b = s->R(lk(l, "layer_norm.bias"));
-        L.w1 = pack(s, lk(l, "feed_forward.intermediate_dense.weight"), 1, I, H, 1, nullptr, st); L.b1 = s->R(lk(l, "feed_forward.intermediate_dense.bias"));
-        L.w2 = pack(s, lk(l, "feed_forward.output_dense.weight"), 1, H, I, 1, nullptr, st); L.b2 = s->R(lk(l, "feed_forward.output_dense.bias"));
-        L.ln2g = s->R(lk(l, "final_layer_norm.weight")); L.ln2b = s->R(lk(l, "final_layer_norm.bias"));
-    }
-    s->lm_w = pack(s, "lm_head.weight", 1, c.vocab, H, 1, nullptr, st); s->lm_b = s->R("lm_head.bias");
-    if (s->alloc_rc != DEX_OK) return s->alloc_rc;
-    if (hipGetLastError() != hipSuccess) return s->fail(DEX_ERR_HIP, "packing the wav2vec2 weights failed");
-    s->finalized = true;
+int pack_all(DexAsr* s, hipStream_t st) {
+    const Trunk& t = s->t;
+    auto pack_pos = [&](const double* scale) {
+        const int G = t.pos_groups, cg = t.hidden / G;
+        if (scale) s->w.pos_w = pack(s, KEYS.ENC + "pos_conv_embed.conv.weight_v", G, cg, cg, t.pos_k, scale, st);
+        s->w.pos_b = s->R(KEYS.ENC + "pos_conv_embed.conv.bias");
+    };
+    if (int rc = finalize_trunk(s, KEYS, t, true, s->w, pack_pos, st)) return rc;
+    s->lm_w = pack(s, "lm_head.weight", 1, s->c.vocab, t.hidden, 1, nullptr, st); s->lm_b = s->R("lm_head.bias");
     return DEX_OK;
 }
 
-// workspace (floats, every piece a multiple of 64): xn [B][n] | fa [B][T_0][C_0] (even layers) | fb [B][T_1][C_1] (odd layers) |
-// h, y [B][T][H] | qkv [B][T][3H] | ff [B][T][I] | part [ksplit][B][T][H] (fc2's slabs) | logits [B][T][V] | mask [B][T] | lens (int) [n_conv + 1][B]
-struct Ws { float *xn, *fa, *fb, *h, *y, *qkv, *ff, *part, *logits, *mask; int* lens; size_t bytes; int Tl[MAXC]; int T; };
-Ws plan(const DexAsrConfig& c, void* ws, long B, long n) {
+// workspace: the trunk's prefix | logits [B][T][V] | mask [B][T] | lens (int) [n_conv + 1][B]
+struct Ws : TrunkWs { float* logits; size_t bytes; };
+Ws plan(const DexAsr* s, void* ws, long B, long n) {
     Ws w{};
-    long fa = 0, fb = 0;
-    for (int l = 0; l < c.n_conv; ++l) {
-        w.Tl[l] = frames_of(c, n, l + 1);
-        long& m = (l & 1) ? fb : fa;
-        const long sz = (long)w.Tl[l] * c.conv_dim[l];
-        m = sz > m ? sz : m;
-    }
-    w.T = w.Tl[c.n_conv - 1];
-    const long T = w.T, H = c.hidden;
-    // the LayerNorm of the feature projection writes the OTHER ping-pong buffer: both hold a [T][C_last] tensor
-    const long last = T * c.conv_dim[c.n_conv - 1];
-    fa = fa > last ? fa : last; fb = fb > last ? fb : last;
-    float* f = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    long off = 0;
-    auto take = [&](long cnt) { float* p = f + off; off += up64(cnt); return p; };
-    w.xn = take(B * n); w.fa = take(B * fa); w.fb = take(B * fb);
-    w.h = take(B * T * H); w.y = take(B * T * H); w.qkv = take(B * T * 3 * H); w.ff = take(B * T * c.intermediate);
-    w.part = take(fc2_ksplit(c) > 1 ? fc2_ksplit(c) * B * T * H : 0);
-    w.logits = take(B * T * c.vocab); w.mask = take(B * T); w.lens = (int*)take((long)(c.n_conv + 1) * B);
-    w.bytes = (size_t)off * sizeof(float) + 256;
+    Taker tk(ws);
+    plan_trunk(s->t, tk, B, n, w);
+    w.logits = tk.take(B * w.T * s->c.vocab); w.mask = tk.take(B * w.T); w.lens = (int*)tk.take((long)(s->t.n_conv + 1) * B);
+    w.bytes = tk.bytes();
     return w;
 }
 
-// the shared argument checks of the calls that take wavs; frames of the padded batch into *T
+// a row needs one frame of the feature extractor
 int check_wavs(DexAsr* s, const void* wav, const int32_t* lengths_host, int B, int n_samples, int* T) {
-    if (!wav || !lengths_host) return s->fail(DEX_ERR_ARG, "null pointer argument");
-    if (B < 1 || B > MAX_B) return s->fail(DEX_ERR_ARG, "B must lie in [1, %d]", MAX_B);
-    if (n_samples < 1 || n_samples > MAX_SAMPLES) return s->fail(DEX_ERR_ARG, "n_samples must lie in [1, %d]", MAX_SAMPLES);
-    for (int b = 0; b < B; ++b) {
-        if (lengths_host[b] < 1 || lengths_host[b] > n_samples) return s->fail(DEX_ERR_ARG, "row lengths must lie in [1, n_samples]");
-        if (frames_of(s->c, lengths_host[b], s->c.n_conv) < 1)
-            return s->fail(DEX_ERR_ARG, "row %d has %d samples: too short for one frame of the feature extractor", b, lengths_host[b]);
-    }
-    if ((long)B * frames_of(s->c, n_samples, 1) > MAX_ROWS) return s->fail(DEX_ERR_ARG, "B x frames must not exceed %ld", MAX_ROWS);
-    *T = frames_of(s->c, n_samples, s->c.n_conv);
-    return DEX_OK;
+    const WavRule r{samples_for(s->t, 1), "too short for one frame of the feature extractor", MAX_SAMPLES, 0};
+    return dex::wavenc::check_wavs(s, s->t, r, wav, lengths_host, B, n_samples, T);
 }
 
 int enqueue_network(DexAsr* s, const float* wav, const int32_t* lengths_host, int B, int n, float* logits, const Ws& w, hipStream_t st) {
-    const DexAsrConfig& c = s->c;
-    const int T = w.T, H = c.hidden, nc = c.n_conv;
-    ConvSpec cs;
-    std::memset(&cs, 0, sizeof cs);
-    cs.n = nc;
-    for (int l = 0; l < nc; ++l) { cs.k[l] = c.conv_kernel[l]; cs.s[l] = c.conv_stride[l]; }
-    enqueue_plan(cs, lengths_host, B, T, w.lens, w.mask, st);
-    enqueue_norm(wav, lengths_host, B, n, w.xn, st);
-    // feature extractor: layer l lives in fa (l even) / fb (l odd)
+    const Trunk& c = s->t;
+    const TrunkWeights& W = s->w;
+    const int T = w.T, H = c.hidden;
+    enqueue_front(c, w, wav, lengths_host, B, n, true, st);
     {
-        const Conv0P p{w.xn, (long)n, s->conv_w[0], s->conv_b[0], s->conv_g[0], s->conv_be[0], c.layer_norm_eps, w.fa, w.Tl[0], c.conv_dim[0],
+        const Conv0P p{w.xn, (long)n, W.conv_w[0], W.conv_b[0], W.conv_g[0], W.conv_be[0], c.layer_norm_eps, w.fa, w.Tl[0], c.conv_dim[0],
                        c.conv_kernel[0], c.conv_stride[0], w.lens + B};
         hipLaunchKernelGGL(asr_conv0_kernel, dim3((w.Tl[0] + F0 - 1) / F0, B), dim3(256), 0, st, p);
     }
-    float* cur = w.fa;
-    for (int l = 1; l < nc; ++l) {
-        float* nxt = (l & 1) ? w.fb : w.fa;
-        gemm(cur, c.conv_dim[l - 1], w.Tl[l - 1], c.conv_dim[l - 1], c.conv_kernel[l], c.conv_stride[l], 0, w.Tl[l], s->conv_w[l], c.conv_dim[l], 1,
-             s->conv_b[l], nxt, 0, nullptr, nullptr, B, st);
-        layer_norm<true>(nxt, nxt, (long)B * w.Tl[l], w.Tl[l], c.conv_dim[l], s->conv_g[l], s->conv_be[l], c.layer_norm_eps, w.lens + (long)(l + 1) * B, st);
-        cur = nxt;
-    }
-    const long rows = (long)B * T;
-    const int C = c.conv_dim[nc - 1];
-    float* fpn = cur == w.fa ? w.fb : w.fa;
-    layer_norm<false>(cur, fpn, rows, T, C, s->fp_g, s->fp_be, c.layer_norm_eps, nullptr, st);
-    linear(fpn, C, s->fp_w, H, s->fp_b, w.y, 0, nullptr, w.mask, T, B, st);            // rows at or past the frame count: 0
+    enqueue_projection(c, W, w, enqueue_conv_tail<true>(c, W, w, B, 0, st), B, st);
     // h = y + GELU(pos_conv(y)) without its last frame
-    {
-        const int G = c.num_conv_pos_embedding_groups, K = c.num_conv_pos_embeddings;
-        gemm(w.y, H, T, H / G, K, 1, -(K / 2), T, s->pos_w, H / G, G, s->pos_b, w.h, 1, w.y, nullptr, B, st);
-    }
-    const int* kv_len = w.lens + (long)nc * B;
-    const int ks = fc2_ksplit(c);
-    for (int l = 0; l < c.n_layers; ++l) {
-        const DexAsr::Layer& L = s->layers[l];
+    gemm(w.y, H, T, H / c.pos_groups, c.pos_k, 1, -(c.pos_k / 2), T, W.pos_w, H / c.pos_groups, c.pos_groups, W.pos_b, w.h, 1, w.y, nullptr, B, st);
+    const long rows = (long)B * T;
+    const int* kv_len = w.lens + (long)c.n_conv * B;
+    for (const TrunkWeights::Layer& L : W.layers) {                                     // pre-norm: h += attn(LN(h)); h += ffn(LN(h))
         layer_norm<false>(w.h, w.y, rows, T, H, L.ln1g, L.ln1b, c.layer_norm_eps, nullptr, st);
         linear(w.y, H, L.wqkv, 3 * H, L.bqkv, w.qkv, 0, nullptr, nullptr, T, B, st);
         dex::AttnP a{};
@@ -401,22 +253,15 @@ int enqueue_network(DexAsr* s, const float* wav, const int32_t* lengths_host, in
         dex::launch_attention(a, dex::PREC_FP32, st);
         linear(w.y, H, L.wo, H, L.bo, w.h, 0, w.h, nullptr, T, B, st);                  // h += out_proj(attn)
         layer_norm<false>(w.h, w.y, rows, T, H, L.ln2g, L.ln2b, c.layer_norm_eps, nullptr, st);
-        linear(w.y, H, L.w1, c.intermediate, L.b1, w.ff, 1, nullptr, nullptr, T, B, st);
-        if (ks > 1) {                                                                   // h += fc2(GELU(fc1)), K in ks slabs
-            gemm(w.ff, c.intermediate, T, c.intermediate, 1, 1, 0, T, L.w2, H, 1, nullptr, w.part, 0, nullptr, nullptr, B, st, ks);
-            const long n4 = rows * H / 4;
-            hipLaunchKernelGGL(asr_ksum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, (const float4*)w.part, n4, ks, (const float4*)L.b2,
-                               H / 4, (float4*)w.h);
-        } else {
-            linear(w.ff, c.intermediate, L.w2, H, L.b2, w.h, 0, w.h, nullptr, T, B, st);
-        }
+        enqueue_ffn(c, L, w, w.y, B, st);
     }
-    layer_norm<false>(w.h, w.y, rows, T, H, s->enc_g, s->enc_be, c.layer_norm_eps, nullptr, st);
-    linear(w.y, H, s->lm_w, c.vocab, s->lm_b, logits, 0, nullptr, w.mask, T, B, st);
+    layer_norm<false>(w.h, w.y, rows, T, H, W.enc_g, W.enc_be, c.layer_norm_eps, nullptr, st);
+    linear(w.y, H, s->lm_w, s->c.vocab, s->lm_b, logits, 0, nullptr, w.mask, T, B, st);
     return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
 }
 
-int enqueue_ctc(const float* logits, const int32_t* frames_host, const int* lengths_host, const DexAsrConfig* c, int B, int T, int V, int32_t* ids,
+// frames_host, or (null) the frame counts of the lengths under trunk c
+int enqueue_ctc(const float* logits, const int32_t* frames_host, const int* lengths_host, const Trunk* c, int B, int T, int V, int32_t* ids,
                 int32_t* counts, hipStream_t st) {
     for (int r0 = 0; r0 < B; r0 += TAB) {
         Tab R;
@@ -428,52 +273,32 @@ int enqueue_ctc(const float* logits, const int32_t* frames_host, const int* leng
     return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
 }
 
+typedef Entry<DexAsr> E;
+
 }  // namespace
 
 extern "C" {
 
-int dex_asr_create(const DexAsrConfig* cfg, DexAsr** out) {
-    if (!out) return DEX_ERR_ARG;
-    *out = nullptr;
-    const DexAsrConfig c = cfg ? *cfg : default_config();
-    if (int rc = check_config(c)) return rc;
-    DexAsr* s = new DexAsr();
-    s->c = c;
-    register_keys(s);
-    *out = s;
-    return DEX_OK;
-}
-
-void dex_asr_destroy(DexAsr* s) {
-    if (!s) return;
-    s->release();
-    delete s;
-}
-
-const char* dex_asr_last_error(const DexAsr* s) { return s ? s->err.c_str() : g_create_err.c_str(); }
-
+int dex_asr_create(const DexAsrConfig* cfg, DexAsr** out) { return E::create(cfg, out, default_config, check_config, register_keys); }
+void dex_asr_destroy(DexAsr* s) { E::destroy(s); }
+const char* dex_asr_last_error(const DexAsr* s) { return E::last_error(s); }
 int dex_asr_load(DexAsr* s, const char* key, const float* w_dev, const int64_t* shape, int ndim, dex_stream_t stream) {
-    if (!s) return DEX_ERR_ARG;
-    if (!key || !w_dev || !shape) return s->fail(DEX_ERR_ARG, "null pointer argument");
-    return s->load(key, w_dev, shape, ndim, (hipStream_t)stream, false);
+    return E::load(s, key, w_dev, shape, ndim, stream);
 }
-
-int dex_asr_finalize(DexAsr* s, dex_stream_t stream) { return s ? finalize(s, (hipStream_t)stream) : DEX_ERR_ARG; }
-int dex_asr_num_weights(const DexAsr* s) { return s ? (int)s->keys.size() : 0; }
-int dex_asr_weight_info(const DexAsr* s, int i, const char** key, int64_t shape[4], int* ndim) { return s ? s->info(i, key, shape, ndim) : DEX_ERR_ARG; }
+int dex_asr_finalize(DexAsr* s, dex_stream_t stream) { return E::finalize(s, stream, pack_all, "packing the wav2vec2 weights failed"); }
+int dex_asr_num_weights(const DexAsr* s) { return E::num_weights(s); }
+int dex_asr_weight_info(const DexAsr* s, int i, const char** key, int64_t shape[4], int* ndim) { return E::weight_info(s, i, key, shape, ndim); }
 
 int dex_asr_num_frames(const DexAsrConfig* cfg, int n_samples) {
-    const DexAsrConfig c = cfg ? *cfg : default_config();
-    if (n_samples < 0 || c.n_conv < 1 || c.n_conv > MAXC) return DEX_ERR_ARG;
-    for (int l = 0; l < c.n_conv; ++l)
-        if (c.conv_kernel[l] < 1 || c.conv_stride[l] < 1) return DEX_ERR_ARG;
-    return frames_of(c, n_samples, c.n_conv);
+    const Trunk t = trunk_of(cfg ? *cfg : default_config());
+    if (n_samples < 0 || !conv_geometry_ok(t)) return DEX_ERR_ARG;
+    return frames_of(t, n_samples, t.n_conv);
 }
 
 size_t dex_asr_workspace_bytes(const DexAsr* s, int B, int max_samples) {
     if (!s || B < 1 || B > MAX_B || max_samples < 1 || max_samples > MAX_SAMPLES) return 0;
-    if (frames_of(s->c, max_samples, s->c.n_conv) < 1 || (long)B * frames_of(s->c, max_samples, 1) > MAX_ROWS) return 0;
-    return plan(s->c, nullptr, B, max_samples).bytes;
+    if (frames_of(s->t, max_samples, s->t.n_conv) < 1 || (long)B * frames_of(s->t, max_samples, 1) > MAX_ROWS) return 0;
+    return plan(s, nullptr, B, max_samples).bytes;
 }
 
 int dex_asr_normalize(DexAsr* s, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, float* out_dev, dex_stream_t stream) {
@@ -493,7 +318,7 @@ int dex_asr_logits(DexAsr* s, const float* wav_dev, const int32_t* lengths_host,
     if (int rc = check_wavs(s, wav_dev, lengths_host, B, n_samples, &T)) return rc;
     if (!logits_dev || !workspace_dev) return s->fail(DEX_ERR_ARG, "null pointer argument");
     if (!s->finalized) return s->fail(DEX_ERR_STATE, "the wav2vec2 weights are not finalized (dex_asr_finalize)");
-    const Ws w = plan(s->c, workspace_dev, B, n_samples);
+    const Ws w = plan(s, workspace_dev, B, n_samples);
     if (workspace_bytes < w.bytes) return s->fail(DEX_ERR_WORKSPACE, "workspace too small (dex_asr_workspace_bytes)");
     const int rc = enqueue_network(s, wav_dev, lengths_host, B, n_samples, logits_dev, w, (hipStream_t)stream);
     return rc ? s->fail(rc, "kernel launch failed") : DEX_OK;
@@ -506,10 +331,10 @@ int dex_asr_transcribe(DexAsr* s, const float* wav_dev, const int32_t* lengths_h
     if (int rc = check_wavs(s, wav_dev, lengths_host, B, n_samples, &T)) return rc;
     if (!ids_dev || !counts_dev || !workspace_dev) return s->fail(DEX_ERR_ARG, "null pointer argument");
     if (!s->finalized) return s->fail(DEX_ERR_STATE, "the wav2vec2 weights are not finalized (dex_asr_finalize)");
-    const Ws w = plan(s->c, workspace_dev, B, n_samples);
+    const Ws w = plan(s, workspace_dev, B, n_samples);
     if (workspace_bytes < w.bytes) return s->fail(DEX_ERR_WORKSPACE, "workspace too small (dex_asr_workspace_bytes)");
     int rc = enqueue_network(s, wav_dev, lengths_host, B, n_samples, w.logits, w, (hipStream_t)stream);
-    if (rc == DEX_OK) rc = enqueue_ctc(w.logits, nullptr, lengths_host, &s->c, B, T, s->c.vocab, ids_dev, counts_dev, (hipStream_t)stream);
+    if (rc == DEX_OK) rc = enqueue_ctc(w.logits, nullptr, lengths_host, &s->t, B, T, s->c.vocab, ids_dev, counts_dev, (hipStream_t)stream);
     return rc ? s->fail(rc, "kernel launch failed") : DEX_OK;
 }
 

@@ -1,7 +1,9 @@
-// wav_encoder.h — what the two waveform transformers of the C ABI share (asr.hip: wav2vec 2.0 CTC; wavlm.hip: WavLM x-vector): the
-// input normalisation, the ragged-batch plan, row LayerNorm, the weight packing (weight norm folded in fp64) and the host wrappers
-// that spell a 1 x k convolution / Linear as a launch of the exact-fp32 implicit GEMM.  Every per-row sum has a fixed order that
-// does not depend on the batch.  Included by those two files only; everything has internal linkage.
+// wav_encoder.h — the kernels the two waveform transformers of the C ABI share (asr.hip: wav2vec 2.0 CTC; wavlm.hip: WavLM x-vector)
+// and their launches: the input normalisation, the ragged-batch plan, row LayerNorm, the weight packing (weight norm folded in fp64),
+// the k-split sum of fc2, and the host wrappers that spell a 1 x k convolution / Linear as a launch of the exact-fp32 implicit GEMM.
+// Every per-row sum has a fixed order that does not depend on the batch.  The host layer of the trunk the two networks share
+// (geometry, keys, packing, workspace, enqueue steps, entry points) is wav_trunk.h, which includes this file; everything has
+// internal linkage.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -22,6 +22,9 @@
 //   wavlm_mix_kernel       the softmax(layer_weights)-weighted sum of the hidden states, accumulated as the layers finish (one buffer).
 //   wavlm_pool_kernel      statistics pooling: mean and unbiased deviation per channel over the row's own TDNN frames, two passes in
 //                          fp64; a channel that is 0 on every frame has deviation exactly 0.
+// This file holds what is WavLM's own: those kernels, the padded pack of the positional convolution, the x-vector head and the
+// post-norm layer loop with its gate, biased attention and layer mix.  The trunk it shares with asr.hip - geometry, key inventory,
+// packing, workspace prefix, the enqueue steps around the layer loop, the boilerplate entry points - is wav_trunk.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -31,7 +34,7 @@
 
 #include "../../include/dex_amd.h"
 #include "kernels.h"
-#include "wav_encoder.h"
+#include "wav_trunk.h"
 #include "weight_store.h"
 
 using namespace dex::wavenc;
@@ -42,11 +45,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 static_assert(MAXC == DEX_WAVLM_MAX_CONV, "ConvSpec holds DEX_WAVLM_MAX_CONV layers");
 constexpr int MAXT = DEX_WAVLM_MAX_TDNN;
 constexpr int MAXF = DEX_WAVLM_MAX_FRAMES;
-constexpr int F0 = 8;                    // frames per workgroup of the first convolution
-constexpr int K0_MAX = 16, S0_MAX = 16;  // its kernel and stride bounds (taps in registers, window in LDS)
-constexpr int C0_MAX = 512;              // its channels: two per thread
-constexpr int MAX_B = 1024;
-constexpr long MAX_ROWS = 1L << 26;      // B x frames of the first layer
 constexpr int GN_CHUNK = 512;            // frames per partial sum of the group norm
 
 struct Conv0P { const float* x; long x_ld; const float* w; const float* bias; float* out; int T0, C, k, s; };
@@ -405,24 +403,12 @@ __global__ __launch_bounds__(256) void wavlm_pad_vec_kernel(const float* src, fl
     dst[i] = c < cg ? src[g * cg + c] : 0.f;
 }
 
-thread_local std::string g_create_err;
-
-int create_fail(const char* fmt, const char* field) {
-    char buf[256];
-    snprintf(buf, sizeof buf, fmt, field);
-    g_create_err = buf;
-    return DEX_ERR_ARG;
-}
-
 DexWavlmConfig default_config() {
     DexWavlmConfig c;
     std::memset(&c, 0, sizeof c);
-    const int k[7] = {10, 3, 3, 3, 3, 2, 2}, s[7] = {5, 2, 2, 2, 2, 2, 2};
-    c.n_conv = 7;
-    for (int i = 0; i < 7; ++i) { c.conv_dim[i] = 512; c.conv_kernel[i] = k[i]; c.conv_stride[i] = s[i]; }
+    default_trunk_geometry(c);
     c.conv_bias = 0; c.feat_extract_norm_group = 1;
     c.hidden = 768; c.n_layers = 12; c.n_heads = 12; c.intermediate = 3072; c.do_stable_layer_norm = 0;
-    c.num_conv_pos_embeddings = 128; c.num_conv_pos_embedding_groups = 16; c.layer_norm_eps = 1e-5f;
     c.num_buckets = 320; c.max_bucket_distance = 800; c.use_weighted_layer_sum = 1;
     const int td[5] = {512, 512, 512, 512, 1500}, tk[5] = {5, 3, 3, 1, 1}, tl[5] = {1, 2, 3, 1, 1};
     c.n_tdnn = 5;
@@ -431,27 +417,11 @@ DexWavlmConfig default_config() {
     return c;
 }
 
-// the family that is built; names the first field outside it
+// the family that is built; names the first field outside it.  The positional groups are padded for the GEMM: any multiple of 4
 int check_config(const DexWavlmConfig& c) {
     if (c.feat_extract_norm_group != 1) return create_fail("%s: only 'group' is built", "feat_extract_norm");
     if (c.do_stable_layer_norm != 0) return create_fail("%s: only False is built", "do_stable_layer_norm");
-    if (c.n_conv < 1 || c.n_conv > MAXC) return create_fail("%s: 1 .. 8 feature-extractor layers", "conv_dim");
-    for (int l = 0; l < c.n_conv; ++l) {
-        if (c.conv_dim[l] < 32 || c.conv_dim[l] % 32 || c.conv_dim[l] > 4096) return create_fail("%s: every width a multiple of 32 in 32 .. 4096", "conv_dim");
-        if (c.conv_kernel[l] < 1 || c.conv_kernel[l] > 64) return create_fail("%s: 1 .. 64", "conv_kernel");
-        if (c.conv_stride[l] < 1 || c.conv_stride[l] > 64) return create_fail("%s: 1 .. 64", "conv_stride");
-    }
-    if (c.conv_dim[0] > C0_MAX) return create_fail("%s: the first layer has at most 512 channels", "conv_dim");
-    if (c.conv_kernel[0] > K0_MAX) return create_fail("%s: the first layer's kernel is at most 16", "conv_kernel");
-    if (c.conv_stride[0] > S0_MAX) return create_fail("%s: the first layer's stride is at most 16", "conv_stride");
-    if (c.n_heads < 1 || c.n_heads > 1024) return create_fail("%s: 1 .. 1024", "num_attention_heads");
-    if (c.hidden < 64 || c.hidden > 16384 || c.hidden != 64 * c.n_heads) return create_fail("%s: hidden_size / num_attention_heads must be 64", "hidden_size");
-    if (c.n_layers < 1 || c.n_layers > 256) return create_fail("%s: 1 .. 256", "num_hidden_layers");
-    if (c.intermediate < 32 || c.intermediate % 32 || c.intermediate > 65536) return create_fail("%s: a multiple of 32 up to 65536", "intermediate_size");
-    const int G = c.num_conv_pos_embedding_groups, K = c.num_conv_pos_embeddings;
-    if (G < 1 || G > 16 || c.hidden % G || (c.hidden / G) % 4) return create_fail("%s: 1 .. 16 groups of a multiple of 4 channels", "num_conv_pos_embedding_groups");
-    if (K < 2 || K % 2 || K > 1024) return create_fail("%s: even, 2 .. 1024", "num_conv_pos_embeddings");
-    if (!(c.layer_norm_eps > 0.f) || !(c.layer_norm_eps < 1.f)) return create_fail("%s: in (0, 1)", "layer_norm_eps");
+    if (int rc = check_trunk(trunk_of(c), 4)) return rc;
     if (c.num_buckets < 4 || c.num_buckets % 4 || c.num_buckets > 65536) return create_fail("%s: a multiple of 4 in 4 .. 65536", "num_buckets");
     if (c.max_bucket_distance <= c.num_buckets / 4 || c.max_bucket_distance > (1 << 24)) return create_fail("%s: above num_buckets / 4", "max_bucket_distance");
     if (c.n_tdnn < 1 || c.n_tdnn > MAXT) return create_fail("%s: 1 .. 8 TDNN layers", "tdnn_dim");
@@ -467,34 +437,20 @@ int check_config(const DexWavlmConfig& c) {
 
 // the geometry alone (the host-only entry points take configs that were never created)
 bool geometry_ok(const DexWavlmConfig& c) {
-    if (c.n_conv < 1 || c.n_conv > MAXC || c.n_tdnn < 1 || c.n_tdnn > MAXT) return false;
-    for (int l = 0; l < c.n_conv; ++l)
-        if (c.conv_kernel[l] < 1 || c.conv_stride[l] < 1) return false;
+    if (!conv_geometry_ok(trunk_of(c)) || c.n_tdnn < 1 || c.n_tdnn > MAXT) return false;
     for (int i = 0; i < c.n_tdnn; ++i)
         if (c.tdnn_kernel[i] < 1 || c.tdnn_dilation[i] < 1) return false;
     return true;
 }
 
-int fc2_ksplit(const DexWavlmConfig& c) {
-    const int r = c.intermediate / c.hidden;
-    return (r * c.hidden == c.intermediate && (r == 2 || r == 4 || r == 8) && (c.intermediate / r) % 32 == 0) ? r : 1;
-}
-
-int frames_of(const DexWavlmConfig& c, long n, int upto) {
-    for (int l = 0; l < upto; ++l) n = n >= c.conv_kernel[l] ? (n - c.conv_kernel[l]) / c.conv_stride[l] + 1 : 0;
-    return (int)n;
-}
 // frames the TDNN layers take off a row
 int tdnn_shrink(const DexWavlmConfig& c) {
     int s = 0;
     for (int i = 0; i < c.n_tdnn; ++i) s += (c.tdnn_kernel[i] - 1) * c.tdnn_dilation[i];
     return s;
 }
-long min_samples(const DexWavlmConfig& c) {
-    long n = tdnn_shrink(c) + 2;                            // two frames after the TDNN layers: the unbiased deviation exists
-    for (int l = c.n_conv - 1; l >= 0; --l) n = (n - 1) * c.conv_stride[l] + c.conv_kernel[l];
-    return n;
-}
+// two frames after the TDNN layers: the unbiased deviation exists
+long min_samples(const DexWavlmConfig& c) { return samples_for(trunk_of(c), tdnn_shrink(c) + 2); }
 // _relative_positions_bucket of the distance d = key - query, in fp64
 int bucket_of(const DexWavlmConfig& c, long d) {
     const int nb = c.num_buckets / 2, max_exact = nb / 2;
@@ -507,60 +463,39 @@ int bucket_of(const DexWavlmConfig& c, long d) {
 }
 int pad32(int n) { return (n + 31) & ~31; }
 // channels of a positional-convolution group as the GEMM takes them
-int pos_group_pad(const DexWavlmConfig& c) { const int cg = c.hidden / c.num_conv_pos_embedding_groups; return cg % 32 ? (cg + 63) & ~63 : cg; }
+int pos_group_pad(const Trunk& t) { const int cg = t.hidden / t.pos_groups; return cg % 32 ? (cg + 63) & ~63 : cg; }
+
+const TrunkKeys KEYS("wavlm.");
+std::string tk(int i, const char* what) { return "tdnn." + std::to_string(i) + ".kernel." + what; }
 
 }  // namespace
 
 struct DexWavlm : dex::WeightStore {
     DexWavlm() : WeightStore("wavlm ") {}
     DexWavlmConfig c;
-    const float* conv_w[MAXC] = {}; const float* conv_b[MAXC] = {};
-    const float *gn_g = nullptr, *gn_b = nullptr;
-    const float *fp_g = nullptr, *fp_be = nullptr, *fp_w = nullptr, *fp_b = nullptr, *pos_w = nullptr, *pos_b = nullptr;
-    const float *enc_g = nullptr, *enc_be = nullptr, *rel_embed = nullptr, *lw = nullptr;
+    Trunk t;
+    TrunkWeights w;                         // conv_g[0] / conv_be[0]: the group norm's affine; pos_w / pos_b: the padded groups
+    struct Gate { const float *gw, *gb, *gc; };
+    std::vector<Gate> gates;                // gru_rel_pos_linear and gru_rel_pos_const per encoder layer
+    const float *rel_embed = nullptr, *lw = nullptr;
     const int* buckets = nullptr;
     std::vector<int32_t> buckets_host;
-    struct Layer { const float *gw, *gb, *gc, *wqkv, *bqkv, *wo, *bo, *ln1g, *ln1b, *w1, *b1, *w2, *b2, *ln2g, *ln2b; };
-    std::vector<Layer> layers;
     const float *proj_w = nullptr, *proj_b = nullptr, *emb_w = nullptr, *emb_b = nullptr;
     const float* tdnn_w[MAXT] = {}; const float* tdnn_b[MAXT] = {};
 };
 
 namespace {
 
-const std::string FE = "wavlm.feature_extractor.conv_layers.", ENC = "wavlm.encoder.", FP = "wavlm.feature_projection.";
-std::string lk(int l, const char* what) { return ENC + "layers." + std::to_string(l) + "." + what; }
-std::string ck(int l, const char* what) { return FE + std::to_string(l) + "." + what; }
-std::string tk(int i, const char* what) { return "tdnn." + std::to_string(i) + ".kernel." + what; }
-
 void register_keys(DexWavlm* s) {
     const DexWavlmConfig& c = s->c;
-    for (int l = 0; l < c.n_conv; ++l) {
-        s->add(ck(l, "conv.weight"), {c.conv_dim[l], l ? c.conv_dim[l - 1] : 1, c.conv_kernel[l]});
-        if (c.conv_bias) s->add(ck(l, "conv.bias"), {c.conv_dim[l]});
-        if (l == 0) { s->add(ck(0, "layer_norm.weight"), {c.conv_dim[0]}); s->add(ck(0, "layer_norm.bias"), {c.conv_dim[0]}); }
-    }
-    const int C = c.conv_dim[c.n_conv - 1], H = c.hidden, I = c.intermediate;
-    s->add(FP + "layer_norm.weight", {C}); s->add(FP + "layer_norm.bias", {C});
-    s->add(FP + "projection.weight", {H, C}); s->add(FP + "projection.bias", {H});
-    s->add(ENC + "pos_conv_embed.conv.bias", {H});
-    s->add(ENC + "pos_conv_embed.conv.weight_g", {1, 1, c.num_conv_pos_embeddings});
-    s->add(ENC + "pos_conv_embed.conv.weight_v", {H, H / c.num_conv_pos_embedding_groups, c.num_conv_pos_embeddings});
-    s->add(ENC + "layer_norm.weight", {H}); s->add(ENC + "layer_norm.bias", {H});
-    for (int l = 0; l < c.n_layers; ++l) {
-        for (const char* pr : {"attention.q_proj", "attention.k_proj", "attention.v_proj", "attention.out_proj"}) {
-            s->add(lk(l, pr) + ".weight", {H, H}); s->add(lk(l, pr) + ".bias", {H});
-        }
-        s->add(lk(l, "attention.gru_rel_pos_const"), {1, c.n_heads, 1, 1});
-        s->add(lk(l, "attention.gru_rel_pos_linear.weight"), {8, 64}); s->add(lk(l, "attention.gru_rel_pos_linear.bias"), {8});
-        if (l == 0) s->add(lk(0, "attention.rel_attn_embed.weight"), {c.num_buckets, c.n_heads});
-        s->add(lk(l, "layer_norm.weight"), {H}); s->add(lk(l, "layer_norm.bias"), {H});
-        s->add(lk(l, "feed_forward.intermediate_dense.weight"), {I, H}); s->add(lk(l, "feed_forward.intermediate_dense.bias"), {I});
-        s->add(lk(l, "feed_forward.output_dense.weight"), {H, I}); s->add(lk(l, "feed_forward.output_dense.bias"), {H});
-        s->add(lk(l, "final_layer_norm.weight"), {H}); s->add(lk(l, "final_layer_norm.bias"), {H});
-    }
+    s->t = trunk_of(c);
+    register_trunk_keys(s, KEYS, s->t, false, [&](int l) {
+        s->add(KEYS.lk(l, "attention.gru_rel_pos_const"), {1, c.n_heads, 1, 1});
+        s->add(KEYS.lk(l, "attention.gru_rel_pos_linear.weight"), {8, 64}); s->add(KEYS.lk(l, "attention.gru_rel_pos_linear.bias"), {8});
+        if (l == 0) s->add(KEYS.lk(0, "attention.rel_attn_embed.weight"), {c.num_buckets, c.n_heads});
+    });
     if (c.use_weighted_layer_sum) s->add("layer_weights", {c.n_layers + 1});
-    s->add("projector.weight", {c.tdnn_dim[0], H}); s->add("projector.bias", {c.tdnn_dim[0]});
+    s->add("projector.weight", {c.tdnn_dim[0], c.hidden}); s->add("projector.bias", {c.tdnn_dim[0]});
     for (int i = 0; i < c.n_tdnn; ++i) {
         const int din = c.tdnn_dim[i ? i - 1 : 0];
         s->add(tk(i, "weight"), {c.tdnn_dim[i], din * c.tdnn_kernel[i]}); s->add(tk(i, "bias"), {c.tdnn_dim[i]});
@@ -582,52 +517,26 @@ const float* pad_vec(DexWavlm* s, const std::string& key, int G, int cg, int cgp
     return d;
 }
 
-int finalize(DexWavlm* s, hipStream_t st) {
-    if (int rc = s->begin_finalize()) return rc;
+int pack_all(DexWavlm* s, hipStream_t st) {
     const DexWavlmConfig& c = s->c;
-    const int H = c.hidden, I = c.intermediate, C = c.conv_dim[c.n_conv - 1];
-    for (int l = 0; l < c.n_conv; ++l) {
-        s->conv_w[l] = l ? pack(s, ck(l, "conv.weight"), 1, c.conv_dim[l], c.conv_dim[l - 1], c.conv_kernel[l], nullptr, st) : s->R(ck(0, "conv.weight"));
-        s->conv_b[l] = c.conv_bias ? s->R(ck(l, "conv.bias")) : nullptr;
-    }
-    s->gn_g = s->R(ck(0, "layer_norm.weight")); s->gn_b = s->R(ck(0, "layer_norm.bias"));
-    s->fp_g = s->R(FP + "layer_norm.weight"); s->fp_be = s->R(FP + "layer_norm.bias");
-    s->fp_w = pack(s, FP + "projection.weight", 1, H, C, 1, nullptr, st); s->fp_b = s->R(FP + "projection.bias");
-    {
-        const int G = c.num_conv_pos_embedding_groups, K = c.num_conv_pos_embeddings, cg = H / G, cgp = pos_group_pad(c);
-        double* scale = (double*)s->alloc(2L * K);
-        float* pw = s->alloc((long)G * K * cgp * cgp);
-        if (scale && pw) {
-            hipLaunchKernelGGL(asr_wn_scale_kernel, dim3(K), dim3(256), 0, st, s->R(ENC + "pos_conv_embed.conv.weight_v"),
-                               s->R(ENC + "pos_conv_embed.conv.weight_g"), scale, (long)H * cg, K);
-            const long n = (long)G * K * cgp * cgp;
-            hipLaunchKernelGGL(wavlm_pack_pos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s->R(ENC + "pos_conv_embed.conv.weight_v"), scale,
+    const Trunk& t = s->t;
+    // the positional convolution with its groups padded to what the GEMM takes (zeros in the padding)
+    auto pack_pos = [&](const double* scale) {
+        const int G = t.pos_groups, K = t.pos_k, cg = t.hidden / G, cgp = pos_group_pad(t);
+        const long n = (long)G * K * cgp * cgp;
+        float* pw = s->alloc(n);
+        if (scale && pw)
+            hipLaunchKernelGGL(wavlm_pack_pos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s->R(KEYS.ENC + "pos_conv_embed.conv.weight_v"), scale,
                                pw, G, cg, cgp, K);
-        }
-        s->pos_w = pw;
-        s->pos_b = pad_vec(s, ENC + "pos_conv_embed.conv.bias", G, cg, cgp, st);
-    }
-    s->enc_g = s->R(ENC + "layer_norm.weight"); s->enc_be = s->R(ENC + "layer_norm.bias");
-    s->rel_embed = s->R(lk(0, "attention.rel_attn_embed.weight"));
-    s->layers.assign(c.n_layers, DexWavlm::Layer{});
-    for (int l = 0; l < c.n_layers && s->alloc_rc == DEX_OK; ++l) {
-        DexWavlm::Layer& L = s->layers[l];
-        float* wqkv = s->alloc(3L * H * H); float* bqkv = s->alloc(3L * H);
-        if (!wqkv || !bqkv) break;
-        const char* pr[3] = {"attention.q_proj", "attention.k_proj", "attention.v_proj"};
-        for (int j = 0; j < 3; ++j) {
-            pack_into(s->R(lk(l, pr[j]) + ".weight"), wqkv, 1, H, H, 1, 3 * H, j * H, nullptr, st);
-            DEX_HIPCHK(s, hipMemcpyAsync(bqkv + (long)j * H, s->R(lk(l, pr[j]) + ".bias"), H * sizeof(float), hipMemcpyDeviceToDevice, st));
-        }
-        L.wqkv = wqkv; L.bqkv = bqkv;
-        L.gw = s->R(lk(l, "attention.gru_rel_pos_linear.weight")); L.gb = s->R(lk(l, "attention.gru_rel_pos_linear.bias"));
-        L.gc = s->R(lk(l, "attention.gru_rel_pos_const"));
-        L.wo = pack(s, lk(l, "attention.out_proj") + ".weight", 1, H, H, 1, nullptr, st); L.bo = s->R(lk(l, "attention.out_proj") + ".bias");
-        L.ln1g = s->R(lk(l, "layer_norm.weight")); L.ln1b = s->R(lk(l, "layer_norm.bias"));
-        L.w1 = pack(s, lk(l, "feed_forward.intermediate_dense.weight"), 1, I, H, 1, nullptr, st); L.b1 = s->R(lk(l, "feed_forward.intermediate_dense.bias"));
-        L.w2 = pack(s, lk(l, "feed_forward.output_dense.weight"), 1, H, I, 1, nullptr, st); L.b2 = s->R(lk(l, "feed_forward.output_dense.bias"));
-        L.ln2g = s->R(lk(l, "final_layer_norm.weight")); L.ln2b = s->R(lk(l, "final_layer_norm.bias"));
-    }
+        s->w.pos_w = pw;
+        s->w.pos_b = pad_vec(s, KEYS.ENC + "pos_conv_embed.conv.bias", G, cg, cgp, st);
+    };
+    if (int rc = finalize_trunk(s, KEYS, t, false, s->w, pack_pos, st)) return rc;
+    s->rel_embed = s->R(KEYS.lk(0, "attention.rel_attn_embed.weight"));
+    s->gates.clear();
+    for (int l = 0; l < t.n_layers; ++l)
+        s->gates.push_back({s->R(KEYS.lk(l, "attention.gru_rel_pos_linear.weight")), s->R(KEYS.lk(l, "attention.gru_rel_pos_linear.bias")),
+                            s->R(KEYS.lk(l, "attention.gru_rel_pos_const"))});
     if (c.use_weighted_layer_sum) {
         float* lw = s->alloc(up64(c.n_layers + 1));
         if (lw) hipLaunchKernelGGL(wavlm_softmax_kernel, dim3(1), dim3(64), 0, st, s->R("layer_weights"), lw, c.n_layers + 1);
@@ -642,7 +551,7 @@ int finalize(DexWavlm* s, hipStream_t st) {
         if (bk) DEX_HIPCHK(s, hipMemcpyAsync(bk, s->buckets_host.data(), (2 * MAXF - 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
         s->buckets = bk;
     }
-    s->proj_w = pack_pad(s, "projector.weight", c.tdnn_dim[0], c.tdnn_dim[0], H, H, 1, st); s->proj_b = s->R("projector.bias");
+    s->proj_w = pack_pad(s, "projector.weight", c.tdnn_dim[0], c.tdnn_dim[0], t.hidden, t.hidden, 1, st); s->proj_b = s->R("projector.bias");
     for (int i = 0; i < c.n_tdnn; ++i) {
         const int din = c.tdnn_dim[i ? i - 1 : 0], K = din * c.tdnn_kernel[i], N = c.tdnn_dim[i], Np = pad32(N);
         s->tdnn_w[i] = pack_pad(s, tk(i, "weight"), N, Np, K, K, 1, st);
@@ -653,82 +562,44 @@ int finalize(DexWavlm* s, hipStream_t st) {
         s->emb_w = pack_pad(s, "feature_extractor.weight", c.xvector_output_dim, c.xvector_output_dim, Cl, pad32(Cl), 2, st);
         s->emb_b = s->R("feature_extractor.bias");
     }
-    if (s->alloc_rc != DEX_OK) return s->alloc_rc;
-    if (hipGetLastError() != hipSuccess) return s->fail(DEX_ERR_HIP, "packing the wavlm weights failed");
-    s->finalized = true;
     return DEX_OK;
 }
 
-// workspace (floats, every piece a multiple of 64): xn [B][n] | fa (even layers) | fb (odd layers) | h, y, mix [B][T][H] | qkv [B][T][3H] |
-// ff [B][T][I] | part [ksplit][B][T][H] | yp, pp [B][T][G cgp] (padded positional groups) | gate [B][heads][T] | rel [heads][2T - 1] |
-// mask [B][T] | gnpart (fp64) [B][chunks][C_0] | gnmean (fp64) [B][C_0] | gnrstd [B][C_0] | ta, tb [B][T][max tdnn width] |
-// stats [B][2 Cpad] | lens (int) [n_conv + 1][B]
-struct Ws { float *xn, *fa, *fb, *h, *y, *mix, *qkv, *ff, *part, *yp, *pp, *gate, *rel, *mask, *gnrstd, *ta, *tb, *stats; double *gnpart, *gnmean;
-            int* lens; size_t bytes; int Tl[MAXC]; int T, nchunk; };
-Ws plan(const DexWavlmConfig& c, void* ws, long B, long n) {
+// workspace: the trunk's prefix | mix [B][T][H] | yp, pp [B][T][G cgp] (padded positional groups) | gate [B][heads][T] |
+// rel [heads][2T - 1] | mask [B][T] | gnpart (fp64) [B][chunks][C_0] | gnmean (fp64) [B][C_0] | gnrstd [B][C_0] |
+// ta, tb [B][T][max tdnn width] | stats [B][2 Cpad] | lens (int) [n_conv + 1][B]
+struct Ws : TrunkWs { float *mix, *yp, *pp, *gate, *rel, *gnrstd, *ta, *tb, *stats; double *gnpart, *gnmean; size_t bytes; int nchunk; };
+Ws plan(const DexWavlm* s, void* ws, long B, long n) {
+    const DexWavlmConfig& c = s->c;
     Ws w{};
-    long fa = 0, fb = 0;
-    for (int l = 0; l < c.n_conv; ++l) {
-        w.Tl[l] = frames_of(c, n, l + 1);
-        long& m = (l & 1) ? fb : fa;
-        const long sz = (long)w.Tl[l] * c.conv_dim[l];
-        m = sz > m ? sz : m;
-    }
-    w.T = w.Tl[c.n_conv - 1];
+    Taker tk(ws);
+    plan_trunk(s->t, tk, B, n, w);
     w.nchunk = (w.Tl[0] + GN_CHUNK - 1) / GN_CHUNK;
     const long T = w.T, H = c.hidden;
-    const long last = T * c.conv_dim[c.n_conv - 1];        // the LayerNorm of the feature projection writes the OTHER ping-pong buffer
-    fa = fa > last ? fa : last; fb = fb > last ? fb : last;
     long tdw = 0;
     for (int i = 0; i < c.n_tdnn; ++i) tdw = pad32(c.tdnn_dim[i]) > tdw ? pad32(c.tdnn_dim[i]) : tdw;
-    const long cgp = pos_group_pad(c), G = c.num_conv_pos_embedding_groups, padded = cgp * G != H;
-    float* f = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    long off = 0;
-    auto take = [&](long cnt) { float* p = f + off; off += up64(cnt); return p; };
-    w.xn = take(B * n); w.fa = take(B * fa); w.fb = take(B * fb);
-    w.h = take(B * T * H); w.y = take(B * T * H); w.mix = take(B * T * H); w.qkv = take(B * T * 3 * H); w.ff = take(B * T * c.intermediate);
-    w.part = take(fc2_ksplit(c) > 1 ? fc2_ksplit(c) * B * T * H : 0);
-    w.yp = take(padded ? B * T * G * cgp : 0); w.pp = take(padded ? B * T * G * cgp : 0);
-    w.gate = take(B * c.n_heads * T); w.rel = take((long)c.n_heads * (2 * T - 1)); w.mask = take(B * T);
-    w.gnpart = (double*)take(2 * B * w.nchunk * c.conv_dim[0]); w.gnmean = (double*)take(2 * B * c.conv_dim[0]); w.gnrstd = take(B * c.conv_dim[0]);
-    w.ta = take(B * T * tdw); w.tb = take(B * T * tdw); w.stats = take(B * 2 * pad32(c.tdnn_dim[c.n_tdnn - 1]));
-    w.lens = (int*)take((long)(c.n_conv + 1) * B);
-    w.bytes = (size_t)off * sizeof(float) + 256;
+    const long cgp = pos_group_pad(s->t), G = s->t.pos_groups, padded = cgp * G != H;
+    w.mix = tk.take(B * T * H);
+    w.yp = tk.take(padded ? B * T * G * cgp : 0); w.pp = tk.take(padded ? B * T * G * cgp : 0);
+    w.gate = tk.take(B * c.n_heads * T); w.rel = tk.take((long)c.n_heads * (2 * T - 1)); w.mask = tk.take(B * T);
+    w.gnpart = (double*)tk.take(2 * B * w.nchunk * c.conv_dim[0]); w.gnmean = (double*)tk.take(2 * B * c.conv_dim[0]); w.gnrstd = tk.take(B * c.conv_dim[0]);
+    w.ta = tk.take(B * T * tdw); w.tb = tk.take(B * T * tdw); w.stats = tk.take(B * 2 * pad32(c.tdnn_dim[c.n_tdnn - 1]));
+    w.lens = (int*)tk.take((long)(c.n_conv + 1) * B);
+    w.bytes = tk.bytes();
     return w;
-}
-
-// the shared argument checks of the calls that take wavs; frames of the padded batch into *T
-int check_wavs(DexWavlm* s, const void* wav, const int32_t* lengths_host, int B, int n_samples, int* T) {
-    if (!wav || !lengths_host) return s->fail(DEX_ERR_ARG, "null pointer argument");
-    if (B < 1 || B > MAX_B) return s->fail(DEX_ERR_ARG, "B must lie in [1, %d]", MAX_B);
-    if (n_samples < 1) return s->fail(DEX_ERR_ARG, "n_samples must be >= 1");
-    *T = frames_of(s->c, n_samples, s->c.n_conv);
-    if (*T > MAXF) return s->fail(DEX_ERR_ARG, "%d samples are %d frames: one call takes at most %d", n_samples, *T, MAXF);
-    const long need = min_samples(s->c);
-    for (int b = 0; b < B; ++b) {
-        if (lengths_host[b] < 1 || lengths_host[b] > n_samples) return s->fail(DEX_ERR_ARG, "row lengths must lie in [1, n_samples]");
-        if (lengths_host[b] < need)
-            return s->fail(DEX_ERR_ARG, "row %d has %d samples: too short, statistics pooling needs two TDNN frames (%ld samples)", b, lengths_host[b], need);
-    }
-    if ((long)B * frames_of(s->c, n_samples, 1) > MAX_ROWS) return s->fail(DEX_ERR_ARG, "B x frames must not exceed %ld", MAX_ROWS);
-    return DEX_OK;
 }
 
 // everything up to the layer-mixed hidden states, stored at `hidden` [B][T][H] (0 past a row's frames)
 int enqueue_encoder(DexWavlm* s, const float* wav, const int32_t* lengths_host, int B, int n, int do_normalize, float* hidden, const Ws& w, hipStream_t st) {
     const DexWavlmConfig& c = s->c;
-    const int T = w.T, H = c.hidden, nc = c.n_conv;
-    ConvSpec cs;
-    std::memset(&cs, 0, sizeof cs);
-    cs.n = nc;
-    for (int l = 0; l < nc; ++l) { cs.k[l] = c.conv_kernel[l]; cs.s[l] = c.conv_stride[l]; }
-    enqueue_plan(cs, lengths_host, B, T, w.lens, w.mask, st);
-    if (do_normalize) enqueue_norm(wav, lengths_host, B, n, w.xn, st);
-    // feature extractor: layer l lives in fa (l even) / fb (l odd)
-    {
+    const Trunk& t = s->t;
+    const TrunkWeights& W = s->w;
+    const int T = w.T, H = c.hidden;
+    enqueue_front(t, w, wav, lengths_host, B, n, do_normalize, st);
+    {   // layer 0: the raw convolution, then the group norm over each row's own frames, GELU
         const int T0 = w.Tl[0], C0 = c.conv_dim[0];
         const int* len0 = w.lens + B;
-        const Conv0P p{do_normalize ? w.xn : wav, (long)n, s->conv_w[0], s->conv_b[0], w.fa, T0, C0, c.conv_kernel[0], c.conv_stride[0]};
+        const Conv0P p{do_normalize ? w.xn : wav, (long)n, W.conv_w[0], W.conv_b[0], w.fa, T0, C0, c.conv_kernel[0], c.conv_stride[0]};
         hipLaunchKernelGGL(wavlm_conv0_kernel, dim3((T0 + F0 - 1) / F0, B), dim3(256), 0, st, p);
         const dim3 pg(w.nchunk, (C0 + 63) / 64, B), fg((C0 + 255) / 256, B);
         hipLaunchKernelGGL(wavlm_gn_part_kernel<false>, pg, dim3(256), 0, st, w.fa, T0, C0, len0, nullptr, w.gnpart);
@@ -736,33 +607,23 @@ int enqueue_encoder(DexWavlm* s, const float* wav, const int32_t* lengths_host, 
         hipLaunchKernelGGL(wavlm_gn_part_kernel<true>, pg, dim3(256), 0, st, w.fa, T0, C0, len0, w.gnmean, w.gnpart);
         hipLaunchKernelGGL(wavlm_gn_final_kernel<true>, fg, dim3(256), 0, st, w.gnpart, w.nchunk, T0, C0, len0, nullptr, w.gnrstd, 1e-5f);
         const long n4 = (long)B * T0 * C0 / 4;
-        hipLaunchKernelGGL(wavlm_gn_apply_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, w.fa, T0, C0, len0, w.gnmean, w.gnrstd, s->gn_g,
-                           s->gn_b, n4);
+        hipLaunchKernelGGL(wavlm_gn_apply_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, w.fa, T0, C0, len0, w.gnmean, w.gnrstd, W.conv_g[0],
+                           W.conv_be[0], n4);
     }
-    float* cur = w.fa;
-    for (int l = 1; l < nc; ++l) {
-        float* nxt = (l & 1) ? w.fb : w.fa;
-        gemm(cur, c.conv_dim[l - 1], w.Tl[l - 1], c.conv_dim[l - 1], c.conv_kernel[l], c.conv_stride[l], 0, w.Tl[l], s->conv_w[l], c.conv_dim[l], 1,
-             s->conv_b[l], nxt, 1, nullptr, nullptr, B, st);
-        cur = nxt;
-    }
+    enqueue_projection(t, W, w, enqueue_conv_tail<false>(t, W, w, B, 1, st), B, st);
     const long rows = (long)B * T;
-    const int C = c.conv_dim[nc - 1];
-    float* fpn = cur == w.fa ? w.fb : w.fa;
-    layer_norm<false>(cur, fpn, rows, T, C, s->fp_g, s->fp_be, c.layer_norm_eps, nullptr, st);
-    linear(fpn, C, s->fp_w, H, s->fp_b, w.y, 0, nullptr, w.mask, T, B, st);            // rows at or past the frame count: 0
     // h = LN(y + GELU(pos_conv(y)) without its last frame)
     {
-        const int G = c.num_conv_pos_embedding_groups, K = c.num_conv_pos_embeddings, cg = H / G, cgp = pos_group_pad(c);
+        const int G = t.pos_groups, K = t.pos_k, cg = H / G, cgp = pos_group_pad(t);
         if (cgp == cg) {
-            gemm(w.y, H, T, cg, K, 1, -(K / 2), T, s->pos_w, cg, G, s->pos_b, w.h, 1, w.y, nullptr, B, st);
+            gemm(w.y, H, T, cg, K, 1, -(K / 2), T, W.pos_w, cg, G, W.pos_b, w.h, 1, w.y, nullptr, B, st);
         } else {
             dex::launch_group_pad(w.y, w.yp, rows, G, cg, cgp, st);
-            gemm(w.yp, G * cgp, T, cgp, K, 1, -(K / 2), T, s->pos_w, cgp, G, s->pos_b, w.pp, 1, nullptr, nullptr, B, st);
+            gemm(w.yp, G * cgp, T, cgp, K, 1, -(K / 2), T, W.pos_w, cgp, G, W.pos_b, w.pp, 1, nullptr, nullptr, B, st);
             hipLaunchKernelGGL(wavlm_unpad_add_kernel, dim3((unsigned)((rows * H + 255) / 256)), dim3(256), 0, st, w.y, w.pp, w.h, rows, G, cg, cgp);
         }
     }
-    layer_norm<false>(w.h, w.h, rows, T, H, s->enc_g, s->enc_be, c.layer_norm_eps, nullptr, st);
+    layer_norm<false>(w.h, w.h, rows, T, H, W.enc_g, W.enc_be, c.layer_norm_eps, nullptr, st);
     const long n4 = rows * H / 4;
     const dim3 mg((unsigned)((n4 + 255) / 256));
     auto mix = [&](int l, bool last) {
@@ -773,25 +634,18 @@ int enqueue_encoder(DexWavlm* s, const float* wav, const int32_t* lengths_host, 
     };
     mix(0, false);
     hipLaunchKernelGGL(wavlm_rel_kernel, dim3((2 * T - 1 + 255) / 256, c.n_heads), dim3(256), 0, st, s->rel_embed, s->buckets, w.rel, T, c.n_heads);
-    const int* kv_len = w.lens + (long)nc * B;
-    const int ks = fc2_ksplit(c);
-    for (int l = 0; l < c.n_layers; ++l) {
-        const DexWavlm::Layer& L = s->layers[l];
-        hipLaunchKernelGGL(wavlm_gate_kernel, dim3((unsigned)((rows * c.n_heads + 255) / 256)), dim3(256), 0, st, w.h, L.gw, L.gb, L.gc, w.gate, B, T,
+    const int* kv_len = w.lens + (long)t.n_conv * B;
+    for (int l = 0; l < c.n_layers; ++l) {                                              // post-norm: h = LN(h + attn(h)); h = LN(h + ffn(h))
+        const TrunkWeights::Layer& L = W.layers[l];
+        const DexWavlm::Gate& g = s->gates[l];
+        hipLaunchKernelGGL(wavlm_gate_kernel, dim3((unsigned)((rows * c.n_heads + 255) / 256)), dim3(256), 0, st, w.h, g.gw, g.gb, g.gc, w.gate, B, T,
                            c.n_heads);
         linear(w.h, H, L.wqkv, 3 * H, L.bqkv, w.qkv, 0, nullptr, nullptr, T, B, st);
         const AttnBiasP a{w.qkv, 3 * H, (long)T * 3 * H, w.y, H, (long)T * H, T, kv_len, c.n_heads, w.rel, w.gate};
         hipLaunchKernelGGL(wavlm_attn_kernel, dim3((T + 31) / 32, c.n_heads, B), dim3(AT_NW * 64), 0, st, a);
         linear(w.y, H, L.wo, H, L.bo, w.h, 0, w.h, nullptr, T, B, st);                  // h += out_proj(attn)
         layer_norm<false>(w.h, w.h, rows, T, H, L.ln1g, L.ln1b, c.layer_norm_eps, nullptr, st);
-        linear(w.h, H, L.w1, c.intermediate, L.b1, w.ff, 1, nullptr, nullptr, T, B, st);
-        if (ks > 1) {                                                                   // h += fc2(GELU(fc1)), K in ks slabs
-            gemm(w.ff, c.intermediate, T, c.intermediate, 1, 1, 0, T, L.w2, H, 1, nullptr, w.part, 0, nullptr, nullptr, B, st, ks);
-            hipLaunchKernelGGL(asr_ksum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, (const float4*)w.part, n4, ks, (const float4*)L.b2,
-                               H / 4, (float4*)w.h);
-        } else {
-            linear(w.ff, c.intermediate, L.w2, H, L.b2, w.h, 0, w.h, nullptr, T, B, st);
-        }
+        enqueue_ffn(t, L, w, w.h, B, st);
         layer_norm<false>(w.h, w.h, rows, T, H, L.ln2g, L.ln2b, c.layer_norm_eps, nullptr, st);
         mix(l + 1, l + 1 == c.n_layers);
     }
@@ -820,10 +674,12 @@ int enqueue_head(DexWavlm* s, const float* hidden, int B, float* embed, const Ws
 int run(DexWavlm* s, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, int do_normalize, float* hidden_dev, float* embed_dev,
         void* workspace_dev, size_t workspace_bytes, hipStream_t st) {
     int T = 0;
-    if (int rc = check_wavs(s, wav_dev, lengths_host, B, n_samples, &T)) return rc;
+    const long need = min_samples(s->c);
+    const std::string why = "too short, statistics pooling needs two TDNN frames (" + std::to_string(need) + " samples)";
+    if (int rc = check_wavs(s, s->t, WavRule{need, why.c_str(), 0, MAXF}, wav_dev, lengths_host, B, n_samples, &T)) return rc;
     if ((!hidden_dev && !embed_dev) || !workspace_dev) return s->fail(DEX_ERR_ARG, "null pointer argument");
     if (!s->finalized) return s->fail(DEX_ERR_STATE, "the wavlm weights are not finalized (dex_wavlm_finalize)");
-    const Ws w = plan(s->c, workspace_dev, B, n_samples);
+    const Ws w = plan(s, workspace_dev, B, n_samples);
     if (workspace_bytes < w.bytes) return s->fail(DEX_ERR_WORKSPACE, "workspace too small (dex_wavlm_workspace_bytes)");
     float* hidden = hidden_dev ? hidden_dev : w.mix;
     int rc = enqueue_encoder(s, wav_dev, lengths_host, B, n_samples, do_normalize, hidden, w, st);
@@ -831,44 +687,26 @@ int run(DexWavlm* s, const float* wav_dev, const int32_t* lengths_host, int B, i
     return rc ? s->fail(rc, "kernel launch failed") : DEX_OK;
 }
 
+typedef Entry<DexWavlm> E;
+
 }  // namespace
 
 extern "C" {
 
-int dex_wavlm_create(const DexWavlmConfig* cfg, DexWavlm** out) {
-    if (!out) return DEX_ERR_ARG;
-    *out = nullptr;
-    const DexWavlmConfig c = cfg ? *cfg : default_config();
-    if (int rc = check_config(c)) return rc;
-    DexWavlm* s = new DexWavlm();
-    s->c = c;
-    register_keys(s);
-    *out = s;
-    return DEX_OK;
-}
-
-void dex_wavlm_destroy(DexWavlm* s) {
-    if (!s) return;
-    s->release();
-    delete s;
-}
-
-const char* dex_wavlm_last_error(const DexWavlm* s) { return s ? s->err.c_str() : g_create_err.c_str(); }
-
+int dex_wavlm_create(const DexWavlmConfig* cfg, DexWavlm** out) { return E::create(cfg, out, default_config, check_config, register_keys); }
+void dex_wavlm_destroy(DexWavlm* s) { E::destroy(s); }
+const char* dex_wavlm_last_error(const DexWavlm* s) { return E::last_error(s); }
 int dex_wavlm_load(DexWavlm* s, const char* key, const float* w_dev, const int64_t* shape, int ndim, dex_stream_t stream) {
-    if (!s) return DEX_ERR_ARG;
-    if (!key || !w_dev || !shape) return s->fail(DEX_ERR_ARG, "null pointer argument");
-    return s->load(key, w_dev, shape, ndim, (hipStream_t)stream, false);
+    return E::load(s, key, w_dev, shape, ndim, stream);
 }
-
-int dex_wavlm_finalize(DexWavlm* s, dex_stream_t stream) { return s ? finalize(s, (hipStream_t)stream) : DEX_ERR_ARG; }
-int dex_wavlm_num_weights(const DexWavlm* s) { return s ? (int)s->keys.size() : 0; }
-int dex_wavlm_weight_info(const DexWavlm* s, int i, const char** key, int64_t shape[4], int* ndim) { return s ? s->info(i, key, shape, ndim) : DEX_ERR_ARG; }
+int dex_wavlm_finalize(DexWavlm* s, dex_stream_t stream) { return E::finalize(s, stream, pack_all, "packing the wavlm weights failed"); }
+int dex_wavlm_num_weights(const DexWavlm* s) { return E::num_weights(s); }
+int dex_wavlm_weight_info(const DexWavlm* s, int i, const char** key, int64_t shape[4], int* ndim) { return E::weight_info(s, i, key, shape, ndim); }
 
 int dex_wavlm_num_frames(const DexWavlmConfig* cfg, int n_samples) {
     const DexWavlmConfig c = cfg ? *cfg : default_config();
     if (n_samples < 0 || !geometry_ok(c)) return DEX_ERR_ARG;
-    return frames_of(c, n_samples, c.n_conv);
+    return frames_of(trunk_of(c), n_samples, c.n_conv);
 }
 
 int dex_wavlm_min_samples(const DexWavlmConfig* cfg) {
@@ -887,8 +725,8 @@ int dex_wavlm_rel_buckets(const DexWavlmConfig* cfg, int n, int32_t* out) {
 
 size_t dex_wavlm_workspace_bytes(const DexWavlm* s, int B, int max_samples) {
     if (!s || B < 1 || B > MAX_B || max_samples < min_samples(s->c)) return 0;
-    if (frames_of(s->c, max_samples, s->c.n_conv) > MAXF || (long)B * frames_of(s->c, max_samples, 1) > MAX_ROWS) return 0;
-    return plan(s->c, nullptr, B, max_samples).bytes;
+    if (frames_of(s->t, max_samples, s->t.n_conv) > MAXF || (long)B * frames_of(s->t, max_samples, 1) > MAX_ROWS) return 0;
+    return plan(s, nullptr, B, max_samples).bytes;
 }
 
 int dex_wavlm_hidden(DexWavlm* s, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, int do_normalize, float* hidden_dev,

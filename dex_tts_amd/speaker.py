@@ -261,11 +261,11 @@ def _encoder(encoder, what: str) -> "VoiceEncoder":
     return encoder
 
 
-def _similarity(what, encoder, syn, syn_lengths, syn_sr, trg, trg_lengths, trg_sr) -> torch.Tensor:
-    """Both sides through ``preprocess_wav``, stacked as 2 B rows, embedded in ONE ``embed_utterances`` call -> cos [B]."""
-    encoder = _encoder(encoder, what)
-    s, sl = preprocess_wav(syn, syn_sr, syn_lengths)
-    t, tl = preprocess_wav(trg, trg_sr, trg_lengths)
+def paired_cosine(what, prepare, embed, syn, trg) -> torch.Tensor:
+    """The similarity of B pairs, for this module's d-vectors and for ``wavlm``'s x-vectors: each side ``(wavs, lengths, sr)`` through
+    ``prepare(wavs, lengths, sr)`` -> (rows [B, n] or [n] at 16 kHz, host lengths), both stacked as 2 B rows, embedded in ONE
+    ``embed(rows, lengths)`` call -> cos [B]."""
+    (s, sl), (t, tl) = prepare(*syn), prepare(*trg)
     s, t = (v[None] if v.dim() == 1 else v for v in (s, t))
     if s.shape[0] != t.shape[0]:
         raise ValueError(f"{what}: {s.shape[0]} synthesised rows against {t.shape[0]} reference rows")
@@ -273,12 +273,20 @@ def _similarity(what, encoder, syn, syn_lengths, syn_sr, trg, trg_lengths, trg_s
     both = torch.zeros(2 * B, n, dtype=torch.float32, device=s.device)
     both[:B, : s.shape[1]] = s
     both[B:, : t.shape[1]] = t
-    e = encoder.embed_utterances(both, np.concatenate([sl, tl]))
+    e = embed(both, np.concatenate([sl, tl]))
     return cosine(e[:B], e[B:])
 
 
-def _mean_stderr(cos: torch.Tensor):
-    c = cos.double().cpu().numpy()
+def _similarity(what, encoder, syn, syn_lengths, syn_sr, trg, trg_lengths, trg_sr) -> torch.Tensor:
+    """Both sides through ``preprocess_wav``, embedded in ONE ``embed_utterances`` call -> cos [B]."""
+    encoder = _encoder(encoder, what)
+    return paired_cosine(what, lambda x, ln, sr: preprocess_wav(x, sr, ln), encoder.embed_utterances, (syn, syn_lengths, syn_sr),
+                         (trg, trg_lengths, trg_sr))
+
+
+def mean_stderr(cos):
+    """(mean, std / sqrt(n)) of cosines (a tensor or an array) with numpy's population std: the error bar of ``asv_score``."""
+    c = (cos.double().cpu().numpy() if torch.is_tensor(cos) else np.asarray(cos, np.float64)).reshape(-1)
     return float(np.mean(c)), float(np.std(c) / np.sqrt(len(c)))
 
 
@@ -291,7 +299,7 @@ def speaker_similarity(syn: torch.Tensor, trg: torch.Tensor, syn_lengths=None, t
 
 def asv_score(syn, trg, syn_lengths=None, trg_lengths=None, source_sr: Optional[int] = 22050, encoder: Optional[VoiceEncoder] = None):
     """calculate_asv_score (metric.py:81-95): (mean, std / sqrt(n)) of the pairs' cosines, with numpy's population std."""
-    return _mean_stderr(speaker_similarity(syn, trg, syn_lengths, trg_lengths, source_sr, encoder))
+    return mean_stderr(speaker_similarity(syn, trg, syn_lengths, trg_lengths, source_sr, encoder))
 
 
 def score_synthesis(audio: Sequence, ref_wavs: Sequence, sr: int = 22050, ref_sr: Optional[int] = None,
@@ -305,4 +313,4 @@ def score_synthesis(audio: Sequence, ref_wavs: Sequence, sr: int = 22050, ref_sr
     syn, sl = pad_wavs(audio, encoder.device, scale_int16=True)
     trg, tl = pad_wavs(ref_wavs, encoder.device, scale_int16=True)
     cos = _similarity("score_synthesis", encoder, syn, sl, sr, trg, tl, ref_sr or sr)
-    return (cos,) + _mean_stderr(cos)
+    return (cos,) + mean_stderr(cos)

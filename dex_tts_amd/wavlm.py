@@ -33,10 +33,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._native import Handle, device_index, device_rows, i32_ptr, pad_wavs, resample_to_16k, stream, upload_weights
+from ._native import device_rows, pad_wavs, resample_to_16k
+from ._wavnet import MAX_CONV, SAMPLING_RATE, WaveformNet, fill_trunk_config, route_hf_state_dict, weight_shapes
+from .speaker import mean_stderr, paired_cosine  # noqa: F401  (mean_stderr is this module's public name too)
 
-SAMPLING_RATE = 16000
-MAX_CONV = MAX_TDNN = 8
+MAX_TDNN = 8
 MAX_FRAMES = 4096                  # DEX_WAVLM_MAX_FRAMES: the encoder frames one call takes (81 s)
 
 
@@ -79,27 +80,12 @@ class DexWavlmConfig(C.Structure):
 
 def _c_config(cfg: WavLMConfig) -> DexWavlmConfig:
     """The C struct of a config; ``NotImplementedError`` for what the struct cannot even express."""
-    for name in ("hidden_act", "feat_extract_activation"):
-        if getattr(cfg, name) != "gelu":
-            raise NotImplementedError(f"{name}={getattr(cfg, name)!r}: only 'gelu' (erf) is built")
-    n = len(cfg.conv_dim)
-    if not (1 <= n <= MAX_CONV) or len(cfg.conv_kernel) != n or len(cfg.conv_stride) != n:
-        raise NotImplementedError(f"conv_dim / conv_kernel / conv_stride: 1 .. {MAX_CONV} layers of equal count, got "
-                                  f"{n} / {len(cfg.conv_kernel)} / {len(cfg.conv_stride)}")
+    c = fill_trunk_config(DexWavlmConfig(), cfg)
     m = len(cfg.tdnn_dim)
     if not (1 <= m <= MAX_TDNN) or len(cfg.tdnn_kernel) != m or len(cfg.tdnn_dilation) != m:
         raise NotImplementedError(f"tdnn_dim / tdnn_kernel / tdnn_dilation: 1 .. {MAX_TDNN} layers of equal count, got "
                                   f"{m} / {len(cfg.tdnn_kernel)} / {len(cfg.tdnn_dilation)}")
-    c = DexWavlmConfig()
-    c.n_conv = n
-    for i in range(n):
-        c.conv_dim[i], c.conv_kernel[i], c.conv_stride[i] = int(cfg.conv_dim[i]), int(cfg.conv_kernel[i]), int(cfg.conv_stride[i])
-    c.conv_bias = int(bool(cfg.conv_bias))
     c.feat_extract_norm_group = int(cfg.feat_extract_norm == "group")
-    c.hidden, c.n_layers, c.n_heads, c.intermediate = int(cfg.hidden_size), int(cfg.num_hidden_layers), int(cfg.num_attention_heads), int(cfg.intermediate_size)
-    c.do_stable_layer_norm = int(bool(cfg.do_stable_layer_norm))
-    c.num_conv_pos_embeddings, c.num_conv_pos_embedding_groups = int(cfg.num_conv_pos_embeddings), int(cfg.num_conv_pos_embedding_groups)
-    c.layer_norm_eps = float(cfg.layer_norm_eps)
     c.num_buckets, c.max_bucket_distance = int(cfg.num_buckets), int(cfg.max_bucket_distance)
     c.use_weighted_layer_sum = int(bool(cfg.use_weighted_layer_sum))
     c.n_tdnn = m
@@ -143,21 +129,9 @@ def relative_position_buckets(n: int, config: Optional[WavLMConfig] = None) -> n
     return out
 
 
-_HF_PARAM = {"parametrizations.weight.original0": "weight_g", "parametrizations.weight.original1": "weight_v"}
-
-
 def _ignored(key: str) -> bool:
     """Training-side keys of the checkpoint: the classifier and the AM-softmax objective make logits and the loss."""
     return key.startswith("classifier.") or key in ("objective.weight", "wavlm.masked_spec_embed")
-
-
-def _shapes(lib, h) -> dict:
-    out = {}
-    key, shape, nd = C.c_char_p(), (C.c_int64 * 4)(), C.c_int()
-    for i in range(lib.dex_wavlm_num_weights(h)):
-        lib.dex_wavlm_weight_info(h, i, C.byref(key), shape, C.byref(nd))
-        out[key.value.decode()] = tuple(int(shape[k]) for k in range(nd.value))
-    return out
 
 
 def state_dict_shapes(config: Optional[WavLMConfig] = None) -> dict:
@@ -167,7 +141,7 @@ def state_dict_shapes(config: Optional[WavLMConfig] = None) -> dict:
     if lib.dex_wavlm_create(C.byref(_c_config(config or WavLMConfig())), C.byref(h)) != _lib.DEX_OK:
         raise NotImplementedError(f"WavLMConfig.{lib.dex_wavlm_last_error(None).decode()}")
     try:
-        return _shapes(lib, h)
+        return weight_shapes(lib, "dex_wavlm", h)
     finally:
         lib.dex_wavlm_destroy(h)
 
@@ -176,26 +150,7 @@ def route_state_dict(sd, want: dict, strict: bool = True):
     """An HF state dict against the inventory ``want`` (``state_dict_shapes``) -> ({key: tensor} of what arrived, missing keys).  The
     positional convolution is taken in either weight-norm spelling; training-side keys are dropped.  A wrong shape or (``strict``)
     a missing or unexpected key raises ``RuntimeError``.  Host only."""
-    routed = {}
-    for k, v in sd.items():
-        for old, new in _HF_PARAM.items():
-            if k.endswith(old):
-                k = k[: -len(old)] + new
-        routed[k] = v
-    missing = [k for k in want if k not in routed]
-    extra = [k for k in routed if k not in want and not _ignored(k)]
-    if strict and missing:
-        raise RuntimeError(f"missing keys {missing[:4]}")
-    if strict and extra:
-        raise RuntimeError(f"unexpected keys {sorted(extra)[:4]}")
-    tensors = {}
-    for k, shape in want.items():
-        if k in routed:
-            v = torch.as_tensor(routed[k])
-            if tuple(v.shape) != shape:
-                raise RuntimeError(f"{k}: expected shape {shape}, got {tuple(v.shape)}")
-            tensors[k] = v
-    return tensors, missing
+    return route_hf_state_dict(sd, want, strict, _ignored)
 
 
 def check_lengths(lengths, n_samples: int, config: Optional[WavLMConfig] = None, what: str = "wavlm") -> int:
@@ -211,72 +166,24 @@ def check_lengths(lengths, n_samples: int, config: Optional[WavLMConfig] = None,
     return T
 
 
-class _Wavlm(Handle):
-    """One DexWavlm handle (the config, and once loaded the packed weights); its workspace is the network's."""
-
-    def __init__(self, cfg: WavLMConfig, device):
-        super().__init__("dex_wavlm", device, C.byref(_c_config(cfg)))
-
-    def create_failed(self, rc):
-        return NotImplementedError(f"WavLMConfig.{self.lib.dex_wavlm_last_error(None).decode()}")
-
-    def shapes(self) -> dict:
-        return _shapes(self.lib, self.h)
-
-    def workspace(self, B: int, n: int) -> torch.Tensor:
-        need = int(self.lib.dex_wavlm_workspace_bytes(self.h, B, n))
-        if need == 0:
-            raise ValueError(f"{B} rows of {n} samples: too short for two TDNN frames, or more than one call takes "
-                             f"({MAX_FRAMES} encoder frames)")
-        return super().workspace(need)
-
-
-class WavLMXVector:
+class WavLMXVector(WaveformNet):
     """HF's ``WavLMForXVector`` in eval mode on one MI355X, fp32, ``attention_mask=None``; a batch row is the row alone.
-    ``load_state_dict`` takes the HF checkpoint's state dict.  ``do_normalize``: apply ``Wav2Vec2FeatureExtractor``'s normalisation
-    (``asr.normalize_input``) to every row first.  It must match the checkpoint's ``preprocessor_config.json``; the library reads no
-    such file and nothing here can check what the published value is, so the default is False and the caller sets it."""
+    ``load_state_dict`` takes the HF checkpoint's state dict; ``classifier.*``, ``objective.weight`` and ``wavlm.masked_spec_embed``
+    are ignored.  ``do_normalize``: apply ``Wav2Vec2FeatureExtractor``'s normalisation (``asr.normalize_input``) to every row first.
+    It must match the checkpoint's ``preprocessor_config.json``; the library reads no such file and nothing here can check what the
+    published value is, so the default is False and the caller sets it."""
+    _prefix, _config_name = "dex_wavlm", "WavLMConfig"
+    _no_workspace = f"too short for two TDNN frames, or more than one call takes ({MAX_FRAMES} encoder frames)"
+    _c_config = staticmethod(_c_config)
+    _ignored = staticmethod(_ignored)
 
     def __init__(self, config: Optional[WavLMConfig] = None, device="cuda", do_normalize: bool = False):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise ValueError("WavLMXVector runs on an MI355X only (no CPU path)")
-        self.config = config or WavLMConfig()
+        super().__init__(config or WavLMConfig(), device)
         self.do_normalize = bool(do_normalize)
-        self.device = torch.device("cuda", device_index(device))
-        self._ctx = _Wavlm(self.config, self.device)
-        self._loaded = False
-
-    def state_dict_shapes(self) -> dict:
-        """The HF state-dict keys the network needs, with their shapes (weight norm in its ``weight_g`` / ``weight_v`` spelling)."""
-        return self._ctx.shapes()
-
-    def load_state_dict(self, sd, strict: bool = True):
-        """HF keys.  The positional convolution is taken as ``...conv.weight_g`` / ``weight_v`` or as ``...conv.parametrizations.
-        weight.original0`` / ``original1``; ``classifier.*``, ``objective.weight`` and ``wavlm.masked_spec_embed`` are ignored.  A
-        wrong shape or (``strict``) a missing or unexpected key raises ``RuntimeError`` before anything is uploaded; with
-        ``strict=False`` the network stays unusable until every key has arrived."""
-        tensors, missing = route_state_dict(sd, self.state_dict_shapes(), strict)
-        self._loaded = False
-        upload_weights(self._ctx, self._ctx.lib.dex_wavlm_load, tensors, self.device)
-        if not missing:
-            self.finalize()
-            torch.cuda.current_stream(self.device).synchronize()        # the operands are packed when this returns
-        return self
-
-    def finalize(self):
-        """Pack the operands (``dex_wavlm_finalize``); ``ValueError`` naming the first key that was never loaded."""
-        ctx = self._ctx
-        with torch.cuda.device(self.device):
-            ctx.check(ctx.lib.dex_wavlm_finalize(ctx.h, stream(self.device)), "dex_wavlm_finalize")
-        self._loaded = True
-        return self
 
     def _inputs(self, wav, lengths, what: str):
-        if not self._loaded:
-            raise ValueError(f"{what}: the network's weights are not loaded (load_state_dict)")
-        x, ln, one = device_rows(wav, lengths, what, refuse=ValueError)
-        return x.to(self.device), ln, one, check_lengths(ln, x.shape[1], self.config, what)
+        x, ln, one = self._rows(wav, lengths, what)
+        return x, ln, one, check_lengths(ln, x.shape[1], self.config, what)
 
     def hidden_states(self, wav: torch.Tensor, lengths=None) -> torch.Tensor:
         """Raw 16 kHz samples [B, n] (or [n]), row b ``lengths[b]`` samples (what is stored past them reaches no result) -> the hidden
@@ -284,29 +191,15 @@ class WavLMXVector:
         the encoder's L + 1 hidden states (``use_weighted_layer_sum``) or the last one.  Row b fills ``num_frames(lengths[b])``
         frames and is 0 past them; it is bitwise the row alone."""
         x, ln, one, T = self._inputs(wav, lengths, "WavLMXVector.hidden_states")
-        B, n = x.shape
-        ctx = self._ctx
-        ws = ctx.workspace(B, n)
-        out = torch.empty(B, T, self.config.hidden_size, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = ctx.lib.dex_wavlm_hidden(ctx.h, x.data_ptr(), i32_ptr(ln), B, n, int(self.do_normalize), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                          stream(self.device))
-        ctx.check(rc, "dex_wavlm_hidden")
-        return out[0] if one else out
+        out = torch.empty(x.shape[0], T, self.config.hidden_size, dtype=torch.float32, device=self.device)
+        return self._run("hidden", x, ln, out, int(self.do_normalize), out.data_ptr(), one=one)
 
     def forward(self, input_values: torch.Tensor, lengths=None) -> torch.Tensor:
         """``WavLMForXVector.forward(input_values).embeddings`` of every row alone: [B, n] (or [n]) -> [B, xvector_output_dim] (or
         [xvector_output_dim]).  Every row needs ``min_samples()`` samples."""
         x, ln, one, _ = self._inputs(input_values, lengths, "WavLMXVector.forward")
-        B, n = x.shape
-        ctx = self._ctx
-        ws = ctx.workspace(B, n)
-        out = torch.empty(B, self.config.xvector_output_dim, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = ctx.lib.dex_wavlm_embed(ctx.h, x.data_ptr(), i32_ptr(ln), B, n, int(self.do_normalize), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                         stream(self.device))
-        ctx.check(rc, "dex_wavlm_embed")
-        return out[0] if one else out
+        out = torch.empty(x.shape[0], self.config.xvector_output_dim, dtype=torch.float32, device=self.device)
+        return self._run("embed", x, ln, out, int(self.do_normalize), out.data_ptr(), one=one)
 
     __call__ = forward
 
@@ -314,16 +207,9 @@ class WavLMXVector:
         """``wavs`` [B, n] with ``lengths``, or a list of wavs (float, or int16 scaled by 1 / 32768), at ``sr`` Hz -> embeddings
         [B, xvector_output_dim] in one network call.  Where ``sr`` is not 16000 the wavs are resampled by ``wavprep.resample``
         (kaiser_best; librosa uses soxr)."""
-        if int(sr) <= 0:
-            raise ValueError(f"WavLMXVector.embed_utterances: sr must be positive, got {sr}")
-        if not isinstance(wavs, torch.Tensor):
-            wavs, lengths = pad_wavs(wavs, self.device, scale_int16=True)
-        elif wavs.dim() != 2:
+        if isinstance(wavs, torch.Tensor) and wavs.dim() != 2:
             raise ValueError(f"WavLMXVector.embed_utterances: expected wavs [B, n] or a list, got {tuple(wavs.shape)}")
-        if int(sr) != SAMPLING_RATE:
-            x, ln, _ = device_rows(wavs, lengths, "WavLMXVector.embed_utterances", refuse=ValueError)
-            wavs, lengths = resample_to_16k(x, ln, sr)
-        return self.forward(wavs, lengths)
+        return self.forward(*self._at_16k(wavs, lengths, sr, "WavLMXVector.embed_utterances"))
 
 
 def _model(model, what: str) -> WavLMXVector:
@@ -334,21 +220,12 @@ def _model(model, what: str) -> WavLMXVector:
 
 def _pair(what, model, syn, syn_lengths, syn_sr, trg, trg_lengths, trg_sr) -> torch.Tensor:
     """Both sides at 16 kHz, stacked as 2 B rows, embedded in ONE call -> cos [B] (``dex_spk_cosine``)."""
-    from . import speaker
     model = _model(model, what)
-    sides = []
-    for x, ln, sr in ((syn, syn_lengths, syn_sr), (trg, trg_lengths, trg_sr)):
+
+    def at_16k(x, ln, sr):
         x, ln, _ = device_rows(x, ln, what, refuse=ValueError)
-        sides.append(resample_to_16k(x.to(model.device), ln, sr))
-    (s, sl), (t, tl) = sides
-    if s.shape[0] != t.shape[0]:
-        raise ValueError(f"{what}: {s.shape[0]} synthesised rows against {t.shape[0]} reference rows")
-    B, n = s.shape[0], max(s.shape[1], t.shape[1])
-    both = torch.zeros(2 * B, n, dtype=torch.float32, device=model.device)
-    both[:B, : s.shape[1]] = s
-    both[B:, : t.shape[1]] = t
-    e = model.forward(both, np.concatenate([sl, tl]))
-    return speaker.cosine(e[:B], e[B:])
+        return resample_to_16k(x.to(model.device), ln, sr)
+    return paired_cosine(what, at_16k, model.forward, (syn, syn_lengths, syn_sr), (trg, trg_lengths, trg_sr))
 
 
 def similarity(syn: torch.Tensor, trg: torch.Tensor, syn_lengths=None, trg_lengths=None, source_sr: Optional[int] = 22050,
@@ -356,12 +233,6 @@ def similarity(syn: torch.Tensor, trg: torch.Tensor, syn_lengths=None, trg_lengt
     """SIM for a batch: syn, trg [B, n] (or [n]) at ``source_sr`` Hz, rows of ``*_lengths`` samples -> the cosine of each pair's
     x-vector embeddings, [B] on the device."""
     return _pair("similarity", model, syn, syn_lengths, source_sr, trg, trg_lengths, source_sr)
-
-
-def mean_stderr(cos) -> Tuple[float, float]:
-    """(mean, std / sqrt(n)) with numpy's population std: the error bar ``speaker.asv_score`` reports."""
-    c = (cos.double().cpu().numpy() if torch.is_tensor(cos) else np.asarray(cos, np.float64)).reshape(-1)
-    return float(np.mean(c)), float(np.std(c) / np.sqrt(len(c)))
 
 
 def sim_score(syn, trg, syn_lengths=None, trg_lengths=None, source_sr: Optional[int] = 22050, model: Optional[WavLMXVector] = None):

@@ -166,6 +166,22 @@ def test_ctc_and_decode_restated():
     assert asr.VOCAB == R.VOCAB and len(asr.VOCAB) == 32
 
 
+def test_state_dict_inventory_is_in_the_restatement_s_order():
+    """The library registers its keys in the order of the restatement's state dict: ``weight_info(i)``, ``state_dict_shapes()`` and
+    the 'missing keys' texts follow that order.  Host only: a handle is created, nothing touches a device."""
+    import ctypes as C
+    from dex_tts_amd import _lib, _wavnet, asr
+    lib = _lib.load()
+    for cfg in (R.TINY, R.DEFAULT):
+        h = C.c_void_p()
+        assert lib.dex_asr_create(C.byref(asr._c_config(R.library_config(cfg))), C.byref(h)) == _lib.DEX_OK
+        try:
+            got = _wavnet.weight_shapes(lib, "dex_asr", h)
+        finally:
+            lib.dex_asr_destroy(h)
+        assert list(got.items()) == list(R.state_dict_shapes(cfg).items())
+
+
 def test_config_outside_the_family_names_the_field():
     from dex_tts_amd import asr
     with pytest.raises(NotImplementedError, match="hidden_act"):

@@ -214,6 +214,7 @@ def test_state_dict_inventory_and_routing():
     from dex_tts_amd import wavlm
     for cfg in (R.TINY, R.DEFAULT, tiny(False, True)):
         assert wavlm.state_dict_shapes(R.library_config(cfg)) == R.state_dict_shapes(cfg)
+        assert list(wavlm.state_dict_shapes(R.library_config(cfg))) == list(R.state_dict_shapes(cfg))      # and in that order
     assert wavlm.state_dict_shapes() == R.state_dict_shapes(R.DEFAULT)
     want = wavlm.state_dict_shapes(R.library_config(R.TINY))
     sd = {k: torch.from_numpy(v) for k, v in R.make_weights(R.TINY, 0).items()}
