@@ -266,6 +266,26 @@ SYMBOLS = [
                                    C.c_void_p]),
     ("dex_wavlm_embed", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                   C.c_void_p]),
+    ("dex_whisper_create", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("dex_whisper_destroy", None, [C.c_void_p]),
+    ("dex_whisper_last_error", C.c_char_p, [C.c_void_p]),
+    ("dex_whisper_load", C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
+    ("dex_whisper_finalize", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("dex_whisper_num_weights", C.c_int, [C.c_void_p]),
+    ("dex_whisper_weight_info", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    ("dex_whisper_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
+    ("dex_whisper_mel_filters", C.c_int, [C.c_int, C.POINTER(C.c_double)]),
+    ("dex_whisper_log_mel", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("dex_whisper_encode", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("dex_whisper_step_linear", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p]),
+    ("dex_whisper_forward", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("dex_whisper_generate", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("dex_whisper_attend", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p]),
+    ("dex_whisper_pick", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                   C.c_int, C.c_void_p]),
 ]
 
 _lib = None

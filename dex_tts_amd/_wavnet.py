@@ -99,8 +99,9 @@ class NetHandle(Handle):
 class WaveformNet:
     """Base of ``Wav2Vec2CTC`` and ``WavLMXVector``: one network of the family in eval mode on one MI355X, fp32.  A subclass names
     its symbols (``_prefix``), its config (``_config_name``, ``_c_config``), what its workspace refuses (``_no_workspace``) and the
-    checkpoint keys it never reads (``_ignored``)."""
+    checkpoint keys it never reads (``_ignored``); ``_handle`` is its handle class where its workspace takes other arguments."""
     _prefix = _config_name = _no_workspace = ""
+    _handle = NetHandle
 
     def __init__(self, config, device):
         device = torch.device(device)
@@ -108,7 +109,7 @@ class WaveformNet:
             raise ValueError(f"{type(self).__name__} runs on an MI355X only (no CPU path)")
         self.config = config
         self.device = torch.device("cuda", device_index(device))
-        self._ctx = NetHandle(self._prefix, self._c_config(config), self.device, self._config_name, self._no_workspace)
+        self._ctx = self._handle(self._prefix, self._c_config(config), self.device, self._config_name, self._no_workspace)
         self._loaded = False
 
     def state_dict_shapes(self) -> dict:

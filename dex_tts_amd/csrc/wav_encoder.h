@@ -168,7 +168,7 @@ long up64(long n) { return (n + 63) & ~63L; }
 
 // C [B][To][ldc] = epi(conv1d(A [B][Ti][lda])): kernel k, stride s, left offset off, taps dil apart, `groups` groups of cin -> N channels each
 void gemm(const float* A, int lda, int Ti, int cin, int k, int stride, int off, int To, const float* W, int N, int groups, const float* bias,
-          float* C, int act, const float* res, const float* outmask, int B, hipStream_t st, int ksplit = 1, int dil = 1) {
+          float* C, int act, const float* res, const float* outmask, int B, hipStream_t st, int ksplit = 1, int dil = 1, bool res_shared = false) {
     dex::IGemmP g{};
     const int ldc = N * groups;
     g.A = A; g.lda = lda; g.a_bstride = (long)Ti * lda;
@@ -180,7 +180,7 @@ void gemm(const float* A, int lda, int Ti, int cin, int k, int stride, int off, 
     g.OHf = 1; g.OWf = To; g.osh = 1; g.osw = 1;
     g.inmask_ws = 1; g.outmask = outmask; g.outmask_ws = 1; g.mask_bstride = To; g.gate_nstride = 1;
     g.act = act;
-    g.res = res; g.ldres = ldc; g.res_bstride = (long)To * ldc;
+    g.res = res; g.ldres = ldc; g.res_bstride = res_shared ? 0 : (long)To * ldc;      // res_shared: one [To][ldc] table for every row
     g.B = B;
     dex::launch_igemm(g, dex::PREC_FP32, st);
 }

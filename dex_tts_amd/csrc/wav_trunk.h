@@ -5,7 +5,7 @@
 // workspace (plan_trunk), the enqueue steps a network composes its forward pass from, the argument checks of a call that takes wavs,
 // and the boilerplate entry points (Entry).  What differs stays with the network: its first convolution and its norm, the order of
 // LayerNorm and attention in a layer, the attention itself, and its head.  The kernels are in wav_encoder.h.  Included by those two
-// files only; everything has internal linkage.
+// files, and by whisper.hip for the handle's boilerplate (create_fail, Taker, Entry) only; everything has internal linkage.
 #pragma once
 #include <vector>
 

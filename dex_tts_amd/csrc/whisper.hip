@@ -1,0 +1,836 @@
+// whisper.hip — the Whisper ASR score on the device: HF's WhisperForConditionalGeneration in eval mode (log-mel front end of
+// WhisperFeatureExtractor, encoder, decoder with a key/value cache, greedy decoding).  fp32 throughout, channels-last.  C ABI
+// dex_whisper_*; dex_tts_amd/whisper.py states the definitions.
+//
+//   wsp_mel_kernel       the front end up to log10: 8 frames per workgroup; the zero-padded, reflect-padded, Hann-windowed frames in
+//                        LDS as fp64, the 400-point DFT as a direct sum in fp64 (400 is no power of two; one thread per bin walks the
+//                        twiddle table by k n mod 400), power, the mel matrix (fp64, built on the host), log10(max(., 1e-10)).
+//   wsp_mel_floor_kernel one workgroup per row: the row's maximum (a maximum has no summation order), the floor at max - 8,
+//                        (x + 4) / 4, rounded to fp32 once and stored [n_mels][frames].
+//   launch_igemm         (igemm.hip, exact-fp32 MFMA) every wide contraction: conv1 (the mel channels padded to a multiple of 32,
+//                        GELU in the epilogue), conv2 (stride 2, GELU and + embed_positions in the epilogue), the encoder's q|k|v,
+//                        out_proj, fc1, fc2, and the cross-attention k|v of every decoder layer, once per utterance.
+//   launch_attention     (attention.hip) the encoder's self-attention: the generic fp32 kernel at head_dim 64, no mask.
+//   wsp_skinny_kernel    the decoder step's linears at M = B <= 32 rows: every weight element is read from HBM once for the whole
+//                        batch.  A lane owns one output column, a wave 64 rows of K (all 64 loads issued before the first wait), the rows
+//                        of x sit in LDS and are read as broadcasts; the four waves of a workgroup meet in LDS in wave order and the
+//                        K slabs of a launch (KS = ceil(K / 256)) land as partials [KS][B][N] that the consumer adds in slab order.
+//   wsp_finish_kernel    consumer of the partials, one workgroup per row: + bias, GELU, + residual, and the LayerNorm that follows.
+//   wsp_attend_kernel    cached single-query attention at head_dim 64, one workgroup per (row, head).  Self-attention appends the
+//                        step's k and v (finished from the q|k|v partials) at position p and attends over 0 .. p; cross-attention
+//                        attends over the encoder frames.  Four lanes share a key's dot product (16 dims each, two shuffles), the
+//                        scores sit in LDS, the maximum is exact, the sum of exponentials and the weighted sum of V (one lane per
+//                        channel, keys dealt to the four waves) are reduced in a fixed order.
+//   wsp_pick_kernel      the greedy step tail, one workgroup per row: logits finished from the partials, suppression, argmax with the
+//                        lowest index on ties, finished / length bookkeeping, and the gather of the next step's embed_tokens +
+//                        embed_positions row.  A step needs no host value.
+// Every per-row sum has an order fixed by the config and the position: a row's logits and ids are bitwise those of the row alone.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/dex_amd.h"
+#include "kernels.h"
+#include "wav_trunk.h"
+#include "weight_store.h"
+
+using namespace dex::wavenc;      // the GEMM wrappers, LayerNorm, packing, Taker and Entry of the waveform transformers
+
+namespace {
+
+constexpr int WB = DEX_WHISPER_MAX_B;
+constexpr int NFFT = DEX_WHISPER_N_FFT, HOP = DEX_WHISPER_HOP, NBIN = NFFT / 2 + 1;
+constexpr int MELF = 8;                  // frames per workgroup of the front end
+constexpr int MAX_KEYS = 4096;           // keys of a single-query attention (their scores sit in LDS)
+constexpr float LN_EPS = 1e-5f;
+
+struct Lens { int a[WB]; };
+
+// ------------------------------------------------------------------------------------------------------------ log-mel front end
+struct MelP { const float* wav; long ld; Lens len; long N; int T, n_mels; const double *win, *cs, *sn, *filt; double* out; };
+
+__global__ __launch_bounds__(256) void wsp_mel_kernel(const MelP p) {
+    __shared__ double xs[MELF][NFFT];
+    __shared__ double cs[NFFT], sn[NFFT];
+    __shared__ double pw[MELF][NBIN];
+    const int tid = threadIdx.x, b = blockIdx.y, t0 = blockIdx.x * MELF, L = p.len.a[b];
+    const float* x = p.wav + (long)b * p.ld;
+    for (int i = tid; i < MELF * NFFT; i += 256) {
+        const int f = i / NFFT, n = i - f * NFFT, t = t0 + f;
+        long j = (long)t * HOP + n - NFFT / 2;                      // centre = True, reflect padding of the zero-padded chunk
+        if (j < 0) j = -j;
+        if (j >= p.N) j = 2 * (p.N - 1) - j;
+        xs[f][n] = (t < p.T && j < L) ? (double)x[j] * p.win[n] : 0.0;
+    }
+    for (int i = tid; i < NFFT; i += 256) { cs[i] = p.cs[i]; sn[i] = p.sn[i]; }
+    __syncthreads();
+    if (tid < NBIN) {
+        double re[MELF], im[MELF];
+#pragma unroll
+        for (int f = 0; f < MELF; ++f) re[f] = im[f] = 0.0;
+        int idx = 0;
+        for (int n = 0; n < NFFT; ++n) {
+            const double c = cs[idx], s = sn[idx];
+#pragma unroll
+            for (int f = 0; f < MELF; ++f) { const double v = xs[f][n]; re[f] = fma(v, c, re[f]); im[f] = fma(v, s, im[f]); }
+            idx += tid;
+            if (idx >= NFFT) idx -= NFFT;
+        }
+#pragma unroll
+        for (int f = 0; f < MELF; ++f) pw[f][tid] = fma(re[f], re[f], im[f] * im[f]);
+    }
+    __syncthreads();
+    for (int o = tid; o < MELF * p.n_mels; o += 256) {
+        const int f = o / p.n_mels, m = o - f * p.n_mels, t = t0 + f;
+        if (t >= p.T) continue;
+        double a = 0.0;
+        for (int k = 0; k < NBIN; ++k) a = fma(p.filt[(long)k * p.n_mels + m], pw[f][k], a);
+        p.out[((long)b * p.T + t) * p.n_mels + m] = log10(fmax(a, 1e-10));
+    }
+}
+
+// logspec [B][T][n_mels] (fp64) -> out [B][n_mels][T]: max(x, rowmax - 8), (x + 4) / 4
+__global__ __launch_bounds__(1024) void wsp_mel_floor_kernel(const double* logspec, float* out, int T, int n_mels) {
+    __shared__ double red[1024];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const long n = (long)T * n_mels;
+    const double* x = logspec + (long)b * n;
+    double m = -1e300;
+    for (long i = tid; i < n; i += 1024) m = fmax(m, x[i]);
+    red[tid] = m;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) {
+        if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
+        __syncthreads();
+    }
+    const double lo = red[0] - 8.0;
+    for (long i = tid; i < n; i += 1024) {
+        const int mel = (int)(i / T), t = (int)(i - (long)mel * T);
+        out[(long)b * n + i] = (float)((fmax(x[(long)t * n_mels + mel], lo) + 4.0) / 4.0);
+    }
+}
+
+// feat [B][n_mels][T] -> cl [B][T][Mp], the channels past n_mels 0
+__global__ __launch_bounds__(256) void wsp_feat_cl_kernel(const float* feat, float* cl, long total, int T, int n_mels, int Mp) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int c = (int)(i % Mp);
+    const long bt = i / Mp;
+    const long b = bt / T, t = bt - b * T;
+    cl[i] = c < n_mels ? feat[(b * n_mels + c) * T + t] : 0.f;
+}
+
+// ------------------------------------------------------------------------------------------------------------ the step's linears
+// A workgroup takes SK_ROWS rows of K, 64 per wave: a wave issues all of its loads before it waits for any.  KS = ceil(K / SK_ROWS)
+// slabs, a function of K alone.  Measured per token at whisper-large-v3, B = 1 / 32: 64 rows per wave 6.06 / 10.7 ms,
+// 32 rows per wave (twice the slabs, twice the partials the consumer reads) 7.75 / 12.3 ms, 16-load batches over 48-64 rows 6.47 / 11.4 ms
+constexpr int SK_ROWS = 256, SK_WAVE = SK_ROWS / 4;
+int slabs(int K) { return (K + SK_ROWS - 1) / SK_ROWS; }
+
+struct SkP { const float* X; int ldx; const float* W; int ldw; int K, N; float* P; int B; };
+
+// P [slab blockIdx.y][b][n] = sum over the slab's rows k of X[b][k] W[k][n], n = 64 blockIdx.x + lane; K % 64 == 0, ldw >= 64 gridDim.x.
+// RB >= B rows are carried; a row's sum is the same fmaf chain whatever RB is
+template <int RB>
+__global__ __launch_bounds__(256) void wsp_skinny_kernel(const SkP p) {
+    extern __shared__ float sm[];
+    float* xs = sm;                                  // [SK_ROWS][RB]
+    float* red = sm + SK_ROWS * RB;                  // [4][RB][64]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = blockIdx.x * 64 + lane, k0 = blockIdx.y * SK_ROWS;
+    const int rows = p.K - k0 < SK_ROWS ? p.K - k0 : SK_ROWS;           // a multiple of 64: a wave has all of its rows or none
+    const int kb = wave * SK_WAVE;
+    const bool live = kb < rows;
+    float w[SK_WAVE];
+    if (live) {
+        const float* W = p.W + (long)(k0 + kb) * p.ldw + n;
+#pragma unroll
+        for (int u = 0; u < SK_WAVE; ++u) w[u] = W[(long)u * p.ldw];
+    }
+    for (int i = tid; i < SK_ROWS * RB; i += 256) {
+        const int b = i / SK_ROWS, k = i - b * SK_ROWS;
+        xs[k * RB + b] = (b < p.B && k < rows) ? p.X[(long)b * p.ldx + k0 + k] : 0.f;
+    }
+    __syncthreads();
+    float acc[RB];
+#pragma unroll
+    for (int b = 0; b < RB; ++b) acc[b] = 0.f;
+    if (live) {
+#pragma unroll
+        for (int u = 0; u < SK_WAVE; ++u) {
+            if constexpr (RB >= 4) {
+                const float4* xr = reinterpret_cast<const float4*>(xs + (kb + u) * RB);
+#pragma unroll
+                for (int q = 0; q < RB / 4; ++q) {
+                    const float4 x = xr[q];
+                    acc[4 * q] = fmaf(x.x, w[u], acc[4 * q]); acc[4 * q + 1] = fmaf(x.y, w[u], acc[4 * q + 1]);
+                    acc[4 * q + 2] = fmaf(x.z, w[u], acc[4 * q + 2]); acc[4 * q + 3] = fmaf(x.w, w[u], acc[4 * q + 3]);
+                }
+            } else {
+                acc[0] = fmaf(xs[kb + u], w[u], acc[0]);
+            }
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < RB; ++b) red[(wave * RB + b) * 64 + lane] = acc[b];
+    __syncthreads();
+    for (int b = wave; b < RB; b += 4) {
+        if (b >= p.B || n >= p.N) continue;
+        const float v = ((red[b * 64 + lane] + red[(RB + b) * 64 + lane]) + red[(2 * RB + b) * 64 + lane]) + red[(3 * RB + b) * 64 + lane];
+        p.P[((long)blockIdx.y * p.B + b) * p.N + n] = v;
+    }
+}
+
+// the value a launch of wsp_skinny_kernel left for (row offset `at`): its slabs in order, then the bias
+__device__ __forceinline__ float finished(const float* P, int KS, long ss, long at, const float* bias, int c) {
+    float v = P[at];
+    for (int s = 1; s < KS; ++s) v += P[(long)s * ss + at];
+    return bias ? v + bias[c] : v;
+}
+
+// sum of one float per thread over the 256 threads: butterfly in the wave, the four waves in order; every thread gets the total
+__device__ __forceinline__ float block_sum256(float v, float* red4) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((red4[0] + red4[1]) + red4[2]) + red4[3];
+}
+
+struct FinP { const float* P; int KS; long ss; int N; const float* bias; const float* res; float* out; int act;
+              const float* g; const float* be; float* y; };
+
+// row blockIdx.x: out = res + act(partials + bias) (P null: out = res); g: y = LayerNorm(out)
+__global__ __launch_bounds__(256) void wsp_finish_kernel(const FinP p) {
+    __shared__ float red4[4];
+    const int tid = threadIdx.x;
+    const long row = (long)blockIdx.x * p.N;
+    float s = 0.f;
+    for (int c = tid; c < p.N; c += 256) {
+        float v;
+        if (p.P) {
+            v = finished(p.P, p.KS, p.ss, row + c, p.bias, c);
+            if (p.act) v = gelu_erf_(v);
+            if (p.res) v = p.res[row + c] + v;
+            p.out[row + c] = v;
+        } else {
+            v = p.res[row + c];
+        }
+        s += v;
+    }
+    if (!p.g) return;
+    const float* o = p.P ? p.out : p.res;
+    const float mean = block_sum256(s, red4) / (float)p.N;
+    float q = 0.f;
+    for (int c = tid; c < p.N; c += 256) { const float d = o[row + c] - mean; q = fmaf(d, d, q); }
+    const float rstd = 1.f / sqrtf(block_sum256(q, red4) / (float)p.N + LN_EPS);
+    for (int c = tid; c < p.N; c += 256) p.y[row + c] = (o[row + c] - mean) * rstd * p.g[c] + p.be[c];
+}
+
+// ------------------------------------------------------------------------------------------------------------ cached attention
+// q, kn, vn: slabs of partials (KS, ss) with row stride ldq, or plain rows (KS = 1); kn / vn (or null) are appended at key n - 1
+struct AtP { const float* q; const float* kn; const float* vn; int KS; long ss; int ldq; const float *qbias, *kbias, *vbias;
+             float* K; float* V; int ldk; long kb; int n; float* out; int ldo; float scale; };
+
+__global__ __launch_bounds__(256) void wsp_attend_kernel(const AtP p) {
+    __shared__ float sc[MAX_KEYS];
+    __shared__ float qs[64];
+    __shared__ float red[4][64];
+    __shared__ float red4[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = blockIdx.x, b = blockIdx.y;
+    float* Kb = p.K + (long)b * p.kb + h * 64;
+    float* Vb = p.V + (long)b * p.kb + h * 64;
+    {
+        const int c = h * 64 + lane;
+        const long at = (long)b * p.ldq + c;
+        if (wave == 0) qs[lane] = p.scale * finished(p.q, p.KS, p.ss, at, p.qbias, c);
+        else if (wave == 1 && p.kn) Kb[(long)(p.n - 1) * p.ldk + lane] = finished(p.kn, p.KS, p.ss, at, p.kbias, c);
+        else if (wave == 2 && p.vn) Vb[(long)(p.n - 1) * p.ldk + lane] = finished(p.vn, p.KS, p.ss, at, p.vbias, c);
+    }
+    __syncthreads();
+    // scores: four lanes per key, 16 dims each
+    const int part = tid & 3, kk = tid >> 2;
+    float qr[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) qr[i] = qs[part * 16 + i];
+    for (int j0 = 0; j0 < p.n; j0 += 64) {
+        const int j = j0 + kk;
+        float s = 0.f;
+        if (j < p.n) {
+            const float4* kr = reinterpret_cast<const float4*>(Kb + (long)j * p.ldk + part * 16);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float4 k4 = kr[i];
+                s = fmaf(qr[4 * i], k4.x, s); s = fmaf(qr[4 * i + 1], k4.y, s); s = fmaf(qr[4 * i + 2], k4.z, s); s = fmaf(qr[4 * i + 3], k4.w, s);
+            }
+        }
+        s += __shfl_xor(s, 1);
+        s += __shfl_xor(s, 2);
+        if (part == 0 && j < p.n) sc[j] = s;
+    }
+    __syncthreads();
+    float m = -INFINITY;
+    for (int j = tid; j < p.n; j += 256) m = fmaxf(m, sc[j]);
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if (lane == 0) red4[wave] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(red4[0], red4[1]), fmaxf(red4[2], red4[3]));
+    float l = 0.f;
+    for (int j = tid; j < p.n; j += 256) { const float e = expf(sc[j] - m); sc[j] = e; l += e; }
+    l = block_sum256(l, red4);                       // (its barriers also publish the exponentials)
+    float acc = 0.f;
+#pragma unroll 8
+    for (int j = wave; j < p.n; j += 4) acc = fmaf(sc[j], Vb[(long)j * p.ldk + lane], acc);
+    red[wave][lane] = acc;
+    __syncthreads();
+    if (wave == 0) p.out[(long)b * p.ldo + h * 64 + lane] = (((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]) / l;
+}
+
+// ------------------------------------------------------------------------------------------------------------ greedy step tail
+struct PickP { const float* P; int KS; long ss; int V; const uint8_t* mask; float* logits; long ldl; int pick, eos;
+               int *finished, *lengths, *count, *ids; int ld_ids, step;
+               const float *emb, *pos; int d, next_pos; float* h; };
+
+__device__ __forceinline__ void better(float& v, int& i, float ov, int oi) {
+    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+}
+
+// row blockIdx.x: the logits finished from the partials (stored where `logits` is given); pick: the id of this step and the bookkeeping;
+// next_pos >= 0: h = embed_tokens[id] + embed_positions[next_pos]
+__global__ __launch_bounds__(1024) void wsp_pick_kernel(const PickP p) {
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    __shared__ int chosen;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+    float best = -INFINITY;
+    int arg = 0x7fffffff;
+    for (int v = tid; v < p.V; v += 1024) {
+        float x = finished(p.P, p.KS, p.ss, (long)b * p.V + v, nullptr, 0);
+        if (p.logits) p.logits[(long)b * p.ldl + v] = x;
+        if (p.mask && p.mask[v]) x = -INFINITY;
+        better(best, arg, x, v);
+    }
+    if (!p.pick) return;
+    for (int o = 32; o > 0; o >>= 1) { const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(arg, o); better(best, arg, ov, oi); }
+    if (lane == 0) { bv[wave] = best; bi[wave] = arg; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 16; ++w) better(best, arg, bv[w], bi[w]);
+        if (arg >= p.V) arg = 0;                     // a row of NaN compares with nothing
+        const int fin = p.finished[b];
+        const int id = fin ? p.eos : arg;
+        if (!fin) {
+            if (id == p.eos) { p.finished[b] = 1; atomicAdd(p.count, 1); }
+            else p.lengths[b] += 1;
+        }
+        p.ids[(long)b * p.ld_ids + p.step] = id;
+        chosen = id;
+    }
+    __syncthreads();
+    if (p.next_pos < 0) return;
+    const float* e = p.emb + (long)chosen * p.d;
+    const float* q = p.pos + (long)p.next_pos * p.d;
+    for (int c = tid; c < p.d; c += 1024) p.h[(long)b * p.d + c] = e[c] + q[c];
+}
+
+// h[b] = embed_tokens[id] + embed_positions[pos], id = ids[b ld + pos] (clamped into the vocabulary) or, ids null, `id`
+__global__ __launch_bounds__(256) void wsp_embed_kernel(const int* ids, int ld, int id, int pos, int V, const float* emb, const float* posw, int d, float* h) {
+    const int b = blockIdx.x;
+    if (ids) id = ids[(long)b * ld + pos];
+    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+    for (int c = threadIdx.x; c < d; c += 256) h[(long)b * d + c] = emb[(long)id * d + c] + posw[(long)pos * d + c];
+}
+
+__global__ __launch_bounds__(256) void wsp_fill_kernel(int* dst, long n, int v) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = v;
+}
+
+// ------------------------------------------------------------------------------------------------------------ host: tables
+void mel_filters(int n_mels, double* out) {
+    const double logstep = 27.0 / std::log(6.4);
+    auto hz2mel = [&](double f) { return f >= 1000.0 ? 15.0 + std::log(f / 1000.0) * logstep : 3.0 * f / 200.0; };
+    auto mel2hz = [&](double m) { return m >= 15.0 ? 1000.0 * std::exp((std::log(6.4) / 27.0) * (m - 15.0)) : 200.0 * m / 3.0; };
+    const double lo = hz2mel(0.0), hi = hz2mel(8000.0), step = (hi - lo) / (n_mels + 1);
+    std::vector<double> ff(n_mels + 2);
+    for (int i = 0; i < n_mels + 2; ++i) ff[i] = mel2hz(i == n_mels + 1 ? hi : lo + i * step);
+    for (int k = 0; k < NBIN; ++k) {
+        const double f = k == NBIN - 1 ? 8000.0 : k * (8000.0 / (NBIN - 1));
+        for (int m = 0; m < n_mels; ++m) {
+            const double down = -(ff[m] - f) / (ff[m + 1] - ff[m]), up = (ff[m + 2] - f) / (ff[m + 2] - ff[m + 1]);
+            const double v = down < up ? down : up;
+            out[(long)k * n_mels + m] = (v > 0.0 ? v : 0.0) * (2.0 / (ff[m + 2] - ff[m]));
+        }
+    }
+}
+
+DexWhisperConfig default_config() {
+    DexWhisperConfig c;
+    std::memset(&c, 0, sizeof c);
+    c.vocab_size = 51866; c.num_mel_bins = 128; c.d_model = 1280;
+    c.encoder_layers = 32; c.encoder_attention_heads = 20; c.encoder_ffn_dim = 5120;
+    c.decoder_layers = 32; c.decoder_attention_heads = 20; c.decoder_ffn_dim = 5120;
+    c.max_source_positions = 1500; c.max_target_positions = 448;
+    c.scale_embedding = 0; c.activation_gelu = 1;
+    return c;
+}
+
+// the family that is built; names the first field outside it
+int check_config(const DexWhisperConfig& c) {
+    if (c.activation_gelu != 1) return create_fail("%s: only 'gelu' (erf) is built", "activation_function");
+    if (c.scale_embedding != 0) return create_fail("%s: only False is built", "scale_embedding");
+    if (c.num_mel_bins < 1 || c.num_mel_bins > 128) return create_fail("%s: 1 .. 128", "num_mel_bins");
+    if (c.d_model < 64 || c.d_model % 64 || c.d_model > 8192) return create_fail("%s: a multiple of 64 in 64 .. 8192", "d_model");
+    if (c.encoder_attention_heads * 64 != c.d_model) return create_fail("%s: d_model / encoder_attention_heads must be 64", "encoder_attention_heads");
+    if (c.decoder_attention_heads * 64 != c.d_model) return create_fail("%s: d_model / decoder_attention_heads must be 64", "decoder_attention_heads");
+    if (c.encoder_layers < 1 || c.encoder_layers > 64) return create_fail("%s: 1 .. 64", "encoder_layers");
+    if (c.decoder_layers < 1 || c.decoder_layers > 64) return create_fail("%s: 1 .. 64", "decoder_layers");
+    if (c.encoder_ffn_dim < 64 || c.encoder_ffn_dim % 64 || c.encoder_ffn_dim > 65536) return create_fail("%s: a multiple of 64 up to 65536", "encoder_ffn_dim");
+    if (c.decoder_ffn_dim < 64 || c.decoder_ffn_dim % 64 || c.decoder_ffn_dim > 65536) return create_fail("%s: a multiple of 64 up to 65536", "decoder_ffn_dim");
+    if (c.vocab_size < 2 || c.vocab_size > (1 << 20)) return create_fail("%s: 2 .. 1048576", "vocab_size");
+    if (c.max_source_positions < 1 || c.max_source_positions > MAX_KEYS) return create_fail("%s: 1 .. 4096", "max_source_positions");
+    if (c.max_target_positions < 1 || c.max_target_positions > MAX_KEYS) return create_fail("%s: 1 .. 4096", "max_target_positions");
+    return DEX_OK;
+}
+
+}  // namespace
+
+struct DexWhisper : dex::WeightStore {
+    DexWhisper() : WeightStore("whisper ") {}
+    DexWhisperConfig c;
+    struct EncLayer { const float *ln1g, *ln1b, *wqkv, *bqkv, *wo, *bo, *ln2g, *ln2b, *w1, *b1, *w2, *b2; };
+    struct DecLayer { const float *ln1g, *ln1b, *wqkv, *bq, *bv, *wo, *bo, *ln2g, *ln2b, *wcq, *bcq, *wckv, *bckv, *wco, *bco,
+                      *ln3g, *ln3b, *w1, *b1, *w2, *b2; };
+    const float *conv1_w = nullptr, *conv1_b = nullptr, *conv2_w = nullptr, *conv2_b = nullptr, *enc_pos = nullptr, *enc_g = nullptr, *enc_be = nullptr;
+    const float *emb = nullptr, *embT = nullptr, *dec_pos = nullptr, *dec_g = nullptr, *dec_be = nullptr;
+    std::vector<EncLayer> enc;
+    std::vector<DecLayer> dec;
+    std::vector<double> tab_host;            // window | cos | sin | mel matrix
+    double* tab_dev = nullptr;
+    int mel_pad() const { return (c.num_mel_bins + 31) / 32 * 32; }
+    int vocab_pad() const { return (c.vocab_size + 63) / 64 * 64; }
+};
+
+namespace {
+
+const std::string ENC = "model.encoder.", DEC = "model.decoder.";
+std::string ek(int l, const char* what) { return ENC + "layers." + std::to_string(l) + "." + what; }
+std::string dk(int l, const char* what) { return DEC + "layers." + std::to_string(l) + "." + what; }
+
+void add_attn(DexWhisper* s, const std::string& p, int d) {
+    s->add(p + "k_proj.weight", {d, d});
+    s->add(p + "v_proj.weight", {d, d}); s->add(p + "v_proj.bias", {d});
+    s->add(p + "q_proj.weight", {d, d}); s->add(p + "q_proj.bias", {d});
+    s->add(p + "out_proj.weight", {d, d}); s->add(p + "out_proj.bias", {d});
+}
+void add_ln(DexWhisper* s, const std::string& p, int d) { s->add(p + ".weight", {d}); s->add(p + ".bias", {d}); }
+
+// HF's own order (WhisperForConditionalGeneration.state_dict() without proj_out.weight, which is the token embedding)
+void register_keys(DexWhisper* s) {
+    const DexWhisperConfig& c = s->c;
+    const int d = c.d_model;
+    s->add(ENC + "conv1.weight", {d, c.num_mel_bins, 3}); s->add(ENC + "conv1.bias", {d});
+    s->add(ENC + "conv2.weight", {d, d, 3}); s->add(ENC + "conv2.bias", {d});
+    s->add(ENC + "embed_positions.weight", {c.max_source_positions, d});
+    for (int l = 0; l < c.encoder_layers; ++l) {
+        add_attn(s, ek(l, "self_attn."), d); add_ln(s, ek(l, "self_attn_layer_norm"), d);
+        s->add(ek(l, "fc1.weight"), {c.encoder_ffn_dim, d}); s->add(ek(l, "fc1.bias"), {c.encoder_ffn_dim});
+        s->add(ek(l, "fc2.weight"), {d, c.encoder_ffn_dim}); s->add(ek(l, "fc2.bias"), {d});
+        add_ln(s, ek(l, "final_layer_norm"), d);
+    }
+    add_ln(s, ENC + "layer_norm", d);
+    s->add(DEC + "embed_tokens.weight", {c.vocab_size, d});
+    s->add(DEC + "embed_positions.weight", {c.max_target_positions, d});
+    for (int l = 0; l < c.decoder_layers; ++l) {
+        add_attn(s, dk(l, "self_attn."), d); add_ln(s, dk(l, "self_attn_layer_norm"), d);
+        add_attn(s, dk(l, "encoder_attn."), d); add_ln(s, dk(l, "encoder_attn_layer_norm"), d);
+        s->add(dk(l, "fc1.weight"), {c.decoder_ffn_dim, d}); s->add(dk(l, "fc1.bias"), {c.decoder_ffn_dim});
+        s->add(dk(l, "fc2.weight"), {d, c.decoder_ffn_dim}); s->add(dk(l, "fc2.bias"), {d});
+        add_ln(s, dk(l, "final_layer_norm"), d);
+    }
+    add_ln(s, DEC + "layer_norm", d);
+}
+
+// the [K = d][N = n d] operand of n projections side by side, and (bias) their biases with 0 where a projection has none
+const float* pack_side(DexWhisper* s, const std::string& p, std::initializer_list<const char*> names, int d, hipStream_t st, const float** bias) {
+    const int n = (int)names.size();
+    float* w = s->alloc((long)n * d * d);
+    float* b = bias ? s->alloc((long)n * d) : nullptr;
+    if (!w || (bias && !b)) return nullptr;
+    if (b) hipMemsetAsync(b, 0, (size_t)n * d * sizeof(float), st);
+    int j = 0;
+    for (const char* nm : names) {
+        pack_into(s->R(p + nm + ".weight"), w, 1, d, d, 1, n * d, j * d, nullptr, st);
+        if (b && s->raw.count(p + nm + ".bias")) hipMemcpyAsync(b + (long)j * d, s->R(p + nm + ".bias"), d * sizeof(float), hipMemcpyDeviceToDevice, st);
+        ++j;
+    }
+    if (bias) *bias = b;
+    return w;
+}
+
+int pack_all(DexWhisper* s, hipStream_t st) {
+    const DexWhisperConfig& c = s->c;
+    const int d = c.d_model;
+    s->conv1_w = dex::conv1d_operand(*s, s->R(ENC + "conv1.weight"), c.num_mel_bins, d, 3, s->mel_pad(), st); s->conv1_b = s->R(ENC + "conv1.bias");
+    s->conv2_w = pack(s, ENC + "conv2.weight", 1, d, d, 3, nullptr, st); s->conv2_b = s->R(ENC + "conv2.bias");
+    s->enc_pos = s->R(ENC + "embed_positions.weight");
+    s->enc_g = s->R(ENC + "layer_norm.weight"); s->enc_be = s->R(ENC + "layer_norm.bias");
+    s->enc.assign(c.encoder_layers, DexWhisper::EncLayer{});
+    for (int l = 0; l < c.encoder_layers && s->alloc_rc == DEX_OK; ++l) {
+        DexWhisper::EncLayer& L = s->enc[l];
+        L.wqkv = pack_side(s, ek(l, "self_attn."), {"q_proj", "k_proj", "v_proj"}, d, st, &L.bqkv);
+        L.wo = pack(s, ek(l, "self_attn.out_proj.weight"), 1, d, d, 1, nullptr, st); L.bo = s->R(ek(l, "self_attn.out_proj.bias"));
+        L.ln1g = s->R(ek(l, "self_attn_layer_norm.weight")); L.ln1b = s->R(ek(l, "self_attn_layer_norm.bias"));
+        L.w1 = pack(s, ek(l, "fc1.weight"), 1, c.encoder_ffn_dim, d, 1, nullptr, st); L.b1 = s->R(ek(l, "fc1.bias"));
+        L.w2 = pack(s, ek(l, "fc2.weight"), 1, d, c.encoder_ffn_dim, 1, nullptr, st); L.b2 = s->R(ek(l, "fc2.bias"));
+        L.ln2g = s->R(ek(l, "final_layer_norm.weight")); L.ln2b = s->R(ek(l, "final_layer_norm.bias"));
+    }
+    s->emb = s->R(DEC + "embed_tokens.weight"); s->dec_pos = s->R(DEC + "embed_positions.weight");
+    s->dec_g = s->R(DEC + "layer_norm.weight"); s->dec_be = s->R(DEC + "layer_norm.bias");
+    {
+        const int Vp = s->vocab_pad();
+        float* t = s->alloc((long)d * Vp);
+        if (t) {
+            hipMemsetAsync(t, 0, (size_t)d * Vp * sizeof(float), st);
+            pack_into(s->emb, t, 1, c.vocab_size, d, 1, Vp, 0, nullptr, st);
+        }
+        s->embT = t;
+    }
+    s->dec.assign(c.decoder_layers, DexWhisper::DecLayer{});
+    for (int l = 0; l < c.decoder_layers && s->alloc_rc == DEX_OK; ++l) {
+        DexWhisper::DecLayer& L = s->dec[l];
+        L.wqkv = pack_side(s, dk(l, "self_attn."), {"q_proj", "k_proj", "v_proj"}, d, st, nullptr);
+        L.bq = s->R(dk(l, "self_attn.q_proj.bias")); L.bv = s->R(dk(l, "self_attn.v_proj.bias"));
+        L.wo = pack(s, dk(l, "self_attn.out_proj.weight"), 1, d, d, 1, nullptr, st); L.bo = s->R(dk(l, "self_attn.out_proj.bias"));
+        L.ln1g = s->R(dk(l, "self_attn_layer_norm.weight")); L.ln1b = s->R(dk(l, "self_attn_layer_norm.bias"));
+        L.wcq = pack(s, dk(l, "encoder_attn.q_proj.weight"), 1, d, d, 1, nullptr, st); L.bcq = s->R(dk(l, "encoder_attn.q_proj.bias"));
+        L.wckv = pack_side(s, dk(l, "encoder_attn."), {"k_proj", "v_proj"}, d, st, &L.bckv);
+        L.wco = pack(s, dk(l, "encoder_attn.out_proj.weight"), 1, d, d, 1, nullptr, st); L.bco = s->R(dk(l, "encoder_attn.out_proj.bias"));
+        L.ln2g = s->R(dk(l, "encoder_attn_layer_norm.weight")); L.ln2b = s->R(dk(l, "encoder_attn_layer_norm.bias"));
+        L.w1 = pack(s, dk(l, "fc1.weight"), 1, c.decoder_ffn_dim, d, 1, nullptr, st); L.b1 = s->R(dk(l, "fc1.bias"));
+        L.w2 = pack(s, dk(l, "fc2.weight"), 1, d, c.decoder_ffn_dim, 1, nullptr, st); L.b2 = s->R(dk(l, "fc2.bias"));
+        L.ln3g = s->R(dk(l, "final_layer_norm.weight")); L.ln3b = s->R(dk(l, "final_layer_norm.bias"));
+    }
+    return DEX_OK;
+}
+
+// workspace (floats, every piece a multiple of 64): logspec (fp64) [B][T][n_mels] | mel [B][T][Mp] | c1 [B][T][d] | he, ye [B][S][d]
+// | qkv [B][S][3d] | ffe [B][S][ffn_e] | enc [B][S][d] | ckv [Ld][B][S][2d] | ck, cv [Ld][B][Tmax][d] | h, y, a [B][d] | ff [B][ffn_d]
+// | P (the largest [KS][B][N] of a step) | state (int): finished [B], count
+struct Ws { double* logspec; float *mel, *c1, *he, *ye, *qkv, *ffe, *enc, *ckv, *ck, *cv, *h, *y, *a, *ff, *P; int *fin, *count; size_t bytes; };
+Ws plan(const DexWhisper* s, void* ws, long B) {
+    const DexWhisperConfig& c = s->c;
+    const long S = c.max_source_positions, T = 2 * S, d = c.d_model, Tm = c.max_target_positions, Ld = c.decoder_layers;
+    Ws w{};
+    Taker tk(ws);
+    w.logspec = (double*)tk.take(2 * B * T * c.num_mel_bins);
+    w.mel = tk.take(B * T * s->mel_pad()); w.c1 = tk.take(B * T * d);
+    w.he = tk.take(B * S * d); w.ye = tk.take(B * S * d); w.qkv = tk.take(B * S * 3 * d); w.ffe = tk.take(B * S * c.encoder_ffn_dim);
+    w.enc = tk.take(B * S * d);
+    w.ckv = tk.take(Ld * B * S * 2 * d); w.ck = tk.take(Ld * B * Tm * d); w.cv = tk.take(Ld * B * Tm * d);
+    w.h = tk.take(B * d); w.y = tk.take(B * d); w.a = tk.take(B * d); w.ff = tk.take(B * c.decoder_ffn_dim);
+    long pn = (long)slabs((int)d) * 3 * d, q = (long)slabs((int)d) * c.decoder_ffn_dim;
+    pn = q > pn ? q : pn; q = (long)slabs(c.decoder_ffn_dim) * d;
+    pn = q > pn ? q : pn; q = (long)slabs((int)d) * c.vocab_size;
+    pn = q > pn ? q : pn;
+    w.P = tk.take(B * pn);
+    w.fin = (int*)tk.take(B + 64); w.count = w.fin + B;
+    w.bytes = tk.bytes();
+    return w;
+}
+
+// P = X [B][ldx] (K columns) x W [K][ldw] (N columns); returns the slabs
+int skinny(const float* X, int ldx, const float* W, int ldw, int K, int N, float* P, int B, hipStream_t st) {
+    const SkP p{X, ldx, W, ldw, K, N, P, B};
+    const dim3 grid((N + 63) / 64, slabs(K));
+    auto lds = [&](int rb) { return (size_t)(SK_ROWS * rb + 4 * rb * 64) * sizeof(float); };
+    if (B == 1) hipLaunchKernelGGL(wsp_skinny_kernel<1>, grid, dim3(256), lds(1), st, p);
+    else if (B <= 4) hipLaunchKernelGGL(wsp_skinny_kernel<4>, grid, dim3(256), lds(4), st, p);
+    else if (B <= 8) hipLaunchKernelGGL(wsp_skinny_kernel<8>, grid, dim3(256), lds(8), st, p);
+    else if (B <= 16) hipLaunchKernelGGL(wsp_skinny_kernel<16>, grid, dim3(256), lds(16), st, p);
+    else hipLaunchKernelGGL(wsp_skinny_kernel<32>, grid, dim3(256), lds(32), st, p);
+    return grid.y;
+}
+
+void finish(const float* P, int KS, int N, const float* bias, const float* res, float* out, int act, const float* g, const float* be, float* y,
+            int B, hipStream_t st) {
+    const FinP p{P, KS, (long)B * N, N, bias, res, out, act, g, be, y};
+    hipLaunchKernelGGL(wsp_finish_kernel, dim3(B), dim3(256), 0, st, p);
+}
+
+void enqueue_log_mel(DexWhisper* s, const float* wav, const int32_t* lengths_host, int B, int n, float* out, const Ws& w, hipStream_t st) {
+    const DexWhisperConfig& c = s->c;
+    const int T = 2 * c.max_source_positions, M = c.num_mel_bins;
+    MelP p{};
+    p.wav = wav; p.ld = n; p.N = (long)T * HOP; p.T = T; p.n_mels = M;
+    for (int b = 0; b < B; ++b) p.len.a[b] = lengths_host[b];
+    p.win = s->tab_dev; p.cs = s->tab_dev + NFFT; p.sn = s->tab_dev + 2 * NFFT; p.filt = s->tab_dev + 3 * NFFT; p.out = w.logspec;
+    hipLaunchKernelGGL(wsp_mel_kernel, dim3((T + MELF - 1) / MELF, B), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(wsp_mel_floor_kernel, dim3(B), dim3(1024), 0, st, w.logspec, out, T, M);
+}
+
+// the window, the twiddles and the mel matrix, on the device from the first front-end call on
+int ensure_tables(DexWhisper* s, hipStream_t st) {
+    if (s->tab_dev) return DEX_OK;
+    const int M = s->c.num_mel_bins;
+    s->tab_host.assign(3 * NFFT + (size_t)NBIN * M, 0.0);
+    for (int n = 0; n < NFFT; ++n) {
+        const double a = 2.0 * M_PI * n / NFFT;
+        s->tab_host[n] = 0.5 - 0.5 * std::cos(a); s->tab_host[NFFT + n] = std::cos(a); s->tab_host[2 * NFFT + n] = -std::sin(a);
+    }
+    mel_filters(M, s->tab_host.data() + 3 * NFFT);
+    DEX_HIPCHK(s, hipMalloc((void**)&s->tab_dev, s->tab_host.size() * sizeof(double)));
+    DEX_HIPCHK(s, hipMemcpyAsync(s->tab_dev, s->tab_host.data(), s->tab_host.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    return DEX_OK;
+}
+
+// mark (or null): an event recorded between the encoder and the cross-attention projections
+void enqueue_encoder(DexWhisper* s, const float* feat, int B, float* enc_out, const Ws& w, hipStream_t st, hipEvent_t mark = nullptr) {
+    const DexWhisperConfig& c = s->c;
+    const int S = c.max_source_positions, T = 2 * S, d = c.d_model, Mp = s->mel_pad();
+    const long total = (long)B * T * Mp;
+    hipLaunchKernelGGL(wsp_feat_cl_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, feat, w.mel, total, T, c.num_mel_bins, Mp);
+    gemm(w.mel, Mp, T, Mp, 3, 1, -1, T, s->conv1_w, d, 1, s->conv1_b, w.c1, 1, nullptr, nullptr, B, st);
+    gemm(w.c1, d, T, d, 3, 2, -1, S, s->conv2_w, d, 1, s->conv2_b, w.he, 1, s->enc_pos, nullptr, B, st, 1, 1, true);
+    const long rows = (long)B * S;
+    for (const DexWhisper::EncLayer& L : s->enc) {
+        layer_norm<false>(w.he, w.ye, rows, S, d, L.ln1g, L.ln1b, LN_EPS, nullptr, st);
+        linear(w.ye, d, L.wqkv, 3 * d, L.bqkv, w.qkv, 0, nullptr, nullptr, S, B, st);
+        dex::AttnP a{};
+        a.Q = w.qkv; a.ldq = 3 * d; a.qb = (long)S * 3 * d;
+        a.K = w.qkv + d; a.ldk = 3 * d; a.kb = a.qb;
+        a.V = w.qkv + 2 * d; a.ldv = 3 * d; a.vb = a.qb;
+        a.O = w.ye; a.ldo = d; a.ob = (long)S * d;
+        a.Nq = S; a.Nk = S; a.kv_len = nullptr; a.kv_len_add = 0; a.heads = c.encoder_attention_heads; a.scale = 0.125f; a.B = B; a.head_dim = 64;
+        dex::launch_attention(a, dex::PREC_FP32, st);
+        linear(w.ye, d, L.wo, d, L.bo, w.he, 0, w.he, nullptr, S, B, st);
+        layer_norm<false>(w.he, w.ye, rows, S, d, L.ln2g, L.ln2b, LN_EPS, nullptr, st);
+        linear(w.ye, d, L.w1, c.encoder_ffn_dim, L.b1, w.ffe, 1, nullptr, nullptr, S, B, st);
+        linear(w.ffe, c.encoder_ffn_dim, L.w2, d, L.b2, w.he, 0, w.he, nullptr, S, B, st);
+    }
+    layer_norm<false>(w.he, w.enc, rows, S, d, s->enc_g, s->enc_be, LN_EPS, nullptr, st);
+    if (enc_out) hipMemcpyAsync(enc_out, w.enc, (size_t)rows * d * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (mark) hipEventRecord(mark, st);
+    for (int l = 0; l < c.decoder_layers; ++l)                                           // the cross-attention k | v, once per utterance
+        linear(w.enc, d, s->dec[l].wckv, 2 * d, s->dec[l].bckv, w.ckv + (long)l * B * S * 2 * d, 0, nullptr, nullptr, S, B, st);
+}
+
+// one decoder position: w.h holds embed_tokens + embed_positions of position p; logits: leaves the partials of the logits in w.P
+// and returns their slabs
+int enqueue_step(DexWhisper* s, int p, int B, const Ws& w, hipStream_t st, bool logits = true) {
+    const DexWhisperConfig& c = s->c;
+    const int d = c.d_model, H = c.decoder_attention_heads, S = c.max_source_positions, Tm = c.max_target_positions, F = c.decoder_ffn_dim;
+    finish(nullptr, 0, d, nullptr, w.h, w.h, 0, s->dec[0].ln1g, s->dec[0].ln1b, w.y, B, st);
+    for (int l = 0; l < c.decoder_layers; ++l) {
+        const DexWhisper::DecLayer& L = s->dec[l];
+        int ks = skinny(w.y, d, L.wqkv, 3 * d, d, 3 * d, w.P, B, st);
+        AtP a{};
+        a.q = w.P; a.kn = w.P + d; a.vn = w.P + 2 * d; a.KS = ks; a.ss = (long)B * 3 * d; a.ldq = 3 * d; a.qbias = L.bq; a.kbias = nullptr; a.vbias = L.bv;
+        a.K = w.ck + (long)l * B * Tm * d; a.V = w.cv + (long)l * B * Tm * d; a.ldk = d; a.kb = (long)Tm * d; a.n = p + 1;
+        a.out = w.a; a.ldo = d; a.scale = 0.125f;
+        hipLaunchKernelGGL(wsp_attend_kernel, dim3(H, B), dim3(256), 0, st, a);
+        ks = skinny(w.a, d, L.wo, d, d, d, w.P, B, st);
+        finish(w.P, ks, d, L.bo, w.h, w.h, 0, L.ln2g, L.ln2b, w.y, B, st);
+        ks = skinny(w.y, d, L.wcq, d, d, d, w.P, B, st);
+        AtP x{};
+        x.q = w.P; x.KS = ks; x.ss = (long)B * d; x.ldq = d; x.qbias = L.bcq;
+        x.K = w.ckv + (long)l * B * S * 2 * d; x.V = x.K + d; x.ldk = 2 * d; x.kb = (long)S * 2 * d; x.n = S;
+        x.out = w.a; x.ldo = d; x.scale = 0.125f;
+        hipLaunchKernelGGL(wsp_attend_kernel, dim3(H, B), dim3(256), 0, st, x);
+        ks = skinny(w.a, d, L.wco, d, d, d, w.P, B, st);
+        finish(w.P, ks, d, L.bco, w.h, w.h, 0, L.ln3g, L.ln3b, w.y, B, st);
+        ks = skinny(w.y, d, L.w1, F, d, F, w.P, B, st);
+        finish(w.P, ks, F, L.b1, nullptr, w.ff, 1, nullptr, nullptr, nullptr, B, st);
+        ks = skinny(w.ff, F, L.w2, d, F, d, w.P, B, st);
+        const bool last = l + 1 == c.decoder_layers;
+        finish(w.P, ks, d, L.b2, w.h, w.h, 0, last ? s->dec_g : s->dec[l + 1].ln1g, last ? s->dec_be : s->dec[l + 1].ln1b, w.y, B, st);
+    }
+    return logits ? skinny(w.y, d, s->embT, s->vocab_pad(), d, c.vocab_size, w.P, B, st) : 0;
+}
+
+int ready(DexWhisper* s, int B, void* ws, size_t bytes, Ws* w) {
+    if (B < 1 || B > WB) return s->fail(DEX_ERR_ARG, "B must lie in [1, %d]", WB);
+    if (!ws) return s->fail(DEX_ERR_ARG, "null pointer argument");
+    *w = plan(s, ws, B);
+    if (bytes < w->bytes) return s->fail(DEX_ERR_WORKSPACE, "workspace too small (dex_whisper_workspace_bytes)");
+    return DEX_OK;
+}
+
+typedef Entry<DexWhisper> E;
+
+}  // namespace
+
+extern "C" {
+
+int dex_whisper_create(const DexWhisperConfig* cfg, DexWhisper** out) { return E::create(cfg, out, default_config, check_config, register_keys); }
+void dex_whisper_destroy(DexWhisper* s) {
+    if (s && s->tab_dev) hipFree(s->tab_dev);
+    E::destroy(s);
+}
+const char* dex_whisper_last_error(const DexWhisper* s) { return E::last_error(s); }
+int dex_whisper_load(DexWhisper* s, const char* key, const float* w_dev, const int64_t* shape, int ndim, dex_stream_t stream) {
+    return E::load(s, key, w_dev, shape, ndim, stream);
+}
+int dex_whisper_finalize(DexWhisper* s, dex_stream_t stream) { return E::finalize(s, stream, pack_all, "packing the whisper weights failed"); }
+int dex_whisper_num_weights(const DexWhisper* s) { return E::num_weights(s); }
+int dex_whisper_weight_info(const DexWhisper* s, int i, const char** key, int64_t shape[4], int* ndim) { return E::weight_info(s, i, key, shape, ndim); }
+
+size_t dex_whisper_workspace_bytes(const DexWhisper* s, int B) {
+    if (!s || B < 1 || B > WB) return 0;
+    return plan(s, nullptr, B).bytes;
+}
+
+int dex_whisper_mel_filters(int n_mels, double* out) {
+    if (n_mels < 1 || n_mels > 128 || !out) return DEX_ERR_ARG;
+    mel_filters(n_mels, out);
+    return DEX_OK;
+}
+
+int dex_whisper_log_mel(DexWhisper* s, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, float* out_dev, void* workspace_dev,
+                        size_t workspace_bytes, dex_stream_t stream) {
+    if (!s) return DEX_ERR_ARG;
+    if (!wav_dev || !lengths_host || !out_dev) return s->fail(DEX_ERR_ARG, "null pointer argument");
+    const long chunk = 2L * s->c.max_source_positions * HOP;
+    if (n_samples < 1 || n_samples > chunk) return s->fail(DEX_ERR_ARG, "n_samples must lie in [1, %ld] (one chunk; long-form audio is not built)", chunk);
+    Ws w;
+    if (int rc = ready(s, B, workspace_dev, workspace_bytes, &w)) return rc;
+    for (int b = 0; b < B; ++b)
+        if (lengths_host[b] < 1 || lengths_host[b] > n_samples) return s->fail(DEX_ERR_ARG, "row lengths must lie in [1, n_samples]");
+    if (int rc = ensure_tables(s, (hipStream_t)stream)) return rc;
+    enqueue_log_mel(s, wav_dev, lengths_host, B, n_samples, out_dev, w, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? DEX_OK : s->fail(DEX_ERR_HIP, "kernel launch failed");
+}
+
+int dex_whisper_encode(DexWhisper* s, const float* feat_dev, int B, float* enc_out_dev, float* ms_host, void* workspace_dev, size_t workspace_bytes,
+                       dex_stream_t stream) {
+    if (!s) return DEX_ERR_ARG;
+    if (!feat_dev) return s->fail(DEX_ERR_ARG, "null pointer argument");
+    Ws w;
+    if (int rc = ready(s, B, workspace_dev, workspace_bytes, &w)) return rc;
+    if (!s->finalized) return s->fail(DEX_ERR_STATE, "the whisper weights are not finalized (dex_whisper_finalize)");
+    if (!ms_host) {
+        enqueue_encoder(s, feat_dev, B, enc_out_dev, w, (hipStream_t)stream);
+        return hipGetLastError() == hipSuccess ? DEX_OK : s->fail(DEX_ERR_HIP, "kernel launch failed");
+    }
+    hipEvent_t ev[3];                                           // the measuring form (tools/whisper_bench.py): waits for the stream
+    for (hipEvent_t& e : ev) DEX_HIPCHK(s, hipEventCreate(&e));
+    hipEventRecord(ev[0], (hipStream_t)stream);
+    enqueue_encoder(s, feat_dev, B, enc_out_dev, w, (hipStream_t)stream, ev[1]);
+    hipEventRecord(ev[2], (hipStream_t)stream);
+    const hipError_t rc = hipEventSynchronize(ev[2]);
+    if (rc == hipSuccess) { hipEventElapsedTime(ms_host, ev[0], ev[1]); hipEventElapsedTime(ms_host + 1, ev[1], ev[2]); }
+    for (hipEvent_t& e : ev) hipEventDestroy(e);
+    return rc == hipSuccess && hipGetLastError() == hipSuccess ? DEX_OK : s->fail(DEX_ERR_HIP, "the encoder failed");
+}
+
+int dex_whisper_forward(DexWhisper* s, const int32_t* ids_dev, int B, int L, float* logits_dev, void* workspace_dev, size_t workspace_bytes,
+                        dex_stream_t stream) {
+    if (!s) return DEX_ERR_ARG;
+    if (!ids_dev || !logits_dev) return s->fail(DEX_ERR_ARG, "null pointer argument");
+    Ws w;
+    if (int rc = ready(s, B, workspace_dev, workspace_bytes, &w)) return rc;
+    if (!s->finalized) return s->fail(DEX_ERR_STATE, "the whisper weights are not finalized (dex_whisper_finalize)");
+    const DexWhisperConfig& c = s->c;
+    if (L < 1 || L > c.max_target_positions) return s->fail(DEX_ERR_ARG, "%d decoder positions: 1 .. max_target_positions = %d", L, c.max_target_positions);
+    hipStream_t st = (hipStream_t)stream;
+    for (int p = 0; p < L; ++p) {
+        hipLaunchKernelGGL(wsp_embed_kernel, dim3(B), dim3(256), 0, st, ids_dev, L, 0, p, c.vocab_size, s->emb, s->dec_pos, c.d_model, w.h);
+        const int ks = enqueue_step(s, p, B, w, st);
+        PickP k{};
+        k.P = w.P; k.KS = ks; k.ss = (long)B * c.vocab_size; k.V = c.vocab_size; k.logits = logits_dev + (long)p * c.vocab_size; k.ldl = (long)L * c.vocab_size;
+        k.next_pos = -1;
+        hipLaunchKernelGGL(wsp_pick_kernel, dim3(B), dim3(1024), 0, st, k);
+    }
+    return hipGetLastError() == hipSuccess ? DEX_OK : s->fail(DEX_ERR_HIP, "kernel launch failed");
+}
+
+int dex_whisper_generate(DexWhisper* s, const int32_t* prompt_host, int n_prompt, const uint8_t* suppress_dev, const uint8_t* begin_dev, int eos, int B,
+                         int max_new, int sync_every, int32_t* ids_dev, int32_t* lengths_dev, int* steps_host, void* workspace_dev,
+                         size_t workspace_bytes, dex_stream_t stream) {
+    if (!s) return DEX_ERR_ARG;
+    if (!prompt_host || !ids_dev || !lengths_dev || !steps_host) return s->fail(DEX_ERR_ARG, "null pointer argument");
+    Ws w;
+    if (int rc = ready(s, B, workspace_dev, workspace_bytes, &w)) return rc;
+    if (!s->finalized) return s->fail(DEX_ERR_STATE, "the whisper weights are not finalized (dex_whisper_finalize)");
+    const DexWhisperConfig& c = s->c;
+    if (n_prompt < 1 || n_prompt > c.max_target_positions)
+        return s->fail(DEX_ERR_ARG, "a prompt of %d ids: 1 .. max_target_positions = %d", n_prompt, c.max_target_positions);
+    for (int i = 0; i < n_prompt; ++i)
+        if (prompt_host[i] < 0 || prompt_host[i] >= c.vocab_size) return s->fail(DEX_ERR_ARG, "prompt id %d is outside the vocabulary of %d", prompt_host[i], c.vocab_size);
+    if (eos < 0 || eos >= c.vocab_size) return s->fail(DEX_ERR_ARG, "eos_token_id %d is outside the vocabulary of %d", eos, c.vocab_size);
+    if (max_new < 1 || sync_every < 0) return s->fail(DEX_ERR_ARG, "max_new must be >= 1 and sync_every >= 0");
+    hipStream_t st = (hipStream_t)stream;
+    const int room = c.max_target_positions - n_prompt, n_new = max_new < room ? max_new : room;      // never past the cache
+    const long n_ids = (long)B * max_new;
+    hipLaunchKernelGGL(wsp_fill_kernel, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, st, ids_dev, n_ids, eos);
+    DEX_HIPCHK(s, hipMemsetAsync(lengths_dev, 0, B * sizeof(int32_t), st));
+    DEX_HIPCHK(s, hipMemsetAsync(w.fin, 0, (B + 1) * sizeof(int), st));
+    int steps = 0;
+    if (n_new > 0) {
+        for (int p = 0; p < n_prompt - 1; ++p) {                                          // the prompt fills the cache; its logits are not needed
+            hipLaunchKernelGGL(wsp_embed_kernel, dim3(B), dim3(256), 0, st, (const int*)nullptr, 0, prompt_host[p], p, c.vocab_size, s->emb, s->dec_pos, c.d_model, w.h);
+            enqueue_step(s, p, B, w, st, false);
+        }
+        hipLaunchKernelGGL(wsp_embed_kernel, dim3(B), dim3(256), 0, st, (const int*)nullptr, 0, prompt_host[n_prompt - 1], n_prompt - 1, c.vocab_size, s->emb,
+                           s->dec_pos, c.d_model, w.h);
+        for (int i = 0; i < n_new; ++i) {
+            const int ks = enqueue_step(s, n_prompt - 1 + i, B, w, st);
+            PickP k{};
+            k.P = w.P; k.KS = ks; k.ss = (long)B * c.vocab_size; k.V = c.vocab_size; k.mask = i == 0 ? begin_dev : suppress_dev;
+            k.pick = 1; k.eos = eos; k.finished = w.fin; k.lengths = lengths_dev; k.count = w.count; k.ids = ids_dev; k.ld_ids = max_new; k.step = i;
+            k.emb = s->emb; k.pos = s->dec_pos; k.d = c.d_model; k.next_pos = i + 1 < n_new ? n_prompt + i : -1; k.h = w.h;
+            hipLaunchKernelGGL(wsp_pick_kernel, dim3(B), dim3(1024), 0, st, k);
+            steps = i + 1;
+            if (sync_every && steps % sync_every == 0 && steps < n_new) {
+                int done = 0;
+                DEX_HIPCHK(s, hipMemcpyAsync(&done, w.count, sizeof(int), hipMemcpyDeviceToHost, st));
+                DEX_HIPCHK(s, hipStreamSynchronize(st));
+                if (done >= B) break;
+            }
+        }
+    }
+    *steps_host = steps;
+    DEX_HIPCHK(s, hipStreamSynchronize(st));
+    return hipGetLastError() == hipSuccess ? DEX_OK : s->fail(DEX_ERR_HIP, "kernel launch failed");
+}
+
+int dex_whisper_attend(const float* q_dev, float* k_dev, float* v_dev, const float* new_k_dev, const float* new_v_dev, float* out_dev, int B, int heads,
+                       int n_keys, int cap, dex_stream_t stream) {
+    if (!q_dev || !k_dev || !v_dev || !out_dev || (new_k_dev == nullptr) != (new_v_dev == nullptr)) return DEX_ERR_ARG;
+    if (B < 1 || B > 65535 || heads < 1 || heads > 1024 || n_keys < 1 || n_keys > cap || cap > MAX_KEYS) return DEX_ERR_ARG;
+    AtP a{};
+    a.q = q_dev; a.kn = new_k_dev; a.vn = new_v_dev; a.KS = 1; a.ss = 0; a.ldq = heads * 64;
+    a.K = k_dev; a.V = v_dev; a.ldk = heads * 64; a.kb = (long)cap * heads * 64; a.n = n_keys; a.out = out_dev; a.ldo = heads * 64; a.scale = 0.125f;
+    hipLaunchKernelGGL(wsp_attend_kernel, dim3(heads, B), dim3(256), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
+}
+
+int dex_whisper_step_linear(const float* x_dev, const float* w_dev, float* y_dev, float* scratch_dev, size_t scratch_floats, int M, int K, int N, int form,
+                            dex_stream_t stream) {
+    if (!x_dev || !w_dev || !y_dev || M < 1 || M > WB || K < 64 || K % 64 || N < 64 || N % 64 || (form != 0 && form != 1)) return DEX_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (form == 1) {
+        linear(x_dev, K, w_dev, N, nullptr, y_dev, 0, nullptr, nullptr, M, 1, st);
+    } else {
+        if (!scratch_dev || scratch_floats < (size_t)slabs(K) * M * N) return DEX_ERR_WORKSPACE;
+        const int ks = skinny(x_dev, K, w_dev, N, K, N, scratch_dev, M, st);
+        finish(scratch_dev, ks, N, nullptr, nullptr, y_dev, 0, nullptr, nullptr, nullptr, M, st);
+    }
+    return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
+}
+
+int dex_whisper_pick(const float* logits_dev, int B, int V, const uint8_t* mask_dev, int eos, int32_t* finished_dev, int32_t* lengths_dev,
+                     int32_t* count_dev, int32_t* ids_dev, int ld_ids, int step, dex_stream_t stream) {
+    if (!logits_dev || !finished_dev || !lengths_dev || !count_dev || !ids_dev) return DEX_ERR_ARG;
+    if (B < 1 || B > 65535 || V < 1 || eos < 0 || eos >= V || step < 0 || step >= ld_ids) return DEX_ERR_ARG;
+    PickP k{};
+    k.P = logits_dev; k.KS = 1; k.V = V; k.mask = mask_dev; k.pick = 1; k.eos = eos; k.finished = finished_dev; k.lengths = lengths_dev; k.count = count_dev;
+    k.ids = ids_dev; k.ld_ids = ld_ids; k.step = step; k.next_pos = -1;
+    hipLaunchKernelGGL(wsp_pick_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, k);
+    return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
+}
+
+}  // extern "C"

@@ -161,6 +161,19 @@ def asr_scores(model, audio, texts, sr: int = 22050):
     return (preds, *asr.score_transcripts(texts, preds))
 
 
+def whisper_scores(model, spec, vocab, audio, texts, sr: int = 22050):
+    """The Whisper ASR score of ``synthesize_tokens``' list of int16 waveforms (``sr`` Hz) against the input texts, in the same order
+    -> (transcripts, cer_mean, cer_stderr, wer_mean, wer_stderr).  ``model`` is a ``whisper.Whisper`` with the checkpoint's weights
+    loaded, ``spec`` its ``GenerationSpec`` and ``vocab`` its token strings (whisper.py states the definitions and the two
+    departures: the resampler, and the reference's ``normalize_sentence`` in place of Whisper's English normaliser)."""
+    from . import whisper
+    if len(audio) != len(texts) or len(audio) < 1:
+        raise ValueError(f"whisper_scores: {len(audio)} waveforms against {len(texts)} texts")
+    if not isinstance(model, whisper.Whisper):
+        raise ValueError("whisper_scores: pass a whisper.Whisper with the checkpoint's weights loaded (the library ships none)")
+    return whisper.whisper_score(list(audio), texts, model=model, spec=spec, vocab=vocab, sr=sr)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--config", required=True, help="a reference base.yaml (GeDEX-TTS/config/*/base.yaml, DEX-TTS/config/*/base.yaml)")

@@ -1,0 +1,376 @@
+"""The Whisper ASR score on the device: the recogniser zero-shot TTS work reports its WER with (``asr.py`` stays the reference's
+wav2vec 2.0 CTC score; numbers from the two recognisers are not comparable).  HF's ``WhisperForConditionalGeneration`` in eval
+mode, fp32 throughout: log-mel front end, encoder, decoder with a key/value cache, greedy decoding.
+
+    WhisperConfig(...)                         HF's field names; defaults = openai/whisper-large-v3
+    Whisper(config=None, device='cuda'):       load_state_dict (HF keys), log_mel, encode, forward, generate, transcribe
+    GenerationSpec(prompt_ids, suppress_tokens, begin_suppress_tokens, eos_token_id);  GenerationSpec.from_generation_config(...)
+    load_vocab(path), decode(ids, vocab)       host only
+    whisper_score(wavs, texts, model=, spec=, vocab=) -> (transcripts, cer_mean, cer_stderr, wer_mean, wer_stderr)
+
+Everything runs in libdexamd.so (``csrc/whisper.hip``, C ABI ``dex_whisper_*``).  Nothing downloads and no checkpoint is shipped:
+weights, the generation config and the vocabulary come from dicts or local files the caller names.  A row's features, logits and ids
+are bitwise those of the row alone: every launch fixes its split and summation order from the config and the position.
+
+Definitions (the contract)
+
+Front end = ``WhisperFeatureExtractor``.  Input is 16 kHz; other rates go through ``wavprep.resample`` (kaiser_best), as in the other
+two scores.  A row is zero-padded to ``n_samples = 2 * max_source_positions * 160`` (480 000 for the real models); a longer row
+raises ``ValueError`` (long-form transcription is not built, and a metric must not truncate silently).  Reflect-pad by 200, periodic
+Hann(400), 400-point DFT at hop 160, power, the last frame dropped, mel (``num_mel_bins`` 80 or 128, Slaney scale and norm,
+0 - 8000 Hz; the matrix is built on the host in float64, ``mel_filters``), ``log10(max(., 1e-10))``, floored at the row's own maximum
+- 8, ``(x + 4) / 4``.  The device computes all of it in fp64 and rounds to fp32 once.
+
+Encoder.  ``conv1`` (k 3, p 1) + erf GELU, ``conv2`` (k 3, s 2, p 1) + GELU, ``+ embed_positions`` (loaded, not recomputed), pre-LN
+layers (``k_proj`` without bias, scale head_dim^-1/2 on q, GELU FFN), a final ``layer_norm``.  No attention mask: the padding is
+attended to, as in HF, so a batch row is the row alone by construction.
+
+Decoder step at position p.  Input ``embed_tokens[id] + embed_positions[p]``; per layer ``self_attn_layer_norm`` -> self-attention
+over cache positions 0 .. p -> residual; ``encoder_attn_layer_norm`` -> cross-attention over all ``max_source_positions`` encoder
+frames (its K and V are computed once per utterance) -> residual; ``final_layer_norm`` -> ``fc1`` -> GELU -> ``fc2`` -> residual;
+then ``decoder.layer_norm`` and logits = h x ``embed_tokens``^T.  ``forward`` runs through this cached step one position at a time;
+there is no other decoder path.
+
+Greedy decoding is the library's own definition, a stated subset of HF ``generate``.  The prompt positions are fed first.  At
+new-token step i ``suppress_tokens`` are set to -inf, at i = 0 ``begin_suppress_tokens`` as well, and the argmax takes the lowest
+index on ties.  A row is finished once it emits ``eos_token_id``; from then on its output is eos.  The loop ends when every row has
+finished, after ``max_new_tokens``, or when ``len(prompt) + i`` reaches ``max_target_positions``: it never writes past the cache.
+Not built: timestamps, temperature fallback, the compression-ratio, log-prob and no-speech thresholds, beams, language detection.
+
+Host syncs.  Token ids, the finished flags and each row's length stay on the device; a step needs no host value.  The host reads
+one finished-count every ``SYNC_EVERY`` = 8 steps to end early: a read drains the queue of launches the host has run ahead with
+(tens of microseconds, against a step that streams the decoder's weights), so one per step would serialise host and device, while
+at 8 an utterance decodes at most 7 steps past its end - a few percent of a sentence's 30 - 100 tokens.
+
+``decode`` is GPT-2 byte-level decoding: the token strings joined, each character mapped back through the 256-entry byte table, the
+bytes decoded as UTF-8 with replacement.  Ids >= ``eos_token_id`` are special and are skipped (in the ``.en`` and the multilingual
+vocabularies alike the specials start at ``<|endoftext|>``).
+
+WER normalisation is the reference's ``asr.normalize_sentence``, not Whisper's ``EnglishTextNormalizer``: numbers stay as written.
+
+Family built: head_dim 64 (every released size), erf GELU, ``scale_embedding=False``, learned decoder positions,
+``num_mel_bins`` <= 128; any other config raises ``NotImplementedError`` naming the field.  At most 32 rows run in one network call
+(the step's linears carry the batch in registers); larger batches are run 32 rows at a time.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import dataclasses
+import json
+import os
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._native import device_rows, i32_ptr, on_device, stream
+from ._wavnet import SAMPLING_RATE, NetHandle, WaveformNet
+from .asr import score_transcripts
+
+N_FFT, HOP = 400, 160
+MAX_ROWS = 32                       # DEX_WHISPER_MAX_B
+SYNC_EVERY = 8
+
+
+@dataclasses.dataclass(frozen=True)
+class WhisperConfig:
+    """HF ``WhisperConfig`` fields the network reads, with the values of openai/whisper-large-v3."""
+    vocab_size: int = 51866
+    num_mel_bins: int = 128
+    d_model: int = 1280
+    encoder_layers: int = 32
+    encoder_attention_heads: int = 20
+    encoder_ffn_dim: int = 5120
+    decoder_layers: int = 32
+    decoder_attention_heads: int = 20
+    decoder_ffn_dim: int = 5120
+    max_source_positions: int = 1500
+    max_target_positions: int = 448
+    scale_embedding: bool = False
+    activation_function: str = "gelu"
+
+
+class DexWhisperConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("vocab_size", "num_mel_bins", "d_model", "encoder_layers", "encoder_attention_heads", "encoder_ffn_dim",
+                                         "decoder_layers", "decoder_attention_heads", "decoder_ffn_dim", "max_source_positions",
+                                         "max_target_positions", "scale_embedding", "activation_gelu")]
+
+
+def _c_config(cfg: WhisperConfig) -> DexWhisperConfig:
+    c = DexWhisperConfig()
+    for name, _ in DexWhisperConfig._fields_[:-2]:
+        setattr(c, name, int(getattr(cfg, name)))
+    c.scale_embedding = int(bool(cfg.scale_embedding))
+    c.activation_gelu = int(cfg.activation_function == "gelu")
+    return c
+
+
+def mel_filters(n_mels: int) -> np.ndarray:
+    """The front end's mel matrix, float64 [201, n_mels] (``transformers.audio_utils.mel_filter_bank(201, n_mels, 0, 8000, 16000,
+    'slaney', 'slaney')``), as the library builds it.  Host only."""
+    out = np.empty((N_FFT // 2 + 1, int(n_mels)), np.float64)
+    if _lib.load().dex_whisper_mel_filters(int(n_mels), out.ctypes.data_as(C.POINTER(C.c_double))) != _lib.DEX_OK:
+        raise ValueError(f"mel_filters: n_mels must lie in [1, 128], got {n_mels}")
+    return out
+
+
+@dataclasses.dataclass(frozen=True)
+class GenerationSpec:
+    """One decode run: the prompt fed before the first new token, the ids never emitted, the ids not emitted first, and eos."""
+    prompt_ids: Tuple[int, ...]
+    suppress_tokens: Tuple[int, ...] = ()
+    begin_suppress_tokens: Tuple[int, ...] = ()
+    eos_token_id: int = 50257
+
+    @classmethod
+    def from_generation_config(cls, config, language: str = "en", task: str = "transcribe") -> "GenerationSpec":
+        """From HF's ``generation_config.json`` (a dict, the file, or the directory that holds it): the prompt
+        ``<|startoftranscript|> [<|lang|> <|task|>] <|notimestamps|>`` (the bracket for ``is_multilingual`` models) from the
+        file's own ``decoder_start_token_id``, ``lang_to_id``, ``task_to_id`` and ``no_timestamps_token_id``, and its
+        ``suppress_tokens``, ``begin_suppress_tokens`` and ``eos_token_id``.  An unknown language or task raises ``ValueError``."""
+        if not isinstance(config, dict):
+            path = os.fspath(config)
+            if os.path.isdir(path):
+                path = os.path.join(path, "generation_config.json")
+            with open(path, encoding="utf-8") as f:
+                config = json.load(f)
+        prompt = [int(config["decoder_start_token_id"])]
+        if config.get("is_multilingual", False):
+            lang = language if language.startswith("<|") else f"<|{language}|>"
+            if lang not in config.get("lang_to_id", {}):
+                raise ValueError(f"GenerationSpec: language {language!r} is not in the generation config's lang_to_id")
+            if task not in config.get("task_to_id", {}):
+                raise ValueError(f"GenerationSpec: task {task!r} is not in the generation config's task_to_id")
+            prompt += [int(config["lang_to_id"][lang]), int(config["task_to_id"][task])]
+        prompt.append(int(config["no_timestamps_token_id"]))
+        eos = config["eos_token_id"]
+        eos = int(eos[0] if isinstance(eos, (list, tuple)) else eos)
+        return cls(tuple(prompt), tuple(int(t) for t in config.get("suppress_tokens") or ()),
+                   tuple(int(t) for t in config.get("begin_suppress_tokens") or ()), eos)
+
+
+def _byte_table():
+    """GPT-2's printable stand-ins of the 256 byte values, inverted: character -> byte."""
+    bs = list(range(33, 127)) + list(range(161, 173)) + list(range(174, 256))
+    cs, n = bs[:], 0
+    for b in range(256):
+        if b not in bs:
+            bs.append(b)
+            cs.append(256 + n)
+            n += 1
+    return {chr(c): b for b, c in zip(bs, cs)}
+
+
+_BYTE_OF = _byte_table()
+
+
+def load_vocab(path) -> list:
+    """HF's ``vocab.json`` ({token: id}; the file or the directory that holds it) -> the token strings by id (``''`` where an id has
+    none).  Host only."""
+    path = os.fspath(path)
+    if os.path.isdir(path):
+        path = os.path.join(path, "vocab.json")
+    with open(path, encoding="utf-8") as f:
+        table = json.load(f)
+    out = [""] * (max(table.values()) + 1)
+    for tok, i in table.items():
+        out[int(i)] = tok
+    return out
+
+
+def decode(ids: Sequence[int], vocab: Sequence[str], eos_token_id: Optional[int] = None) -> str:
+    """GPT-2 byte-level decoding of ``ids``; ids at or above ``eos_token_id`` (default: the id of ``<|endoftext|>`` in ``vocab``,
+    else its length) are special and are skipped.  Host only."""
+    if eos_token_id is None:
+        eos_token_id = list(vocab).index("<|endoftext|>") if "<|endoftext|>" in vocab else len(vocab)
+    text = "".join(vocab[int(i)] for i in ids if 0 <= int(i) < eos_token_id and int(i) < len(vocab))
+    raw = bytearray()
+    for ch in text:
+        raw += bytes([_BYTE_OF[ch]]) if ch in _BYTE_OF else ch.encode("utf-8")
+    return raw.decode("utf-8", errors="replace")
+
+
+class _Handle(NetHandle):
+    """The workspace of this network is a function of the row count alone."""
+
+    def workspace(self, B: int) -> torch.Tensor:
+        need = int(self._fn("workspace_bytes")(self.h, B))
+        if need == 0:
+            raise ValueError(f"{B} rows: {self.no_workspace}")
+        return super(NetHandle, self).workspace(need)
+
+
+class Whisper(WaveformNet):
+    """HF's ``WhisperForConditionalGeneration`` in eval mode on one MI355X, fp32 (the module docstring states the definitions)."""
+    _prefix, _config_name, _no_workspace = "dex_whisper", "WhisperConfig", f"one network call takes 1 .. {MAX_ROWS} rows"
+    _c_config = staticmethod(_c_config)
+    _ignored = staticmethod(lambda key: False)
+    _handle = _Handle
+
+    def __init__(self, config: Optional[WhisperConfig] = None, device="cuda"):
+        super().__init__(config or WhisperConfig(), device)
+
+    @property
+    def n_samples(self) -> int:
+        """Samples of one chunk: 2 x max_source_positions x 160."""
+        return 2 * self.config.max_source_positions * HOP
+
+    def load_state_dict(self, sd, strict: bool = True):
+        """HF keys, with or without the ``model.`` prefix.  ``proj_out.weight`` is accepted and must equal
+        ``decoder.embed_tokens.weight`` bitwise (``RuntimeError`` otherwise: an untied head is another network)."""
+        out, proj = {}, None
+        for k, v in sd.items():
+            if k == "proj_out.weight":
+                proj = v
+            else:
+                out[k if k.startswith("model.") else "model." + k] = v
+        if proj is not None:
+            emb = out.get("model.decoder.embed_tokens.weight")
+            if emb is None or not torch.equal(torch.as_tensor(proj).cpu(), torch.as_tensor(emb).cpu()):
+                raise RuntimeError("proj_out.weight differs from model.decoder.embed_tokens.weight: only the tied head is built")
+        return super().load_state_dict(out, strict)
+
+    # ---- front end
+    def log_mel(self, wavs, lengths=None, sr: int = SAMPLING_RATE) -> torch.Tensor:
+        """``wavs`` [B, n] (or [n]) with ``lengths``, or a list of wavs, at ``sr`` Hz -> features [B, num_mel_bins, 2 x
+        max_source_positions] (``WhisperFeatureExtractor``).  What is stored past a row's length is not read.  A row longer than
+        ``n_samples`` raises ``ValueError``.  Needs no weights."""
+        what = "Whisper.log_mel"
+        wavs, lengths = self._at_16k(wavs, lengths, sr, what)
+        x, ln, one = device_rows(wavs, lengths, what, refuse=ValueError)
+        if int(ln.max()) > self.n_samples:
+            raise ValueError(f"{what}: a row of {int(ln.max())} samples is longer than one chunk of {self.n_samples} (long-form audio is not built)")
+        x = x[:, : self.n_samples].contiguous().to(self.device)
+        B, n = x.shape
+        out = torch.empty(B, self.config.num_mel_bins, 2 * self.config.max_source_positions, dtype=torch.float32, device=self.device)
+        ctx = self._ctx
+        for r in range(0, B, MAX_ROWS):
+            xb, ob, lb = x[r:r + MAX_ROWS], out[r:r + MAX_ROWS], np.ascontiguousarray(ln[r:r + MAX_ROWS])
+            ws = ctx.workspace(xb.shape[0])
+            with torch.cuda.device(self.device):
+                rc = ctx.lib.dex_whisper_log_mel(ctx.h, xb.data_ptr(), i32_ptr(lb), xb.shape[0], n, ob.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                 stream(self.device))
+            ctx.check(rc, "dex_whisper_log_mel")
+        return out[0] if one else out
+
+    def _features(self, features, what: str) -> torch.Tensor:
+        self._need_weights(what)
+        on_device(features, what, ValueError)
+        c = self.config
+        if features.dim() != 3 or tuple(features.shape[1:]) != (c.num_mel_bins, 2 * c.max_source_positions) or features.shape[0] < 1:
+            raise ValueError(f"{what}: expected features [B, {c.num_mel_bins}, {2 * c.max_source_positions}], got {tuple(features.shape)}")
+        return features.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def _encode(self, f: torch.Tensor, out, ms=None) -> torch.Tensor:
+        """The encoder of at most ``MAX_ROWS`` rows; its output and the cross-attention K / V stay in the workspace.  ``ms``: a
+        ``c_float * 2`` that receives the milliseconds of the encoder and of the cross K / V (the call then waits)."""
+        ctx = self._ctx
+        ws = ctx.workspace(f.shape[0])
+        with torch.cuda.device(self.device):
+            rc = ctx.lib.dex_whisper_encode(ctx.h, f.data_ptr(), f.shape[0], out.data_ptr() if out is not None else None, ms, ws.data_ptr(),
+                                            ws.numel(), stream(self.device))
+        ctx.check(rc, "dex_whisper_encode")
+        return ws
+
+    def encode(self, features: torch.Tensor) -> torch.Tensor:
+        """features [B, num_mel_bins, 2 x max_source_positions] -> the encoder's last hidden state [B, max_source_positions, d_model]."""
+        f = self._features(features, "Whisper.encode")
+        out = torch.empty(f.shape[0], self.config.max_source_positions, self.config.d_model, dtype=torch.float32, device=self.device)
+        for r in range(0, f.shape[0], MAX_ROWS):
+            self._encode(f[r:r + MAX_ROWS], out[r:r + MAX_ROWS])
+        return out
+
+    def forward(self, features: torch.Tensor, decoder_input_ids: torch.Tensor) -> torch.Tensor:
+        """features as for ``encode``, decoder_input_ids [B, L] (L <= max_target_positions) -> logits [B, L, vocab_size], through
+        the cached step one position at a time."""
+        what = "Whisper.forward"
+        f = self._features(features, what)
+        on_device(decoder_input_ids, what, ValueError)
+        c = self.config
+        if decoder_input_ids.dim() != 2 or decoder_input_ids.shape[0] != f.shape[0] or decoder_input_ids.shape[1] < 1:
+            raise ValueError(f"{what}: expected decoder_input_ids [{f.shape[0]}, L], got {tuple(decoder_input_ids.shape)}")
+        ids = decoder_input_ids.to(device=self.device, dtype=torch.int32).contiguous()
+        B, L = ids.shape
+        if L > c.max_target_positions:
+            raise ValueError(f"{what}: {L} decoder positions, max_target_positions is {c.max_target_positions}")
+        if int(ids.min()) < 0 or int(ids.max()) >= c.vocab_size:
+            raise ValueError(f"{what}: decoder_input_ids must lie in [0, vocab_size = {c.vocab_size})")
+        out = torch.empty(B, L, c.vocab_size, dtype=torch.float32, device=self.device)
+        ctx = self._ctx
+        for r in range(0, B, MAX_ROWS):
+            fb, ib, ob = f[r:r + MAX_ROWS], ids[r:r + MAX_ROWS], out[r:r + MAX_ROWS]
+            ws = self._encode(fb, None)
+            with torch.cuda.device(self.device):
+                rc = ctx.lib.dex_whisper_forward(ctx.h, ib.data_ptr(), fb.shape[0], L, ob.data_ptr(), ws.data_ptr(), ws.numel(), stream(self.device))
+            ctx.check(rc, "dex_whisper_forward")
+        return out
+
+    __call__ = forward
+
+    def _masks(self, spec: GenerationSpec):
+        V = self.config.vocab_size
+        for name in ("prompt_ids", "suppress_tokens", "begin_suppress_tokens"):
+            bad = [t for t in getattr(spec, name) if not 0 <= int(t) < V]
+            if bad:
+                raise ValueError(f"Whisper.generate: {name} holds {bad[0]}, outside the vocabulary of {V}")
+        sup = np.zeros(V, np.uint8)
+        sup[list(spec.suppress_tokens)] = 1
+        beg = sup.copy()
+        beg[list(spec.begin_suppress_tokens)] = 1
+        return torch.from_numpy(sup).to(self.device), torch.from_numpy(beg).to(self.device)
+
+    def generate(self, features_or_wavs, spec: GenerationSpec, max_new_tokens: Optional[int] = None, lengths=None, sr: int = SAMPLING_RATE):
+        """Greedy decoding (the module docstring's definition) of features [B, num_mel_bins, frames], or of wavs as ``log_mel`` takes
+        them -> (ids [B, n] int32, a row padded with eos after its end; lengths [B] int32, the tokens before a row's eos), both on the
+        device.  n is the number of steps decoded: at most ``max_new_tokens`` and ``max_target_positions - len(prompt)``."""
+        what = "Whisper.generate"
+        self._need_weights(what)
+        c = self.config
+        if not spec.prompt_ids or len(spec.prompt_ids) > c.max_target_positions:
+            raise ValueError(f"{what}: a prompt of {len(spec.prompt_ids)} ids, max_target_positions is {c.max_target_positions}")
+        if torch.is_tensor(features_or_wavs) and features_or_wavs.dim() == 3:
+            f = self._features(features_or_wavs, what)
+        else:
+            f = self.log_mel(features_or_wavs, lengths, sr)
+            f = f[None] if f.dim() == 2 else f
+        room = c.max_target_positions - len(spec.prompt_ids)
+        max_new = room if max_new_tokens is None else int(max_new_tokens)
+        if max_new < 1:
+            raise ValueError(f"{what}: max_new_tokens must be >= 1 (and the prompt leave room in the cache), got {max_new}")
+        sup, beg = self._masks(spec)
+        prompt = np.ascontiguousarray(np.asarray(spec.prompt_ids, np.int32))
+        B = f.shape[0]
+        ids = torch.empty(B, max_new, dtype=torch.int32, device=self.device)
+        lens = torch.empty(B, dtype=torch.int32, device=self.device)
+        ctx, steps, n = self._ctx, C.c_int(0), 0
+        for r in range(0, B, MAX_ROWS):
+            fb, ib, lb = f[r:r + MAX_ROWS], ids[r:r + MAX_ROWS], lens[r:r + MAX_ROWS]
+            ws = self._encode(fb, None)
+            with torch.cuda.device(self.device):
+                rc = ctx.lib.dex_whisper_generate(ctx.h, i32_ptr(prompt), len(prompt), sup.data_ptr(), beg.data_ptr(), int(spec.eos_token_id),
+                                                  fb.shape[0], max_new, SYNC_EVERY, ib.data_ptr(), lb.data_ptr(), C.byref(steps), ws.data_ptr(),
+                                                  ws.numel(), stream(self.device))
+            ctx.check(rc, "dex_whisper_generate")
+            n = max(n, steps.value)
+        return ids[:, :n], lens
+
+    def transcribe(self, wavs, spec: GenerationSpec, vocab: Sequence[str], lengths=None, sr: int = SAMPLING_RATE,
+                   max_new_tokens: Optional[int] = None):
+        """``wavs`` as ``log_mel`` takes them -> a list of transcripts (``decode`` of each row's tokens; one device-to-host copy)."""
+        ids, lens = self.generate(wavs, spec, max_new_tokens, lengths, sr)
+        ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
+        return [decode(ids[b, : int(lens[b])], vocab, spec.eos_token_id) for b in range(ids.shape[0])]
+
+
+def whisper_score(wavs, texts: Sequence[str], model: Optional[Whisper] = None, spec: Optional[GenerationSpec] = None,
+                  vocab: Optional[Sequence[str]] = None, sr: int = SAMPLING_RATE, lengths=None):
+    """Every wav transcribed by ``model``; CER and WER of ``asr.normalize_sentence(transcript)`` against
+    ``asr.normalize_sentence(text)`` (the reference's normaliser, not Whisper's: numbers stay as written) ->
+    (transcripts, cer_mean, cer_stderr, wer_mean, wer_stderr), the errors ``np.std / sqrt(n)``."""
+    if not isinstance(model, Whisper) or spec is None or vocab is None:
+        raise ValueError("whisper_score: pass model=Whisper(...) with the checkpoint's weights loaded, spec= and vocab= (the library ships none)")
+    preds = model.transcribe(wavs, spec, vocab, lengths, sr)
+    if len(preds) != len(texts) or not preds:
+        raise ValueError(f"whisper_score: {len(texts)} texts against {len(preds)} wavs")
+    return (preds, *score_transcripts(texts, preds))

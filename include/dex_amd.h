@@ -679,6 +679,75 @@ int  dex_wavlm_hidden(DexWavlm* w, const float* wav_dev, const int32_t* lengths_
 int  dex_wavlm_embed(DexWavlm* w, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, int do_normalize,
                      float* embed_dev, void* workspace_dev, size_t workspace_bytes, dex_stream_t stream);
 
+/* ---- Whisper ASR score: HF's WhisperForConditionalGeneration in eval mode (log-mel front end of WhisperFeatureExtractor, encoder,
+ * decoder with a key/value cache, greedy decoding), in fp32.  The family built: head_dim 64, erf GELU, scale_embedding = False,
+ * learned decoder positions, num_mel_bins <= 128.  One workspace carries a batch from dex_whisper_encode (encoder output, the
+ * cross-attention keys and values of every decoder layer) through dex_whisper_forward / dex_whisper_generate (the self-attention
+ * cache, the decode state), so those calls take the same B and the same workspace.  A row's results do not depend on its batch:
+ * every launch fixes its split and summation order from the config and the position.  Bad arguments return an error code, with a
+ * message in the handle's last error, before anything is enqueued.  dex_tts_amd/whisper.py states the definitions. */
+typedef struct DexWhisper DexWhisper;
+#define DEX_WHISPER_MAX_B 32
+#define DEX_WHISPER_N_FFT 400
+#define DEX_WHISPER_HOP 160
+typedef struct {
+    int32_t vocab_size, num_mel_bins, d_model;
+    int32_t encoder_layers, encoder_attention_heads, encoder_ffn_dim;
+    int32_t decoder_layers, decoder_attention_heads, decoder_ffn_dim;
+    int32_t max_source_positions, max_target_positions;
+    int32_t scale_embedding;                          /* 0 (the only one built) */
+    int32_t activation_gelu;                          /* 1 = 'gelu' (the only one built) */
+} DexWhisperConfig;
+/* NULL = the whisper-large-v3 values.  DEX_ERR_ARG (and *out = NULL) for a config outside the family that is built. */
+int  dex_whisper_create(const DexWhisperConfig* cfg, DexWhisper** out);
+void dex_whisper_destroy(DexWhisper* w);
+const char* dex_whisper_last_error(const DexWhisper* w);
+/* one weight under its HF state-dict key (model.encoder.conv1.weight ..., model.decoder.layer_norm.bias); stream-ordered */
+int  dex_whisper_load(DexWhisper* w, const char* key, const float* w_dev, const int64_t* shape, int ndim, dex_stream_t stream);
+int  dex_whisper_finalize(DexWhisper* w, dex_stream_t stream);
+int  dex_whisper_num_weights(const DexWhisper* w);
+int  dex_whisper_weight_info(const DexWhisper* w, int i, const char** key, int64_t shape[4], int* ndim);
+size_t dex_whisper_workspace_bytes(const DexWhisper* w, int B);                  /* 0 for bad arguments; B <= DEX_WHISPER_MAX_B */
+/* host only: the mel filter bank [201][n_mels] in float64 (Slaney scale and norm, 0 - 8000 Hz at 16 kHz) */
+int  dex_whisper_mel_filters(int n_mels, double* out);
+/* wav_dev [B, n_samples] at 16 kHz, row b lengths_host[b] samples (what lies past them is not read), n_samples <= 2 x
+ * max_source_positions x 160 -> out_dev [B, num_mel_bins, 2 x max_source_positions].  Needs no weights. */
+int  dex_whisper_log_mel(DexWhisper* w, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, float* out_dev,
+                         void* workspace_dev, size_t workspace_bytes, dex_stream_t stream);
+/* feat_dev [B, num_mel_bins, 2 x max_source_positions] -> the encoder output and every decoder layer's cross-attention keys and
+ * values, kept in the workspace; enc_out_dev [B, max_source_positions, d_model] (or NULL) receives a copy of the encoder output.
+ * ms_host [2] (or NULL; the measuring form, which waits for the stream) receives the milliseconds of the encoder and of the
+ * cross-attention projections. */
+int  dex_whisper_encode(DexWhisper* w, const float* feat_dev, int B, float* enc_out_dev, float* ms_host, void* workspace_dev,
+                        size_t workspace_bytes, dex_stream_t stream);
+/* after dex_whisper_encode: ids_dev [B, L] int32 (every id in [0, vocab): the caller's check), fed one position at a time through
+ * the cached step -> logits_dev [B, L, vocab] */
+int  dex_whisper_forward(DexWhisper* w, const int32_t* ids_dev, int B, int L, float* logits_dev, void* workspace_dev, size_t workspace_bytes,
+                         dex_stream_t stream);
+/* after dex_whisper_encode: greedy decoding.  prompt_host [n_prompt] feeds positions 0 .. n_prompt - 1 of every row; suppress_dev /
+ * begin_dev [vocab] bytes (non-zero = -inf; begin_dev holds at the first new token and includes suppress_dev).  ids_dev [B, max_new]
+ * is filled with eos, then with the tokens; lengths_dev [B] = the tokens of a row before its eos.  The loop ends after max_new
+ * tokens, when position max_target_positions is reached, or when a read of the finished count (every sync_every steps; 0 = never)
+ * finds every row finished; *steps_host = the tokens decoded.  Synchronises the stream before returning. */
+int  dex_whisper_generate(DexWhisper* w, const int32_t* prompt_host, int n_prompt, const uint8_t* suppress_dev, const uint8_t* begin_dev,
+                          int eos, int B, int max_new, int sync_every, int32_t* ids_dev, int32_t* lengths_dev, int* steps_host,
+                          void* workspace_dev, size_t workspace_bytes, dex_stream_t stream);
+/* the cached single-query attention alone (head_dim 64): q_dev [B, heads x 64], k_dev / v_dev [B, cap, heads x 64] over keys
+ * 0 .. n_keys - 1 -> out_dev [B, heads x 64], scores scaled by 1 / 8.  new_k_dev / new_v_dev [B, heads x 64] (or both NULL) are
+ * first appended at position n_keys - 1, as the self-attention of a step does. */
+int  dex_whisper_attend(const float* q_dev, float* k_dev, float* v_dev, const float* new_k_dev, const float* new_v_dev, float* out_dev,
+                        int B, int heads, int n_keys, int cap, dex_stream_t stream);
+/* one linear of the decoder step alone, y_dev [M, N] = x_dev [M, K] x w_dev [K, N] (M <= 32, K and N multiples of 64): form 0 the
+ * skinny-M streaming kernel and its consumer (scratch_dev: dex_whisper_step_linear's partials, at least ceil(K / 64) x M x N
+ * floats), form 1 launch_igemm - for tests and for the measurement of the two against the weight's bytes */
+int  dex_whisper_step_linear(const float* x_dev, const float* w_dev, float* y_dev, float* scratch_dev, size_t scratch_floats, int M, int K,
+                             int N, int form, dex_stream_t stream);
+/* the greedy step tail alone: logits_dev [B, V], mask_dev [V] bytes (or NULL) -> ids_dev [B * ld_ids] at column `step`: eos for a
+ * row whose finished_dev flag is set, else the first index of the maximum of the unmasked logits; emitting eos sets the flag and
+ * adds one to *count_dev, any other id adds one to lengths_dev[b] */
+int  dex_whisper_pick(const float* logits_dev, int B, int V, const uint8_t* mask_dev, int eos, int32_t* finished_dev, int32_t* lengths_dev,
+                      int32_t* count_dev, int32_t* ids_dev, int ld_ids, int step, dex_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
