@@ -356,6 +356,23 @@ __global__ __launch_bounds__(256) void igemm_lp_ss_kernel(const IGemmP p) {
 // Its epilogue is the unpatchify scatter only (bias, output mask, crop): everything that depends on the token row is computed
 // once for the whole walk.
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// Phase stamps of the column walkers (-DDEX_TIMING builds only, tools/dit_ends_stamps): cycles of thread 0 of a workgroup between
+// consecutive stamps, written to nw_dbg[workgroup * 8 + k] (k = 7: the whole workgroup); the tool sets the pointer (nw_set_dbg).
+#ifdef DEX_TIMING
+__device__ long long* nw_dbg = nullptr;
+void nw_set_dbg(long long* d) { (void)hipMemcpyToSymbol(HIP_SYMBOL(nw_dbg), &d, sizeof d); }
+#define NSTAMP_DECL long long tk[8] = {0, 0, 0, 0, 0, 0, 0, 0}; const long long tk0 = __builtin_readcyclecounter(); long long tlast = tk0;
+#define NSTAMP(k) do { const long long now_ = __builtin_readcyclecounter(); tk[k] += now_ - tlast; tlast = now_; } while (0)
+#define NSTAMP_STORE()                                                                                                \
+    if (nw_dbg && threadIdx.x == 0) {                                                                                 \
+        tk[7] = __builtin_readcyclecounter() - tk0;                                                                   \
+        for (int k_ = 0; k_ < 8; ++k_) nw_dbg[((long)blockIdx.y * gridDim.x + blockIdx.x) * 8 + k_] = tk[k_];         \
+    }
+#else
+#define NSTAMP_DECL
+#define NSTAMP(k) do {} while (0)
+#define NSTAMP_STORE()
+#endif
 // BM rows per workgroup, BM / 16 waves (a wave = 32 rows x 32 of the tile's 64 columns).  BM = 128 (round 6): every 64-column weight
 // tile a workgroup stages serves 128 rows instead of 64 (650 -> 360 MB of L2 -> LDS weight traffic per launch at DEX B = 32) - measured
 // no faster, so it is opt-in (launch_nwalk).
@@ -384,6 +401,7 @@ __global__ __launch_bounds__(BM * 4) void igemm_lp_nwalk_kernel(const IGemmP p) 
     const int b = blockIdx.z;
     const int M = p.Ho * p.Wo;
     const int m0 = blockIdx.x * BM;
+    NSTAMP_DECL
     const int ntile_all = p.N / BN;
     const int ntile = ntile_all / (int)gridDim.y, nt_first = blockIdx.y * ntile;      // this workgroup's share of the column tiles
     const float* Ab = p.A + (long)b * p.a_bstride + p.a_coff;
@@ -449,6 +467,7 @@ __global__ __launch_bounds__(BM * 4) void igemm_lp_nwalk_kernel(const IGemmP p) 
     NW_LOAD_LO(0)
 #endif
     if constexpr (!DMA) { NW_LOAD_B(0) }
+    NSTAMP(0);                                            // first weight tile requested
 #pragma unroll
     for (int a0 = 0; a0 < AIT; a0 += ABATCH) {
         float4 f0[ABATCH], f1[ABATCH];
@@ -495,7 +514,9 @@ __global__ __launch_bounds__(BM * 4) void igemm_lp_nwalk_kernel(const IGemmP p) 
             *reinterpret_cast<uint4*>(As + row * LDS_LD + k8) = v;
         }
     }
+    NSTAMP(1);                                            // rows loaded, LayerNorm + modulate, A tile and first weight tile written
     __syncthreads();
+    NSTAMP(2);
     const u16* ap = As + (wm * (MT * 32) + i) * LDS_LD + hh * 8;
     const u16* bp = Bs + (wn * 32 + i) * LDS_LD + hh * 8;            // (DMA: the ring slot's piece (wn, 0), set per tile)
     // unpatchify scatter without activation / gate / residual (the FinalLayer): everything that depends on the ROW only - token
@@ -589,6 +610,7 @@ __global__ __launch_bounds__(BM * 4) void igemm_lp_nwalk_kernel(const IGemmP p) 
             acc[0] = DEX_MFMA_LP(*reinterpret_cast<const lp8*>(blp + ks * 16), afr[ks], acc[0], 0, 0, 0);
 #endif
         }
+        NSTAMP(3);                                        // fragment reads + MFMA chain
         {
             // values first (the mask / bias loads are consumed here, once), then the stores: a store under a per-lane branch that still
             // depends on a load gets an s_waitcnt vmcnt(0) of its own, which also drains every earlier STORE
@@ -643,6 +665,7 @@ __global__ __launch_bounds__(BM * 4) void igemm_lp_nwalk_kernel(const IGemmP p) 
                 }
             }
         }
+        NSTAMP(4);                                        // scatter issued
         if (!DMA && nt + 1 < ntile) {
             __syncthreads();                              // every wave is done with this weight tile
             NW_STORE_B()
@@ -653,6 +676,160 @@ __global__ __launch_bounds__(BM * 4) void igemm_lp_nwalk_kernel(const IGemmP p) 
         }
     }
     if constexpr (DMA) { NW_FLUSH() }
+    NSTAMP_STORE()
+}
+
+// ---- small-grid form of the column walker (B = 1: 21 row tiles).  With one 64-column tile per 64-row workgroup the launch is
+// N / 64 = 32 workgroups per row tile - 352 at the headline shape, two rounds on part of the chip - and each of them stages (loads,
+// LayerNorms, modulates, rounds) the same 64 rows, then passes its weight tile through registers and LDS behind a second barrier.
+// Here a workgroup owns 32 rows and FOUR 64-column tiles, one per wave: the rows are staged once per 256 columns (the row statistics
+// run over the row's 32 lanes as above), and each wave's weight fragments are requested at kernel entry straight into operand
+// registers from the fragment-ordered twin (IGemmP::Wfrag, 1 KB contiguous per wave and K step) - no weight LDS tile, one barrier.
+// 21 x 8 = 168 workgroups: one round.  The product (transposed, K steps 0..15 in order) and the scatter are the walker's, to the bit.
+template <int K>
+__global__ __launch_bounds__(256) void igemm_lp_nwalk_kernel_small(const IGemmP p) {
+    constexpr int BM = 32, NTHR = 256, LDS_LD = K + 8, KC = K / 8, AIT = BM * KC / NTHR;
+    static_assert(KC == 32 && AIT * NTHR == BM * KC, "a row = 32 lanes of 8 values");
+    __shared__ __attribute__((aligned(16))) u16 As[BM * LDS_LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i = lane & 31, hh = lane >> 5;
+    const int b = blockIdx.z;
+    const int M = p.Ho * p.Wo;
+    const int m0 = blockIdx.x * BM;
+    const int ct = blockIdx.y * 4 + wave;                 // this wave's 64-column tile
+    NSTAMP_DECL
+    const float* Ab = p.A + (long)b * p.a_bstride + p.a_coff;
+    const float* mrow = p.inmask ? p.inmask + (long)b * p.mask_bstride : nullptr;
+    const int step = p.step + b * p.row_bstride;
+    const float* lsh = p.ln_shift ? p.ln_shift + (long)step * p.ln_step_stride : nullptr;
+    const float* lsc = p.ln_scale ? p.ln_scale + (long)step * p.ln_step_stride : nullptr;
+    // the rows first, the weight fragments behind them: the staging waits for the rows only
+    const int k8 = (tid % KC) * 8;                        // (the same K chunk for each of a thread's AIT rows)
+    float4 f0[AIT], f1[AIT];
+    float mk[AIT];
+#pragma unroll
+    for (int j = 0; j < AIT; ++j) {
+        const int row = (tid + NTHR * j) / KC;
+        const int m = m0 + row;
+        const int mm = m < M ? m : 0;
+        const float* src = Ab + (long)mm * p.lda + k8;
+        f0[j] = *reinterpret_cast<const float4*>(src);
+        f1[j] = *reinterpret_cast<const float4*>(src + 4);
+        const float mv = mrow ? mrow[(mm % p.Wi) * p.inmask_ws] : 1.f;
+        mk[j] = m < M ? mv : 0.f;
+    }
+    float4 sc0 = make_float4(0.f, 0.f, 0.f, 0.f), sc1 = sc0, sh0 = sc0, sh1 = sc0;
+    if (lsh) {
+        sc0 = *reinterpret_cast<const float4*>(lsc + k8); sc1 = *reinterpret_cast<const float4*>(lsc + k8 + 4);
+        sh0 = *reinterpret_cast<const float4*>(lsh + k8); sh1 = *reinterpret_cast<const float4*>(lsh + k8 + 4);
+    }
+    union Fr { uint4 u; lp8 v; };
+    Fr wfr[2][K / 16];                                    // [32-column half][K step]: piece (wn, ks) of tile ct, 16 B per lane
+    {
+        const uint4* Wf = reinterpret_cast<const uint4*>(p.Wfrag) + (long)ct * (2 * (K / 16) * 64) + lane;
+#pragma unroll
+        for (int wn = 0; wn < 2; ++wn)
+#pragma unroll
+            for (int ks = 0; ks < K / 16; ++ks) wfr[wn][ks].u = Wf[(wn * (K / 16) + ks) * 64];
+    }
+    NSTAMP(0);                                            // rows and weight fragments requested
+#pragma unroll
+    for (int j = 0; j < AIT; ++j) {
+        const int row = (tid + NTHR * j) / KC;
+        float4 a = f0[j], c = f1[j];
+        if (lsh) {
+            float s = (a.x + a.y) + (a.z + a.w) + (c.x + c.y) + (c.z + c.w);
+#pragma unroll
+            for (int o = 1; o < KC; o <<= 1) s += __shfl_xor(s, o);
+            const float mean = s * (1.f / (float)K);
+            a.x -= mean; a.y -= mean; a.z -= mean; a.w -= mean; c.x -= mean; c.y -= mean; c.z -= mean; c.w -= mean;
+            float q = a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w + c.x * c.x + c.y * c.y + c.z * c.z + c.w * c.w;
+#pragma unroll
+            for (int o = 1; o < KC; o <<= 1) q += __shfl_xor(q, o);
+            const float rstd = rsqrtf(q * (1.f / (float)K) + 1e-6f);
+            a.x = a.x * rstd * (1.f + sc0.x) + sh0.x; a.y = a.y * rstd * (1.f + sc0.y) + sh0.y;
+            a.z = a.z * rstd * (1.f + sc0.z) + sh0.z; a.w = a.w * rstd * (1.f + sc0.w) + sh0.w;
+            c.x = c.x * rstd * (1.f + sc1.x) + sh1.x; c.y = c.y * rstd * (1.f + sc1.y) + sh1.y;
+            c.z = c.z * rstd * (1.f + sc1.z) + sh1.z; c.w = c.w * rstd * (1.f + sc1.w) + sh1.w;
+        }
+        const float m_ = mk[j];
+        uint4 v;
+        v.x = pack2_lp(a.x * m_, a.y * m_); v.y = pack2_lp(a.z * m_, a.w * m_);
+        v.z = pack2_lp(c.x * m_, c.y * m_); v.w = pack2_lp(c.z * m_, c.w * m_);
+        *reinterpret_cast<uint4*>(As + row * LDS_LD + k8) = v;
+    }
+    NSTAMP(1);                                            // rows back, LayerNorm + modulate, A tile written
+    lds_barrier();                                        // (LDS only: the weight fragments stay in flight)
+    NSTAMP(2);
+    lp8 afr[K / 16];
+    {
+        const u16* ap = As + i * LDS_LD + hh * 8;
+#pragma unroll
+        for (int ks = 0; ks < K / 16; ++ks) afr[ks] = *reinterpret_cast<const lp8*>(ap + ks * 16);
+    }
+    // row-only terms of the unpatchify scatter, once (as in the walker)
+    int u_pix, u_f, u_w;
+    {
+        const int m = m0 + i;
+        const bool v = m < M;
+        const int mm = v ? m : 0;
+        const int f = mm / p.Wo, w = mm - f * p.Wo;
+        u_f = v ? f * p.unpatch_s : 0x40000000;
+        u_w = w * p.unpatch_s;
+        u_pix = f * p.unpatch_s * p.OWf + w * p.unpatch_s;
+    }
+    const float* omask = p.outmask ? p.outmask + (long)b * p.mask_bstride : nullptr;
+    const float* biasb = p.bias ? p.bias + (long)b * p.bias_bstride : nullptr;
+#pragma unroll
+    for (int wn = 0; wn < 2; ++wn) {
+        const int ng0 = ct * 64 + wn * 32, pp = ng0 / p.unpatch_C;
+        const int u_c0 = ng0 - pp * p.unpatch_C;
+        const int u_p1 = pp / p.unpatch_s, u_p2 = pp - u_p1 * p.unpatch_s;
+        const float u_mk = omask ? omask[min(u_w + u_p2, p.OWf - 1) * p.outmask_ws] : 1.f;
+        float4 b4[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) b4[q] = biasb ? *reinterpret_cast<const float4*>(biasb + ng0 + 8 * q + 4 * hh) : make_float4(0.f, 0.f, 0.f, 0.f);
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < K / 16; ++ks) acc = DEX_MFMA_LP(wfr[wn][ks].v, afr[ks], acc, 0, 0, 0);
+        NSTAMP(3);                                        // fragment reads, wait for the weight fragments, MFMA chain
+        float val[16];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            val[4 * q + 0] = (acc[4 * q + 0] + b4[q].x) * u_mk; val[4 * q + 1] = (acc[4 * q + 1] + b4[q].y) * u_mk;
+            val[4 * q + 2] = (acc[4 * q + 2] + b4[q].z) * u_mk; val[4 * q + 3] = (acc[4 * q + 3] + b4[q].w) * u_mk;
+        }
+        const bool ok = u_f + u_p1 < p.OHf && u_w + u_p2 < p.OWf;
+        const long e0 = (long)b * p.c_bstride + p.c_coff + (long)(u_p1 * p.OWf + u_p2 + u_pix) * p.ldc + u_c0;
+        if (p.c_lp) {
+            typedef unsigned u32x2n __attribute__((ext_vector_type(2)));
+            unsigned D[4][2];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { D[q][0] = pack2_lp(val[4 * q], val[4 * q + 1]); D[q][1] = pack2_lp(val[4 * q + 2], val[4 * q + 3]); }
+            uint4 ch[2];
+#pragma unroll
+            for (int pr = 0; pr < 2; ++pr) {
+                const u32x2n s0 = __builtin_amdgcn_permlane32_swap(D[2 * pr][0], D[2 * pr + 1][0], false, false);
+                const u32x2n s1 = __builtin_amdgcn_permlane32_swap(D[2 * pr][1], D[2 * pr + 1][1], false, false);
+                ch[pr] = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+            }
+            u16* cph = reinterpret_cast<u16*>(p.C) + e0 + 8 * hh;
+            if (ok) {
+                *reinterpret_cast<uint4*>(cph) = ch[0];
+                *reinterpret_cast<uint4*>(cph + 16) = ch[1];
+            }
+        } else {
+            float* cp = p.C + e0 + 4 * hh;
+            if (ok) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) *reinterpret_cast<float4*>(cp + 8 * q) = make_float4(val[4 * q], val[4 * q + 1], val[4 * q + 2], val[4 * q + 3]);
+            }
+        }
+        NSTAMP(4);                                        // scatter issued
+    }
+    NSTAMP_STORE()
 }
 
 static bool nwalk_eligible(const IGemmP& p) {
@@ -719,6 +896,24 @@ static void launch_nwalk(const IGemmP& p, hipStream_t st) {
         g_last_symbol = "igemm_lp_nwalk_kernel<256,64,1>";
         hipLaunchKernelGGL((igemm_lp_nwalk_kernel<K, 64, true>), dim3((p.Ho * p.Wo + 63) / 64, nsplit, p.B), dim3(256), lds_dma, st, p);
         return;
+    }
+#endif
+#ifndef DEX_LP_WSPLIT
+    // the small-grid form (igemm_lp_nwalk_kernel_small): where the one-tile-per-workgroup grid below would be more than one round of the
+    // CUs and 32-row workgroups of four column tiles fit one (B <= 3: the batch regime keeps its instructions).  DEX_NWALK_SMALL=0: never, =1: wherever the form exists (tests);
+    // a forced DEX_NWALK_SPLIT keeps its meaning (the walker at that split).
+    // The 16-bit output (c_lp) exists only with the concatenation buffer's 16-bit twin, i.e. at >= 256 tail workgroups (batch): the rule
+    // never meets it, the small form's 16-bit scatter runs only under DEX_NWALK_SMALL=1 (tests/test_gpu_dit_ends_small.py at B = 4).
+    if (p.Wfrag && p.w_bstride == 0 && (p.N % 256) == 0 && knob_or("DEX_NWALK_SPLIT", 0) <= 0) {
+        const int rt64 = (p.Ho * p.Wo + 63) / 64, rt32 = (p.Ho * p.Wo + 31) / 32;
+        const long ncu = device_cus();
+        const bool rule = p.B < 4 && (long)rt64 * p.B <= 16 && (long)rt64 * p.B * (p.N / 64) > ncu && (long)rt32 * p.B * (p.N / 256) <= ncu;
+        const int mode = knob_or("DEX_NWALK_SMALL", -1);
+        if (mode > 0 || (mode < 0 && rule)) {
+            g_last_symbol = "igemm_lp_nwalk_kernel_small<256>";
+            hipLaunchKernelGGL((igemm_lp_nwalk_kernel_small<K>), dim3(rt32, p.N / 256, p.B), dim3(256), 0, st, p);
+            return;
+        }
     }
 #endif
     g_last_symbol = "igemm_lp_nwalk_kernel<256>";
