@@ -24,6 +24,12 @@
 //   wsp_pick_kernel      the greedy step tail, one workgroup per row: logits finished from the partials, suppression, argmax with the
 //                        lowest index on ties, finished / length bookkeeping, and the gather of the next step's embed_tokens +
 //                        embed_positions row.  A step needs no host value.
+//   wsp_pick_ts_kernel   the same tail under the timestamp rule of long-form decoding (WhisperTimeStampLogitsProcessor): the masks of
+//                        the rule as index ranges from the row's own state (its last two ids, its last timestamp, its new-token
+//                        count, all on the device), the best text id, the best timestamp id and logsumexp(timestamps) in one pass
+//                        over the logits, reduced in a fixed order; the plain kernel is untouched.
+//   wsp_mel_long_kernel, wsp_mel_floor_long_kernel, wsp_gather_kernel   the front end of a row longer than one chunk (its own ends
+//                        reflected, len / 160 frames, one maximum over all of them) and the cut of a 30 s window at a row's seek.
 // Every per-row sum has an order fixed by the config and the position: a row's logits and ids are bitwise those of the row alone.
 #include <hip/hip_runtime.h>
 
@@ -52,18 +58,19 @@ struct Lens { int a[WB]; };
 // ------------------------------------------------------------------------------------------------------------ log-mel front end
 struct MelP { const float* wav; long ld; Lens len; long N; int T, n_mels; const double *win, *cs, *sn, *filt; double* out; };
 
-__global__ __launch_bounds__(256) void wsp_mel_kernel(const MelP p) {
+// frames t0 .. t0 + MELF - 1 of one row: x its samples, L of them stored, reflected at N (centre = True), T frames in the row; out the
+// row's [T][n_mels]
+__device__ __forceinline__ void mel_frames(const MelP& p, const float* x, int L, long N, int T, int t0, double* out) {
     __shared__ double xs[MELF][NFFT];
     __shared__ double cs[NFFT], sn[NFFT];
     __shared__ double pw[MELF][NBIN];
-    const int tid = threadIdx.x, b = blockIdx.y, t0 = blockIdx.x * MELF, L = p.len.a[b];
-    const float* x = p.wav + (long)b * p.ld;
+    const int tid = threadIdx.x;
     for (int i = tid; i < MELF * NFFT; i += 256) {
         const int f = i / NFFT, n = i - f * NFFT, t = t0 + f;
-        long j = (long)t * HOP + n - NFFT / 2;                      // centre = True, reflect padding of the zero-padded chunk
+        long j = (long)t * HOP + n - NFFT / 2;                      // centre = True, reflect padding of the N samples (the zero-padded chunk, or a long row)
         if (j < 0) j = -j;
-        if (j >= p.N) j = 2 * (p.N - 1) - j;
-        xs[f][n] = (t < p.T && j < L) ? (double)x[j] * p.win[n] : 0.0;
+        if (j >= N) j = 2 * (N - 1) - j;
+        xs[f][n] = (t < T && j < L) ? (double)x[j] * p.win[n] : 0.0;
     }
     for (int i = tid; i < NFFT; i += 256) { cs[i] = p.cs[i]; sn[i] = p.sn[i]; }
     __syncthreads();
@@ -85,11 +92,28 @@ __global__ __launch_bounds__(256) void wsp_mel_kernel(const MelP p) {
     __syncthreads();
     for (int o = tid; o < MELF * p.n_mels; o += 256) {
         const int f = o / p.n_mels, m = o - f * p.n_mels, t = t0 + f;
-        if (t >= p.T) continue;
+        if (t >= T) continue;
         double a = 0.0;
         for (int k = 0; k < NBIN; ++k) a = fma(p.filt[(long)k * p.n_mels + m], pw[f][k], a);
-        p.out[((long)b * p.T + t) * p.n_mels + m] = log10(fmax(a, 1e-10));
+        out[(long)t * p.n_mels + m] = log10(fmax(a, 1e-10));
     }
+}
+
+__global__ __launch_bounds__(256) void wsp_mel_kernel(const MelP p) {
+    const int b = blockIdx.y;
+    mel_frames(p, p.wav + (long)b * p.ld, p.len.a[b], p.N, p.T, blockIdx.x * MELF, p.out + (long)b * p.T * p.n_mels);
+}
+
+// the frames of a row in the long form: at most one chunk (p.N samples) -> the chunk's p.T frames of the zero-padded row, as above;
+// longer -> len / 160 frames of the row reflected at its own ends
+__device__ __forceinline__ int long_frames(int L, long chunk, int T) { return L <= chunk ? T : L / HOP; }
+
+// rows of any length: p.T = the frames of a chunk, p.N its samples; out [B][Fmax][n_mels]
+__global__ __launch_bounds__(256) void wsp_mel_long_kernel(const MelP p, int Fmax) {
+    const int b = blockIdx.y, L = p.len.a[b], t0 = blockIdx.x * MELF;
+    const int T = long_frames(L, p.N, p.T);
+    if (t0 >= T) return;
+    mel_frames(p, p.wav + (long)b * p.ld, L, L <= p.N ? p.N : (long)L, T, t0, p.out + (long)b * Fmax * p.n_mels);
 }
 
 // logspec [B][T][n_mels] (fp64) -> out [B][n_mels][T]: max(x, rowmax - 8), (x + 4) / 4
@@ -121,6 +145,38 @@ __global__ __launch_bounds__(256) void wsp_feat_cl_kernel(const float* feat, flo
     const long bt = i / Mp;
     const long b = bt / T, t = bt - b * T;
     cl[i] = c < n_mels ? feat[(b * n_mels + c) * T + t] : 0.f;
+}
+
+// logspec [B][Fmax][n_mels] (fp64), row b of long_frames(len[b]) frames -> out [B][n_mels][Fmax]: the floor at the maximum over all of
+// the row's frames - 8, (x + 4) / 4; 0 behind the row's frames
+__global__ __launch_bounds__(1024) void wsp_mel_floor_long_kernel(const double* logspec, float* out, Lens len, long chunk, int Tc, int Fmax, int n_mels) {
+    __shared__ double red[1024];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int T = long_frames(len.a[b], chunk, Tc);
+    const long n = (long)T * n_mels, all = (long)Fmax * n_mels;
+    const double* x = logspec + (long)b * all;
+    double m = -1e300;
+    for (long i = tid; i < n; i += 1024) m = fmax(m, x[i]);
+    red[tid] = m;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) {
+        if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
+        __syncthreads();
+    }
+    const double lo = red[0] - 8.0;
+    for (long i = tid; i < all; i += 1024) {
+        const int mel = (int)(i / Fmax), t = (int)(i - (long)mel * Fmax);
+        out[(long)b * all + i] = t < T ? (float)((fmax(x[(long)t * n_mels + mel], lo) + 4.0) / 4.0) : 0.f;
+    }
+}
+
+// out [a][n_mels][W] = feat [row[a]][n_mels][seek[a] .. seek[a] + n[a]), 0.0 behind n[a]
+struct GatherP { const float* feat; float* out; int Fmax, n_mels, W; Lens row, seek, n; };
+__global__ __launch_bounds__(256) void wsp_gather_kernel(const GatherP p) {
+    const int a = blockIdx.z, mel = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= p.W) return;
+    const float* src = p.feat + ((long)p.row.a[a] * p.n_mels + mel) * p.Fmax + p.seek.a[a];
+    p.out[((long)a * p.n_mels + mel) * p.W + t] = t < p.n.a[a] ? src[t] : 0.f;
 }
 
 // ------------------------------------------------------------------------------------------------------------ the step's linears
@@ -336,6 +392,89 @@ __global__ __launch_bounds__(1024) void wsp_pick_kernel(const PickP p) {
     for (int c = tid; c < p.d; c += 1024) p.h[(long)b * p.d + c] = e[c] + q[c];
 }
 
+// The tail under the timestamp rule.  tb = the first timestamp id (no_timestamps + 1), max_init >= 0: the cap of the first timestamp;
+// last_ts [B] the row's last emitted timestamp id (-1: none), n_new [B] its new-token count; its last two new ids are read from `ids`
+// at columns step - 1 and step - 2
+struct PickTsP { PickP k; int nots, tb, max_init; int *last_ts, *n_new; };
+
+// (m, s): a maximum and sum exp(x - m) over a set of values; the union of two sets.  Symmetric in its operands, bit for bit
+__device__ __forceinline__ void lse_join(float& m, float& s, float om, float os) {
+    const float M = fmaxf(m, om);
+    const float a = m == -INFINITY ? 0.f : s * expf(m - M), c = om == -INFINITY ? 0.f : os * expf(om - M);
+    m = M; s = a + c;
+}
+
+// row blockIdx.x, as wsp_pick_kernel with the rule of WhisperTimeStampLogitsProcessor between the masks and the argmax.  Every mask of
+// the rule is an index range fixed by the row's state, so a thread decides an id's fate from registers: text ids (below tb) live in
+// [text_lo, tb), timestamps in [ts_lo, ts_hi], no_timestamps never.  A masked id does not compete; where nothing competes (a row of
+// NaN) the id is 0.  Thread t owns ids t, t + 1024, ...; the wave butterfly and the 16 waves in order fix the order of every
+// reduction from V alone
+__global__ __launch_bounds__(1024) void wsp_pick_ts_kernel(const PickTsP q) {
+    __shared__ float tv[16], sv[16], mv[16], lv[16];
+    __shared__ int ti[16], si[16];
+    __shared__ int chosen;
+    const PickP& p = q.k;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x, V = p.V, tb = q.tb;
+    const int i = q.n_new[b], seen = q.last_ts[b];
+    const int last = i >= 1 ? p.ids[(long)b * p.ld_ids + p.step - 1] : -1, pen = i >= 2 ? p.ids[(long)b * p.ld_ids + p.step - 2] : -1;
+    const bool last_ts = i >= 1 && last >= tb, pen_ts = i < 2 || pen >= tb;
+    int text_lo = 0, ts_lo = tb, ts_hi = V - 1;
+    if (last_ts) {
+        if (pen_ts) ts_lo = V;                       // a pair is closed: text next
+        else text_lo = p.eos;                        // a lone timestamp: its partner (or eos) next
+    }
+    if (seen >= 0) {                                 // timestamps never decrease, and only a pair's partner may repeat
+        const int lo = (last_ts && !pen_ts) ? seen : seen + 1;
+        ts_lo = ts_lo > lo ? ts_lo : lo;
+    }
+    if (i == 0) {
+        text_lo = tb;
+        if (q.max_init >= 0 && tb + q.max_init < ts_hi) ts_hi = tb + q.max_init;
+    }
+    float bt = -INFINITY, bs = -INFINITY, m = -INFINITY, s = 0.f;
+    int at = 0x7fffffff, as = 0x7fffffff;
+    for (int v = tid; v < V; v += 1024) {
+        if (v == q.nots || (p.mask && p.mask[v])) continue;
+        if (v < tb) {
+            if (v >= text_lo) better(bt, at, finished(p.P, p.KS, p.ss, (long)b * V + v, nullptr, 0), v);
+        } else if (v >= ts_lo && v <= ts_hi) {
+            const float x = finished(p.P, p.KS, p.ss, (long)b * V + v, nullptr, 0);
+            better(bs, as, x, v);
+            lse_join(m, s, x, 1.f);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        better(bt, at, __shfl_xor(bt, o), __shfl_xor(at, o));
+        better(bs, as, __shfl_xor(bs, o), __shfl_xor(as, o));
+        lse_join(m, s, __shfl_xor(m, o), __shfl_xor(s, o));
+    }
+    if (lane == 0) { tv[wave] = bt; ti[wave] = at; sv[wave] = bs; si[wave] = as; mv[wave] = m; lv[wave] = s; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 16; ++w) { better(bt, at, tv[w], ti[w]); better(bs, as, sv[w], si[w]); lse_join(m, s, mv[w], lv[w]); }
+        // logsumexp(timestamps) > max(text): the timestamps' summed probability beats every text id; no normaliser is needed
+        const bool force = m + logf(s) > bt;
+        int arg = as;
+        if (!force) { float bv = bt; arg = at; better(bv, arg, bs, as); }
+        if (arg >= V) arg = 0;                       // nothing competed
+        const int fin = p.finished[b];
+        const int id = fin ? p.eos : arg;
+        if (!fin) {
+            if (id == p.eos) { p.finished[b] = 1; atomicAdd(p.count, 1); }
+            else p.lengths[b] += 1;
+            if (id >= tb) q.last_ts[b] = id;
+        }
+        q.n_new[b] = i + 1;
+        p.ids[(long)b * p.ld_ids + p.step] = id;
+        chosen = id;
+    }
+    __syncthreads();
+    if (p.next_pos < 0) return;
+    const float* e = p.emb + (long)chosen * p.d;
+    const float* pq = p.pos + (long)p.next_pos * p.d;
+    for (int c = tid; c < p.d; c += 1024) p.h[(long)b * p.d + c] = e[c] + pq[c];
+}
+
 // h[b] = embed_tokens[id] + embed_positions[pos], id = ids[b ld + pos] (clamped into the vocabulary) or, ids null, `id`
 __global__ __launch_bounds__(256) void wsp_embed_kernel(const int* ids, int ld, int id, int pos, int V, const float* emb, const float* posw, int d, float* h) {
     const int b = blockIdx.x;
@@ -519,8 +658,8 @@ int pack_all(DexWhisper* s, hipStream_t st) {
 
 // workspace (floats, every piece a multiple of 64): logspec (fp64) [B][T][n_mels] | mel [B][T][Mp] | c1 [B][T][d] | he, ye [B][S][d]
 // | qkv [B][S][3d] | ffe [B][S][ffn_e] | enc [B][S][d] | ckv [Ld][B][S][2d] | ck, cv [Ld][B][Tmax][d] | h, y, a [B][d] | ff [B][ffn_d]
-// | P (the largest [KS][B][N] of a step) | state (int): finished [B], count
-struct Ws { double* logspec; float *mel, *c1, *he, *ye, *qkv, *ffe, *enc, *ckv, *ck, *cv, *h, *y, *a, *ff, *P; int *fin, *count; size_t bytes; };
+// | P (the largest [KS][B][N] of a step) | state (int): finished [B], count, new-token count [B], last timestamp [B]
+struct Ws { double* logspec; float *mel, *c1, *he, *ye, *qkv, *ffe, *enc, *ckv, *ck, *cv, *h, *y, *a, *ff, *P; int *fin, *count, *n_new, *last_ts; size_t bytes; };
 Ws plan(const DexWhisper* s, void* ws, long B) {
     const DexWhisperConfig& c = s->c;
     const long S = c.max_source_positions, T = 2 * S, d = c.d_model, Tm = c.max_target_positions, Ld = c.decoder_layers;
@@ -537,7 +676,7 @@ Ws plan(const DexWhisper* s, void* ws, long B) {
     pn = q > pn ? q : pn; q = (long)slabs((int)d) * c.vocab_size;
     pn = q > pn ? q : pn;
     w.P = tk.take(B * pn);
-    w.fin = (int*)tk.take(B + 64); w.count = w.fin + B;
+    w.fin = (int*)tk.take(3 * B + 64); w.count = w.fin + B; w.n_new = w.count + 1; w.last_ts = w.n_new + B;
     w.bytes = tk.bytes();
     return w;
 }
@@ -659,6 +798,18 @@ int ready(DexWhisper* s, int B, void* ws, size_t bytes, Ws* w) {
     return DEX_OK;
 }
 
+// the timestamp ids of a spec: eos below no_timestamps, and one id per 20 ms of a window and its end behind it
+int check_timestamps(DexWhisper* s, int eos, int nots, int max_init) {
+    const DexWhisperConfig& c = s->c;
+    if (nots >= c.vocab_size - 1) return s->fail(DEX_ERR_ARG, "no_timestamps_token_id %d is outside the vocabulary of %d", nots, c.vocab_size);
+    if (eos > nots) return s->fail(DEX_ERR_ARG, "eos_token_id %d lies above no_timestamps_token_id %d", eos, nots);
+    if (c.vocab_size - (nots + 1) < c.max_source_positions + 1)
+        return s->fail(DEX_ERR_ARG, "%d timestamp ids behind no_timestamps_token_id: max_source_positions + 1 = %d are needed", c.vocab_size - (nots + 1),
+                       c.max_source_positions + 1);
+    if (max_init < -1) return s->fail(DEX_ERR_ARG, "max_initial_timestamp_index must be >= 0, or -1 for none");
+    return DEX_OK;
+}
+
 typedef Entry<DexWhisper> E;
 
 }  // namespace
@@ -747,9 +898,10 @@ int dex_whisper_forward(DexWhisper* s, const int32_t* ids_dev, int B, int L, flo
     return hipGetLastError() == hipSuccess ? DEX_OK : s->fail(DEX_ERR_HIP, "kernel launch failed");
 }
 
-int dex_whisper_generate(DexWhisper* s, const int32_t* prompt_host, int n_prompt, const uint8_t* suppress_dev, const uint8_t* begin_dev, int eos, int B,
-                         int max_new, int sync_every, int32_t* ids_dev, int32_t* lengths_dev, int* steps_host, void* workspace_dev,
-                         size_t workspace_bytes, dex_stream_t stream) {
+// the body of dex_whisper_generate (nots < 0) and dex_whisper_generate_ts
+static int generate(DexWhisper* s, const int32_t* prompt_host, int n_prompt, const uint8_t* suppress_dev, const uint8_t* begin_dev, int eos, int nots,
+                    int max_init, int B, int max_new, int sync_every, int32_t* ids_dev, int32_t* lengths_dev, int* steps_host, void* workspace_dev,
+                    size_t workspace_bytes, dex_stream_t stream) {
     if (!s) return DEX_ERR_ARG;
     if (!prompt_host || !ids_dev || !lengths_dev || !steps_host) return s->fail(DEX_ERR_ARG, "null pointer argument");
     Ws w;
@@ -763,6 +915,11 @@ int dex_whisper_generate(DexWhisper* s, const int32_t* prompt_host, int n_prompt
     if (eos < 0 || eos >= c.vocab_size) return s->fail(DEX_ERR_ARG, "eos_token_id %d is outside the vocabulary of %d", eos, c.vocab_size);
     if (max_new < 1 || sync_every < 0) return s->fail(DEX_ERR_ARG, "max_new must be >= 1 and sync_every >= 0");
     hipStream_t st = (hipStream_t)stream;
+    if (nots >= 0) {
+        if (int rc = check_timestamps(s, eos, nots, max_init)) return rc;
+        DEX_HIPCHK(s, hipMemsetAsync(w.n_new, 0, B * sizeof(int), st));
+        hipLaunchKernelGGL(wsp_fill_kernel, dim3(1), dim3(256), 0, st, w.last_ts, (long)B, -1);
+    }
     const int room = c.max_target_positions - n_prompt, n_new = max_new < room ? max_new : room;      // never past the cache
     const long n_ids = (long)B * max_new;
     hipLaunchKernelGGL(wsp_fill_kernel, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, st, ids_dev, n_ids, eos);
@@ -782,7 +939,8 @@ int dex_whisper_generate(DexWhisper* s, const int32_t* prompt_host, int n_prompt
             k.P = w.P; k.KS = ks; k.ss = (long)B * c.vocab_size; k.V = c.vocab_size; k.mask = i == 0 ? begin_dev : suppress_dev;
             k.pick = 1; k.eos = eos; k.finished = w.fin; k.lengths = lengths_dev; k.count = w.count; k.ids = ids_dev; k.ld_ids = max_new; k.step = i;
             k.emb = s->emb; k.pos = s->dec_pos; k.d = c.d_model; k.next_pos = i + 1 < n_new ? n_prompt + i : -1; k.h = w.h;
-            hipLaunchKernelGGL(wsp_pick_kernel, dim3(B), dim3(1024), 0, st, k);
+            if (nots >= 0) hipLaunchKernelGGL(wsp_pick_ts_kernel, dim3(B), dim3(1024), 0, st, PickTsP{k, nots, nots + 1, max_init, w.last_ts, w.n_new});
+            else hipLaunchKernelGGL(wsp_pick_kernel, dim3(B), dim3(1024), 0, st, k);
             steps = i + 1;
             if (sync_every && steps % sync_every == 0 && steps < n_new) {
                 int done = 0;
@@ -794,6 +952,69 @@ int dex_whisper_generate(DexWhisper* s, const int32_t* prompt_host, int n_prompt
     }
     *steps_host = steps;
     DEX_HIPCHK(s, hipStreamSynchronize(st));
+    return hipGetLastError() == hipSuccess ? DEX_OK : s->fail(DEX_ERR_HIP, "kernel launch failed");
+}
+
+int dex_whisper_generate(DexWhisper* s, const int32_t* prompt_host, int n_prompt, const uint8_t* suppress_dev, const uint8_t* begin_dev, int eos, int B,
+                         int max_new, int sync_every, int32_t* ids_dev, int32_t* lengths_dev, int* steps_host, void* workspace_dev,
+                         size_t workspace_bytes, dex_stream_t stream) {
+    return generate(s, prompt_host, n_prompt, suppress_dev, begin_dev, eos, -1, -1, B, max_new, sync_every, ids_dev, lengths_dev, steps_host, workspace_dev,
+                    workspace_bytes, stream);
+}
+
+int dex_whisper_generate_ts(DexWhisper* s, const int32_t* prompt_host, int n_prompt, const uint8_t* suppress_dev, const uint8_t* begin_dev, int eos,
+                            int no_timestamps_token_id, int max_initial_timestamp_index, int B, int max_new, int sync_every, int32_t* ids_dev,
+                            int32_t* lengths_dev, int* steps_host, void* workspace_dev, size_t workspace_bytes, dex_stream_t stream) {
+    if (!s) return DEX_ERR_ARG;
+    if (no_timestamps_token_id < 0) return s->fail(DEX_ERR_ARG, "no_timestamps_token_id %d is outside the vocabulary of %d", no_timestamps_token_id, s->c.vocab_size);
+    return generate(s, prompt_host, n_prompt, suppress_dev, begin_dev, eos, no_timestamps_token_id, max_initial_timestamp_index, B, max_new, sync_every,
+                    ids_dev, lengths_dev, steps_host, workspace_dev, workspace_bytes, stream);
+}
+
+int dex_whisper_log_mel_long(DexWhisper* s, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, float* out_dev, int max_frames,
+                             int32_t* frames_host, void* scratch_dev, size_t scratch_bytes, dex_stream_t stream) {
+    if (!s) return DEX_ERR_ARG;
+    if (!wav_dev || !lengths_host || !out_dev || !frames_host || !scratch_dev) return s->fail(DEX_ERR_ARG, "null pointer argument");
+    if (B < 1 || B > WB) return s->fail(DEX_ERR_ARG, "B must lie in [1, %d]", WB);
+    if (n_samples < 1 || n_samples > DEX_WHISPER_MAX_LONG_SAMPLES) return s->fail(DEX_ERR_ARG, "n_samples must lie in [1, %d] (the cap of a long row)", DEX_WHISPER_MAX_LONG_SAMPLES);
+    const DexWhisperConfig& c = s->c;
+    const int Tc = 2 * c.max_source_positions, M = c.num_mel_bins;
+    const long chunk = (long)Tc * HOP;
+    MelP p{};
+    int F = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lengths_host[b] < 1 || lengths_host[b] > n_samples) return s->fail(DEX_ERR_ARG, "row lengths must lie in [1, n_samples]");
+        p.len.a[b] = lengths_host[b];
+        frames_host[b] = lengths_host[b] <= chunk ? Tc : lengths_host[b] / HOP;
+        F = frames_host[b] > F ? frames_host[b] : F;
+    }
+    if (max_frames < F) return s->fail(DEX_ERR_ARG, "max_frames %d is below the longest row's %d frames", max_frames, F);
+    if (scratch_bytes < (size_t)B * max_frames * M * sizeof(double)) return s->fail(DEX_ERR_WORKSPACE, "scratch too small (B x max_frames x num_mel_bins doubles)");
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = ensure_tables(s, st)) return rc;
+    p.wav = wav_dev; p.ld = n_samples; p.N = chunk; p.T = Tc; p.n_mels = M;
+    p.win = s->tab_dev; p.cs = s->tab_dev + NFFT; p.sn = s->tab_dev + 2 * NFFT; p.filt = s->tab_dev + 3 * NFFT; p.out = (double*)scratch_dev;
+    hipLaunchKernelGGL(wsp_mel_long_kernel, dim3((F + MELF - 1) / MELF, B), dim3(256), 0, st, p, max_frames);
+    hipLaunchKernelGGL(wsp_mel_floor_long_kernel, dim3(B), dim3(1024), 0, st, (const double*)scratch_dev, out_dev, p.len, chunk, Tc, max_frames, M);
+    return hipGetLastError() == hipSuccess ? DEX_OK : s->fail(DEX_ERR_HIP, "kernel launch failed");
+}
+
+int dex_whisper_gather_windows(DexWhisper* s, const float* feat_dev, int rows, int max_frames, const int32_t* row_host, const int32_t* seek_host,
+                               const int32_t* n_host, int active, float* out_dev, dex_stream_t stream) {
+    if (!s) return DEX_ERR_ARG;
+    if (!feat_dev || !row_host || !seek_host || !n_host || !out_dev) return s->fail(DEX_ERR_ARG, "null pointer argument");
+    if (active < 1 || active > WB) return s->fail(DEX_ERR_ARG, "B must lie in [1, %d]", WB);
+    const int W = 2 * s->c.max_source_positions;
+    GatherP p{};
+    if (rows < 1 || max_frames < 1) return s->fail(DEX_ERR_ARG, "rows and max_frames must be >= 1");
+    for (int a = 0; a < active; ++a) {
+        if (row_host[a] < 0 || row_host[a] >= rows) return s->fail(DEX_ERR_ARG, "row index %d is outside the %d rows", row_host[a], rows);
+        if (seek_host[a] < 0 || n_host[a] < 1 || n_host[a] > W || (long)seek_host[a] + n_host[a] > max_frames)
+            return s->fail(DEX_ERR_ARG, "a window [seek, seek + n) must lie in the row's %d frames, n in [1, %d]", max_frames, W);
+        p.row.a[a] = row_host[a]; p.seek.a[a] = seek_host[a]; p.n.a[a] = n_host[a];
+    }
+    p.feat = feat_dev; p.out = out_dev; p.Fmax = max_frames; p.n_mels = s->c.num_mel_bins; p.W = W;
+    hipLaunchKernelGGL(wsp_gather_kernel, dim3((W + 255) / 256, p.n_mels, active), dim3(256), 0, (hipStream_t)stream, p);
     return hipGetLastError() == hipSuccess ? DEX_OK : s->fail(DEX_ERR_HIP, "kernel launch failed");
 }
 
@@ -830,6 +1051,20 @@ int dex_whisper_pick(const float* logits_dev, int B, int V, const uint8_t* mask_
     k.P = logits_dev; k.KS = 1; k.V = V; k.mask = mask_dev; k.pick = 1; k.eos = eos; k.finished = finished_dev; k.lengths = lengths_dev; k.count = count_dev;
     k.ids = ids_dev; k.ld_ids = ld_ids; k.step = step; k.next_pos = -1;
     hipLaunchKernelGGL(wsp_pick_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, k);
+    return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
+}
+
+int dex_whisper_pick_ts(const float* logits_dev, int B, int V, const uint8_t* mask_dev, int eos, int no_timestamps_token_id,
+                        int max_initial_timestamp_index, int32_t* finished_dev, int32_t* lengths_dev, int32_t* count_dev, int32_t* ids_dev, int ld_ids,
+                        int step, int32_t* last_timestamp_dev, int32_t* n_new_dev, dex_stream_t stream) {
+    if (!logits_dev || !finished_dev || !lengths_dev || !count_dev || !ids_dev || !last_timestamp_dev || !n_new_dev) return DEX_ERR_ARG;
+    if (B < 1 || B > 65535 || V < 1 || eos < 0 || eos >= V || step < 2 || step >= ld_ids) return DEX_ERR_ARG;
+    if (no_timestamps_token_id < eos || no_timestamps_token_id >= V - 1 || max_initial_timestamp_index < -1) return DEX_ERR_ARG;
+    PickP k{};
+    k.P = logits_dev; k.KS = 1; k.V = V; k.mask = mask_dev; k.pick = 1; k.eos = eos; k.finished = finished_dev; k.lengths = lengths_dev; k.count = count_dev;
+    k.ids = ids_dev; k.ld_ids = ld_ids; k.step = step; k.next_pos = -1;
+    hipLaunchKernelGGL(wsp_pick_ts_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream,
+                       PickTsP{k, no_timestamps_token_id, no_timestamps_token_id + 1, max_initial_timestamp_index, last_timestamp_dev, n_new_dev});
     return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
 }
 

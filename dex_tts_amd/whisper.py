@@ -3,10 +3,12 @@ wav2vec 2.0 CTC score; numbers from the two recognisers are not comparable).  HF
 mode, fp32 throughout: log-mel front end, encoder, decoder with a key/value cache, greedy decoding.
 
     WhisperConfig(...)                         HF's field names; defaults = openai/whisper-large-v3
-    Whisper(config=None, device='cuda'):       load_state_dict (HF keys), log_mel, encode, forward, generate, transcribe
-    GenerationSpec(prompt_ids, suppress_tokens, begin_suppress_tokens, eos_token_id);  GenerationSpec.from_generation_config(...)
+    Whisper(config=None, device='cuda'):       load_state_dict (HF keys), log_mel, encode, forward, generate, transcribe;
+                                               long form: log_mel_long, generate_segments, transcribe_long
+    GenerationSpec(prompt_ids, suppress_tokens, begin_suppress_tokens, eos_token_id, no_timestamps_token_id=None,
+                   max_initial_timestamp_index=None);  GenerationSpec.from_generation_config(..., timestamps=False)
     load_vocab(path), decode(ids, vocab)       host only
-    whisper_score(wavs, texts, model=, spec=, vocab=) -> (transcripts, cer_mean, cer_stderr, wer_mean, wer_stderr)
+    whisper_score(wavs, texts, model=, spec=, vocab=, long_form=False) -> (transcripts, cer_mean, cer_stderr, wer_mean, wer_stderr)
 
 Everything runs in libdexamd.so (``csrc/whisper.hip``, C ABI ``dex_whisper_*``).  Nothing downloads and no checkpoint is shipped:
 weights, the generation config and the vocabulary come from dicts or local files the caller names.  A row's features, logits and ids
@@ -16,7 +18,7 @@ Definitions (the contract)
 
 Front end = ``WhisperFeatureExtractor``.  Input is 16 kHz; other rates go through ``wavprep.resample`` (kaiser_best), as in the other
 two scores.  A row is zero-padded to ``n_samples = 2 * max_source_positions * 160`` (480 000 for the real models); a longer row
-raises ``ValueError`` (long-form transcription is not built, and a metric must not truncate silently).  Reflect-pad by 200, periodic
+raises ``ValueError`` in ``log_mel``, ``generate`` and ``transcribe`` (a metric must not truncate silently; the long form below takes it).  Reflect-pad by 200, periodic
 Hann(400), 400-point DFT at hop 160, power, the last frame dropped, mel (``num_mel_bins`` 80 or 128, Slaney scale and norm,
 0 - 8000 Hz; the matrix is built on the host in float64, ``mel_filters``), ``log10(max(., 1e-10))``, floored at the row's own maximum
 - 8, ``(x + 4) / 4``.  The device computes all of it in fp64 and rounds to fp32 once.
@@ -35,7 +37,51 @@ Greedy decoding is the library's own definition, a stated subset of HF ``generat
 new-token step i ``suppress_tokens`` are set to -inf, at i = 0 ``begin_suppress_tokens`` as well, and the argmax takes the lowest
 index on ties.  A row is finished once it emits ``eos_token_id``; from then on its output is eos.  The loop ends when every row has
 finished, after ``max_new_tokens``, or when ``len(prompt) + i`` reaches ``max_target_positions``: it never writes past the cache.
-Not built: timestamps, temperature fallback, the compression-ratio, log-prob and no-speech thresholds, beams, language detection.
+Not built: temperature fallback, the compression-ratio, log-prob and no-speech thresholds, beams, language detection,
+``condition_on_prev_tokens``, token-level timestamps.  Timestamps are built for the long form only (below).
+
+Long form (``log_mel_long``, ``generate_segments``, ``transcribe_long``, ``whisper_score(long_form=True)``) mirrors HF
+``generate(..., return_timestamps=True)`` at temperature 0 with ``condition_on_prev_tokens=False``: no no-speech, log-prob or
+compression-ratio threshold, no fallback, no beams.  The spec carries ``no_timestamps_token_id`` (``timestamp_begin`` is that id + 1;
+``from_generation_config(timestamps=True)`` fills it, leaves ``<|notimestamps|>`` out of the prompt and reads
+``max_initial_timestamp_index``); a spec without it raises ``ValueError``, and so do fewer than ``max_source_positions + 1``
+timestamp ids (``vocab_size - timestamp_begin``).
+
+  Step rule.  At new-token step i of a window a row's logits pass, in HF's order, through ``begin_suppress_tokens`` (i = 0 only),
+  ``suppress_tokens`` and the timestamp rule, in the order of operations of ``WhisperTimeStampLogitsProcessor.__call__``:
+  ``no_timestamps_token_id`` -> -inf.  Pairing, with ``seq`` the new tokens so far: if the last token is a timestamp and the one
+  before it is a timestamp too (or there is only one new token) every timestamp -> -inf; if the last is a timestamp and the one
+  before it is not, ids [0, eos) -> -inf.  Monotonicity: if any timestamp was emitted, timestamps below ``last`` (in the "last is a
+  timestamp, the one before is not" case) or below ``last + 1`` (otherwise) -> -inf.  At i = 0 every id below ``timestamp_begin``
+  -> -inf, and with ``max_initial_timestamp_index`` every timestamp above ``timestamp_begin + max_initial_timestamp_index``.  Last,
+  if ``logsumexp(timestamp logits) > max(text logits)`` over the masked row (text = every id below ``timestamp_begin``, eos
+  included; both sides lack the same normaliser, so none is computed) every id below ``timestamp_begin`` -> -inf.  Then the argmax,
+  lowest index on ties; finished and length bookkeeping as in the plain form.  The device keeps the rule's state (a row's last
+  timestamp and its new-token count; its last two ids are in the ids buffer), so a step still needs no host value.  A masked id
+  does not compete, and a row in which nothing competes (all NaN) yields id 0.
+
+  Front end of a row of more than ``n_samples`` samples = ``WhisperFeatureExtractor(truncation=False)`` on that row alone: reflect-pad
+  by 200 at the row's own ends, ``len // 160`` frames, the floor at the whole row's maximum - 8, fp64 rounded once.  A row of at most
+  ``n_samples`` keeps ``log_mel``'s features (zero-padded, ``2 x max_source_positions`` frames).  ``F`` is the row's frame count.  A
+  row above ``MAX_LONG_SAMPLES`` (30 minutes) raises ``ValueError``.  The fp64 log-spectrum of a call sits in a scratch buffer of
+  rows x F_max x num_mel_bins doubles; rows are taken in groups that keep it under 1 GiB.
+
+  Window loop.  ``seek = 0``; while ``seek < F``: ``n = min(F - seek, 2 x max_source_positions)``; the window's features are frames
+  [seek, seek + n) followed by the feature value 0.0 up to the full window (HF's ``_get_input_segment``); encode, decode under the
+  step rule from the prompt up to the cache's room; strip the trailing eos; cut the ids into segments and advance ``seek`` as
+  ``_retrieve_segment`` does: consecutive timestamp pairs close segments; a single trailing timestamp means the whole window is
+  consumed (``seek += n``); otherwise ``seek`` moves to the last pair's first timestamp index x 2 frames and the ids after that pair
+  are discarded; with no pair at all the window is one segment and is consumed whole.  Times are ``seek x 0.01 + index x 0.02``
+  seconds in float64.  A row's transcript is ``decode`` of its segments' ids joined (timestamp ids lie above eos and are skipped).
+
+  The loop ends: ``seek`` grows by at least 2 frames per window (or reaches F).  A consumed window adds n >= 1, and n < 2 only for
+  the last frame of the row.  Otherwise a pair exists and seek moves to its first timestamp's index x 2; that index is >= 1, because
+  step 0 emits a timestamp (index >= 0), step 1 may not emit one (only one new token: all timestamps masked), and every later
+  timestamp that follows text must exceed the last one emitted (``last + 1``), so the first member of any pair has index >= 1.
+
+  Rows are independent: each window call gathers the rows still active (32 at most per network call); a row's features, segments
+  and ids are bitwise those of the row alone.  One device-to-host copy of ids and lengths per window call is the only sync beyond
+  the plain form's.
 
 Host syncs.  Token ids, the finished flags and each row's length stay on the device; a step needs no host value.  The host reads
 one finished-count every ``SYNC_EVERY`` = 8 steps to end early: a read drains the queue of launches the host has run ahead with
@@ -71,6 +117,8 @@ from .asr import score_transcripts
 N_FFT, HOP = 400, 160
 MAX_ROWS = 32                       # DEX_WHISPER_MAX_B
 SYNC_EVERY = 8
+MAX_LONG_SAMPLES = 28_800_000       # DEX_WHISPER_MAX_LONG_SAMPLES: 30 minutes at 16 kHz
+_LONG_SCRATCH = 1 << 30             # bytes of fp64 log-spectrum one front-end call of the long form may hold
 
 
 @dataclasses.dataclass(frozen=True)
@@ -117,18 +165,27 @@ def mel_filters(n_mels: int) -> np.ndarray:
 
 @dataclasses.dataclass(frozen=True)
 class GenerationSpec:
-    """One decode run: the prompt fed before the first new token, the ids never emitted, the ids not emitted first, and eos."""
+    """One decode run: the prompt fed before the first new token, the ids never emitted, the ids not emitted first, and eos; for the
+    long form also ``<|notimestamps|>`` (the timestamps start behind it) and the cap of a window's first timestamp."""
     prompt_ids: Tuple[int, ...]
     suppress_tokens: Tuple[int, ...] = ()
     begin_suppress_tokens: Tuple[int, ...] = ()
     eos_token_id: int = 50257
+    no_timestamps_token_id: Optional[int] = None
+    max_initial_timestamp_index: Optional[int] = None
+
+    @property
+    def timestamp_begin(self) -> Optional[int]:
+        return None if self.no_timestamps_token_id is None else self.no_timestamps_token_id + 1
 
     @classmethod
-    def from_generation_config(cls, config, language: str = "en", task: str = "transcribe") -> "GenerationSpec":
+    def from_generation_config(cls, config, language: str = "en", task: str = "transcribe", timestamps: bool = False) -> "GenerationSpec":
         """From HF's ``generation_config.json`` (a dict, the file, or the directory that holds it): the prompt
         ``<|startoftranscript|> [<|lang|> <|task|>] <|notimestamps|>`` (the bracket for ``is_multilingual`` models) from the
         file's own ``decoder_start_token_id``, ``lang_to_id``, ``task_to_id`` and ``no_timestamps_token_id``, and its
-        ``suppress_tokens``, ``begin_suppress_tokens`` and ``eos_token_id``.  An unknown language or task raises ``ValueError``."""
+        ``suppress_tokens``, ``begin_suppress_tokens`` and ``eos_token_id``.  An unknown language or task raises ``ValueError``.
+        ``timestamps=True`` (the long form): the prompt ends before ``<|notimestamps|>``, and ``no_timestamps_token_id`` and
+        ``max_initial_timestamp_index`` (where the file has one) are carried in the spec."""
         if not isinstance(config, dict):
             path = os.fspath(config)
             if os.path.isdir(path):
@@ -143,11 +200,19 @@ class GenerationSpec:
             if task not in config.get("task_to_id", {}):
                 raise ValueError(f"GenerationSpec: task {task!r} is not in the generation config's task_to_id")
             prompt += [int(config["lang_to_id"][lang]), int(config["task_to_id"][task])]
-        prompt.append(int(config["no_timestamps_token_id"]))
+        if not timestamps:
+            prompt.append(int(config["no_timestamps_token_id"]))
         eos = config["eos_token_id"]
         eos = int(eos[0] if isinstance(eos, (list, tuple)) else eos)
-        return cls(tuple(prompt), tuple(int(t) for t in config.get("suppress_tokens") or ()),
+        spec = cls(tuple(prompt), tuple(int(t) for t in config.get("suppress_tokens") or ()),
                    tuple(int(t) for t in config.get("begin_suppress_tokens") or ()), eos)
+        if not timestamps:
+            return spec
+        if config.get("no_timestamps_token_id") is None:
+            raise ValueError("GenerationSpec: timestamps=True needs the generation config's no_timestamps_token_id")
+        cap = config.get("max_initial_timestamp_index")
+        return dataclasses.replace(spec, no_timestamps_token_id=int(config["no_timestamps_token_id"]),
+                                   max_initial_timestamp_index=None if cap is None else int(cap))
 
 
 def _byte_table():
@@ -320,13 +385,17 @@ class Whisper(WaveformNet):
         beg[list(spec.begin_suppress_tokens)] = 1
         return torch.from_numpy(sup).to(self.device), torch.from_numpy(beg).to(self.device)
 
-    def generate(self, features_or_wavs, spec: GenerationSpec, max_new_tokens: Optional[int] = None, lengths=None, sr: int = SAMPLING_RATE):
+    def generate(self, features_or_wavs, spec: GenerationSpec, max_new_tokens: Optional[int] = None, lengths=None, sr: int = SAMPLING_RATE,
+                 timestamps: bool = False):
         """Greedy decoding (the module docstring's definition) of features [B, num_mel_bins, frames], or of wavs as ``log_mel`` takes
         them -> (ids [B, n] int32, a row padded with eos after its end; lengths [B] int32, the tokens before a row's eos), both on the
-        device.  n is the number of steps decoded: at most ``max_new_tokens`` and ``max_target_positions - len(prompt)``."""
+        device.  n is the number of steps decoded: at most ``max_new_tokens`` and ``max_target_positions - len(prompt)``.
+        ``timestamps=True`` decodes one window under the long form's step rule (``spec`` with the timestamp fields)."""
         what = "Whisper.generate"
         self._need_weights(what)
         c = self.config
+        if timestamps:
+            self._timestamp_spec(spec, what)
         if not spec.prompt_ids or len(spec.prompt_ids) > c.max_target_positions:
             raise ValueError(f"{what}: a prompt of {len(spec.prompt_ids)} ids, max_target_positions is {c.max_target_positions}")
         if torch.is_tensor(features_or_wavs) and features_or_wavs.dim() == 3:
@@ -347,11 +416,15 @@ class Whisper(WaveformNet):
         for r in range(0, B, MAX_ROWS):
             fb, ib, lb = f[r:r + MAX_ROWS], ids[r:r + MAX_ROWS], lens[r:r + MAX_ROWS]
             ws = self._encode(fb, None)
+            tail = (fb.shape[0], max_new, SYNC_EVERY, ib.data_ptr(), lb.data_ptr(), C.byref(steps), ws.data_ptr(), ws.numel(), stream(self.device))
             with torch.cuda.device(self.device):
-                rc = ctx.lib.dex_whisper_generate(ctx.h, i32_ptr(prompt), len(prompt), sup.data_ptr(), beg.data_ptr(), int(spec.eos_token_id),
-                                                  fb.shape[0], max_new, SYNC_EVERY, ib.data_ptr(), lb.data_ptr(), C.byref(steps), ws.data_ptr(),
-                                                  ws.numel(), stream(self.device))
-            ctx.check(rc, "dex_whisper_generate")
+                if timestamps:
+                    cap = -1 if spec.max_initial_timestamp_index is None else int(spec.max_initial_timestamp_index)
+                    rc = ctx.lib.dex_whisper_generate_ts(ctx.h, i32_ptr(prompt), len(prompt), sup.data_ptr(), beg.data_ptr(), int(spec.eos_token_id),
+                                                         int(spec.no_timestamps_token_id), cap, *tail)
+                else:
+                    rc = ctx.lib.dex_whisper_generate(ctx.h, i32_ptr(prompt), len(prompt), sup.data_ptr(), beg.data_ptr(), int(spec.eos_token_id), *tail)
+            ctx.check(rc, "dex_whisper_generate_ts" if timestamps else "dex_whisper_generate")
             n = max(n, steps.value)
         return ids[:, :n], lens
 
@@ -363,14 +436,128 @@ class Whisper(WaveformNet):
         return [decode(ids[b, : int(lens[b])], vocab, spec.eos_token_id) for b in range(ids.shape[0])]
 
 
+    # ---- long form (the module docstring's definition)
+    def _timestamp_spec(self, spec: GenerationSpec, what: str):
+        c = self.config
+        if spec.no_timestamps_token_id is None:
+            raise ValueError(f"{what}: the spec has no no_timestamps_token_id (GenerationSpec.from_generation_config(..., timestamps=True))")
+        nots = int(spec.no_timestamps_token_id)
+        if not 0 <= int(spec.eos_token_id) <= nots < c.vocab_size - 1:
+            raise ValueError(f"{what}: no_timestamps_token_id {nots} must lie at or above eos_token_id {spec.eos_token_id} and inside the vocabulary of {c.vocab_size}")
+        if c.vocab_size - (nots + 1) < c.max_source_positions + 1:
+            raise ValueError(f"{what}: {c.vocab_size - (nots + 1)} timestamp ids behind no_timestamps_token_id, a window needs "
+                             f"max_source_positions + 1 = {c.max_source_positions + 1}")
+        if spec.max_initial_timestamp_index is not None and int(spec.max_initial_timestamp_index) < 0:
+            raise ValueError(f"{what}: max_initial_timestamp_index must be >= 0, got {spec.max_initial_timestamp_index}")
+
+    def log_mel_long(self, wavs, lengths=None, sr: int = SAMPLING_RATE):
+        """``wavs`` as ``log_mel`` takes them, rows of any length up to ``MAX_LONG_SAMPLES`` -> (features [B, num_mel_bins, F_max],
+        0.0 behind a row's frames; the rows' frame counts F, host int32 [B]).  A row of at most ``n_samples`` has ``log_mel``'s
+        features, a longer one those of ``WhisperFeatureExtractor(truncation=False)`` on the row alone.  Needs no weights."""
+        what = "Whisper.log_mel_long"
+        wavs, lengths = self._at_16k(wavs, lengths, sr, what)
+        x, ln, _ = device_rows(wavs, lengths, what, refuse=ValueError)
+        if int(ln.max()) > MAX_LONG_SAMPLES:
+            raise ValueError(f"{what}: a row of {int(ln.max())} samples is above the cap of {MAX_LONG_SAMPLES} (30 minutes)")
+        x = x[:, : int(ln.max())].contiguous().to(self.device)
+        B, n = x.shape
+        M, chunk_frames = self.config.num_mel_bins, 2 * self.config.max_source_positions
+        frames = np.where(ln <= self.n_samples, chunk_frames, ln // HOP).astype(np.int32)
+        F = int(frames.max())
+        out = torch.empty(B, M, F, dtype=torch.float32, device=self.device)
+        group = max(1, min(MAX_ROWS, _LONG_SCRATCH // (F * M * 8)))
+        scratch = torch.empty(min(group, B) * F * M, dtype=torch.float64, device=self.device)
+        ctx = self._ctx
+        for r in range(0, B, group):
+            xb, ob, lb = x[r:r + group], out[r:r + group], np.ascontiguousarray(ln[r:r + group])
+            fb = np.zeros(len(lb), np.int32)
+            with torch.cuda.device(self.device):
+                rc = ctx.lib.dex_whisper_log_mel_long(ctx.h, xb.data_ptr(), i32_ptr(lb), xb.shape[0], n, ob.data_ptr(), F, i32_ptr(fb),
+                                                      scratch.data_ptr(), scratch.numel() * 8, stream(self.device))
+            ctx.check(rc, "dex_whisper_log_mel_long")
+            assert np.array_equal(fb, frames[r:r + group])
+        return out, frames
+
+    def _gather(self, feats: torch.Tensor, rows, seeks, ns) -> torch.Tensor:
+        """The windows [seek, seek + n) of ``rows`` of ``feats`` [B, num_mel_bins, F_max] -> [len(rows), num_mel_bins, 2 x
+        max_source_positions], 0.0 behind n (at most ``MAX_ROWS`` windows)."""
+        ctx = self._ctx
+        out = torch.empty(len(rows), self.config.num_mel_bins, 2 * self.config.max_source_positions, dtype=torch.float32, device=self.device)
+        r, s, n = (np.ascontiguousarray(np.asarray(a, np.int32)) for a in (rows, seeks, ns))
+        with torch.cuda.device(self.device):
+            rc = ctx.lib.dex_whisper_gather_windows(ctx.h, feats.data_ptr(), feats.shape[0], feats.shape[2], i32_ptr(r), i32_ptr(s), i32_ptr(n), len(r),
+                                                    out.data_ptr(), stream(self.device))
+        ctx.check(rc, "dex_whisper_gather_windows")
+        return out
+
+    def generate_segments(self, wavs, spec: GenerationSpec, lengths=None, sr: int = SAMPLING_RATE, max_new_tokens: Optional[int] = None,
+                          _trace: Optional[list] = None):
+        """Long-form decoding (the module docstring's window loop) of ``wavs`` as ``log_mel_long`` takes them -> per row a list of
+        segments ``{"start", "end", "tokens"}``: seconds in float64 and the segment's ids (its timestamps included) as host ints.
+        ``_trace`` (a list, for tests and measurement) receives per network call the list of its (row, seek, n, new ids)."""
+        what = "Whisper.generate_segments"
+        self._need_weights(what)
+        self._timestamp_spec(spec, what)
+        feats, frames = self.log_mel_long(wavs, lengths, sr)
+        B, W, tb = feats.shape[0], 2 * self.config.max_source_positions, int(spec.no_timestamps_token_id) + 1
+        seek, out = [0] * B, [[] for _ in range(B)]
+        while True:
+            active = [b for b in range(B) if seek[b] < int(frames[b])]
+            if not active:
+                return out
+            for r in range(0, len(active), MAX_ROWS):
+                rows = active[r:r + MAX_ROWS]
+                ns = [min(int(frames[b]) - seek[b], W) for b in rows]
+                ids, lens = self.generate(self._gather(feats, rows, [seek[b] for b in rows], ns), spec, max_new_tokens, timestamps=True)
+                host = torch.cat([ids, lens[:, None]], dim=1).cpu().numpy()                 # the window's one device-to-host copy
+                if _trace is not None:                                                      # one entry per network call: (row, seek, n, ids)
+                    _trace.append([(b, seek[b], ns[a], host[a, : int(host[a, -1])].tolist()) for a, b in enumerate(rows)])
+                for a, b in enumerate(rows):
+                    segments, advance = retrieve_segments(host[a, : int(host[a, -1])].tolist(), tb, seek[b], ns[a])
+                    out[b] += segments
+                    seek[b] += advance
+
+    def transcribe_long(self, wavs, spec: GenerationSpec, vocab: Sequence[str], lengths=None, sr: int = SAMPLING_RATE,
+                        max_new_tokens: Optional[int] = None):
+        """``wavs`` of any length -> a list of transcripts: ``decode`` of each row's segments' ids joined."""
+        rows = self.generate_segments(wavs, spec, lengths, sr, max_new_tokens)
+        return [decode([t for seg in segments for t in seg["tokens"]], vocab, spec.eos_token_id) for segments in rows]
+
+
+def retrieve_segments(tokens: Sequence[int], timestamp_begin: int, seek: int, n: int):
+    """One window's new ids (the trailing eos stripped), decoded at frame ``seek`` over ``n`` frames -> (segments, the frames to
+    advance ``seek`` by), as HF's ``_retrieve_segment`` cuts them.  Host only."""
+    ts = [t >= timestamp_begin for t in tokens]
+    single_ending = ts[-2:] == [False, True]
+    cuts = [i + 1 for i in range(len(tokens) - 1) if ts[i] and ts[i + 1]]
+    t0 = seek * 0.01
+    if not cuts:
+        stamps = [t for t in tokens if t >= timestamp_begin]
+        # HF takes the window's end from a float32 tensor: int(n x 0.01 / 0.02) in that precision
+        last = float(stamps[-1] - timestamp_begin) if stamps and stamps[-1] != timestamp_begin else int(np.float32(n) * np.float32(0.01) / np.float32(0.02))
+        return [{"start": t0, "end": t0 + last * 0.02, "tokens": list(tokens)}], n
+    if single_ending:
+        cuts.append(len(tokens))
+    else:
+        cuts[-1] += 1                                 # the last pair's second timestamp stays with its segment's successor, as in HF
+    segments, prev = [], 0
+    for i, cut in enumerate(cuts):
+        piece = list(tokens[prev:cut])
+        end = piece[-1] if i < len(cuts) - 1 or single_ending else piece[-2]
+        segments.append({"start": t0 + float(piece[0] - timestamp_begin) * 0.02, "end": t0 + float(end - timestamp_begin) * 0.02, "tokens": piece})
+        prev = cut
+    return segments, n if single_ending else (tokens[prev - 2] - timestamp_begin) * 2
+
+
 def whisper_score(wavs, texts: Sequence[str], model: Optional[Whisper] = None, spec: Optional[GenerationSpec] = None,
-                  vocab: Optional[Sequence[str]] = None, sr: int = SAMPLING_RATE, lengths=None):
+                  vocab: Optional[Sequence[str]] = None, sr: int = SAMPLING_RATE, lengths=None, long_form: bool = False):
     """Every wav transcribed by ``model``; CER and WER of ``asr.normalize_sentence(transcript)`` against
     ``asr.normalize_sentence(text)`` (the reference's normaliser, not Whisper's: numbers stay as written) ->
-    (transcripts, cer_mean, cer_stderr, wer_mean, wer_stderr), the errors ``np.std / sqrt(n)``."""
+    (transcripts, cer_mean, cer_stderr, wer_mean, wer_stderr), the errors ``np.std / sqrt(n)``.  ``long_form=True``: rows of any
+    length, through ``transcribe_long`` (``spec`` with the timestamp fields)."""
     if not isinstance(model, Whisper) or spec is None or vocab is None:
         raise ValueError("whisper_score: pass model=Whisper(...) with the checkpoint's weights loaded, spec= and vocab= (the library ships none)")
-    preds = model.transcribe(wavs, spec, vocab, lengths, sr)
+    preds = (model.transcribe_long if long_form else model.transcribe)(wavs, spec, vocab, lengths, sr)
     if len(preds) != len(texts) or not preds:
         raise ValueError(f"whisper_score: {len(texts)} texts against {len(preds)} wavs")
     return (preds, *score_transcripts(texts, preds))

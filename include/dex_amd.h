@@ -747,6 +747,32 @@ int  dex_whisper_step_linear(const float* x_dev, const float* w_dev, float* y_de
  * adds one to *count_dev, any other id adds one to lengths_dev[b] */
 int  dex_whisper_pick(const float* logits_dev, int B, int V, const uint8_t* mask_dev, int eos, int32_t* finished_dev, int32_t* lengths_dev,
                       int32_t* count_dev, int32_t* ids_dev, int ld_ids, int step, dex_stream_t stream);
+/* ---- long-form scoring: decoding under the timestamp rule over 30 s windows (dex_tts_amd/whisper.py states the definition) */
+#define DEX_WHISPER_MAX_LONG_SAMPLES 28800000       /* the cap of a long row: 30 minutes at 16 kHz */
+/* the front end of rows of any length up to the cap: wav_dev [B, n_samples], row b lengths_host[b] samples.  A row of at most one
+ * chunk has the chunk's frames (the features of dex_whisper_log_mel); a longer row is reflected at its own ends, has lengths_host[b]
+ * / 160 frames and is floored at its own maximum over all of them - 8.  frames_host [B] receives the frame counts; out_dev [B,
+ * num_mel_bins, max_frames] (max_frames >= the largest count) is 0 behind a row's frames.  scratch_dev holds the fp64 log-spectrum
+ * of the call, B x max_frames x num_mel_bins doubles.  Needs no weights. */
+int  dex_whisper_log_mel_long(DexWhisper* w, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, float* out_dev,
+                              int max_frames, int32_t* frames_host, void* scratch_dev, size_t scratch_bytes, dex_stream_t stream);
+/* feat_dev [rows, num_mel_bins, max_frames] -> out_dev [active, num_mel_bins, 2 x max_source_positions]: window a is frames
+ * [seek_host[a], seek_host[a] + n_host[a]) of row row_host[a], followed by 0.0; active <= DEX_WHISPER_MAX_B */
+int  dex_whisper_gather_windows(DexWhisper* w, const float* feat_dev, int rows, int max_frames, const int32_t* row_host,
+                                const int32_t* seek_host, const int32_t* n_host, int active, float* out_dev, dex_stream_t stream);
+/* dex_whisper_generate under the timestamp rule (WhisperTimeStampLogitsProcessor) between the masks and the argmax: timestamps
+ * start at no_timestamps_token_id + 1 (at least max_source_positions + 1 of them), max_initial_timestamp_index -1 for none.  The
+ * rule's state (a row's last timestamp and new-token count) lives in the workspace; a step needs no host value. */
+int  dex_whisper_generate_ts(DexWhisper* w, const int32_t* prompt_host, int n_prompt, const uint8_t* suppress_dev, const uint8_t* begin_dev,
+                             int eos, int no_timestamps_token_id, int max_initial_timestamp_index, int B, int max_new, int sync_every,
+                             int32_t* ids_dev, int32_t* lengths_dev, int* steps_host, void* workspace_dev, size_t workspace_bytes,
+                             dex_stream_t stream);
+/* the step tail under the timestamp rule alone, as dex_whisper_pick (step >= 2): n_new_dev [B] a row's new-token count (the rule's
+ * step index i; one is added), last_timestamp_dev [B] its last emitted timestamp id or -1 (updated), its last two new ids are read
+ * from ids_dev at columns step - 1 and step - 2 where n_new has them */
+int  dex_whisper_pick_ts(const float* logits_dev, int B, int V, const uint8_t* mask_dev, int eos, int no_timestamps_token_id,
+                         int max_initial_timestamp_index, int32_t* finished_dev, int32_t* lengths_dev, int32_t* count_dev,
+                         int32_t* ids_dev, int ld_ids, int step, int32_t* last_timestamp_dev, int32_t* n_new_dev, dex_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,15 @@ Each timing is a host clock around one call that ends in a device synchronise (t
 split by events inside its call); the two implementations alternate inside every repetition; medians are printed.  ``prompt`` and
 ``per token`` are derived: a 1-token and an n-token decode differ by n - 1 steps.  For the step the bytes of the decoder's weights
 (read once per token for the whole batch) and of the cross-attention K / V (read once per token per row) are divided by its time.
-The second table times one linear of the step alone, the skinny-M streaming kernel against launch_igemm, at M = 1, 8 and 32 rows."""
+The second table times one linear of the step alone, the skinny-M streaming kernel against launch_igemm, at M = 1, 8 and 32 rows.
+
+    python tools/whisper_bench.py --long 46 [--batches 1,8] [--reps 5] [--tokens 48]
+
+The long form at whisper-large-v3 geometry, random weights: (a) the per-token time of ``generate`` under the timestamp rule against
+plain ``generate`` on the same features with the same forced step count (eos suppressed), the two alternating inside every
+repetition, with the run-to-run spread (max - min over the repetitions) of each; (b) one ``generate_segments`` call on wavs of that
+many seconds (``--tokens`` new tokens per window at most): its time and window count against the sum of its window calls (gather,
+encoder, decode) run one by one, and the long front end alone."""
 import argparse
 import ctypes as C
 import json
@@ -216,6 +224,49 @@ def bench_linear(cfg, reps):
     return rows
 
 
+LONG_NOTS, LONG_EOS = 50364, 50257          # whisper-large-v3: <|notimestamps|>, <|endoftext|>; 1501 timestamps behind the former
+
+
+def bench_long(cfg, seconds, batches, reps, warmup, n_tok, seed):
+    with torch.no_grad():
+        lib = whisper.Whisper(R.library_config(cfg), "cuda").load_state_dict(make_weights(cfg, seed, "cuda"))
+        plain = whisper.GenerationSpec(PROMPT, (LONG_EOS,), (LONG_EOS,), LONG_EOS)
+        rule = whisper.GenerationSpec(PROMPT, (LONG_EOS,), (LONG_EOS,), LONG_EOS, LONG_NOTS, 50)
+        rows = []
+        for B in batches:
+            g = torch.Generator().manual_seed(seed + 1)
+            n = int(seconds * 16000)
+            wavs = (0.1 * torch.randn(B, n, generator=g).cumsum(1).sin() + 0.01 * torch.randn(B, n, generator=g)).float().cuda()
+            feat = lib.log_mel(wavs[:, : R.n_samples(cfg)])
+            t = {k: [] for k in ("plain", "rule", "mel", "call", "windows")}
+            for r in range(warmup + reps):
+                one, _ = timed(lambda: lib.generate(feat, plain, 1))
+                all_, _ = timed(lambda: lib.generate(feat, plain, n_tok))
+                r_one, _ = timed(lambda: lib.generate(feat, rule, 1, timestamps=True))
+                r_all, (ids, _) = timed(lambda: lib.generate(feat, rule, n_tok, timestamps=True))
+                assert ids.shape[1] == n_tok
+                mel, _ = timed(lambda: lib.log_mel_long(wavs))
+                trace = []
+                call, _ = timed(lambda: lib.generate_segments(wavs, rule, max_new_tokens=n_tok, _trace=trace))
+                feats, _ = lib.log_mel_long(wavs)
+                parts = 0.0
+                for grp in trace:
+                    ms, _ = timed(lambda: lib.generate(lib._gather(feats, [b for b, _, _, _ in grp], [s for _, s, _, _ in grp], [nn for _, _, nn, _ in grp]),
+                                                       rule, n_tok, timestamps=True))
+                    parts += ms
+                if r >= warmup:
+                    for k, v in zip(t, ((all_ - one) / (n_tok - 1), (r_all - r_one) / (n_tok - 1), mel, call, parts)):
+                        t[k].append(v)
+            row = dict(model="large-v3", B=B, seconds=seconds, tokens=n_tok, reps=reps,
+                       plain_per_token_ms=med(t["plain"]), plain_spread_ms=max(t["plain"]) - min(t["plain"]),
+                       rule_per_token_ms=med(t["rule"]), rule_spread_ms=max(t["rule"]) - min(t["rule"]),
+                       long_mel_ms=med(t["mel"]), long_call_ms=med(t["call"]), window_calls=len(trace), windows=sum(len(grp) for grp in trace),
+                       sum_of_windows_ms=med(t["windows"]))
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        return rows
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="base.en,large-v3")
@@ -225,7 +276,15 @@ def main(argv=None):
     ap.add_argument("--tokens", type=int, default=48)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--long", type=float, default=None, metavar="SECONDS", help="the long-form case alone (large-v3 geometry, B = 1 and 8 by default)")
     a = ap.parse_args(argv)
+    if a.long is not None:
+        out = {"long": bench_long(MODELS["large-v3"], a.long, [int(b) for b in (a.batches if a.batches != "1,8,32" else "1,8").split(",")], a.reps,
+                                  a.warmup, a.tokens, a.seed)}
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     out = {"network": [], "linear": []}
     for name in a.models.split(","):
         out["linear"] += [dict(r, model=name) for r in bench_linear(MODELS[name], a.reps)]
