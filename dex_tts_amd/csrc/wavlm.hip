@@ -3,6 +3,7 @@
 // bias, TDNN / statistics-pooling head).  fp32 throughout, channels-last [B][T][C].  C ABI dex_wavlm_*.  Row b of a batch is the
 // network applied to row b alone at its own length.
 //
+// (the next four kernels and the padded positional convolution are in wav_groupnorm.h, shared with mos.hip)
 //   wavlm_conv0_kernel     the first convolution (Cin = 1), raw: 8 frames x all channels per workgroup, the sample window in LDS.
 //   wavlm_gn_part_kernel,  GroupNorm(C, C) of layer 0: per (row, channel) over the row's OWN frames, two passes - the sums of 512-frame
 //   wavlm_gn_final_kernel, chunks in fp64, added in chunk order, first of x (mean), then of (x - mean)^2 (biased variance): a DC offset
@@ -34,6 +35,7 @@
 
 #include "../../include/dex_amd.h"
 #include "kernels.h"
+#include "wav_groupnorm.h"
 #include "wav_trunk.h"
 #include "weight_store.h"
 
@@ -45,107 +47,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 static_assert(MAXC == DEX_WAVLM_MAX_CONV, "ConvSpec holds DEX_WAVLM_MAX_CONV layers");
 constexpr int MAXT = DEX_WAVLM_MAX_TDNN;
 constexpr int MAXF = DEX_WAVLM_MAX_FRAMES;
-constexpr int GN_CHUNK = 512;            // frames per partial sum of the group norm
-
-struct Conv0P { const float* x; long x_ld; const float* w; const float* bias; float* out; int T0, C, k, s; };
-
-// frames [F0 blockIdx.x, + F0) of utterance blockIdx.y: out[b][t][c] = bias[c] + sum_j w[c][j] x[b][t s + j] (taps ascending, fmaf)
-__global__ __launch_bounds__(256) void wavlm_conv0_kernel(const Conv0P p) {
-    __shared__ float xs[(F0 - 1) * S0_MAX + K0_MAX];
-    const int tid = threadIdx.x, b = blockIdx.y, t0 = blockIdx.x * F0;
-    const int nwin = (F0 - 1) * p.s + p.k;
-    const float* x = p.x + (long)b * p.x_ld;
-    for (int i = tid; i < nwin; i += 256) {
-        const long idx = (long)t0 * p.s + i;
-        xs[i] = idx < p.x_ld ? x[idx] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int ci = 0; ci < 2; ++ci) {
-        const int c = tid + 256 * ci;
-        if (c >= p.C) continue;
-        float w[K0_MAX];
-#pragma unroll
-        for (int j = 0; j < K0_MAX; ++j) w[j] = j < p.k ? p.w[(long)c * p.k + j] : 0.f;
-        const float bs = p.bias ? p.bias[c] : 0.f;
-#pragma unroll
-        for (int f = 0; f < F0; ++f) {
-            float v = bs;
-#pragma unroll
-            for (int j = 0; j < K0_MAX; ++j)
-                if (j < p.k) v = fmaf(w[j], xs[f * p.s + j], v);
-            if (t0 + f < p.T0) p.out[((long)b * p.T0 + t0 + f) * p.C + c] = v;
-        }
-    }
-}
-
-// part[b][chunk][c] = sum over the chunk's frames below len0[b] of x (SQ: of (x - mean[b][c])^2), fp64; 64 channels x 4 frame lanes
-// per workgroup, the four lanes added in a fixed order.  grid (chunks, ceil(C / 64), B)
-template <bool SQ>
-__global__ __launch_bounds__(256) void wavlm_gn_part_kernel(const float* X, int T0, int C, const int* len0, const double* mean, double* part) {
-    __shared__ double red[4][64];
-    const int cl = threadIdx.x & 63, ts = threadIdx.x >> 6;
-    const int c = blockIdx.y * 64 + cl, b = blockIdx.z, ch = blockIdx.x;
-    const int L = min(len0[b], T0);
-    const int tbeg = ch * GN_CHUNK, tend = min(tbeg + GN_CHUNK, L);
-    double s = 0.0;
-    if (c < C) {
-        const double m = SQ ? mean[(long)b * C + c] : 0.0;
-        const float* x = X + (long)b * T0 * C + c;
-        for (int t = tbeg + ts; t < tend; t += 4) {
-            const double v = (double)x[(long)t * C] - m;
-            s = SQ ? fma(v, v, s) : s + v;
-        }
-    }
-    red[ts][cl] = s;
-    __syncthreads();
-    if (ts == 0 && c < C) part[((long)b * gridDim.x + ch) * C + c] = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
-}
-
-// the chunks of a row in order: mean[b][c] = sum / L (SQ: rstd[b][c] = 1 / sqrt(sum / L + eps))
-template <bool SQ>
-__global__ __launch_bounds__(256) void wavlm_gn_final_kernel(const double* part, int nchunk, int T0, int C, const int* len0, double* mean, float* rstd,
-                                                            float eps) {
-    const int c = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-    if (c >= C) return;
-    const int L = min(len0[b], T0), nc = (L + GN_CHUNK - 1) / GN_CHUNK;
-    double s = 0.0;
-    for (int ch = 0; ch < nc; ++ch) s += part[((long)b * nchunk + ch) * C + c];
-    if (SQ) rstd[(long)b * C + c] = (float)(1.0 / sqrt(s / (double)L + (double)eps));
-    else mean[(long)b * C + c] = s / (double)L;
-}
-
-// X [B][T0][C] in place: GELU((x - mean) rstd gamma + beta), the difference in fp64; 0 at or past len0[b]
-__global__ __launch_bounds__(256) void wavlm_gn_apply_kernel(float* X, int T0, int C, const int* len0, const double* mean, const float* rstd,
-                                                            const float* gamma, const float* beta, long n4) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n4) return;
-    const long e = i * 4, row = e / C;
-    const int c = (int)(e - row * C);
-    const int b = (int)(row / T0), t = (int)(row - (long)b * T0);
-    float4* x4 = reinterpret_cast<float4*>(X) + i;
-    if (t >= len0[b]) { *x4 = make_float4(0.f, 0.f, 0.f, 0.f); return; }
-    const float4 v = *x4;
-    const float xv[4] = {v.x, v.y, v.z, v.w};
-    float r[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const long sc = (long)b * C + c + u;
-        const float d = (float)((double)xv[u] - mean[sc]);
-        r[u] = gelu_erf_(d * rstd[sc] * gamma[c + u] + beta[c + u]);
-    }
-    *x4 = make_float4(r[0], r[1], r[2], r[3]);
-}
-
-// h[row][g cg + c] = y[row][g cg + c] + pp[row][g cgp + c]: the padded groups of the positional convolution back onto the residual
-__global__ __launch_bounds__(256) void wavlm_unpad_add_kernel(const float* y, const float* pp, float* h, long rows, int G, int cg, int cgp) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    const int H = G * cg;
-    if (i >= rows * H) return;
-    const long row = i / H;
-    const int ch = (int)(i - row * H), g = ch / cg, c = ch - g * cg;
-    h[i] = y[i] + pp[(row * G + g) * cgp + c];
-}
 
 // one thread per (frame, head): gw [8][64], gb [8], gc [heads] -> gate [B][heads][T]
 __global__ __launch_bounds__(256) void wavlm_gate_kernel(const float* X, const float* gw, const float* gb, const float* gc, float* gate, int B, int T,
@@ -384,25 +285,6 @@ __global__ __launch_bounds__(256) void wavlm_pack_pad_kernel(const float* src, f
     dst[idx] = (n < N && c < seg) ? src[(long)n * nseg * seg + (long)sg * seg + c] : 0.f;
 }
 
-// positional convolution v [G cg][cg][k] times scale[tap] (fp64) -> per group [k cgp][cgp] (row = tap cgp + ci), zeros in the padding
-__global__ __launch_bounds__(256) void wavlm_pack_pos_kernel(const float* v, const double* scale, float* dst, int G, int cg, int cgp, int k) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long)G * k * cgp * cgp) return;
-    const int co = (int)(idx % cgp);
-    long r = idx / cgp;
-    const int ci = (int)(r % cgp); r /= cgp;
-    const int tap = (int)(r % k), g = (int)(r / k);
-    dst[idx] = (co < cg && ci < cg) ? (float)((double)v[((long)(g * cg + co) * cg + ci) * k + tap] * scale[tap]) : 0.f;
-}
-
-// dst [G cgp] = src [G cg] with zeros in the padding
-__global__ __launch_bounds__(256) void wavlm_pad_vec_kernel(const float* src, float* dst, int G, int cg, int cgp) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= G * cgp) return;
-    const int g = i / cgp, c = i - g * cgp;
-    dst[i] = c < cg ? src[g * cg + c] : 0.f;
-}
-
 DexWavlmConfig default_config() {
     DexWavlmConfig c;
     std::memset(&c, 0, sizeof c);
@@ -461,10 +343,6 @@ int bucket_of(const DexWavlmConfig& c, long d) {
     const long big = max_exact + (long)v;
     return side + (int)(big < nb - 1 ? big : nb - 1);
 }
-int pad32(int n) { return (n + 31) & ~31; }
-// channels of a positional-convolution group as the GEMM takes them
-int pos_group_pad(const Trunk& t) { const int cg = t.hidden / t.pos_groups; return cg % 32 ? (cg + 63) & ~63 : cg; }
-
 const TrunkKeys KEYS("wavlm.");
 std::string tk(int i, const char* what) { return "tdnn." + std::to_string(i) + ".kernel." + what; }
 
@@ -510,27 +388,11 @@ const float* pack_pad(DexWavlm* s, const std::string& key, int N, int Npad, int 
     if (d) hipLaunchKernelGGL(wavlm_pack_pad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s->R(key), d, N, Npad, seg, segpad, nseg);
     return d;
 }
-const float* pad_vec(DexWavlm* s, const std::string& key, int G, int cg, int cgp, hipStream_t st) {
-    if (cg == cgp) return s->R(key);
-    float* d = s->alloc((long)G * cgp);
-    if (d) hipLaunchKernelGGL(wavlm_pad_vec_kernel, dim3((G * cgp + 255) / 256), dim3(256), 0, st, s->R(key), d, G, cg, cgp);
-    return d;
-}
 
 int pack_all(DexWavlm* s, hipStream_t st) {
     const DexWavlmConfig& c = s->c;
     const Trunk& t = s->t;
-    // the positional convolution with its groups padded to what the GEMM takes (zeros in the padding)
-    auto pack_pos = [&](const double* scale) {
-        const int G = t.pos_groups, K = t.pos_k, cg = t.hidden / G, cgp = pos_group_pad(t);
-        const long n = (long)G * K * cgp * cgp;
-        float* pw = s->alloc(n);
-        if (scale && pw)
-            hipLaunchKernelGGL(wavlm_pack_pos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s->R(KEYS.ENC + "pos_conv_embed.conv.weight_v"), scale,
-                               pw, G, cg, cgp, K);
-        s->w.pos_w = pw;
-        s->w.pos_b = pad_vec(s, KEYS.ENC + "pos_conv_embed.conv.bias", G, cg, cgp, st);
-    };
+    auto pack_pos = [&](const double* scale) { pack_pos_padded(s, KEYS, t, s->w, scale, st); };
     if (int rc = finalize_trunk(s, KEYS, t, false, s->w, pack_pos, st)) return rc;
     s->rel_embed = s->R(KEYS.lk(0, "attention.rel_attn_embed.weight"));
     s->gates.clear();
@@ -568,21 +430,19 @@ int pack_all(DexWavlm* s, hipStream_t st) {
 // workspace: the trunk's prefix | mix [B][T][H] | yp, pp [B][T][G cgp] (padded positional groups) | gate [B][heads][T] |
 // rel [heads][2T - 1] | mask [B][T] | gnpart (fp64) [B][chunks][C_0] | gnmean (fp64) [B][C_0] | gnrstd [B][C_0] |
 // ta, tb [B][T][max tdnn width] | stats [B][2 Cpad] | lens (int) [n_conv + 1][B]
-struct Ws : TrunkWs { float *mix, *yp, *pp, *gate, *rel, *gnrstd, *ta, *tb, *stats; double *gnpart, *gnmean; size_t bytes; int nchunk; };
+struct Ws : TrunkWs, GnWs, PosWs { float *mix, *gate, *rel, *ta, *tb, *stats; size_t bytes; };
 Ws plan(const DexWavlm* s, void* ws, long B, long n) {
     const DexWavlmConfig& c = s->c;
     Ws w{};
     Taker tk(ws);
     plan_trunk(s->t, tk, B, n, w);
-    w.nchunk = (w.Tl[0] + GN_CHUNK - 1) / GN_CHUNK;
     const long T = w.T, H = c.hidden;
     long tdw = 0;
     for (int i = 0; i < c.n_tdnn; ++i) tdw = pad32(c.tdnn_dim[i]) > tdw ? pad32(c.tdnn_dim[i]) : tdw;
-    const long cgp = pos_group_pad(s->t), G = s->t.pos_groups, padded = cgp * G != H;
     w.mix = tk.take(B * T * H);
-    w.yp = tk.take(padded ? B * T * G * cgp : 0); w.pp = tk.take(padded ? B * T * G * cgp : 0);
+    plan_pos_padded(s->t, tk, B, T, w);
     w.gate = tk.take(B * c.n_heads * T); w.rel = tk.take((long)c.n_heads * (2 * T - 1)); w.mask = tk.take(B * T);
-    w.gnpart = (double*)tk.take(2 * B * w.nchunk * c.conv_dim[0]); w.gnmean = (double*)tk.take(2 * B * c.conv_dim[0]); w.gnrstd = tk.take(B * c.conv_dim[0]);
+    plan_groupnorm(tk, B, w.Tl[0], c.conv_dim[0], w);
     w.ta = tk.take(B * T * tdw); w.tb = tk.take(B * T * tdw); w.stats = tk.take(B * 2 * pad32(c.tdnn_dim[c.n_tdnn - 1]));
     w.lens = (int*)tk.take((long)(c.n_conv + 1) * B);
     w.bytes = tk.bytes();
@@ -596,33 +456,10 @@ int enqueue_encoder(DexWavlm* s, const float* wav, const int32_t* lengths_host, 
     const TrunkWeights& W = s->w;
     const int T = w.T, H = c.hidden;
     enqueue_front(t, w, wav, lengths_host, B, n, do_normalize, st);
-    {   // layer 0: the raw convolution, then the group norm over each row's own frames, GELU
-        const int T0 = w.Tl[0], C0 = c.conv_dim[0];
-        const int* len0 = w.lens + B;
-        const Conv0P p{do_normalize ? w.xn : wav, (long)n, W.conv_w[0], W.conv_b[0], w.fa, T0, C0, c.conv_kernel[0], c.conv_stride[0]};
-        hipLaunchKernelGGL(wavlm_conv0_kernel, dim3((T0 + F0 - 1) / F0, B), dim3(256), 0, st, p);
-        const dim3 pg(w.nchunk, (C0 + 63) / 64, B), fg((C0 + 255) / 256, B);
-        hipLaunchKernelGGL(wavlm_gn_part_kernel<false>, pg, dim3(256), 0, st, w.fa, T0, C0, len0, nullptr, w.gnpart);
-        hipLaunchKernelGGL(wavlm_gn_final_kernel<false>, fg, dim3(256), 0, st, w.gnpart, w.nchunk, T0, C0, len0, w.gnmean, nullptr, 0.f);
-        hipLaunchKernelGGL(wavlm_gn_part_kernel<true>, pg, dim3(256), 0, st, w.fa, T0, C0, len0, w.gnmean, w.gnpart);
-        hipLaunchKernelGGL(wavlm_gn_final_kernel<true>, fg, dim3(256), 0, st, w.gnpart, w.nchunk, T0, C0, len0, nullptr, w.gnrstd, 1e-5f);
-        const long n4 = (long)B * T0 * C0 / 4;
-        hipLaunchKernelGGL(wavlm_gn_apply_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, w.fa, T0, C0, len0, w.gnmean, w.gnrstd, W.conv_g[0],
-                           W.conv_be[0], n4);
-    }
+    enqueue_conv0_groupnorm(t, W, w, w, do_normalize ? w.xn : wav, B, n, st);       // layer 0: the raw convolution, the group norm, GELU
     enqueue_projection(t, W, w, enqueue_conv_tail<false>(t, W, w, B, 1, st), B, st);
     const long rows = (long)B * T;
-    // h = LN(y + GELU(pos_conv(y)) without its last frame)
-    {
-        const int G = t.pos_groups, K = t.pos_k, cg = H / G, cgp = pos_group_pad(t);
-        if (cgp == cg) {
-            gemm(w.y, H, T, cg, K, 1, -(K / 2), T, W.pos_w, cg, G, W.pos_b, w.h, 1, w.y, nullptr, B, st);
-        } else {
-            dex::launch_group_pad(w.y, w.yp, rows, G, cg, cgp, st);
-            gemm(w.yp, G * cgp, T, cgp, K, 1, -(K / 2), T, W.pos_w, cgp, G, W.pos_b, w.pp, 1, nullptr, nullptr, B, st);
-            hipLaunchKernelGGL(wavlm_unpad_add_kernel, dim3((unsigned)((rows * H + 255) / 256)), dim3(256), 0, st, w.y, w.pp, w.h, rows, G, cg, cgp);
-        }
-    }
+    enqueue_pos_padded(t, W, w, w, B, st);                                              // h = LN(y + GELU(pos_conv(y)) without its last frame)
     layer_norm<false>(w.h, w.h, rows, T, H, W.enc_g, W.enc_be, c.layer_norm_eps, nullptr, st);
     const long n4 = rows * H / 4;
     const dim3 mg((unsigned)((n4 + 255) / 256));

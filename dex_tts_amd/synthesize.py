@@ -148,6 +148,14 @@ def sim_scores(model, audio, ref_wavs, sr: int = 22050, ref_sr: Optional[int] = 
     return wavlm.score_synthesis(model, audio, ref_wavs, sr, ref_sr)
 
 
+def mos_scores(model, audio, sr: int = 22050, domain: int = 0, judge: int = 288):
+    """The UTMOS naturalness score (predicted MOS) of ``synthesize_tokens``' list of int16 waveforms (``sr`` Hz), on the device ->
+    (mos [B], mean, stderr).  ``model`` is a ``mos.UTMOS`` with the checkpoint's weights loaded (mos.py states what the score is and
+    its departures: the row-alone batching, the resampler, and that it has not been checked against the real checkpoint)."""
+    from . import mos
+    return mos.score_synthesis(model, audio, sr, domain, judge)
+
+
 def asr_scores(model, audio, texts, sr: int = 22050):
     """The reference's ASR score (src/metric.py:21-67) of ``synthesize_tokens``' list of int16 waveforms (``sr`` Hz) against the
     input texts, in the same order -> (transcripts, cer_mean, cer_stderr, wer_mean, wer_stderr).  ``model`` is an

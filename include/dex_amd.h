@@ -679,6 +679,64 @@ int  dex_wavlm_hidden(DexWavlm* w, const float* wav_dev, const int32_t* lengths_
 int  dex_wavlm_embed(DexWavlm* w, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, int do_normalize,
                      float* embed_dev, void* workspace_dev, size_t workspace_bytes, dex_stream_t stream);
 
+/* ---- UTMOS naturalness score (MOS prediction): the UTMOS22 "strong learner" in eval mode, fp32 - the wav2vec 2.0 base trunk
+ * (group-norm feature extractor, post-layer-norm encoder, head_dim 64, plain softmax attention; last_hidden_state), every frame
+ * conditioned on a domain and a listener embedding, a bidirectional single-layer LSTM, Linear - ReLU - Linear per frame, and
+ * mean over the frames x 2 + 3.  Row b of a batch is the network applied to row b alone at its own length: the group norm, the
+ * attention keys, the reverse direction of the LSTM (which starts at the row's own last frame) and the mean end at its own frames.
+ * Lengths and ids are HOST arrays; bad arguments return an error code, with a message in the handle's last error, before anything
+ * is enqueued.  No compute call synchronises or allocates.  One call takes rows of at most DEX_MOS_MAX_FRAMES encoder frames; every
+ * row needs one frame (dex_mos_min_samples). */
+typedef struct DexMos DexMos;
+#define DEX_MOS_MAX_CONV 8
+#define DEX_MOS_MAX_FRAMES 4096
+#define DEX_MOS_MAX_LSTM 512
+typedef struct {
+    int32_t n_conv;                                   /* feature-extractor layers (7) */
+    int32_t conv_dim[DEX_MOS_MAX_CONV], conv_kernel[DEX_MOS_MAX_CONV], conv_stride[DEX_MOS_MAX_CONV];
+    int32_t conv_bias;                                /* 1: the convolutions carry a bias (0 in wav2vec2-base) */
+    int32_t feat_extract_norm_group;                  /* 1 = 'group' (the only one built) */
+    int32_t hidden, n_layers, n_heads, intermediate;
+    int32_t do_stable_layer_norm;                     /* 0 (the only one built) */
+    int32_t num_conv_pos_embeddings, num_conv_pos_embedding_groups;
+    float   layer_norm_eps;
+    int32_t num_domains, domain_dim, num_judges, judge_dim;    /* Embedding(3, 128), Embedding(3000, 128) */
+    int32_t lstm_hidden;                              /* H of the bidirectional LSTM: a multiple of 64 up to DEX_MOS_MAX_LSTM (512) */
+    int32_t proj_hidden;                              /* width of the projection's hidden layer (2048) */
+} DexMosConfig;
+/* NULL = the UTMOS22 strong-learner values.  DEX_ERR_ARG (and *out = NULL) for a config outside the family that is built. */
+int  dex_mos_create(const DexMosConfig* cfg, DexMos** out);
+void dex_mos_destroy(DexMos* m);
+const char* dex_mos_last_error(const DexMos* m);
+/* one weight under its key: the trunk's HF keys under wav2vec2. (the positional convolution as weight_g / weight_v),
+ * domain_embedding.weight, judge_embedding.weight, decoder_rnn.{weight_ih,weight_hh,bias_ih,bias_hh}_l0[_reverse],
+ * projection.0.{weight,bias}, projection.3.{weight,bias}; stream-ordered */
+int  dex_mos_load(DexMos* m, const char* key, const float* w_dev, const int64_t* shape, int ndim, dex_stream_t stream);
+int  dex_mos_finalize(DexMos* m, dex_stream_t stream);
+int  dex_mos_num_weights(const DexMos* m);
+int  dex_mos_weight_info(const DexMos* m, int i, const char** key, int64_t shape[4], int* ndim);
+/* host only (NULL = default config): encoder frames of n_samples samples; the fewest samples a row may have (400: one frame) */
+int  dex_mos_num_frames(const DexMosConfig* cfg, int n_samples);
+int  dex_mos_min_samples(const DexMosConfig* cfg);
+size_t dex_mos_workspace_bytes(const DexMos* m, int B, int max_samples);         /* 0 for bad arguments */
+size_t dex_mos_bilstm_workspace_bytes(const DexMos* m, int B, int T);            /* of dex_mos_bilstm; 0 for bad arguments */
+/* wav_dev [B, n_samples] raw samples, row b lengths_host[b] samples; do_normalize != 0: zero mean and unit variance per row first
+ * -> hidden_dev [B, T, hidden], T = dex_mos_num_frames(n_samples): last_hidden_state; row b fills its own frames and 0 past them */
+int  dex_mos_hidden(DexMos* m, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, int do_normalize,
+                    float* hidden_dev, void* workspace_dev, size_t workspace_bytes, dex_stream_t stream);
+/* the recurrence alone: feat_dev [B, T, hidden], row b frames_host[b] frames (1 .. T), conditioned on domain_host[b], judge_host[b]
+ * -> out_dev [B, T, 2 x lstm_hidden] (forward | reverse), 0 past a row's frames */
+int  dex_mos_bilstm(DexMos* m, const float* feat_dev, const int32_t* frames_host, const int32_t* domain_host, const int32_t* judge_host,
+                    int B, int T, float* out_dev, void* workspace_dev, size_t workspace_bytes, dex_stream_t stream);
+/* the whole network -> frames_dev [B, T]: the projection's score of every frame, 0 past a row's frames */
+int  dex_mos_frames(DexMos* m, const float* wav_dev, const int32_t* lengths_host, const int32_t* domain_host, const int32_t* judge_host,
+                    int B, int n_samples, int do_normalize, float* frames_dev, void* workspace_dev, size_t workspace_bytes,
+                    dex_stream_t stream);
+/* the whole network -> score_dev [B]: mean over the row's own frames x 2 + 3 */
+int  dex_mos_score(DexMos* m, const float* wav_dev, const int32_t* lengths_host, const int32_t* domain_host, const int32_t* judge_host,
+                   int B, int n_samples, int do_normalize, float* score_dev, void* workspace_dev, size_t workspace_bytes,
+                   dex_stream_t stream);
+
 /* ---- Whisper ASR score: HF's WhisperForConditionalGeneration in eval mode (log-mel front end of WhisperFeatureExtractor, encoder,
  * decoder with a key/value cache, greedy decoding), in fp32.  The family built: head_dim 64, erf GELU, scale_embedding = False,
  * learned decoder positions, num_mel_bins <= 128.  One workspace carries a batch from dex_whisper_encode (encoder output, the
