@@ -1,14 +1,16 @@
-"""What the wrappers of the two waveform transformers share (asr.py: wav2vec 2.0 CTC; wavlm.py: WavLM x-vector), the Python side of
-``csrc/wav_trunk.h``: the trunk's half of the config struct (``fill_trunk_config``), the weight inventory of a handle
-(``weight_shapes``), the routing of an HF state dict (``route_hf_state_dict``), the handle (``NetHandle``) and the base class of the
-two networks (``WaveformNet``: device, weights, the front end that brings wavs to 16 kHz rows, and the body of every network call).
-``_native.py`` stays what every wrapper of the library shares."""
+"""What the wrappers of the waveform networks share (asr.py: wav2vec 2.0 CTC; wavlm.py: WavLM x-vector; mos.py: UTMOS; whisper.py),
+the Python side of ``csrc/wav_trunk.h``: the trunk's half of the config struct (``fill_trunk_config``), the weight inventory of a
+handle (``weight_shapes``), the host-only entry points of a network (``HostEntry``: frame counts, the inventory of a config, the
+lengths one call refuses), the routing of an HF state dict (``route_hf_state_dict``), the handle (``NetHandle``) and the base class
+of the networks (``WaveformNet``: device, weights, the front end that brings wavs to 16 kHz rows, the checked inputs and the body of
+every network call).  ``_native.py`` stays what every wrapper of the library shares."""
 from __future__ import annotations
 
 import ctypes as C
 
 import torch
 
+from . import _lib
 from ._native import Handle, device_index, device_rows, i32_ptr, pad_wavs, resample_to_16k, stream, upload_weights
 
 SAMPLING_RATE = 16000
@@ -44,6 +46,51 @@ def weight_shapes(lib, prefix: str, handle) -> dict:
         getattr(lib, prefix + "_weight_info")(handle, i, C.byref(key), shape, C.byref(nd))
         out[key.value.decode()] = tuple(int(shape[k]) for k in range(nd.value))
     return out
+
+
+class HostEntry:
+    """The host-only entry points of the network whose C symbols start with ``prefix``: ``c_config`` makes the C struct of a config,
+    ``default`` is the config class, ``config_name`` heads the refusal of a config outside the family.  No device is touched."""
+
+    def __init__(self, prefix: str, c_config, default, config_name: str):
+        self.prefix, self.c_config, self.default, self.config_name = prefix, c_config, default, config_name
+
+    def _c(self, config):
+        return self.c_config(config or self.default())
+
+    def num_frames(self, n_samples: int, config=None) -> int:
+        n = int(getattr(_lib.load(), self.prefix + "_num_frames")(C.byref(self._c(config)), int(n_samples)))
+        if n < 0:
+            raise ValueError(f"num_frames: bad arguments ({n_samples} samples)")
+        return n
+
+    def min_samples(self, config=None) -> int:
+        n = int(getattr(_lib.load(), self.prefix + "_min_samples")(C.byref(self._c(config))))
+        if n < 0:
+            raise ValueError("min_samples: bad geometry")
+        return n
+
+    def state_dict_shapes(self, config=None) -> dict:
+        """The inventory of a handle that lives for this call only."""
+        lib, h = _lib.load(), C.c_void_p()
+        if getattr(lib, self.prefix + "_create")(C.byref(self._c(config)), C.byref(h)) != _lib.DEX_OK:
+            raise NotImplementedError(f"{self.config_name}.{getattr(lib, self.prefix + '_last_error')(None).decode()}")
+        try:
+            return weight_shapes(lib, self.prefix, h)
+        finally:
+            getattr(lib, self.prefix + "_destroy")(h)
+
+    def check_lengths(self, lengths, n_samples: int, config, what: str, too_short: str, max_frames: int) -> int:
+        """``ValueError`` for a row below ``min_samples`` (``too_short`` says what needs them) and for a padded length of more than
+        ``max_frames`` encoder frames.  Returns the frames of ``n_samples``."""
+        need = self.min_samples(config)
+        short = [int(v) for v in lengths if v < need]
+        if short:
+            raise ValueError(f"{what}: {short[0]} samples are too short: {too_short.format(need=need)}")
+        T = self.num_frames(n_samples, config)
+        if T > max_frames:
+            raise ValueError(f"{what}: {n_samples} samples are {T} encoder frames; one call takes at most {max_frames}")
+        return T
 
 
 _HF_PARAM = {"parametrizations.weight.original0": "weight_g", "parametrizations.weight.original1": "weight_v"}
@@ -97,9 +144,10 @@ class NetHandle(Handle):
 
 
 class WaveformNet:
-    """Base of ``Wav2Vec2CTC`` and ``WavLMXVector``: one network of the family in eval mode on one MI355X, fp32.  A subclass names
-    its symbols (``_prefix``), its config (``_config_name``, ``_c_config``), what its workspace refuses (``_no_workspace``) and the
-    checkpoint keys it never reads (``_ignored``); ``_handle`` is its handle class where its workspace takes other arguments."""
+    """Base of ``Wav2Vec2CTC``, ``WavLMXVector``, ``UTMOS`` and ``Whisper``: one network in eval mode on one MI355X, fp32.  A subclass
+    names its symbols (``_prefix``), its config (``_config_name``, ``_c_config``), what its workspace refuses (``_no_workspace``),
+    the checkpoint keys it never reads (``_ignored``) and, where its calls take wavs, the module's ``check_lengths``
+    (``_check_lengths``); ``_handle`` is its handle class where its workspace takes other arguments."""
     _prefix = _config_name = _no_workspace = ""
     _handle = NetHandle
 
@@ -146,6 +194,29 @@ class WaveformNet:
         self._need_weights(what)
         x, ln, one = device_rows(wav, lengths, what, refuse=ValueError)
         return x.to(self.device), ln, one
+
+    def _inputs(self, wav, lengths, what: str):
+        """``_rows`` and the frames of the padded batch, once the module's ``check_lengths`` has passed the lengths."""
+        x, ln, one = self._rows(wav, lengths, what)
+        return x, ln, one, self._check_lengths(ln, x.shape[1], self.config, what)
+
+    def _hidden(self, wav, lengths) -> torch.Tensor:
+        """The body of a subclass's ``hidden_states``: [B, n] (or [n]) -> ``<prefix>_hidden``'s [B, T, hidden] (or [T, hidden])."""
+        x, ln, one, T = self._inputs(wav, lengths, f"{type(self).__name__}.hidden_states")
+        out = torch.empty(x.shape[0], T, self.config.hidden_size, dtype=torch.float32, device=self.device)
+        return self._run("hidden", x, ln, out, int(self.do_normalize), out.data_ptr(), one=one)
+
+    @classmethod
+    def _model(cls, model, what: str):
+        if not isinstance(model, cls):
+            raise ValueError(f"{what}: pass model={cls.__name__}(...) with the checkpoint's weights loaded (the library ships none)")
+        return model
+
+    def _utterances(self, wavs, lengths, sr, what: str):
+        """``wavs`` [B, n] with ``lengths``, or a list of wavs, at ``sr`` Hz -> (wavs, lengths) at 16 kHz."""
+        if isinstance(wavs, torch.Tensor) and wavs.dim() != 2:
+            raise ValueError(f"{what}: expected wavs [B, n] or a list, got {tuple(wavs.shape)}")
+        return self._at_16k(wavs, lengths, sr, what)
 
     def _run(self, name: str, x, ln, out, *args, one: bool = False):
         """The body of a network call ``<prefix>_<name>(h, x, lengths, B, n, *args, workspace, bytes, stream)`` -> ``out``."""

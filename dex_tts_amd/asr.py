@@ -29,9 +29,8 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
 from ._native import device_rows, host_lengths, i32_ptr, on_device, per_device, stream
-from ._wavnet import MAX_CONV, SAMPLING_RATE, NetHandle, WaveformNet, fill_trunk_config
+from ._wavnet import MAX_CONV, SAMPLING_RATE, HostEntry, NetHandle, WaveformNet, fill_trunk_config
 
 VOCAB = ("<pad>", "<s>", "</s>", "<unk>", "|", "E", "T", "A", "O", "N", "I", "H", "S", "R", "D", "L", "U", "M", "W", "C", "F", "G", "Y", "P",
          "B", "V", "K", "'", "X", "J", "Q", "Z")
@@ -74,14 +73,21 @@ def _c_config(cfg: Wav2Vec2Config) -> DexAsrConfig:
     return c
 
 
+_HOST = HostEntry("dex_asr", _c_config, Wav2Vec2Config, "Wav2Vec2Config")
+
+
 def num_frames(n_samples: int, config: Optional[Wav2Vec2Config] = None) -> int:
     """Frames the feature extractor makes of ``n_samples`` samples: ``floor((L - k) / s) + 1`` chained over its layers, 0 below the
     receptive field (400 samples in the default config).  Host integers."""
-    c = _c_config(config or Wav2Vec2Config())
-    n = int(_lib.load().dex_asr_num_frames(C.byref(c), int(n_samples)))
-    if n < 0:
-        raise ValueError(f"num_frames: bad arguments ({n_samples} samples)")
-    return n
+    return _HOST.num_frames(n_samples, config)
+
+
+def _check_lengths(lengths, n_samples: int, config, what: str) -> int:
+    """``ValueError`` for a row below one frame; the frames of ``n_samples``."""
+    short = [v for v in lengths if num_frames(v, config) < 1]
+    if short:
+        raise ValueError(f"{what}: {short[0]} samples are too short for one frame of the feature extractor")
+    return num_frames(n_samples, config)
 
 
 _NO_WORKSPACE = "too short for one frame, or more than one call takes"
@@ -178,6 +184,7 @@ class Wav2Vec2CTC(WaveformNet):
     _prefix, _config_name, _no_workspace = "dex_asr", "Wav2Vec2Config", _NO_WORKSPACE
     _c_config = staticmethod(_c_config)
     _ignored = staticmethod(lambda key: key == "wav2vec2.masked_spec_embed")
+    _check_lengths = staticmethod(_check_lengths)
 
     def __init__(self, config: Optional[Wav2Vec2Config] = None, device="cuda", vocab: Optional[Sequence[str]] = None):
         super().__init__(config or Wav2Vec2Config(), device)
@@ -185,27 +192,20 @@ class Wav2Vec2CTC(WaveformNet):
         if len(self.vocab) != self.config.vocab_size:
             raise ValueError(f"Wav2Vec2CTC: {len(self.vocab)} symbols for vocab_size {self.config.vocab_size}")
 
-    def _inputs(self, wav, lengths, what: str):
-        x, ln, one = self._rows(wav, lengths, what)
-        short = [v for v in ln if num_frames(v, self.config) < 1]
-        if short:
-            raise ValueError(f"{what}: {short[0]} samples are too short for one frame of the feature extractor")
-        return x, ln, one
-
     def forward(self, input_values: torch.Tensor, lengths=None) -> torch.Tensor:
         """Raw 16 kHz samples [B, n] (or [n]), row b ``lengths[b]`` samples (what is stored past them is not read into any result)
         -> logits [B, T, V] with T = ``num_frames(n)``; row b fills ``num_frames(lengths[b])`` frames and is 0 past them.  The input
         normalisation is part of the call.  A row's logits are bitwise those of the row alone."""
-        x, ln, one = self._inputs(input_values, lengths, "Wav2Vec2CTC.forward")
-        out = torch.empty(x.shape[0], num_frames(x.shape[1], self.config), self.config.vocab_size, dtype=torch.float32, device=self.device)
+        x, ln, one, T = self._inputs(input_values, lengths, "Wav2Vec2CTC.forward")
+        out = torch.empty(x.shape[0], T, self.config.vocab_size, dtype=torch.float32, device=self.device)
         return self._run("logits", x, ln, out, out.data_ptr(), one=one)
 
     __call__ = forward
 
     def transcribe_ids(self, wavs: torch.Tensor, lengths=None):
         """forward + greedy CTC in one stream-ordered sequence -> a list of id lists; one device-to-host copy of ids and counts."""
-        x, ln, _ = self._inputs(wavs, lengths, "Wav2Vec2CTC.transcribe")
-        B, T = x.shape[0], num_frames(x.shape[1], self.config)
+        x, ln, _, T = self._inputs(wavs, lengths, "Wav2Vec2CTC.transcribe")
+        B = x.shape[0]
         buf = torch.empty(B * T + B, dtype=torch.int32, device=self.device)
         return _unpack(self._run("transcribe", x, ln, buf, buf.data_ptr(), buf.data_ptr() + 4 * B * T), B, T)
 

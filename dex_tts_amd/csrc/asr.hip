@@ -24,9 +24,10 @@
 //                        dropped, compacted with a block scan; ids and counts are all that travels to the host.
 // Every per-row sum has a fixed order that does not depend on the batch: a row's logits are bitwise the row run alone.
 // This file holds what is wav2vec 2.0's own: the first convolution with its LayerNorm, the CTC kernel, the checks of the layer-norm
-// family, lm_head and the pre-norm layer loop.  The trunk it shares with the WavLM x-vector network (wavlm.hip) is elsewhere:
-// asr_norm / plan / ln / wn_scale / pack / ksum and the launch_igemm wrappers in wav_encoder.h; geometry, key inventory, packing,
-// workspace prefix, the enqueue steps around the layer loop and the boilerplate entry points in wav_trunk.h.
+// family and lm_head.  What it shares with the other waveform networks (wavlm.hip, mos.hip, whisper.hip) is elsewhere: asr_norm /
+// plan / ln / wn_scale / pack / ksum and the launch_igemm wrappers in wav_encoder.h; geometry, key inventory, packing, workspace
+// prefix, the enqueue steps, the encoder layer (instantiated pre-norm here, with the plain attention) and the entry points with the
+// skeleton of a call in wav_trunk.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -38,7 +39,7 @@
 #include "wav_trunk.h"
 #include "weight_store.h"
 
-using namespace dex::wavenc;      // the trunk shared with wavlm.hip
+using namespace dex::wavenc;
 
 namespace {
 
@@ -181,11 +182,9 @@ const TrunkKeys KEYS("wav2vec2.");
 
 }  // namespace
 
-struct DexAsr : dex::WeightStore {
-    DexAsr() : WeightStore("wav2vec2 ") {}
+struct DexAsr : TrunkStore {
+    DexAsr() : TrunkStore("wav2vec2 ", "dex_asr") {}
     DexAsrConfig c;
-    Trunk t;
-    TrunkWeights w;
     const float *lm_w = nullptr, *lm_b = nullptr;
 };
 
@@ -193,6 +192,7 @@ namespace {
 
 void register_keys(DexAsr* s) {
     s->t = trunk_of(s->c);
+    s->rule = WavRule{samples_for(s->t, 1), "too short for one frame of the feature extractor", MAX_SAMPLES, 0};      // a row needs one frame
     register_trunk_keys(s, KEYS, s->t, true, [](int) {});
     s->add("lm_head.weight", {s->c.vocab, s->c.hidden}); s->add("lm_head.bias", {s->c.vocab});
 }
@@ -220,12 +220,6 @@ Ws plan(const DexAsr* s, void* ws, long B, long n) {
     return w;
 }
 
-// a row needs one frame of the feature extractor
-int check_wavs(DexAsr* s, const void* wav, const int32_t* lengths_host, int B, int n_samples, int* T) {
-    const WavRule r{samples_for(s->t, 1), "too short for one frame of the feature extractor", MAX_SAMPLES, 0};
-    return dex::wavenc::check_wavs(s, s->t, r, wav, lengths_host, B, n_samples, T);
-}
-
 int enqueue_network(DexAsr* s, const float* wav, const int32_t* lengths_host, int B, int n, float* logits, const Ws& w, hipStream_t st) {
     const Trunk& c = s->t;
     const TrunkWeights& W = s->w;
@@ -239,23 +233,9 @@ int enqueue_network(DexAsr* s, const float* wav, const int32_t* lengths_host, in
     enqueue_projection(c, W, w, enqueue_conv_tail<true>(c, W, w, B, 0, st), B, st);
     // h = y + GELU(pos_conv(y)) without its last frame
     gemm(w.y, H, T, H / c.pos_groups, c.pos_k, 1, -(c.pos_k / 2), T, W.pos_w, H / c.pos_groups, c.pos_groups, W.pos_b, w.h, 1, w.y, nullptr, B, st);
-    const long rows = (long)B * T;
     const int* kv_len = w.lens + (long)c.n_conv * B;
-    for (const TrunkWeights::Layer& L : W.layers) {                                     // pre-norm: h += attn(LN(h)); h += ffn(LN(h))
-        layer_norm<false>(w.h, w.y, rows, T, H, L.ln1g, L.ln1b, c.layer_norm_eps, nullptr, st);
-        linear(w.y, H, L.wqkv, 3 * H, L.bqkv, w.qkv, 0, nullptr, nullptr, T, B, st);
-        dex::AttnP a{};
-        a.Q = w.qkv; a.ldq = 3 * H; a.qb = (long)T * 3 * H;
-        a.K = w.qkv + H; a.ldk = 3 * H; a.kb = a.qb;
-        a.V = w.qkv + 2 * H; a.ldv = 3 * H; a.vb = a.qb;
-        a.O = w.y; a.ldo = H; a.ob = (long)T * H;
-        a.Nq = T; a.Nk = T; a.kv_len = kv_len; a.kv_len_add = 0; a.heads = c.n_heads; a.scale = 0.125f; a.B = B; a.head_dim = 64;
-        dex::launch_attention(a, dex::PREC_FP32, st);
-        linear(w.y, H, L.wo, H, L.bo, w.h, 0, w.h, nullptr, T, B, st);                  // h += out_proj(attn)
-        layer_norm<false>(w.h, w.y, rows, T, H, L.ln2g, L.ln2b, c.layer_norm_eps, nullptr, st);
-        enqueue_ffn(c, L, w, w.y, B, st);
-    }
-    layer_norm<false>(w.h, w.y, rows, T, H, W.enc_g, W.enc_be, c.layer_norm_eps, nullptr, st);
+    for (const TrunkWeights::Layer& L : W.layers) enqueue_plain_layer<true>(layer_dims(c), L, w, kv_len, B, st);      // pre-norm
+    layer_norm<false>(w.h, w.y, (long)B * T, T, H, W.enc_g, W.enc_be, c.layer_norm_eps, nullptr, st);
     linear(w.y, H, s->lm_w, s->c.vocab, s->lm_b, logits, 0, nullptr, w.mask, T, B, st);
     return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
 }
@@ -263,13 +243,8 @@ int enqueue_network(DexAsr* s, const float* wav, const int32_t* lengths_host, in
 // frames_host, or (null) the frame counts of the lengths under trunk c
 int enqueue_ctc(const float* logits, const int32_t* frames_host, const int* lengths_host, const Trunk* c, int B, int T, int V, int32_t* ids,
                 int32_t* counts, hipStream_t st) {
-    for (int r0 = 0; r0 < B; r0 += TAB) {
-        Tab R;
-        std::memset(&R, 0, sizeof R);
-        R.n = B - r0 < TAB ? B - r0 : TAB;
-        for (int e = 0; e < R.n; ++e) R.a[e] = frames_host ? frames_host[r0 + e] : frames_of(*c, lengths_host[r0 + e], c->n_conv);
-        hipLaunchKernelGGL(asr_ctc_kernel, dim3(R.n), dim3(256), 0, st, logits, T, V, ids, counts, r0, R);
-    }
+    for_each_row_table<Tab>(B, [&](Tab& R, int e, int b) { R.a[e] = frames_host ? frames_host[b] : frames_of(*c, lengths_host[b], c->n_conv); },
+                            [&](int r0, const Tab& R) { hipLaunchKernelGGL(asr_ctc_kernel, dim3(R.n), dim3(256), 0, st, logits, T, V, ids, counts, r0, R); });
     return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
 }
 
@@ -289,17 +264,8 @@ int dex_asr_finalize(DexAsr* s, dex_stream_t stream) { return E::finalize(s, str
 int dex_asr_num_weights(const DexAsr* s) { return E::num_weights(s); }
 int dex_asr_weight_info(const DexAsr* s, int i, const char** key, int64_t shape[4], int* ndim) { return E::weight_info(s, i, key, shape, ndim); }
 
-int dex_asr_num_frames(const DexAsrConfig* cfg, int n_samples) {
-    const Trunk t = trunk_of(cfg ? *cfg : default_config());
-    if (n_samples < 0 || !conv_geometry_ok(t)) return DEX_ERR_ARG;
-    return frames_of(t, n_samples, t.n_conv);
-}
-
-size_t dex_asr_workspace_bytes(const DexAsr* s, int B, int max_samples) {
-    if (!s || B < 1 || B > MAX_B || max_samples < 1 || max_samples > MAX_SAMPLES) return 0;
-    if (frames_of(s->t, max_samples, s->t.n_conv) < 1 || (long)B * frames_of(s->t, max_samples, 1) > MAX_ROWS) return 0;
-    return plan(s, nullptr, B, max_samples).bytes;
-}
+int dex_asr_num_frames(const DexAsrConfig* cfg, int n_samples) { return E::num_frames(cfg, n_samples, default_config, conv_ok<DexAsrConfig>); }
+size_t dex_asr_workspace_bytes(const DexAsr* s, int B, int max_samples) { return E::workspace_bytes(s, B, max_samples, plan); }
 
 int dex_asr_normalize(DexAsr* s, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, float* out_dev, dex_stream_t stream) {
     if (!s) return DEX_ERR_ARG;
@@ -314,28 +280,17 @@ int dex_asr_normalize(DexAsr* s, const float* wav_dev, const int32_t* lengths_ho
 int dex_asr_logits(DexAsr* s, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, float* logits_dev, void* workspace_dev,
                    size_t workspace_bytes, dex_stream_t stream) {
     if (!s) return DEX_ERR_ARG;
-    int T = 0;
-    if (int rc = check_wavs(s, wav_dev, lengths_host, B, n_samples, &T)) return rc;
-    if (!logits_dev || !workspace_dev) return s->fail(DEX_ERR_ARG, "null pointer argument");
-    if (!s->finalized) return s->fail(DEX_ERR_STATE, "the wav2vec2 weights are not finalized (dex_asr_finalize)");
-    const Ws w = plan(s, workspace_dev, B, n_samples);
-    if (workspace_bytes < w.bytes) return s->fail(DEX_ERR_WORKSPACE, "workspace too small (dex_asr_workspace_bytes)");
-    const int rc = enqueue_network(s, wav_dev, lengths_host, B, n_samples, logits_dev, w, (hipStream_t)stream);
-    return rc ? s->fail(rc, "kernel launch failed") : DEX_OK;
+    return E::call(s, wav_dev, lengths_host, B, n_samples, logits_dev != nullptr, workspace_dev, workspace_bytes, plan, no_further_check,
+                   [&](const Ws& w, int) { return enqueue_network(s, wav_dev, lengths_host, B, n_samples, logits_dev, w, (hipStream_t)stream); });
 }
 
 int dex_asr_transcribe(DexAsr* s, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, int32_t* ids_dev, int32_t* counts_dev,
                        void* workspace_dev, size_t workspace_bytes, dex_stream_t stream) {
     if (!s) return DEX_ERR_ARG;
-    int T = 0;
-    if (int rc = check_wavs(s, wav_dev, lengths_host, B, n_samples, &T)) return rc;
-    if (!ids_dev || !counts_dev || !workspace_dev) return s->fail(DEX_ERR_ARG, "null pointer argument");
-    if (!s->finalized) return s->fail(DEX_ERR_STATE, "the wav2vec2 weights are not finalized (dex_asr_finalize)");
-    const Ws w = plan(s, workspace_dev, B, n_samples);
-    if (workspace_bytes < w.bytes) return s->fail(DEX_ERR_WORKSPACE, "workspace too small (dex_asr_workspace_bytes)");
-    int rc = enqueue_network(s, wav_dev, lengths_host, B, n_samples, w.logits, w, (hipStream_t)stream);
-    if (rc == DEX_OK) rc = enqueue_ctc(w.logits, nullptr, lengths_host, &s->t, B, T, s->c.vocab, ids_dev, counts_dev, (hipStream_t)stream);
-    return rc ? s->fail(rc, "kernel launch failed") : DEX_OK;
+    return E::call(s, wav_dev, lengths_host, B, n_samples, ids_dev && counts_dev, workspace_dev, workspace_bytes, plan, no_further_check, [&](const Ws& w, int T) {
+        const int rc = enqueue_network(s, wav_dev, lengths_host, B, n_samples, w.logits, w, (hipStream_t)stream);
+        return rc ? rc : enqueue_ctc(w.logits, nullptr, lengths_host, &s->t, B, T, s->c.vocab, ids_dev, counts_dev, (hipStream_t)stream);
+    });
 }
 
 int dex_asr_ctc(DexAsr* s, const float* logits_dev, const int32_t* frames_host, int B, int T, int V, int32_t* ids_dev, int32_t* counts_dev,

@@ -4,9 +4,9 @@
 // Linear - ReLU - Linear per frame, mean over the frames x 2 + 3.  fp32 throughout, channels-last [B][T][C].  C ABI dex_mos_*.
 // Row b of a batch is the network applied to row b alone at its own length.
 //
-//   the trunk              composed from wav_trunk.h / wav_groupnorm.h: the raw first convolution and its group norm, the GELU
-//                          convolutions, the feature projection, the padded positional convolution, then per layer
-//                          h = LN(h + attn(h)); h = LN(h + ffn(h)) with dex::launch_attention (PREC_FP32, keys ending at the row's frames).
+//   the trunk              composed from wav_groupnorm.h / wav_trunk.h: the group-norm front end (enqueue_groupnorm_front), then the
+//                          shared encoder layer in its post-norm order, h = LN(h + attn(h)); h = LN(h + ffn(h)), with the plain
+//                          attention (dex::launch_attention, PREC_FP32, keys ending at the row's frames).
 //   mos_cond_kernel        the embeddings are constant over time, so [T][hidden + domain_dim + judge_dim] is never built: once per call
 //                          cbias[b][2 x 4H] = ((b_ih + b_hh) + dom[domain_b] . W_ih[:, hidden : hidden + dd]^T) + judge[judge_b] . W_ih[:, hidden + dd :]^T,
 //                          two fmaf chains, k ascending.
@@ -25,6 +25,8 @@
 //   the projection         two launches of the implicit GEMM (ReLU in the epilogue of the first; the second's single column padded to 32).
 //   mos_mean_kernel        frames[b][t] = the score of frame t (0 past the row's frames); score[b] = mean x 2 + 3, the sum in fp64 in a
 //                          fixed order (256 strided partials, an LDS tree).
+// This file holds what is UTMOS's own: the head and its kernels.  Geometry, keys, packing, workspace prefix, the layer and the
+// entry points with the skeleton of a call are wav_trunk.h's.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -257,17 +259,17 @@ int check_config(const DexMosConfig& c) {
     return DEX_OK;
 }
 
+long min_samples(const DexMosConfig& c) { return samples_for(trunk_of(c), 1); }      // one encoder frame
+
 const TrunkKeys KEYS("wav2vec2.");
 const char* const DIRS[2] = {"", "_reverse"};
 std::string rk(const char* what, int d) { return std::string("decoder_rnn.") + what + "_l0" + DIRS[d]; }
 
 }  // namespace
 
-struct DexMos : dex::WeightStore {
-    DexMos() : WeightStore("utmos ") {}
+struct DexMos : TrunkStore {
+    DexMos() : TrunkStore("utmos ", "dex_mos") {}
     DexMosConfig c;
-    Trunk t;
-    TrunkWeights w;
     const float *dom = nullptr, *judge = nullptr;
     const float *wih = nullptr, *wcond = nullptr, *bias = nullptr;       // [hidden][2 G], [dd + jd][2 G], [2 G] = b_ih + b_hh
     const float4* whh = nullptr;                                          // [2][H / 4][G]
@@ -279,6 +281,8 @@ namespace {
 void register_keys(DexMos* s) {
     const DexMosConfig& c = s->c;
     s->t = trunk_of(c);
+    s->why = "too short for one frame of the feature extractor (" + std::to_string(min_samples(c)) + " samples)";
+    s->rule = WavRule{min_samples(c), s->why.c_str(), 0, MAXF};
     register_trunk_keys(s, KEYS, s->t, false, [](int) {});
     const int H = c.lstm_hidden, in = c.hidden + c.domain_dim + c.judge_dim;
     s->add("domain_embedding.weight", {c.num_domains, c.domain_dim});
@@ -363,29 +367,11 @@ BiWs plan_bilstm(const DexMos* s, void* ws, long B, long T) {
 int enqueue_trunk(DexMos* s, const float* wav, const int32_t* lengths_host, int B, int n, int do_normalize, float* hidden, const Ws& w, hipStream_t st) {
     const Trunk& t = s->t;
     const TrunkWeights& W = s->w;
-    const int T = w.T, H = t.hidden;
-    enqueue_front(t, w, wav, lengths_host, B, n, do_normalize, st);
-    enqueue_conv0_groupnorm(t, W, w, w, do_normalize ? w.xn : wav, B, n, st);
-    enqueue_projection(t, W, w, enqueue_conv_tail<false>(t, W, w, B, 1, st), B, st);
-    const long rows = (long)B * T;
-    enqueue_pos_padded(t, W, w, w, B, st);                                              // h = LN(y + GELU(pos_conv(y)) without its last frame)
-    layer_norm<false>(w.h, w.h, rows, T, H, W.enc_g, W.enc_be, t.layer_norm_eps, nullptr, st);
+    const int H = t.hidden;
+    enqueue_groupnorm_front(t, W, w, w, w, wav, lengths_host, B, n, do_normalize, st);
     const int* kv_len = w.lens + (long)t.n_conv * B;
-    for (const TrunkWeights::Layer& L : W.layers) {                                     // post-norm: h = LN(h + attn(h)); h = LN(h + ffn(h))
-        linear(w.h, H, L.wqkv, 3 * H, L.bqkv, w.qkv, 0, nullptr, nullptr, T, B, st);
-        dex::AttnP a{};
-        a.Q = w.qkv; a.ldq = 3 * H; a.qb = (long)T * 3 * H;
-        a.K = w.qkv + H; a.ldk = 3 * H; a.kb = a.qb;
-        a.V = w.qkv + 2 * H; a.ldv = 3 * H; a.vb = a.qb;
-        a.O = w.y; a.ldo = H; a.ob = (long)T * H;
-        a.Nq = T; a.Nk = T; a.kv_len = kv_len; a.kv_len_add = 0; a.heads = t.n_heads; a.scale = 0.125f; a.B = B; a.head_dim = 64;
-        dex::launch_attention(a, dex::PREC_FP32, st);
-        linear(w.y, H, L.wo, H, L.bo, w.h, 0, w.h, nullptr, T, B, st);                  // h += out_proj(attn)
-        layer_norm<false>(w.h, w.h, rows, T, H, L.ln1g, L.ln1b, t.layer_norm_eps, nullptr, st);
-        enqueue_ffn(t, L, w, w.h, B, st);
-        layer_norm<false>(w.h, w.h, rows, T, H, L.ln2g, L.ln2b, t.layer_norm_eps, nullptr, st);
-    }
-    const long n4 = rows * H / 4;
+    for (const TrunkWeights::Layer& L : W.layers) enqueue_plain_layer<false>(layer_dims(t), L, w, kv_len, B, st);      // post-norm
+    const long n4 = (long)B * w.T * H / 4;
     hipLaunchKernelGGL(mos_mask_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, (const float4*)w.h, w.mask, (float4*)hidden, n4, H / 4);
     return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
 }
@@ -395,14 +381,11 @@ int enqueue_bilstm(DexMos* s, const float* feat, const int32_t* frames_host, con
                    float* out, const HeadWs& w, hipStream_t st) {
     const DexMosConfig& c = s->c;
     const int H = c.lstm_hidden, G = 4 * H, N = 2 * G;
-    for (int r0 = 0; r0 < B; r0 += TAB) {
-        RowTab R;
-        std::memset(&R, 0, sizeof R);
-        R.n = B - r0 < TAB ? B - r0 : TAB;
-        for (int e = 0; e < R.n; ++e) { R.dom[e] = domain_host[r0 + e]; R.judge[e] = judge_host[r0 + e]; R.frames[e] = frames_host[r0 + e]; }
+    for_each_row_table<RowTab>(B, [&](RowTab& R, int e, int b) { R.dom[e] = domain_host[b]; R.judge[e] = judge_host[b]; R.frames[e] = frames_host[b]; },
+                               [&](int r0, const RowTab& R) {
         hipLaunchKernelGGL(mos_cond_kernel, dim3(R.n, (N + 255) / 256), dim3(256), 0, st, s->dom, s->judge, s->wcond, s->bias, w.cbias, w.flens,
                            c.domain_dim, c.judge_dim, N, r0, R);
-    }
+    });
     {   // gi = feat W_ih[:, : hidden]^T + cbias[b]: the GEMM of wav_encoder.h's linear() with a per-row bias
         dex::IGemmP g{};
         g.A = feat; g.lda = c.hidden; g.a_bstride = (long)T * c.hidden;
@@ -444,34 +427,25 @@ int check_ids(DexMos* s, const int32_t* domain_host, const int32_t* judge_host, 
     return DEX_OK;
 }
 
-long min_samples(const DexMosConfig& c) { return samples_for(trunk_of(c), 1); }
+typedef Entry<DexMos> E;
 
 // hidden_dev, frames_dev, score_dev: whichever is asked for (the ids are read only where the head runs)
 int run(DexMos* s, const float* wav_dev, const int32_t* lengths_host, const int32_t* domain_host, const int32_t* judge_host, int B, int n_samples,
         int do_normalize, float* hidden_dev, float* frames_dev, float* score_dev, void* workspace_dev, size_t workspace_bytes, hipStream_t st) {
-    int T = 0;
-    const long need = min_samples(s->c);
-    const std::string why = "too short for one frame of the feature extractor (" + std::to_string(need) + " samples)";
-    if (int rc = check_wavs(s, s->t, WavRule{need, why.c_str(), 0, MAXF}, wav_dev, lengths_host, B, n_samples, &T)) return rc;
     const bool head = frames_dev || score_dev;
-    if ((!hidden_dev && !head) || !workspace_dev) return s->fail(DEX_ERR_ARG, "null pointer argument");
-    if (head)
-        if (int rc = check_ids(s, domain_host, judge_host, B)) return rc;
-    if (!s->finalized) return s->fail(DEX_ERR_STATE, "the utmos weights are not finalized (dex_mos_finalize)");
-    const Ws w = plan(s, workspace_dev, B, n_samples);
-    if (workspace_bytes < w.bytes) return s->fail(DEX_ERR_WORKSPACE, "workspace too small (dex_mos_workspace_bytes)");
-    float* hidden = hidden_dev ? hidden_dev : w.hid;
-    int rc = enqueue_trunk(s, wav_dev, lengths_host, B, n_samples, do_normalize, hidden, w, st);
-    if (rc == DEX_OK && head) {
-        std::vector<int32_t> frames(B);
-        for (int b = 0; b < B; ++b) frames[b] = frames_of(s->t, lengths_host[b], s->t.n_conv);
-        rc = enqueue_bilstm(s, hidden, frames.data(), domain_host, judge_host, B, T, w.lo, w, st);
-        if (rc == DEX_OK) rc = enqueue_projection_head(s, B, T, frames_dev, score_dev, w, st);
-    }
-    return rc ? s->fail(rc, "kernel launch failed") : DEX_OK;
+    return E::call(s, wav_dev, lengths_host, B, n_samples, hidden_dev || head, workspace_dev, workspace_bytes, plan,
+                   [&] { return head ? check_ids(s, domain_host, judge_host, B) : DEX_OK; }, [&](const Ws& w, int T) {
+        float* hidden = hidden_dev ? hidden_dev : w.hid;
+        int rc = enqueue_trunk(s, wav_dev, lengths_host, B, n_samples, do_normalize, hidden, w, st);
+        if (rc == DEX_OK && head) {
+            std::vector<int32_t> frames(B);
+            for (int b = 0; b < B; ++b) frames[b] = frames_of(s->t, lengths_host[b], s->t.n_conv);
+            rc = enqueue_bilstm(s, hidden, frames.data(), domain_host, judge_host, B, T, w.lo, w, st);
+            if (rc == DEX_OK) rc = enqueue_projection_head(s, B, T, frames_dev, score_dev, w, st);
+        }
+        return rc;
+    });
 }
-
-typedef Entry<DexMos> E;
 
 }  // namespace
 
@@ -487,24 +461,9 @@ int dex_mos_finalize(DexMos* s, dex_stream_t stream) { return E::finalize(s, str
 int dex_mos_num_weights(const DexMos* s) { return E::num_weights(s); }
 int dex_mos_weight_info(const DexMos* s, int i, const char** key, int64_t shape[4], int* ndim) { return E::weight_info(s, i, key, shape, ndim); }
 
-int dex_mos_num_frames(const DexMosConfig* cfg, int n_samples) {
-    const Trunk t = trunk_of(cfg ? *cfg : default_config());
-    if (n_samples < 0 || !conv_geometry_ok(t)) return DEX_ERR_ARG;
-    return frames_of(t, n_samples, t.n_conv);
-}
-
-int dex_mos_min_samples(const DexMosConfig* cfg) {
-    const DexMosConfig c = cfg ? *cfg : default_config();
-    if (!conv_geometry_ok(trunk_of(c))) return DEX_ERR_ARG;
-    const long n = min_samples(c);
-    return n > 0x7fffffffL ? DEX_ERR_ARG : (int)n;
-}
-
-size_t dex_mos_workspace_bytes(const DexMos* s, int B, int max_samples) {
-    if (!s || B < 1 || B > MAX_B || max_samples < min_samples(s->c)) return 0;
-    if (frames_of(s->t, max_samples, s->t.n_conv) > MAXF || (long)B * frames_of(s->t, max_samples, 1) > MAX_ROWS) return 0;
-    return plan(s, nullptr, B, max_samples).bytes;
-}
+int dex_mos_num_frames(const DexMosConfig* cfg, int n_samples) { return E::num_frames(cfg, n_samples, default_config, conv_ok<DexMosConfig>); }
+int dex_mos_min_samples(const DexMosConfig* cfg) { return E::min_samples(cfg, default_config, conv_ok<DexMosConfig>, min_samples); }
+size_t dex_mos_workspace_bytes(const DexMos* s, int B, int max_samples) { return E::workspace_bytes(s, B, max_samples, plan); }
 
 size_t dex_mos_bilstm_workspace_bytes(const DexMos* s, int B, int T) {
     if (!s || B < 1 || B > MAX_B || T < 1 || T > MAXF) return 0;

@@ -1,9 +1,9 @@
-// wav_encoder.h — the kernels the two waveform transformers of the C ABI share (asr.hip: wav2vec 2.0 CTC; wavlm.hip: WavLM x-vector)
-// and their launches: the input normalisation, the ragged-batch plan, row LayerNorm, the weight packing (weight norm folded in fp64),
-// the k-split sum of fc2, and the host wrappers that spell a 1 x k convolution / Linear as a launch of the exact-fp32 implicit GEMM.
-// Every per-row sum has a fixed order that does not depend on the batch.  The host layer of the trunk the two networks share
-// (geometry, keys, packing, workspace, enqueue steps, entry points) is wav_trunk.h, which includes this file; everything has
-// internal linkage.
+// wav_encoder.h — the kernels the waveform networks of the C ABI share (asr.hip: wav2vec 2.0 CTC; wavlm.hip: WavLM x-vector; mos.hip:
+// UTMOS; whisper.hip: the Whisper encoder) and their launches: the input normalisation, the ragged-batch plan, row LayerNorm, the
+// weight packing (weight norm folded in fp64), the k-split sum of fc2, the host wrappers that spell a 1 x k convolution / Linear as
+// a launch of the exact-fp32 implicit GEMM, and the walk over a batch in tables of rows that travel as kernel arguments.  Every
+// per-row sum has a fixed order that does not depend on the batch.  The host layer above them (geometry, keys, packing, workspace,
+// the encoder layer, entry points) is wav_trunk.h, which includes this file; everything has internal linkage.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -194,25 +194,29 @@ void layer_norm(const float* X, float* Y, long rows, int T, int C, const float* 
     hipLaunchKernelGGL(asr_ln_kernel<GELU>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, p);
 }
 
-void enqueue_norm(const float* wav, const int32_t* lengths_host, int B, int n, float* out, hipStream_t st) {
+// the batch in tables of TAB rows: fill(R, e, b) sets entry e of a zeroed table to row b = r0 + e, launch(r0, R) takes the R.n rows
+template <class T, class Fill, class Launch>
+void for_each_row_table(int B, Fill fill, Launch launch) {
     for (int r0 = 0; r0 < B; r0 += TAB) {
-        Tab R;
+        T R;
         std::memset(&R, 0, sizeof R);
         R.n = B - r0 < TAB ? B - r0 : TAB;
-        for (int e = 0; e < R.n; ++e) R.a[e] = lengths_host[r0 + e];
-        hipLaunchKernelGGL(asr_norm_kernel, dim3(R.n), dim3(NORM_T), 0, st, wav, out, (long)n, r0, R);
+        for (int e = 0; e < R.n; ++e) fill(R, e, r0 + e);
+        launch(r0, R);
     }
 }
 
-// the per-layer frame counts of rows r0 .. of the batch, and the encoder's frame mask (asr_plan_kernel), TAB rows per launch
+void enqueue_norm(const float* wav, const int32_t* lengths_host, int B, int n, float* out, hipStream_t st) {
+    for_each_row_table<Tab>(B, [&](Tab& R, int e, int b) { R.a[e] = lengths_host[b]; }, [&](int r0, const Tab& R) {
+        hipLaunchKernelGGL(asr_norm_kernel, dim3(R.n), dim3(NORM_T), 0, st, wav, out, (long)n, r0, R);
+    });
+}
+
+// the per-layer frame counts of every row of the batch, and the encoder's frame mask (asr_plan_kernel)
 void enqueue_plan(const ConvSpec& cs, const int32_t* lengths_host, int B, int T, int* lens, float* mask, hipStream_t st) {
-    for (int r0 = 0; r0 < B; r0 += TAB) {
-        Tab R;
-        std::memset(&R, 0, sizeof R);
-        R.n = B - r0 < TAB ? B - r0 : TAB;
-        for (int e = 0; e < R.n; ++e) R.a[e] = lengths_host[r0 + e];
+    for_each_row_table<Tab>(B, [&](Tab& R, int e, int b) { R.a[e] = lengths_host[b]; }, [&](int r0, const Tab& R) {
         hipLaunchKernelGGL(asr_plan_kernel, dim3(R.n), dim3(256), 0, st, lens, mask, B, T, r0, cs, R);
-    }
+    });
 }
 
 }  // namespace

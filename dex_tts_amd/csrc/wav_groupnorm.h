@@ -8,8 +8,8 @@
 //   wavlm_pack_pos_kernel, groups of the positional convolution that are no multiple of 32 channels wide (768 / 16 = 48) are padded to
 //   wavlm_pad_vec_kernel,  64 for the exact-fp32 implicit GEMM (zeros in the padding) and come back onto the residual through
 //   wavlm_unpad_add_kernel wavlm_unpad_add_kernel.
-// with the workspace pieces (GnWs, PosWs) and the enqueue steps around them.  Included after wav_trunk.h; everything has internal
-// linkage.
+// with the workspace pieces (GnWs, PosWs), the enqueue steps around them, and the whole front end of such a network up to its first
+// encoder layer (enqueue_groupnorm_front).  Includes wav_trunk.h; everything has internal linkage.
 #pragma once
 #include "wav_trunk.h"
 
@@ -192,7 +192,7 @@ void enqueue_conv0_groupnorm(const Trunk& c, const TrunkWeights& W, const TrunkW
                        W.conv_be[0], n4);
 }
 
-// h = y + GELU(pos_conv(y)) without its last frame (the LayerNorm that follows is the caller's)
+// h = y + GELU(pos_conv(y)) without its last frame (the LayerNorm that follows is enqueue_groupnorm_front's)
 void enqueue_pos_padded(const Trunk& t, const TrunkWeights& W, const TrunkWs& w, const PosWs& p, int B, hipStream_t st) {
     const int T = w.T, H = t.hidden, G = t.pos_groups, K = t.pos_k, cg = H / G, cgp = pos_group_pad(t);
     const long rows = (long)B * T;
@@ -203,6 +203,17 @@ void enqueue_pos_padded(const Trunk& t, const TrunkWeights& W, const TrunkWs& w,
         gemm(p.yp, G * cgp, T, cgp, K, 1, -(K / 2), T, W.pos_w, cgp, G, W.pos_b, p.pp, 1, nullptr, nullptr, B, st);
         hipLaunchKernelGGL(wavlm_unpad_add_kernel, dim3((unsigned)((rows * H + 255) / 256)), dim3(256), 0, st, w.y, p.pp, w.h, rows, G, cg, cgp);
     }
+}
+
+// everything before the encoder layers of a group-norm network: the frame plan (normalize: and the input normalisation), layer 0
+// with its group norm, the GELU convolutions, the feature projection, and h = LN(y + GELU(pos_conv(y)))
+void enqueue_groupnorm_front(const Trunk& t, const TrunkWeights& W, const TrunkWs& w, const GnWs& g, const PosWs& p, const float* wav,
+                             const int32_t* lengths_host, int B, int n, bool normalize, hipStream_t st) {
+    enqueue_front(t, w, wav, lengths_host, B, n, normalize, st);
+    enqueue_conv0_groupnorm(t, W, w, g, normalize ? w.xn : wav, B, n, st);
+    enqueue_projection(t, W, w, enqueue_conv_tail<false>(t, W, w, B, 1, st), B, st);
+    enqueue_pos_padded(t, W, w, p, B, st);
+    layer_norm<false>(w.h, w.h, (long)B * w.T, w.T, t.hidden, W.enc_g, W.enc_be, t.layer_norm_eps, nullptr, st);
 }
 
 }  // namespace

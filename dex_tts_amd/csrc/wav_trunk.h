@@ -1,11 +1,14 @@
-// wav_trunk.h — the host layer of the wav2vec-family trunk the two waveform transformers share (asr.hip: wav2vec 2.0 CTC; wavlm.hip:
-// WavLM x-vector): a feature extractor of 1 x k convolutions, the feature projection, a grouped weight-normed positional
-// convolution, and N encoder layers of qkv | out_proj | fc1 | k-split fc2.  Here, once: the geometry (Trunk) with its defaults and
-// refusals, the HF key inventory in registration order, the packed weights (TrunkWeights, finalize_trunk), the shared prefix of the
-// workspace (plan_trunk), the enqueue steps a network composes its forward pass from, the argument checks of a call that takes wavs,
-// and the boilerplate entry points (Entry).  What differs stays with the network: its first convolution and its norm, the order of
-// LayerNorm and attention in a layer, the attention itself, and its head.  The kernels are in wav_encoder.h.  Included by those two
-// files, and by whisper.hip for the handle's boilerplate (create_fail, Taker, Entry) only; everything has internal linkage.
+// wav_trunk.h — the host layer of the waveform networks (asr.hip: wav2vec 2.0 CTC; wavlm.hip: WavLM x-vector; mos.hip: UTMOS;
+// whisper.hip: the Whisper encoder).  Three of them run the wav2vec-family trunk: a feature extractor of 1 x k convolutions, the
+// feature projection, a grouped weight-normed positional convolution, and N encoder layers of qkv | out_proj | fc1 | fc2.  Here,
+// once: the trunk's geometry (Trunk) with its defaults and refusals, the HF key inventory in registration order, the packed weights
+// (TrunkWeights, pack_side, finalize_trunk), the shared prefix of the workspace (plan_trunk), the enqueue steps a network composes
+// its forward pass from, the encoder layer in both norm orders (enqueue_layer) with the plain self-attention over a packed q | k | v
+// (enqueue_self_attention), the argument checks of a call that takes wavs, and the entry points (Entry: the boilerplate, the
+// host-only frame counts, and the skeleton of a network call).  What differs stays with the network: its first convolution and its
+// norm, which norm order it instantiates, an attention that is not the plain one (WavLM's gated bias), and its head.  Whisper has no
+// trunk: its encoder takes the layer (LayerDims, LayerWs, TrunkWeights::Layer, pack_side) and the handle's boilerplate.  The kernels
+// are in wav_encoder.h; everything has internal linkage.
 #pragma once
 #include <vector>
 
@@ -96,6 +99,10 @@ int fc2_ksplit(const Trunk& c) {
     return (r * c.hidden == c.intermediate && (r == 2 || r == 4 || r == 8) && (c.intermediate / r) % 32 == 0) ? r : 1;
 }
 
+// what an encoder layer reads of a geometry: the widths, the k-split of fc2 (1: one launch, no `part` buffer), the LayerNorms' eps
+struct LayerDims { int hidden, heads, intermediate, ksplit; float eps; };
+LayerDims layer_dims(const Trunk& c) { return {c.hidden, c.n_heads, c.intermediate, fc2_ksplit(c), c.layer_norm_eps}; }
+
 // frames after the first `upto` convolutions of n samples
 int frames_of(const Trunk& c, long n, int upto) {
     for (int l = 0; l < upto; ++l) n = n >= c.conv_kernel[l] ? (n - c.conv_kernel[l]) / c.conv_stride[l] + 1 : 0;
@@ -164,6 +171,24 @@ struct TrunkWeights {
     std::vector<Layer> layers;
 };
 
+// the [K = d][N = n d] operand of the n projections `p + name` side by side (q | k | v, k | v), and (bias) their biases in one
+// vector with 0 where a projection has none.  Null where an alloc failed
+const float* pack_side(WeightStore* s, const std::string& p, std::initializer_list<const char*> names, int d, hipStream_t st, const float** bias) {
+    const int n = (int)names.size();
+    float* w = s->alloc((long)n * d * d);
+    float* b = bias ? s->alloc((long)n * d) : nullptr;
+    if (!w || (bias && !b)) return nullptr;
+    if (b) hipMemsetAsync(b, 0, (size_t)n * d * sizeof(float), st);
+    int j = 0;
+    for (const char* nm : names) {
+        pack_into(s->R(p + nm + ".weight"), w, 1, d, d, 1, n * d, j * d, nullptr, st);
+        if (b && s->raw.count(p + nm + ".bias")) hipMemcpyAsync(b + (long)j * d, s->R(p + nm + ".bias"), d * sizeof(float), hipMemcpyDeviceToDevice, st);
+        ++j;
+    }
+    if (bias) *bias = b;
+    return w;
+}
+
 // Every weight transposed to the GEMM's [K][N] operand, q | k | v as one; weight_norm(dim = 2) of the positional convolution folded
 // as scale[tap] (fp64), which pack_pos(scale) turns into pos_w / pos_b in the network's own layout.  Norm parameters and biases are
 // read where they were uploaded.
@@ -189,14 +214,7 @@ int finalize_trunk(WeightStore* s, const TrunkKeys& k, const Trunk& c, bool conv
     W.layers.assign(c.n_layers, TrunkWeights::Layer{});
     for (int l = 0; l < c.n_layers && s->alloc_rc == DEX_OK; ++l) {
         TrunkWeights::Layer& L = W.layers[l];
-        float* wqkv = s->alloc(3L * H * H); float* bqkv = s->alloc(3L * H);
-        if (!wqkv || !bqkv) break;
-        const char* pr[3] = {"attention.q_proj", "attention.k_proj", "attention.v_proj"};
-        for (int j = 0; j < 3; ++j) {
-            pack_into(s->R(k.lk(l, pr[j]) + ".weight"), wqkv, 1, H, H, 1, 3 * H, j * H, nullptr, st);
-            DEX_HIPCHK(s, hipMemcpyAsync(bqkv + (long)j * H, s->R(k.lk(l, pr[j]) + ".bias"), H * sizeof(float), hipMemcpyDeviceToDevice, st));
-        }
-        L.wqkv = wqkv; L.bqkv = bqkv;
+        L.wqkv = pack_side(s, k.lk(l, "attention."), {"q_proj", "k_proj", "v_proj"}, H, st, &L.bqkv);
         L.wo = pack(s, k.lk(l, "attention.out_proj") + ".weight", 1, H, H, 1, nullptr, st); L.bo = s->R(k.lk(l, "attention.out_proj") + ".bias");
         L.ln1g = s->R(k.lk(l, "layer_norm.weight")); L.ln1b = s->R(k.lk(l, "layer_norm.bias"));
         L.w1 = pack(s, k.lk(l, "feed_forward.intermediate_dense.weight"), 1, I, H, 1, nullptr, st); L.b1 = s->R(k.lk(l, "feed_forward.intermediate_dense.bias"));
@@ -208,8 +226,10 @@ int finalize_trunk(WeightStore* s, const TrunkKeys& k, const Trunk& c, bool conv
 
 // ---- workspace.  Floats, every piece a multiple of 64.  The trunk's prefix: xn [B][n] | fa [B][T_0][C_0] (even layers) |
 // fb [B][T_1][C_1] (odd layers) | h, y [B][T][H] | qkv [B][T][3H] | ff [B][T][I] | part [ksplit][B][T][H] (fc2's slabs); a network
-// takes its own pieces after it, and mask [B][T] and lens (int) [n_conv + 1][B] among them.
-struct TrunkWs { float *xn, *fa, *fb, *h, *y, *qkv, *ff, *part, *mask; int* lens; int Tl[MAXC]; int T; };
+// takes its own pieces after it, and mask [B][T] and lens (int) [n_conv + 1][B] among them.  LayerWs: what an encoder layer touches,
+// with T the frames of a row (part may be null where fc2 is not split)
+struct LayerWs { float *h, *y, *qkv, *ff, *part; int T; };
+struct TrunkWs : LayerWs { float *xn, *fa, *fb, *mask; int* lens; int Tl[MAXC]; };
 
 struct Taker {
     explicit Taker(void* ws) : f((float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255)) {}
@@ -256,6 +276,23 @@ int check_wavs(WeightStore* s, const Trunk& c, const WavRule& r, const void* wav
     return DEX_OK;
 }
 
+// what the handle of a trunk network holds beside its config S::c.  prefix: of its C symbols ("dex_asr"); rule (with `why`, where
+// the network composes that text) is set when the keys are registered
+struct TrunkStore : WeightStore {
+    TrunkStore(const char* noun, const char* prefix) : WeightStore(noun), prefix(prefix) {}
+    const char* prefix;
+    Trunk t;
+    TrunkWeights w;
+    std::string why;
+    WavRule rule{};
+};
+
+// kernels and strides of a config as conv_geometry_ok sees them
+template <class Cfg>
+bool conv_ok(const Cfg& c) { return conv_geometry_ok(trunk_of(c)); }
+
+inline int no_further_check() { return DEX_OK; }
+
 // ---- the steps a network's forward pass is composed of
 // the per-layer frame counts and the frame mask; normalize: the input normalisation into xn
 void enqueue_front(const Trunk& c, const TrunkWs& w, const float* wav, const int32_t* lengths_host, int B, int n, bool normalize, hipStream_t st) {
@@ -287,18 +324,53 @@ void enqueue_projection(const Trunk& c, const TrunkWeights& W, const TrunkWs& w,
     linear(fpn, C, W.fp_w, c.hidden, W.fp_b, w.y, 0, nullptr, w.mask, w.T, B, st);
 }
 
-// h += fc2(GELU(fc1(x))): fc2 in one launch, or its K in fc2_ksplit slabs that asr_ksum_kernel adds in slab order
-void enqueue_ffn(const Trunk& c, const TrunkWeights::Layer& L, const TrunkWs& w, const float* x, int B, hipStream_t st) {
-    const int T = w.T, H = c.hidden, ks = fc2_ksplit(c);
-    linear(x, H, L.w1, c.intermediate, L.b1, w.ff, 1, nullptr, nullptr, T, B, st);
-    if (ks > 1) {
-        gemm(w.ff, c.intermediate, T, c.intermediate, 1, 1, 0, T, L.w2, H, 1, nullptr, w.part, 0, nullptr, nullptr, B, st, ks);
+// ---- the encoder layer
+// h += fc2(GELU(fc1(x))): fc2 in one launch, or its K in d.ksplit slabs that asr_ksum_kernel adds in slab order
+void enqueue_ffn(const LayerDims& d, const TrunkWeights::Layer& L, const LayerWs& w, const float* x, int B, hipStream_t st) {
+    const int T = w.T, H = d.hidden, I = d.intermediate;
+    linear(x, H, L.w1, I, L.b1, w.ff, 1, nullptr, nullptr, T, B, st);
+    if (d.ksplit > 1) {
+        gemm(w.ff, I, T, I, 1, 1, 0, T, L.w2, H, 1, nullptr, w.part, 0, nullptr, nullptr, B, st, d.ksplit);
         const long n4 = (long)B * T * H / 4;
-        hipLaunchKernelGGL(asr_ksum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, (const float4*)w.part, n4, ks, (const float4*)L.b2,
-                           H / 4, (float4*)w.h);
+        hipLaunchKernelGGL(asr_ksum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, (const float4*)w.part, n4, d.ksplit,
+                           (const float4*)L.b2, H / 4, (float4*)w.h);
     } else {
-        linear(w.ff, c.intermediate, L.w2, H, L.b2, w.h, 0, w.h, nullptr, T, B, st);
+        linear(w.ff, I, L.w2, H, L.b2, w.h, 0, w.h, nullptr, T, B, st);
     }
+}
+
+// out [B][T][H] = softmax((q / 8) k^T) v per head of 64 over the packed qkv [B][T][3 H] (attention.hip's generic fp32 kernel); the
+// keys of row b end at kv_len[b] (null: all T)
+void enqueue_self_attention(const float* qkv, float* out, int T, int H, int heads, const int* kv_len, int B, hipStream_t st) {
+    dex::AttnP a{};
+    a.Q = qkv; a.ldq = 3 * H; a.qb = (long)T * 3 * H;
+    a.K = qkv + H; a.ldk = 3 * H; a.kb = a.qb;
+    a.V = qkv + 2 * H; a.ldv = 3 * H; a.vb = a.qb;
+    a.O = out; a.ldo = H; a.ob = (long)T * H;
+    a.Nq = T; a.Nk = T; a.kv_len = kv_len; a.kv_len_add = 0; a.heads = heads; a.scale = 0.125f; a.B = B; a.head_dim = 64;
+    dex::launch_attention(a, dex::PREC_FP32, st);
+}
+
+// One layer on h.  attn(qkv, out) enqueues the attention over the packed q | k | v; it may read h, which still holds the layer's input.
+//   PRE_NORM:  y = LN1(h); qkv = y Wqkv; y = attn; h += y Wo; y = LN2(h); h += ffn(y)
+//   post-norm: qkv = h Wqkv; y = attn; h += y Wo; h = LN1(h); h += ffn(h); h = LN2(h)
+template <bool PRE_NORM, class Attn>
+void enqueue_layer(const LayerDims& d, const TrunkWeights::Layer& L, const LayerWs& w, int B, Attn attn, hipStream_t st) {
+    const int T = w.T, H = d.hidden;
+    const long rows = (long)B * T;
+    float* x = PRE_NORM ? w.y : w.h;                      // what the GEMMs read: the normed copy, or h normed in place
+    if (PRE_NORM) layer_norm<false>(w.h, x, rows, T, H, L.ln1g, L.ln1b, d.eps, nullptr, st);
+    linear(x, H, L.wqkv, 3 * H, L.bqkv, w.qkv, 0, nullptr, nullptr, T, B, st);
+    attn(w.qkv, w.y);
+    linear(w.y, H, L.wo, H, L.bo, w.h, 0, w.h, nullptr, T, B, st);
+    layer_norm<false>(w.h, x, rows, T, H, PRE_NORM ? L.ln2g : L.ln1g, PRE_NORM ? L.ln2b : L.ln1b, d.eps, nullptr, st);
+    enqueue_ffn(d, L, w, x, B, st);
+    if (!PRE_NORM) layer_norm<false>(w.h, w.h, rows, T, H, L.ln2g, L.ln2b, d.eps, nullptr, st);
+}
+// the layer with the plain attention
+template <bool PRE_NORM>
+void enqueue_plain_layer(const LayerDims& d, const TrunkWeights::Layer& L, const LayerWs& w, const int* kv_len, int B, hipStream_t st) {
+    enqueue_layer<PRE_NORM>(d, L, w, B, [&](const float* qkv, float* out) { enqueue_self_attention(qkv, out, w.T, d.hidden, d.heads, kv_len, B, st); }, st);
 }
 
 // ---- the entry points every handle of the family has: S derives from WeightStore and holds its config as S::c
@@ -339,6 +411,45 @@ struct Entry {
     }
     static int num_weights(const S* s) { return s ? (int)s->keys.size() : 0; }
     static int weight_info(const S* s, int i, const char** key, int64_t shape[4], int* ndim) { return s ? s->info(i, key, shape, ndim) : DEX_ERR_ARG; }
+
+    // ---- for S a TrunkStore.  The host-only entry points take configs that were never created: ok is the network's own predicate
+    // of a geometry it can chain frame counts over, need its fewest samples of a row
+    static int num_frames(const Cfg* cfg, int n_samples, Cfg (*default_config)(), bool (*ok)(const Cfg&)) {
+        const Cfg c = cfg ? *cfg : default_config();
+        if (n_samples < 0 || !ok(c)) return DEX_ERR_ARG;
+        const Trunk t = trunk_of(c);
+        return frames_of(t, n_samples, t.n_conv);
+    }
+    static int min_samples(const Cfg* cfg, Cfg (*default_config)(), bool (*ok)(const Cfg&), long (*need)(const Cfg&)) {
+        const Cfg c = cfg ? *cfg : default_config();
+        if (!ok(c)) return DEX_ERR_ARG;
+        const long n = need(c);
+        return n > 0x7fffffffL ? DEX_ERR_ARG : (int)n;
+    }
+    // the bytes plan(s, nullptr, B, max_samples) lays out; 0 for a batch the handle's rule refuses
+    template <class Plan>
+    static size_t workspace_bytes(const S* s, int B, int max_samples, Plan plan) {
+        if (!s || B < 1 || B > MAX_B || max_samples < s->rule.need || (s->rule.max_samples && max_samples > s->rule.max_samples)) return 0;
+        const int T = frames_of(s->t, max_samples, s->t.n_conv);
+        if ((s->rule.max_frames && T > s->rule.max_frames) || (long)B * frames_of(s->t, max_samples, 1) > MAX_ROWS) return 0;
+        return plan(s, nullptr, B, max_samples).bytes;
+    }
+    // A network call that takes wavs.  The checks come in an order a caller can observe: the wavs under the handle's rule, the output
+    // and workspace pointers (outputs_ok: none of the outputs asked for is null), more() (the network's further argument checks),
+    // finalized, the workspace's size; then enqueue(w, T) with the planned workspace and the frames of the padded batch
+    template <class Plan, class More, class Enqueue>
+    static int call(S* s, const float* wav, const int32_t* lengths_host, int B, int n_samples, bool outputs_ok, void* ws, size_t ws_bytes, Plan plan,
+                    More more, Enqueue enqueue) {
+        int T = 0;
+        if (int rc = check_wavs(s, s->t, s->rule, wav, lengths_host, B, n_samples, &T)) return rc;
+        if (!outputs_ok || !ws) return s->fail(DEX_ERR_ARG, "null pointer argument");
+        if (int rc = more()) return rc;
+        if (!s->finalized) return s->fail(DEX_ERR_STATE, "the %sweights are not finalized (%s_finalize)", s->noun, s->prefix);
+        const auto w = plan(s, ws, B, n_samples);
+        if (ws_bytes < w.bytes) return s->fail(DEX_ERR_WORKSPACE, "workspace too small (%s_workspace_bytes)", s->prefix);
+        const int rc = enqueue(w, T);
+        return rc ? s->fail(rc, "kernel launch failed") : DEX_OK;
+    }
 };
 
 }  // namespace

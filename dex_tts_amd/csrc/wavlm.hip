@@ -23,9 +23,10 @@
 //   wavlm_mix_kernel       the softmax(layer_weights)-weighted sum of the hidden states, accumulated as the layers finish (one buffer).
 //   wavlm_pool_kernel      statistics pooling: mean and unbiased deviation per channel over the row's own TDNN frames, two passes in
 //                          fp64; a channel that is 0 on every frame has deviation exactly 0.
-// This file holds what is WavLM's own: those kernels, the padded pack of the positional convolution, the x-vector head and the
-// post-norm layer loop with its gate, biased attention and layer mix.  The trunk it shares with asr.hip - geometry, key inventory,
-// packing, workspace prefix, the enqueue steps around the layer loop, the boilerplate entry points - is wav_trunk.h.
+// This file holds what is WavLM's own: those kernels, the gate + biased attention it hands the shared encoder layer (post-norm), the
+// layer mix and the x-vector head.  What it shares with the other waveform networks - geometry, key inventory, packing, workspace
+// prefix, the enqueue steps, the layer, the entry points with the skeleton of a call - is wav_trunk.h; the group-norm front end it
+// shares with mos.hip is wav_groupnorm.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -348,11 +349,9 @@ std::string tk(int i, const char* what) { return "tdnn." + std::to_string(i) + "
 
 }  // namespace
 
-struct DexWavlm : dex::WeightStore {
-    DexWavlm() : WeightStore("wavlm ") {}
+struct DexWavlm : TrunkStore {             // w.conv_g[0] / conv_be[0]: the group norm's affine; w.pos_w / pos_b: the padded groups
+    DexWavlm() : TrunkStore("wavlm ", "dex_wavlm") {}
     DexWavlmConfig c;
-    Trunk t;
-    TrunkWeights w;                         // conv_g[0] / conv_be[0]: the group norm's affine; pos_w / pos_b: the padded groups
     struct Gate { const float *gw, *gb, *gc; };
     std::vector<Gate> gates;                // gru_rel_pos_linear and gru_rel_pos_const per encoder layer
     const float *rel_embed = nullptr, *lw = nullptr;
@@ -367,6 +366,8 @@ namespace {
 void register_keys(DexWavlm* s) {
     const DexWavlmConfig& c = s->c;
     s->t = trunk_of(c);
+    s->why = "too short, statistics pooling needs two TDNN frames (" + std::to_string(min_samples(c)) + " samples)";
+    s->rule = WavRule{min_samples(c), s->why.c_str(), 0, MAXF};
     register_trunk_keys(s, KEYS, s->t, false, [&](int l) {
         s->add(KEYS.lk(l, "attention.gru_rel_pos_const"), {1, c.n_heads, 1, 1});
         s->add(KEYS.lk(l, "attention.gru_rel_pos_linear.weight"), {8, 64}); s->add(KEYS.lk(l, "attention.gru_rel_pos_linear.bias"), {8});
@@ -455,12 +456,8 @@ int enqueue_encoder(DexWavlm* s, const float* wav, const int32_t* lengths_host, 
     const Trunk& t = s->t;
     const TrunkWeights& W = s->w;
     const int T = w.T, H = c.hidden;
-    enqueue_front(t, w, wav, lengths_host, B, n, do_normalize, st);
-    enqueue_conv0_groupnorm(t, W, w, w, do_normalize ? w.xn : wav, B, n, st);       // layer 0: the raw convolution, the group norm, GELU
-    enqueue_projection(t, W, w, enqueue_conv_tail<false>(t, W, w, B, 1, st), B, st);
+    enqueue_groupnorm_front(t, W, w, w, w, wav, lengths_host, B, n, do_normalize, st);
     const long rows = (long)B * T;
-    enqueue_pos_padded(t, W, w, w, B, st);                                              // h = LN(y + GELU(pos_conv(y)) without its last frame)
-    layer_norm<false>(w.h, w.h, rows, T, H, W.enc_g, W.enc_be, c.layer_norm_eps, nullptr, st);
     const long n4 = rows * H / 4;
     const dim3 mg((unsigned)((n4 + 255) / 256));
     auto mix = [&](int l, bool last) {
@@ -472,18 +469,14 @@ int enqueue_encoder(DexWavlm* s, const float* wav, const int32_t* lengths_host, 
     mix(0, false);
     hipLaunchKernelGGL(wavlm_rel_kernel, dim3((2 * T - 1 + 255) / 256, c.n_heads), dim3(256), 0, st, s->rel_embed, s->buckets, w.rel, T, c.n_heads);
     const int* kv_len = w.lens + (long)t.n_conv * B;
-    for (int l = 0; l < c.n_layers; ++l) {                                              // post-norm: h = LN(h + attn(h)); h = LN(h + ffn(h))
-        const TrunkWeights::Layer& L = W.layers[l];
+    for (int l = 0; l < c.n_layers; ++l) {
         const DexWavlm::Gate& g = s->gates[l];
-        hipLaunchKernelGGL(wavlm_gate_kernel, dim3((unsigned)((rows * c.n_heads + 255) / 256)), dim3(256), 0, st, w.h, g.gw, g.gb, g.gc, w.gate, B, T,
-                           c.n_heads);
-        linear(w.h, H, L.wqkv, 3 * H, L.bqkv, w.qkv, 0, nullptr, nullptr, T, B, st);
-        const AttnBiasP a{w.qkv, 3 * H, (long)T * 3 * H, w.y, H, (long)T * H, T, kv_len, c.n_heads, w.rel, w.gate};
-        hipLaunchKernelGGL(wavlm_attn_kernel, dim3((T + 31) / 32, c.n_heads, B), dim3(AT_NW * 64), 0, st, a);
-        linear(w.y, H, L.wo, H, L.bo, w.h, 0, w.h, nullptr, T, B, st);                  // h += out_proj(attn)
-        layer_norm<false>(w.h, w.h, rows, T, H, L.ln1g, L.ln1b, c.layer_norm_eps, nullptr, st);
-        enqueue_ffn(t, L, w, w.h, B, st);
-        layer_norm<false>(w.h, w.h, rows, T, H, L.ln2g, L.ln2b, c.layer_norm_eps, nullptr, st);
+        enqueue_layer<false>(layer_dims(t), W.layers[l], w, B, [&](const float* qkv, float* out) {      // post-norm; the gate reads the layer's input
+            hipLaunchKernelGGL(wavlm_gate_kernel, dim3((unsigned)((rows * c.n_heads + 255) / 256)), dim3(256), 0, st, w.h, g.gw, g.gb, g.gc, w.gate, B, T,
+                               c.n_heads);
+            const AttnBiasP a{qkv, 3 * H, (long)T * 3 * H, out, H, (long)T * H, T, kv_len, c.n_heads, w.rel, w.gate};
+            hipLaunchKernelGGL(wavlm_attn_kernel, dim3((T + 31) / 32, c.n_heads, B), dim3(AT_NW * 64), 0, st, a);
+        }, st);
         mix(l + 1, l + 1 == c.n_layers);
     }
     return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
@@ -508,23 +501,17 @@ int enqueue_head(DexWavlm* s, const float* hidden, int B, float* embed, const Ws
     return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
 }
 
+typedef Entry<DexWavlm> E;
+
 int run(DexWavlm* s, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, int do_normalize, float* hidden_dev, float* embed_dev,
         void* workspace_dev, size_t workspace_bytes, hipStream_t st) {
-    int T = 0;
-    const long need = min_samples(s->c);
-    const std::string why = "too short, statistics pooling needs two TDNN frames (" + std::to_string(need) + " samples)";
-    if (int rc = check_wavs(s, s->t, WavRule{need, why.c_str(), 0, MAXF}, wav_dev, lengths_host, B, n_samples, &T)) return rc;
-    if ((!hidden_dev && !embed_dev) || !workspace_dev) return s->fail(DEX_ERR_ARG, "null pointer argument");
-    if (!s->finalized) return s->fail(DEX_ERR_STATE, "the wavlm weights are not finalized (dex_wavlm_finalize)");
-    const Ws w = plan(s, workspace_dev, B, n_samples);
-    if (workspace_bytes < w.bytes) return s->fail(DEX_ERR_WORKSPACE, "workspace too small (dex_wavlm_workspace_bytes)");
-    float* hidden = hidden_dev ? hidden_dev : w.mix;
-    int rc = enqueue_encoder(s, wav_dev, lengths_host, B, n_samples, do_normalize, hidden, w, st);
-    if (rc == DEX_OK && embed_dev) rc = enqueue_head(s, hidden, B, embed_dev, w, st);
-    return rc ? s->fail(rc, "kernel launch failed") : DEX_OK;
+    return E::call(s, wav_dev, lengths_host, B, n_samples, hidden_dev || embed_dev, workspace_dev, workspace_bytes, plan, no_further_check,
+                   [&](const Ws& w, int) {
+        float* hidden = hidden_dev ? hidden_dev : w.mix;
+        const int rc = enqueue_encoder(s, wav_dev, lengths_host, B, n_samples, do_normalize, hidden, w, st);
+        return rc == DEX_OK && embed_dev ? enqueue_head(s, hidden, B, embed_dev, w, st) : rc;
+    });
 }
-
-typedef Entry<DexWavlm> E;
 
 }  // namespace
 
@@ -540,18 +527,8 @@ int dex_wavlm_finalize(DexWavlm* s, dex_stream_t stream) { return E::finalize(s,
 int dex_wavlm_num_weights(const DexWavlm* s) { return E::num_weights(s); }
 int dex_wavlm_weight_info(const DexWavlm* s, int i, const char** key, int64_t shape[4], int* ndim) { return E::weight_info(s, i, key, shape, ndim); }
 
-int dex_wavlm_num_frames(const DexWavlmConfig* cfg, int n_samples) {
-    const DexWavlmConfig c = cfg ? *cfg : default_config();
-    if (n_samples < 0 || !geometry_ok(c)) return DEX_ERR_ARG;
-    return frames_of(trunk_of(c), n_samples, c.n_conv);
-}
-
-int dex_wavlm_min_samples(const DexWavlmConfig* cfg) {
-    const DexWavlmConfig c = cfg ? *cfg : default_config();
-    if (!geometry_ok(c)) return DEX_ERR_ARG;
-    const long n = min_samples(c);
-    return n > 0x7fffffffL ? DEX_ERR_ARG : (int)n;
-}
+int dex_wavlm_num_frames(const DexWavlmConfig* cfg, int n_samples) { return E::num_frames(cfg, n_samples, default_config, geometry_ok); }
+int dex_wavlm_min_samples(const DexWavlmConfig* cfg) { return E::min_samples(cfg, default_config, geometry_ok, min_samples); }
 
 int dex_wavlm_rel_buckets(const DexWavlmConfig* cfg, int n, int32_t* out) {
     const DexWavlmConfig c = cfg ? *cfg : default_config();
@@ -560,11 +537,7 @@ int dex_wavlm_rel_buckets(const DexWavlmConfig* cfg, int n, int32_t* out) {
     return DEX_OK;
 }
 
-size_t dex_wavlm_workspace_bytes(const DexWavlm* s, int B, int max_samples) {
-    if (!s || B < 1 || B > MAX_B || max_samples < min_samples(s->c)) return 0;
-    if (frames_of(s->t, max_samples, s->t.n_conv) > MAXF || (long)B * frames_of(s->t, max_samples, 1) > MAX_ROWS) return 0;
-    return plan(s, nullptr, B, max_samples).bytes;
-}
+size_t dex_wavlm_workspace_bytes(const DexWavlm* s, int B, int max_samples) { return E::workspace_bytes(s, B, max_samples, plan); }
 
 int dex_wavlm_hidden(DexWavlm* s, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, int do_normalize, float* hidden_dev,
                      void* workspace_dev, size_t workspace_bytes, dex_stream_t stream) {

@@ -2,15 +2,19 @@
 // WhisperFeatureExtractor, encoder, decoder with a key/value cache, greedy decoding).  fp32 throughout, channels-last.  C ABI
 // dex_whisper_*; dex_tts_amd/whisper.py states the definitions.
 //
-//   wsp_mel_kernel       the front end up to log10: 8 frames per workgroup; the zero-padded, reflect-padded, Hann-windowed frames in
+//   wsp_mel_long_kernel  the front end up to log10: 8 frames per workgroup; the zero-padded, reflect-padded, Hann-windowed frames in
 //                        LDS as fp64, the 400-point DFT as a direct sum in fp64 (400 is no power of two; one thread per bin walks the
-//                        twiddle table by k n mod 400), power, the mel matrix (fp64, built on the host), log10(max(., 1e-10)).
-//   wsp_mel_floor_kernel one workgroup per row: the row's maximum (a maximum has no summation order), the floor at max - 8,
-//                        (x + 4) / 4, rounded to fp32 once and stored [n_mels][frames].
+//                        twiddle table by k n mod 400), power, the mel matrix (fp64, built on the host), log10(max(., 1e-10)).  A row of
+//                        at most one chunk is zero-padded to the chunk and has its frames; a longer row has its own ends reflected and
+//                        len / 160 frames.
+//   wsp_mel_floor_long_kernel  one workgroup per row: the maximum over all of the row's frames (a maximum has no summation order), the
+//                        floor at max - 8, (x + 4) / 4, rounded to fp32 once and stored [n_mels][frames], 0 behind the row's frames.
+//   wsp_gather_kernel    the cut of a 30 s window at a row's seek.
 //   launch_igemm         (igemm.hip, exact-fp32 MFMA) every wide contraction: conv1 (the mel channels padded to a multiple of 32,
 //                        GELU in the epilogue), conv2 (stride 2, GELU and + embed_positions in the epilogue), the encoder's q|k|v,
-//                        out_proj, fc1, fc2, and the cross-attention k|v of every decoder layer, once per utterance.
-//   launch_attention     (attention.hip) the encoder's self-attention: the generic fp32 kernel at head_dim 64, no mask.
+//                        out_proj, fc1, fc2, and the cross-attention k|v of every decoder layer, once per utterance.  The encoder
+//                        layer is wav_trunk.h's, pre-norm with the plain attention (attention.hip's generic fp32 kernel at
+//                        head_dim 64, no mask) and fc2 as one launch.
 //   wsp_skinny_kernel    the decoder step's linears at M = B <= 32 rows: every weight element is read from HBM once for the whole
 //                        batch.  A lane owns one output column, a wave 64 rows of K (all 64 loads issued before the first wait), the rows
 //                        of x sit in LDS and are read as broadcasts; the four waves of a workgroup meet in LDS in wave order and the
@@ -27,9 +31,7 @@
 //   wsp_pick_ts_kernel   the same tail under the timestamp rule of long-form decoding (WhisperTimeStampLogitsProcessor): the masks of
 //                        the rule as index ranges from the row's own state (its last two ids, its last timestamp, its new-token
 //                        count, all on the device), the best text id, the best timestamp id and logsumexp(timestamps) in one pass
-//                        over the logits, reduced in a fixed order; the plain kernel is untouched.
-//   wsp_mel_long_kernel, wsp_mel_floor_long_kernel, wsp_gather_kernel   the front end of a row longer than one chunk (its own ends
-//                        reflected, len / 160 frames, one maximum over all of them) and the cut of a 30 s window at a row's seek.
+//                        over the logits, reduced in a fixed order.  Both kernels end in pick_commit.
 // Every per-row sum has an order fixed by the config and the position: a row's logits and ids are bitwise those of the row alone.
 #include <hip/hip_runtime.h>
 
@@ -43,7 +45,7 @@
 #include "wav_trunk.h"
 #include "weight_store.h"
 
-using namespace dex::wavenc;      // the GEMM wrappers, LayerNorm, packing, Taker and Entry of the waveform transformers
+using namespace dex::wavenc;      // the GEMM wrappers, LayerNorm, packing, the encoder layer, Taker and Entry of the waveform networks
 
 namespace {
 
@@ -99,13 +101,8 @@ __device__ __forceinline__ void mel_frames(const MelP& p, const float* x, int L,
     }
 }
 
-__global__ __launch_bounds__(256) void wsp_mel_kernel(const MelP p) {
-    const int b = blockIdx.y;
-    mel_frames(p, p.wav + (long)b * p.ld, p.len.a[b], p.N, p.T, blockIdx.x * MELF, p.out + (long)b * p.T * p.n_mels);
-}
-
-// the frames of a row in the long form: at most one chunk (p.N samples) -> the chunk's p.T frames of the zero-padded row, as above;
-// longer -> len / 160 frames of the row reflected at its own ends
+// the frames of a row: at most one chunk (p.N samples) -> the chunk's p.T frames of the zero-padded row; longer -> len / 160 frames
+// of the row reflected at its own ends
 __device__ __forceinline__ int long_frames(int L, long chunk, int T) { return L <= chunk ? T : L / HOP; }
 
 // rows of any length: p.T = the frames of a chunk, p.N its samples; out [B][Fmax][n_mels]
@@ -114,27 +111,6 @@ __global__ __launch_bounds__(256) void wsp_mel_long_kernel(const MelP p, int Fma
     const int T = long_frames(L, p.N, p.T);
     if (t0 >= T) return;
     mel_frames(p, p.wav + (long)b * p.ld, L, L <= p.N ? p.N : (long)L, T, t0, p.out + (long)b * Fmax * p.n_mels);
-}
-
-// logspec [B][T][n_mels] (fp64) -> out [B][n_mels][T]: max(x, rowmax - 8), (x + 4) / 4
-__global__ __launch_bounds__(1024) void wsp_mel_floor_kernel(const double* logspec, float* out, int T, int n_mels) {
-    __shared__ double red[1024];
-    const int tid = threadIdx.x, b = blockIdx.x;
-    const long n = (long)T * n_mels;
-    const double* x = logspec + (long)b * n;
-    double m = -1e300;
-    for (long i = tid; i < n; i += 1024) m = fmax(m, x[i]);
-    red[tid] = m;
-    __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
-        __syncthreads();
-    }
-    const double lo = red[0] - 8.0;
-    for (long i = tid; i < n; i += 1024) {
-        const int mel = (int)(i / T), t = (int)(i - (long)mel * T);
-        out[(long)b * n + i] = (float)((fmax(x[(long)t * n_mels + mel], lo) + 4.0) / 4.0);
-    }
 }
 
 // feat [B][n_mels][T] -> cl [B][T][Mp], the channels past n_mels 0
@@ -354,6 +330,31 @@ __device__ __forceinline__ void better(float& v, int& i, float ov, int oi) {
     if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
 }
 
+// The end of a step for row b.  Thread 0 commits the id it chose (arg >= V: nothing competed - a row of NaN compares with nothing -
+// and the id is 0; a finished row emits eos): the finished / count / lengths bookkeeping, under the timestamp rule (n_new given) the
+// row's last timestamp (ids from tb on) and its new-token count, and the id store.  Then every thread gathers the next step's
+// h = embed_tokens[id] + embed_positions[next_pos] (next_pos >= 0).  One writer per row
+__device__ __forceinline__ void pick_commit(const PickP& p, int b, int arg, int* chosen, int tb, int* last_ts, int* n_new) {
+    if (threadIdx.x == 0) {
+        if (arg >= p.V) arg = 0;
+        const int fin = p.finished[b];
+        const int id = fin ? p.eos : arg;
+        if (!fin) {
+            if (id == p.eos) { p.finished[b] = 1; atomicAdd(p.count, 1); }
+            else p.lengths[b] += 1;
+            if (n_new && id >= tb) last_ts[b] = id;
+        }
+        if (n_new) n_new[b] += 1;
+        p.ids[(long)b * p.ld_ids + p.step] = id;
+        *chosen = id;
+    }
+    __syncthreads();
+    if (p.next_pos < 0) return;
+    const float* e = p.emb + (long)*chosen * p.d;
+    const float* q = p.pos + (long)p.next_pos * p.d;
+    for (int c = threadIdx.x; c < p.d; c += 1024) p.h[(long)b * p.d + c] = e[c] + q[c];
+}
+
 // row blockIdx.x: the logits finished from the partials (stored where `logits` is given); pick: the id of this step and the bookkeeping;
 // next_pos >= 0: h = embed_tokens[id] + embed_positions[next_pos]
 __global__ __launch_bounds__(1024) void wsp_pick_kernel(const PickP p) {
@@ -373,23 +374,9 @@ __global__ __launch_bounds__(1024) void wsp_pick_kernel(const PickP p) {
     for (int o = 32; o > 0; o >>= 1) { const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(arg, o); better(best, arg, ov, oi); }
     if (lane == 0) { bv[wave] = best; bi[wave] = arg; }
     __syncthreads();
-    if (tid == 0) {
+    if (tid == 0)
         for (int w = 1; w < 16; ++w) better(best, arg, bv[w], bi[w]);
-        if (arg >= p.V) arg = 0;                     // a row of NaN compares with nothing
-        const int fin = p.finished[b];
-        const int id = fin ? p.eos : arg;
-        if (!fin) {
-            if (id == p.eos) { p.finished[b] = 1; atomicAdd(p.count, 1); }
-            else p.lengths[b] += 1;
-        }
-        p.ids[(long)b * p.ld_ids + p.step] = id;
-        chosen = id;
-    }
-    __syncthreads();
-    if (p.next_pos < 0) return;
-    const float* e = p.emb + (long)chosen * p.d;
-    const float* q = p.pos + (long)p.next_pos * p.d;
-    for (int c = tid; c < p.d; c += 1024) p.h[(long)b * p.d + c] = e[c] + q[c];
+    pick_commit(p, b, arg, &chosen, 0, nullptr, nullptr);
 }
 
 // The tail under the timestamp rule.  tb = the first timestamp id (no_timestamps + 1), max_init >= 0: the cap of the first timestamp;
@@ -450,29 +437,15 @@ __global__ __launch_bounds__(1024) void wsp_pick_ts_kernel(const PickTsP q) {
     }
     if (lane == 0) { tv[wave] = bt; ti[wave] = at; sv[wave] = bs; si[wave] = as; mv[wave] = m; lv[wave] = s; }
     __syncthreads();
+    int arg = 0;
     if (tid == 0) {
         for (int w = 1; w < 16; ++w) { better(bt, at, tv[w], ti[w]); better(bs, as, sv[w], si[w]); lse_join(m, s, mv[w], lv[w]); }
         // logsumexp(timestamps) > max(text): the timestamps' summed probability beats every text id; no normaliser is needed
         const bool force = m + logf(s) > bt;
-        int arg = as;
+        arg = as;
         if (!force) { float bv = bt; arg = at; better(bv, arg, bs, as); }
-        if (arg >= V) arg = 0;                       // nothing competed
-        const int fin = p.finished[b];
-        const int id = fin ? p.eos : arg;
-        if (!fin) {
-            if (id == p.eos) { p.finished[b] = 1; atomicAdd(p.count, 1); }
-            else p.lengths[b] += 1;
-            if (id >= tb) q.last_ts[b] = id;
-        }
-        q.n_new[b] = i + 1;
-        p.ids[(long)b * p.ld_ids + p.step] = id;
-        chosen = id;
     }
-    __syncthreads();
-    if (p.next_pos < 0) return;
-    const float* e = p.emb + (long)chosen * p.d;
-    const float* pq = p.pos + (long)p.next_pos * p.d;
-    for (int c = tid; c < p.d; c += 1024) p.h[(long)b * p.d + c] = e[c] + pq[c];
+    pick_commit(p, b, arg, &chosen, tb, q.last_ts, q.n_new);
 }
 
 // h[b] = embed_tokens[id] + embed_positions[pos], id = ids[b ld + pos] (clamped into the vocabulary) or, ids null, `id`
@@ -540,12 +513,11 @@ int check_config(const DexWhisperConfig& c) {
 struct DexWhisper : dex::WeightStore {
     DexWhisper() : WeightStore("whisper ") {}
     DexWhisperConfig c;
-    struct EncLayer { const float *ln1g, *ln1b, *wqkv, *bqkv, *wo, *bo, *ln2g, *ln2b, *w1, *b1, *w2, *b2; };
     struct DecLayer { const float *ln1g, *ln1b, *wqkv, *bq, *bv, *wo, *bo, *ln2g, *ln2b, *wcq, *bcq, *wckv, *bckv, *wco, *bco,
                       *ln3g, *ln3b, *w1, *b1, *w2, *b2; };
     const float *conv1_w = nullptr, *conv1_b = nullptr, *conv2_w = nullptr, *conv2_b = nullptr, *enc_pos = nullptr, *enc_g = nullptr, *enc_be = nullptr;
     const float *emb = nullptr, *embT = nullptr, *dec_pos = nullptr, *dec_g = nullptr, *dec_be = nullptr;
-    std::vector<EncLayer> enc;
+    std::vector<TrunkWeights::Layer> enc;      // ln1 = self_attn_layer_norm, ln2 = final_layer_norm
     std::vector<DecLayer> dec;
     std::vector<double> tab_host;            // window | cos | sin | mel matrix
     double* tab_dev = nullptr;
@@ -593,23 +565,6 @@ void register_keys(DexWhisper* s) {
     add_ln(s, DEC + "layer_norm", d);
 }
 
-// the [K = d][N = n d] operand of n projections side by side, and (bias) their biases with 0 where a projection has none
-const float* pack_side(DexWhisper* s, const std::string& p, std::initializer_list<const char*> names, int d, hipStream_t st, const float** bias) {
-    const int n = (int)names.size();
-    float* w = s->alloc((long)n * d * d);
-    float* b = bias ? s->alloc((long)n * d) : nullptr;
-    if (!w || (bias && !b)) return nullptr;
-    if (b) hipMemsetAsync(b, 0, (size_t)n * d * sizeof(float), st);
-    int j = 0;
-    for (const char* nm : names) {
-        pack_into(s->R(p + nm + ".weight"), w, 1, d, d, 1, n * d, j * d, nullptr, st);
-        if (b && s->raw.count(p + nm + ".bias")) hipMemcpyAsync(b + (long)j * d, s->R(p + nm + ".bias"), d * sizeof(float), hipMemcpyDeviceToDevice, st);
-        ++j;
-    }
-    if (bias) *bias = b;
-    return w;
-}
-
 int pack_all(DexWhisper* s, hipStream_t st) {
     const DexWhisperConfig& c = s->c;
     const int d = c.d_model;
@@ -617,9 +572,9 @@ int pack_all(DexWhisper* s, hipStream_t st) {
     s->conv2_w = pack(s, ENC + "conv2.weight", 1, d, d, 3, nullptr, st); s->conv2_b = s->R(ENC + "conv2.bias");
     s->enc_pos = s->R(ENC + "embed_positions.weight");
     s->enc_g = s->R(ENC + "layer_norm.weight"); s->enc_be = s->R(ENC + "layer_norm.bias");
-    s->enc.assign(c.encoder_layers, DexWhisper::EncLayer{});
+    s->enc.assign(c.encoder_layers, TrunkWeights::Layer{});
     for (int l = 0; l < c.encoder_layers && s->alloc_rc == DEX_OK; ++l) {
-        DexWhisper::EncLayer& L = s->enc[l];
+        TrunkWeights::Layer& L = s->enc[l];
         L.wqkv = pack_side(s, ek(l, "self_attn."), {"q_proj", "k_proj", "v_proj"}, d, st, &L.bqkv);
         L.wo = pack(s, ek(l, "self_attn.out_proj.weight"), 1, d, d, 1, nullptr, st); L.bo = s->R(ek(l, "self_attn.out_proj.bias"));
         L.ln1g = s->R(ek(l, "self_attn_layer_norm.weight")); L.ln1b = s->R(ek(l, "self_attn_layer_norm.bias"));
@@ -700,15 +655,16 @@ void finish(const float* P, int KS, int N, const float* bias, const float* res, 
     hipLaunchKernelGGL(wsp_finish_kernel, dim3(B), dim3(256), 0, st, p);
 }
 
-void enqueue_log_mel(DexWhisper* s, const float* wav, const int32_t* lengths_host, int B, int n, float* out, const Ws& w, hipStream_t st) {
+// log-mel features of rows of any length (the tables are up): logspec fp64 [B][Fmax][n_mels] -> out [B][n_mels][Fmax], F the frames
+// of the longest row.  Rows of at most one chunk have the chunk's frames: Fmax = F = those is the one-chunk front end
+void enqueue_log_mel(DexWhisper* s, const float* wav, const int32_t* lengths_host, int B, int n, double* logspec, float* out, int F, int Fmax, hipStream_t st) {
     const DexWhisperConfig& c = s->c;
-    const int T = 2 * c.max_source_positions, M = c.num_mel_bins;
     MelP p{};
-    p.wav = wav; p.ld = n; p.N = (long)T * HOP; p.T = T; p.n_mels = M;
+    p.wav = wav; p.ld = n; p.T = 2 * c.max_source_positions; p.N = (long)p.T * HOP; p.n_mels = c.num_mel_bins;
     for (int b = 0; b < B; ++b) p.len.a[b] = lengths_host[b];
-    p.win = s->tab_dev; p.cs = s->tab_dev + NFFT; p.sn = s->tab_dev + 2 * NFFT; p.filt = s->tab_dev + 3 * NFFT; p.out = w.logspec;
-    hipLaunchKernelGGL(wsp_mel_kernel, dim3((T + MELF - 1) / MELF, B), dim3(256), 0, st, p);
-    hipLaunchKernelGGL(wsp_mel_floor_kernel, dim3(B), dim3(1024), 0, st, w.logspec, out, T, M);
+    p.win = s->tab_dev; p.cs = s->tab_dev + NFFT; p.sn = s->tab_dev + 2 * NFFT; p.filt = s->tab_dev + 3 * NFFT; p.out = logspec;
+    hipLaunchKernelGGL(wsp_mel_long_kernel, dim3((F + MELF - 1) / MELF, B), dim3(256), 0, st, p, Fmax);
+    hipLaunchKernelGGL(wsp_mel_floor_long_kernel, dim3(B), dim3(1024), 0, st, (const double*)logspec, out, p.len, p.N, p.T, Fmax, p.n_mels);
 }
 
 // the window, the twiddles and the mel matrix, on the device from the first front-end call on
@@ -734,22 +690,10 @@ void enqueue_encoder(DexWhisper* s, const float* feat, int B, float* enc_out, co
     hipLaunchKernelGGL(wsp_feat_cl_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, feat, w.mel, total, T, c.num_mel_bins, Mp);
     gemm(w.mel, Mp, T, Mp, 3, 1, -1, T, s->conv1_w, d, 1, s->conv1_b, w.c1, 1, nullptr, nullptr, B, st);
     gemm(w.c1, d, T, d, 3, 2, -1, S, s->conv2_w, d, 1, s->conv2_b, w.he, 1, s->enc_pos, nullptr, B, st, 1, 1, true);
+    const LayerDims ld{d, c.encoder_attention_heads, c.encoder_ffn_dim, 1, LN_EPS};      // fc2 as one launch
+    const LayerWs lw{w.he, w.ye, w.qkv, w.ffe, nullptr, S};
+    for (const TrunkWeights::Layer& L : s->enc) enqueue_plain_layer<true>(ld, L, lw, nullptr, B, st);
     const long rows = (long)B * S;
-    for (const DexWhisper::EncLayer& L : s->enc) {
-        layer_norm<false>(w.he, w.ye, rows, S, d, L.ln1g, L.ln1b, LN_EPS, nullptr, st);
-        linear(w.ye, d, L.wqkv, 3 * d, L.bqkv, w.qkv, 0, nullptr, nullptr, S, B, st);
-        dex::AttnP a{};
-        a.Q = w.qkv; a.ldq = 3 * d; a.qb = (long)S * 3 * d;
-        a.K = w.qkv + d; a.ldk = 3 * d; a.kb = a.qb;
-        a.V = w.qkv + 2 * d; a.ldv = 3 * d; a.vb = a.qb;
-        a.O = w.ye; a.ldo = d; a.ob = (long)S * d;
-        a.Nq = S; a.Nk = S; a.kv_len = nullptr; a.kv_len_add = 0; a.heads = c.encoder_attention_heads; a.scale = 0.125f; a.B = B; a.head_dim = 64;
-        dex::launch_attention(a, dex::PREC_FP32, st);
-        linear(w.ye, d, L.wo, d, L.bo, w.he, 0, w.he, nullptr, S, B, st);
-        layer_norm<false>(w.he, w.ye, rows, S, d, L.ln2g, L.ln2b, LN_EPS, nullptr, st);
-        linear(w.ye, d, L.w1, c.encoder_ffn_dim, L.b1, w.ffe, 1, nullptr, nullptr, S, B, st);
-        linear(w.ffe, c.encoder_ffn_dim, L.w2, d, L.b2, w.he, 0, w.he, nullptr, S, B, st);
-    }
     layer_norm<false>(w.he, w.enc, rows, S, d, s->enc_g, s->enc_be, LN_EPS, nullptr, st);
     if (enc_out) hipMemcpyAsync(enc_out, w.enc, (size_t)rows * d * sizeof(float), hipMemcpyDeviceToDevice, st);
     if (mark) hipEventRecord(mark, st);
@@ -851,7 +795,8 @@ int dex_whisper_log_mel(DexWhisper* s, const float* wav_dev, const int32_t* leng
     for (int b = 0; b < B; ++b)
         if (lengths_host[b] < 1 || lengths_host[b] > n_samples) return s->fail(DEX_ERR_ARG, "row lengths must lie in [1, n_samples]");
     if (int rc = ensure_tables(s, (hipStream_t)stream)) return rc;
-    enqueue_log_mel(s, wav_dev, lengths_host, B, n_samples, out_dev, w, (hipStream_t)stream);
+    const int T = 2 * s->c.max_source_positions;
+    enqueue_log_mel(s, wav_dev, lengths_host, B, n_samples, w.logspec, out_dev, T, T, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? DEX_OK : s->fail(DEX_ERR_HIP, "kernel launch failed");
 }
 
@@ -980,11 +925,9 @@ int dex_whisper_log_mel_long(DexWhisper* s, const float* wav_dev, const int32_t*
     const DexWhisperConfig& c = s->c;
     const int Tc = 2 * c.max_source_positions, M = c.num_mel_bins;
     const long chunk = (long)Tc * HOP;
-    MelP p{};
     int F = 0;
     for (int b = 0; b < B; ++b) {
         if (lengths_host[b] < 1 || lengths_host[b] > n_samples) return s->fail(DEX_ERR_ARG, "row lengths must lie in [1, n_samples]");
-        p.len.a[b] = lengths_host[b];
         frames_host[b] = lengths_host[b] <= chunk ? Tc : lengths_host[b] / HOP;
         F = frames_host[b] > F ? frames_host[b] : F;
     }
@@ -992,10 +935,7 @@ int dex_whisper_log_mel_long(DexWhisper* s, const float* wav_dev, const int32_t*
     if (scratch_bytes < (size_t)B * max_frames * M * sizeof(double)) return s->fail(DEX_ERR_WORKSPACE, "scratch too small (B x max_frames x num_mel_bins doubles)");
     hipStream_t st = (hipStream_t)stream;
     if (int rc = ensure_tables(s, st)) return rc;
-    p.wav = wav_dev; p.ld = n_samples; p.N = chunk; p.T = Tc; p.n_mels = M;
-    p.win = s->tab_dev; p.cs = s->tab_dev + NFFT; p.sn = s->tab_dev + 2 * NFFT; p.filt = s->tab_dev + 3 * NFFT; p.out = (double*)scratch_dev;
-    hipLaunchKernelGGL(wsp_mel_long_kernel, dim3((F + MELF - 1) / MELF, B), dim3(256), 0, st, p, max_frames);
-    hipLaunchKernelGGL(wsp_mel_floor_long_kernel, dim3(B), dim3(1024), 0, st, (const double*)scratch_dev, out_dev, p.len, chunk, Tc, max_frames, M);
+    enqueue_log_mel(s, wav_dev, lengths_host, B, n_samples, (double*)scratch_dev, out_dev, F, max_frames, st);
     return hipGetLastError() == hipSuccess ? DEX_OK : s->fail(DEX_ERR_HIP, "kernel launch failed");
 }
 

@@ -34,9 +34,8 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
 from ._native import Handle, host_lengths, i32_ptr, on_device, stream
-from ._wavnet import MAX_CONV, SAMPLING_RATE, WaveformNet, fill_trunk_config, weight_shapes
+from ._wavnet import MAX_CONV, SAMPLING_RATE, HostEntry, WaveformNet, fill_trunk_config
 from .speaker import mean_stderr  # noqa: F401  (this module's public name too)
 
 MAX_FRAMES = 4096                  # DEX_MOS_MAX_FRAMES: the encoder frames one call takes (81 s)
@@ -89,22 +88,17 @@ def _c_config(cfg: MOSConfig) -> DexMosConfig:
     return c
 
 
+_HOST = HostEntry("dex_mos", _c_config, MOSConfig, "MOSConfig")
+
+
 def num_frames(n_samples: int, config: Optional[MOSConfig] = None) -> int:
     """Encoder frames of ``n_samples`` samples: ``floor((L - k) / s) + 1`` chained over the feature extractor.  Host integers."""
-    c = _c_config(config or MOSConfig())
-    n = int(_lib.load().dex_mos_num_frames(C.byref(c), int(n_samples)))
-    if n < 0:
-        raise ValueError(f"num_frames: bad arguments ({n_samples} samples)")
-    return n
+    return _HOST.num_frames(n_samples, config)
 
 
 def min_samples(config: Optional[MOSConfig] = None) -> int:
     """The fewest samples a row may have: one encoder frame (400 with the default geometry).  Host integers."""
-    c = _c_config(config or MOSConfig())
-    n = int(_lib.load().dex_mos_min_samples(C.byref(c)))
-    if n < 0:
-        raise ValueError("min_samples: bad geometry")
-    return n
+    return _HOST.min_samples(config)
 
 
 def _ignored(key: str) -> bool:
@@ -117,26 +111,13 @@ def state_dict_shapes(config: Optional[MOSConfig] = None) -> dict:
     ``weight_g`` / ``weight_v`` spelling), ``domain_embedding.weight``, ``judge_embedding.weight``, ``decoder_rnn.*_l0`` and
     ``*_l0_reverse``, ``projection.0.*`` and ``projection.3.*``; ``NotImplementedError`` naming the field for a config outside the
     family that is built.  Host only."""
-    lib, h = _lib.load(), C.c_void_p()
-    if lib.dex_mos_create(C.byref(_c_config(config or MOSConfig())), C.byref(h)) != _lib.DEX_OK:
-        raise NotImplementedError(f"MOSConfig.{lib.dex_mos_last_error(None).decode()}")
-    try:
-        return weight_shapes(lib, "dex_mos", h)
-    finally:
-        lib.dex_mos_destroy(h)
+    return _HOST.state_dict_shapes(config)
 
 
 def check_lengths(lengths, n_samples: int, config: Optional[MOSConfig] = None, what: str = "mos") -> int:
     """What one call refuses, before anything is enqueued: a row below ``min_samples`` (``ValueError`` 'too short') and a padded
     length of more than ``MAX_FRAMES`` encoder frames.  Returns the frames of ``n_samples``.  Host only."""
-    need = min_samples(config)
-    short = [int(v) for v in lengths if v < need]
-    if short:
-        raise ValueError(f"{what}: {short[0]} samples are too short: the feature extractor needs {need} samples for one frame")
-    T = num_frames(n_samples, config)
-    if T > MAX_FRAMES:
-        raise ValueError(f"{what}: {n_samples} samples are {T} encoder frames; one call takes at most {MAX_FRAMES}")
-    return T
+    return _HOST.check_lengths(lengths, n_samples, config, what, "the feature extractor needs {need} samples for one frame", MAX_FRAMES)
 
 
 _FAIRSEQ = (("self_attn_layer_norm.", "layer_norm."), ("self_attn.", "attention."), ("fc1.", "feed_forward.intermediate_dense."),
@@ -204,14 +185,11 @@ class UTMOS(WaveformNet):
     _no_workspace = f"too short for one frame, or more than one call takes ({MAX_FRAMES} encoder frames)"
     _c_config = staticmethod(_c_config)
     _ignored = staticmethod(_ignored)
+    _check_lengths = staticmethod(check_lengths)
 
     def __init__(self, config: Optional[MOSConfig] = None, device="cuda", do_normalize: bool = False):
         super().__init__(config or MOSConfig(), device)
         self.do_normalize = bool(do_normalize)
-
-    def _inputs(self, wav, lengths, what: str):
-        x, ln, one = self._rows(wav, lengths, what)
-        return x, ln, one, check_lengths(ln, x.shape[1], self.config, what)
 
     def _ids(self, domain, judge, B: int, what: str):
         """``domain`` / ``judge`` (an int, or one value per row) -> host int32 [B] each; ``ValueError`` out of range."""
@@ -231,9 +209,7 @@ class UTMOS(WaveformNet):
         """Raw 16 kHz samples [B, n] (or [n]), row b ``lengths[b]`` samples (what is stored past them reaches no result) ->
         ``Wav2Vec2Model``'s ``last_hidden_state`` [B, T, hidden] with T = ``num_frames(n)``.  Row b fills
         ``num_frames(lengths[b])`` frames and is 0 past them; it is bitwise the row alone."""
-        x, ln, one, T = self._inputs(wav, lengths, "UTMOS.hidden_states")
-        out = torch.empty(x.shape[0], T, self.config.hidden_size, dtype=torch.float32, device=self.device)
-        return self._run("hidden", x, ln, out, int(self.do_normalize), out.data_ptr(), one=one)
+        return self._hidden(wav, lengths)
 
     def bilstm(self, features: torch.Tensor, lengths=None, domain=DOMAIN, judge=JUDGE) -> torch.Tensor:
         """The recurrence alone: features [B, T, hidden] (or [T, hidden]), row b ``lengths[b]`` frames, conditioned on the row's
@@ -288,27 +264,19 @@ class UTMOS(WaveformNet):
     def score_utterances(self, wavs, lengths=None, sr: int = SAMPLING_RATE, domain=DOMAIN, judge=JUDGE) -> torch.Tensor:
         """``wavs`` [B, n] with ``lengths``, or a list of wavs (float, or int16 scaled by 1 / 32768), at ``sr`` Hz -> MOS [B] in one
         network call.  Where ``sr`` is not 16000 the wavs are resampled by ``wavprep.resample`` (kaiser_best)."""
-        if isinstance(wavs, torch.Tensor) and wavs.dim() != 2:
-            raise ValueError(f"UTMOS.score_utterances: expected wavs [B, n] or a list, got {tuple(wavs.shape)}")
-        x, ln = self._at_16k(wavs, lengths, sr, "UTMOS.score_utterances")
+        x, ln = self._utterances(wavs, lengths, sr, "UTMOS.score_utterances")
         return self.forward(x, ln, domain, judge)
-
-
-def _model(model, what: str) -> UTMOS:
-    if not isinstance(model, UTMOS):
-        raise ValueError(f"{what}: pass model=UTMOS(...) with the checkpoint's weights loaded (the library ships none)")
-    return model
 
 
 def mos_score(wavs, lengths=None, source_sr: Optional[int] = 22050, model: Optional[UTMOS] = None, domain=DOMAIN, judge=JUDGE):
     """(mean, stderr) of the predicted MOS of ``wavs`` ([B, n] with ``lengths``, or a list) at ``source_sr`` Hz, the stderr as
     ``speaker.asv_score`` defines it (population std over sqrt(n))."""
-    return mean_stderr(_model(model, "mos_score").score_utterances(wavs, lengths, source_sr or SAMPLING_RATE, domain, judge))
+    return mean_stderr(UTMOS._model(model, "mos_score").score_utterances(wavs, lengths, source_sr or SAMPLING_RATE, domain, judge))
 
 
 def score_synthesis(model, audio, sr: int = 22050, domain=DOMAIN, judge=JUDGE):
     """``synthesize.synthesize_tokens``' list of int16 waveforms (``sr`` Hz) -> (MOS [B] on the device, mean, stderr)."""
     if len(audio) < 1:
         raise ValueError("score_synthesis: no waveforms")
-    mos = _model(model, "score_synthesis").score_utterances(list(audio), None, sr, domain, judge)
+    mos = UTMOS._model(model, "score_synthesis").score_utterances(list(audio), None, sr, domain, judge)
     return (mos,) + mean_stderr(mos)

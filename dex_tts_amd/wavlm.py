@@ -34,7 +34,7 @@ import torch
 
 from . import _lib
 from ._native import device_rows, pad_wavs, resample_to_16k
-from ._wavnet import MAX_CONV, SAMPLING_RATE, WaveformNet, fill_trunk_config, route_hf_state_dict, weight_shapes
+from ._wavnet import MAX_CONV, SAMPLING_RATE, HostEntry, WaveformNet, fill_trunk_config, route_hf_state_dict
 from .speaker import mean_stderr, paired_cosine  # noqa: F401  (mean_stderr is this module's public name too)
 
 MAX_TDNN = 8
@@ -95,23 +95,18 @@ def _c_config(cfg: WavLMConfig) -> DexWavlmConfig:
     return c
 
 
+_HOST = HostEntry("dex_wavlm", _c_config, WavLMConfig, "WavLMConfig")
+
+
 def num_frames(n_samples: int, config: Optional[WavLMConfig] = None) -> int:
     """Encoder frames of ``n_samples`` samples: ``floor((L - k) / s) + 1`` chained over the feature extractor.  Host integers."""
-    c = _c_config(config or WavLMConfig())
-    n = int(_lib.load().dex_wavlm_num_frames(C.byref(c), int(n_samples)))
-    if n < 0:
-        raise ValueError(f"num_frames: bad arguments ({n_samples} samples)")
-    return n
+    return _HOST.num_frames(n_samples, config)
 
 
 def min_samples(config: Optional[WavLMConfig] = None) -> int:
     """The fewest samples a row may have: two frames must be left after the TDNN layers, since statistics pooling takes the unbiased
     deviation over them (one frame: NaN in torch).  5200 samples = 16 encoder frames with the default geometry.  Host integers."""
-    c = _c_config(config or WavLMConfig())
-    n = int(_lib.load().dex_wavlm_min_samples(C.byref(c)))
-    if n < 0:
-        raise ValueError("min_samples: bad geometry")
-    return n
+    return _HOST.min_samples(config)
 
 
 def relative_position_buckets(n: int, config: Optional[WavLMConfig] = None) -> np.ndarray:
@@ -137,13 +132,7 @@ def _ignored(key: str) -> bool:
 def state_dict_shapes(config: Optional[WavLMConfig] = None) -> dict:
     """The HF state-dict keys the network of ``config`` needs, with their shapes (weight norm in its ``weight_g`` / ``weight_v``
     spelling); ``NotImplementedError`` naming the field for a config outside the family that is built.  Host only."""
-    lib, h = _lib.load(), C.c_void_p()
-    if lib.dex_wavlm_create(C.byref(_c_config(config or WavLMConfig())), C.byref(h)) != _lib.DEX_OK:
-        raise NotImplementedError(f"WavLMConfig.{lib.dex_wavlm_last_error(None).decode()}")
-    try:
-        return weight_shapes(lib, "dex_wavlm", h)
-    finally:
-        lib.dex_wavlm_destroy(h)
+    return _HOST.state_dict_shapes(config)
 
 
 def route_state_dict(sd, want: dict, strict: bool = True):
@@ -156,14 +145,7 @@ def route_state_dict(sd, want: dict, strict: bool = True):
 def check_lengths(lengths, n_samples: int, config: Optional[WavLMConfig] = None, what: str = "wavlm") -> int:
     """What one call refuses, before anything is enqueued: a row below ``min_samples`` (``ValueError`` 'too short') and a padded
     length of more than ``MAX_FRAMES`` encoder frames.  Returns the frames of ``n_samples``.  Host only."""
-    need = min_samples(config)
-    short = [int(v) for v in lengths if v < need]
-    if short:
-        raise ValueError(f"{what}: {short[0]} samples are too short: statistics pooling needs two TDNN frames ({need} samples)")
-    T = num_frames(n_samples, config)
-    if T > MAX_FRAMES:
-        raise ValueError(f"{what}: {n_samples} samples are {T} encoder frames; one call takes at most {MAX_FRAMES}")
-    return T
+    return _HOST.check_lengths(lengths, n_samples, config, what, "statistics pooling needs two TDNN frames ({need} samples)", MAX_FRAMES)
 
 
 class WavLMXVector(WaveformNet):
@@ -176,23 +158,18 @@ class WavLMXVector(WaveformNet):
     _no_workspace = f"too short for two TDNN frames, or more than one call takes ({MAX_FRAMES} encoder frames)"
     _c_config = staticmethod(_c_config)
     _ignored = staticmethod(_ignored)
+    _check_lengths = staticmethod(check_lengths)
 
     def __init__(self, config: Optional[WavLMConfig] = None, device="cuda", do_normalize: bool = False):
         super().__init__(config or WavLMConfig(), device)
         self.do_normalize = bool(do_normalize)
-
-    def _inputs(self, wav, lengths, what: str):
-        x, ln, one = self._rows(wav, lengths, what)
-        return x, ln, one, check_lengths(ln, x.shape[1], self.config, what)
 
     def hidden_states(self, wav: torch.Tensor, lengths=None) -> torch.Tensor:
         """Raw 16 kHz samples [B, n] (or [n]), row b ``lengths[b]`` samples (what is stored past them reaches no result) -> the hidden
         states the x-vector head reads, [B, T, hidden] with T = ``num_frames(n)``: the softmax(``layer_weights``)-weighted sum of
         the encoder's L + 1 hidden states (``use_weighted_layer_sum``) or the last one.  Row b fills ``num_frames(lengths[b])``
         frames and is 0 past them; it is bitwise the row alone."""
-        x, ln, one, T = self._inputs(wav, lengths, "WavLMXVector.hidden_states")
-        out = torch.empty(x.shape[0], T, self.config.hidden_size, dtype=torch.float32, device=self.device)
-        return self._run("hidden", x, ln, out, int(self.do_normalize), out.data_ptr(), one=one)
+        return self._hidden(wav, lengths)
 
     def forward(self, input_values: torch.Tensor, lengths=None) -> torch.Tensor:
         """``WavLMForXVector.forward(input_values).embeddings`` of every row alone: [B, n] (or [n]) -> [B, xvector_output_dim] (or
@@ -207,20 +184,12 @@ class WavLMXVector(WaveformNet):
         """``wavs`` [B, n] with ``lengths``, or a list of wavs (float, or int16 scaled by 1 / 32768), at ``sr`` Hz -> embeddings
         [B, xvector_output_dim] in one network call.  Where ``sr`` is not 16000 the wavs are resampled by ``wavprep.resample``
         (kaiser_best; librosa uses soxr)."""
-        if isinstance(wavs, torch.Tensor) and wavs.dim() != 2:
-            raise ValueError(f"WavLMXVector.embed_utterances: expected wavs [B, n] or a list, got {tuple(wavs.shape)}")
-        return self.forward(*self._at_16k(wavs, lengths, sr, "WavLMXVector.embed_utterances"))
-
-
-def _model(model, what: str) -> WavLMXVector:
-    if not isinstance(model, WavLMXVector):
-        raise ValueError(f"{what}: pass model=WavLMXVector(...) with the checkpoint's weights loaded (the library ships none)")
-    return model
+        return self.forward(*self._utterances(wavs, lengths, sr, "WavLMXVector.embed_utterances"))
 
 
 def _pair(what, model, syn, syn_lengths, syn_sr, trg, trg_lengths, trg_sr) -> torch.Tensor:
     """Both sides at 16 kHz, stacked as 2 B rows, embedded in ONE call -> cos [B] (``dex_spk_cosine``)."""
-    model = _model(model, what)
+    model = WavLMXVector._model(model, what)
 
     def at_16k(x, ln, sr):
         x, ln, _ = device_rows(x, ln, what, refuse=ValueError)
@@ -245,7 +214,7 @@ def score_synthesis(model, audio, ref_wavs, sr: int = 22050, ref_sr: Optional[in
     Hz, default ``sr``) -> (cos [B] on the device, mean, stderr)."""
     if len(audio) != len(ref_wavs) or len(audio) < 1:
         raise ValueError(f"score_synthesis: {len(audio)} waveforms against {len(ref_wavs)} reference wavs")
-    model = _model(model, "score_synthesis")
+    model = WavLMXVector._model(model, "score_synthesis")
     syn, sl = pad_wavs(audio, model.device, scale_int16=True)
     trg, tl = pad_wavs(ref_wavs, model.device, scale_int16=True)
     cos = _pair("score_synthesis", model, syn, sl, sr, trg, tl, ref_sr or sr)
