@@ -1583,9 +1583,12 @@ void launch_dit_rowchain(const DitChainP& p, hipStream_t st) {
         const int tiles = p.B * ((p.rows_per_batch + RC_ROWS - 1) / RC_ROWS);
         const int xc = p.xlocal ? (p.xcds >= 1 && p.xcds <= 8 ? p.xcds : 8) : 8;
         const dim3 gridc((p.xlocal ? (tiles + xc - 1) / xc * 8 : tiles) * DIT_CLUSTER);
-        if (p.qkv_only) hipLaunchKernelGGL((dit_rowchain_cluster_kernel<true, false>), gridc, dim3(RC_NW * 64), RC_LDS_CLUSTER, st, p);
-        else if (p.xdrop == 2) {        // tests only: L2-scope hand-offs between members dealt to DIFFERENT XCDs - must end as an error, never as a mel
+        if (p.qkv_only) {
+            g_last_symbol = "dit_rowchain_cluster_kernel<true,false>";
+            hipLaunchKernelGGL((dit_rowchain_cluster_kernel<true, false>), gridc, dim3(RC_NW * 64), RC_LDS_CLUSTER, st, p);
+        } else if (p.xdrop == 2) {        // tests only: L2-scope hand-offs between members dealt to DIFFERENT XCDs - must end as an error, never as a mel
             DitChainP q = p; q.xlocal = 0;
+            g_last_symbol = "dit_rowchain_cluster_kernel<false,true>";
             hipLaunchKernelGGL((dit_rowchain_cluster_kernel<false, true>), dim3(tiles * DIT_CLUSTER), dim3(RC_NW * 64), RC_LDS_CLUSTER, st, q);
         } else if (p.xlocal) {
             g_last_symbol = "dit_rowchain_cluster_kernel<false,true>";
@@ -1631,10 +1634,13 @@ void launch_dit_rowchain(const DitChainP& p, hipStream_t st) {
     if (p.attn_inline && !p.qkv_only) {
         DitChainP q = p;
         q.xcd_map = (p.B % 8 == 0 && !knob_off("DEX_XCD_MAP")) ? 1 : 0;      // 0: the plain b-major order
+        g_last_symbol = q.xcd_map ? "dit_rowchain_kernel<true> xcd_map=1" : "dit_rowchain_kernel<true> xcd_map=0";
         hipLaunchKernelGGL(dit_rowchain_kernel<true>, grid, dim3(RC_NW * 64), RC_LDS_ATTN > RC_LDS ? RC_LDS_ATTN : RC_LDS, st, q);
     }
-    else
+    else {
+        g_last_symbol = "dit_rowchain_kernel<false>";
         hipLaunchKernelGGL(dit_rowchain_kernel<false>, grid, dim3(RC_NW * 64), RC_LDS, st, p);
+    }
 }
 
 // fp32 [K][N] -> bf16 in MFMA B-fragment order: dst[((nt * K/16 + ks) * 64 + lane) * 8 + j] =

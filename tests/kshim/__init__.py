@@ -16,7 +16,12 @@ ERRORS = {-1: "precision", -2: "null pointer", -3: "shape", -4: "unsupported by 
           -6: "stride / offset"}
 PREDICATES = {"conv3x3_bf16_supported": 0, "conv3x3_bf16_tail_supported": 1, "conv3x3_bf16_res_supported": 2,
               "conv3x3_bf16_xb_supported": 3, "conv3x3_plain_lp_in_supported": 4, "conv3x3_cat_lp_in_supported": 5,
-              "conv3x3_res2_form": 6, "conv_down_supported": 7, "convt_up_supported": 8}
+              "conv3x3_res2_form": 6, "conv_down_supported": 7, "convt_up_supported": 8, "dit_rowchain_supported": 9,
+              "dit_rowchain64_form": 10, "dit_rowchain_cluster_form": 11, "dit_rowchain_cluster_local_fits": 12,
+              "dit_rowchain_cluster_xcds": 13}
+DIT_CLUSTER = 4                                  # csrc/kernels.h
+DIT_CLUSTER_SLAB_FLOATS = 2 * DIT_CLUSTER * (32 * 256 + 256)
+DIT_CLUSTER_FLAG_WORDS = 2 * DIT_CLUSTER
 GN_SLOTS = 32
 
 
@@ -55,6 +60,15 @@ class KsAttn(C.Structure):
                 + _ints("N", "Npad", "B", "ksplit", "o_lp", "tail_g", "tail_ks", "half_g", "half_n", "precision"))
 
 
+class KsRowChain(C.Structure):
+    _fields_ = (_ptrs("X", "O", "ml", "Wp", "W1", "W2", "Wq", "bp", "b1", "b2", "bq", "ada", "next_shift", "next_scale", "Qh", "Kh", "Vt",
+                      "Qin", "Kin", "Vin", "xslab", "xflag")
+                + [("o_sstride", C.c_int64), ("next_step_stride", C.c_int64)]
+                + _ints("precision", "B", "N", "Npad", "ksplit", "qkv_only", "attn_inline", "step", "row_bstride", "o_lp", "tail_row0",
+                        "tail_ks", "xlocal")
+                + [("epoch", C.c_uint32), ("qscale", C.c_float)])
+
+
 ATTN_PLANS = {"attention_direct_batch_regime": 0, "attention_direct_ksplit": 1, "attention_q64_ksplit": 2}
 _lib = None
 
@@ -69,7 +83,7 @@ def load():
     dexlib.load()                                     # torch's HIP runtime, then the library the shim links against
     lib = C.CDLL(LIB_PATH)
     lib.ks_struct_bytes.restype, lib.ks_struct_bytes.argtypes = C.c_int, [C.c_int]
-    for k, T in enumerate((KsConv3, KsConvDown, KsConvTUp, KsAttn)):
+    for k, T in enumerate((KsConv3, KsConvDown, KsConvTUp, KsAttn, KsRowChain)):
         if lib.ks_struct_bytes(k) != C.sizeof(T):
             raise RuntimeError(f"descriptor {T.__name__}: {C.sizeof(T)} bytes here, {lib.ks_struct_bytes(k)} in the shim")
     lib.ks_predicate.restype, lib.ks_predicate.argtypes = C.c_int, [C.c_int] * 8
@@ -77,7 +91,7 @@ def load():
     lib.ks_pack.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p]
     lib.ks_attn_plan.restype, lib.ks_attn_plan.argtypes = C.c_int, [C.c_int] * 5
     for name, T in (("ks_conv3x3", KsConv3), ("ks_conv_down", KsConvDown), ("ks_convt_up", KsConvTUp), ("ks_attn_direct", KsAttn),
-                    ("ks_attn_q64", KsAttn)):
+                    ("ks_attn_q64", KsAttn), ("ks_dit_rowchain", KsRowChain)):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = C.c_int, [C.POINTER(T), C.c_void_p, C.c_char_p, C.c_int]
     lib.ks_conv3x3_strip_form.restype, lib.ks_conv3x3_strip_form.argtypes = C.c_int, [C.POINTER(KsConv3)]
@@ -98,6 +112,12 @@ def _stream():
 def predicate(name, prec, *args):
     a = list(args) + [0] * (6 - len(args))
     return bool(_check(load().ks_predicate(PREDICATES[name], PREC[prec], *a), name))
+
+
+def predicate_int(name, prec, *args):
+    """A predicate that answers with a count (dit_rowchain_cluster_xcds)."""
+    a = list(args) + [0] * (6 - len(args))
+    return _check(load().ks_predicate(PREDICATES[name], PREC[prec], *a), name)
 
 
 def _need(t, nbytes, name):
@@ -246,3 +266,55 @@ def attn_q64(prec, tensors, *, N, Npad, B, ksplit=1, o_sstride, o_lp=False, tail
     plan launched: "attn_q64_kernel nunits=.. grid=.. ks=.. tail_g=.. tail_ks=.. half_g=.. half_n=.. xcd_mode=.."."""
     return _attn("ks_attn_q64", prec, tensors, N=N, Npad=Npad, B=B, ksplit=ksplit, o_sstride=o_sstride, o_lp=o_lp, tail_g=tail_g,
                  tail_ks=tail_ks, half_g=half_g, half_n=half_n)
+
+
+def cluster_grid_tiles(prec, N, B, xlocal):
+    """Clusters launch_dit_rowchain grids for: the row tiles, padded to whole rounds over the XCDs in use for XCD-local launches."""
+    tiles = B * ((N + 31) // 32)
+    if not xlocal:
+        return tiles
+    xc = predicate_int("dit_rowchain_cluster_xcds", prec, N, B)
+    return (tiles + xc - 1) // xc * 8
+
+
+def dit_rowchain(prec, t, *, B, N, Npad, ksplit=0, o_sstride=0, qkv_only=False, attn_inline=False, step=0, row_bstride=0, o_lp=False,
+                 tail_row0=0, tail_ks=0, next_step_stride=0, qscale=1.0, epoch=0, xlocal=False):
+    """One launch_dit_rowchain (DitChainP, csrc/kernels.h).  t: tensors by descriptor member name (absent / None = null): X fp32
+    [B * N][256]; O fp32 slots (16-bit rows in slot 0 when o_lp), ml; Wp / W1 / W2 / Wq from pack("frag", ..) (the split mode's lo half
+    behind the hi half); bp, b1, b2, bq; ada [steps][6 * 256]; next_shift / next_scale rows of next_step_stride floats; Qh / Kh / Vt
+    (written) and Qin / Kin / Vin (read by the in-kernel attention), B * 2 * Npad * 128 16-bit each; xslab, and xflag whose last word
+    is xerr.  Returns the instantiation the launcher picked."""
+    if min(B, N, Npad) <= 0 or min(ksplit, tail_ks, tail_row0, o_sstride, step, row_bstride, next_step_stride, epoch) < 0:
+        raise ShimError("dit_rowchain: negative or empty extent")
+    split = 2 if prec == "fp16x2" else 1
+    rows = step + (B - 1) * row_bstride + 1                  # rows of the conditioning tables the launch reads
+    slots = 1 + tail_ks if tail_ks > 1 else max(ksplit, 1)
+    opnd = B * 2 * Npad * 128 * 2
+    gt = cluster_grid_tiles(prec, N, B, xlocal) if t.get("xflag") is not None else 0
+    sizes = {"X": B * N * 256 * 4,
+             "O": B * N * 256 * 2 if (o_lp and slots == 1) else ((slots - 1) * o_sstride + B * N * 256) * 4,
+             "ml": max(ksplit, tail_ks) * B * 2 * N * 2 * 4,
+             "Wp": 256 * 256 * split * 2, "W1": 256 * 512 * split * 2, "W2": 512 * 256 * split * 2, "Wq": 256 * 768 * split * 2,
+             "bp": 256 * 4, "b1": 512 * 4, "b2": 256 * 4, "bq": 768 * 4, "ada": rows * 6 * 256 * 4,
+             "next_shift": ((rows - 1) * next_step_stride + 256) * 4, "next_scale": ((rows - 1) * next_step_stride + 256) * 4,
+             "Qh": opnd, "Kh": opnd, "Vt": opnd, "Qin": opnd, "Kin": opnd, "Vin": opnd,
+             "xslab": B * ((N + 31) // 32) * DIT_CLUSTER_SLAB_FLOATS * 4, "xflag": (gt * DIT_CLUSTER_FLAG_WORDS + 1) * 4}
+    d = KsRowChain()
+    for name in t:
+        if name not in sizes:
+            raise ShimError(f"dit_rowchain: unknown tensor {name}")
+    for name, nbytes in sizes.items():
+        setattr(d, name, _need(t.get(name), nbytes, name))
+    for n in ("Qh", "Kh", "Vt", "Qin", "Kin", "Vin"):
+        if t.get(n) is not None and t[n].dtype != LP_DTYPE[prec]:
+            raise ShimError(f"dit_rowchain: {n} is {t[n].dtype}, the mode's operands are {LP_DTYPE[prec]}")
+    for n in ("X", "ml", "bp", "b1", "b2", "bq", "ada", "next_shift", "next_scale", "xslab"):
+        if t.get(n) is not None and t[n].dtype != torch.float32:
+            raise ShimError(f"dit_rowchain: {n} is {t[n].dtype}, not float32")
+    d.o_sstride, d.next_step_stride = o_sstride, next_step_stride
+    d.precision, d.B, d.N, d.Npad, d.ksplit, d.qkv_only, d.attn_inline = PREC[prec], B, N, Npad, ksplit, int(qkv_only), int(attn_inline)
+    d.step, d.row_bstride, d.o_lp, d.tail_row0, d.tail_ks, d.xlocal = step, row_bstride, int(o_lp), tail_row0, tail_ks, int(xlocal)
+    d.epoch, d.qscale = epoch, qscale
+    form = C.create_string_buffer(128)
+    _check(load().ks_dit_rowchain(C.byref(d), _stream(), form, 128), "dit_rowchain")
+    return form.value.decode()

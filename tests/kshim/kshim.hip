@@ -1,5 +1,5 @@
-// tests/kshim/kshim.hip — test-only launch shim: ONE launch of the reduced-precision convolution kernels and of the fragment-operand
-// softmax attention kernels of libdexamd.so from a flat descriptor (tests/kshim/__init__.py mirrors the structs with ctypes).  Host
+// tests/kshim/kshim.hip — test-only launch shim: ONE launch of the reduced-precision convolution kernels, of the fragment-operand
+// softmax attention kernels and of the fused DiT row chain of libdexamd.so from a flat descriptor (tests/kshim/__init__.py mirrors the structs with ctypes).  Host
 // code only, no kernels: every entry point fills the library's parameter struct by member name, sets the split-weight flag as
 // dex_api.hip does for a call, runs the library's own launcher on the given stream and returns the instantiation it picked
 // (dex::g_last_symbol; the attention launchers leave none: their entries return the kernel and the plan, recomputed here).
@@ -63,14 +63,28 @@ struct KsAttn {               // mirrors AttnDirectP (csrc/kernels.h); xcd_map, 
     int N, Npad, B, ksplit, o_lp, tail_g, tail_ks, half_g, half_n, precision;
 };
 
+// mirrors DitChainP (csrc/kernels.h).  heads = 2, M = B * N, xcd_map and xcds are the launcher's / dex_api.hip's own; there is no
+// hand-off drop knob here (xdrop is always 0).  A null next_shift is the last block (no qkv stage); xslab / xflag given = the cluster
+// form, whose xerr word is the one behind the flag words of every cluster the launch grids for.
+struct KsRowChain {
+    void* X; const void *O, *ml, *Wp, *W1, *W2, *Wq, *bp, *b1, *b2, *bq, *ada, *next_shift, *next_scale;
+    void *Qh, *Kh, *Vt; const void *Qin, *Kin, *Vin; void *xslab, *xflag;
+    long long o_sstride, next_step_stride;
+    int precision, B, N, Npad, ksplit, qkv_only, attn_inline, step, row_bstride, o_lp, tail_row0, tail_ks, xlocal;
+    unsigned epoch; float qscale;
+};
+
 int ks_struct_bytes(int which) {
-    return which == 0 ? (int)sizeof(KsConv3) : which == 1 ? (int)sizeof(KsConvDown) : which == 2 ? (int)sizeof(KsConvTUp) : (int)sizeof(KsAttn);
+    return which == 0 ? (int)sizeof(KsConv3) : which == 1 ? (int)sizeof(KsConvDown) : which == 2 ? (int)sizeof(KsConvTUp)
+         : which == 3 ? (int)sizeof(KsAttn) : (int)sizeof(KsRowChain);
 }
 
 // ---- shape predicates of the library, for the mode `precision` -------------------------------------------------------------
 // which: 0 conv3x3_bf16_supported(a, b)   1 conv3x3_bf16_tail_supported(a)   2 conv3x3_bf16_res_supported(a, b)
 //        3 conv3x3_bf16_xb_supported(a, b)   4 conv3x3_plain_lp_in_supported(a, b, c, d, e)   5 conv3x3_cat_lp_in_supported(a, b, c, d, e)
 //        6 conv3x3_res2_form(a, b, c)   7 conv_down_supported(a, b, c, d, e, f)   8 convt_up_supported(a, b, c, d, e)
+//        9 dit_rowchain_supported(a, b)   10 dit_rowchain64_form(a, b, c)   11 dit_rowchain_cluster_form(a, b)
+//        12 dit_rowchain_cluster_local_fits(a, b)   13 dit_rowchain_cluster_xcds(a, b) (a count, not a truth value)
 int ks_predicate(int which, int precision, int a, int b, int c, int d, int e, int f) {
     if (!lp_prec(precision)) return KS_E_PREC;
     WsplitScope ws(precision);
@@ -84,6 +98,11 @@ int ks_predicate(int which, int precision, int a, int b, int c, int d, int e, in
         case 6: return conv3x3_res2_form(a, b, c);
         case 7: return conv_down_supported(a, b, c, d, e, f);
         case 8: return convt_up_supported(a, b, c, d, e);
+        case 9: return dit_rowchain_supported(a, b);
+        case 10: return dit_rowchain64_form(a, b, c);
+        case 11: return dit_rowchain_cluster_form(a, b);
+        case 12: return dit_rowchain_cluster_local_fits(a, b);
+        case 13: return dit_rowchain_cluster_xcds(a, b);
     }
     return KS_E_SHAPE;
 }
@@ -334,6 +353,74 @@ int ks_attn_q64(const KsAttn* d, void* stream, char* form, int form_len) {
     if (form && form_len > 0)
         snprintf(form, (size_t)form_len, "attn_q64_kernel nunits=%ld grid=%ld ks=%d tail_g=%d tail_ks=%d half_g=%d half_n=%d xcd_mode=%d",
                  nunits, nunits < 256 ? nunits : 256L, ks, tg, tks, hg, hn, xcd_mode);
+    return KS_OK;
+}
+
+// ---- fused DiT row chain (dit_rowchain.hip) -------------------------------------------------------------------------------------
+// One launch_dit_rowchain.  Every descriptor the launcher would run on another form than the members ask for, and every one the
+// kernels' index arithmetic does not cover, is an error code.  form: g_last_symbol (the launcher names every branch).
+int ks_dit_rowchain(const KsRowChain* d, void* stream, char* form, int form_len) {
+    if (!d) return KS_E_NULL;
+    if (!lp_prec(d->precision)) return KS_E_PREC;
+    WsplitScope ws(d->precision);
+    if (!dit_rowchain_supported(256, 512)) return KS_E_UNSUPPORTED;
+    if (d->N <= 0 || d->B <= 0 || d->N > (1 << 16) || d->B > (1 << 12) || d->step < 0 || d->row_bstride < 0) return KS_E_SHAPE;
+    if (d->Npad % 32 != 0 || d->Npad < (d->N + 31) / 32 * 32) return KS_E_SHAPE;
+    if (d->ksplit < 0 || d->ksplit > 8 || d->tail_ks < 0 || d->tail_ks > 8) return KS_E_SHAPE;
+    const bool has_q = d->next_shift != nullptr;
+    const bool chain = !d->qkv_only;
+    if (!d->X || !d->ada) return KS_E_NULL;
+    if (d->qkv_only && (!has_q || d->attn_inline)) return KS_E_FORM;
+    if (has_q) { if (!d->next_scale || !d->Wq || !d->bq || !d->Qh || !d->Kh || !d->Vt) return KS_E_NULL; if (d->next_step_stride < 0 || d->next_step_stride % 4 != 0) return KS_E_STRIDE; }
+    else if (d->next_scale || d->Wq || d->bq) return KS_E_FORM;
+    if (chain && (!d->Wp || !d->W1 || !d->W2 || !d->bp || !d->b1 || !d->b2)) return KS_E_NULL;
+    if (chain && d->attn_inline && (!d->Qin || !d->Kin || !d->Vin)) return KS_E_NULL;
+    if (chain && d->attn_inline && (d->ksplit > 1 || d->o_lp || d->tail_ks > 1)) return KS_E_FORM;
+    const bool sep = chain && !d->attn_inline;
+    if (sep) {
+        if (!d->O) return KS_E_NULL;
+        if ((d->ksplit > 1 || d->tail_ks > 1) && !d->ml) return KS_E_NULL;
+        if (d->o_sstride < (long long)d->B * d->N * 256) return KS_E_STRIDE;
+    }
+    const bool form64 = dit_rowchain64_form(d->N, d->B, d->attn_inline);
+    if (d->o_lp && (!sep || d->ksplit > 1 || !form64)) return KS_E_FORM;          // 16-bit O rows: the 64-row form, one key split
+    if (d->tail_ks > 1) {                                                            // the tail merge: the round-3 64-row kernel only
+        if (!sep || !form64 || d->ksplit > 1) return KS_E_FORM;
+        if (d->tail_row0 <= 0 || d->tail_row0 % 64 != 0 || d->tail_row0 >= d->N) return KS_E_SHAPE;
+    } else if (d->tail_row0 != 0 || d->tail_ks == 1) return KS_E_SHAPE;
+    const bool slabs = d->xslab || d->xflag;
+    if (slabs) {
+        if (!d->xslab || !d->xflag) return KS_E_NULL;
+        if (!(d->attn_inline || d->qkv_only) || !dit_rowchain_cluster_form(d->N, d->B)) return KS_E_FORM;
+        if (d->epoch == 0) return KS_E_SHAPE;
+        if (d->xlocal && d->epoch >= (1u << 24)) return KS_E_SHAPE;
+        if (d->xlocal && !dit_rowchain_cluster_local_fits(d->N, d->B)) return KS_E_UNSUPPORTED;
+    } else if (d->xlocal || d->epoch) return KS_E_FORM;
+
+    DitChainP p{};
+    p.O = (const float*)d->O; p.ksplit = d->ksplit; p.o_sstride = (long)d->o_sstride; p.ml = (const float*)d->ml; p.heads = 2;
+    p.rows_per_batch = d->N; p.X = (float*)d->X;
+    p.Wp = d->Wp; p.W1 = d->W1; p.W2 = d->W2; p.Wq = d->Wq;
+    p.bp = (const float*)d->bp; p.b1 = (const float*)d->b1; p.b2 = (const float*)d->b2; p.bq = (const float*)d->bq;
+    p.ada = (const float*)d->ada; p.next_shift = (const float*)d->next_shift; p.next_scale = (const float*)d->next_scale;
+    p.next_step_stride = (long)d->next_step_stride;
+    p.Qh = d->Qh; p.Kh = d->Kh; p.Vt = d->Vt; p.Npad = d->Npad; p.qscale = d->qscale;
+    p.Qin = d->Qin; p.Kin = d->Kin; p.Vin = d->Vin;
+    p.qkv_only = d->qkv_only ? 1 : 0; p.attn_inline = d->attn_inline ? 1 : 0;
+    p.step = d->step; p.M = d->B * d->N; p.B = d->B; p.dbg = nullptr;
+    p.o_lp = d->o_lp ? 1 : 0; p.xcd_map = 0; p.xdrop = 0;
+    p.tail_row0 = d->tail_row0; p.tail_ks = d->tail_ks; p.row_bstride = d->row_bstride;
+    if (slabs) {
+        const long tiles = (long)d->B * ((d->N + 31) / 32);
+        p.xcds = dit_rowchain_cluster_xcds(d->N, d->B);
+        p.xlocal = d->xlocal ? 1 : 0;
+        const long grid_tiles = p.xlocal ? (tiles + p.xcds - 1) / p.xcds * 8 : tiles;      // the clusters launch_dit_rowchain grids for
+        p.xslab = (float*)d->xslab; p.xflag = (unsigned*)d->xflag; p.epoch = d->epoch;
+        p.xerr = reinterpret_cast<int*>((unsigned*)d->xflag + grid_tiles * (long)DIT_CLUSTER_FLAG_WORDS);
+    }
+    g_last_symbol = nullptr;
+    launch_dit_rowchain(p, d->precision, (hipStream_t)stream);
+    put_symbol(form, form_len);
     return KS_OK;
 }
 

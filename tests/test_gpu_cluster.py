@@ -1,7 +1,8 @@
 """The cluster form of the fused DiT block (dit_rowchain_cluster_kernel): four workgroups per 32-row tile exchange split-K partial
 sums inside ONE launch (write-through stores + flags).  What can go wrong is visibility — a stale slab or flag — so the tests
 hammer it: many back-to-back calls must be bitwise identical, eager == graph replay, results equal the one-workgroup form to
-reduced-precision rounding and the oracle to the stated tolerance, and no hand-off wait ever times out."""
+reduced-precision rounding and the oracle to the stated tolerance, and no hand-off wait ever times out.
+(Accuracy of ONE cluster launch against an fp64 reference of the same operation: tests/test_gpu_rowchain_kernels.py.)"""
 import os
 
 import numpy as np
