@@ -266,6 +266,21 @@ SYMBOLS = [
                                    C.c_void_p]),
     ("dex_wavlm_embed", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                   C.c_void_p]),
+    ("dex_ecapa_create", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("dex_ecapa_destroy", None, [C.c_void_p]),
+    ("dex_ecapa_last_error", C.c_char_p, [C.c_void_p]),
+    ("dex_ecapa_load", C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
+    ("dex_ecapa_finalize", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("dex_ecapa_num_weights", C.c_int, [C.c_void_p]),
+    ("dex_ecapa_weight_info", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    ("dex_ecapa_num_frames", C.c_int, [C.c_void_p, C.c_int]),
+    ("dex_ecapa_min_samples", C.c_int, [C.c_void_p]),
+    ("dex_ecapa_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    ("dex_ecapa_hidden", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                   C.c_void_p]),
+    ("dex_ecapa_embed", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                  C.c_void_p]),
+    ("dex_ecapa_res2", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("dex_mos_create", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     ("dex_mos_destroy", None, [C.c_void_p]),
     ("dex_mos_last_error", C.c_char_p, [C.c_void_p]),

@@ -1,5 +1,5 @@
-// wav_encoder.h — the kernels the waveform networks of the C ABI share (asr.hip: wav2vec 2.0 CTC; wavlm.hip: WavLM x-vector; mos.hip:
-// UTMOS; whisper.hip: the Whisper encoder) and their launches: the input normalisation, the ragged-batch plan, row LayerNorm, the
+// wav_encoder.h — the kernels the waveform networks of the C ABI share (asr.hip: wav2vec 2.0 CTC; wavlm.hip: WavLM x-vector; ecapa.hip:
+// WavLM-large + ECAPA-TDNN; mos.hip: UTMOS; whisper.hip: the Whisper encoder) and their launches: the input normalisation, the ragged-batch plan, row LayerNorm, the
 // weight packing (weight norm folded in fp64), the k-split sum of fc2, the host wrappers that spell a 1 x k convolution / Linear as
 // a launch of the exact-fp32 implicit GEMM, and the walk over a batch in tables of rows that travel as kernel arguments.  Every
 // per-row sum has a fixed order that does not depend on the batch.  The host layer above them (geometry, keys, packing, workspace,

@@ -1,14 +1,15 @@
-// wav_trunk.h — the host layer of the waveform networks (asr.hip: wav2vec 2.0 CTC; wavlm.hip: WavLM x-vector; mos.hip: UTMOS;
-// whisper.hip: the Whisper encoder).  Three of them run the wav2vec-family trunk: a feature extractor of 1 x k convolutions, the
-// feature projection, a grouped weight-normed positional convolution, and N encoder layers of qkv | out_proj | fc1 | fc2.  Here,
+// wav_trunk.h — the host layer of the waveform networks (asr.hip: wav2vec 2.0 CTC; wavlm.hip: WavLM x-vector; ecapa.hip: WavLM-large
+// + ECAPA-TDNN; mos.hip: UTMOS; whisper.hip: the Whisper encoder).  Four of them run the wav2vec-family trunk: a feature extractor
+// of 1 x k convolutions, the feature projection, a grouped weight-normed positional convolution, and N encoder layers of
+// qkv | out_proj | fc1 | fc2.  Here,
 // once: the trunk's geometry (Trunk) with its defaults and refusals, the HF key inventory in registration order, the packed weights
 // (TrunkWeights, pack_side, finalize_trunk), the shared prefix of the workspace (plan_trunk), the enqueue steps a network composes
 // its forward pass from, the encoder layer in both norm orders (enqueue_layer) with the plain self-attention over a packed q | k | v
 // (enqueue_self_attention), the argument checks of a call that takes wavs, and the entry points (Entry: the boilerplate, the
 // host-only frame counts, and the skeleton of a network call).  What differs stays with the network: its first convolution and its
-// norm, which norm order it instantiates, an attention that is not the plain one (WavLM's gated bias), and its head.  Whisper has no
-// trunk: its encoder takes the layer (LayerDims, LayerWs, TrunkWeights::Layer, pack_side) and the handle's boilerplate.  The kernels
-// are in wav_encoder.h; everything has internal linkage.
+// norm (wav_layernorm.h, wav_groupnorm.h), which norm order it instantiates, an attention that is not the plain one (WavLM's gated
+// bias, wav_gated_attn.h), and its head.  Whisper has no trunk: its encoder takes the layer (LayerDims, LayerWs,
+// TrunkWeights::Layer, pack_side) and the handle's boilerplate.  The kernels are in wav_encoder.h; everything has internal linkage.
 #pragma once
 #include <vector>
 

@@ -148,6 +148,15 @@ def sim_scores(model, audio, ref_wavs, sr: int = 22050, ref_sr: Optional[int] = 
     return wavlm.score_synthesis(model, audio, ref_wavs, sr, ref_sr)
 
 
+def ecapa_sim_scores(model, audio, ref_wavs, sr: int = 22050, ref_sr: Optional[int] = None):
+    """The WavLM-large + ECAPA-TDNN speaker similarity (the SIM-o of zero-shot TTS tables) of ``synthesize_tokens``' list of int16
+    waveforms against the reference wavs, in the same order, on the device -> (cos [B], mean, stderr).  ``model`` is an
+    ``ecapa.WavLMEcapa`` with the checkpoint's weights loaded (ecapa.py states what the score is and its departures: the row-alone
+    batching, the resampler, and that it has not been checked against the real checkpoint)."""
+    from . import ecapa
+    return ecapa.score_synthesis(model, audio, ref_wavs, sr, ref_sr)
+
+
 def mos_scores(model, audio, sr: int = 22050, domain: int = 0, judge: int = 288):
     """The UTMOS naturalness score (predicted MOS) of ``synthesize_tokens``' list of int16 waveforms (``sr`` Hz), on the device ->
     (mos [B], mean, stderr).  ``model`` is a ``mos.UTMOS`` with the checkpoint's weights loaded (mos.py states what the score is and

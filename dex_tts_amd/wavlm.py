@@ -12,8 +12,8 @@ their ``embeddings``.
 The network runs in libdexamd.so (``csrc/wavlm.hip``, C ABI ``dex_wavlm_*``), fp32 throughout: a metric has no reduced-precision mode.
 Nothing downloads: weights come from a dict or a local file the caller names, and the library ships no checkpoint.  Only this model
 family is built (group-norm feature extractor, post-layer-norm encoder, head_dim 64, erf GELU, at most 8 convolution and 8 TDNN
-layers); any other config raises ``NotImplementedError`` naming the field.  It is NOT the WavLM-large + ECAPA-TDNN verification model
-some papers use for SIM.
+layers); any other config raises ``NotImplementedError`` naming the field.  The WavLM-large + ECAPA-TDNN verification model
+most SIM-o tables use is another network: ``dex_tts_amd/ecapa.py``.
 
 What a caller comparing numbers must know:
   * batching: row b of any batch is the network applied to row b ALONE at its own length.  HF with a zero-padded batch and no

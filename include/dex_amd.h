@@ -679,6 +679,66 @@ int  dex_wavlm_hidden(DexWavlm* w, const float* wav_dev, const int32_t* lengths_
 int  dex_wavlm_embed(DexWavlm* w, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, int do_normalize,
                      float* embed_dev, void* workspace_dev, size_t workspace_bytes, dex_stream_t stream);
 
+/* ---- WavLM-large + ECAPA-TDNN speaker similarity (the SIM-o of zero-shot TTS tables): HF's WavLMModel of the large family
+ * (layer-norm feature extractor, stable-layer-norm encoder, head_dim 64, gated relative-position bias; all n_layers + 1 hidden states)
+ * feeding the ECAPA-TDNN head of the UniSpeech speaker-verification recipe (softmax(feature_weight) layer mix, InstanceNorm1d, three
+ * SE-Res2 blocks, attentive statistics pooling, BatchNorm, Linear), eval mode, fp32.  Written down from a reading of the public
+ * code and NOT checked against the real checkpoint.  Row b of a batch is the network applied to row b alone at its own length: every
+ * statistic and every convolution's zero padding end at the row's own frames.  The cosine of two embeddings is dex_spk_cosine.
+ * Lengths are HOST arrays; bad arguments return an error code, with a message in the handle's last error, before anything is
+ * enqueued.  No compute call synchronises or allocates.  One call takes rows of at most DEX_ECAPA_MAX_FRAMES encoder frames; every
+ * row needs two (dex_ecapa_min_samples: the instance norm over one frame is undefined). */
+typedef struct DexEcapa DexEcapa;
+#define DEX_ECAPA_MAX_CONV 8
+#define DEX_ECAPA_MAX_FRAMES 4096
+#define DEX_ECAPA_BLOCKS 3
+#define DEX_ECAPA_RES2_TILE 72                        /* frames one workgroup of the Res2 chain stores */
+typedef struct {
+    int32_t n_conv;                                   /* feature-extractor layers (7) */
+    int32_t conv_dim[DEX_ECAPA_MAX_CONV], conv_kernel[DEX_ECAPA_MAX_CONV], conv_stride[DEX_ECAPA_MAX_CONV];
+    int32_t conv_bias;                                /* 1 in wavlm-large */
+    int32_t feat_extract_norm_layer;                  /* 1 = 'layer' (the only one built) */
+    int32_t hidden, n_layers, n_heads, intermediate;
+    int32_t do_stable_layer_norm;                     /* 1 (the only one built) */
+    int32_t num_conv_pos_embeddings, num_conv_pos_embedding_groups;
+    float   layer_norm_eps;
+    int32_t num_buckets, max_bucket_distance;         /* relative-position buckets (320, 800) */
+    int32_t channels, emb_dim;                        /* ECAPA_TDNN(channels = 512, emb_dim = 256) */
+    int32_t res2_scale;                               /* 8 (the only one built); channels / 8 must be 32 or 64 */
+    int32_t se_bottleneck_dim, attention_channels;    /* 128, 128 */
+    int32_t global_context_att;                       /* 1: the pooling's attention also reads each channel's mean and deviation over time */
+    int32_t dilations[DEX_ECAPA_BLOCKS];              /* of the three SE-Res2 blocks (2, 3, 4), each 1 .. 4 */
+} DexEcapaConfig;
+/* NULL = the wavlm-large / ECAPA_TDNN(512, 256) values.  DEX_ERR_ARG (and *out = NULL) for a config outside the family that is built. */
+int  dex_ecapa_create(const DexEcapaConfig* cfg, DexEcapa** out);
+void dex_ecapa_destroy(DexEcapa* e);
+const char* dex_ecapa_last_error(const DexEcapa* e);
+/* one weight under its key: the trunk's HF keys under wavlm. (the positional convolution as weight_g / weight_v), then the head's
+ * UniSpeech names: feature_weight, layer1.{conv,bn}.*, layerN.{Conv1dReluBn1,Conv1dReluBn2}.{conv,bn}.*, layerN.Res2Conv1dReluBn.
+ * {convs,bns}.i.*, layerN.SE_Connect.linear{1,2}.*, conv.*, pooling.linear{1,2}.*, bn.*, linear.*; stream-ordered */
+int  dex_ecapa_load(DexEcapa* e, const char* key, const float* w_dev, const int64_t* shape, int ndim, dex_stream_t stream);
+/* packs the operands (weight norm and every eval-mode BatchNorm folded in fp64, the layer weights' softmax, the bucket table) */
+int  dex_ecapa_finalize(DexEcapa* e, dex_stream_t stream);
+int  dex_ecapa_num_weights(const DexEcapa* e);
+int  dex_ecapa_weight_info(const DexEcapa* e, int i, const char** key, int64_t shape[4], int* ndim);
+/* host only (NULL = default config): encoder frames of n_samples samples; the fewest samples a row may have (720: two frames) */
+int  dex_ecapa_num_frames(const DexEcapaConfig* cfg, int n_samples);
+int  dex_ecapa_min_samples(const DexEcapaConfig* cfg);
+size_t dex_ecapa_workspace_bytes(const DexEcapa* e, int B, int max_samples);     /* 0 for bad arguments */
+/* wav_dev [B, n_samples] raw samples, row b lengths_host[b] samples; do_normalize != 0: (x - mean) / sqrt(var + 1e-5) per row first
+ * (the upstream's F.layer_norm(wav, wav.shape)) -> hidden_dev [B, T, hidden], T = dex_ecapa_num_frames(n_samples): the
+ * softmax(feature_weight)-mixed hidden states after the head's instance norm; row b fills its own frames and 0 past them */
+int  dex_ecapa_hidden(DexEcapa* e, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, int do_normalize,
+                      float* hidden_dev, void* workspace_dev, size_t workspace_bytes, dex_stream_t stream);
+/* the same inputs -> embed_dev [B, emb_dim]: the speaker embedding of every row alone */
+int  dex_ecapa_embed(DexEcapa* e, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, int do_normalize,
+                     float* embed_dev, void* workspace_dev, size_t workspace_bytes, dex_stream_t stream);
+/* the Res2 chain of SE-Res2 block `block` (0 .. 2) alone, one launch: x_dev [B, T, channels], row b frames_host[b] frames (1 .. T)
+ * -> out_dev [B, T, channels] (not x_dev): seven dilated convolutions with ReLU and BatchNorm over the first seven channel slices,
+ * each zero-padded at the row's own ends, the eighth slice copied; 0 past a row's frames */
+int  dex_ecapa_res2(DexEcapa* e, int block, const float* x_dev, const int32_t* frames_host, int B, int T, float* out_dev,
+                    dex_stream_t stream);
+
 /* ---- UTMOS naturalness score (MOS prediction): the UTMOS22 "strong learner" in eval mode, fp32 - the wav2vec 2.0 base trunk
  * (group-norm feature extractor, post-layer-norm encoder, head_dim 64, plain softmax attention; last_hidden_state), every frame
  * conditioned on a domain and a listener embedding, a bidirectional single-layer LSTM, Linear - ReLU - Linear per frame, and
