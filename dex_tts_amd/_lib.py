@@ -111,6 +111,11 @@ class DexDenoiseBatchArgs(C.Structure):
     _fields_ = [("s", DexSampleArgs), ("x_dev", C.c_void_p), ("sigma_dev", C.c_void_p)]
 
 
+class DexWhisperBeamState(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("run_score", "pool_score", "seq_in", "seq_out", "anc_in", "anc_out", "pool_ids", "pool_len", "pool_order",
+                                          "pool_n", "done", "count")] + [("ld_seq", C.c_int32), ("ld_anc", C.c_int32)]
+
+
 # every symbol include/dex_amd.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("dex_ctx_create", C.c_int, [C.POINTER(DexConfig), C.POINTER(C.c_void_p)]),
@@ -328,6 +333,15 @@ SYMBOLS = [
                                           C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.c_void_p]),
     ("dex_whisper_pick_ts", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("dex_whisper_attend_beam", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    ("dex_whisper_beam_pick", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                        C.POINTER(DexWhisperBeamState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("dex_whisper_beam_pick_scratch_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    ("dex_whisper_beam_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    ("dex_whisper_generate_beam", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double,
+                                            C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 ]
 
 _lib = None

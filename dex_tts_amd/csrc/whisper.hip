@@ -32,6 +32,13 @@
 //                        the rule as index ranges from the row's own state (its last two ids, its last timestamp, its new-token
 //                        count, all on the device), the best text id, the best timestamp id and logsumexp(timestamps) in one pass
 //                        over the logits, reduced in a fixed order.  Both kernels end in pick_commit.
+//   wsp_attend_anc_kernel, wsp_attend_cross_beam_kernel, wsp_beam_lse_kernel, wsp_beam_top_kernel, wsp_beam_pick_kernel
+//                        beam search (U utterances of K beams = U x K rows of the step).  The self-attention form reads key t of row r
+//                        from row anc[r][t] of the cache - no cache element moves when beams are reordered - and shares its body
+//                        (attend_row) with wsp_attend_kernel; the cross form streams an utterance's K / V once for its K queries,
+//                        K score rows in LDS, per query the plain kernel's operations in the plain kernel's order; the tail is three
+//                        launches: the fp64 log-softmax sums by chunk of 2048 ids, every chunk's 2K best by score, and per
+//                        utterance the top 2K of those, the running set, the pool, the stop, the ancestry and the next embeddings.
 // Every per-row sum has an order fixed by the config and the position: a row's logits and ids are bitwise those of the row alone.
 #include <hip/hip_runtime.h>
 
@@ -267,14 +274,30 @@ __global__ __launch_bounds__(256) void wsp_finish_kernel(const FinP p) {
 struct AtP { const float* q; const float* kn; const float* vn; int KS; long ss; int ldq; const float *qbias, *kbias, *vbias;
              float* K; float* V; int ldk; long kb; int n; float* out; int ldo; float scale; };
 
-__global__ __launch_bounds__(256) void wsp_attend_kernel(const AtP p) {
+// The body of the single-query attention of row blockIdx.y, head blockIdx.x.  ANC: key t is read from row base + anc[t] of the
+// cache (the row's own at the appended position); otherwise from the row's own, and the code is that of the plain kernel
+template <bool ANC>
+__device__ __forceinline__ void attend_row(const AtP& p, const int* anc, int base, int beams) {
     __shared__ float sc[MAX_KEYS];
     __shared__ float qs[64];
     __shared__ float red[4][64];
     __shared__ float red4[4];
+    __shared__ int ancs[ANC ? MAX_KEYS : 1];         // the row's ancestry, staged once: a key's address must not wait for a global load
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = blockIdx.x, b = blockIdx.y;
     float* Kb = p.K + (long)b * p.kb + h * 64;
     float* Vb = p.V + (long)b * p.kb + h * 64;
+    if constexpr (ANC)
+        for (int j = tid; j < p.n; j += 256) ancs[j] = anc[j];
+    // the offset of key j's row from the row's own (0 without ancestry); an entry outside the utterance's beams reads the row's own
+    auto hop = [&](int j) -> long {
+        if constexpr (ANC) {
+            if (p.kn && j == p.n - 1) return 0;
+            const int a = ancs[j];
+            return a >= 0 && a < beams ? (long)(base + a - b) * p.kb : 0;
+        } else {
+            return 0;
+        }
+    };
     {
         const int c = h * 64 + lane;
         const long at = (long)b * p.ldq + c;
@@ -292,7 +315,7 @@ __global__ __launch_bounds__(256) void wsp_attend_kernel(const AtP p) {
         const int j = j0 + kk;
         float s = 0.f;
         if (j < p.n) {
-            const float4* kr = reinterpret_cast<const float4*>(Kb + (long)j * p.ldk + part * 16);
+            const float4* kr = reinterpret_cast<const float4*>(Kb + hop(j) + (long)j * p.ldk + part * 16);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const float4 k4 = kr[i];
@@ -315,10 +338,122 @@ __global__ __launch_bounds__(256) void wsp_attend_kernel(const AtP p) {
     l = block_sum256(l, red4);                       // (its barriers also publish the exponentials)
     float acc = 0.f;
 #pragma unroll 8
-    for (int j = wave; j < p.n; j += 4) acc = fmaf(sc[j], Vb[(long)j * p.ldk + lane], acc);
+    for (int j = wave; j < p.n; j += 4) acc = fmaf(sc[j], Vb[hop(j) + (long)j * p.ldk + lane], acc);
     red[wave][lane] = acc;
     __syncthreads();
     if (wave == 0) p.out[(long)b * p.ldo + h * 64 + lane] = (((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]) / l;
+}
+
+__global__ __launch_bounds__(256) void wsp_attend_kernel(const AtP p) { attend_row<false>(p, nullptr, 0, 0); }
+
+// ------------------------------------------------------------------------------------------------------------ beam attention
+// The self form: row blockIdx.y = u beams + r appends its k and v in its own row and reads the earlier positions through its ancestry
+// anc [rows][ld_anc] (beam indices within the utterance).  No cache element moves when the beams are reordered
+__global__ __launch_bounds__(256) void wsp_attend_anc_kernel(const AtP p, const int* anc, int ld_anc, int beams) {
+    const int b = blockIdx.y;
+    attend_row<true>(p, anc + (long)b * ld_anc, b / beams * beams, beams);
+}
+
+// The cross form: workgroup (head blockIdx.x, utterance blockIdx.y) streams the utterance's K / V (p.K, p.V, row stride p.kb per
+// UTTERANCE) once for its KB queries, rows u KB + q of q and out.  KB sets of scores sit in dynamic LDS [KB][n].  Per query the
+// operations and their order are those of attend_row: four lanes per key with 16 dims each, the same max and sum reductions, V
+// accumulated by wave with stride 4 - a row is bitwise the plain kernel's
+template <int KB>
+__global__ __launch_bounds__(256) void wsp_attend_cross_beam_kernel(const AtP p) {
+    extern __shared__ float scb[];                   // [KB][n]
+    __shared__ float qs[KB][64];
+    __shared__ float red[KB][4][64];
+    __shared__ float red4[KB][4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = blockIdx.x, u = blockIdx.y, n = p.n;
+    const float* Kb = p.K + (long)u * p.kb + h * 64;
+    const float* Vb = p.V + (long)u * p.kb + h * 64;
+    for (int q = wave; q < KB; q += 4) {
+        const int c = h * 64 + lane;
+        qs[q][lane] = p.scale * finished(p.q, p.KS, p.ss, (long)(u * KB + q) * p.ldq + c, p.qbias, c);
+    }
+    __syncthreads();
+    const int part = tid & 3, kk = tid >> 2;
+    float qr[KB][16];
+#pragma unroll
+    for (int q = 0; q < KB; ++q)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) qr[q][i] = qs[q][part * 16 + i];
+    // KT tiles of 64 keys per trip, all 4 KT loads of a lane issued before the first is used: the workgroups are few (heads x
+    // utterances) and each waits on HBM, so the loads in flight per lane set the pace
+    constexpr int KT = 4;
+    for (int j0 = 0; j0 < n; j0 += 64 * KT) {
+        float4 k4[KT][4];
+#pragma unroll
+        for (int t = 0; t < KT; ++t) {
+            const int j = j0 + 64 * t + kk;
+            const float4* kr = reinterpret_cast<const float4*>(Kb + (long)(j < n ? j : 0) * p.ldk + part * 16);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) k4[t][i] = kr[i];
+        }
+#pragma unroll
+        for (int t = 0; t < KT; ++t) {
+            const int j = j0 + 64 * t + kk;
+#pragma unroll
+            for (int q = 0; q < KB; ++q) {
+                float s = 0.f;
+                if (j < n) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        s = fmaf(qr[q][4 * i], k4[t][i].x, s); s = fmaf(qr[q][4 * i + 1], k4[t][i].y, s);
+                        s = fmaf(qr[q][4 * i + 2], k4[t][i].z, s); s = fmaf(qr[q][4 * i + 3], k4[t][i].w, s);
+                    }
+                }
+                s += __shfl_xor(s, 1);
+                s += __shfl_xor(s, 2);
+                if (part == 0 && j < n) scb[q * n + j] = s;
+            }
+        }
+    }
+    __syncthreads();
+    float m[KB], l[KB];
+#pragma unroll
+    for (int q = 0; q < KB; ++q) {
+        float v = -INFINITY;
+        for (int j = tid; j < n; j += 256) v = fmaxf(v, scb[q * n + j]);
+        for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+        if (lane == 0) red4[q][wave] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < KB; ++q) {
+        m[q] = fmaxf(fmaxf(red4[q][0], red4[q][1]), fmaxf(red4[q][2], red4[q][3]));
+        float v = 0.f;
+        for (int j = tid; j < n; j += 256) { const float e = expf(scb[q * n + j] - m[q]); scb[q * n + j] = e; v += e; }
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        l[q] = v;
+    }
+    __syncthreads();                                 // the maxima are read; the exponentials are published
+    if (lane == 0)
+#pragma unroll
+        for (int q = 0; q < KB; ++q) red4[q][wave] = l[q];
+    __syncthreads();
+    float acc[KB];
+#pragma unroll
+    for (int q = 0; q < KB; ++q) { l[q] = ((red4[q][0] + red4[q][1]) + red4[q][2]) + red4[q][3]; acc[q] = 0.f; }
+    constexpr int VU = 32;                            // V rows in flight per wave; a query's sum still runs over j in steps of 4
+    for (int j0 = wave; j0 < n; j0 += 4 * VU) {
+        float v[VU];
+#pragma unroll
+        for (int t = 0; t < VU; ++t) { const int j = j0 + 4 * t; v[t] = Vb[(long)(j < n ? j : 0) * p.ldk + lane]; }
+#pragma unroll
+        for (int t = 0; t < VU; ++t) {
+            const int j = j0 + 4 * t;
+            if (j < n) {
+#pragma unroll
+                for (int q = 0; q < KB; ++q) acc[q] = fmaf(scb[q * n + j], v[t], acc[q]);
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < KB; ++q) red[q][wave][lane] = acc[q];
+    __syncthreads();
+    for (int q = wave; q < KB; q += 4)
+        p.out[(long)(u * KB + q) * p.ldo + h * 64 + lane] = (((red[q][0][lane] + red[q][1][lane]) + red[q][2][lane]) + red[q][3][lane]) / l[q];
 }
 
 // ------------------------------------------------------------------------------------------------------------ greedy step tail
@@ -446,6 +581,247 @@ __global__ __launch_bounds__(1024) void wsp_pick_ts_kernel(const PickTsP q) {
         if (!force) { float bv = bt; arg = at; better(bv, arg, bs, as); }
     }
     pick_commit(p, b, arg, &chosen, tb, q.last_ts, q.n_new);
+}
+
+// ------------------------------------------------------------------------------------------------------------ beam step tail
+constexpr int KMAX = DEX_WHISPER_MAX_BEAMS;
+
+constexpr int BCH = 2048, BPT = BCH / 256;      // ids per scan workgroup, and per thread of it
+int beam_chunks(int V) { return (V + BCH - 1) / BCH; }
+
+// The tail is three launches.  C = beam_chunks(V) chunks per row.  lg (or null where P is the logits, KS = 1): the finished fp32
+// logits [U K][V].  part [U K][C][2] fp64: a chunk's maximum and sum exp(x - maximum).  cand_s (fp64) / cand_f [U K][C][2K]: a
+// chunk's 2K best scores in order and their flat indices r V + id (-1: nothing was left).  div = (step + 1)^length_penalty.  tok /
+// par / trace (or null): the step's new running set.  next_pos >= 0: h = embed_tokens + embed_positions of every row's next input
+struct BeamP { const float* P; int KS; long ss; int V, K, C; const uint8_t* mask; float* lg; double *part, *cand_s; int* cand_f;
+               int eos, step, pos, last; double div; DexWhisperBeamState s; int *tok, *par; double* trace;
+               const float *emb, *posw; int d, next_pos; float* h; };
+
+__device__ __forceinline__ void better64(double& v, int& i, double ov, int oi) {
+    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+}
+
+// chunk blockIdx.x of row blockIdx.y: the logits finished from the partials (stored where lg is given), the chunk's maximum and its
+// sum exp(x - maximum) in fp64: per thread in id order, the wave butterfly, the four waves in order
+__global__ __launch_bounds__(256) void wsp_beam_lse_kernel(const BeamP p) {
+    __shared__ float rm[4];
+    __shared__ double rs[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = blockIdx.x, row = blockIdx.y, V = p.V;
+    if (p.s.done[row / p.K]) return;
+    const long at = (long)row * V;
+    float x[BPT], m = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < BPT; ++e) {
+        const int v = c * BCH + e * 256 + tid;
+        x[e] = v < V ? finished(p.P, p.KS, p.ss, at + v, nullptr, 0) : -INFINITY;
+        if (v < V && p.lg) p.lg[at + v] = x[e];
+        m = fmaxf(m, x[e]);
+    }
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if (lane == 0) rm[wave] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(rm[0], rm[1]), fmaxf(rm[2], rm[3]));
+    double sum = 0.0;
+#pragma unroll
+    for (int e = 0; e < BPT; ++e)
+        if (c * BCH + e * 256 + tid < V && m > -INFINITY) sum += exp((double)x[e] - (double)m);
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if (lane == 0) rs[wave] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        double* o = p.part + ((long)row * p.C + c) * 2;
+        o[0] = (double)m; o[1] = ((rs[0] + rs[1]) + rs[2]) + rs[3];
+    }
+}
+
+// chunk blockIdx.x of row blockIdx.y: the row's log-softmax normaliser from its chunks in chunk order (every workgroup of the row
+// computes the same), score = running + (x - normaliser) in fp64 of the chunk's unmasked ids in registers, and 2K rounds of the
+// block-wide best in the order (score descending, flat index ascending): the chunk's 2K best, of which the row's, and the
+// utterance's, 2K best are a subset
+__global__ __launch_bounds__(256) void wsp_beam_top_kernel(const BeamP p) {
+    __shared__ double rs[4], lse;
+    __shared__ int ri[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = blockIdx.x, row = blockIdx.y, V = p.V, T = 2 * p.K;
+    if (p.s.done[row / p.K]) return;
+    if (tid == 0) {
+        const double* q = p.part + (long)row * p.C * 2;
+        double M = -INFINITY, t = 0.0;
+        for (int i = 0; i < p.C; ++i) M = fmax(M, q[2 * i]);
+        for (int i = 0; i < p.C; ++i)
+            if (q[2 * i] > -INFINITY) t += q[2 * i + 1] * exp(q[2 * i] - M);
+        lse = M + log(t);
+    }
+    __syncthreads();
+    const float* lg = (p.lg ? p.lg : p.P) + (long)row * V;
+    const double base = p.s.run_score[row], nrm = lse;
+    const int f0 = (row % p.K) * V;
+    double sc[BPT];
+#pragma unroll
+    for (int e = 0; e < BPT; ++e) {
+        const int v = c * BCH + e * 256 + tid;
+        sc[e] = v < V && !(p.mask && p.mask[v]) ? base + ((double)lg[v] - nrm) : -INFINITY;          // -inf (and NaN) never competes
+    }
+    unsigned taken = 0;
+    double* os = p.cand_s + ((long)row * p.C + c) * T;
+    int* of = p.cand_f + ((long)row * p.C + c) * T;
+    for (int j = 0; j < T; ++j) {
+        double best = -INFINITY;
+        int arg = 0x7fffffff, be = -1;
+#pragma unroll
+        for (int e = 0; e < BPT; ++e) {
+            const int flat = f0 + c * BCH + e * 256 + tid;
+            if (!((taken >> e) & 1) && (sc[e] > best || (sc[e] == best && flat < arg))) { best = sc[e]; arg = flat; be = e; }
+        }
+        const int mine = arg;
+        for (int o = 32; o > 0; o >>= 1) { const double ov = __shfl_xor(best, o); const int oi = __shfl_xor(arg, o); better64(best, arg, ov, oi); }
+        if (lane == 0) { rs[wave] = best; ri[wave] = arg; }
+        __syncthreads();
+        best = rs[0]; arg = ri[0];
+        for (int w = 1; w < 4; ++w) better64(best, arg, rs[w], ri[w]);
+        if (be >= 0 && mine == arg) taken |= 1u << be;
+        if (tid == 0) { os[j] = best; of[j] = arg == 0x7fffffff ? -1 : arg; }
+        __syncthreads();
+    }
+}
+
+// Utterance blockIdx.x (whisper.py states the rule).  2K rounds over the utterance's K x C x 2K chunk candidates, each the block-wide
+// best among those that come after the previous round's winner in the order (score descending, flat index ascending): the 2K
+// candidates in order, ties to the lowest flat index.  Thread 0 then walks them (running set, pool merge through the slot order, the
+// stop), and all threads gather the sequences and the ancestry by parent into the _out buffers, copy the pooled hypotheses into
+// their slots and gather the next step's embedding rows.  A done utterance only carries its state across
+__global__ __launch_bounds__(1024) void wsp_beam_pick_kernel(const BeamP p) {
+    __shared__ double rs[16], cs[2 * KMAX], nsc[KMAX];
+    __shared__ int ri[16], cf[2 * KMAX], npar[KMAX], nid[KMAX], pslot[KMAX], ppar[KMAX], pid[KMAX], n_pool, frozen;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, u = blockIdx.x, K = p.K, V = p.V, r0 = u * K;
+    const DexWhisperBeamState& s = p.s;
+    if (tid == 0) { frozen = s.done[u] != 0; n_pool = 0; }
+    __syncthreads();
+    if (!frozen) {
+        const int n = K * p.C * 2 * K;
+        const double* qs = p.cand_s + (long)r0 * p.C * 2 * K;
+        const int* qf = p.cand_f + (long)r0 * p.C * 2 * K;
+        for (int c = 0; c < 2 * K; ++c) {
+            const double ps = c ? cs[c - 1] : 0.0;
+            const int pf = c ? cf[c - 1] : -1;
+            double best = -INFINITY;
+            int arg = 0x7fffffff;
+            if (c == 0 || pf >= 0) {
+                for (int i = tid; i < n; i += 1024) {
+                    const int flat = qf[i];
+                    const double sc = qs[i];
+                    if (flat < 0 || (c && !(sc < ps || (sc == ps && flat > pf)))) continue;
+                    better64(best, arg, sc, flat);
+                }
+            }
+            for (int o = 32; o > 0; o >>= 1) { const double ov = __shfl_xor(best, o); const int oi = __shfl_xor(arg, o); better64(best, arg, ov, oi); }
+            if (lane == 0) { rs[wave] = best; ri[wave] = arg; }
+            __syncthreads();
+            if (tid == 0) {
+                for (int w = 1; w < 16; ++w) better64(best, arg, rs[w], ri[w]);
+                cs[c] = best; cf[c] = arg == 0x7fffffff ? -1 : arg;          // -1: nothing is left to compete
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            int pn = s.pool_n[u], nr = 0, order[KMAX];
+            for (int t = 0; t < pn; ++t) order[t] = s.pool_order[r0 + t];
+            for (int c = 0; c < 2 * K; ++c) {
+                if (cf[c] < 0) continue;
+                const int r = cf[c] / V, id = cf[c] - r * V;
+                if (!p.last && id != p.eos) {
+                    if (nr < K) { npar[nr] = r; nid[nr] = id; nsc[nr] = cs[c]; ++nr; }
+                    continue;
+                }
+                if (c >= K) continue;                                        // a finished candidate of rank >= K is dropped
+                const double sc = cs[c] / p.div;
+                int t = 0;
+                while (t < pn && !(s.pool_score[r0 + order[t]] < sc)) ++t;  // behind every entry that is at least as good
+                if (t >= K) continue;
+                const int slot = pn < K ? pn : order[K - 1];
+                for (int x = pn < K ? pn : K - 1; x > t; --x) order[x] = order[x - 1];
+                order[t] = slot;
+                if (pn < K) ++pn;
+                s.pool_score[r0 + slot] = sc;
+                s.pool_len[r0 + slot] = id == p.eos ? p.step : p.step + 1;
+                pslot[n_pool] = slot; ppar[n_pool] = r; pid[n_pool] = id; ++n_pool;
+            }
+            for (int t = 0; t < pn; ++t) s.pool_order[r0 + t] = order[t];
+            s.pool_n[u] = pn;
+            bool done = p.last != 0;
+            if (!p.last) {
+                for (; nr < K; ++nr) { npar[nr] = nr; nid[nr] = p.eos; nsc[nr] = -INFINITY; }      // only where nothing was left to compete
+                for (int x = 0; x < K; ++x) {
+                    s.run_score[r0 + x] = nsc[x];
+                    if (p.tok) { p.tok[r0 + x] = nid[x]; p.par[r0 + x] = npar[x]; }
+                    if (p.trace) p.trace[r0 + x] = nsc[x];
+                }
+                done = pn == K && nsc[0] / p.div <= s.pool_score[r0 + order[K - 1]];
+            } else {
+                frozen = 1;
+            }
+            if (done) { s.done[u] = 1; atomicAdd(s.count, 1); }
+        }
+        __syncthreads();
+    }
+    const int ls = s.ld_seq, la = s.ld_anc;
+    for (int x = 0; x < K; ++x) {
+        const int par = frozen ? x : npar[x];
+        const int* si = s.seq_in + (long)(r0 + par) * ls;
+        const int* ai = s.anc_in + (long)(r0 + par) * la;
+        int* so = s.seq_out + (long)(r0 + x) * ls;
+        int* ao = s.anc_out + (long)(r0 + x) * la;
+        if (frozen) {
+            for (int t = tid; t < ls; t += 1024) so[t] = si[t];
+            for (int t = tid; t < la; t += 1024) ao[t] = ai[t];
+        } else {
+            for (int t = tid; t < ls; t += 1024) so[t] = t < p.step ? si[t] : (t == p.step ? nid[x] : p.eos);
+            for (int t = tid; t < la; t += 1024) ao[t] = t <= p.pos ? ai[t] : x;
+        }
+    }
+    for (int e = 0; e < n_pool; ++e) {
+        const int* si = s.seq_in + (long)(r0 + ppar[e]) * ls;
+        int* po = s.pool_ids + (long)(r0 + pslot[e]) * ls;
+        for (int t = tid; t < ls; t += 1024) po[t] = t < p.step ? si[t] : (t == p.step ? pid[e] : p.eos);
+    }
+    if (p.next_pos < 0) return;
+    const float* q = p.posw + (long)p.next_pos * p.d;
+    for (int x = 0; x < K; ++x) {
+        const float* e = p.emb + (long)(frozen ? p.eos : nid[x]) * p.d;
+        for (int c = tid; c < p.d; c += 1024) p.h[(long)(r0 + x) * p.d + c] = e[c] + q[c];
+    }
+}
+
+// the state before the first step: identity ancestry in both buffers, running scores 0, -1e9, ..., empty pools, nothing done
+__global__ __launch_bounds__(256) void wsp_beam_init_kernel(const DexWhisperBeamState s, int U, int K) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x, rows = (long)U * K;
+    if (i < rows * s.ld_anc) { const int r = (int)(i / s.ld_anc); s.anc_in[i] = r % K; s.anc_out[i] = r % K; }
+    if (i < rows) { s.run_score[i] = i % K ? -1e9 : 0.0; s.pool_score[i] = -INFINITY; s.pool_len[i] = 0; s.pool_order[i] = (int)(i % K); }
+    if (i < U) { s.pool_n[i] = 0; s.done[i] = 0; }
+    if (i == 0) *s.count = 0;
+}
+
+// The best pooled hypothesis of utterance blockIdx.x -> ids [U][max_new] (eos behind it), lengths, scores; pool_* (or null): the
+// pool best first, ids [U K][max_new]
+struct BeamOutP { DexWhisperBeamState s; int K, eos, max_new; int *ids, *lengths; double* scores; int *pool_ids, *pool_len; double* pool_scores; int* pool_n; };
+__global__ __launch_bounds__(256) void wsp_beam_result_kernel(const BeamOutP p) {
+    const int u = blockIdx.x, r0 = u * p.K, pn = p.s.pool_n[u], tid = threadIdx.x;
+    for (int k = 0; k < p.K; ++k) {
+        if (k && !p.pool_ids) break;
+        const int slot = k < pn ? p.s.pool_order[r0 + k] : -1;
+        const int* src = slot >= 0 ? p.s.pool_ids + (long)(r0 + slot) * p.s.ld_seq : nullptr;
+        for (int t = tid; t < p.max_new; t += 256) {
+            const int id = src && t < p.s.ld_seq ? src[t] : p.eos;
+            if (k == 0) p.ids[(long)u * p.max_new + t] = id;
+            if (p.pool_ids) p.pool_ids[(long)(r0 + k) * p.max_new + t] = id;
+        }
+        if (tid == 0) {
+            const int len = slot >= 0 ? p.s.pool_len[r0 + slot] : 0;
+            const double sc = slot >= 0 ? p.s.pool_score[r0 + slot] : -INFINITY;
+            if (k == 0) { p.lengths[u] = len; p.scores[u] = sc; }
+            if (p.pool_ids) { p.pool_len[r0 + k] = len; p.pool_scores[r0 + k] = sc; }
+        }
+    }
+    if (tid == 0 && p.pool_n) p.pool_n[u] = pn;
 }
 
 // h[b] = embed_tokens[id] + embed_positions[pos], id = ids[b ld + pos] (clamped into the vocabulary) or, ids null, `id`
@@ -614,6 +990,15 @@ int pack_all(DexWhisper* s, hipStream_t st) {
 // workspace (floats, every piece a multiple of 64): logspec (fp64) [B][T][n_mels] | mel [B][T][Mp] | c1 [B][T][d] | he, ye [B][S][d]
 // | qkv [B][S][3d] | ffe [B][S][ffn_e] | enc [B][S][d] | ckv [Ld][B][S][2d] | ck, cv [Ld][B][Tmax][d] | h, y, a [B][d] | ff [B][ffn_d]
 // | P (the largest [KS][B][N] of a step) | state (int): finished [B], count, new-token count [B], last timestamp [B]
+// the floats per row of the largest [KS][B][N] of a step
+long step_partials(const DexWhisperConfig& c) {
+    const long d = c.d_model;
+    long pn = (long)slabs((int)d) * 3 * d, q = (long)slabs((int)d) * c.decoder_ffn_dim;
+    pn = q > pn ? q : pn; q = (long)slabs(c.decoder_ffn_dim) * d;
+    pn = q > pn ? q : pn; q = (long)slabs((int)d) * c.vocab_size;
+    return q > pn ? q : pn;
+}
+
 struct Ws { double* logspec; float *mel, *c1, *he, *ye, *qkv, *ffe, *enc, *ckv, *ck, *cv, *h, *y, *a, *ff, *P; int *fin, *count, *n_new, *last_ts; size_t bytes; };
 Ws plan(const DexWhisper* s, void* ws, long B) {
     const DexWhisperConfig& c = s->c;
@@ -626,11 +1011,7 @@ Ws plan(const DexWhisper* s, void* ws, long B) {
     w.enc = tk.take(B * S * d);
     w.ckv = tk.take(Ld * B * S * 2 * d); w.ck = tk.take(Ld * B * Tm * d); w.cv = tk.take(Ld * B * Tm * d);
     w.h = tk.take(B * d); w.y = tk.take(B * d); w.a = tk.take(B * d); w.ff = tk.take(B * c.decoder_ffn_dim);
-    long pn = (long)slabs((int)d) * 3 * d, q = (long)slabs((int)d) * c.decoder_ffn_dim;
-    pn = q > pn ? q : pn; q = (long)slabs(c.decoder_ffn_dim) * d;
-    pn = q > pn ? q : pn; q = (long)slabs((int)d) * c.vocab_size;
-    pn = q > pn ? q : pn;
-    w.P = tk.take(B * pn);
+    w.P = tk.take(B * step_partials(c));
     w.fin = (int*)tk.take(3 * B + 64); w.count = w.fin + B; w.n_new = w.count + 1; w.last_ts = w.n_new + B;
     w.bytes = tk.bytes();
     return w;
@@ -701,9 +1082,23 @@ void enqueue_encoder(DexWhisper* s, const float* feat, int B, float* enc_out, co
         linear(w.enc, d, s->dec[l].wckv, 2 * d, s->dec[l].bckv, w.ckv + (long)l * B * S * 2 * d, 0, nullptr, nullptr, S, B, st);
 }
 
+// the beams of a step: B = U x K rows, row u K + r beam r of utterance u; the cross K / V is per utterance, the self-attention
+// cache is read through the ancestry anc [B][ld_anc]
+struct BeamAt { int U, K; const int* anc; int ld_anc; };
+
+void attend_cross_beam(const AtP& x, int H, const BeamAt& bm, hipStream_t st) {
+    const dim3 grid(H, bm.U);
+    const size_t lds = (size_t)bm.K * x.n * sizeof(float);
+    switch (bm.K) {
+#define DEX_BEAM_CASE(k) case k: hipLaunchKernelGGL(wsp_attend_cross_beam_kernel<k>, grid, dim3(256), lds, st, x); break;
+        DEX_BEAM_CASE(2) DEX_BEAM_CASE(3) DEX_BEAM_CASE(4) DEX_BEAM_CASE(5) DEX_BEAM_CASE(6) DEX_BEAM_CASE(7) DEX_BEAM_CASE(8)
+#undef DEX_BEAM_CASE
+    }
+}
+
 // one decoder position: w.h holds embed_tokens + embed_positions of position p; logits: leaves the partials of the logits in w.P
-// and returns their slabs
-int enqueue_step(DexWhisper* s, int p, int B, const Ws& w, hipStream_t st, bool logits = true) {
+// and returns their slabs.  bm: the step of U x K beams (the two attention launches take their beam forms)
+int enqueue_step(DexWhisper* s, int p, int B, const Ws& w, hipStream_t st, bool logits = true, const BeamAt* bm = nullptr) {
     const DexWhisperConfig& c = s->c;
     const int d = c.d_model, H = c.decoder_attention_heads, S = c.max_source_positions, Tm = c.max_target_positions, F = c.decoder_ffn_dim;
     finish(nullptr, 0, d, nullptr, w.h, w.h, 0, s->dec[0].ln1g, s->dec[0].ln1b, w.y, B, st);
@@ -714,15 +1109,17 @@ int enqueue_step(DexWhisper* s, int p, int B, const Ws& w, hipStream_t st, bool 
         a.q = w.P; a.kn = w.P + d; a.vn = w.P + 2 * d; a.KS = ks; a.ss = (long)B * 3 * d; a.ldq = 3 * d; a.qbias = L.bq; a.kbias = nullptr; a.vbias = L.bv;
         a.K = w.ck + (long)l * B * Tm * d; a.V = w.cv + (long)l * B * Tm * d; a.ldk = d; a.kb = (long)Tm * d; a.n = p + 1;
         a.out = w.a; a.ldo = d; a.scale = 0.125f;
-        hipLaunchKernelGGL(wsp_attend_kernel, dim3(H, B), dim3(256), 0, st, a);
+        if (bm) hipLaunchKernelGGL(wsp_attend_anc_kernel, dim3(H, B), dim3(256), 0, st, a, bm->anc, bm->ld_anc, bm->K);
+        else hipLaunchKernelGGL(wsp_attend_kernel, dim3(H, B), dim3(256), 0, st, a);
         ks = skinny(w.a, d, L.wo, d, d, d, w.P, B, st);
         finish(w.P, ks, d, L.bo, w.h, w.h, 0, L.ln2g, L.ln2b, w.y, B, st);
         ks = skinny(w.y, d, L.wcq, d, d, d, w.P, B, st);
         AtP x{};
         x.q = w.P; x.KS = ks; x.ss = (long)B * d; x.ldq = d; x.qbias = L.bcq;
-        x.K = w.ckv + (long)l * B * S * 2 * d; x.V = x.K + d; x.ldk = 2 * d; x.kb = (long)S * 2 * d; x.n = S;
+        x.K = w.ckv + (long)l * (bm ? bm->U : B) * S * 2 * d; x.V = x.K + d; x.ldk = 2 * d; x.kb = (long)S * 2 * d; x.n = S;
         x.out = w.a; x.ldo = d; x.scale = 0.125f;
-        hipLaunchKernelGGL(wsp_attend_kernel, dim3(H, B), dim3(256), 0, st, x);
+        if (bm) attend_cross_beam(x, H, *bm, st);
+        else hipLaunchKernelGGL(wsp_attend_kernel, dim3(H, B), dim3(256), 0, st, x);
         ks = skinny(w.a, d, L.wco, d, d, d, w.P, B, st);
         finish(w.P, ks, d, L.bco, w.h, w.h, 0, L.ln3g, L.ln3b, w.y, B, st);
         ks = skinny(w.y, d, L.w1, F, d, F, w.P, B, st);
@@ -752,6 +1149,45 @@ int check_timestamps(DexWhisper* s, int eos, int nots, int max_init) {
                        c.max_source_positions + 1);
     if (max_init < -1) return s->fail(DEX_ERR_ARG, "max_initial_timestamp_index must be >= 0, or -1 for none");
     return DEX_OK;
+}
+
+// Beam search workspace: the layout of U rows (the encoder's pieces and the cross K / V of the U utterances) and behind it the step of
+// R = U x K rows: ck, cv [Ld][R][Tmax][d] | h, y, a [R][d] | ff [R][ffn_d] | P | logits [R][V] | run, pool scores (fp64) [R] |
+// chunk maxima and sums (fp64) [R][C][2] | chunk candidates: scores (fp64), flat indices [R][C][2K] | seq, anc, pool ids (int)
+// 2 x [R][Tmax] each but the last | pool len, order [R] | pool n, done [U], count
+struct BeamWs { Ws w; float* lg; double *part, *cand_s; int* cand_f; DexWhisperBeamState s; int *seq[2], *anc[2]; size_t bytes; };
+BeamWs plan_beam(const DexWhisper* s, void* ws, long U, long K) {
+    const DexWhisperConfig& c = s->c;
+    const long R = U * K, d = c.d_model, Tm = c.max_target_positions, Ld = c.decoder_layers;
+    BeamWs b{};
+    b.w = plan(s, ws, U);
+    Taker tk(ws);
+    tk.off = (long)((b.w.bytes - 256) / sizeof(float));
+    b.w.ck = tk.take(Ld * R * Tm * d); b.w.cv = tk.take(Ld * R * Tm * d);
+    b.w.h = tk.take(R * d); b.w.y = tk.take(R * d); b.w.a = tk.take(R * d); b.w.ff = tk.take(R * c.decoder_ffn_dim);
+    b.w.P = tk.take(R * step_partials(c));
+    b.lg = tk.take(R * c.vocab_size);
+    const long C = beam_chunks(c.vocab_size);
+    b.part = (double*)tk.take(4 * R * C); b.cand_s = (double*)tk.take(2 * R * C * 2 * K); b.cand_f = (int*)tk.take(R * C * 2 * K);
+    b.s.run_score = (double*)tk.take(2 * R); b.s.pool_score = (double*)tk.take(2 * R);
+    for (int i = 0; i < 2; ++i) { b.seq[i] = (int*)tk.take(R * Tm); b.anc[i] = (int*)tk.take(R * Tm); }
+    b.s.pool_ids = (int*)tk.take(R * Tm);
+    b.s.pool_len = (int*)tk.take(R); b.s.pool_order = (int*)tk.take(R);
+    b.s.pool_n = (int*)tk.take(2 * U + 64); b.s.done = b.s.pool_n + U; b.s.count = b.s.done + U;
+    b.s.ld_seq = b.s.ld_anc = (int)Tm;
+    b.bytes = tk.bytes();
+    return b;
+}
+
+bool beams_ok(const DexWhisper* s, int U, int K) {
+    return U >= 1 && K >= DEX_WHISPER_MIN_BEAMS && K <= DEX_WHISPER_MAX_BEAMS && U * K <= WB && (long)K * s->c.max_source_positions <= DEX_WHISPER_BEAM_KEYS;
+}
+
+// the three launches of a step's tail
+void launch_beam_pick(const BeamP& k, int U, hipStream_t st) {
+    hipLaunchKernelGGL(wsp_beam_lse_kernel, dim3(k.C, U * k.K), dim3(256), 0, st, k);
+    hipLaunchKernelGGL(wsp_beam_top_kernel, dim3(k.C, U * k.K), dim3(256), 0, st, k);
+    hipLaunchKernelGGL(wsp_beam_pick_kernel, dim3(U), dim3(1024), 0, st, k);
 }
 
 typedef Entry<DexWhisper> E;
@@ -1006,6 +1442,134 @@ int dex_whisper_pick_ts(const float* logits_dev, int B, int V, const uint8_t* ma
     hipLaunchKernelGGL(wsp_pick_ts_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream,
                        PickTsP{k, no_timestamps_token_id, no_timestamps_token_id + 1, max_initial_timestamp_index, last_timestamp_dev, n_new_dev});
     return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
+}
+
+int dex_whisper_attend_beam(const float* q_dev, float* k_dev, float* v_dev, const float* new_k_dev, const float* new_v_dev, const int32_t* anc_dev,
+                            int ld_anc, float* out_dev, int U, int K, int heads, int n_keys, int cap, dex_stream_t stream) {
+    if (!q_dev || !k_dev || !v_dev || !out_dev || (new_k_dev == nullptr) != (new_v_dev == nullptr)) return DEX_ERR_ARG;
+    if (U < 1 || K < DEX_WHISPER_MIN_BEAMS || K > DEX_WHISPER_MAX_BEAMS || (long)U * K > 65535 || heads < 1 || heads > 1024) return DEX_ERR_ARG;
+    if (n_keys < 1 || n_keys > cap || cap > MAX_KEYS) return DEX_ERR_ARG;
+    AtP a{};
+    a.q = q_dev; a.KS = 1; a.ss = 0; a.ldq = heads * 64;
+    a.K = k_dev; a.V = v_dev; a.ldk = heads * 64; a.kb = (long)cap * heads * 64; a.n = n_keys; a.out = out_dev; a.ldo = heads * 64; a.scale = 0.125f;
+    if (anc_dev) {
+        if (ld_anc < n_keys) return DEX_ERR_ARG;
+        a.kn = new_k_dev; a.vn = new_v_dev;
+        hipLaunchKernelGGL(wsp_attend_anc_kernel, dim3(heads, U * K), dim3(256), 0, (hipStream_t)stream, a, (const int*)anc_dev, ld_anc, K);
+    } else {
+        if (new_k_dev || (long)K * n_keys > DEX_WHISPER_BEAM_KEYS) return DEX_ERR_ARG;
+        attend_cross_beam(a, heads, BeamAt{U, K, nullptr, 0}, (hipStream_t)stream);
+    }
+    return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
+}
+
+size_t dex_whisper_beam_pick_scratch_bytes(int U, int K, int V) {
+    if (U < 1 || K < DEX_WHISPER_MIN_BEAMS || K > DEX_WHISPER_MAX_BEAMS || V < 1) return 0;
+    const size_t RC = (size_t)U * K * beam_chunks(V);
+    return RC * (2 * sizeof(double) + 2 * K * (sizeof(double) + sizeof(int)));
+}
+
+int dex_whisper_beam_pick(const float* logits_dev, int U, int K, int V, const uint8_t* mask_dev, int eos, int step, int pos, int last,
+                          double length_penalty, const DexWhisperBeamState* state, int32_t* tokens_dev, int32_t* parents_dev, void* scratch_dev,
+                          size_t scratch_bytes, dex_stream_t stream) {
+    if (!logits_dev || !state || !scratch_dev || (tokens_dev == nullptr) != (parents_dev == nullptr)) return DEX_ERR_ARG;
+    const DexWhisperBeamState& s = *state;
+    if (!s.run_score || !s.pool_score || !s.seq_in || !s.seq_out || !s.anc_in || !s.anc_out || !s.pool_ids || !s.pool_len || !s.pool_order || !s.pool_n ||
+        !s.done || !s.count)
+        return DEX_ERR_ARG;
+    if (U < 1 || U > 65535 || K < DEX_WHISPER_MIN_BEAMS || K > DEX_WHISPER_MAX_BEAMS || V < 2 * K || (long)K * V > 0x7fffffffL || eos < 0 || eos >= V)
+        return DEX_ERR_ARG;
+    if (step < 0 || step >= s.ld_seq || pos < 0 || pos >= s.ld_anc) return DEX_ERR_ARG;
+    BeamP k{};
+    k.P = logits_dev; k.KS = 1; k.V = V; k.K = K; k.mask = mask_dev; k.eos = eos; k.step = step; k.pos = pos; k.last = last != 0;
+    k.div = std::pow((double)(step + 1), length_penalty); k.s = s; k.tok = tokens_dev; k.par = parents_dev; k.next_pos = -1;
+    if (((uintptr_t)scratch_dev & 7) || scratch_bytes < dex_whisper_beam_pick_scratch_bytes(U, K, V)) return DEX_ERR_WORKSPACE;
+    const long RC = (long)U * K * beam_chunks(V);
+    k.C = beam_chunks(V); k.part = (double*)scratch_dev; k.cand_s = k.part + 2 * RC; k.cand_f = (int*)(k.cand_s + RC * 2 * K);
+    launch_beam_pick(k, U, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
+}
+
+size_t dex_whisper_beam_workspace_bytes(const DexWhisper* s, int U, int K) {
+    if (!s || !beams_ok(s, U, K)) return 0;
+    return plan_beam(s, nullptr, U, K).bytes;
+}
+
+int dex_whisper_generate_beam(DexWhisper* s, const int32_t* prompt_host, int n_prompt, const uint8_t* suppress_dev, const uint8_t* begin_dev, int eos, int U,
+                              int K, double length_penalty, int max_new, int sync_every, int32_t* ids_dev, int32_t* lengths_dev, double* scores_dev,
+                              int* steps_host, float* trace_logits_dev, int32_t* trace_tokens_dev, int32_t* trace_parents_dev, double* trace_scores_dev,
+                              int32_t* pool_ids_dev, int32_t* pool_len_dev, double* pool_scores_dev, int32_t* pool_n_dev, void* workspace_dev,
+                              size_t workspace_bytes, dex_stream_t stream) {
+    if (!s) return DEX_ERR_ARG;
+    if (!prompt_host || !ids_dev || !lengths_dev || !scores_dev || !steps_host || !workspace_dev) return s->fail(DEX_ERR_ARG, "null pointer argument");
+    const bool trace = trace_logits_dev != nullptr, pool = pool_ids_dev != nullptr;
+    if (trace != (trace_tokens_dev != nullptr) || trace != (trace_parents_dev != nullptr) || trace != (trace_scores_dev != nullptr))
+        return s->fail(DEX_ERR_ARG, "the trace buffers come all or none");
+    if (pool != (pool_len_dev != nullptr) || pool != (pool_scores_dev != nullptr) || pool != (pool_n_dev != nullptr))
+        return s->fail(DEX_ERR_ARG, "the pool buffers come all or none");
+    const DexWhisperConfig& c = s->c;
+    if (!beams_ok(s, U, K))
+        return s->fail(DEX_ERR_ARG, "num_beams must lie in [%d, %d], utterances x num_beams in [1, %d] and num_beams x max_source_positions within %d",
+                       DEX_WHISPER_MIN_BEAMS, DEX_WHISPER_MAX_BEAMS, WB, DEX_WHISPER_BEAM_KEYS);
+    BeamWs b = plan_beam(s, workspace_dev, U, K);
+    if (workspace_bytes < b.bytes) return s->fail(DEX_ERR_WORKSPACE, "workspace too small (dex_whisper_beam_workspace_bytes)");
+    if (!s->finalized) return s->fail(DEX_ERR_STATE, "the whisper weights are not finalized (dex_whisper_finalize)");
+    if (n_prompt < 1 || n_prompt > c.max_target_positions)
+        return s->fail(DEX_ERR_ARG, "a prompt of %d ids: 1 .. max_target_positions = %d", n_prompt, c.max_target_positions);
+    for (int i = 0; i < n_prompt; ++i)
+        if (prompt_host[i] < 0 || prompt_host[i] >= c.vocab_size) return s->fail(DEX_ERR_ARG, "prompt id %d is outside the vocabulary of %d", prompt_host[i], c.vocab_size);
+    if (eos < 0 || eos >= c.vocab_size) return s->fail(DEX_ERR_ARG, "eos_token_id %d is outside the vocabulary of %d", eos, c.vocab_size);
+    if (max_new < 1 || sync_every < 0) return s->fail(DEX_ERR_ARG, "max_new must be >= 1 and sync_every >= 0");
+    if (c.vocab_size < 2 * K) return s->fail(DEX_ERR_ARG, "a vocabulary of %d ids is below 2 x num_beams", c.vocab_size);
+    if (!(length_penalty == length_penalty)) return s->fail(DEX_ERR_ARG, "length_penalty is NaN");
+    hipStream_t st = (hipStream_t)stream;
+    const int R = U * K, V = c.vocab_size, Tm = c.max_target_positions;
+    const int room = Tm - n_prompt, n_new = max_new < room ? max_new : room;
+    const long init = (long)R * Tm;
+    hipLaunchKernelGGL(wsp_beam_init_kernel, dim3((unsigned)((init + 255) / 256)), dim3(256), 0, st, [&] { DexWhisperBeamState t = b.s; t.anc_in = b.anc[0]; t.anc_out = b.anc[1]; return t; }(), U, K);
+    if (trace) {
+        const long n = (long)max_new * R;
+        hipLaunchKernelGGL(wsp_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, trace_tokens_dev, n, -1);
+        hipLaunchKernelGGL(wsp_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, trace_parents_dev, n, -1);
+        DEX_HIPCHK(s, hipMemsetAsync(trace_scores_dev, 0, n * sizeof(double), st));
+        DEX_HIPCHK(s, hipMemsetAsync(trace_logits_dev, 0, n * V * sizeof(float), st));
+    }
+    int steps = 0;
+    if (n_new > 0) {
+        // the prompt is fed on all K rows of an utterance: identical rows, and the identity ancestry the first step starts from
+        BeamAt bm{U, K, b.anc[0], Tm};
+        for (int p = 0; p < n_prompt; ++p) {
+            hipLaunchKernelGGL(wsp_embed_kernel, dim3(R), dim3(256), 0, st, (const int*)nullptr, 0, prompt_host[p], p, V, s->emb, s->dec_pos, c.d_model, b.w.h);
+            if (p < n_prompt - 1) enqueue_step(s, p, R, b.w, st, false, &bm);
+        }
+        for (int i = 0; i < n_new; ++i) {
+            bm.anc = b.anc[i & 1];
+            const int ks = enqueue_step(s, n_prompt - 1 + i, R, b.w, st, true, &bm);
+            BeamP k{};
+            k.P = b.w.P; k.KS = ks; k.ss = (long)R * V; k.V = V; k.K = K; k.mask = i == 0 ? begin_dev : suppress_dev;
+            k.lg = trace ? trace_logits_dev + (long)i * R * V : b.lg; k.C = beam_chunks(V); k.part = b.part; k.cand_s = b.cand_s; k.cand_f = b.cand_f;
+            k.eos = eos; k.step = i; k.pos = n_prompt - 1 + i; k.last = i + 1 == n_new; k.div = std::pow((double)(i + 1), length_penalty);
+            k.s = b.s;
+            if (trace) { k.tok = trace_tokens_dev + (long)i * R; k.par = trace_parents_dev + (long)i * R; k.trace = trace_scores_dev + (long)i * R; }
+            k.emb = s->emb; k.posw = s->dec_pos; k.d = c.d_model; k.next_pos = i + 1 < n_new ? n_prompt + i : -1; k.h = b.w.h;
+            k.s.seq_in = b.seq[i & 1]; k.s.seq_out = b.seq[(i & 1) ^ 1]; k.s.anc_in = b.anc[i & 1]; k.s.anc_out = b.anc[(i & 1) ^ 1];
+            launch_beam_pick(k, U, st);
+            steps = i + 1;
+            if (sync_every && steps % sync_every == 0 && steps < n_new) {
+                int done = 0;
+                DEX_HIPCHK(s, hipMemcpyAsync(&done, b.s.count, sizeof(int), hipMemcpyDeviceToHost, st));
+                DEX_HIPCHK(s, hipStreamSynchronize(st));
+                if (done >= U) break;
+            }
+        }
+    }
+    BeamOutP o{};
+    o.s = b.s; o.K = K; o.eos = eos; o.max_new = max_new; o.ids = ids_dev; o.lengths = lengths_dev; o.scores = scores_dev;
+    o.pool_ids = pool_ids_dev; o.pool_len = pool_len_dev; o.pool_scores = pool_scores_dev; o.pool_n = pool_n_dev;
+    hipLaunchKernelGGL(wsp_beam_result_kernel, dim3(U), dim3(256), 0, st, o);
+    *steps_host = steps;
+    DEX_HIPCHK(s, hipStreamSynchronize(st));
+    return hipGetLastError() == hipSuccess ? DEX_OK : s->fail(DEX_ERR_HIP, "kernel launch failed");
 }
 
 }  // extern "C"

@@ -1,14 +1,15 @@
 """The Whisper ASR score on the device: the recogniser zero-shot TTS work reports its WER with (``asr.py`` stays the reference's
 wav2vec 2.0 CTC score; numbers from the two recognisers are not comparable).  HF's ``WhisperForConditionalGeneration`` in eval
-mode, fp32 throughout: log-mel front end, encoder, decoder with a key/value cache, greedy decoding.
+mode, fp32 throughout: log-mel front end, encoder, decoder with a key/value cache, greedy decoding and beam search.
 
     WhisperConfig(...)                         HF's field names; defaults = openai/whisper-large-v3
-    Whisper(config=None, device='cuda'):       load_state_dict (HF keys), log_mel, encode, forward, generate, transcribe;
+    Whisper(config=None, device='cuda'):       load_state_dict (HF keys), log_mel, encode, forward, generate, generate_beam, transcribe;
                                                long form: log_mel_long, generate_segments, transcribe_long
     GenerationSpec(prompt_ids, suppress_tokens, begin_suppress_tokens, eos_token_id, no_timestamps_token_id=None,
                    max_initial_timestamp_index=None);  GenerationSpec.from_generation_config(..., timestamps=False)
     load_vocab(path), decode(ids, vocab)       host only
-    whisper_score(wavs, texts, model=, spec=, vocab=, long_form=False) -> (transcripts, cer_mean, cer_stderr, wer_mean, wer_stderr)
+    whisper_score(wavs, texts, model=, spec=, vocab=, long_form=False, num_beams=1, length_penalty=1.0)
+                                               -> (transcripts, cer_mean, cer_stderr, wer_mean, wer_stderr)
 
 Everything runs in libdexamd.so (``csrc/whisper.hip``, C ABI ``dex_whisper_*``).  Nothing downloads and no checkpoint is shipped:
 weights, the generation config and the vocabulary come from dicts or local files the caller names.  A row's features, logits and ids
@@ -37,12 +38,53 @@ Greedy decoding is the library's own definition, a stated subset of HF ``generat
 new-token step i ``suppress_tokens`` are set to -inf, at i = 0 ``begin_suppress_tokens`` as well, and the argmax takes the lowest
 index on ties.  A row is finished once it emits ``eos_token_id``; from then on its output is eos.  The loop ends when every row has
 finished, after ``max_new_tokens``, or when ``len(prompt) + i`` reaches ``max_target_positions``: it never writes past the cache.
-Not built: temperature fallback, the compression-ratio, log-prob and no-speech thresholds, beams, language detection,
+Not built: temperature fallback, the compression-ratio, log-prob and no-speech thresholds, language detection,
 ``condition_on_prev_tokens``, token-level timestamps.  Timestamps are built for the long form only (below).
+
+Beam search (``generate_beam``; ``generate``, ``transcribe``, ``whisper_score`` with ``num_beams`` > 1) is HF ``generate(num_beams=K,
+do_sample=False, early_stopping=False, num_return_sequences=1)``, one utterance at a time.  K = ``num_beams``, V = ``vocab_size``, P =
+``len(prompt)``, ``lp`` = ``length_penalty`` (default 1.0).  ``num_beams=1`` is the greedy path above, untouched and bitwise.
+
+  State per utterance.  K running hypotheses, each with an accumulated score, initially ``[0, -1e9, ...]`` (step 0 is decided by beam
+  0 alone); a pool of at most K finished hypotheses with scores; a ``done`` flag.
+
+  Step i = 0, 1, ..., for each running beam r: the fp32 logits of the cached step; ``log_softmax`` over the whole, unmasked row,
+  computed in fp64 from the fp32 logits (a stated departure: HF computes it in fp32); ``suppress_tokens`` -> -inf, at i = 0
+  ``begin_suppress_tokens`` as well (masked ids are not renormalised away - HF's order: softmax first, processors second); the beam's
+  running score is added in fp64.
+
+  Candidates.  The 2K largest of the K x V accumulated scores, in descending order; ties go to the lowest flat index ``r V + id``.
+  Fewer than 2K unmasked ids raise ``ValueError``.  A candidate is finished if its id is eos; on the last step, ``i = n_new - 1`` with
+  ``n_new = min(max_new_tokens, max_target_positions - P)``, every candidate is finished.  The next running beams are the first K
+  unfinished candidates, in order: their scores, ids and parents become the running state (on the last step it stays as it is).
+
+  Pool.  Only a finished candidate of rank < K enters, with the score ``score / (i + 1)^lp`` (the eos counts in the length).  The
+  old pool comes first, then the new entries in rank order; the best K are kept, ties go to the earlier entry.
+
+  Stop.  After the step the utterance is done if it was the last step, or if the pool holds K entries and ``best running score /
+  (i + 1)^lp <= worst pool score``.  Done is sticky: a done utterance's state no longer changes, whatever the others do.
+
+  Result.  The pool's best hypothesis -> ``ids`` (padded with eos), ``lengths`` (the tokens before the eos; the full count of a
+  capped hypothesis) and ``scores`` (its pool score, float64).  The pool is never empty at the end.  An utterance's ids, lengths and
+  scores are bitwise those of the utterance alone at the same K.
+
+  On the device.  U utterances of K beams are U x K rows of the step.  The cross-attention K / V is computed and stored once per
+  utterance, and one workgroup per (head, utterance) streams it once for the K queries.  The self-attention cache never moves: row
+  r writes its new k / v into its own row at position p and reads position t from row ``anc[r][t]``; after the selection
+  ``anc'[r'][0..p] = anc[parent(r')][0..p]`` and ``anc'[r'][p + 1] = r'``, an int copy.  The prompt is fed on all K rows.  The
+  step's tail (three launches: the normaliser's chunk sums, the 2K best of every chunk of 2048 ids by the fp64 score, and the
+  merge with the whole rule and the gather of the next step's embeddings) needs no host value; the host reads the done count every
+  ``SYNC_EVERY`` steps.  Per query both attention forms keep the plain kernel's arithmetic bit for bit, so greedy and beam logits
+  are comparable.
+
+  Limits: ``2 <= K <= 8``; ``K x max_source_positions <= 13000`` (the K score rows of a cross-attention launch sit in LDS); ``U x K
+  <= 32`` rows per network call, larger batches run ``32 // K`` utterances at a time.  Out of scope, each a ``ValueError`` naming the
+  argument: ``timestamps=True`` or ``long_form=True`` with ``num_beams`` > 1 (the rule's per-row state would have to follow the
+  parents), ``early_stopping`` other than ``False``, ``num_return_sequences`` > 1, sampling and temperature fallback.
 
 Long form (``log_mel_long``, ``generate_segments``, ``transcribe_long``, ``whisper_score(long_form=True)``) mirrors HF
 ``generate(..., return_timestamps=True)`` at temperature 0 with ``condition_on_prev_tokens=False``: no no-speech, log-prob or
-compression-ratio threshold, no fallback, no beams.  The spec carries ``no_timestamps_token_id`` (``timestamp_begin`` is that id + 1;
+compression-ratio threshold, no fallback, no beams (beam search is built for the plain form only).  The spec carries ``no_timestamps_token_id`` (``timestamp_begin`` is that id + 1;
 ``from_generation_config(timestamps=True)`` fills it, leaves ``<|notimestamps|>`` out of the prompt and reads
 ``max_initial_timestamp_index``); a spec without it raises ``ValueError``, and so do fewer than ``max_source_positions + 1``
 timestamp ids (``vocab_size - timestamp_begin``).
@@ -119,6 +161,8 @@ MAX_ROWS = 32                       # DEX_WHISPER_MAX_B
 SYNC_EVERY = 8
 MAX_LONG_SAMPLES = 28_800_000       # DEX_WHISPER_MAX_LONG_SAMPLES: 30 minutes at 16 kHz
 _LONG_SCRATCH = 1 << 30             # bytes of fp64 log-spectrum one front-end call of the long form may hold
+MIN_BEAMS, MAX_BEAMS = 2, 8         # DEX_WHISPER_MIN_BEAMS, DEX_WHISPER_MAX_BEAMS
+BEAM_KEYS = 13000                   # DEX_WHISPER_BEAM_KEYS
 
 
 @dataclasses.dataclass(frozen=True)
@@ -215,6 +259,33 @@ class GenerationSpec:
                                    max_initial_timestamp_index=None if cap is None else int(cap))
 
 
+def check_beam_args(config: WhisperConfig, spec: GenerationSpec, num_beams: int, length_penalty: float = 1.0, timestamps: bool = False,
+                    long_form: bool = False, early_stopping=False, num_return_sequences: int = 1, what: str = "Whisper.generate_beam") -> int:
+    """The host-side refusals of beam search (the module docstring's limits and out-of-scope list), each a ``ValueError`` naming the
+    argument.  Returns K.  Host only."""
+    if isinstance(num_beams, bool) or int(num_beams) != num_beams or not MIN_BEAMS <= int(num_beams) <= MAX_BEAMS:
+        raise ValueError(f"{what}: num_beams must be an integer in [{MIN_BEAMS}, {MAX_BEAMS}] (1 is greedy decoding, through generate), got {num_beams!r}")
+    K = int(num_beams)
+    if timestamps:
+        raise ValueError(f"{what}: timestamps=True with num_beams > 1 is not built (the timestamp rule's state would have to follow the parents)")
+    if long_form:
+        raise ValueError(f"{what}: long_form=True with num_beams > 1 is not built (the long form decodes under the timestamp rule)")
+    if early_stopping is not False:
+        raise ValueError(f"{what}: early_stopping must be False, got {early_stopping!r}")
+    if num_return_sequences != 1:
+        raise ValueError(f"{what}: num_return_sequences must be 1, got {num_return_sequences!r}")
+    lp = float(length_penalty)
+    if not np.isfinite(lp):
+        raise ValueError(f"{what}: length_penalty must be finite, got {length_penalty!r}")
+    if K * config.max_source_positions > BEAM_KEYS:
+        raise ValueError(f"{what}: num_beams x max_source_positions = {K * config.max_source_positions} is above {BEAM_KEYS} (the beams' scores of one "
+                         "cross-attention launch sit in LDS)")
+    masked = {int(t) for t in spec.suppress_tokens} | {int(t) for t in spec.begin_suppress_tokens}
+    if config.vocab_size - len(masked) < 2 * K:
+        raise ValueError(f"{what}: suppress_tokens and begin_suppress_tokens leave {config.vocab_size - len(masked)} ids, num_beams = {K} needs 2 x {K}")
+    return K
+
+
 def _byte_table():
     """GPT-2's printable stand-ins of the 256 byte values, inverted: character -> byte."""
     bs = list(range(33, 127)) + list(range(161, 173)) + list(range(174, 256))
@@ -263,6 +334,12 @@ class _Handle(NetHandle):
         need = int(self._fn("workspace_bytes")(self.h, B))
         if need == 0:
             raise ValueError(f"{B} rows: {self.no_workspace}")
+        return super(NetHandle, self).workspace(need)
+
+    def beam_workspace(self, U: int, K: int) -> torch.Tensor:
+        need = int(self._fn("beam_workspace_bytes")(self.h, U, K))
+        if need == 0:
+            raise ValueError(f"{U} utterances of {K} beams: {self.no_workspace}")
         return super(NetHandle, self).workspace(need)
 
 
@@ -386,12 +463,18 @@ class Whisper(WaveformNet):
         return torch.from_numpy(sup).to(self.device), torch.from_numpy(beg).to(self.device)
 
     def generate(self, features_or_wavs, spec: GenerationSpec, max_new_tokens: Optional[int] = None, lengths=None, sr: int = SAMPLING_RATE,
-                 timestamps: bool = False):
+                 timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1):
         """Greedy decoding (the module docstring's definition) of features [B, num_mel_bins, frames], or of wavs as ``log_mel`` takes
         them -> (ids [B, n] int32, a row padded with eos after its end; lengths [B] int32, the tokens before a row's eos), both on the
         device.  n is the number of steps decoded: at most ``max_new_tokens`` and ``max_target_positions - len(prompt)``.
-        ``timestamps=True`` decodes one window under the long form's step rule (``spec`` with the timestamp fields)."""
+        ``timestamps=True`` decodes one window under the long form's step rule (``spec`` with the timestamp fields).
+        ``num_beams`` > 1: beam search, the first two results of ``generate_beam``."""
         what = "Whisper.generate"
+        if num_beams != 1:
+            check_beam_args(self.config, spec, num_beams, length_penalty, timestamps, False, early_stopping, num_return_sequences, what)
+            return self.generate_beam(features_or_wavs, spec, num_beams, length_penalty, max_new_tokens, lengths, sr)[:2]
+        if early_stopping is not False or num_return_sequences != 1:
+            raise ValueError(f"{what}: early_stopping and num_return_sequences belong to beam search (num_beams > 1)")
         self._need_weights(what)
         c = self.config
         if timestamps:
@@ -428,10 +511,71 @@ class Whisper(WaveformNet):
             n = max(n, steps.value)
         return ids[:, :n], lens
 
+    def generate_beam(self, features_or_wavs, spec: GenerationSpec, num_beams: int, length_penalty: float = 1.0, max_new_tokens: Optional[int] = None,
+                      lengths=None, sr: int = SAMPLING_RATE, trace: bool = False):
+        """Beam search (the module docstring's definition) of features or wavs as ``generate`` takes them -> (ids [U, n] int32, the
+        best hypothesis padded with eos; lengths [U] int32; scores [U] float64, its pool score), on the device.  ``trace=True`` adds a
+        dict: ``logits`` [n, U, K, V] fp32, ``tokens``, ``parents`` [n, U, K] int32 (-1 on an utterance's last step and once it is
+        done), ``scores`` [n, U, K] float64 (the running scores after the step), and the pool at the end, best first: ``pool_ids``
+        [U, K, n], ``pool_lengths``, ``pool_scores`` [U, K], ``pool_n`` [U]."""
+        what = "Whisper.generate_beam"
+        K = check_beam_args(self.config, spec, num_beams, length_penalty, what=what)
+        self._need_weights(what)
+        c = self.config
+        if not spec.prompt_ids or len(spec.prompt_ids) > c.max_target_positions:
+            raise ValueError(f"{what}: a prompt of {len(spec.prompt_ids)} ids, max_target_positions is {c.max_target_positions}")
+        if torch.is_tensor(features_or_wavs) and features_or_wavs.dim() == 3:
+            f = self._features(features_or_wavs, what)
+        else:
+            f = self.log_mel(features_or_wavs, lengths, sr)
+            f = f[None] if f.dim() == 2 else f
+        room = c.max_target_positions - len(spec.prompt_ids)
+        max_new = room if max_new_tokens is None else min(int(max_new_tokens), room)
+        if max_new < 1:
+            raise ValueError(f"{what}: max_new_tokens must be >= 1 (and the prompt leave room in the cache), got {max_new}")
+        sup, beg = self._masks(spec)
+        prompt = np.ascontiguousarray(np.asarray(spec.prompt_ids, np.int32))
+        U, V, dev = f.shape[0], c.vocab_size, self.device
+        ids = torch.empty(U, max_new, dtype=torch.int32, device=dev)
+        lens = torch.empty(U, dtype=torch.int32, device=dev)
+        scores = torch.empty(U, dtype=torch.float64, device=dev)
+        tr = None
+        if trace:
+            tr = dict(logits=torch.empty(max_new, U, K, V, dtype=torch.float32, device=dev), tokens=torch.empty(max_new, U, K, dtype=torch.int32, device=dev),
+                      parents=torch.empty(max_new, U, K, dtype=torch.int32, device=dev), scores=torch.empty(max_new, U, K, dtype=torch.float64, device=dev),
+                      pool_ids=torch.empty(U, K, max_new, dtype=torch.int32, device=dev), pool_lengths=torch.empty(U, K, dtype=torch.int32, device=dev),
+                      pool_scores=torch.empty(U, K, dtype=torch.float64, device=dev), pool_n=torch.empty(U, dtype=torch.int32, device=dev))
+        ctx, steps, n, group = self._ctx, C.c_int(0), 0, MAX_ROWS // K
+        for r in range(0, U, group):
+            fb = f[r:r + group]
+            u = fb.shape[0]
+            ws = ctx.beam_workspace(u, K)
+            with torch.cuda.device(dev):
+                ctx.check(ctx.lib.dex_whisper_encode(ctx.h, fb.data_ptr(), u, None, None, ws.data_ptr(), ws.numel(), stream(dev)), "dex_whisper_encode")
+                t = [None] * 8
+                if trace:                                       # per group: the group's utterances are contiguous only along dim 1
+                    g = {k: (v[:, r:r + u].contiguous() if k in ("logits", "tokens", "parents", "scores") else v[r:r + u]) for k, v in tr.items()}
+                    t = [g[k].data_ptr() for k in ("logits", "tokens", "parents", "scores", "pool_ids", "pool_lengths", "pool_scores", "pool_n")]
+                rc = ctx.lib.dex_whisper_generate_beam(ctx.h, i32_ptr(prompt), len(prompt), sup.data_ptr(), beg.data_ptr(), int(spec.eos_token_id), u, K,
+                                                       float(length_penalty), max_new, SYNC_EVERY, ids[r:r + u].data_ptr(), lens[r:r + u].data_ptr(),
+                                                       scores[r:r + u].data_ptr(), C.byref(steps), *t, ws.data_ptr(), ws.numel(), stream(dev))
+            ctx.check(rc, "dex_whisper_generate_beam")
+            if trace:
+                for k in ("logits", "tokens", "parents", "scores"):
+                    tr[k][:, r:r + u] = g[k]
+            n = max(n, steps.value)
+        if trace:
+            for k in ("logits", "tokens", "parents", "scores"):
+                tr[k] = tr[k][:n]
+            tr["pool_ids"] = tr["pool_ids"][:, :, :n]
+            return ids[:, :n], lens, scores, tr
+        return ids[:, :n], lens, scores
+
     def transcribe(self, wavs, spec: GenerationSpec, vocab: Sequence[str], lengths=None, sr: int = SAMPLING_RATE,
-                   max_new_tokens: Optional[int] = None):
-        """``wavs`` as ``log_mel`` takes them -> a list of transcripts (``decode`` of each row's tokens; one device-to-host copy)."""
-        ids, lens = self.generate(wavs, spec, max_new_tokens, lengths, sr)
+                   max_new_tokens: Optional[int] = None, num_beams: int = 1, length_penalty: float = 1.0):
+        """``wavs`` as ``log_mel`` takes them -> a list of transcripts (``decode`` of each row's tokens; one device-to-host copy).
+        ``num_beams`` > 1 decodes by beam search."""
+        ids, lens = self.generate(wavs, spec, max_new_tokens, lengths, sr, num_beams=num_beams, length_penalty=length_penalty)
         ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
         return [decode(ids[b, : int(lens[b])], vocab, spec.eos_token_id) for b in range(ids.shape[0])]
 
@@ -550,14 +694,19 @@ def retrieve_segments(tokens: Sequence[int], timestamp_begin: int, seek: int, n:
 
 
 def whisper_score(wavs, texts: Sequence[str], model: Optional[Whisper] = None, spec: Optional[GenerationSpec] = None,
-                  vocab: Optional[Sequence[str]] = None, sr: int = SAMPLING_RATE, lengths=None, long_form: bool = False):
+                  vocab: Optional[Sequence[str]] = None, sr: int = SAMPLING_RATE, lengths=None, long_form: bool = False, num_beams: int = 1,
+                  length_penalty: float = 1.0):
     """Every wav transcribed by ``model``; CER and WER of ``asr.normalize_sentence(transcript)`` against
     ``asr.normalize_sentence(text)`` (the reference's normaliser, not Whisper's: numbers stay as written) ->
     (transcripts, cer_mean, cer_stderr, wer_mean, wer_stderr), the errors ``np.std / sqrt(n)``.  ``long_form=True``: rows of any
-    length, through ``transcribe_long`` (``spec`` with the timestamp fields)."""
+    length, through ``transcribe_long`` (``spec`` with the timestamp fields).  ``num_beams`` > 1: beam search (not with the long form)."""
     if not isinstance(model, Whisper) or spec is None or vocab is None:
         raise ValueError("whisper_score: pass model=Whisper(...) with the checkpoint's weights loaded, spec= and vocab= (the library ships none)")
-    preds = (model.transcribe_long if long_form else model.transcribe)(wavs, spec, vocab, lengths, sr)
+    if num_beams != 1:
+        check_beam_args(model.config, spec, num_beams, length_penalty, long_form=long_form, what="whisper_score")
+        preds = model.transcribe(wavs, spec, vocab, lengths, sr, num_beams=num_beams, length_penalty=length_penalty)
+    else:
+        preds = (model.transcribe_long if long_form else model.transcribe)(wavs, spec, vocab, lengths, sr)
     if len(preds) != len(texts) or not preds:
         raise ValueError(f"whisper_score: {len(texts)} texts against {len(preds)} wavs")
     return (preds, *score_transcripts(texts, preds))

@@ -891,6 +891,56 @@ int  dex_whisper_generate_ts(DexWhisper* w, const int32_t* prompt_host, int n_pr
 int  dex_whisper_pick_ts(const float* logits_dev, int B, int V, const uint8_t* mask_dev, int eos, int no_timestamps_token_id,
                          int max_initial_timestamp_index, int32_t* finished_dev, int32_t* lengths_dev, int32_t* count_dev,
                          int32_t* ids_dev, int ld_ids, int step, int32_t* last_timestamp_dev, int32_t* n_new_dev, dex_stream_t stream);
+/* ---- beam search (dex_tts_amd/whisper.py states the definition): U utterances of K beams are the U x K rows u K + r of a step */
+#define DEX_WHISPER_MIN_BEAMS 2
+#define DEX_WHISPER_MAX_BEAMS 8
+#define DEX_WHISPER_BEAM_KEYS 13000     /* K x keys of one cross-form launch: their scores sit in LDS */
+/* The state of U utterances between two tail launches, all on the device.  A row's token sequence and ancestry are read from the
+ * _in buffers and written to the _out buffers (the caller swaps them between steps; no element is permuted in place).  Ancestry
+ * entries are beam indices 0 .. K - 1 within the utterance.  The pool of finished hypotheses lives in K slots per utterance;
+ * pool_order lists an utterance's slots best first, pool_n of them. */
+typedef struct DexWhisperBeamState {
+    double*  run_score;                 /* [U K] accumulated score of each running beam */
+    double*  pool_score;                /* [U K] by slot */
+    int32_t* seq_in;  int32_t* seq_out; /* [U K, ld_seq] the new tokens of each running beam */
+    int32_t* anc_in;  int32_t* anc_out; /* [U K, ld_anc] the row whose cache slot holds position t of a beam's prefix */
+    int32_t* pool_ids;                  /* [U K, ld_seq] by slot */
+    int32_t* pool_len;                  /* [U K] by slot: the tokens before the eos; the full count of a capped hypothesis */
+    int32_t* pool_order;                /* [U K] */
+    int32_t* pool_n;                    /* [U] */
+    int32_t* done;                      /* [U] */
+    int32_t* count;                     /* [1] the done utterances */
+    int32_t  ld_seq, ld_anc;
+} DexWhisperBeamState;
+/* the single-query attention of K beams per utterance alone (head_dim 64), a row bitwise dex_whisper_attend of that query.
+ * anc_dev NULL, the cross form: q_dev [U K, heads x 64] against the utterance's k_dev / v_dev [U, cap, heads x 64] over keys
+ * 0 .. n_keys - 1 (K x n_keys <= DEX_WHISPER_BEAM_KEYS), one workgroup per (head, utterance) streaming the keys once.
+ * anc_dev [U K, ld_anc] given, the self form: k_dev / v_dev [U K, cap, heads x 64]; row r first appends new_k_dev / new_v_dev
+ * [U K, heads x 64] (or both NULL) at position n_keys - 1 of its own row, and reads position t < n_keys - 1 (t <= n_keys - 1 with
+ * nothing appended) from row anc[r][t] of its utterance. */
+int  dex_whisper_attend_beam(const float* q_dev, float* k_dev, float* v_dev, const float* new_k_dev, const float* new_v_dev,
+                             const int32_t* anc_dev, int ld_anc, float* out_dev, int U, int K, int heads, int n_keys, int cap,
+                             dex_stream_t stream);
+/* the beam step tail alone (its three launches), new-token step `step` at cache position `pos`: logits_dev [U K, V] fp32, mask_dev
+ * [V] bytes (or NULL); scratch_dev (8-byte aligned, dex_whisper_beam_pick_scratch_bytes) holds the chunk sums and candidates.
+ * `last` marks the last step (every candidate finished).  tokens_dev / parents_dev [U K] (or NULL) receive the new running set of
+ * the utterances that were not done (nothing is written on the last step). */
+int  dex_whisper_beam_pick(const float* logits_dev, int U, int K, int V, const uint8_t* mask_dev, int eos, int step, int pos, int last,
+                           double length_penalty, const DexWhisperBeamState* state, int32_t* tokens_dev, int32_t* parents_dev,
+                           void* scratch_dev, size_t scratch_bytes, dex_stream_t stream);
+size_t dex_whisper_beam_pick_scratch_bytes(int U, int K, int V);                 /* 0 for bad arguments */
+size_t dex_whisper_beam_workspace_bytes(const DexWhisper* w, int U, int K);     /* 0 for bad arguments; U x K <= DEX_WHISPER_MAX_B */
+/* Beam search over the cached step after dex_whisper_encode of the U utterances in the same workspace (the encoder's layout of U
+ * rows heads it).  ids_dev [U, max_new] (eos behind the hypothesis), lengths_dev [U], scores_dev [U] (fp64).  trace_*_dev (all or
+ * none): the fp32 logits [max_new, U K, V], and tokens, parents (int32, -1 where an utterance was done) and running scores (fp64)
+ * [max_new, U K] of every step.  pool_*_dev (or NULL): the pool at the end, best first: ids [U K, max_new], lengths and scores
+ * [U K], entries [U]. */
+int  dex_whisper_generate_beam(DexWhisper* w, const int32_t* prompt_host, int n_prompt, const uint8_t* suppress_dev, const uint8_t* begin_dev,
+                               int eos, int U, int K, double length_penalty, int max_new, int sync_every, int32_t* ids_dev,
+                               int32_t* lengths_dev, double* scores_dev, int* steps_host, float* trace_logits_dev, int32_t* trace_tokens_dev,
+                               int32_t* trace_parents_dev, double* trace_scores_dev, int32_t* pool_ids_dev, int32_t* pool_len_dev,
+                               double* pool_scores_dev, int32_t* pool_n_dev, void* workspace_dev, size_t workspace_bytes,
+                               dex_stream_t stream);
 
 #ifdef __cplusplus
 }

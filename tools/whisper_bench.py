@@ -18,7 +18,14 @@ The long form at whisper-large-v3 geometry, random weights: (a) the per-token ti
 plain ``generate`` on the same features with the same forced step count (eos suppressed), the two alternating inside every
 repetition, with the run-to-run spread (max - min over the repetitions) of each; (b) one ``generate_segments`` call on wavs of that
 many seconds (``--tokens`` new tokens per window at most): its time and window count against the sum of its window calls (gather,
-encoder, decode) run one by one, and the long front end alone."""
+encoder, decode) run one by one, and the long front end alone.
+
+    python tools/whisper_bench.py --beams 5 [--batches 1,6] [--reps 5] [--tokens 48]
+
+Beam search at whisper-large-v3 geometry, random weights, eos suppressed: the per-token time of ``generate_beam`` at U utterances of
+K beams against the greedy ``generate`` on U x K independent rows (the same row count, each row with its own cross-attention K / V)
+and against the torch graph with a key/value cache where a beam step is ``log_softmax`` + ``topk`` + ``index_select`` of the cache;
+the three alternate inside every repetition; medians and the run-to-run spread (max - min) of each."""
 import argparse
 import ctypes as C
 import json
@@ -145,6 +152,23 @@ class TorchWhisper:
         return torch.stack(out, dim=1)
 
 
+    def decode_beam(self, U, K, n_new, mask):
+        """Beam search as torch users write it: U x K rows, the caches reordered by ``index_select`` every step -> ids [U, n_new]."""
+        B = U * K
+        for p, t in enumerate(PROMPT[:-1]):
+            self.step(torch.full((B,), t, device="cuda"), p)
+        tok = torch.full((B,), PROMPT[-1], device="cuda")
+        score = torch.tensor([0.0] + [-1e9] * (K - 1), device="cuda").repeat(U)
+        seqs, base = torch.zeros(B, 0, dtype=torch.long, device="cuda"), (torch.arange(U, device="cuda") * K)[:, None]
+        for i in range(n_new):
+            lp = torch.log_softmax(self.step(tok, len(PROMPT) - 1 + i), dim=-1) + mask + score[:, None]
+            top, flat = lp.reshape(U, -1).topk(2 * K, dim=1)
+            score, parent, tok = top[:, :K].reshape(B), (base + flat[:, :K] // lp.shape[1]).reshape(B), (flat[:, :K] % lp.shape[1]).reshape(B)
+            self.k, self.v = self.k.index_select(1, parent), self.v.index_select(1, parent)
+            seqs = torch.cat([seqs[parent], tok[:, None]], dim=1)
+        return seqs.reshape(U, K, -1)[:, 0]
+
+
 def timed(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -267,6 +291,42 @@ def bench_long(cfg, seconds, batches, reps, warmup, n_tok, seed):
         return rows
 
 
+def bench_beams(cfg, K, batches, reps, warmup, n_tok, seed):
+    with torch.no_grad():
+        w = make_weights(cfg, seed, "cuda")
+        lib = whisper.Whisper(R.library_config(cfg), "cuda").load_state_dict(w)
+        ref = TorchWhisper(cfg, w)
+        eos = cfg.vocab_size - 1
+        spec = whisper.GenerationSpec(PROMPT, (eos,), (eos,), eos)
+        mask = torch.zeros(cfg.vocab_size, device="cuda")
+        mask[eos] = float("-inf")
+        rows = []
+        for U in batches:
+            feat = lib.log_mel(make_wavs(U, seed).cuda())
+            rep_feat = feat.repeat_interleave(K, dim=0)
+            enc = ref.encode(feat).repeat_interleave(K, dim=0)
+            t = {k: [] for k in ("beam", "greedy", "torch")}
+            for r in range(warmup + reps):
+                b1, _ = timed(lambda: lib.generate_beam(feat, spec, K, max_new_tokens=1))
+                bn, (ids, _, _) = timed(lambda: lib.generate_beam(feat, spec, K, max_new_tokens=n_tok))
+                g1, _ = timed(lambda: lib.generate(rep_feat, spec, 1))
+                gn, _ = timed(lambda: lib.generate(rep_feat, spec, n_tok))
+                ref.cross_kv(enc)
+                t1, _ = timed(lambda: ref.decode_beam(U, K, 1, mask))
+                ref.cross_kv(enc)
+                tn, rids = timed(lambda: ref.decode_beam(U, K, n_tok, mask))
+                assert ids.shape[1] == n_tok
+                if r >= warmup:
+                    for k, v in zip(t, (bn - b1, gn - g1, tn - t1)):
+                        t[k].append(v / (n_tok - 1))
+            row = dict(model="large-v3", U=U, K=K, rows=U * K, tokens=n_tok, reps=reps, ids_equal_torch=float((ids.long() == rids).float().mean()))
+            for k, v in t.items():
+                row[f"{k}_per_token_ms"], row[f"{k}_spread_ms"] = med(v), max(v) - min(v)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        return rows
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="base.en,large-v3")
@@ -277,7 +337,15 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--json", default=None)
     ap.add_argument("--long", type=float, default=None, metavar="SECONDS", help="the long-form case alone (large-v3 geometry, B = 1 and 8 by default)")
+    ap.add_argument("--beams", type=int, default=None, metavar="K", help="the beam-search case alone (large-v3 geometry, U = 1 and 6 by default)")
     a = ap.parse_args(argv)
+    if a.beams is not None:
+        out = {"beams": bench_beams(MODELS["large-v3"], a.beams, [int(b) for b in (a.batches if a.batches != "1,8,32" else "1,6").split(",")], a.reps,
+                                    a.warmup, a.tokens, a.seed)}
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     if a.long is not None:
         out = {"long": bench_long(MODELS["large-v3"], a.long, [int(b) for b in (a.batches if a.batches != "1,8,32" else "1,8").split(",")], a.reps,
                                   a.warmup, a.tokens, a.seed)}
