@@ -8,6 +8,7 @@ text as character and word error rates.
     normalize_input(wav, lengths=None)                    Wav2Vec2FeatureExtractor's do_normalize
     num_frames(n_samples, config=None)                    floor((L - k) / s) + 1 chained over the feature extractor
     ctc_greedy(logits, frames) -> [[int]];  decode(ids, vocab=None) -> str
+    Wav2Vec2CTC.align(wavs, texts) / .text_nll(wavs, texts)   word and character timings, the text's likelihood (ctc_align.py)
     normalize_sentence, wer, cer                          metric.py:97-110 normalize_sentence and jiwer's two rates (host strings)
     asr_score(texts, wavs, sr=16000, model=) -> (cer_mean, cer_stderr, wer_mean, wer_stderr)
 
@@ -214,6 +215,51 @@ class Wav2Vec2CTC(WaveformNet):
         transcripts.  Where ``sr`` is not 16000 the wavs are resampled by ``wavprep.resample`` (kaiser_best; librosa uses soxr)."""
         wavs, lengths = self._at_16k(wavs, lengths, sr, "Wav2Vec2CTC.transcribe")
         return [decode(ids, self.vocab) for ids in self.transcribe_ids(wavs, lengths)]
+
+    def _text_inputs(self, wavs, texts, lengths, sr, unknown: str, what: str):
+        """The checked inputs of the calls that take a text per wav: (rows, host lengths, T, (ids, words) per row, frames, targets,
+        target lengths); ``ValueError`` for a text outside the vocabulary or one that does not fit its row's frames."""
+        from .ctc_align import check_targets, text_to_targets
+        wavs, lengths = self._at_16k(wavs, lengths, sr, what)
+        x, ln, _, T = self._inputs(wavs, lengths, what)
+        texts = [texts] if isinstance(texts, str) else list(texts)
+        if len(texts) != x.shape[0]:
+            raise ValueError(f"{what}: {len(texts)} texts against {x.shape[0]} wavs")
+        pairs = [text_to_targets(t, self.vocab, unknown=unknown) for t in texts]
+        frames = [num_frames(int(v), self.config) for v in ln]
+        fr, tg, tl = check_targets(x.shape[0], T, self.config.vocab_size, frames, [p[0] for p in pairs], None, 0, True, what)
+        return x, ln, T, pairs, fr, tg, tl
+
+    def align(self, wavs, texts, lengths=None, sr: int = SAMPLING_RATE, unknown: str = "error"):
+        """Forced alignment of each wav to its text (``ctc_align.py`` holds the definitions): forward, the Viterbi pass and the
+        likelihood in one stream-ordered sequence, one device-to-host copy.  ``wavs`` as for ``transcribe``; ``texts`` one string per
+        wav, turned into targets by ``text_to_targets`` (``unknown`` as there).  Per row ``{"words": [{"word", "start", "end",
+        "score"}], "chars": [{"char", "start", "end", "score"}], "score", "nll", "frames"}``: times in seconds (frame t starts at
+        sample ``t * prod(conv_stride)``; an end is clipped to the row's length), ``chars`` without the word delimiters, a word from
+        its first character's start to its last character's end with the frame-weighted mean of its characters' scores.
+        ``ValueError`` naming a row that cannot be aligned (too few frames, or -inf / NaN logits)."""
+        from .ctc_align import AlignBuffers, ctc_workspace, word_alignment
+        what = "Wav2Vec2CTC.align"
+        x, ln, T, pairs, fr, tg, tl = self._text_inputs(wavs, texts, lengths, sr, unknown, what)
+        B, Lm = x.shape[0], tg.shape[1]
+        cws = ctc_workspace(self.device, B, T, self.config.vocab_size, Lm)
+        out = AlignBuffers(B, T, Lm, self.device)
+        self._run("align", x, ln, out.buf, i32_ptr(tg), i32_ptr(tl), Lm, *out.pointers(), cws.data_ptr(), cws.numel())
+        host = {k: v.numpy() for k, v in out.views(out.buf.cpu()).items()}
+        stride = int(np.prod(self.config.conv_stride))
+        rows = []
+        for b, (ids, words) in enumerate(pairs):
+            if not np.isfinite(host["score"][b]):
+                raise ValueError(f"{what}: row {b} has no alignment (score {host['score'][b]}): its logits hold -inf or NaN")
+            rows.append(word_alignment(ids, words, host["spans"][b], host["token_scores"][b], host["score"][b], host["nll"][b], int(fr[b]),
+                                       int(ln[b]), stride, self.vocab))
+        return rows
+
+    def text_nll(self, wavs, texts, lengths=None, sr: int = SAMPLING_RATE, unknown: str = "error") -> torch.Tensor:
+        """The recogniser's negative log-likelihood of each wav's text: ``ctc_nll`` of ``forward``'s logits -> [B] fp64 on the device."""
+        from .ctc_align import ctc_nll
+        x, ln, _, _, fr, tg, tl = self._text_inputs(wavs, texts, lengths, sr, unknown, "Wav2Vec2CTC.text_nll")
+        return ctc_nll(self.forward(x, ln), fr, tg, tl, 0)
 
 
 def asr_score(texts: Sequence[str], wavs, sr: int = SAMPLING_RATE, model: Optional[Wav2Vec2CTC] = None, lengths=None):

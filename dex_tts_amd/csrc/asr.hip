@@ -215,6 +215,38 @@ int dex_asr_transcribe(DexAsr* s, const float* wav_dev, const int32_t* lengths_h
     });
 }
 
+int dex_asr_align(DexAsr* s, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, const int32_t* targets_host,
+                  const int32_t* target_lengths_host, int Lmax, int32_t* states_dev, int32_t* spans_dev, double* token_scores_dev, double* score_dev,
+                  double* nll_dev, void* ctc_workspace_dev, size_t ctc_workspace_bytes, void* workspace_dev, size_t workspace_bytes,
+                  dex_stream_t stream) {
+    if (!s) return DEX_ERR_ARG;
+    int32_t frames[DEX_CTC_MAX_ROWS];
+    const auto more = [&]() {
+        if (!target_lengths_host || !ctc_workspace_dev || (Lmax > 0 && !targets_host)) return s->fail(DEX_ERR_ARG, "null pointer argument");
+        const int T = frames_of(s->t, n_samples, s->t.n_conv);
+        if (B > DEX_CTC_MAX_ROWS || T > DEX_CTC_MAX_FRAMES)
+            return s->fail(DEX_ERR_ARG, "an alignment takes at most %d rows of %d frames", DEX_CTC_MAX_ROWS, DEX_CTC_MAX_FRAMES);
+        for (int b = 0; b < B; ++b) frames[b] = frames_of(s->t, lengths_host[b], s->t.n_conv);
+        const size_t need = dex_ctc_workspace_bytes(B, T, s->c.vocab, Lmax);
+        if (need == 0) return s->fail(DEX_ERR_ARG, "Lmax must lie in [0, %d]", DEX_CTC_MAX_TARGET);
+        if (ctc_workspace_bytes < need) return s->fail(DEX_ERR_WORKSPACE, "CTC workspace too small (dex_ctc_workspace_bytes)");
+        for (int b = 0; b < B; ++b) {
+            if (target_lengths_host[b] < 0 || target_lengths_host[b] > Lmax) return s->fail(DEX_ERR_ARG, "target lengths must lie in [0, Lmax]");
+            for (int l = 0; l < target_lengths_host[b]; ++l) {
+                const int v = targets_host[(long)b * Lmax + l];
+                if (v < 1 || v >= s->c.vocab) return s->fail(DEX_ERR_ARG, "target ids must lie in [1, vocab): id 0 is the blank");
+            }
+        }
+        return (int)DEX_OK;
+    };
+    return E::call(s, wav_dev, lengths_host, B, n_samples, states_dev && spans_dev && token_scores_dev && score_dev, workspace_dev, workspace_bytes, plan,
+                   more, [&](const Ws& w, int T) {
+        const int rc = enqueue_network(s, wav_dev, lengths_host, B, n_samples, w.logits, w, (hipStream_t)stream);
+        return rc ? rc : dex_ctc_align(w.logits, frames, B, T, s->c.vocab, targets_host, target_lengths_host, Lmax, 0, states_dev, spans_dev,
+                                       token_scores_dev, score_dev, nll_dev, ctc_workspace_dev, ctc_workspace_bytes, stream);
+    });
+}
+
 int dex_asr_ctc(DexAsr* s, const float* logits_dev, const int32_t* frames_host, int B, int T, int V, int32_t* ids_dev, int32_t* counts_dev,
                 dex_stream_t stream) {
     if (!s) return DEX_ERR_ARG;

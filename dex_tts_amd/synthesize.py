@@ -178,6 +178,19 @@ def asr_scores(model, audio, texts, sr: int = 22050):
     return (preds, *asr.score_transcripts(texts, preds))
 
 
+def align_scores(model, audio, texts, sr: int = 22050):
+    """Word and character timings of ``synthesize_tokens``' list of int16 waveforms (``sr`` Hz) against the input texts, in the same
+    order, and the recogniser's likelihood of each text -> (alignments, nll_per_char_mean, nll_per_char_stderr); an alignment is a
+    row of ``asr.Wav2Vec2CTC.align`` (ctc_align.py holds the definitions).  ``model`` is an ``asr.Wav2Vec2CTC`` with the checkpoint's
+    weights loaded.  The same departure as the other scores: the waveforms are resampled by ``wavprep.resample``."""
+    from . import asr, ctc_align
+    if len(audio) != len(texts) or len(audio) < 1:
+        raise ValueError(f"align_scores: {len(audio)} waveforms against {len(texts)} texts")
+    if not isinstance(model, asr.Wav2Vec2CTC):
+        raise ValueError("align_scores: pass an asr.Wav2Vec2CTC with the checkpoint's weights loaded (the library ships none)")
+    return ctc_align.alignment_score(texts, list(audio), sr=sr, model=model)
+
+
 def whisper_scores(model, spec, vocab, audio, texts, sr: int = 22050, long_form: bool = False, num_beams: int = 1, length_penalty: float = 1.0):
     """The Whisper ASR score of ``synthesize_tokens``' list of int16 waveforms (``sr`` Hz) against the input texts, in the same order
     -> (transcripts, cer_mean, cer_stderr, wer_mean, wer_stderr).  ``model`` is a ``whisper.Whisper`` with the checkpoint's weights

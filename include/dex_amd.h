@@ -625,6 +625,38 @@ int  dex_asr_transcribe(DexAsr* asr, const float* wav_dev, const int32_t* length
 int  dex_asr_ctc(DexAsr* asr, const float* logits_dev, const int32_t* frames_host, int B, int T, int V, int32_t* ids_dev,
                  int32_t* counts_dev, dex_stream_t stream);
 
+/* ---- CTC forced alignment and text likelihood (the contract is the docstring of dex_tts_amd/ctc_align.py; tests/ctc_ref.py restates
+ * it in numpy).  logits_dev [B, T, V] fp32, row b frames_host[b] frames; the known text of row b is targets_host[b, 0 .. L_b) of
+ * [B, Lmax] int32, L_b = target_lengths_host[b], ids in [0, V) and none equal to blank.  Stateless.  Targets and lengths are HOST
+ * arrays, copied to the workspace in stream order and validated first: DEX_ERR_ARG, with nothing enqueued, for a null pointer, an id
+ * outside [0, V) or equal to blank, blank outside [0, V), L_b outside [0, Lmax], Lmax outside [0, DEX_CTC_MAX_TARGET], frames outside
+ * [1, T], T outside [1, DEX_CTC_MAX_FRAMES], V outside [1, 65536] or B outside [1, DEX_CTC_MAX_ROWS]; DEX_ERR_WORKSPACE below the
+ * bytes the sizing call returns.  targets_host may be NULL where Lmax is 0.  Every output of a row is bitwise that of the row alone. */
+#define DEX_CTC_MAX_FRAMES 4096
+#define DEX_CTC_MAX_TARGET 1023
+#define DEX_CTC_MAX_ROWS 1024
+size_t dex_ctc_workspace_bytes(int B, int T, int V, int Lmax);          /* 0 for bad arguments */
+/* nll_dev [B] fp64: the negative log-likelihood of the text, F.ctc_loss(log_softmax(x), reduction='none'); +inf for a row whose text
+ * does not fit its frames */
+int  dex_ctc_nll(const float* logits_dev, const int32_t* frames_host, int B, int T, int V, const int32_t* targets_host,
+                 const int32_t* target_lengths_host, int Lmax, int blank, double* nll_dev, void* workspace_dev, size_t workspace_bytes,
+                 dex_stream_t stream);
+/* the Viterbi path over the 2 L + 1 states: states_dev [B, T] int32 (-1 past a row's frames), spans_dev [B, Lmax, 2] int32 (first frame,
+ * one past the last frame of each target position; -1 past L_b), token_scores_dev [B, Lmax] fp64 (NaN past L_b), score_dev [B] fp64;
+ * nll_dev [B] fp64 is optional (NULL: not computed).  A row whose score is -inf or NaN has no alignment: states and spans -1, token
+ * scores NaN. */
+int  dex_ctc_align(const float* logits_dev, const int32_t* frames_host, int B, int T, int V, const int32_t* targets_host,
+                   const int32_t* target_lengths_host, int Lmax, int blank, int32_t* states_dev, int32_t* spans_dev,
+                   double* token_scores_dev, double* score_dev, double* nll_dev, void* workspace_dev, size_t workspace_bytes,
+                   dex_stream_t stream);
+/* the network's logits, kept in its workspace, followed by the alignment and the likelihood in one stream-ordered sequence; the frames of
+ * row b are those of lengths_host[b], T those of n_samples (at most DEX_CTC_MAX_FRAMES).  ctc_workspace_dev holds the bytes the CTC sizing
+ * call returns for (B, T, vocab, Lmax); blank is id 0. */
+int  dex_asr_align(DexAsr* asr, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, const int32_t* targets_host,
+                   const int32_t* target_lengths_host, int Lmax, int32_t* states_dev, int32_t* spans_dev, double* token_scores_dev,
+                   double* score_dev, double* nll_dev, void* ctc_workspace_dev, size_t ctc_workspace_bytes, void* workspace_dev,
+                   size_t workspace_bytes, dex_stream_t stream);
+
 /* ---- WavLM x-vector speaker similarity (SIM): the embeddings of HF's WavLMForXVector in eval mode with attention_mask = None
  * (microsoft/wavlm-base-plus-sv and its family: group-norm feature extractor, post-layer-norm encoder, head_dim 64, softmax attention
  * with the gated relative-position bias, TDNN / statistics-pooling head), in fp32.  Row b of a batch is the network applied to row b
