@@ -32,6 +32,13 @@
 //                        the rule as index ranges from the row's own state (its last two ids, its last timestamp, its new-token
 //                        count, all on the device), the best text id, the best timestamp id and logsumexp(timestamps) in one pass
 //                        over the logits, reduced in a fixed order.  Both kernels end in pick_commit.
+//   wsp_pick_policy_kernel, wsp_nospeech_kernel, wsp_attend_rows_kernel
+//                        fallback decoding (DecodingPolicy).  The tail in its plain and timestamp-rule forms: the greedy tail's
+//                        pass unchanged (the same ids at T = 0), then the fp64 log-sum-exp of the surviving ids, at T > 0 the
+//                        Gumbel-max sample on Philox4x32-10 noise, and the chosen id's log-probability added to the row's sums.
+//                        The probe: the fp64 softmax of the unprocessed logits of prompt position 0 at <|nospeech|>.  The rows
+//                        form of the cross-attention reads the cache row of the encoded batch a retried row came from: a retry
+//                        never runs the encoder again.
 //   wsp_attend_anc_kernel, wsp_attend_cross_beam_kernel, wsp_beam_lse_kernel, wsp_beam_top_kernel, wsp_beam_pick_kernel
 //                        beam search (U utterances of K beams = U x K rows of the step).  The self-attention form reads key t of row r
 //                        from row anc[r][t] of the cache - no cache element moves when beams are reordered - and shares its body
@@ -277,15 +284,15 @@ struct AtP { const float* q; const float* kn; const float* vn; int KS; long ss; 
 // The body of the single-query attention of row blockIdx.y, head blockIdx.x.  ANC: key t is read from row base + anc[t] of the
 // cache (the row's own at the appended position); otherwise from the row's own, and the code is that of the plain kernel
 template <bool ANC>
-__device__ __forceinline__ void attend_row(const AtP& p, const int* anc, int base, int beams) {
+__device__ __forceinline__ void attend_row(const AtP& p, const int* anc, int base, int beams, int kvb) {
     __shared__ float sc[MAX_KEYS];
     __shared__ float qs[64];
     __shared__ float red[4][64];
     __shared__ float red4[4];
     __shared__ int ancs[ANC ? MAX_KEYS : 1];         // the row's ancestry, staged once: a key's address must not wait for a global load
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = blockIdx.x, b = blockIdx.y;
-    float* Kb = p.K + (long)b * p.kb + h * 64;
-    float* Vb = p.V + (long)b * p.kb + h * 64;
+    float* Kb = p.K + (long)kvb * p.kb + h * 64;          // kvb: the row of the cache that holds this row's keys (its own, but in the rows form)
+    float* Vb = p.V + (long)kvb * p.kb + h * 64;
     if constexpr (ANC)
         for (int j = tid; j < p.n; j += 256) ancs[j] = anc[j];
     // the offset of key j's row from the row's own (0 without ancestry); an entry outside the utterance's beams reads the row's own
@@ -344,14 +351,18 @@ __device__ __forceinline__ void attend_row(const AtP& p, const int* anc, int bas
     if (wave == 0) p.out[(long)b * p.ldo + h * 64 + lane] = (((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]) / l;
 }
 
-__global__ __launch_bounds__(256) void wsp_attend_kernel(const AtP p) { attend_row<false>(p, nullptr, 0, 0); }
+__global__ __launch_bounds__(256) void wsp_attend_kernel(const AtP p) { attend_row<false>(p, nullptr, 0, 0, blockIdx.y); }
+
+// The rows form of the cross-attention: query row blockIdx.y attends over cache row rows.a[blockIdx.y].  A retry of some rows of an
+// encoded batch decodes them from the cross K / V where the encoder left it; per query the arithmetic is the plain kernel's
+__global__ __launch_bounds__(256) void wsp_attend_rows_kernel(const AtP p, const Lens rows) { attend_row<false>(p, nullptr, 0, 0, rows.a[blockIdx.y]); }
 
 // ------------------------------------------------------------------------------------------------------------ beam attention
 // The self form: row blockIdx.y = u beams + r appends its k and v in its own row and reads the earlier positions through its ancestry
 // anc [rows][ld_anc] (beam indices within the utterance).  No cache element moves when the beams are reordered
 __global__ __launch_bounds__(256) void wsp_attend_anc_kernel(const AtP p, const int* anc, int ld_anc, int beams) {
     const int b = blockIdx.y;
-    attend_row<true>(p, anc + (long)b * ld_anc, b / beams * beams, beams);
+    attend_row<true>(p, anc + (long)b * ld_anc, b / beams * beams, beams, b);
 }
 
 // The cross form: workgroup (head blockIdx.x, utterance blockIdx.y) streams the utterance's K / V (p.K, p.V, row stride p.kb per
@@ -583,6 +594,160 @@ __global__ __launch_bounds__(1024) void wsp_pick_ts_kernel(const PickTsP q) {
     pick_commit(p, b, arg, &chosen, tb, q.last_ts, q.n_new);
 }
 
+// ------------------------------------------------------------------------------------------------------------ policy step tail
+// The tail of decoding under a DecodingPolicy (temperature fallback with the log-prob statistics), plain (TS false) and under the
+// timestamp rule.  Sweep 1 is the greedy tail's: the same ownership (thread t owns ids t, t + 1024, ...), the same fp32 reductions in
+// the same order, so the rule's decision and at T = 0 the id are those of wsp_pick_kernel / wsp_pick_ts_kernel bit for bit.  It fixes
+// the surviving ids and their maximum M.  Sweep 2 (the row now sits in L2) sums exp(x - M) over the survivors in fp64 - a thread's ids
+// in order, the wave butterfly, the 16 waves in order: fixed by V alone - and at T > 0 takes the argmax of x / T + g, lowest index on
+// ties, g = -log(-log(u)) the Gumbel noise of id v: u = (w + 0.5) 2^-32, w word v & 3 of Philox4x32-10 at counter (v >> 2, step,
+// attempt + 16 seek, row key) under the key (seed low, seed high).  The chosen id's log-probability x - M - log(sum) is added to the
+// row's sum_lp and one to n_scored unless the row had finished; the bookkeeping is pick_commit's.
+struct RowKeys { uint32_t key[WB], c2[WB]; };
+struct PolP { PickP k; int nots, tb, max_init; int *last_ts, *n_new; double T; uint32_t k0, k1; RowKeys rk; double* sum_lp; int* n_scored; };
+
+__device__ __forceinline__ uint32_t philox_word(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, int word) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return word == 0 ? c0 : word == 1 ? c1 : word == 2 ? c2 : c3;
+}
+
+__device__ __forceinline__ void better64(double& v, int& i, double ov, int oi) {
+    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+}
+
+template <bool TS>
+__global__ __launch_bounds__(1024) void wsp_pick_policy_kernel(const PolP q) {
+    __shared__ float tv[16], sv[16], mv[16], lv[16];
+    __shared__ int ti[16], si[16], di[16];
+    __shared__ double dv[16], ds[16];
+    __shared__ int chosen, s_force, s_arg, s_fin;
+    __shared__ float s_max;
+    __shared__ double s_lse;
+    const PickP& p = q.k;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x, V = p.V, tb = TS ? q.tb : V;
+    int text_lo = 0, ts_lo = tb, ts_hi = V - 1;
+    if constexpr (TS) {                                  // the ranges of wsp_pick_ts_kernel
+        const int i = q.n_new[b], seen = q.last_ts[b];
+        const int last = i >= 1 ? p.ids[(long)b * p.ld_ids + p.step - 1] : -1, pen = i >= 2 ? p.ids[(long)b * p.ld_ids + p.step - 2] : -1;
+        const bool last_ts = i >= 1 && last >= tb, pen_ts = i < 2 || pen >= tb;
+        if (last_ts) {
+            if (pen_ts) ts_lo = V;
+            else text_lo = p.eos;
+        }
+        if (seen >= 0) {
+            const int lo = (last_ts && !pen_ts) ? seen : seen + 1;
+            ts_lo = ts_lo > lo ? ts_lo : lo;
+        }
+        if (i == 0) {
+            text_lo = tb;
+            if (q.max_init >= 0 && tb + q.max_init < ts_hi) ts_hi = tb + q.max_init;
+        }
+    }
+    // whether id v competes before the rule's last part (the plain form's masked ids compete as -inf, as in wsp_pick_kernel)
+    auto open = [&](int v) -> bool {
+        if (p.mask && p.mask[v]) return false;
+        if constexpr (TS) return v != q.nots && (v < tb ? v >= text_lo : (v >= ts_lo && v <= ts_hi));
+        return true;
+    };
+    float bt = -INFINITY, bs = -INFINITY, m = -INFINITY, s = 0.f;
+    int at = 0x7fffffff, as = 0x7fffffff;
+    for (int v = tid; v < V; v += 1024) {
+        if constexpr (TS) {
+            if (!open(v)) continue;
+            const float x = finished(p.P, p.KS, p.ss, (long)b * V + v, nullptr, 0);
+            if (v < tb) better(bt, at, x, v);
+            else { better(bs, as, x, v); lse_join(m, s, x, 1.f); }
+        } else {
+            better(bt, at, open(v) ? finished(p.P, p.KS, p.ss, (long)b * V + v, nullptr, 0) : -INFINITY, v);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        better(bt, at, __shfl_xor(bt, o), __shfl_xor(at, o));
+        if constexpr (TS) {
+            better(bs, as, __shfl_xor(bs, o), __shfl_xor(as, o));
+            lse_join(m, s, __shfl_xor(m, o), __shfl_xor(s, o));
+        }
+    }
+    if (lane == 0) { tv[wave] = bt; ti[wave] = at; sv[wave] = bs; si[wave] = as; mv[wave] = m; lv[wave] = s; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 16; ++w) {
+            better(bt, at, tv[w], ti[w]);
+            if constexpr (TS) { better(bs, as, sv[w], si[w]); lse_join(m, s, mv[w], lv[w]); }
+        }
+        bool force = false;
+        int arg = at;
+        float top = bt;
+        if constexpr (TS) {
+            force = m + logf(s) > bt;
+            arg = as; top = bs;
+            if (!force) { top = bt; arg = at; better(top, arg, bs, as); }
+        }
+        s_force = force; s_arg = arg; s_max = top; s_fin = p.finished[b];
+    }
+    __syncthreads();
+    const bool force = s_force != 0, sample = q.T > 0.0;
+    const double M = (double)s_max;
+    const uint32_t c1 = (uint32_t)p.step, c2 = q.rk.c2[b], c3 = q.rk.key[b];
+    double sum = 0.0, best = -INFINITY;
+    int arg = 0x7fffffff;
+    for (int v = tid; v < V; v += 1024) {
+        if (!open(v) || (force && v < tb)) continue;
+        const double x = (double)finished(p.P, p.KS, p.ss, (long)b * V + v, nullptr, 0);
+        sum += exp(x - M);
+        if (sample) {
+            const double u = ((double)philox_word((uint32_t)v >> 2, c1, c2, c3, q.k0, q.k1, v & 3) + 0.5) * 0x1p-32;
+            better64(best, arg, x / q.T - log(-log(u)), v);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        sum += __shfl_xor(sum, o);
+        better64(best, arg, __shfl_xor(best, o), __shfl_xor(arg, o));
+    }
+    if (lane == 0) { ds[wave] = sum; dv[wave] = best; di[wave] = arg; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 16; ++w) { sum += ds[w]; better64(best, arg, dv[w], di[w]); }
+        s_lse = M + log(sum);
+        if (!sample) arg = s_arg;
+    }
+    pick_commit(p, b, arg, &chosen, TS ? tb : 0, TS ? q.last_ts : nullptr, TS ? q.n_new : nullptr);
+    if (tid == 0 && !s_fin) {
+        q.sum_lp[b] += (double)finished(p.P, p.KS, p.ss, (long)b * V + chosen, nullptr, 0) - s_lse;
+        q.n_scored[b] += 1;
+    }
+}
+
+// The no-speech probe: row blockIdx.x's unprocessed logits (the partials of the output projection at prompt position 0) -> the fp64
+// softmax at id `ns`.  The maximum is exact, the sum runs in the policy tail's order
+struct ProbeP { const float* P; int KS; long ss; int V, ns; double* out; };
+__global__ __launch_bounds__(1024) void wsp_nospeech_kernel(const ProbeP p) {
+    __shared__ float mv[16];
+    __shared__ double ds[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+    float m = -INFINITY;
+    for (int v = tid; v < p.V; v += 1024) m = fmaxf(m, finished(p.P, p.KS, p.ss, (long)b * p.V + v, nullptr, 0));
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if (lane == 0) mv[wave] = m;
+    __syncthreads();
+    for (int w = 0; w < 16; ++w) m = fmaxf(m, mv[w]);
+    double sum = 0.0;
+    for (int v = tid; v < p.V; v += 1024) sum += exp((double)finished(p.P, p.KS, p.ss, (long)b * p.V + v, nullptr, 0) - (double)m);
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if (lane == 0) ds[wave] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 16; ++w) sum += ds[w];
+        p.out[b] = exp((double)finished(p.P, p.KS, p.ss, (long)b * p.V + p.ns, nullptr, 0) - (double)m) / sum;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------ beam step tail
 constexpr int KMAX = DEX_WHISPER_MAX_BEAMS;
 
@@ -596,10 +761,6 @@ int beam_chunks(int V) { return (V + BCH - 1) / BCH; }
 struct BeamP { const float* P; int KS; long ss; int V, K, C; const uint8_t* mask; float* lg; double *part, *cand_s; int* cand_f;
                int eos, step, pos, last; double div; DexWhisperBeamState s; int *tok, *par; double* trace;
                const float *emb, *posw; int d, next_pos; float* h; };
-
-__device__ __forceinline__ void better64(double& v, int& i, double ov, int oi) {
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-}
 
 // chunk blockIdx.x of row blockIdx.y: the logits finished from the partials (stored where lg is given), the chunk's maximum and its
 // sum exp(x - maximum) in fp64: per thread in id order, the wave butterfly, the four waves in order
@@ -1096,9 +1257,12 @@ void attend_cross_beam(const AtP& x, int H, const BeamAt& bm, hipStream_t st) {
     }
 }
 
+// the rows of a step that decodes some rows of an encoded batch: row b's cross K / V is row `row.a[b]` of the `encoded` rows' layout
+struct CrossRows { int encoded; Lens row; };
+
 // one decoder position: w.h holds embed_tokens + embed_positions of position p; logits: leaves the partials of the logits in w.P
 // and returns their slabs.  bm: the step of U x K beams (the two attention launches take their beam forms)
-int enqueue_step(DexWhisper* s, int p, int B, const Ws& w, hipStream_t st, bool logits = true, const BeamAt* bm = nullptr) {
+int enqueue_step(DexWhisper* s, int p, int B, const Ws& w, hipStream_t st, bool logits = true, const BeamAt* bm = nullptr, const CrossRows* cr = nullptr) {
     const DexWhisperConfig& c = s->c;
     const int d = c.d_model, H = c.decoder_attention_heads, S = c.max_source_positions, Tm = c.max_target_positions, F = c.decoder_ffn_dim;
     finish(nullptr, 0, d, nullptr, w.h, w.h, 0, s->dec[0].ln1g, s->dec[0].ln1b, w.y, B, st);
@@ -1116,9 +1280,10 @@ int enqueue_step(DexWhisper* s, int p, int B, const Ws& w, hipStream_t st, bool 
         ks = skinny(w.y, d, L.wcq, d, d, d, w.P, B, st);
         AtP x{};
         x.q = w.P; x.KS = ks; x.ss = (long)B * d; x.ldq = d; x.qbias = L.bcq;
-        x.K = w.ckv + (long)l * (bm ? bm->U : B) * S * 2 * d; x.V = x.K + d; x.ldk = 2 * d; x.kb = (long)S * 2 * d; x.n = S;
+        x.K = w.ckv + (long)l * (bm ? bm->U : cr ? cr->encoded : B) * S * 2 * d; x.V = x.K + d; x.ldk = 2 * d; x.kb = (long)S * 2 * d; x.n = S;
         x.out = w.a; x.ldo = d; x.scale = 0.125f;
         if (bm) attend_cross_beam(x, H, *bm, st);
+        else if (cr) hipLaunchKernelGGL(wsp_attend_rows_kernel, dim3(H, B), dim3(256), 0, st, x, cr->row);
         else hipLaunchKernelGGL(wsp_attend_kernel, dim3(H, B), dim3(256), 0, st, x);
         ks = skinny(w.a, d, L.wco, d, d, d, w.P, B, st);
         finish(w.P, ks, d, L.bco, w.h, w.h, 0, L.ln3g, L.ln3b, w.y, B, st);
@@ -1352,6 +1517,98 @@ int dex_whisper_generate_ts(DexWhisper* s, const int32_t* prompt_host, int n_pro
                     ids_dev, lengths_dev, steps_host, workspace_dev, workspace_bytes, stream);
 }
 
+// the Philox key and the per-row counter words of an attempt
+static void policy_noise(PolP* q, double temperature, uint64_t seed, int attempt, const uint32_t* row_keys_host, const int32_t* seek_host, int B) {
+    q->T = temperature; q->k0 = (uint32_t)seed; q->k1 = (uint32_t)(seed >> 32);
+    for (int b = 0; b < B; ++b) { q->rk.key[b] = row_keys_host[b]; q->rk.c2[b] = (uint32_t)attempt + 16u * (uint32_t)seek_host[b]; }
+}
+
+int dex_whisper_generate_policy(DexWhisper* s, const int32_t* prompt_host, int n_prompt, const uint8_t* suppress_dev, const uint8_t* begin_dev, int eos,
+                                int timestamps, int no_timestamps_token_id, int max_initial_timestamp_index, double temperature, uint64_t seed,
+                                int attempt, const uint32_t* row_keys_host, const int32_t* seek_host, int encoded, const int32_t* rows_host, int B,
+                                int max_new, int sync_every, int32_t* ids_dev, int32_t* lengths_dev, double* sum_logprob_dev, int32_t* n_scored_dev,
+                                int no_speech_token_id, double* no_speech_prob_dev, int* steps_host, void* workspace_dev, size_t workspace_bytes,
+                                dex_stream_t stream) {
+    if (!s) return DEX_ERR_ARG;
+    if (!prompt_host || !ids_dev || !lengths_dev || !steps_host || !row_keys_host || !seek_host || !rows_host || !sum_logprob_dev || !n_scored_dev)
+        return s->fail(DEX_ERR_ARG, "null pointer argument");
+    Ws w;
+    if (int rc = ready(s, encoded, workspace_dev, workspace_bytes, &w)) return rc;
+    if (!s->finalized) return s->fail(DEX_ERR_STATE, "the whisper weights are not finalized (dex_whisper_finalize)");
+    const DexWhisperConfig& c = s->c;
+    if (B < 1 || B > encoded) return s->fail(DEX_ERR_ARG, "B must lie in [1, encoded = %d]", encoded);
+    CrossRows cr{};
+    cr.encoded = encoded;
+    for (int b = 0; b < B; ++b) {
+        if (rows_host[b] < 0 || rows_host[b] >= encoded) return s->fail(DEX_ERR_ARG, "row %d is outside the %d encoded rows", rows_host[b], encoded);
+        if (seek_host[b] < 0) return s->fail(DEX_ERR_ARG, "a row's seek must be >= 0");
+        cr.row.a[b] = rows_host[b];
+    }
+    if (n_prompt < 1 || n_prompt > c.max_target_positions)
+        return s->fail(DEX_ERR_ARG, "a prompt of %d ids: 1 .. max_target_positions = %d", n_prompt, c.max_target_positions);
+    for (int i = 0; i < n_prompt; ++i)
+        if (prompt_host[i] < 0 || prompt_host[i] >= c.vocab_size) return s->fail(DEX_ERR_ARG, "prompt id %d is outside the vocabulary of %d", prompt_host[i], c.vocab_size);
+    if (eos < 0 || eos >= c.vocab_size) return s->fail(DEX_ERR_ARG, "eos_token_id %d is outside the vocabulary of %d", eos, c.vocab_size);
+    if (max_new < 1 || sync_every < 0) return s->fail(DEX_ERR_ARG, "max_new must be >= 1 and sync_every >= 0");
+    if (!(temperature >= 0.0) || !std::isfinite(temperature)) return s->fail(DEX_ERR_ARG, "temperature must be finite and >= 0");
+    if (attempt < 0 || attempt > 15) return s->fail(DEX_ERR_ARG, "attempt must lie in [0, 15]");
+    if (no_speech_prob_dev && (no_speech_token_id < 0 || no_speech_token_id >= c.vocab_size))
+        return s->fail(DEX_ERR_ARG, "no_speech_token_id %d is outside the vocabulary of %d", no_speech_token_id, c.vocab_size);
+    hipStream_t st = (hipStream_t)stream;
+    if (timestamps) {
+        if (no_timestamps_token_id < 0) return s->fail(DEX_ERR_ARG, "no_timestamps_token_id %d is outside the vocabulary of %d", no_timestamps_token_id, c.vocab_size);
+        if (int rc = check_timestamps(s, eos, no_timestamps_token_id, max_initial_timestamp_index)) return rc;
+        DEX_HIPCHK(s, hipMemsetAsync(w.n_new, 0, B * sizeof(int), st));
+        hipLaunchKernelGGL(wsp_fill_kernel, dim3(1), dim3(256), 0, st, w.last_ts, (long)B, -1);
+    }
+    const int room = c.max_target_positions - n_prompt, n_new = max_new < room ? max_new : room;      // never past the cache
+    const long n_ids = (long)B * max_new;
+    hipLaunchKernelGGL(wsp_fill_kernel, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, st, ids_dev, n_ids, eos);
+    DEX_HIPCHK(s, hipMemsetAsync(lengths_dev, 0, B * sizeof(int32_t), st));
+    DEX_HIPCHK(s, hipMemsetAsync(sum_logprob_dev, 0, B * sizeof(double), st));
+    DEX_HIPCHK(s, hipMemsetAsync(n_scored_dev, 0, B * sizeof(int32_t), st));
+    DEX_HIPCHK(s, hipMemsetAsync(w.fin, 0, (encoded + 1) * sizeof(int), st));               // the flags and, behind the encoded rows', the count
+    PolP q{};
+    policy_noise(&q, temperature, seed, attempt, row_keys_host, seek_host, B);
+    q.nots = no_timestamps_token_id; q.tb = no_timestamps_token_id + 1; q.max_init = max_initial_timestamp_index; q.last_ts = w.last_ts; q.n_new = w.n_new;
+    q.sum_lp = sum_logprob_dev; q.n_scored = n_scored_dev;
+    auto probe = [&](int ks) {                                                            // the unprocessed logits of prompt position 0 are in w.P
+        if (no_speech_prob_dev)
+            hipLaunchKernelGGL(wsp_nospeech_kernel, dim3(B), dim3(1024), 0, st, ProbeP{w.P, ks, (long)B * c.vocab_size, c.vocab_size, no_speech_token_id, no_speech_prob_dev});
+    };
+    int steps = 0;
+    if (n_new > 0) {
+        for (int p = 0; p < n_prompt - 1; ++p) {
+            hipLaunchKernelGGL(wsp_embed_kernel, dim3(B), dim3(256), 0, st, (const int*)nullptr, 0, prompt_host[p], p, c.vocab_size, s->emb, s->dec_pos, c.d_model, w.h);
+            const int ks = enqueue_step(s, p, B, w, st, p == 0 && no_speech_prob_dev, nullptr, &cr);
+            if (p == 0) probe(ks);
+        }
+        hipLaunchKernelGGL(wsp_embed_kernel, dim3(B), dim3(256), 0, st, (const int*)nullptr, 0, prompt_host[n_prompt - 1], n_prompt - 1, c.vocab_size, s->emb,
+                           s->dec_pos, c.d_model, w.h);
+        for (int i = 0; i < n_new; ++i) {
+            const int ks = enqueue_step(s, n_prompt - 1 + i, B, w, st, true, nullptr, &cr);
+            if (i == 0 && n_prompt == 1) probe(ks);
+            PickP& k = q.k;
+            k = PickP{};
+            k.P = w.P; k.KS = ks; k.ss = (long)B * c.vocab_size; k.V = c.vocab_size; k.mask = i == 0 ? begin_dev : suppress_dev;
+            k.pick = 1; k.eos = eos; k.finished = w.fin; k.lengths = lengths_dev; k.count = w.count; k.ids = ids_dev; k.ld_ids = max_new; k.step = i;
+            k.emb = s->emb; k.pos = s->dec_pos; k.d = c.d_model; k.next_pos = i + 1 < n_new ? n_prompt + i : -1; k.h = w.h;
+            if (timestamps) hipLaunchKernelGGL(wsp_pick_policy_kernel<true>, dim3(B), dim3(1024), 0, st, q);
+            else hipLaunchKernelGGL(wsp_pick_policy_kernel<false>, dim3(B), dim3(1024), 0, st, q);
+            steps = i + 1;
+            if (sync_every && steps % sync_every == 0 && steps < n_new) {
+                int done = 0;
+                DEX_HIPCHK(s, hipMemcpyAsync(&done, w.count, sizeof(int), hipMemcpyDeviceToHost, st));
+                DEX_HIPCHK(s, hipStreamSynchronize(st));
+                if (done >= B) break;
+            }
+        }
+    }
+    *steps_host = steps;
+    DEX_HIPCHK(s, hipStreamSynchronize(st));
+    return hipGetLastError() == hipSuccess ? DEX_OK : s->fail(DEX_ERR_HIP, "kernel launch failed");
+}
+
 int dex_whisper_log_mel_long(DexWhisper* s, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, float* out_dev, int max_frames,
                              int32_t* frames_host, void* scratch_dev, size_t scratch_bytes, dex_stream_t stream) {
     if (!s) return DEX_ERR_ARG;
@@ -1441,6 +1698,35 @@ int dex_whisper_pick_ts(const float* logits_dev, int B, int V, const uint8_t* ma
     k.ids = ids_dev; k.ld_ids = ld_ids; k.step = step; k.next_pos = -1;
     hipLaunchKernelGGL(wsp_pick_ts_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream,
                        PickTsP{k, no_timestamps_token_id, no_timestamps_token_id + 1, max_initial_timestamp_index, last_timestamp_dev, n_new_dev});
+    return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
+}
+
+int dex_whisper_pick_policy(const float* logits_dev, int B, int V, const uint8_t* mask_dev, int eos, int timestamps, int no_timestamps_token_id,
+                            int max_initial_timestamp_index, double temperature, uint64_t seed, int attempt, const uint32_t* row_keys_host,
+                            const int32_t* seek_host, int32_t* finished_dev, int32_t* lengths_dev, int32_t* count_dev, int32_t* ids_dev, int ld_ids,
+                            int step, int32_t* last_timestamp_dev, int32_t* n_new_dev, double* sum_logprob_dev, int32_t* n_scored_dev,
+                            dex_stream_t stream) {
+    if (!logits_dev || !finished_dev || !lengths_dev || !count_dev || !ids_dev || !row_keys_host || !seek_host || !sum_logprob_dev || !n_scored_dev)
+        return DEX_ERR_ARG;
+    if (B < 1 || B > WB || V < 1 || eos < 0 || eos >= V || step < 0 || step >= ld_ids) return DEX_ERR_ARG;
+    if (!(temperature >= 0.0) || !std::isfinite(temperature) || attempt < 0 || attempt > 15) return DEX_ERR_ARG;
+    for (int b = 0; b < B; ++b)
+        if (seek_host[b] < 0) return DEX_ERR_ARG;
+    PolP q{};
+    PickP& k = q.k;
+    k.P = logits_dev; k.KS = 1; k.V = V; k.mask = mask_dev; k.pick = 1; k.eos = eos; k.finished = finished_dev; k.lengths = lengths_dev; k.count = count_dev;
+    k.ids = ids_dev; k.ld_ids = ld_ids; k.step = step; k.next_pos = -1;
+    policy_noise(&q, temperature, seed, attempt, row_keys_host, seek_host, B);
+    q.sum_lp = sum_logprob_dev; q.n_scored = n_scored_dev;
+    if (timestamps) {
+        if (!last_timestamp_dev || !n_new_dev || step < 2) return DEX_ERR_ARG;
+        if (no_timestamps_token_id < eos || no_timestamps_token_id >= V - 1 || max_initial_timestamp_index < -1) return DEX_ERR_ARG;
+        q.nots = no_timestamps_token_id; q.tb = no_timestamps_token_id + 1; q.max_init = max_initial_timestamp_index;
+        q.last_ts = last_timestamp_dev; q.n_new = n_new_dev;
+        hipLaunchKernelGGL(wsp_pick_policy_kernel<true>, dim3(B), dim3(1024), 0, (hipStream_t)stream, q);
+    } else {
+        hipLaunchKernelGGL(wsp_pick_policy_kernel<false>, dim3(B), dim3(1024), 0, (hipStream_t)stream, q);
+    }
     return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
 }
 

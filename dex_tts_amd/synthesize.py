@@ -191,20 +191,22 @@ def align_scores(model, audio, texts, sr: int = 22050):
     return ctc_align.alignment_score(texts, list(audio), sr=sr, model=model)
 
 
-def whisper_scores(model, spec, vocab, audio, texts, sr: int = 22050, long_form: bool = False, num_beams: int = 1, length_penalty: float = 1.0):
+def whisper_scores(model, spec, vocab, audio, texts, sr: int = 22050, long_form: bool = False, num_beams: int = 1, length_penalty: float = 1.0,
+                   policy=None):
     """The Whisper ASR score of ``synthesize_tokens``' list of int16 waveforms (``sr`` Hz) against the input texts, in the same order
     -> (transcripts, cer_mean, cer_stderr, wer_mean, wer_stderr).  ``model`` is a ``whisper.Whisper`` with the checkpoint's weights
     loaded, ``spec`` its ``GenerationSpec`` and ``vocab`` its token strings (whisper.py states the definitions and the two
     departures: the resampler, and the reference's ``normalize_sentence`` in place of Whisper's English normaliser).  ``long_form=True``
     scores waveforms of any length by timestamp-rule decoding over 30 s windows (``spec`` with the timestamp fields).  ``num_beams`` > 1
-    decodes by beam search with ``length_penalty`` (not with the long form)."""
+    decodes by beam search with ``length_penalty`` (not with the long form).  ``policy`` (a ``whisper.DecodingPolicy``): temperature
+    fallback under the compression-ratio, log-prob and no-speech thresholds, short or long form (not with beams)."""
     from . import whisper
     if len(audio) != len(texts) or len(audio) < 1:
         raise ValueError(f"whisper_scores: {len(audio)} waveforms against {len(texts)} texts")
     if not isinstance(model, whisper.Whisper):
         raise ValueError("whisper_scores: pass a whisper.Whisper with the checkpoint's weights loaded (the library ships none)")
     return whisper.whisper_score(list(audio), texts, model=model, spec=spec, vocab=vocab, sr=sr, long_form=long_form, num_beams=num_beams,
-                                 length_penalty=length_penalty)
+                                 length_penalty=length_penalty, policy=policy)
 
 
 def main(argv=None):

@@ -38,8 +38,8 @@ Greedy decoding is the library's own definition, a stated subset of HF ``generat
 new-token step i ``suppress_tokens`` are set to -inf, at i = 0 ``begin_suppress_tokens`` as well, and the argmax takes the lowest
 index on ties.  A row is finished once it emits ``eos_token_id``; from then on its output is eos.  The loop ends when every row has
 finished, after ``max_new_tokens``, or when ``len(prompt) + i`` reaches ``max_target_positions``: it never writes past the cache.
-Not built: temperature fallback, the compression-ratio, log-prob and no-speech thresholds, language detection,
-``condition_on_prev_tokens``, token-level timestamps.  Timestamps are built for the long form only (below).
+Not built: language detection, ``condition_on_prev_tokens``, token-level timestamps.  Timestamps are built for the long form only
+(below); temperature fallback and the three thresholds are the policy (further below).
 
 Beam search (``generate_beam``; ``generate``, ``transcribe``, ``whisper_score`` with ``num_beams`` > 1) is HF ``generate(num_beams=K,
 do_sample=False, early_stopping=False, num_return_sequences=1)``, one utterance at a time.  K = ``num_beams``, V = ``vocab_size``, P =
@@ -125,6 +125,50 @@ timestamp ids (``vocab_size - timestamp_begin``).
   and ids are bitwise those of the row alone.  One device-to-host copy of ids and lengths per window call is the only sync beyond
   the plain form's.
 
+Fallback decoding (``DecodingPolicy``; ``policy=`` of ``generate``, ``transcribe``, ``generate_segments``, ``transcribe_long``,
+``whisper_score``; ``None`` is the paths above, untouched) mirrors HF's ``generate_with_fallback``, ``_need_fallback``,
+``_retrieve_avg_logprobs``, ``_retrieve_compression_ratio`` and ``WhisperNoSpeechDetection`` applied to ONE ROW ALONE: HF indexes its
+skip and fallback flags by position in the shrinking fallback sub-batch; here a row's result is bitwise the row alone.
+
+    DecodingPolicy(temperatures=(0.0, 0.2, 0.4, 0.6, 0.8, 1.0), compression_ratio_threshold=None, logprob_threshold=None,
+                   no_speech_threshold=None, no_speech_token_id=None, seed=0);  DecodingPolicy.from_generation_config(config, ...)
+
+  ``None`` switches a threshold off; ``no_speech_threshold`` requires ``logprob_threshold`` and ``no_speech_token_id``
+  (``from_generation_config``: ``no_timestamps_token_id - 1``, as HF).  The first temperature is 0, temperatures rise, at most 8;
+  anything else is a ``ValueError`` naming the field.  A policy with ``num_beams`` > 1 raises ``ValueError``.
+
+  Per attempt and row the device keeps ``sum_logprob`` (fp64): over the new tokens, the emitted eos included, the sum of
+  ``log_softmax(masked logits)[token]`` where the row is taken after ``begin_suppress_tokens``, ``suppress_tokens`` and, under
+  timestamps, the timestamp rule, at temperature 1 (HF multiplies the temperature back in), normalised by an fp64 log-sum-exp over
+  the surviving ids of the fp32 logits; ``n_scored``, the count of those tokens; ``avg_logprob = sum_logprob / n_scored``; and
+  ``no_speech_prob``, the fp64 softmax of the UNPROCESSED logits at prompt position 0 (``<|startoftranscript|>``) at
+  ``no_speech_token_id`` - the output projection at that one position, once per window, not per attempt (NaN without the id).
+  The compression ratio stays on the host: HF's, on token bytes (``int(log2(V) / 8) + 1`` bytes per id, little endian,
+  ``zlib.compress``) over the tokens HF passes (the eos included).
+
+  Decision after an attempt, in HF's order: a retry is needed if the ratio exceeds its threshold or ``avg_logprob <
+  logprob_threshold``; with ``no_speech_threshold``, ``avg_logprob < logprob_threshold and no_speech_prob > no_speech_threshold``
+  skips the window instead (the long form adds the window's n frames to ``seek`` and emits no segment, the short form returns an
+  empty row); otherwise the row is decoded again at the next temperature; after the last one its result stands.
+
+  Sampling at T > 0 is the library's own (HF's ``torch.multinomial`` stream cannot be reproduced on a device): Gumbel-max.  The masked
+  fp32 logits go to fp64, are divided by T, ``g = -log(-log(u))`` is added and the argmax is taken, lowest index on ties, through
+  the greedy tail's finished / length / eos bookkeeping.  ``u = (w + 0.5) 2^-32`` with w a word of Philox4x32-10: key = ``seed`` (low,
+  high 32 bits), counter = (id >> 2, new-token step i, attempt + 16 x seek, row key), word id & 3.  The row key defaults to the
+  utterance's index in the call (``row_keys=``); ``seek`` is the window's first frame (0 in the short form).  The noise depends on
+  nothing else: not the batch, not the rows decoded beside it.
+
+  On the device.  One tail launch per step (``wsp_pick_policy_kernel``, plain and under the rule): sweep 1 is the greedy tail's own
+  pass (the same ownership and fp32 reductions, so the rule's decision and at T = 0 the id are the existing tails' bit for bit);
+  sweep 2 over the row, now in L2, sums exp(x - max) over the survivors in fp64 in an order fixed by V, perturbs, takes the argmax
+  and adds the chosen id's log-probability to the row's sums.  A retry does NOT run the encoder again: the attempt decodes the rows
+  that need one from the cross-attention K / V where the encoder left it (``wsp_attend_rows_kernel`` reads row ``rows[b]`` of the
+  encoded batch).  Each attempt costs one device-to-host copy (ids, lengths and the statistics in one tensor).
+
+  Departures from HF, stated plainly: the sampling stream is the library's; ``log_softmax`` and the no-speech softmax are fp64 (HF:
+  fp32); a row is decided alone (HF: by sub-batch position); the ratio is on token bytes (HF's), not on decoded text
+  (``openai-whisper``'s).
+
 Host syncs.  Token ids, the finished flags and each row's length stay on the device; a step needs no host value.  The host reads
 one finished-count every ``SYNC_EVERY`` = 8 steps to end early: a read drains the queue of launches the host has run ahead with
 (tens of microseconds, against a step that streams the decoder's weights), so one per step would serialise host and device, while
@@ -145,7 +189,9 @@ from __future__ import annotations
 import ctypes as C
 import dataclasses
 import json
+import math
 import os
+import zlib
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -163,6 +209,7 @@ MAX_LONG_SAMPLES = 28_800_000       # DEX_WHISPER_MAX_LONG_SAMPLES: 30 minutes a
 _LONG_SCRATCH = 1 << 30             # bytes of fp64 log-spectrum one front-end call of the long form may hold
 MIN_BEAMS, MAX_BEAMS = 2, 8         # DEX_WHISPER_MIN_BEAMS, DEX_WHISPER_MAX_BEAMS
 BEAM_KEYS = 13000                   # DEX_WHISPER_BEAM_KEYS
+MAX_TEMPERATURES = 8                # the attempts of a DecodingPolicy (the noise counter gives an attempt 4 bits)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -257,6 +304,73 @@ class GenerationSpec:
         cap = config.get("max_initial_timestamp_index")
         return dataclasses.replace(spec, no_timestamps_token_id=int(config["no_timestamps_token_id"]),
                                    max_initial_timestamp_index=None if cap is None else int(cap))
+
+
+@dataclasses.dataclass(frozen=True)
+class DecodingPolicy:
+    """Fallback decoding (the module docstring's definition): the temperatures of the attempts in order, HF's three thresholds
+    (``None`` switches a check off), ``<|nospeech|>`` and the key of the sampling noise."""
+    temperatures: Tuple[float, ...] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0)
+    compression_ratio_threshold: Optional[float] = None
+    logprob_threshold: Optional[float] = None
+    no_speech_threshold: Optional[float] = None
+    no_speech_token_id: Optional[int] = None
+    seed: int = 0
+
+    def __post_init__(self):
+        try:
+            t = tuple(float(x) for x in self.temperatures)
+        except TypeError:
+            raise ValueError(f"DecodingPolicy: temperatures must be a sequence of numbers, got {self.temperatures!r}") from None
+        object.__setattr__(self, "temperatures", t)
+        if not 1 <= len(t) <= MAX_TEMPERATURES or t[0] != 0.0 or not all(np.isfinite(x) for x in t) or any(b <= a for a, b in zip(t, t[1:])):
+            raise ValueError(f"DecodingPolicy: temperatures must start at 0, rise, and number 1 .. {MAX_TEMPERATURES}, got {t!r}")
+        for name in ("compression_ratio_threshold", "logprob_threshold", "no_speech_threshold"):
+            v = getattr(self, name)
+            if v is not None and not np.isfinite(float(v)):
+                raise ValueError(f"DecodingPolicy: {name} must be finite or None, got {v!r}")
+        if self.no_speech_threshold is not None and self.logprob_threshold is None:
+            raise ValueError("DecodingPolicy: no_speech_threshold requires logprob_threshold (a window is skipped only where both say so)")
+        if self.no_speech_threshold is not None and self.no_speech_token_id is None:
+            raise ValueError("DecodingPolicy: no_speech_threshold requires no_speech_token_id (DecodingPolicy.from_generation_config)")
+        if self.no_speech_token_id is not None and int(self.no_speech_token_id) < 0:
+            raise ValueError(f"DecodingPolicy: no_speech_token_id must be >= 0, got {self.no_speech_token_id!r}")
+        if isinstance(self.seed, bool) or int(self.seed) != self.seed or not 0 <= int(self.seed) < 1 << 64:
+            raise ValueError(f"DecodingPolicy: seed must be an integer in [0, 2^64), got {self.seed!r}")
+
+    @classmethod
+    def from_generation_config(cls, config, **fields) -> "DecodingPolicy":
+        """From HF's ``generation_config.json`` (a dict, the file, or the directory that holds it): ``no_speech_token_id`` is
+        ``no_timestamps_token_id - 1``, as in HF; ``fields`` are the other fields."""
+        if not isinstance(config, dict):
+            path = os.fspath(config)
+            if os.path.isdir(path):
+                path = os.path.join(path, "generation_config.json")
+            with open(path, encoding="utf-8") as f:
+                config = json.load(f)
+        if config.get("no_timestamps_token_id") is None:
+            raise ValueError("DecodingPolicy: the generation config has no no_timestamps_token_id (no_speech_token_id is that id - 1)")
+        return cls(no_speech_token_id=int(config["no_timestamps_token_id"]) - 1, **fields)
+
+
+def compression_ratio(tokens: Sequence[int], vocab_size: int) -> float:
+    """HF's ``_retrieve_compression_ratio``: the ids as ``int(log2(V) / 8) + 1`` little-endian bytes each, their length over the
+    length of their ``zlib.compress``.  Host only."""
+    width = int(math.log2(vocab_size) / 8) + 1
+    raw = b"".join(int(t).to_bytes(width, "little") for t in tokens)
+    return len(raw) / len(zlib.compress(raw))
+
+
+def fallback_decision(policy: DecodingPolicy, ratio: float, avg_logprob: float, no_speech_prob: float):
+    """HF's ``_need_fallback`` for one row -> (needs a retry, is skipped as silence).  Host only."""
+    need = skip = False
+    if policy.compression_ratio_threshold is not None and ratio > policy.compression_ratio_threshold:
+        need = True
+    if policy.logprob_threshold is not None and avg_logprob < policy.logprob_threshold:
+        need = True
+    if policy.no_speech_threshold is not None and avg_logprob < policy.logprob_threshold and no_speech_prob > policy.no_speech_threshold:
+        need, skip = False, True
+    return need, skip
 
 
 def check_beam_args(config: WhisperConfig, spec: GenerationSpec, num_beams: int, length_penalty: float = 1.0, timestamps: bool = False,
@@ -413,6 +527,7 @@ class Whisper(WaveformNet):
             rc = ctx.lib.dex_whisper_encode(ctx.h, f.data_ptr(), f.shape[0], out.data_ptr() if out is not None else None, ms, ws.data_ptr(),
                                             ws.numel(), stream(self.device))
         ctx.check(rc, "dex_whisper_encode")
+        self.encoder_calls = getattr(self, "encoder_calls", 0) + 1          # what ``_trace`` reports under a policy
         return ws
 
     def encode(self, features: torch.Tensor) -> torch.Tensor:
@@ -463,13 +578,25 @@ class Whisper(WaveformNet):
         return torch.from_numpy(sup).to(self.device), torch.from_numpy(beg).to(self.device)
 
     def generate(self, features_or_wavs, spec: GenerationSpec, max_new_tokens: Optional[int] = None, lengths=None, sr: int = SAMPLING_RATE,
-                 timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1):
+                 timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1,
+                 policy: Optional[DecodingPolicy] = None, row_keys=None, seeks=None):
         """Greedy decoding (the module docstring's definition) of features [B, num_mel_bins, frames], or of wavs as ``log_mel`` takes
         them -> (ids [B, n] int32, a row padded with eos after its end; lengths [B] int32, the tokens before a row's eos), both on the
         device.  n is the number of steps decoded: at most ``max_new_tokens`` and ``max_target_positions - len(prompt)``.
         ``timestamps=True`` decodes one window under the long form's step rule (``spec`` with the timestamp fields).
-        ``num_beams`` > 1: beam search, the first two results of ``generate_beam``."""
+        ``num_beams`` > 1: beam search, the first two results of ``generate_beam``.
+        ``policy``: fallback decoding; a third result is a dict of per-row float64 / bool arrays on the host: ``temperature`` (of the
+        attempt that stands), ``avg_logprob``, ``compression_ratio``, ``no_speech_prob`` (NaN without ``no_speech_token_id``),
+        ``skipped`` (the row is silence: length 0) and ``attempts``.  ``row_keys`` [B] (default: the row's index) and ``seeks`` [B]
+        (default 0) are the words of the noise counter."""
         what = "Whisper.generate"
+        if policy is not None:
+            if not isinstance(policy, DecodingPolicy):
+                raise ValueError(f"{what}: policy must be a DecodingPolicy, got {type(policy).__name__}")
+            if num_beams != 1:
+                raise ValueError(f"{what}: num_beams > 1 with a policy is not built (sampling turns beams off; the greedy attempt has none either)")
+        elif row_keys is not None or seeks is not None:
+            raise ValueError(f"{what}: row_keys and seeks belong to a policy")
         if num_beams != 1:
             check_beam_args(self.config, spec, num_beams, length_penalty, timestamps, False, early_stopping, num_return_sequences, what)
             return self.generate_beam(features_or_wavs, spec, num_beams, length_penalty, max_new_tokens, lengths, sr)[:2]
@@ -493,6 +620,8 @@ class Whisper(WaveformNet):
         sup, beg = self._masks(spec)
         prompt = np.ascontiguousarray(np.asarray(spec.prompt_ids, np.int32))
         B = f.shape[0]
+        if policy is not None:
+            return self._generate_policy(f, spec, policy, max_new, timestamps, sup, beg, prompt, row_keys, seeks, what)
         ids = torch.empty(B, max_new, dtype=torch.int32, device=self.device)
         lens = torch.empty(B, dtype=torch.int32, device=self.device)
         ctx, steps, n = self._ctx, C.c_int(0), 0
@@ -510,6 +639,79 @@ class Whisper(WaveformNet):
             ctx.check(rc, "dex_whisper_generate_ts" if timestamps else "dex_whisper_generate")
             n = max(n, steps.value)
         return ids[:, :n], lens
+
+    def _decode_policy(self, f: torch.Tensor, spec: GenerationSpec, policy: DecodingPolicy, max_new: int, timestamps: bool, sup, beg, prompt,
+                       keys, seeks, attempts_out: Optional[list] = None) -> list:
+        """Fallback decoding of at most ``MAX_ROWS`` rows of features: the encoder once, then per attempt one decode of the rows that
+        still need one, from the cross K / V where the encoder left it -> per row a dict ``tokens`` (host ints, no eos), ``temperature``,
+        ``avg_logprob``, ``compression_ratio``, ``no_speech_prob``, ``skipped``, ``attempts``.  ``attempts_out`` receives per attempt
+        the list of its (row, temperature, tokens)."""
+        ctx, dev, B, V = self._ctx, self.device, f.shape[0], self.config.vocab_size
+        ws = self._encode(f, None)
+        probe = policy.no_speech_token_id is not None
+        if probe and not 0 <= int(policy.no_speech_token_id) < V:
+            raise ValueError(f"DecodingPolicy: no_speech_token_id {policy.no_speech_token_id} is outside the vocabulary of {V}")
+        cap = -1 if spec.max_initial_timestamp_index is None else int(spec.max_initial_timestamp_index)
+        nots = int(spec.no_timestamps_token_id) if timestamps else -1
+        u32, out, pending, steps = C.POINTER(C.c_uint32), [None] * B, list(range(B)), C.c_int(0)
+        no_speech = np.full(B, np.nan)
+        for attempt, T in enumerate(policy.temperatures):
+            R = len(pending)
+            rows = np.ascontiguousarray(np.asarray(pending, np.int32))
+            kk = np.ascontiguousarray(np.asarray([keys[r] for r in pending], np.uint32))
+            sk = np.ascontiguousarray(np.asarray([seeks[r] for r in pending], np.int32))
+            ids = torch.empty(R, max_new, dtype=torch.int32, device=dev)
+            lens = torch.empty(R, dtype=torch.int32, device=dev)
+            slp, nsp = torch.zeros(R, dtype=torch.float64, device=dev), torch.zeros(R, dtype=torch.float64, device=dev)
+            scored = torch.empty(R, dtype=torch.int32, device=dev)
+            first = attempt == 0 and probe
+            with torch.cuda.device(dev):
+                rc = ctx.lib.dex_whisper_generate_policy(
+                    ctx.h, i32_ptr(prompt), len(prompt), sup.data_ptr(), beg.data_ptr(), int(spec.eos_token_id), int(timestamps), nots, cap, float(T),
+                    int(policy.seed), attempt, kk.ctypes.data_as(u32), i32_ptr(sk), B, i32_ptr(rows), R, max_new, SYNC_EVERY, ids.data_ptr(), lens.data_ptr(),
+                    slp.data_ptr(), scored.data_ptr(), int(policy.no_speech_token_id) if probe else 0, nsp.data_ptr() if first else None, C.byref(steps),
+                    ws.data_ptr(), ws.numel(), stream(dev))
+            ctx.check(rc, "dex_whisper_generate_policy")
+            n = steps.value
+            # the attempt's one device-to-host copy: ids, lengths and the statistics, as float64 (every int32 is exact in it)
+            host = torch.cat([ids[:, :n].double(), lens[:, None].double(), scored[:, None].double(), slp[:, None], nsp[:, None]], dim=1).cpu().numpy()
+            retry, seen = [], []
+            for a, r in enumerate(pending):
+                length, n_scored, sum_lp = int(host[a, n]), int(host[a, n + 1]), float(host[a, n + 2])
+                if first:
+                    no_speech[r] = float(host[a, n + 3])
+                tokens = host[a, :length].astype(np.int64).tolist()
+                scored_tokens = tokens + [int(spec.eos_token_id)] * (n_scored - length)       # HF scores the emitted eos with the row
+                avg, ratio = sum_lp / n_scored, compression_ratio(scored_tokens, V)
+                need, skip = fallback_decision(policy, ratio, avg, no_speech[r])
+                out[r] = dict(tokens=[] if skip else tokens, temperature=float(T), avg_logprob=avg, compression_ratio=ratio,
+                              no_speech_prob=float(no_speech[r]), skipped=skip, attempts=attempt + 1)
+                seen.append((r, float(T), tokens))
+                if need:
+                    retry.append(r)
+            if attempts_out is not None:
+                attempts_out.append(seen)
+            pending = retry
+            if not pending:
+                break
+        return out
+
+    def _generate_policy(self, f, spec, policy, max_new, timestamps, sup, beg, prompt, row_keys, seeks, what):
+        B = f.shape[0]
+        keys = list(range(B)) if row_keys is None else [int(k) for k in row_keys]
+        seeks = [0] * B if seeks is None else [int(s) for s in seeks]
+        if len(keys) != B or len(seeks) != B or any(not 0 <= k < 1 << 32 for k in keys) or any(not 0 <= s < 1 << 27 for s in seeks):
+            raise ValueError(f"{what}: row_keys and seeks must hold one value per row, keys in [0, 2^32), seeks in [0, 2^27)")
+        rows = []
+        for r in range(0, B, MAX_ROWS):
+            rows += self._decode_policy(f[r:r + MAX_ROWS], spec, policy, max_new, timestamps, sup, beg, prompt, keys[r:r + MAX_ROWS], seeks[r:r + MAX_ROWS])
+        n = max(1, max(len(x["tokens"]) + 1 for x in rows))
+        n = min(n, max_new)
+        ids = np.full((B, n), int(spec.eos_token_id), np.int32)
+        for b, x in enumerate(rows):
+            ids[b, : len(x["tokens"])] = x["tokens"]
+        info = {k: np.asarray([x[k] for x in rows]) for k in ("temperature", "avg_logprob", "compression_ratio", "no_speech_prob", "skipped", "attempts")}
+        return torch.from_numpy(ids).to(self.device), torch.tensor([len(x["tokens"]) for x in rows], dtype=torch.int32, device=self.device), info
 
     def generate_beam(self, features_or_wavs, spec: GenerationSpec, num_beams: int, length_penalty: float = 1.0, max_new_tokens: Optional[int] = None,
                       lengths=None, sr: int = SAMPLING_RATE, trace: bool = False):
@@ -572,10 +774,10 @@ class Whisper(WaveformNet):
         return ids[:, :n], lens, scores
 
     def transcribe(self, wavs, spec: GenerationSpec, vocab: Sequence[str], lengths=None, sr: int = SAMPLING_RATE,
-                   max_new_tokens: Optional[int] = None, num_beams: int = 1, length_penalty: float = 1.0):
+                   max_new_tokens: Optional[int] = None, num_beams: int = 1, length_penalty: float = 1.0, policy: Optional[DecodingPolicy] = None):
         """``wavs`` as ``log_mel`` takes them -> a list of transcripts (``decode`` of each row's tokens; one device-to-host copy).
-        ``num_beams`` > 1 decodes by beam search."""
-        ids, lens = self.generate(wavs, spec, max_new_tokens, lengths, sr, num_beams=num_beams, length_penalty=length_penalty)
+        ``num_beams`` > 1 decodes by beam search; ``policy``: fallback decoding (a row skipped as silence is ``''``)."""
+        ids, lens = self.generate(wavs, spec, max_new_tokens, lengths, sr, num_beams=num_beams, length_penalty=length_penalty, policy=policy)[:2]
         ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
         return [decode(ids[b, : int(lens[b])], vocab, spec.eos_token_id) for b in range(ids.shape[0])]
 
@@ -635,16 +837,35 @@ class Whisper(WaveformNet):
         return out
 
     def generate_segments(self, wavs, spec: GenerationSpec, lengths=None, sr: int = SAMPLING_RATE, max_new_tokens: Optional[int] = None,
-                          _trace: Optional[list] = None):
+                          _trace: Optional[list] = None, policy: Optional[DecodingPolicy] = None, row_keys=None):
         """Long-form decoding (the module docstring's window loop) of ``wavs`` as ``log_mel_long`` takes them -> per row a list of
         segments ``{"start", "end", "tokens"}``: seconds in float64 and the segment's ids (its timestamps included) as host ints.
-        ``_trace`` (a list, for tests and measurement) receives per network call the list of its (row, seek, n, new ids)."""
+        ``_trace`` (a list, for tests and measurement) receives per network call the list of its (row, seek, n, new ids).
+        ``policy``: fallback decoding of every window; a segment also carries its window's ``temperature``, ``avg_logprob``,
+        ``compression_ratio`` and ``no_speech_prob``, a window skipped as silence emits none, and ``_trace`` receives per window group a
+        dict: ``encoder_calls`` (1), ``windows`` [(row, seek, n)], ``attempts`` (per attempt its (row, temperature, ids)) and ``skipped``
+        [(row, seek, n)].  ``row_keys`` [B] (default: the row's index): the rows' word of the noise counter."""
         what = "Whisper.generate_segments"
         self._need_weights(what)
         self._timestamp_spec(spec, what)
+        if policy is not None and not isinstance(policy, DecodingPolicy):
+            raise ValueError(f"{what}: policy must be a DecodingPolicy, got {type(policy).__name__}")
+        if policy is None and row_keys is not None:
+            raise ValueError(f"{what}: row_keys belong to a policy")
         feats, frames = self.log_mel_long(wavs, lengths, sr)
         B, W, tb = feats.shape[0], 2 * self.config.max_source_positions, int(spec.no_timestamps_token_id) + 1
         seek, out = [0] * B, [[] for _ in range(B)]
+        if policy is not None:
+            keys = list(range(B)) if row_keys is None else [int(k) for k in row_keys]
+            if len(keys) != B or any(not 0 <= k < 1 << 32 for k in keys):
+                raise ValueError(f"{what}: row_keys must hold one value in [0, 2^32) per row")
+            c = self.config
+            room = c.max_target_positions - len(spec.prompt_ids)
+            max_new = room if max_new_tokens is None else int(max_new_tokens)
+            if not spec.prompt_ids or max_new < 1:
+                raise ValueError(f"{what}: max_new_tokens must be >= 1 and the prompt of {len(spec.prompt_ids)} ids leave room in the cache")
+            sup, beg = self._masks(spec)
+            prompt = np.ascontiguousarray(np.asarray(spec.prompt_ids, np.int32))
         while True:
             active = [b for b in range(B) if seek[b] < int(frames[b])]
             if not active:
@@ -652,6 +873,23 @@ class Whisper(WaveformNet):
             for r in range(0, len(active), MAX_ROWS):
                 rows = active[r:r + MAX_ROWS]
                 ns = [min(int(frames[b]) - seek[b], W) for b in rows]
+                if policy is not None:
+                    calls, attempts = getattr(self, "encoder_calls", 0), []
+                    res = self._decode_policy(self._gather(feats, rows, [seek[b] for b in rows], ns), spec, policy, max_new, True, sup, beg, prompt,
+                                              [keys[b] for b in rows], [seek[b] for b in rows], attempts)
+                    if _trace is not None:
+                        _trace.append(dict(encoder_calls=self.encoder_calls - calls, windows=[(b, seek[b], ns[a]) for a, b in enumerate(rows)],
+                                           attempts=[[(rows[a], T, t) for a, T, t in att] for att in attempts],
+                                           skipped=[(b, seek[b], ns[a]) for a, b in enumerate(rows) if res[a]["skipped"]]))
+                    for a, b in enumerate(rows):
+                        if res[a]["skipped"]:
+                            seek[b] += ns[a]
+                            continue
+                        segments, advance = retrieve_segments(res[a]["tokens"], tb, seek[b], ns[a])
+                        extra = {k: res[a][k] for k in ("temperature", "avg_logprob", "compression_ratio", "no_speech_prob")}
+                        out[b] += [dict(s, **extra) for s in segments]
+                        seek[b] += advance
+                    continue
                 ids, lens = self.generate(self._gather(feats, rows, [seek[b] for b in rows], ns), spec, max_new_tokens, timestamps=True)
                 host = torch.cat([ids, lens[:, None]], dim=1).cpu().numpy()                 # the window's one device-to-host copy
                 if _trace is not None:                                                      # one entry per network call: (row, seek, n, ids)
@@ -662,9 +900,10 @@ class Whisper(WaveformNet):
                     seek[b] += advance
 
     def transcribe_long(self, wavs, spec: GenerationSpec, vocab: Sequence[str], lengths=None, sr: int = SAMPLING_RATE,
-                        max_new_tokens: Optional[int] = None):
-        """``wavs`` of any length -> a list of transcripts: ``decode`` of each row's segments' ids joined."""
-        rows = self.generate_segments(wavs, spec, lengths, sr, max_new_tokens)
+                        max_new_tokens: Optional[int] = None, policy: Optional[DecodingPolicy] = None):
+        """``wavs`` of any length -> a list of transcripts: ``decode`` of each row's segments' ids joined.  ``policy``: fallback
+        decoding of every window."""
+        rows = self.generate_segments(wavs, spec, lengths, sr, max_new_tokens, policy=policy)
         return [decode([t for seg in segments for t in seg["tokens"]], vocab, spec.eos_token_id) for segments in rows]
 
 
@@ -695,14 +934,19 @@ def retrieve_segments(tokens: Sequence[int], timestamp_begin: int, seek: int, n:
 
 def whisper_score(wavs, texts: Sequence[str], model: Optional[Whisper] = None, spec: Optional[GenerationSpec] = None,
                   vocab: Optional[Sequence[str]] = None, sr: int = SAMPLING_RATE, lengths=None, long_form: bool = False, num_beams: int = 1,
-                  length_penalty: float = 1.0):
+                  length_penalty: float = 1.0, policy: Optional[DecodingPolicy] = None):
     """Every wav transcribed by ``model``; CER and WER of ``asr.normalize_sentence(transcript)`` against
     ``asr.normalize_sentence(text)`` (the reference's normaliser, not Whisper's: numbers stay as written) ->
     (transcripts, cer_mean, cer_stderr, wer_mean, wer_stderr), the errors ``np.std / sqrt(n)``.  ``long_form=True``: rows of any
-    length, through ``transcribe_long`` (``spec`` with the timestamp fields).  ``num_beams`` > 1: beam search (not with the long form)."""
+    length, through ``transcribe_long`` (``spec`` with the timestamp fields).  ``num_beams`` > 1: beam search (not with the long form).
+    ``policy``: fallback decoding, short or long form (not with beams)."""
     if not isinstance(model, Whisper) or spec is None or vocab is None:
         raise ValueError("whisper_score: pass model=Whisper(...) with the checkpoint's weights loaded, spec= and vocab= (the library ships none)")
-    if num_beams != 1:
+    if policy is not None:
+        if num_beams != 1:
+            raise ValueError("whisper_score: num_beams > 1 with a policy is not built")
+        preds = (model.transcribe_long if long_form else model.transcribe)(wavs, spec, vocab, lengths, sr, policy=policy)
+    elif num_beams != 1:
         check_beam_args(model.config, spec, num_beams, length_penalty, long_form=long_form, what="whisper_score")
         preds = model.transcribe(wavs, spec, vocab, lengths, sr, num_beams=num_beams, length_penalty=length_penalty)
     else:

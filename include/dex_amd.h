@@ -923,6 +923,28 @@ int  dex_whisper_generate_ts(DexWhisper* w, const int32_t* prompt_host, int n_pr
 int  dex_whisper_pick_ts(const float* logits_dev, int B, int V, const uint8_t* mask_dev, int eos, int no_timestamps_token_id,
                          int max_initial_timestamp_index, int32_t* finished_dev, int32_t* lengths_dev, int32_t* count_dev,
                          int32_t* ids_dev, int ld_ids, int step, int32_t* last_timestamp_dev, int32_t* n_new_dev, dex_stream_t stream);
+/* ---- decoding under a policy: temperature fallback with the log-prob and no-speech statistics (dex_tts_amd/whisper.py states the
+ * definition).  One attempt of B <= `encoded` rows after dex_whisper_encode of `encoded` rows in the same workspace: decode row b reads
+ * the cross-attention keys and values of encoded row rows_host[b], so a retry of some rows does not run the encoder again.
+ * `timestamps` != 0 decodes under the timestamp rule (the arguments of dex_whisper_generate_ts).  temperature 0 is greedy (the ids of
+ * dex_whisper_generate / _generate_ts bit for bit); above 0 the id is the Gumbel-max sample at Philox4x32-10 counter (id >> 2, step,
+ * attempt + 16 x seek_host[b], row_keys_host[b]), key `seed`, word id & 3.  sum_logprob_dev [B] (fp64) and n_scored_dev [B]: the sum
+ * over a row's new tokens (its eos included) of the fp64 log-softmax of the masked logits at the token, and their count.
+ * no_speech_prob_dev [B] (fp64, or NULL): the softmax of the unprocessed logits at prompt position 0 at no_speech_token_id. */
+int  dex_whisper_generate_policy(DexWhisper* w, const int32_t* prompt_host, int n_prompt, const uint8_t* suppress_dev, const uint8_t* begin_dev,
+                                 int eos, int timestamps, int no_timestamps_token_id, int max_initial_timestamp_index, double temperature,
+                                 uint64_t seed, int attempt, const uint32_t* row_keys_host, const int32_t* seek_host, int encoded,
+                                 const int32_t* rows_host, int B, int max_new, int sync_every, int32_t* ids_dev, int32_t* lengths_dev,
+                                 double* sum_logprob_dev, int32_t* n_scored_dev, int no_speech_token_id, double* no_speech_prob_dev,
+                                 int* steps_host, void* workspace_dev, size_t workspace_bytes, dex_stream_t stream);
+/* the policy step tail alone, as dex_whisper_pick (timestamps == 0) or dex_whisper_pick_ts (timestamps != 0, step >= 2) with B <=
+ * DEX_WHISPER_MAX_B: `step` is the counter's step word; the chosen id's log-probability is added to sum_logprob_dev[b] and one to
+ * n_scored_dev[b] unless the row's finished flag was set */
+int  dex_whisper_pick_policy(const float* logits_dev, int B, int V, const uint8_t* mask_dev, int eos, int timestamps, int no_timestamps_token_id,
+                             int max_initial_timestamp_index, double temperature, uint64_t seed, int attempt, const uint32_t* row_keys_host,
+                             const int32_t* seek_host, int32_t* finished_dev, int32_t* lengths_dev, int32_t* count_dev, int32_t* ids_dev,
+                             int ld_ids, int step, int32_t* last_timestamp_dev, int32_t* n_new_dev, double* sum_logprob_dev,
+                             int32_t* n_scored_dev, dex_stream_t stream);
 /* ---- beam search (dex_tts_amd/whisper.py states the definition): U utterances of K beams are the U x K rows u K + r of a step */
 #define DEX_WHISPER_MIN_BEAMS 2
 #define DEX_WHISPER_MAX_BEAMS 8

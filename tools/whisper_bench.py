@@ -25,7 +25,13 @@ encoder, decode) run one by one, and the long front end alone.
 Beam search at whisper-large-v3 geometry, random weights, eos suppressed: the per-token time of ``generate_beam`` at U utterances of
 K beams against the greedy ``generate`` on U x K independent rows (the same row count, each row with its own cross-attention K / V)
 and against the torch graph with a key/value cache where a beam step is ``log_softmax`` + ``topk`` + ``index_select`` of the cache;
-the three alternate inside every repetition; medians and the run-to-run spread (max - min) of each."""
+the three alternate inside every repetition; medians and the run-to-run spread (max - min) of each.
+
+    python tools/whisper_bench.py --policy [--batches 1,8] [--reps 5] [--tokens 48]
+
+Fallback decoding at whisper-large-v3 geometry, random weights, eos suppressed: per token the plain greedy tail, the policy tail at
+T = 0 and at T = 0.4 of the same build, alternating inside every repetition, with their spreads; and one retried window (no encoder)
+against a fresh one."""
 import argparse
 import ctypes as C
 import json
@@ -327,6 +333,40 @@ def bench_beams(cfg, K, batches, reps, warmup, n_tok, seed):
         return rows
 
 
+def bench_policy(cfg, batches, reps, warmup, n_tok, seed):
+    """Per token: the plain greedy tail, the policy tail at T = 0 (one attempt) and at T = 0.4 (the second of two attempts: a log-prob
+    threshold of 0 refuses every first one), alternating inside every repetition, with the run-to-run spread of each; and one retried
+    window (the second attempt: no encoder) against a fresh window (encoder + one attempt)."""
+    with torch.no_grad():
+        lib = whisper.Whisper(R.library_config(cfg), "cuda").load_state_dict(make_weights(cfg, seed, "cuda"))
+        eos = cfg.vocab_size - 1
+        spec = whisper.GenerationSpec(PROMPT, (eos,), (eos,), eos)
+        one = whisper.DecodingPolicy(temperatures=(0.0,))
+        two = whisper.DecodingPolicy(temperatures=(0.0, 0.4), logprob_threshold=0.0)
+        rows = []
+        for B in batches:
+            feat = lib.log_mel(make_wavs(B, seed).cuda())
+            t = {k: [] for k in ("plain", "policy_t0", "policy_t04", "fresh_window", "retried_window")}
+            for r in range(warmup + reps):
+                p1, _ = timed(lambda: lib.generate(feat, spec, 1))
+                pn, _ = timed(lambda: lib.generate(feat, spec, n_tok))
+                a1, _ = timed(lambda: lib.generate(feat, spec, 1, policy=one))
+                an, (ids, _, _) = timed(lambda: lib.generate(feat, spec, n_tok, policy=one))
+                b1, _ = timed(lambda: lib.generate(feat, spec, 1, policy=two))
+                bn, (_, _, info) = timed(lambda: lib.generate(feat, spec, n_tok, policy=two))
+                assert ids.shape[1] == n_tok and (info["attempts"] == 2).all()
+                if r >= warmup:
+                    t0 = (an - a1) / (n_tok - 1)
+                    for k, v in zip(t, ((pn - p1) / (n_tok - 1), t0, (bn - b1) / (n_tok - 1) - t0, an, bn - an)):
+                        t[k].append(v)
+            row = dict(model="large-v3", B=B, tokens=n_tok, reps=reps)
+            for k, v in t.items():
+                row[f"{k}_ms" if "window" in k else f"{k}_per_token_ms"], row[f"{k}_spread_ms"] = med(v), max(v) - min(v)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        return rows
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="base.en,large-v3")
@@ -338,7 +378,15 @@ def main(argv=None):
     ap.add_argument("--json", default=None)
     ap.add_argument("--long", type=float, default=None, metavar="SECONDS", help="the long-form case alone (large-v3 geometry, B = 1 and 8 by default)")
     ap.add_argument("--beams", type=int, default=None, metavar="K", help="the beam-search case alone (large-v3 geometry, U = 1 and 6 by default)")
+    ap.add_argument("--policy", action="store_true", help="the fallback-decoding case alone (large-v3 geometry, B = 1 and 8 by default)")
     a = ap.parse_args(argv)
+    if a.policy:
+        out = {"policy": bench_policy(MODELS["large-v3"], [int(b) for b in (a.batches if a.batches != "1,8,32" else "1,8").split(",")], a.reps, a.warmup,
+                                      a.tokens, a.seed)}
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     if a.beams is not None:
         out = {"beams": bench_beams(MODELS["large-v3"], a.beams, [int(b) for b in (a.batches if a.batches != "1,8,32" else "1,6").split(",")], a.reps,
                                     a.warmup, a.tokens, a.seed)}
