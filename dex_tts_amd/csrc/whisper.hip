@@ -25,16 +25,17 @@
 //                        attends over the encoder frames.  Four lanes share a key's dot product (16 dims each, two shuffles), the
 //                        scores sit in LDS, the maximum is exact, the sum of exponentials and the weighted sum of V (one lane per
 //                        channel, keys dealt to the four waves) are reduced in a fixed order.
-//   wsp_pick_kernel      the greedy step tail, one workgroup per row: logits finished from the partials, suppression, argmax with the
-//                        lowest index on ties, finished / length bookkeeping, and the gather of the next step's embed_tokens +
-//                        embed_positions row.  A step needs no host value.
-//   wsp_pick_ts_kernel   the same tail under the timestamp rule of long-form decoding (WhisperTimeStampLogitsProcessor): the masks of
-//                        the rule as index ranges from the row's own state (its last two ids, its last timestamp, its new-token
-//                        count, all on the device), the best text id, the best timestamp id and logsumexp(timestamps) in one pass
-//                        over the logits, reduced in a fixed order.  Both kernels end in pick_commit.
+//   tail_first_sweep     the one pass over a row's logits that every greedy and policy tail starts with, plain or (rule_ranges: the
+//                        masks of WhisperTimeStampLogitsProcessor as index ranges from the row's own state - its last two ids, its
+//                        last timestamp, its new-token count, all on the device) under the timestamp rule of long-form decoding:
+//                        logits finished from the partials, suppression, the best text id, the best timestamp id and
+//                        logsumexp(timestamps), reduced in a fixed order, the lowest index on ties.
+//   wsp_pick_kernel      the greedy step tail, one workgroup per row: the plain sweep, then pick_commit: finished / length
+//                        bookkeeping and the gather of the next step's embed_tokens + embed_positions row.  A step needs no host value.
+//   wsp_pick_ts_kernel   the same tail under the timestamp rule: the rule's sweep, then pick_commit.
 //   wsp_pick_policy_kernel, wsp_nospeech_kernel, wsp_attend_rows_kernel
-//                        fallback decoding (DecodingPolicy).  The tail in its plain and timestamp-rule forms: the greedy tail's
-//                        pass unchanged (the same ids at T = 0), then the fp64 log-sum-exp of the surviving ids, at T > 0 the
+//                        fallback decoding (DecodingPolicy).  The tail in its plain and timestamp-rule forms: the same sweep (so
+//                        the same ids at T = 0), then the fp64 log-sum-exp of the surviving ids, at T > 0 the
 //                        Gumbel-max sample on Philox4x32-10 noise, and the chosen id's log-probability added to the row's sums.
 //                        The probe: the fp64 softmax of the unprocessed logits of prompt position 0 at <|nospeech|>.  The rows
 //                        form of the cross-attention reads the cache row of the encoded batch a retried row came from: a retry
@@ -46,6 +47,9 @@
 //                        K score rows in LDS, per query the plain kernel's operations in the plain kernel's order; the tail is three
 //                        launches: the fp64 log-softmax sums by chunk of 2048 ids, every chunk's 2K best by score, and per
 //                        utterance the top 2K of those, the running set, the pool, the stop, the ancestry and the next embeddings.
+// Host: decode_loop is the one loop of the greedy, rule, policy and beam decoders (prompt fill, steps, the early exit on a device
+// counter); each hands it the launch of its tail.  check_decode_args refuses what they all refuse; pick_over_logits and pick_in_step
+// build the tail's parameters for the dex_whisper_pick* entry points and for a step of a decode.
 // Every per-row sum has an order fixed by the config and the position: a row's logits and ids are bitwise those of the row alone.
 #include <hip/hip_runtime.h>
 
@@ -501,34 +505,11 @@ __device__ __forceinline__ void pick_commit(const PickP& p, int b, int arg, int*
     for (int c = threadIdx.x; c < p.d; c += 1024) p.h[(long)b * p.d + c] = e[c] + q[c];
 }
 
-// row blockIdx.x: the logits finished from the partials (stored where `logits` is given); pick: the id of this step and the bookkeeping;
-// next_pos >= 0: h = embed_tokens[id] + embed_positions[next_pos]
-__global__ __launch_bounds__(1024) void wsp_pick_kernel(const PickP p) {
-    __shared__ float bv[16];
-    __shared__ int bi[16];
-    __shared__ int chosen;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
-    float best = -INFINITY;
-    int arg = 0x7fffffff;
-    for (int v = tid; v < p.V; v += 1024) {
-        float x = finished(p.P, p.KS, p.ss, (long)b * p.V + v, nullptr, 0);
-        if (p.logits) p.logits[(long)b * p.ldl + v] = x;
-        if (p.mask && p.mask[v]) x = -INFINITY;
-        better(best, arg, x, v);
-    }
-    if (!p.pick) return;
-    for (int o = 32; o > 0; o >>= 1) { const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(arg, o); better(best, arg, ov, oi); }
-    if (lane == 0) { bv[wave] = best; bi[wave] = arg; }
-    __syncthreads();
-    if (tid == 0)
-        for (int w = 1; w < 16; ++w) better(best, arg, bv[w], bi[w]);
-    pick_commit(p, b, arg, &chosen, 0, nullptr, nullptr);
-}
-
-// The tail under the timestamp rule.  tb = the first timestamp id (no_timestamps + 1), max_init >= 0: the cap of the first timestamp;
-// last_ts [B] the row's last emitted timestamp id (-1: none), n_new [B] its new-token count; its last two new ids are read from `ids`
-// at columns step - 1 and step - 2
-struct PickTsP { PickP k; int nots, tb, max_init; int *last_ts, *n_new; };
+// The timestamp rule of long-form decoding (WhisperTimeStampLogitsProcessor) in a tail's parameters.  tb = the first timestamp id
+// (no_timestamps + 1), max_init >= 0: the cap of the first timestamp; last_ts [B] the row's last emitted timestamp id (-1: none),
+// n_new [B] its new-token count; its last two new ids are read from `ids` at columns step - 1 and step - 2
+struct RuleP { int nots, tb, max_init; int *last_ts, *n_new; };
+struct PickTsP { PickP k; RuleP r; };
 
 // (m, s): a maximum and sum exp(x - m) over a set of values; the union of two sets.  Symmetric in its operands, bit for bit
 __device__ __forceinline__ void lse_join(float& m, float& s, float om, float os) {
@@ -537,74 +518,134 @@ __device__ __forceinline__ void lse_join(float& m, float& s, float om, float os)
     m = M; s = a + c;
 }
 
-// row blockIdx.x, as wsp_pick_kernel with the rule of WhisperTimeStampLogitsProcessor between the masks and the argmax.  Every mask of
-// the rule is an index range fixed by the row's state, so a thread decides an id's fate from registers: text ids (below tb) live in
-// [text_lo, tb), timestamps in [ts_lo, ts_hi], no_timestamps never.  A masked id does not compete; where nothing competes (a row of
-// NaN) the id is 0.  Thread t owns ids t, t + 1024, ...; the wave butterfly and the 16 waves in order fix the order of every
-// reduction from V alone
-__global__ __launch_bounds__(1024) void wsp_pick_ts_kernel(const PickTsP q) {
-    __shared__ float tv[16], sv[16], mv[16], lv[16];
-    __shared__ int ti[16], si[16];
-    __shared__ int chosen;
-    const PickP& p = q.k;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x, V = p.V, tb = q.tb;
-    const int i = q.n_new[b], seen = q.last_ts[b];
-    const int last = i >= 1 ? p.ids[(long)b * p.ld_ids + p.step - 1] : -1, pen = i >= 2 ? p.ids[(long)b * p.ld_ids + p.step - 2] : -1;
-    const bool last_ts = i >= 1 && last >= tb, pen_ts = i < 2 || pen >= tb;
-    int text_lo = 0, ts_lo = tb, ts_hi = V - 1;
+// Every mask of the rule is an index range fixed by the row's state, so a thread decides an id's fate from registers: text ids
+// (below tb) live in [text_lo, tb), timestamps in [ts_lo, ts_hi], no_timestamps never.  The state: the row's new-token count, its
+// last timestamp `seen`, its last and penultimate new ids.  Without the rule tb = V: every id is text
+struct Ranges { int text_lo, ts_lo, ts_hi; };
+__device__ __forceinline__ Ranges rule_ranges(int V, int tb, int eos, int max_init, int n_new, int seen, int last, int pen) {
+    const bool last_ts = n_new >= 1 && last >= tb, pen_ts = n_new < 2 || pen >= tb;
+    Ranges g{0, tb, V - 1};
     if (last_ts) {
-        if (pen_ts) ts_lo = V;                       // a pair is closed: text next
-        else text_lo = p.eos;                        // a lone timestamp: its partner (or eos) next
+        if (pen_ts) g.ts_lo = V;                     // a pair is closed: text next
+        else g.text_lo = eos;                        // a lone timestamp: its partner (or eos) next
     }
     if (seen >= 0) {                                 // timestamps never decrease, and only a pair's partner may repeat
         const int lo = (last_ts && !pen_ts) ? seen : seen + 1;
-        ts_lo = ts_lo > lo ? ts_lo : lo;
+        g.ts_lo = g.ts_lo > lo ? g.ts_lo : lo;
     }
-    if (i == 0) {
-        text_lo = tb;
-        if (q.max_init >= 0 && tb + q.max_init < ts_hi) ts_hi = tb + q.max_init;
+    if (n_new == 0) {
+        g.text_lo = tb;
+        if (max_init >= 0 && tb + max_init < g.ts_hi) g.ts_hi = tb + max_init;
     }
+    return g;
+}
+
+// the ranges of row b at this step (TS false: the plain tail's, every id open)
+template <bool TS>
+__device__ __forceinline__ Ranges row_ranges(const PickP& p, const RuleP& r, int b) {
+    if constexpr (TS) {
+        const int i = r.n_new[b];
+        const int* at = p.ids + (long)b * p.ld_ids + p.step;
+        return rule_ranges(p.V, r.tb, p.eos, r.max_init, i, r.last_ts[b], i >= 1 ? at[-1] : -1, i >= 2 ? at[-2] : -1);
+    } else {
+        return Ranges{0, p.V, p.V - 1};
+    }
+}
+
+// whether id v competes before the rule's last part
+template <bool TS>
+__device__ __forceinline__ bool open_id(const PickP& p, const RuleP& r, const Ranges& g, int v) {
+    if (p.mask && p.mask[v]) return false;
+    if constexpr (TS) return v != r.nots && (v < r.tb ? v >= g.text_lo : (v >= g.ts_lo && v <= g.ts_hi));
+    return true;
+}
+
+// The first sweep of every tail over row b's logits, finished from the partials.  Thread t owns ids t, t + 1024, ...; the wave
+// butterfly and the 16 waves in order fix the order of every reduction from V alone.  TS: the best text id, the best timestamp id
+// and logsumexp(timestamps) in one pass; a closed id does not compete.  Plain: the logits are stored where `logits` is given, a
+// masked id competes as -inf at its own index, and false is returned before any reduction where pick is 0.  Thread 0 leaves the
+// greedy id `arg` (>= V: nothing competed, a row of NaN), its logit `top`, and `force`: logsumexp(timestamps) > max(text), the
+// timestamps' summed probability beats every text id (no normaliser is needed) and the id is the best timestamp
+struct Sweep { int arg; float top; bool force; };
+template <bool TS>
+__device__ __forceinline__ bool tail_first_sweep(const PickP& p, const RuleP& r, const Ranges& g, int b, Sweep& out) {
+    __shared__ float tv[16], sv[TS ? 16 : 1], mv[TS ? 16 : 1], lv[TS ? 16 : 1];
+    __shared__ int ti[16], si[TS ? 16 : 1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, V = p.V;
     float bt = -INFINITY, bs = -INFINITY, m = -INFINITY, s = 0.f;
     int at = 0x7fffffff, as = 0x7fffffff;
     for (int v = tid; v < V; v += 1024) {
-        if (v == q.nots || (p.mask && p.mask[v])) continue;
-        if (v < tb) {
-            if (v >= text_lo) better(bt, at, finished(p.P, p.KS, p.ss, (long)b * V + v, nullptr, 0), v);
-        } else if (v >= ts_lo && v <= ts_hi) {
+        if constexpr (TS) {
+            if (!open_id<true>(p, r, g, v)) continue;
             const float x = finished(p.P, p.KS, p.ss, (long)b * V + v, nullptr, 0);
-            better(bs, as, x, v);
-            lse_join(m, s, x, 1.f);
+            if (v < r.tb) better(bt, at, x, v);
+            else { better(bs, as, x, v); lse_join(m, s, x, 1.f); }
+        } else {
+            float x = finished(p.P, p.KS, p.ss, (long)b * V + v, nullptr, 0);
+            if (p.logits) p.logits[(long)b * p.ldl + v] = x;
+            if (!open_id<false>(p, r, g, v)) x = -INFINITY;
+            better(bt, at, x, v);
         }
     }
+    if constexpr (!TS)
+        if (!p.pick) return false;
     for (int o = 32; o > 0; o >>= 1) {
         better(bt, at, __shfl_xor(bt, o), __shfl_xor(at, o));
-        better(bs, as, __shfl_xor(bs, o), __shfl_xor(as, o));
-        lse_join(m, s, __shfl_xor(m, o), __shfl_xor(s, o));
+        if constexpr (TS) {
+            better(bs, as, __shfl_xor(bs, o), __shfl_xor(as, o));
+            lse_join(m, s, __shfl_xor(m, o), __shfl_xor(s, o));
+        }
     }
-    if (lane == 0) { tv[wave] = bt; ti[wave] = at; sv[wave] = bs; si[wave] = as; mv[wave] = m; lv[wave] = s; }
+    if (lane == 0) {
+        tv[wave] = bt; ti[wave] = at;
+        if constexpr (TS) { sv[wave] = bs; si[wave] = as; mv[wave] = m; lv[wave] = s; }
+    }
     __syncthreads();
-    int arg = 0;
     if (tid == 0) {
-        for (int w = 1; w < 16; ++w) { better(bt, at, tv[w], ti[w]); better(bs, as, sv[w], si[w]); lse_join(m, s, mv[w], lv[w]); }
-        // logsumexp(timestamps) > max(text): the timestamps' summed probability beats every text id; no normaliser is needed
-        const bool force = m + logf(s) > bt;
-        arg = as;
-        if (!force) { float bv = bt; arg = at; better(bv, arg, bs, as); }
+        for (int w = 1; w < 16; ++w) {
+            better(bt, at, tv[w], ti[w]);
+            if constexpr (TS) { better(bs, as, sv[w], si[w]); lse_join(m, s, mv[w], lv[w]); }
+        }
+        out = Sweep{at, bt, false};
+        if constexpr (TS) {
+            out.force = m + logf(s) > bt;
+            if (out.force) { out.arg = as; out.top = bs; }
+            else better(out.top, out.arg, bs, as);
+        }
     }
-    pick_commit(p, b, arg, &chosen, tb, q.last_ts, q.n_new);
+    return true;
+}
+
+// row blockIdx.x: the first sweep in its plain form (the logits stored where `logits` is given); pick: the id of this step and the
+// bookkeeping; next_pos >= 0: h = embed_tokens[id] + embed_positions[next_pos]
+__global__ __launch_bounds__(1024) void wsp_pick_kernel(const PickP p) {
+    __shared__ int chosen;
+    const int b = blockIdx.x;
+    Sweep w{};
+    if (!tail_first_sweep<false>(p, RuleP{}, row_ranges<false>(p, RuleP{}, b), b, w)) return;
+    pick_commit(p, b, w.arg, &chosen, 0, nullptr, nullptr);
+}
+
+// row blockIdx.x, as wsp_pick_kernel with the rule of WhisperTimeStampLogitsProcessor between the masks and the argmax
+__global__ __launch_bounds__(1024) void wsp_pick_ts_kernel(const PickTsP q) {
+    __shared__ int chosen;
+    const int b = blockIdx.x;
+    Sweep w{};
+    tail_first_sweep<true>(q.k, q.r, row_ranges<true>(q.k, q.r, b), b, w);
+    pick_commit(q.k, b, w.arg, &chosen, q.r.tb, q.r.last_ts, q.r.n_new);
 }
 
 // ------------------------------------------------------------------------------------------------------------ policy step tail
 // The tail of decoding under a DecodingPolicy (temperature fallback with the log-prob statistics), plain (TS false) and under the
-// timestamp rule.  Sweep 1 is the greedy tail's: the same ownership (thread t owns ids t, t + 1024, ...), the same fp32 reductions in
-// the same order, so the rule's decision and at T = 0 the id are those of wsp_pick_kernel / wsp_pick_ts_kernel bit for bit.  It fixes
-// the surviving ids and their maximum M.  Sweep 2 (the row now sits in L2) sums exp(x - M) over the survivors in fp64 - a thread's ids
+// timestamp rule.  Sweep 1 is tail_first_sweep, the body of wsp_pick_kernel / wsp_pick_ts_kernel: the rule's decision and at T = 0
+// the id are theirs because the code is.  It fixes the surviving ids and their maximum M.
+// Sweep 2 (the row now sits in L2) sums exp(x - M) over the survivors in fp64 - a thread's ids
 // in order, the wave butterfly, the 16 waves in order: fixed by V alone - and at T > 0 takes the argmax of x / T + g, lowest index on
 // ties, g = -log(-log(u)) the Gumbel noise of id v: u = (w + 0.5) 2^-32, w word v & 3 of Philox4x32-10 at counter (v >> 2, step,
 // attempt + 16 seek, row key) under the key (seed low, seed high).  The chosen id's log-probability x - M - log(sum) is added to the
 // row's sum_lp and one to n_scored unless the row had finished; the bookkeeping is pick_commit's.
 struct RowKeys { uint32_t key[WB], c2[WB]; };
-struct PolP { PickP k; int nots, tb, max_init; int *last_ts, *n_new; double T; uint32_t k0, k1; RowKeys rk; double* sum_lp; int* n_scored; };
+struct PolP { PickP k; RuleP r; double T; uint32_t k0, k1; RowKeys rk; double* sum_lp; int* n_scored; };
 
 __device__ __forceinline__ uint32_t philox_word(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, int word) {
 #pragma unroll
@@ -623,74 +664,17 @@ __device__ __forceinline__ void better64(double& v, int& i, double ov, int oi) {
 
 template <bool TS>
 __global__ __launch_bounds__(1024) void wsp_pick_policy_kernel(const PolP q) {
-    __shared__ float tv[16], sv[16], mv[16], lv[16];
-    __shared__ int ti[16], si[16], di[16];
+    __shared__ int di[16];
     __shared__ double dv[16], ds[16];
     __shared__ int chosen, s_force, s_arg, s_fin;
     __shared__ float s_max;
     __shared__ double s_lse;
     const PickP& p = q.k;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x, V = p.V, tb = TS ? q.tb : V;
-    int text_lo = 0, ts_lo = tb, ts_hi = V - 1;
-    if constexpr (TS) {                                  // the ranges of wsp_pick_ts_kernel
-        const int i = q.n_new[b], seen = q.last_ts[b];
-        const int last = i >= 1 ? p.ids[(long)b * p.ld_ids + p.step - 1] : -1, pen = i >= 2 ? p.ids[(long)b * p.ld_ids + p.step - 2] : -1;
-        const bool last_ts = i >= 1 && last >= tb, pen_ts = i < 2 || pen >= tb;
-        if (last_ts) {
-            if (pen_ts) ts_lo = V;
-            else text_lo = p.eos;
-        }
-        if (seen >= 0) {
-            const int lo = (last_ts && !pen_ts) ? seen : seen + 1;
-            ts_lo = ts_lo > lo ? ts_lo : lo;
-        }
-        if (i == 0) {
-            text_lo = tb;
-            if (q.max_init >= 0 && tb + q.max_init < ts_hi) ts_hi = tb + q.max_init;
-        }
-    }
-    // whether id v competes before the rule's last part (the plain form's masked ids compete as -inf, as in wsp_pick_kernel)
-    auto open = [&](int v) -> bool {
-        if (p.mask && p.mask[v]) return false;
-        if constexpr (TS) return v != q.nots && (v < tb ? v >= text_lo : (v >= ts_lo && v <= ts_hi));
-        return true;
-    };
-    float bt = -INFINITY, bs = -INFINITY, m = -INFINITY, s = 0.f;
-    int at = 0x7fffffff, as = 0x7fffffff;
-    for (int v = tid; v < V; v += 1024) {
-        if constexpr (TS) {
-            if (!open(v)) continue;
-            const float x = finished(p.P, p.KS, p.ss, (long)b * V + v, nullptr, 0);
-            if (v < tb) better(bt, at, x, v);
-            else { better(bs, as, x, v); lse_join(m, s, x, 1.f); }
-        } else {
-            better(bt, at, open(v) ? finished(p.P, p.KS, p.ss, (long)b * V + v, nullptr, 0) : -INFINITY, v);
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        better(bt, at, __shfl_xor(bt, o), __shfl_xor(at, o));
-        if constexpr (TS) {
-            better(bs, as, __shfl_xor(bs, o), __shfl_xor(as, o));
-            lse_join(m, s, __shfl_xor(m, o), __shfl_xor(s, o));
-        }
-    }
-    if (lane == 0) { tv[wave] = bt; ti[wave] = at; sv[wave] = bs; si[wave] = as; mv[wave] = m; lv[wave] = s; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 16; ++w) {
-            better(bt, at, tv[w], ti[w]);
-            if constexpr (TS) { better(bs, as, sv[w], si[w]); lse_join(m, s, mv[w], lv[w]); }
-        }
-        bool force = false;
-        int arg = at;
-        float top = bt;
-        if constexpr (TS) {
-            force = m + logf(s) > bt;
-            arg = as; top = bs;
-            if (!force) { top = bt; arg = at; better(top, arg, bs, as); }
-        }
-        s_force = force; s_arg = arg; s_max = top; s_fin = p.finished[b];
-    }
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x, V = p.V, tb = TS ? q.r.tb : V;
+    const Ranges g = row_ranges<TS>(p, q.r, b);
+    Sweep w{};
+    tail_first_sweep<TS>(p, q.r, g, b, w);
+    if (tid == 0) { s_force = w.force; s_arg = w.arg; s_max = w.top; s_fin = p.finished[b]; }
     __syncthreads();
     const bool force = s_force != 0, sample = q.T > 0.0;
     const double M = (double)s_max;
@@ -698,7 +682,7 @@ __global__ __launch_bounds__(1024) void wsp_pick_policy_kernel(const PolP q) {
     double sum = 0.0, best = -INFINITY;
     int arg = 0x7fffffff;
     for (int v = tid; v < V; v += 1024) {
-        if (!open(v) || (force && v < tb)) continue;
+        if (!open_id<TS>(p, q.r, g, v) || (force && v < tb)) continue;
         const double x = (double)finished(p.P, p.KS, p.ss, (long)b * V + v, nullptr, 0);
         sum += exp(x - M);
         if (sample) {
@@ -717,7 +701,7 @@ __global__ __launch_bounds__(1024) void wsp_pick_policy_kernel(const PolP q) {
         s_lse = M + log(sum);
         if (!sample) arg = s_arg;
     }
-    pick_commit(p, b, arg, &chosen, TS ? tb : 0, TS ? q.last_ts : nullptr, TS ? q.n_new : nullptr);
+    pick_commit(p, b, arg, &chosen, TS ? tb : 0, TS ? q.r.last_ts : nullptr, TS ? q.r.n_new : nullptr);
     if (tid == 0 && !s_fin) {
         q.sum_lp[b] += (double)finished(p.P, p.KS, p.ss, (long)b * V + chosen, nullptr, 0) - s_lse;
         q.n_scored[b] += 1;
@@ -1355,6 +1339,93 @@ void launch_beam_pick(const BeamP& k, int U, hipStream_t st) {
     hipLaunchKernelGGL(wsp_beam_pick_kernel, dim3(U), dim3(1024), 0, st, k);
 }
 
+// ------------------------------------------------------------------------------------------------------------ host: decoding
+// what every decoder refuses before any launch
+int check_decode_args(DexWhisper* s, const int32_t* prompt_host, int n_prompt, int eos, int max_new, int sync_every) {
+    if (!s->finalized) return s->fail(DEX_ERR_STATE, "the whisper weights are not finalized (dex_whisper_finalize)");
+    const DexWhisperConfig& c = s->c;
+    if (n_prompt < 1 || n_prompt > c.max_target_positions)
+        return s->fail(DEX_ERR_ARG, "a prompt of %d ids: 1 .. max_target_positions = %d", n_prompt, c.max_target_positions);
+    for (int i = 0; i < n_prompt; ++i)
+        if (prompt_host[i] < 0 || prompt_host[i] >= c.vocab_size) return s->fail(DEX_ERR_ARG, "prompt id %d is outside the vocabulary of %d", prompt_host[i], c.vocab_size);
+    if (eos < 0 || eos >= c.vocab_size) return s->fail(DEX_ERR_ARG, "eos_token_id %d is outside the vocabulary of %d", eos, c.vocab_size);
+    if (max_new < 1 || sync_every < 0) return s->fail(DEX_ERR_ARG, "max_new must be >= 1 and sync_every >= 0");
+    return DEX_OK;
+}
+
+// a tail over finished fp32 logits [B][V] (the dex_whisper_pick* entry points): one slab, no next embedding
+PickP pick_over_logits(const float* logits, int V, const uint8_t* mask, int eos, int* finished, int* lengths, int* count, int* ids, int ld_ids, int step) {
+    PickP k{};
+    k.P = logits; k.KS = 1; k.V = V; k.mask = mask; k.pick = 1; k.eos = eos; k.finished = finished; k.lengths = lengths; k.count = count;
+    k.ids = ids; k.ld_ids = ld_ids; k.step = step; k.next_pos = -1;
+    return k;
+}
+
+// what a greedy or policy decode of B rows is given: the masks, eos, the prompt's length and ids [B][max_new], lengths [B]
+struct RowsOut { const uint8_t *suppress, *begin; int eos, n_prompt, max_new; int32_t *ids, *lengths; };
+
+// the tail of step i of n_new inside such a decode: the logits' partials (ks slabs) in w.P, the begin mask at step 0, and the
+// embedding of the next position where a step follows
+PickP pick_in_step(const DexWhisper* s, const Ws& w, const RowsOut& o, int B, int ks, int i, int n_new) {
+    const DexWhisperConfig& c = s->c;
+    PickP k = pick_over_logits(w.P, c.vocab_size, i == 0 ? o.begin : o.suppress, o.eos, w.fin, o.lengths, w.count, o.ids, o.max_new, i);
+    k.KS = ks; k.ss = (long)B * c.vocab_size;
+    k.emb = s->emb; k.pos = s->dec_pos; k.d = c.d_model; k.next_pos = i + 1 < n_new ? o.n_prompt + i : -1; k.h = w.h;
+    return k;
+}
+
+// the rows' state before the first step: ids all eos, lengths 0, nothing finished (the count sits behind `flags` flags), and under the
+// timestamp rule no new token and no timestamp yet
+int reset_rows(DexWhisper* s, const Ws& w, const RowsOut& o, int B, int flags, bool rule, hipStream_t st) {
+    if (rule) {
+        DEX_HIPCHK(s, hipMemsetAsync(w.n_new, 0, B * sizeof(int), st));
+        hipLaunchKernelGGL(wsp_fill_kernel, dim3(1), dim3(256), 0, st, w.last_ts, (long)B, -1);
+    }
+    const long n_ids = (long)B * o.max_new;
+    hipLaunchKernelGGL(wsp_fill_kernel, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, st, o.ids, n_ids, o.eos);
+    DEX_HIPCHK(s, hipMemsetAsync(o.lengths, 0, B * sizeof(int32_t), st));
+    DEX_HIPCHK(s, hipMemsetAsync(w.fin, 0, (flags + 1) * sizeof(int), st));
+    return DEX_OK;
+}
+
+// One decode: `rows` rows of the step (bm: U x K beams, the ancestry of the step to come in bm->anc; cr: rows of an encoded batch).
+// It ends early once the device counter `count`, polled every sync_every steps, has reached `enough`.
+struct LoopP { const int32_t* prompt; int n_prompt, max_new, sync_every, rows, enough; const int* count; const BeamAt* bm; const CrossRows* cr; bool probe0; };
+
+// The prompt fills the cache (its logits are not needed, but position 0's where probe0), then n_new = min(max_new, the room in the
+// cache) steps, each ended by tail(i, n_new, ks), which leaves the next position's embedding in w.h.  after_prompt(p, ks) follows
+// the step of every prompt position p (ks: its logits' slabs, 0 where it has none).  Returns the steps taken in *steps
+template <class After, class Tail>
+int decode_loop(DexWhisper* s, const Ws& w, const LoopP& L, hipStream_t st, After after_prompt, Tail tail, int* steps) {
+    const DexWhisperConfig& c = s->c;
+    const int room = c.max_target_positions - L.n_prompt, n_new = L.max_new < room ? L.max_new : room;      // never past the cache
+    *steps = 0;
+    if (n_new <= 0) return DEX_OK;
+    for (int p = 0; p < L.n_prompt; ++p) {
+        hipLaunchKernelGGL(wsp_embed_kernel, dim3(L.rows), dim3(256), 0, st, (const int*)nullptr, 0, L.prompt[p], p, c.vocab_size, s->emb, s->dec_pos, c.d_model, w.h);
+        if (p < L.n_prompt - 1) after_prompt(p, enqueue_step(s, p, L.rows, w, st, p == 0 && L.probe0, L.bm, L.cr));
+    }
+    for (int i = 0; i < n_new; ++i) {
+        const int ks = enqueue_step(s, L.n_prompt - 1 + i, L.rows, w, st, true, L.bm, L.cr);
+        if (i == 0) after_prompt(L.n_prompt - 1, ks);
+        tail(i, n_new, ks);
+        *steps = i + 1;
+        if (L.sync_every && *steps % L.sync_every == 0 && *steps < n_new) {
+            int done = 0;
+            DEX_HIPCHK(s, hipMemcpyAsync(&done, L.count, sizeof(int), hipMemcpyDeviceToHost, st));
+            DEX_HIPCHK(s, hipStreamSynchronize(st));
+            if (done >= L.enough) break;
+        }
+    }
+    return DEX_OK;
+}
+
+// the end of a decoding call: it waits for the stream
+int decode_done(DexWhisper* s, hipStream_t st) {
+    DEX_HIPCHK(s, hipStreamSynchronize(st));
+    return hipGetLastError() == hipSuccess ? DEX_OK : s->fail(DEX_ERR_HIP, "kernel launch failed");
+}
+
 typedef Entry<DexWhisper> E;
 
 }  // namespace
@@ -1452,53 +1523,21 @@ static int generate(DexWhisper* s, const int32_t* prompt_host, int n_prompt, con
     if (!prompt_host || !ids_dev || !lengths_dev || !steps_host) return s->fail(DEX_ERR_ARG, "null pointer argument");
     Ws w;
     if (int rc = ready(s, B, workspace_dev, workspace_bytes, &w)) return rc;
-    if (!s->finalized) return s->fail(DEX_ERR_STATE, "the whisper weights are not finalized (dex_whisper_finalize)");
-    const DexWhisperConfig& c = s->c;
-    if (n_prompt < 1 || n_prompt > c.max_target_positions)
-        return s->fail(DEX_ERR_ARG, "a prompt of %d ids: 1 .. max_target_positions = %d", n_prompt, c.max_target_positions);
-    for (int i = 0; i < n_prompt; ++i)
-        if (prompt_host[i] < 0 || prompt_host[i] >= c.vocab_size) return s->fail(DEX_ERR_ARG, "prompt id %d is outside the vocabulary of %d", prompt_host[i], c.vocab_size);
-    if (eos < 0 || eos >= c.vocab_size) return s->fail(DEX_ERR_ARG, "eos_token_id %d is outside the vocabulary of %d", eos, c.vocab_size);
-    if (max_new < 1 || sync_every < 0) return s->fail(DEX_ERR_ARG, "max_new must be >= 1 and sync_every >= 0");
-    hipStream_t st = (hipStream_t)stream;
-    if (nots >= 0) {
+    if (int rc = check_decode_args(s, prompt_host, n_prompt, eos, max_new, sync_every)) return rc;
+    if (nots >= 0)
         if (int rc = check_timestamps(s, eos, nots, max_init)) return rc;
-        DEX_HIPCHK(s, hipMemsetAsync(w.n_new, 0, B * sizeof(int), st));
-        hipLaunchKernelGGL(wsp_fill_kernel, dim3(1), dim3(256), 0, st, w.last_ts, (long)B, -1);
-    }
-    const int room = c.max_target_positions - n_prompt, n_new = max_new < room ? max_new : room;      // never past the cache
-    const long n_ids = (long)B * max_new;
-    hipLaunchKernelGGL(wsp_fill_kernel, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, st, ids_dev, n_ids, eos);
-    DEX_HIPCHK(s, hipMemsetAsync(lengths_dev, 0, B * sizeof(int32_t), st));
-    DEX_HIPCHK(s, hipMemsetAsync(w.fin, 0, (B + 1) * sizeof(int), st));
-    int steps = 0;
-    if (n_new > 0) {
-        for (int p = 0; p < n_prompt - 1; ++p) {                                          // the prompt fills the cache; its logits are not needed
-            hipLaunchKernelGGL(wsp_embed_kernel, dim3(B), dim3(256), 0, st, (const int*)nullptr, 0, prompt_host[p], p, c.vocab_size, s->emb, s->dec_pos, c.d_model, w.h);
-            enqueue_step(s, p, B, w, st, false);
-        }
-        hipLaunchKernelGGL(wsp_embed_kernel, dim3(B), dim3(256), 0, st, (const int*)nullptr, 0, prompt_host[n_prompt - 1], n_prompt - 1, c.vocab_size, s->emb,
-                           s->dec_pos, c.d_model, w.h);
-        for (int i = 0; i < n_new; ++i) {
-            const int ks = enqueue_step(s, n_prompt - 1 + i, B, w, st);
-            PickP k{};
-            k.P = w.P; k.KS = ks; k.ss = (long)B * c.vocab_size; k.V = c.vocab_size; k.mask = i == 0 ? begin_dev : suppress_dev;
-            k.pick = 1; k.eos = eos; k.finished = w.fin; k.lengths = lengths_dev; k.count = w.count; k.ids = ids_dev; k.ld_ids = max_new; k.step = i;
-            k.emb = s->emb; k.pos = s->dec_pos; k.d = c.d_model; k.next_pos = i + 1 < n_new ? n_prompt + i : -1; k.h = w.h;
-            if (nots >= 0) hipLaunchKernelGGL(wsp_pick_ts_kernel, dim3(B), dim3(1024), 0, st, PickTsP{k, nots, nots + 1, max_init, w.last_ts, w.n_new});
-            else hipLaunchKernelGGL(wsp_pick_kernel, dim3(B), dim3(1024), 0, st, k);
-            steps = i + 1;
-            if (sync_every && steps % sync_every == 0 && steps < n_new) {
-                int done = 0;
-                DEX_HIPCHK(s, hipMemcpyAsync(&done, w.count, sizeof(int), hipMemcpyDeviceToHost, st));
-                DEX_HIPCHK(s, hipStreamSynchronize(st));
-                if (done >= B) break;
-            }
-        }
-    }
-    *steps_host = steps;
-    DEX_HIPCHK(s, hipStreamSynchronize(st));
-    return hipGetLastError() == hipSuccess ? DEX_OK : s->fail(DEX_ERR_HIP, "kernel launch failed");
+    hipStream_t st = (hipStream_t)stream;
+    const RowsOut o{suppress_dev, begin_dev, eos, n_prompt, max_new, ids_dev, lengths_dev};
+    if (int rc = reset_rows(s, w, o, B, B, nots >= 0, st)) return rc;
+    const RuleP rule{nots, nots + 1, max_init, w.last_ts, w.n_new};
+    auto tail = [&](int i, int n_new, int ks) {
+        const PickP k = pick_in_step(s, w, o, B, ks, i, n_new);
+        if (nots >= 0) hipLaunchKernelGGL(wsp_pick_ts_kernel, dim3(B), dim3(1024), 0, st, PickTsP{k, rule});
+        else hipLaunchKernelGGL(wsp_pick_kernel, dim3(B), dim3(1024), 0, st, k);
+    };
+    const LoopP loop{prompt_host, n_prompt, max_new, sync_every, B, B, w.count, nullptr, nullptr, false};
+    if (int rc = decode_loop(s, w, loop, st, [](int, int) {}, tail, steps_host)) return rc;
+    return decode_done(s, st);
 }
 
 int dex_whisper_generate(DexWhisper* s, const int32_t* prompt_host, int n_prompt, const uint8_t* suppress_dev, const uint8_t* begin_dev, int eos, int B,
@@ -1534,7 +1573,6 @@ int dex_whisper_generate_policy(DexWhisper* s, const int32_t* prompt_host, int n
         return s->fail(DEX_ERR_ARG, "null pointer argument");
     Ws w;
     if (int rc = ready(s, encoded, workspace_dev, workspace_bytes, &w)) return rc;
-    if (!s->finalized) return s->fail(DEX_ERR_STATE, "the whisper weights are not finalized (dex_whisper_finalize)");
     const DexWhisperConfig& c = s->c;
     if (B < 1 || B > encoded) return s->fail(DEX_ERR_ARG, "B must lie in [1, encoded = %d]", encoded);
     CrossRows cr{};
@@ -1544,69 +1582,36 @@ int dex_whisper_generate_policy(DexWhisper* s, const int32_t* prompt_host, int n
         if (seek_host[b] < 0) return s->fail(DEX_ERR_ARG, "a row's seek must be >= 0");
         cr.row.a[b] = rows_host[b];
     }
-    if (n_prompt < 1 || n_prompt > c.max_target_positions)
-        return s->fail(DEX_ERR_ARG, "a prompt of %d ids: 1 .. max_target_positions = %d", n_prompt, c.max_target_positions);
-    for (int i = 0; i < n_prompt; ++i)
-        if (prompt_host[i] < 0 || prompt_host[i] >= c.vocab_size) return s->fail(DEX_ERR_ARG, "prompt id %d is outside the vocabulary of %d", prompt_host[i], c.vocab_size);
-    if (eos < 0 || eos >= c.vocab_size) return s->fail(DEX_ERR_ARG, "eos_token_id %d is outside the vocabulary of %d", eos, c.vocab_size);
-    if (max_new < 1 || sync_every < 0) return s->fail(DEX_ERR_ARG, "max_new must be >= 1 and sync_every >= 0");
+    if (int rc = check_decode_args(s, prompt_host, n_prompt, eos, max_new, sync_every)) return rc;
     if (!(temperature >= 0.0) || !std::isfinite(temperature)) return s->fail(DEX_ERR_ARG, "temperature must be finite and >= 0");
     if (attempt < 0 || attempt > 15) return s->fail(DEX_ERR_ARG, "attempt must lie in [0, 15]");
     if (no_speech_prob_dev && (no_speech_token_id < 0 || no_speech_token_id >= c.vocab_size))
         return s->fail(DEX_ERR_ARG, "no_speech_token_id %d is outside the vocabulary of %d", no_speech_token_id, c.vocab_size);
-    hipStream_t st = (hipStream_t)stream;
     if (timestamps) {
         if (no_timestamps_token_id < 0) return s->fail(DEX_ERR_ARG, "no_timestamps_token_id %d is outside the vocabulary of %d", no_timestamps_token_id, c.vocab_size);
         if (int rc = check_timestamps(s, eos, no_timestamps_token_id, max_initial_timestamp_index)) return rc;
-        DEX_HIPCHK(s, hipMemsetAsync(w.n_new, 0, B * sizeof(int), st));
-        hipLaunchKernelGGL(wsp_fill_kernel, dim3(1), dim3(256), 0, st, w.last_ts, (long)B, -1);
     }
-    const int room = c.max_target_positions - n_prompt, n_new = max_new < room ? max_new : room;      // never past the cache
-    const long n_ids = (long)B * max_new;
-    hipLaunchKernelGGL(wsp_fill_kernel, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, st, ids_dev, n_ids, eos);
-    DEX_HIPCHK(s, hipMemsetAsync(lengths_dev, 0, B * sizeof(int32_t), st));
+    hipStream_t st = (hipStream_t)stream;
+    const RowsOut o{suppress_dev, begin_dev, eos, n_prompt, max_new, ids_dev, lengths_dev};
+    if (int rc = reset_rows(s, w, o, B, encoded, timestamps != 0, st)) return rc;           // the count sits behind the encoded rows' flags
     DEX_HIPCHK(s, hipMemsetAsync(sum_logprob_dev, 0, B * sizeof(double), st));
     DEX_HIPCHK(s, hipMemsetAsync(n_scored_dev, 0, B * sizeof(int32_t), st));
-    DEX_HIPCHK(s, hipMemsetAsync(w.fin, 0, (encoded + 1) * sizeof(int), st));               // the flags and, behind the encoded rows', the count
     PolP q{};
     policy_noise(&q, temperature, seed, attempt, row_keys_host, seek_host, B);
-    q.nots = no_timestamps_token_id; q.tb = no_timestamps_token_id + 1; q.max_init = max_initial_timestamp_index; q.last_ts = w.last_ts; q.n_new = w.n_new;
+    q.r = RuleP{no_timestamps_token_id, no_timestamps_token_id + 1, max_initial_timestamp_index, w.last_ts, w.n_new};
     q.sum_lp = sum_logprob_dev; q.n_scored = n_scored_dev;
-    auto probe = [&](int ks) {                                                            // the unprocessed logits of prompt position 0 are in w.P
-        if (no_speech_prob_dev)
+    auto probe = [&](int p, int ks) {                                                     // the unprocessed logits of prompt position 0 are in w.P
+        if (p == 0 && no_speech_prob_dev)
             hipLaunchKernelGGL(wsp_nospeech_kernel, dim3(B), dim3(1024), 0, st, ProbeP{w.P, ks, (long)B * c.vocab_size, c.vocab_size, no_speech_token_id, no_speech_prob_dev});
     };
-    int steps = 0;
-    if (n_new > 0) {
-        for (int p = 0; p < n_prompt - 1; ++p) {
-            hipLaunchKernelGGL(wsp_embed_kernel, dim3(B), dim3(256), 0, st, (const int*)nullptr, 0, prompt_host[p], p, c.vocab_size, s->emb, s->dec_pos, c.d_model, w.h);
-            const int ks = enqueue_step(s, p, B, w, st, p == 0 && no_speech_prob_dev, nullptr, &cr);
-            if (p == 0) probe(ks);
-        }
-        hipLaunchKernelGGL(wsp_embed_kernel, dim3(B), dim3(256), 0, st, (const int*)nullptr, 0, prompt_host[n_prompt - 1], n_prompt - 1, c.vocab_size, s->emb,
-                           s->dec_pos, c.d_model, w.h);
-        for (int i = 0; i < n_new; ++i) {
-            const int ks = enqueue_step(s, n_prompt - 1 + i, B, w, st, true, nullptr, &cr);
-            if (i == 0 && n_prompt == 1) probe(ks);
-            PickP& k = q.k;
-            k = PickP{};
-            k.P = w.P; k.KS = ks; k.ss = (long)B * c.vocab_size; k.V = c.vocab_size; k.mask = i == 0 ? begin_dev : suppress_dev;
-            k.pick = 1; k.eos = eos; k.finished = w.fin; k.lengths = lengths_dev; k.count = w.count; k.ids = ids_dev; k.ld_ids = max_new; k.step = i;
-            k.emb = s->emb; k.pos = s->dec_pos; k.d = c.d_model; k.next_pos = i + 1 < n_new ? n_prompt + i : -1; k.h = w.h;
-            if (timestamps) hipLaunchKernelGGL(wsp_pick_policy_kernel<true>, dim3(B), dim3(1024), 0, st, q);
-            else hipLaunchKernelGGL(wsp_pick_policy_kernel<false>, dim3(B), dim3(1024), 0, st, q);
-            steps = i + 1;
-            if (sync_every && steps % sync_every == 0 && steps < n_new) {
-                int done = 0;
-                DEX_HIPCHK(s, hipMemcpyAsync(&done, w.count, sizeof(int), hipMemcpyDeviceToHost, st));
-                DEX_HIPCHK(s, hipStreamSynchronize(st));
-                if (done >= B) break;
-            }
-        }
-    }
-    *steps_host = steps;
-    DEX_HIPCHK(s, hipStreamSynchronize(st));
-    return hipGetLastError() == hipSuccess ? DEX_OK : s->fail(DEX_ERR_HIP, "kernel launch failed");
+    auto tail = [&](int i, int n_new, int ks) {
+        q.k = pick_in_step(s, w, o, B, ks, i, n_new);
+        if (timestamps) hipLaunchKernelGGL(wsp_pick_policy_kernel<true>, dim3(B), dim3(1024), 0, st, q);
+        else hipLaunchKernelGGL(wsp_pick_policy_kernel<false>, dim3(B), dim3(1024), 0, st, q);
+    };
+    const LoopP loop{prompt_host, n_prompt, max_new, sync_every, B, B, w.count, nullptr, &cr, no_speech_prob_dev != nullptr};
+    if (int rc = decode_loop(s, w, loop, st, probe, tail, steps_host)) return rc;
+    return decode_done(s, st);
 }
 
 int dex_whisper_log_mel_long(DexWhisper* s, const float* wav_dev, const int32_t* lengths_host, int B, int n_samples, float* out_dev, int max_frames,
@@ -1680,9 +1685,7 @@ int dex_whisper_pick(const float* logits_dev, int B, int V, const uint8_t* mask_
                      int32_t* count_dev, int32_t* ids_dev, int ld_ids, int step, dex_stream_t stream) {
     if (!logits_dev || !finished_dev || !lengths_dev || !count_dev || !ids_dev) return DEX_ERR_ARG;
     if (B < 1 || B > 65535 || V < 1 || eos < 0 || eos >= V || step < 0 || step >= ld_ids) return DEX_ERR_ARG;
-    PickP k{};
-    k.P = logits_dev; k.KS = 1; k.V = V; k.mask = mask_dev; k.pick = 1; k.eos = eos; k.finished = finished_dev; k.lengths = lengths_dev; k.count = count_dev;
-    k.ids = ids_dev; k.ld_ids = ld_ids; k.step = step; k.next_pos = -1;
+    const PickP k = pick_over_logits(logits_dev, V, mask_dev, eos, finished_dev, lengths_dev, count_dev, ids_dev, ld_ids, step);
     hipLaunchKernelGGL(wsp_pick_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, k);
     return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
 }
@@ -1693,11 +1696,9 @@ int dex_whisper_pick_ts(const float* logits_dev, int B, int V, const uint8_t* ma
     if (!logits_dev || !finished_dev || !lengths_dev || !count_dev || !ids_dev || !last_timestamp_dev || !n_new_dev) return DEX_ERR_ARG;
     if (B < 1 || B > 65535 || V < 1 || eos < 0 || eos >= V || step < 2 || step >= ld_ids) return DEX_ERR_ARG;
     if (no_timestamps_token_id < eos || no_timestamps_token_id >= V - 1 || max_initial_timestamp_index < -1) return DEX_ERR_ARG;
-    PickP k{};
-    k.P = logits_dev; k.KS = 1; k.V = V; k.mask = mask_dev; k.pick = 1; k.eos = eos; k.finished = finished_dev; k.lengths = lengths_dev; k.count = count_dev;
-    k.ids = ids_dev; k.ld_ids = ld_ids; k.step = step; k.next_pos = -1;
+    const PickP k = pick_over_logits(logits_dev, V, mask_dev, eos, finished_dev, lengths_dev, count_dev, ids_dev, ld_ids, step);
     hipLaunchKernelGGL(wsp_pick_ts_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream,
-                       PickTsP{k, no_timestamps_token_id, no_timestamps_token_id + 1, max_initial_timestamp_index, last_timestamp_dev, n_new_dev});
+                       PickTsP{k, RuleP{no_timestamps_token_id, no_timestamps_token_id + 1, max_initial_timestamp_index, last_timestamp_dev, n_new_dev}});
     return hipGetLastError() == hipSuccess ? DEX_OK : DEX_ERR_HIP;
 }
 
@@ -1713,16 +1714,13 @@ int dex_whisper_pick_policy(const float* logits_dev, int B, int V, const uint8_t
     for (int b = 0; b < B; ++b)
         if (seek_host[b] < 0) return DEX_ERR_ARG;
     PolP q{};
-    PickP& k = q.k;
-    k.P = logits_dev; k.KS = 1; k.V = V; k.mask = mask_dev; k.pick = 1; k.eos = eos; k.finished = finished_dev; k.lengths = lengths_dev; k.count = count_dev;
-    k.ids = ids_dev; k.ld_ids = ld_ids; k.step = step; k.next_pos = -1;
+    q.k = pick_over_logits(logits_dev, V, mask_dev, eos, finished_dev, lengths_dev, count_dev, ids_dev, ld_ids, step);
     policy_noise(&q, temperature, seed, attempt, row_keys_host, seek_host, B);
     q.sum_lp = sum_logprob_dev; q.n_scored = n_scored_dev;
     if (timestamps) {
         if (!last_timestamp_dev || !n_new_dev || step < 2) return DEX_ERR_ARG;
         if (no_timestamps_token_id < eos || no_timestamps_token_id >= V - 1 || max_initial_timestamp_index < -1) return DEX_ERR_ARG;
-        q.nots = no_timestamps_token_id; q.tb = no_timestamps_token_id + 1; q.max_init = max_initial_timestamp_index;
-        q.last_ts = last_timestamp_dev; q.n_new = n_new_dev;
+        q.r = RuleP{no_timestamps_token_id, no_timestamps_token_id + 1, max_initial_timestamp_index, last_timestamp_dev, n_new_dev};
         hipLaunchKernelGGL(wsp_pick_policy_kernel<true>, dim3(B), dim3(1024), 0, (hipStream_t)stream, q);
     } else {
         hipLaunchKernelGGL(wsp_pick_policy_kernel<false>, dim3(B), dim3(1024), 0, (hipStream_t)stream, q);
@@ -1799,18 +1797,11 @@ int dex_whisper_generate_beam(DexWhisper* s, const int32_t* prompt_host, int n_p
                        DEX_WHISPER_MIN_BEAMS, DEX_WHISPER_MAX_BEAMS, WB, DEX_WHISPER_BEAM_KEYS);
     BeamWs b = plan_beam(s, workspace_dev, U, K);
     if (workspace_bytes < b.bytes) return s->fail(DEX_ERR_WORKSPACE, "workspace too small (dex_whisper_beam_workspace_bytes)");
-    if (!s->finalized) return s->fail(DEX_ERR_STATE, "the whisper weights are not finalized (dex_whisper_finalize)");
-    if (n_prompt < 1 || n_prompt > c.max_target_positions)
-        return s->fail(DEX_ERR_ARG, "a prompt of %d ids: 1 .. max_target_positions = %d", n_prompt, c.max_target_positions);
-    for (int i = 0; i < n_prompt; ++i)
-        if (prompt_host[i] < 0 || prompt_host[i] >= c.vocab_size) return s->fail(DEX_ERR_ARG, "prompt id %d is outside the vocabulary of %d", prompt_host[i], c.vocab_size);
-    if (eos < 0 || eos >= c.vocab_size) return s->fail(DEX_ERR_ARG, "eos_token_id %d is outside the vocabulary of %d", eos, c.vocab_size);
-    if (max_new < 1 || sync_every < 0) return s->fail(DEX_ERR_ARG, "max_new must be >= 1 and sync_every >= 0");
+    if (int rc = check_decode_args(s, prompt_host, n_prompt, eos, max_new, sync_every)) return rc;
     if (c.vocab_size < 2 * K) return s->fail(DEX_ERR_ARG, "a vocabulary of %d ids is below 2 x num_beams", c.vocab_size);
     if (!(length_penalty == length_penalty)) return s->fail(DEX_ERR_ARG, "length_penalty is NaN");
     hipStream_t st = (hipStream_t)stream;
     const int R = U * K, V = c.vocab_size, Tm = c.max_target_positions;
-    const int room = Tm - n_prompt, n_new = max_new < room ? max_new : room;
     const long init = (long)R * Tm;
     hipLaunchKernelGGL(wsp_beam_init_kernel, dim3((unsigned)((init + 255) / 256)), dim3(256), 0, st, [&] { DexWhisperBeamState t = b.s; t.anc_in = b.anc[0]; t.anc_out = b.anc[1]; return t; }(), U, K);
     if (trace) {
@@ -1820,42 +1811,27 @@ int dex_whisper_generate_beam(DexWhisper* s, const int32_t* prompt_host, int n_p
         DEX_HIPCHK(s, hipMemsetAsync(trace_scores_dev, 0, n * sizeof(double), st));
         DEX_HIPCHK(s, hipMemsetAsync(trace_logits_dev, 0, n * V * sizeof(float), st));
     }
-    int steps = 0;
-    if (n_new > 0) {
-        // the prompt is fed on all K rows of an utterance: identical rows, and the identity ancestry the first step starts from
-        BeamAt bm{U, K, b.anc[0], Tm};
-        for (int p = 0; p < n_prompt; ++p) {
-            hipLaunchKernelGGL(wsp_embed_kernel, dim3(R), dim3(256), 0, st, (const int*)nullptr, 0, prompt_host[p], p, V, s->emb, s->dec_pos, c.d_model, b.w.h);
-            if (p < n_prompt - 1) enqueue_step(s, p, R, b.w, st, false, &bm);
-        }
-        for (int i = 0; i < n_new; ++i) {
-            bm.anc = b.anc[i & 1];
-            const int ks = enqueue_step(s, n_prompt - 1 + i, R, b.w, st, true, &bm);
-            BeamP k{};
-            k.P = b.w.P; k.KS = ks; k.ss = (long)R * V; k.V = V; k.K = K; k.mask = i == 0 ? begin_dev : suppress_dev;
-            k.lg = trace ? trace_logits_dev + (long)i * R * V : b.lg; k.C = beam_chunks(V); k.part = b.part; k.cand_s = b.cand_s; k.cand_f = b.cand_f;
-            k.eos = eos; k.step = i; k.pos = n_prompt - 1 + i; k.last = i + 1 == n_new; k.div = std::pow((double)(i + 1), length_penalty);
-            k.s = b.s;
-            if (trace) { k.tok = trace_tokens_dev + (long)i * R; k.par = trace_parents_dev + (long)i * R; k.trace = trace_scores_dev + (long)i * R; }
-            k.emb = s->emb; k.posw = s->dec_pos; k.d = c.d_model; k.next_pos = i + 1 < n_new ? n_prompt + i : -1; k.h = b.w.h;
-            k.s.seq_in = b.seq[i & 1]; k.s.seq_out = b.seq[(i & 1) ^ 1]; k.s.anc_in = b.anc[i & 1]; k.s.anc_out = b.anc[(i & 1) ^ 1];
-            launch_beam_pick(k, U, st);
-            steps = i + 1;
-            if (sync_every && steps % sync_every == 0 && steps < n_new) {
-                int done = 0;
-                DEX_HIPCHK(s, hipMemcpyAsync(&done, b.s.count, sizeof(int), hipMemcpyDeviceToHost, st));
-                DEX_HIPCHK(s, hipStreamSynchronize(st));
-                if (done >= U) break;
-            }
-        }
-    }
+    // the prompt is fed on all K rows of an utterance: identical rows, and the identity ancestry the first step starts from
+    BeamAt bm{U, K, b.anc[0], Tm};
+    auto tail = [&](int i, int n_new, int ks) {
+        BeamP k{};
+        k.P = b.w.P; k.KS = ks; k.ss = (long)R * V; k.V = V; k.K = K; k.mask = i == 0 ? begin_dev : suppress_dev;
+        k.lg = trace ? trace_logits_dev + (long)i * R * V : b.lg; k.C = beam_chunks(V); k.part = b.part; k.cand_s = b.cand_s; k.cand_f = b.cand_f;
+        k.eos = eos; k.step = i; k.pos = n_prompt - 1 + i; k.last = i + 1 == n_new; k.div = std::pow((double)(i + 1), length_penalty);
+        k.s = b.s;
+        if (trace) { k.tok = trace_tokens_dev + (long)i * R; k.par = trace_parents_dev + (long)i * R; k.trace = trace_scores_dev + (long)i * R; }
+        k.emb = s->emb; k.posw = s->dec_pos; k.d = c.d_model; k.next_pos = i + 1 < n_new ? n_prompt + i : -1; k.h = b.w.h;
+        k.s.seq_in = b.seq[i & 1]; k.s.seq_out = b.seq[(i & 1) ^ 1]; k.s.anc_in = b.anc[i & 1]; k.s.anc_out = b.anc[(i & 1) ^ 1];
+        launch_beam_pick(k, U, st);
+        bm.anc = k.s.anc_out;                                                             // the swap: the next step reads what this one wrote
+    };
+    const LoopP loop{prompt_host, n_prompt, max_new, sync_every, R, U, b.s.count, &bm, nullptr, false};
+    if (int rc = decode_loop(s, b.w, loop, st, [](int, int) {}, tail, steps_host)) return rc;
     BeamOutP o{};
     o.s = b.s; o.K = K; o.eos = eos; o.max_new = max_new; o.ids = ids_dev; o.lengths = lengths_dev; o.scores = scores_dev;
     o.pool_ids = pool_ids_dev; o.pool_len = pool_len_dev; o.pool_scores = pool_scores_dev; o.pool_n = pool_n_dev;
     hipLaunchKernelGGL(wsp_beam_result_kernel, dim3(U), dim3(256), 0, st, o);
-    *steps_host = steps;
-    DEX_HIPCHK(s, hipStreamSynchronize(st));
-    return hipGetLastError() == hipSuccess ? DEX_OK : s->fail(DEX_ERR_HIP, "kernel launch failed");
+    return decode_done(s, st);
 }
 
 }  // extern "C"

@@ -577,6 +577,40 @@ class Whisper(WaveformNet):
         beg[list(spec.begin_suppress_tokens)] = 1
         return torch.from_numpy(sup).to(self.device), torch.from_numpy(beg).to(self.device)
 
+    def _decode_setup(self, spec: GenerationSpec, max_new_tokens: Optional[int], clamp: bool, refusal):
+        """-> (max_new, the suppress and begin masks, the prompt as a host array).  ``max_new`` defaults to the room the prompt leaves
+        in the cache; ``clamp`` cuts it to that room here (otherwise the library does).  ``refusal(max_new)``: the caller's message
+        where no step could be taken."""
+        room = self.config.max_target_positions - len(spec.prompt_ids)
+        max_new = room if max_new_tokens is None else int(max_new_tokens)
+        max_new = min(max_new, room) if clamp else max_new
+        if not spec.prompt_ids or max_new < 1:
+            raise ValueError(refusal(max_new))
+        return (max_new, *self._masks(spec), np.ascontiguousarray(np.asarray(spec.prompt_ids, np.int32)))
+
+    def _decode_inputs(self, what: str, features_or_wavs, spec: GenerationSpec, max_new_tokens, lengths, sr, clamp: bool):
+        """What every decoder starts from -> (f, max_new, sup, beg, prompt): the features (given, or ``log_mel`` of the wavs) and
+        ``_decode_setup``'s results."""
+        c = self.config
+        if not spec.prompt_ids or len(spec.prompt_ids) > c.max_target_positions:
+            raise ValueError(f"{what}: a prompt of {len(spec.prompt_ids)} ids, max_target_positions is {c.max_target_positions}")
+        if torch.is_tensor(features_or_wavs) and features_or_wavs.dim() == 3:
+            f = self._features(features_or_wavs, what)
+        else:
+            f = self.log_mel(features_or_wavs, lengths, sr)
+            f = f[None] if f.dim() == 2 else f
+        return (f, *self._decode_setup(spec, max_new_tokens, clamp,
+                                       lambda n: f"{what}: max_new_tokens must be >= 1 (and the prompt leave room in the cache), got {n}"))
+
+    @staticmethod
+    def _keys_and_seeks(what: str, B: int, row_keys, seeks, rule: str):
+        """The words of the noise counter, one per row -> (keys, default the row's index; seeks, default 0); ``rule`` words the refusal."""
+        keys = list(range(B)) if row_keys is None else [int(k) for k in row_keys]
+        seeks = [0] * B if seeks is None else [int(s) for s in seeks]
+        if len(keys) != B or len(seeks) != B or any(not 0 <= k < 1 << 32 for k in keys) or any(not 0 <= s < 1 << 27 for s in seeks):
+            raise ValueError(f"{what}: {rule}")
+        return keys, seeks
+
     def generate(self, features_or_wavs, spec: GenerationSpec, max_new_tokens: Optional[int] = None, lengths=None, sr: int = SAMPLING_RATE,
                  timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1,
                  policy: Optional[DecodingPolicy] = None, row_keys=None, seeks=None):
@@ -603,22 +637,9 @@ class Whisper(WaveformNet):
         if early_stopping is not False or num_return_sequences != 1:
             raise ValueError(f"{what}: early_stopping and num_return_sequences belong to beam search (num_beams > 1)")
         self._need_weights(what)
-        c = self.config
         if timestamps:
             self._timestamp_spec(spec, what)
-        if not spec.prompt_ids or len(spec.prompt_ids) > c.max_target_positions:
-            raise ValueError(f"{what}: a prompt of {len(spec.prompt_ids)} ids, max_target_positions is {c.max_target_positions}")
-        if torch.is_tensor(features_or_wavs) and features_or_wavs.dim() == 3:
-            f = self._features(features_or_wavs, what)
-        else:
-            f = self.log_mel(features_or_wavs, lengths, sr)
-            f = f[None] if f.dim() == 2 else f
-        room = c.max_target_positions - len(spec.prompt_ids)
-        max_new = room if max_new_tokens is None else int(max_new_tokens)
-        if max_new < 1:
-            raise ValueError(f"{what}: max_new_tokens must be >= 1 (and the prompt leave room in the cache), got {max_new}")
-        sup, beg = self._masks(spec)
-        prompt = np.ascontiguousarray(np.asarray(spec.prompt_ids, np.int32))
+        f, max_new, sup, beg, prompt = self._decode_inputs(what, features_or_wavs, spec, max_new_tokens, lengths, sr, clamp=False)
         B = f.shape[0]
         if policy is not None:
             return self._generate_policy(f, spec, policy, max_new, timestamps, sup, beg, prompt, row_keys, seeks, what)
@@ -698,10 +719,7 @@ class Whisper(WaveformNet):
 
     def _generate_policy(self, f, spec, policy, max_new, timestamps, sup, beg, prompt, row_keys, seeks, what):
         B = f.shape[0]
-        keys = list(range(B)) if row_keys is None else [int(k) for k in row_keys]
-        seeks = [0] * B if seeks is None else [int(s) for s in seeks]
-        if len(keys) != B or len(seeks) != B or any(not 0 <= k < 1 << 32 for k in keys) or any(not 0 <= s < 1 << 27 for s in seeks):
-            raise ValueError(f"{what}: row_keys and seeks must hold one value per row, keys in [0, 2^32), seeks in [0, 2^27)")
+        keys, seeks = self._keys_and_seeks(what, B, row_keys, seeks, "row_keys and seeks must hold one value per row, keys in [0, 2^32), seeks in [0, 2^27)")
         rows = []
         for r in range(0, B, MAX_ROWS):
             rows += self._decode_policy(f[r:r + MAX_ROWS], spec, policy, max_new, timestamps, sup, beg, prompt, keys[r:r + MAX_ROWS], seeks[r:r + MAX_ROWS])
@@ -723,21 +741,8 @@ class Whisper(WaveformNet):
         what = "Whisper.generate_beam"
         K = check_beam_args(self.config, spec, num_beams, length_penalty, what=what)
         self._need_weights(what)
-        c = self.config
-        if not spec.prompt_ids or len(spec.prompt_ids) > c.max_target_positions:
-            raise ValueError(f"{what}: a prompt of {len(spec.prompt_ids)} ids, max_target_positions is {c.max_target_positions}")
-        if torch.is_tensor(features_or_wavs) and features_or_wavs.dim() == 3:
-            f = self._features(features_or_wavs, what)
-        else:
-            f = self.log_mel(features_or_wavs, lengths, sr)
-            f = f[None] if f.dim() == 2 else f
-        room = c.max_target_positions - len(spec.prompt_ids)
-        max_new = room if max_new_tokens is None else min(int(max_new_tokens), room)
-        if max_new < 1:
-            raise ValueError(f"{what}: max_new_tokens must be >= 1 (and the prompt leave room in the cache), got {max_new}")
-        sup, beg = self._masks(spec)
-        prompt = np.ascontiguousarray(np.asarray(spec.prompt_ids, np.int32))
-        U, V, dev = f.shape[0], c.vocab_size, self.device
+        f, max_new, sup, beg, prompt = self._decode_inputs(what, features_or_wavs, spec, max_new_tokens, lengths, sr, clamp=True)
+        U, V, dev = f.shape[0], self.config.vocab_size, self.device
         ids = torch.empty(U, max_new, dtype=torch.int32, device=dev)
         lens = torch.empty(U, dtype=torch.int32, device=dev)
         scores = torch.empty(U, dtype=torch.float64, device=dev)
@@ -854,18 +859,11 @@ class Whisper(WaveformNet):
             raise ValueError(f"{what}: row_keys belong to a policy")
         feats, frames = self.log_mel_long(wavs, lengths, sr)
         B, W, tb = feats.shape[0], 2 * self.config.max_source_positions, int(spec.no_timestamps_token_id) + 1
-        seek, out = [0] * B, [[] for _ in range(B)]
+        seek, out, keys, setup = [0] * B, [[] for _ in range(B)], None, None
         if policy is not None:
-            keys = list(range(B)) if row_keys is None else [int(k) for k in row_keys]
-            if len(keys) != B or any(not 0 <= k < 1 << 32 for k in keys):
-                raise ValueError(f"{what}: row_keys must hold one value in [0, 2^32) per row")
-            c = self.config
-            room = c.max_target_positions - len(spec.prompt_ids)
-            max_new = room if max_new_tokens is None else int(max_new_tokens)
-            if not spec.prompt_ids or max_new < 1:
-                raise ValueError(f"{what}: max_new_tokens must be >= 1 and the prompt of {len(spec.prompt_ids)} ids leave room in the cache")
-            sup, beg = self._masks(spec)
-            prompt = np.ascontiguousarray(np.asarray(spec.prompt_ids, np.int32))
+            keys, _ = self._keys_and_seeks(what, B, row_keys, None, "row_keys must hold one value in [0, 2^32) per row")
+            setup = self._decode_setup(spec, max_new_tokens, False,
+                                       lambda n: f"{what}: max_new_tokens must be >= 1 and the prompt of {len(spec.prompt_ids)} ids leave room in the cache")
         while True:
             active = [b for b in range(B) if seek[b] < int(frames[b])]
             if not active:
@@ -873,31 +871,32 @@ class Whisper(WaveformNet):
             for r in range(0, len(active), MAX_ROWS):
                 rows = active[r:r + MAX_ROWS]
                 ns = [min(int(frames[b]) - seek[b], W) for b in rows]
-                if policy is not None:
-                    calls, attempts = getattr(self, "encoder_calls", 0), []
-                    res = self._decode_policy(self._gather(feats, rows, [seek[b] for b in rows], ns), spec, policy, max_new, True, sup, beg, prompt,
-                                              [keys[b] for b in rows], [seek[b] for b in rows], attempts)
-                    if _trace is not None:
-                        _trace.append(dict(encoder_calls=self.encoder_calls - calls, windows=[(b, seek[b], ns[a]) for a, b in enumerate(rows)],
-                                           attempts=[[(rows[a], T, t) for a, T, t in att] for att in attempts],
-                                           skipped=[(b, seek[b], ns[a]) for a, b in enumerate(rows) if res[a]["skipped"]]))
-                    for a, b in enumerate(rows):
-                        if res[a]["skipped"]:
-                            seek[b] += ns[a]
-                            continue
-                        segments, advance = retrieve_segments(res[a]["tokens"], tb, seek[b], ns[a])
-                        extra = {k: res[a][k] for k in ("temperature", "avg_logprob", "compression_ratio", "no_speech_prob")}
-                        out[b] += [dict(s, **extra) for s in segments]
-                        seek[b] += advance
-                    continue
-                ids, lens = self.generate(self._gather(feats, rows, [seek[b] for b in rows], ns), spec, max_new_tokens, timestamps=True)
-                host = torch.cat([ids, lens[:, None]], dim=1).cpu().numpy()                 # the window's one device-to-host copy
-                if _trace is not None:                                                      # one entry per network call: (row, seek, n, ids)
-                    _trace.append([(b, seek[b], ns[a], host[a, : int(host[a, -1])].tolist()) for a, b in enumerate(rows)])
-                for a, b in enumerate(rows):
-                    segments, advance = retrieve_segments(host[a, : int(host[a, -1])].tolist(), tb, seek[b], ns[a])
-                    out[b] += segments
+                res, entry = self._decode_window(feats, rows, [seek[b] for b in rows], ns, spec, max_new_tokens, policy, setup, keys)
+                if _trace is not None:
+                    _trace.append(entry)
+                for (tokens, extra, skipped), b, n in zip(res, rows, ns):
+                    if skipped:
+                        seek[b] += n
+                        continue
+                    segments, advance = retrieve_segments(tokens, tb, seek[b], n)
+                    out[b] += segments if extra is None else [dict(s, **extra) for s in segments]
                     seek[b] += advance
+
+    def _decode_window(self, feats, rows, seeks, ns, spec, max_new_tokens, policy, setup, keys):
+        """One network call of the window loop: the windows [seek, seek + n) of ``rows`` of ``feats``, decoded under the timestamp rule,
+        plainly or (``setup`` from ``_decode_setup``, ``keys`` by row of ``feats``) under ``policy`` -> (per window its (new ids, the
+        statistics a policy attaches to its segments or None, skipped as silence), the call's ``_trace`` entry)."""
+        f, where = self._gather(feats, rows, seeks, ns), list(zip(rows, seeks, ns))
+        if policy is None:
+            ids, lens = self.generate(f, spec, max_new_tokens, timestamps=True)
+            host = torch.cat([ids, lens[:, None]], dim=1).cpu().numpy()                     # the window's one device-to-host copy
+            res = [(row[: int(row[-1])].tolist(), None, False) for row in host]
+            return res, [(*w, x[0]) for w, x in zip(where, res)]                            # one entry per network call: (row, seek, n, ids)
+        calls, attempts = getattr(self, "encoder_calls", 0), []
+        got = self._decode_policy(f, spec, policy, setup[0], True, *setup[1:], [keys[b] for b in rows], seeks, attempts)
+        res = [(x["tokens"], {k: x[k] for k in ("temperature", "avg_logprob", "compression_ratio", "no_speech_prob")}, x["skipped"]) for x in got]
+        return res, dict(encoder_calls=self.encoder_calls - calls, windows=where, attempts=[[(rows[a], T, t) for a, T, t in att] for att in attempts],
+                         skipped=[w for w, x in zip(where, got) if x["skipped"]])
 
     def transcribe_long(self, wavs, spec: GenerationSpec, vocab: Sequence[str], lengths=None, sr: int = SAMPLING_RATE,
                         max_new_tokens: Optional[int] = None, policy: Optional[DecodingPolicy] = None):

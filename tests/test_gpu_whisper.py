@@ -345,3 +345,49 @@ def test_errors():
         whisper.Whisper(R.library_config(R._cfg(**dict(vars(cfg), scale_embedding=True))), "cuda")
     with pytest.raises(ValueError, match="MI355X"):
         whisper.Whisper(R.library_config(cfg), "cpu")
+
+
+REFUSALS = {"prompt id": (dict(prompt=(1, 96, 7)), -1, "prompt id 96 is outside the vocabulary of 96"),
+            "eos": (dict(eos=96), -1, "eos_token_id 96 is outside the vocabulary of 96"),
+            "max_new": (dict(max_new=0), -1, "max_new must be >= 1 and sync_every >= 0"),
+            "sync_every": (dict(sync_every=-1), -1, "max_new must be >= 1 and sync_every >= 0"),
+            "not finalized": (dict(finalized=False), -2, "the whisper weights are not finalized (dex_whisper_finalize)")}
+
+
+@pytest.mark.parametrize("entry", ["generate", "generate_ts", "generate_policy", "generate_beam"])
+def test_refusal_parity(entry):
+    """The four decoding entry points refuse the arguments they share in the same words with the same code, in host code: the
+    outputs still hold what the test put there (a first launch would have filled the ids with eos)."""
+    from dex_tts_amd import whisper
+    cfg = R.TINY
+    empty = whisper.Whisper(R.library_config(cfg), "cuda")
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    mask = torch.zeros(cfg.vocab_size, dtype=torch.uint8, device="cuda")
+    for what, (change, code, text) in REFUSALS.items():
+        a = dict(prompt=PROMPT, eos=30, max_new=4, sync_every=2, finalized=True)
+        a.update(change)
+        ctx = (model("TINY") if a["finalized"] else empty)._ctx
+        prompt = np.ascontiguousarray(np.asarray(a["prompt"], np.int32))
+        ids, lens = torch.full((1, 4), -7, dtype=torch.int32, device="cuda"), torch.full((1,), -7, dtype=torch.int32, device="cuda")
+        stat, steps = torch.full((3,), -7.0, dtype=torch.float64, device="cuda"), C.c_int(-7)
+        head = (ctx.h, prompt.ctypes.data_as(C.POINTER(C.c_int32)), len(prompt), mask.data_ptr(), mask.data_ptr(), a["eos"])
+        if entry == "generate_beam":
+            ws = ctx.beam_workspace(1, 2)
+            rc = ctx.lib.dex_whisper_generate_beam(*head, 1, 2, 1.0, a["max_new"], a["sync_every"], ids.data_ptr(), lens.data_ptr(), stat.data_ptr(),
+                                                   C.byref(steps), *[None] * 8, ws.data_ptr(), ws.numel(), st)
+        else:
+            ws = ctx.workspace(1)
+            tail = (1, a["max_new"], a["sync_every"], ids.data_ptr(), lens.data_ptr())
+            end = (C.byref(steps), ws.data_ptr(), ws.numel(), st)
+            if entry == "generate":
+                rc = ctx.lib.dex_whisper_generate(*head, *tail, *end)
+            elif entry == "generate_ts":
+                rc = ctx.lib.dex_whisper_generate_ts(*head, 40, -1, *tail, *end)
+            else:
+                key, zero = (C.c_uint32 * 1)(0), (C.c_int32 * 1)(0)
+                rc = ctx.lib.dex_whisper_generate_policy(*head, 0, -1, -1, 0.0, 0, 0, key, zero, 1, zero, *tail, stat[:1].data_ptr(), lens.data_ptr(), 0,
+                                                         None, *end)
+        got = ctx.lib.dex_whisper_last_error(ctx.h).decode()
+        torch.cuda.synchronize()
+        assert (rc, got) == (code, text), (entry, what, rc, got)
+        assert steps.value == -7 and (ids.cpu() == -7).all() and (lens.cpu() == -7).all() and (stat.cpu() == -7.0).all(), (entry, what)
