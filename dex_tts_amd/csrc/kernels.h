@@ -40,6 +40,9 @@ typedef long long gnfix_t;
 // Profiling aid: launch functions that pick one of several template instantiations leave the chosen SYMBOL here, so the
 // library's event profile (dex_profile_get) names rows like rocprofv3's kernel trace does instead of by kernel class.
 extern thread_local const char* g_last_symbol;
+// ... and, where a launcher has more instantiations than symbols (the fused linear attention: C, PRO, FL, ROWS of the context pass, the
+// form of the tail), the whole instantiation as text.  Read by the per-launch tests (tests/kshim); the profile keeps g_last_symbol.
+extern thread_local const char* g_last_form;
 
 // Precision modes (== DexPrecision of include/dex_amd.h).  The reduced-precision kernels exist twice — namespace dex::bf16
 // and dex::f16, the same sources compiled for either operand type (lp_config.h) — and the launch functions below that

@@ -673,6 +673,20 @@ __global__ __launch_bounds__(1024) void linattn_kvctx_hw_kernel(const LinKvCtxP 
     KSTAMP_STORE(7)
 }
 
+// The instantiation a context-pass launch takes, as text (g_last_form): kernel, C, PRO, FL, and ROWS of the head-parallel form.
+static const char* kvctx_form(bool hw, int C, bool pro, int fl, bool rows) {
+#define KVF_ROW(K, CC, RW)                                                                                                            \
+    { K " C=" #CC " PRO=0 FL=-1" RW, K " C=" #CC " PRO=1 FL=-1" RW, K " C=" #CC " PRO=1 FL=1" RW, K " C=" #CC " PRO=1 FL=3" RW,        \
+      K " C=" #CC " PRO=1 FL=5" RW, K " C=" #CC " PRO=1 FL=7" RW, K " C=" #CC " PRO=1 FL=9" RW, K " C=" #CC " PRO=1 FL=11" RW,         \
+      K " C=" #CC " PRO=1 FL=13" RW, K " C=" #CC " PRO=1 FL=15" RW }
+    static const char* const names[6][10] = {
+        KVF_ROW("linattn_kvctx_kernel", 64, ""), KVF_ROW("linattn_kvctx_kernel", 128, ""),
+        KVF_ROW("linattn_kvctx_hw_kernel", 64, " ROWS=0"), KVF_ROW("linattn_kvctx_hw_kernel", 128, " ROWS=0"),
+        KVF_ROW("linattn_kvctx_hw_kernel", 64, " ROWS=1"), KVF_ROW("linattn_kvctx_hw_kernel", 128, " ROWS=1") };
+#undef KVF_ROW
+    const int col = !pro ? 0 : (fl >= 1 && fl <= 15 && (fl & 1)) ? 2 + fl / 2 : 1;       // the launchers' switch: odd FL = 16-bit H2
+    return names[(hw ? 2 + (rows ? 2 : 0) : 0) + (C == 128 ? 1 : 0)][col];
+}
 // the head-parallel form exists for every C of every build but the split-weight one at C = 128 (LDS)
 static bool kvctx_hw_supported(int C) {
 #ifdef DEX_LP_WSPLIT
@@ -736,6 +750,7 @@ void launch_linattn_kvctx(const LinKvCtxP& p, hipStream_t st) {
     const int fl = pro ? (p.h2_bf16 != 0 ? 1 : 0) | (p.res_lp != 0 ? 2 : 0) | (p.xout_lp != 0 ? 4 : 0) | (p.res_under_mask != 0 ? 8 : 0) : -1;
     if (p.headwaves && kvctx_hw_supported(p.C)) {
         g_last_symbol = "linattn_kvctx_hw_kernel";
+        g_last_form = kvctx_form(true, p.C, pro, fl, p.rows != 0);
         // weight image(s) + the x image [4][2][32][C + 8]; the merge reuses the same bytes
         const size_t lds_hw = lds_w + (size_t)4 * 2 * 32 * (p.C + 8) * sizeof(u16);
         const size_t lds2 = lds_hw > lds_m ? lds_hw : lds_m;
@@ -756,6 +771,7 @@ void launch_linattn_kvctx(const LinKvCtxP& p, hipStream_t st) {
             else hipLaunchKernelGGL((linattn_kvctx_kernel<CC, false>), grid, dim3(256), lds, st, p);                                   \
     }
     g_last_symbol = "linattn_kvctx_kernel";
+    g_last_form = kvctx_form(false, p.C, pro, fl, false);
     if (p.C == 64) { KVCTX_LAUNCH(64) } else { KVCTX_LAUNCH(128) }
 #undef KVCTX_LAUNCH
 #undef KVCTX_CASE
@@ -1296,6 +1312,8 @@ void launch_linattn_out2(const LinOut2P& p, hipStream_t st) {
     const bool lp_io = p.x_lp || p.y_lp || p.Y2;
     if (p.hw && !lp_io) {                              // the wave-split latency form (launcher: DEX_LINATTN_OUT2_HW)
         g_last_symbol = "linattn_out2_hw_kernel";
+        g_last_form = p.C == 64 ? (p.rows ? "linattn_out2_hw_kernel C=64 rows=1" : "linattn_out2_hw_kernel C=64 rows=0")
+                                : (p.rows ? "linattn_out2_hw_kernel C=128 rows=1" : "linattn_out2_hw_kernel C=128 rows=0");
         const dim3 g1((p.npix + 31) / 32, p.B);
         if (p.rows) {                                  // x and y as whole pixel rows (launcher: DEX_OUT2_ROWS)
             if (p.C == 64) hipLaunchKernelGGL((linattn_out2_hw_kernel<64, true>), g1, dim3(256), 0, st, p);
@@ -1307,10 +1325,12 @@ void launch_linattn_out2(const LinOut2P& p, hipStream_t st) {
         return;
     }
     if ((long)grid.x * p.B < out2_min_wgs()) {        // latency regime: the direct form
+        g_last_form = p.C == 64 ? "linattn_out2_direct_kernel C=64" : "linattn_out2_direct_kernel C=128";
         if (p.C == 64) hipLaunchKernelGGL(linattn_out2_direct_kernel<64>, grid, dim3(256), 0, st, p);
         else hipLaunchKernelGGL(linattn_out2_direct_kernel<128>, grid, dim3(256), 0, st, p);
         return;
     }
+    g_last_form = p.C == 64 ? "linattn_out2_kernel C=64 (throughput)" : "linattn_out2_kernel C=128 (throughput)";
     if (p.C == 64) hipLaunchKernelGGL(linattn_out2_kernel<64>, grid, dim3(256), lds, st, p);
     else hipLaunchKernelGGL(linattn_out2_kernel<128>, grid, dim3(256), lds, st, p);
 }

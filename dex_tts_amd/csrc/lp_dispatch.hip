@@ -14,6 +14,7 @@
 namespace dex {
 
 thread_local const char* g_last_symbol = nullptr;
+thread_local const char* g_last_form = nullptr;
 thread_local bool g_lp_wsplit = false;
 
 // shape predicates do not depend on the operand type - but the split-weight build (f16w) has its own: a kernel without a split form

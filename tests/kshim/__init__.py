@@ -69,6 +69,32 @@ class KsRowChain(C.Structure):
                 + [("epoch", C.c_uint32), ("qscale", C.c_float)])
 
 
+class KsLinKvCtx(C.Structure):
+    _fields_ = (_ptrs("X", "Wkv", "H2", "gn_stats", "gamma", "beta", "res", "mask", "part_m", "part_s", "part_c", "Xout")
+                + [("xb", C.c_int64), ("resb", C.c_int64), ("mask_bstride", C.c_int64), ("wkv_lo_off", C.c_int64)]
+                + _ints("precision", "npix", "C", "B", "ldx", "x_coff", "nsub", "nblk", "headwaves", "rows", "ldres", "res_under_mask",
+                        "mask_ws", "W", "h2_bf16", "res_lp", "xout_lp", "reserved"))
+
+
+class KsLinMerge(C.Structure):
+    _fields_ = _ptrs("part_m", "part_s", "part_c", "Wout", "g", "W2") + _ints("precision", "nblk", "C", "B")
+
+
+class KsLinOut2(C.Structure):
+    _fields_ = (_ptrs("X", "Wq", "W2", "bias", "Y", "Y2")
+                + [("xb", C.c_int64), ("yb", C.c_int64), ("y2b", C.c_int64), ("wq_lo_off", C.c_int64)]
+                + _ints("precision", "npix", "C", "B", "ldx", "x_coff", "ldy", "y_coff", "ldy2", "y2_coff", "x_lp", "y_lp", "hw", "rows"))
+
+
+class KsLinCtx(C.Structure):
+    _fields_ = (_ptrs("qkv", "part_m", "part_s", "part_c") + [("bstride", C.c_int64)]
+                + _ints("ld", "n", "heads", "chunk", "nchunks", "B"))
+
+
+class KsLinCombine(C.Structure):
+    _fields_ = _ptrs("part_m", "part_s", "part_c", "Wout", "g", "Weff") + _ints("nchunks", "heads", "C", "B")
+
+
 ATTN_PLANS = {"attention_direct_batch_regime": 0, "attention_direct_ksplit": 1, "attention_q64_ksplit": 2}
 _lib = None
 
@@ -83,7 +109,7 @@ def load():
     dexlib.load()                                     # torch's HIP runtime, then the library the shim links against
     lib = C.CDLL(LIB_PATH)
     lib.ks_struct_bytes.restype, lib.ks_struct_bytes.argtypes = C.c_int, [C.c_int]
-    for k, T in enumerate((KsConv3, KsConvDown, KsConvTUp, KsAttn, KsRowChain)):
+    for k, T in enumerate((KsConv3, KsConvDown, KsConvTUp, KsAttn, KsRowChain, KsLinKvCtx, KsLinMerge, KsLinOut2, KsLinCtx, KsLinCombine)):
         if lib.ks_struct_bytes(k) != C.sizeof(T):
             raise RuntimeError(f"descriptor {T.__name__}: {C.sizeof(T)} bytes here, {lib.ks_struct_bytes(k)} in the shim")
     lib.ks_predicate.restype, lib.ks_predicate.argtypes = C.c_int, [C.c_int] * 8
@@ -91,7 +117,9 @@ def load():
     lib.ks_pack.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p]
     lib.ks_attn_plan.restype, lib.ks_attn_plan.argtypes = C.c_int, [C.c_int] * 5
     for name, T in (("ks_conv3x3", KsConv3), ("ks_conv_down", KsConvDown), ("ks_convt_up", KsConvTUp), ("ks_attn_direct", KsAttn),
-                    ("ks_attn_q64", KsAttn), ("ks_dit_rowchain", KsRowChain)):
+                    ("ks_attn_q64", KsAttn), ("ks_dit_rowchain", KsRowChain), ("ks_linattn_kvctx", KsLinKvCtx),
+                    ("ks_linattn_merge", KsLinMerge), ("ks_linattn_out2", KsLinOut2), ("ks_linattn_ctx", KsLinCtx),
+                    ("ks_linattn_combine", KsLinCombine)):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = C.c_int, [C.POINTER(T), C.c_void_p, C.c_char_p, C.c_int]
     lib.ks_conv3x3_strip_form.restype, lib.ks_conv3x3_strip_form.argtypes = C.c_int, [C.POINTER(KsConv3)]
@@ -132,15 +160,17 @@ def _need(t, nbytes, name):
 
 
 def pack(kind, w_kn, prec):
-    """The library's packing of a device fp32 [K][N] matrix: kind "nk" (16-bit [N][K]) or "frag" (MFMA fragment order).
-    Returns (uint16 pack as an int16 tensor, lo_off): the split-weight mode's lo pack sits lo_off elements behind the hi pack."""
-    K, N = w_kn.shape
+    """The library's packing of a device fp32 matrix: kind "nk" ([K][N] -> 16-bit [N][K]), "frag" ([K][N] -> MFMA fragment order),
+    "frag_nk" (a [N][K] source -> the same fragment order: Wq of the linear attention's tail) or "cast" (the row-major 16-bit cast: Wkv
+    of its context pass).  Returns (uint16 pack as an int16 tensor, lo_off): the split-weight mode's lo pack sits lo_off elements behind
+    the hi pack, as dex_api.hip's pack3 lays it out."""
+    K, N = w_kn.shape if kind != "frag_nk" else w_kn.shape[::-1]
     assert w_kn.is_cuda and w_kn.dtype == torch.float32 and w_kn.is_contiguous()
     split = prec == "fp16x2"
     lo_off = K * N if split else 0
     dst = torch.zeros(K * N * (2 if split else 1), dtype=torch.int16, device=w_kn.device)
     scratch = torch.zeros(K * N, dtype=torch.float32, device=w_kn.device) if split else None
-    _check(load().ks_pack({"nk": 0, "frag": 1}[kind], w_kn.data_ptr(), dst.data_ptr(), scratch.data_ptr() if split else None,
+    _check(load().ks_pack({"nk": 0, "frag": 1, "frag_nk": 2, "cast": 3}[kind], w_kn.data_ptr(), dst.data_ptr(), scratch.data_ptr() if split else None,
                           K, N, lo_off, PREC[prec], _stream()), f"pack {kind}")
     torch.cuda.current_stream().synchronize()         # (scratch is released on return)
     return dst, lo_off
@@ -318,3 +348,114 @@ def dit_rowchain(prec, t, *, B, N, Npad, ksplit=0, o_sstride=0, qkv_only=False, 
     form = C.create_string_buffer(128)
     _check(load().ks_dit_rowchain(C.byref(d), _stream(), form, 128), "dit_rowchain")
     return form.value.decode()
+
+
+def _fill(d, entry, t, sizes, dtypes=None):
+    """Descriptor pointers from the tensors t, each checked against the extent in sizes (bytes) and, where given, its dtype."""
+    for name in t:
+        if name not in sizes:
+            raise ShimError(f"{entry}: unknown tensor {name}")
+    for name, nbytes in sizes.items():
+        setattr(d, name, _need(t.get(name), nbytes, name))
+        want = (dtypes or {}).get(name)
+        if want is not None and t.get(name) is not None and t[name].dtype not in (want if isinstance(want, tuple) else (want,)):
+            raise ShimError(f"{entry}: {name} is {t[name].dtype}, not {want}")
+
+
+def _run(entry, d):
+    form = C.create_string_buffer(128)
+    _check(getattr(load(), entry)(C.byref(d), _stream(), form, 128), entry)
+    return form.value.decode()
+
+
+def linattn_kvctx(prec, t, *, npix, C_, B, nsub, nblk, ldx=0, x_coff=0, xb=None, headwaves=False, rows=False, W=0, mask_ws=0,
+                  mask_bstride=0, ldres=0, resb=None, res_under_mask=False, h2_bf16=False, res_lp=False, xout_lp=False, wkv_lo_off=0):
+    """One launch_linattn_kvctx (LinKvCtxP, csrc/kernels.h).  t: X fp32 rows of ldx floats (non-PRO), or H2 / gn_stats / gamma / beta /
+    mask / Xout and optionally res (the PRO form; X is not read); Wkv 16-bit [256][C] (the split mode's lo image wkv_lo_off elements
+    behind); part_m / part_s [B][4][nblk][32], part_c [B][4][nblk][32][32].  Returns the instantiation, e.g.
+    "linattn_kvctx_hw_kernel C=64 PRO=1 FL=5 ROWS=1"."""
+    if min(npix, C_, B, nsub, nblk) <= 0 or min(ldx, x_coff, W, mask_ws, mask_bstride, ldres, wkv_lo_off) < 0:
+        raise ShimError("linattn_kvctx: negative or empty extent")
+    xb = npix * ldx if xb is None else xb
+    resb = (npix * ldres if t.get("res") is not None else 0) if resb is None else resb
+    split = prec == "fp16x2"
+    f32, lp = torch.float32, LP_DTYPE[prec]
+    sizes = {"X": ((B - 1) * xb + npix * ldx) * 4, "Wkv": ((wkv_lo_off if split else 0) + 256 * C_) * 2,
+             "H2": B * npix * C_ * (2 if h2_bf16 else 4), "gn_stats": B * 8 * GN_SLOTS * 2 * 8, "gamma": C_ * 4, "beta": C_ * 4,
+             "res": ((B - 1) * resb + npix * ldres) * (2 if res_lp else 4),
+             "mask": ((B - 1) * mask_bstride + (max(W, 1) - 1) * mask_ws + 1) * 4,
+             "part_m": B * 4 * nblk * 32 * 4, "part_s": B * 4 * nblk * 32 * 4, "part_c": B * 4 * nblk * 1024 * 4,
+             "Xout": B * npix * C_ * (2 if xout_lp else 4)}
+    d = KsLinKvCtx()
+    _fill(d, "linattn_kvctx", t, sizes, {"X": f32, "H2": lp if h2_bf16 else f32, "res": lp if res_lp else f32, "mask": f32, "gamma": f32,
+                                         "beta": f32, "gn_stats": torch.int64, "part_m": f32, "part_s": f32, "part_c": f32,
+                                         "Xout": lp if xout_lp else f32, "Wkv": (torch.int16, lp)})
+    d.xb, d.resb, d.mask_bstride, d.wkv_lo_off = xb, resb, mask_bstride, wkv_lo_off
+    d.precision, d.npix, d.C, d.B, d.ldx, d.x_coff, d.nsub, d.nblk = PREC[prec], npix, C_, B, ldx, x_coff, nsub, nblk
+    d.headwaves, d.rows, d.ldres, d.res_under_mask, d.mask_ws, d.W = int(headwaves), int(rows), ldres, int(res_under_mask), mask_ws, W
+    d.h2_bf16, d.res_lp, d.xout_lp, d.reserved = int(h2_bf16), int(res_lp), int(xout_lp), 0
+    return _run("ks_linattn_kvctx", d)
+
+
+def linattn_merge(prec, t, *, nblk, C_, B):
+    """One launch_linattn_merge.  t: part_m / part_s / part_c as the context pass writes them, Wout fp32 [C][128], g fp32 [1], W2 16-bit
+    [B][C / 32][8][64][8] (written).  Returns "linattn_merge_kernel merge_fold<8 | 16 | 24>"."""
+    if min(nblk, C_, B) <= 0:
+        raise ShimError("linattn_merge: negative or empty extent")
+    f32 = torch.float32
+    sizes = {"part_m": B * 4 * nblk * 32 * 4, "part_s": B * 4 * nblk * 32 * 4, "part_c": B * 4 * nblk * 1024 * 4, "Wout": C_ * 128 * 4,
+             "g": 4, "W2": B * C_ * 128 * 2}
+    d = KsLinMerge()
+    _fill(d, "linattn_merge", t, sizes, {"part_m": f32, "part_s": f32, "part_c": f32, "Wout": f32, "g": f32})
+    d.precision, d.nblk, d.C, d.B = PREC[prec], nblk, C_, B
+    return _run("ks_linattn_merge", d)
+
+
+def linattn_out2(prec, t, *, npix, C_, B, ldx, x_coff=0, xb=None, ldy, y_coff=0, yb=None, ldy2=0, y2_coff=0, y2b=None, x_lp=False,
+                 y_lp=False, hw=False, rows=False, wq_lo_off=0):
+    """One launch_linattn_out2.  t: X (fp32, or the mode's 16-bit type when x_lp), Wq from pack("frag_nk", ..), W2 in the merge kernel's
+    layout, bias fp32 [C] (g * b_out), Y (fp32, 16-bit when y_lp) and optionally Y2 (16-bit).  Returns the form: "linattn_out2_direct_kernel
+    C=..", "linattn_out2_hw_kernel C=.. rows=..", or "linattn_out2_kernel C=.. (throughput)"."""
+    if min(npix, C_, B, ldx, ldy) <= 0 or min(x_coff, y_coff, ldy2, y2_coff, wq_lo_off) < 0:
+        raise ShimError("linattn_out2: negative or empty extent")
+    xb = npix * ldx if xb is None else xb
+    yb = npix * ldy if yb is None else yb
+    y2b = (npix * ldy2 if t.get("Y2") is not None else 0) if y2b is None else y2b
+    split = prec == "fp16x2"
+    f32, lp = torch.float32, LP_DTYPE[prec]
+    sizes = {"X": ((B - 1) * xb + npix * ldx) * (2 if x_lp else 4), "Wq": ((wq_lo_off if split else 0) + 128 * C_) * 2, "W2": B * C_ * 128 * 2,
+             "bias": C_ * 4, "Y": ((B - 1) * yb + npix * ldy) * (2 if y_lp else 4), "Y2": ((B - 1) * y2b + npix * ldy2) * 2}
+    d = KsLinOut2()
+    _fill(d, "linattn_out2", t, sizes, {"X": lp if x_lp else f32, "bias": f32})
+    d.xb, d.yb, d.y2b, d.wq_lo_off = xb, yb, y2b, wq_lo_off
+    d.precision, d.npix, d.C, d.B, d.ldx, d.x_coff, d.ldy, d.y_coff = PREC[prec], npix, C_, B, ldx, x_coff, ldy, y_coff
+    d.ldy2, d.y2_coff, d.x_lp, d.y_lp, d.hw, d.rows = ldy2, y2_coff, int(x_lp), int(y_lp), int(hw), int(rows)
+    return _run("ks_linattn_out2", d)
+
+
+def linattn_ctx(t, *, n, B, ld=384, bstride=None, chunk=512, nchunks=None, heads=4):
+    """One launch_linattn_ctx (fp32 mode).  t: qkv fp32 rows of ld floats (q | k | v), part_m / part_s / part_c (written)."""
+    if min(n, B, ld, chunk, heads) <= 0:
+        raise ShimError("linattn_ctx: negative or empty extent")
+    nchunks = (n + chunk - 1) // chunk if nchunks is None else nchunks
+    bstride = n * ld if bstride is None else bstride
+    f32 = torch.float32
+    sizes = {"qkv": ((B - 1) * bstride + n * ld) * 4, "part_m": B * heads * nchunks * 32 * 4, "part_s": B * heads * nchunks * 32 * 4,
+             "part_c": B * heads * nchunks * 1024 * 4}
+    d = KsLinCtx()
+    _fill(d, "linattn_ctx", t, sizes, {k: f32 for k in sizes})
+    d.bstride, d.ld, d.n, d.heads, d.chunk, d.nchunks, d.B = bstride, ld, n, heads, chunk, nchunks, B
+    return _run("ks_linattn_ctx", d)
+
+
+def linattn_combine(t, *, nchunks, C_, B, heads=4):
+    """One launch_linattn_combine (fp32 mode).  t: the partials, Wout fp32 [C][128], g fp32 [1], Weff fp32 [B][128][C] (written)."""
+    if min(nchunks, C_, B, heads) <= 0:
+        raise ShimError("linattn_combine: negative or empty extent")
+    f32 = torch.float32
+    sizes = {"part_m": B * heads * nchunks * 32 * 4, "part_s": B * heads * nchunks * 32 * 4, "part_c": B * heads * nchunks * 1024 * 4,
+             "Wout": C_ * heads * 32 * 4, "g": 4, "Weff": B * heads * 32 * C_ * 4}
+    d = KsLinCombine()
+    _fill(d, "linattn_combine", t, sizes, {k: f32 for k in sizes})
+    d.nchunks, d.heads, d.C, d.B = nchunks, heads, C_, B
+    return _run("ks_linattn_combine", d)

@@ -1,5 +1,5 @@
 // tests/kshim/kshim.hip — test-only launch shim: ONE launch of the reduced-precision convolution kernels, of the fragment-operand
-// softmax attention kernels and of the fused DiT row chain of libdexamd.so from a flat descriptor (tests/kshim/__init__.py mirrors the structs with ctypes).  Host
+// softmax attention kernels, of the fused DiT row chain and of the linear attention (fused and fp32) of libdexamd.so from a flat descriptor (tests/kshim/__init__.py mirrors the structs with ctypes).  Host
 // code only, no kernels: every entry point fills the library's parameter struct by member name, sets the split-weight flag as
 // dex_api.hip does for a call, runs the library's own launcher on the given stream and returns the instantiation it picked
 // (dex::g_last_symbol; the attention launchers leave none: their entries return the kernel and the plan, recomputed here).
@@ -74,9 +74,36 @@ struct KsRowChain {
     unsigned epoch; float qscale;
 };
 
+// mirror LinKvCtxP, LinMergeP, LinOut2P, LinAttnCtxP and LinAttnCombineP (csrc/kernels.h).  Everything the sampler derives from its
+// knobs (nsub, nblk, headwaves, rows, hw and the storage flags) is a member; only DEX_OUT2_MIN stays a knob (the launcher reads it).
+struct KsLinKvCtx {
+    const void *X, *Wkv, *H2, *gn_stats, *gamma, *beta, *res, *mask; void *part_m, *part_s, *part_c, *Xout;
+    long long xb, resb, mask_bstride, wkv_lo_off;
+    int precision, npix, C, B, ldx, x_coff, nsub, nblk, headwaves, rows, ldres, res_under_mask, mask_ws, W, h2_bf16, res_lp, xout_lp, reserved;
+};
+struct KsLinMerge { const void *part_m, *part_s, *part_c, *Wout, *g; void* W2; int precision, nblk, C, B; };
+struct KsLinOut2 {
+    const void *X, *Wq, *W2, *bias; void *Y, *Y2;
+    long long xb, yb, y2b, wq_lo_off;
+    int precision, npix, C, B, ldx, x_coff, ldy, y_coff, ldy2, y2_coff, x_lp, y_lp, hw, rows;
+};
+struct KsLinCtx { const void* qkv; void *part_m, *part_s, *part_c; long long bstride; int ld, n, heads, chunk, nchunks, B; };
+struct KsLinCombine { const void *part_m, *part_s, *part_c, *Wout, *g; void* Weff; int nchunks, heads, C, B; };
+
 int ks_struct_bytes(int which) {
-    return which == 0 ? (int)sizeof(KsConv3) : which == 1 ? (int)sizeof(KsConvDown) : which == 2 ? (int)sizeof(KsConvTUp)
-         : which == 3 ? (int)sizeof(KsAttn) : (int)sizeof(KsRowChain);
+    switch (which) {
+        case 0: return (int)sizeof(KsConv3);
+        case 1: return (int)sizeof(KsConvDown);
+        case 2: return (int)sizeof(KsConvTUp);
+        case 3: return (int)sizeof(KsAttn);
+        case 4: return (int)sizeof(KsRowChain);
+        case 5: return (int)sizeof(KsLinKvCtx);
+        case 6: return (int)sizeof(KsLinMerge);
+        case 7: return (int)sizeof(KsLinOut2);
+        case 8: return (int)sizeof(KsLinCtx);
+        case 9: return (int)sizeof(KsLinCombine);
+    }
+    return KS_E_SHAPE;
 }
 
 // ---- shape predicates of the library, for the mode `precision` -------------------------------------------------------------
@@ -108,20 +135,25 @@ int ks_predicate(int which, int precision, int a, int b, int c, int d, int e, in
 }
 
 // ---- weight packing by the library's own code ------------------------------------------------------------------------------
-// kind: 0 launch_pack_lp_nk (fp32 [K][N] -> 16-bit [N][K])   1 launch_pack_lp_frag (fp32 [K][N] -> MFMA fragment order).
+// kind: 0 launch_pack_lp_nk (fp32 [K][N] -> 16-bit [N][K])   1 launch_pack_lp_frag (fp32 [K][N] -> MFMA fragment order)
+//       2 launch_pack_lp_frag_nk (fp32 [N][K] -> the same fragment order: Wq of the linear attention's tail)
+//       3 launch_f32_to_lp (the row-major 16-bit cast of K * N elements: Wkv of its context pass).
 // The split-weight mode packs the fp16 rounding of the weight, then what that rounding lost (through `scratch`, K*N floats), in the
 // same layout `lo_off` elements behind - dex_api.hip's pack3.  lo_off is ignored in the other modes.
 int ks_pack(int kind, const void* src, void* dst, void* scratch, int K, int N, long long lo_off, int precision, void* stream) {
     if (!lp_prec(precision)) return KS_E_PREC;
     if (!src || !dst || (precision == PREC_FP16X2 && !scratch)) return KS_E_NULL;
-    if (K <= 0 || N <= 0 || (kind != 0 && kind != 1)) return KS_E_SHAPE;
-    if (kind == 1 && (K % 16 != 0 || N % 32 != 0)) return KS_E_SHAPE;
+    if (K <= 0 || N <= 0 || kind < 0 || kind > 3) return KS_E_SHAPE;
+    if ((kind == 1 || kind == 2) && (K % 16 != 0 || N % 32 != 0)) return KS_E_SHAPE;
     if (precision == PREC_FP16X2 && lo_off < (long long)K * N) return KS_E_STRIDE;
     hipStream_t st = (hipStream_t)stream;
     const float* s = (const float*)src;
     unsigned short* d = (unsigned short*)dst;
     auto pack = [&](const float* from, unsigned short* to, int prec) {
-        if (kind == 0) launch_pack_lp_nk(from, to, K, N, prec, st); else launch_pack_lp_frag(from, to, K, N, prec, st);
+        if (kind == 0) launch_pack_lp_nk(from, to, K, N, prec, st);
+        else if (kind == 1) launch_pack_lp_frag(from, to, K, N, prec, st);
+        else if (kind == 2) launch_pack_lp_frag_nk(from, to, K, N, prec, st);
+        else launch_f32_to_lp(from, to, (long)K * N, prec, st);
     };
     if (precision != PREC_FP16X2) { pack(s, d, precision); return KS_OK; }
     pack(s, d, PREC_FP16);
@@ -421,6 +453,134 @@ int ks_dit_rowchain(const KsRowChain* d, void* stream, char* form, int form_len)
     g_last_symbol = nullptr;
     launch_dit_rowchain(p, d->precision, (hipStream_t)stream);
     put_symbol(form, form_len);
+    return KS_OK;
+}
+
+// ---- linear attention of the U-Net stages (linattn_fused.hip; linattn.hip in the fp32 mode) --------------------------------------
+// One launch each.  form: g_last_form, the whole instantiation as the launcher names it (the fp32 kernels have one form each).
+static void put_form(char* form, int n) {
+    if (!form || n <= 0) return;
+    const char* s = g_last_form ? g_last_form : "";
+    strncpy(form, s, (size_t)n - 1);
+    form[n - 1] = 0;
+}
+static int lin_common(int precision, int C, int B) {
+    if (!lp_prec(precision)) return KS_E_PREC;
+    if (C != 64 && C != 128) return KS_E_SHAPE;
+    if (B <= 0 || B > 65535) return KS_E_SHAPE;
+    if (!linattn_fused_supported(C)) return KS_E_UNSUPPORTED;
+    return KS_OK;
+}
+
+int ks_linattn_kvctx(const KsLinKvCtx* d, void* stream, char* form, int form_len) {
+    if (!d) return KS_E_NULL;
+    if (!lp_prec(d->precision)) return KS_E_PREC;
+    WsplitScope ws(d->precision);
+    const int rc = lin_common(d->precision, d->C, d->B);
+    if (rc != KS_OK) return rc;
+    const int C = d->C;
+    if (d->npix <= 0 || d->nsub < 1 || d->nsub > 8) return KS_E_SHAPE;
+    if ((long long)d->nblk != ((long long)d->npix + 128LL * d->nsub - 1) / (128LL * d->nsub)) return KS_E_SHAPE;
+    if (!d->Wkv || !d->part_m || !d->part_s || !d->part_c) return KS_E_NULL;
+    if (d->precision == PREC_FP16X2 && (d->wkv_lo_off < 256LL * C || d->wkv_lo_off % 8 != 0)) return KS_E_STRIDE;
+    if (d->headwaves && d->precision == PREC_FP16X2 && C == 128) return KS_E_UNSUPPORTED;      // (two weight images + the x image: LDS)
+    if (d->rows && !d->headwaves) return KS_E_FORM;
+    const bool pro = d->H2 != nullptr;
+    if (pro) {
+        if (!d->gn_stats || !d->gamma || !d->beta || !d->mask || !d->Xout) return KS_E_NULL;
+        if (d->W <= 0 || d->npix % d->W != 0 || d->mask_ws < 1 || d->mask_bstride < 0) return KS_E_SHAPE;
+        if (d->res) {
+            if (d->ldres < C || d->ldres % (d->res_lp ? 8 : 4) != 0 || d->resb < (long long)d->npix * d->ldres) return KS_E_STRIDE;
+        } else if (d->ldres || d->resb) return KS_E_FORM;
+    } else {
+        if (!d->X) return KS_E_NULL;
+        if (d->gn_stats || d->gamma || d->beta || d->res || d->mask || d->Xout) return KS_E_FORM;
+        if (d->h2_bf16 || d->res_lp || d->xout_lp || d->res_under_mask || d->W || d->ldres) return KS_E_FORM;
+        if (d->x_coff < 0 || d->x_coff % 4 != 0 || d->ldx % 4 != 0 || d->ldx < d->x_coff + C) return KS_E_STRIDE;
+        if (d->xb < (long long)d->npix * d->ldx) return KS_E_STRIDE;
+    }
+    LinKvCtxP p{};
+    p.X = (const float*)d->X; p.ldx = d->ldx; p.x_coff = d->x_coff; p.xb = (long)d->xb; p.npix = d->npix; p.C = C; p.Wkv = d->Wkv;
+    p.nsub = d->nsub; p.nblk = d->nblk; p.part_m = (float*)d->part_m; p.part_s = (float*)d->part_s; p.part_c = (float*)d->part_c; p.B = d->B;
+    p.H2 = (const float*)d->H2; p.gn_stats = (const gnfix_t*)d->gn_stats; p.gamma = (const float*)d->gamma; p.beta = (const float*)d->beta;
+    p.res = (const float*)d->res; p.ldres = d->ldres; p.resb = (long)d->resb; p.res_under_mask = d->res_under_mask ? 1 : 0;
+    p.mask = (const float*)d->mask; p.mask_ws = d->mask_ws; p.mask_bstride = (long)d->mask_bstride; p.W = d->W; p.Xout = (float*)d->Xout;
+    p.h2_bf16 = d->h2_bf16 ? 1 : 0; p.res_lp = d->res_lp ? 1 : 0; p.xout_lp = d->xout_lp ? 1 : 0; p.wkv_lo_off = (long)d->wkv_lo_off;
+    p.headwaves = d->headwaves ? 1 : 0; p.rows = d->rows ? 1 : 0; p.dbg = nullptr;
+    g_last_form = nullptr;
+    launch_linattn_kvctx(p, d->precision, (hipStream_t)stream);
+    put_form(form, form_len);
+    return KS_OK;
+}
+
+int ks_linattn_merge(const KsLinMerge* d, void* stream, char* form, int form_len) {
+    if (!d) return KS_E_NULL;
+    if (!lp_prec(d->precision)) return KS_E_PREC;
+    WsplitScope ws(d->precision);
+    const int rc = lin_common(d->precision, d->C, d->B);
+    if (rc != KS_OK) return rc;
+    if (d->nblk < 1) return KS_E_SHAPE;
+    if (!d->part_m || !d->part_s || !d->part_c || !d->Wout || !d->g || !d->W2) return KS_E_NULL;
+    LinMergeP p{(const float*)d->part_m, (const float*)d->part_s, (const float*)d->part_c, d->nblk, (const float*)d->Wout,
+                (const float*)d->g, d->C, d->W2, d->B};
+    launch_linattn_merge(p, d->precision, (hipStream_t)stream);
+    if (form && form_len > 0) snprintf(form, (size_t)form_len, "linattn_merge_kernel merge_fold<%d>", (d->nblk + 7) / 8 <= 8 ? 8 : (d->nblk + 7) / 8 <= 16 ? 16 : 24);
+    return KS_OK;
+}
+
+int ks_linattn_out2(const KsLinOut2* d, void* stream, char* form, int form_len) {
+    if (!d) return KS_E_NULL;
+    if (!lp_prec(d->precision)) return KS_E_PREC;
+    WsplitScope ws(d->precision);
+    const int rc = lin_common(d->precision, d->C, d->B);
+    if (rc != KS_OK) return rc;
+    const int C = d->C;
+    if (d->npix <= 0) return KS_E_SHAPE;
+    if (!d->X || !d->Wq || !d->W2 || !d->bias || !d->Y) return KS_E_NULL;
+    const bool lp_io = d->x_lp || d->y_lp || d->Y2;
+    if (d->hw && lp_io) return KS_E_FORM;                                         // the wave-split form: fp32 X and Y only
+    if (d->rows && !d->hw) return KS_E_FORM;
+    if (lp_io && !linattn_out2_lp_out_supported(d->npix, d->B)) return KS_E_FORM;  // 16-bit I/O: the throughput form only
+    const int xa = d->x_lp ? 8 : 4;
+    if (d->x_coff < 0 || d->x_coff % xa != 0 || d->ldx % xa != 0 || d->ldx < d->x_coff + C || d->xb < (long long)d->npix * d->ldx) return KS_E_STRIDE;
+    if (d->y_coff < 0 || d->y_coff % 4 != 0 || d->ldy % 4 != 0 || d->ldy < d->y_coff + C || d->yb < (long long)d->npix * d->ldy) return KS_E_STRIDE;
+    if (d->Y2) {
+        if (d->y2_coff < 0 || d->y2_coff % 4 != 0 || d->ldy2 % 4 != 0 || d->ldy2 < d->y2_coff + C || d->y2b < (long long)d->npix * d->ldy2) return KS_E_STRIDE;
+    } else if (d->ldy2 || d->y2_coff || d->y2b) return KS_E_FORM;
+    if (d->precision == PREC_FP16X2 && (d->wq_lo_off < 128LL * C || d->wq_lo_off % 8 != 0)) return KS_E_STRIDE;
+    LinOut2P p{};
+    p.X = (const float*)d->X; p.ldx = d->ldx; p.x_coff = d->x_coff; p.xb = (long)d->xb; p.npix = d->npix; p.C = C; p.Wq = d->Wq; p.W2 = d->W2;
+    p.bias = (const float*)d->bias; p.Y = (float*)d->Y; p.ldy = d->ldy; p.y_coff = d->y_coff; p.yb = (long)d->yb; p.B = d->B;
+    p.y_lp = d->y_lp ? 1 : 0; p.Y2 = d->Y2; p.ldy2 = d->ldy2; p.y2_coff = d->y2_coff; p.y2b = (long)d->y2b; p.x_lp = d->x_lp ? 1 : 0;
+    p.wq_lo_off = (long)d->wq_lo_off; p.hw = d->hw ? 1 : 0; p.rows = d->rows ? 1 : 0; p.dbg = nullptr;
+    g_last_form = nullptr;
+    launch_linattn_out2(p, d->precision, (hipStream_t)stream);
+    put_form(form, form_len);
+    return KS_OK;
+}
+
+// the fp32 mode's pair (linattn.hip): chunks of LA_CHUNK = 512 positions (dex_api.hip), four heads of 32
+int ks_linattn_ctx(const KsLinCtx* d, void* stream, char* form, int form_len) {
+    if (!d) return KS_E_NULL;
+    if (!d->qkv || !d->part_m || !d->part_s || !d->part_c) return KS_E_NULL;
+    if (d->n <= 0 || d->B <= 0 || d->B > 65535 || d->heads != 4 || d->chunk != 512) return KS_E_SHAPE;
+    if (d->nchunks != (d->n + d->chunk - 1) / d->chunk) return KS_E_SHAPE;
+    if (d->ld % 4 != 0 || d->ld < 3 * d->heads * 32 || d->bstride < (long long)d->n * d->ld) return KS_E_STRIDE;
+    LinAttnCtxP p{(const float*)d->qkv, d->ld, (long)d->bstride, d->n, d->heads, d->chunk, d->nchunks,
+                  (float*)d->part_m, (float*)d->part_s, (float*)d->part_c, d->B};
+    launch_linattn_ctx(p, (hipStream_t)stream);
+    if (form && form_len > 0) snprintf(form, (size_t)form_len, "linattn_ctx_kernel");
+    return KS_OK;
+}
+
+int ks_linattn_combine(const KsLinCombine* d, void* stream, char* form, int form_len) {
+    if (!d) return KS_E_NULL;
+    if (!d->part_m || !d->part_s || !d->part_c || !d->Wout || !d->g || !d->Weff) return KS_E_NULL;
+    if (d->nchunks <= 0 || d->B <= 0 || d->B > 65535 || d->heads != 4 || d->C <= 0 || d->C > 256) return KS_E_SHAPE;
+    LinAttnCombineP p{(const float*)d->part_m, (const float*)d->part_s, (const float*)d->part_c, d->nchunks, d->heads,
+                      (const float*)d->Wout, (const float*)d->g, d->C, (float*)d->Weff, d->B};
+    launch_linattn_combine(p, (hipStream_t)stream);
+    if (form && form_len > 0) snprintf(form, (size_t)form_len, "linattn_combine_kernel");
     return KS_OK;
 }
 
